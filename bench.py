@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline measurement of the MI355X hot path (BASELINE.json metric: rows/sec TableScan+JoinHash, TPC-H SF10).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, roofline of the timed steps);
+`--full` adds everything else below: the median-placement stretch, the first join without the key hint, the operator legs, cases,
+the C++ operator chain, SSB, the multi-GPU legs, the CPU baselines and the details file.  `--dump-outputs DIR` writes what the last
+timed step computed (the scan's PosLists, the join's pairs: a fixed, seeded sample of each plus exact per-chunk / per-slice sums) as
+float64 .npy files, 50 MB in all; the inputs are seeded, so two builds can be compared file by file.
 
 One step = ONE TableScan + ONE JoinHash on the same GPU, inputs and outputs resident in HBM:
   * TableScan ColumnVsValue (config 2): TPC-H SF10 lineitem `l_shipdate` (59 986 052 rows, 916 chunks of 65 535, DictionarySegment<int32>
@@ -58,9 +64,19 @@ def parse_args(argv=None):
                     help="A/B: one of the library's named switches (hyrise_amd/abi.py _SWITCHES, e.g. HY_JOIN_NO_HINT=1) for the whole run")
     ap.add_argument("--placements", type=int, default=32, help="result-buffer placements the join's output pool is calibrated over before the timed region (1 = take the first)")
     ap.add_argument("--headline-only", action="store_true", help="only the timed TableScan + JoinHash step (no legs, no CPU baselines)")
-    ap.add_argument("--details", default=os.path.join(ROOT, "bench_details.json"),
-                    help="file the full result object goes to (every leg, every case, prose); stdout gets the compact line only")
-    return ap.parse_args(argv)
+    ap.add_argument("--details", default=None,
+                    help="file the full result object goes to (every leg, every case, prose); stdout gets the compact line only "
+                         "(default with --full: bench_details.json; a plain run writes it only when named)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: median-placement step, first join without the hint, legs, cases, SSB, multi-GPU legs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, seeded samples, < 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.full and args.details is None:
+        args.details = os.path.join(ROOT, "bench_details.json")
+    return args
 
 
 def oracle_support():
@@ -1023,9 +1039,73 @@ def cpp_operator_chain(placements):
     return {"error": (proc.stdout + proc.stderr)[-400:]}
 
 
+DUMP_SAMPLE_ROWS = 1 << 20      # RowIDs / pairs of a PosList that --dump-outputs writes when there are more (a fixed, seeded sample)
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def sample_rows(total, seed):
+    """Ascending indices of a fixed sample of `total` rows, drawn from `seed` (every row when there are few enough)."""
+    import numpy as np
+    if total <= DUMP_SAMPLE_ROWS:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(total, DUMP_SAMPLE_ROWS, replace=False))
+
+
+def dump_outputs(directory, lib, host_column, matches, offsets, counts, join_result, slice_offsets):
+    """--dump-outputs: the results of the last timed step as a caller of hy_table_scan / hy_join_hash receives them, float64 .npy files.
+      scan_chunk_counts [n_chunks]             RowIDs per chunk
+      scan_chunk_offset_sums [n_chunks]        sum of the chunk offsets of each chunk's PosList (exact: every RowID counts)
+      scan_pos_list_sample [<= 2^20, 2]        (chunk_id, chunk_offset) at sample_rows(matches, 1) of the chunks' PosLists back to back
+      join_slice_offsets [n_slices + 1]        boundaries of the per-probe-slice PosLists
+      join_slice_sums [n_slices, 4]            per slice: sums of left chunk_id, left chunk_offset, right chunk_id, right chunk_offset
+      join_pairs_sample [<= 2^20, 4]           (left chunk_id, left chunk_offset, right chunk_id, right chunk_offset) at sample_rows(pairs, 2)
+    A chunk whose count is its size is an ALL_MATCH chunk: its PosList is every row, whether the scan wrote it or elided it."""
+    import numpy as np
+    from hyrise_amd import abi
+    os.makedirs(directory, exist_ok=True)
+    out = {}
+    # TableScan: chunk c's PosList is matches[offsets[c] : offsets[c] + counts[c]] (HY_SCAN_CHUNK_REGIONS)
+    offsets, counts, rows = offsets.cpu().numpy().astype(np.int64), counts.cpu().numpy().astype(np.int64), matches.cpu().numpy()
+    parts, offset_sums = [], np.zeros(len(counts), dtype=np.float64)
+    for c, segment in enumerate(host_column.segments):
+        size = segment.size
+        if counts[c] == size:
+            part = np.stack((np.full(size, c, dtype=np.int64), np.arange(size, dtype=np.int64)), 1)
+        else:
+            part = rows[offsets[c]:offsets[c] + counts[c]].astype(np.int64)
+        offset_sums[c] = part[:, 1].sum()
+        parts.append(part)
+    pos_list = np.concatenate(parts)
+    out["scan_chunk_counts"] = counts.astype(np.float64)
+    out["scan_chunk_offset_sums"] = offset_sums
+    out["scan_pos_list_sample"] = pos_list[sample_rows(len(pos_list), 1)].astype(np.float64)
+    del rows, parts, pos_list
+    # JoinHash: n_pairs (left RowID, right RowID) pairs in the library's pool, cut into n_slices PosLists by slice_offsets
+    n_pairs, n_slices = int(join_result.n_pairs), int(join_result.n_slices)
+    pairs = np.empty((n_pairs, 4), dtype=np.uint32)
+    for column, pointer in ((0, join_result.left_pos), (2, join_result.right_pos)):
+        side = np.empty((n_pairs, 2), dtype=np.uint32)
+        abi.check(lib.hy_memcpy_d2h(side.ctypes.data, pointer, side.nbytes))
+        pairs[:, column:column + 2] = side
+    del side
+    bounds = slice_offsets[:n_slices + 1].cpu().numpy().astype(np.int64)
+    sums = np.zeros((n_slices, 4), dtype=np.float64)
+    for column in range(4):
+        running = np.concatenate(([0], np.cumsum(pairs[:, column], dtype=np.int64)))
+        sums[:, column] = running[bounds[1:]] - running[bounds[:-1]]
+    out["join_slice_offsets"] = bounds.astype(np.float64)
+    out["join_slice_sums"] = sums
+    out["join_pairs_sample"] = pairs[sample_rows(n_pairs, 2)].astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    for name, array in out.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
+
+
 def main():
     args = parse_args()
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_cases = args.no_join = args.no_aggregate = args.no_multi = args.no_ssb = True
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1127,10 +1207,12 @@ def main():
     run_join.finish()   # (the last join's pair count and fit flag: device memory until now)
     kinds = kernel_times(lib)
     abi.check(lib.hy_set_profiling(0))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lib, host_column, matches, offsets, counts, join_result, join_buffers[2])
     # The same timed region with the join's PosLists in the MEDIAN candidate of the calibration -- what a pool that is not calibrated gets on
     # average (`ms_per_step` is the calibrated placement, this is the honest second number)
     elapsed_median = None
-    if run_join.use_median:
+    if args.full and run_join.use_median:
         run_join.use_median()
         for _ in range(max(2, args.warmup)):
             step()
@@ -1146,9 +1228,10 @@ def main():
         run_join.use_best()
 
     n_matches = int(counts.sum().item())
-    expected = int((days < tpch.DAY_1995_01_01).sum())
-    if n_matches != expected:
-        raise SystemExit(f"rank {rank}: scan produced {n_matches} matches, numpy says {expected}")
+    if args.full:
+        expected = int((days < tpch.DAY_1995_01_01).sum())
+        if n_matches != expected:
+            raise SystemExit(f"rank {rank}: scan produced {n_matches} matches, numpy says {expected}")
     n_pairs = int(join_result.n_pairs)
     if n_pairs != n_lineitems:
         raise SystemExit(f"rank {rank}: join produced {n_pairs} pairs, every one of the {n_lineitems} lineitems has exactly one order")
@@ -1178,7 +1261,7 @@ def main():
 
     # the join WITHOUT the build column's key hint (what the first join over a freshly loaded column costs: two passes over the build keys)
     first_join_no_hint_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         with abi.option(abi.OPT_JOIN_HINT, 0):
             times = []
             for _ in range(5):
@@ -1192,7 +1275,7 @@ def main():
 
     # ---- the operators alone, the other configs (N = 1) ---------------------------------------------------------------
     scan_info = None
-    if single:
+    if single and args.full:
         dt_scan, scan_kernel_ms = timed_kernel(lib, torch, scan_step, args.steps, PROFILE_EVERY, kind="scan")
         scan_info = {"workload": "configs[1] alone: TableScan ColumnVsValue, SF10 lineitem l_shipdate < 1995-01-01, three column copies in rotation",
                      "rows_per_s": rows / dt_scan, "ms_per_scan": dt_scan * 1e3, "matches": n_matches, "algorithmic_bytes": scan_bytes,
@@ -1297,7 +1380,8 @@ def main():
             line.setdefault("join", {})["first_join_no_hint_ms"] = first_join_no_hint_ms
         # the reference's benchmark runner writes its detailed results to a file (-o) and prints a summary
         # (src/benchmarklib/benchmark_runner.cpp:443-531): the full object goes to --details, the LAST stdout line is its summary
-        write_details(line, args.details)
+        if args.details:
+            write_details(line, args.details)
         print(json.dumps(compact_line(line, args.details), separators=(",", ":")))
     if dist is not None:
         dist.barrier()

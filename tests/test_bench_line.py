@@ -109,3 +109,65 @@ def test_line_carries_median_placement_and_the_cpp_operator_chain():
     parsed = check(bench.compact_line(line))
     assert parsed["ms_per_step_median_placement"] == 0.4321
     assert parsed["legs"]["cpp_operator_chain_ms"]["join_orders_lineitem_device_resident"] == 0.64 and "hy_result_pool_calibrate" in parsed["config"]["workload"]
+
+
+def test_plain_run_and_full_run_options():
+    """A plain run times the headline step only; `--full` adds the legs, baselines and the details file."""
+    import pytest
+    import bench
+    plain, full = bench.parse_args(["--steps", "7", "--warmup", "2"]), bench.parse_args(["--full"])
+    assert (plain.steps, plain.warmup, plain.full, plain.details, plain.dump_outputs) == (7, 2, False, None, None)
+    assert full.full and full.details == os.path.join(ROOT, "bench_details.json")
+    assert bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path, monkeypatch):
+    """--dump-outputs: the scan's PosLists (an elided ALL_MATCH chunk is every row of it) and the join's pairs and slices, float64,
+    a fixed sample of each plus exact per-chunk / per-slice sums."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    import bench
+    from hyrise_amd import abi, tpch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ROWS", 5000)
+    days, column = tpch.shipdate_column(300_000, seed=42)
+    sizes = [s.size for s in column.segments]
+    starts = np.concatenate(([0], np.cumsum(sizes)))
+    matches = np.full((column.rows, 2), -7, dtype=np.int32)
+    counts = np.zeros(column.n_chunks, dtype=np.int32)
+    want = []
+    for c in range(column.n_chunks):
+        hit = np.arange(sizes[c]) if c == 2 else np.nonzero(days[starts[c]:starts[c + 1]] < tpch.DAY_1995_01_01)[0]
+        counts[c] = len(hit)
+        if c != 2:   # (chunk 2: ALL_MATCH, no RowIDs written)
+            matches[starts[c]:starts[c] + len(hit)] = np.stack((np.full(len(hit), c), hit), 1)
+        want.append(np.stack((np.full(len(hit), c), hit), 1))
+    want = np.concatenate(want)
+    offsets = np.concatenate((starts[:-1], [0])).astype(np.int64)
+    n_pairs = 70_000
+    left = np.random.default_rng(3).integers(0, 1000, (n_pairs, 2)).astype(np.uint32)
+    right = np.random.default_rng(4).integers(0, 1000, (n_pairs, 2)).astype(np.uint32)
+    slices = np.array([0, 10, 10, 40_000, n_pairs], dtype=np.int64)
+    result = abi.JoinResult()
+    result.left_pos, result.right_pos, result.n_pairs, result.n_slices = left.ctypes.data, right.ctypes.data, n_pairs, len(slices) - 1
+
+    class HostCopies:
+        @staticmethod
+        def hy_memcpy_d2h(dst, src, n):
+            C.memmove(dst, src, n)
+            return 0
+
+    bench.dump_outputs(str(tmp_path), HostCopies(), column, torch.from_numpy(matches), torch.from_numpy(offsets), torch.from_numpy(counts),
+                       result, torch.from_numpy(np.concatenate((slices, [99, 99]))))
+    got = {name[:-4]: np.load(tmp_path / name) for name in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float64 for a in got.values()) and len(got) == 6
+    assert np.array_equal(got["scan_chunk_counts"], counts)
+    assert np.array_equal(got["scan_chunk_offset_sums"], [w[:, 1].sum() for w in np.split(want, np.cumsum(counts)[:-1])])
+    assert np.array_equal(got["scan_pos_list_sample"], want[bench.sample_rows(len(want), 1)])
+    pairs = np.concatenate((left, right), 1).astype(np.int64)
+    assert np.array_equal(got["join_pairs_sample"], pairs[bench.sample_rows(n_pairs, 2)]) and len(got["join_pairs_sample"]) == 5000
+    assert np.array_equal(got["join_slice_offsets"], slices)
+    assert np.array_equal(got["join_slice_sums"], [pairs[a:b].sum(0) for a, b in zip(slices[:-1], slices[1:])])
+    assert np.array_equal(bench.sample_rows(10 ** 6, 1), bench.sample_rows(10 ** 6, 1))

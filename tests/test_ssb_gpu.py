@@ -48,7 +48,7 @@ def test_ssb_query_on_device(device, query, sql):
 def test_ssb_scale_factor_one_on_device(device):
     """Config 5 at scale factor 1 (6 000 000 lineorder rows, 92 chunks; part 200 000, customer 30 000, supplier 2 000 rows): the operator
     chain and the one-call plan on the device against the same plans on the CPU oracle (every thread) and against SQLite -- group rows,
-    sums and joined-row counts are integers: equal, not close.  (SF30 itself is checked by bench.py against the oracle on every run.)"""
+    sums and joined-row counts are integers: equal, not close.  (SF30 itself is checked by `bench.py --full` against the oracle.)"""
     import os
     from hyrise_amd import abi
     from hyrise_amd.operators import star_join_aggregate
