@@ -121,6 +121,10 @@ class EntireChunkPosList : public AbstractPosList {   // pos_lists/entire_chunk_
 // library's result-buffer pool (hy_result_pool_*), the operators below hand the device pointer to the next call (a scan's PosLists as the
 // reference column of a join, a join's as the input of an aggregate) and nothing crosses the host link; code that indexes the list gets
 // a host copy made on first use.  The block goes back to the pool when the last PosList in it dies.
+// What the release orders: on a thread of the block's device, only the work queued on THAT thread's stream (the pool records an event
+// there; the next owner's stream waits for it) -- a reader on any other stream must have finished before the last reference drops.  Every
+// operator below synchronises before it returns, which is what makes that hold.  On a thread of another device the release waits for the
+// block's whole device instead.
 struct DeviceBlock {
   explicit DeviceBlock(void* init) : ptr(init) {}
   DeviceBlock(const DeviceBlock&) = delete;
