@@ -23,7 +23,6 @@ constexpr int64_t FIXED_PART_SLICES = 0;            // one scan part per chunk
 constexpr int64_t FIXED_JOIN_IDENTITY = 1;          // a sorted build column of equally sized chunks is read in place (rank = row number)
 constexpr int64_t FIXED_JOIN_FETCH_AHEAD = 1;       // probe segments are read through SliceViews (wide loads)
 constexpr int64_t FIXED_JOIN_ORDERED_ATOMICS = 1;   // rank pairs with one returning LDS atomic each where the LDS serves lanes in order (probed once per process)
-constexpr int64_t FIXED_JOIN_STORES = 2;            // pk_emit: write-back stores for the lines runs share, nontemporal ones in between
 constexpr int64_t FIXED_JOIN_WGS_PER_CU = 0;        // persistent probe kernels: what the occupancy query says
 constexpr int64_t FIXED_JOIN_EMIT_TILE_GROUP = 64;  // pk_emit: consecutive tiles per XCD (one front of 8 x 64 tiles moves through the probe side)
 constexpr int64_t FIXED_JOIN_CLEAN_TABLES = 1;      // a hinted build's table and filter come zeroed: the join before cleared them

@@ -680,79 +680,111 @@ __device__ __forceinline__ void pk_evaluate(const PkArgs& a, const SliceView& vi
 
 // ---- pass 2 -------------------------------------------------------------------------------------------------------------------
 // LDS, in 4-byte words: staged pairs {row | partition << 13 | null partner << 21, partner's rank} (one spare slot per
-// partition, see rt_probe_emit) | pairs per (wave, partition), then the first slot of (wave, partition) | global pair index of
-// staging slot 0 per partition | wave totals of the partition scan, reserved slots.
+// partition, see rt_probe_emit) | pairs per (wave, partition), then the first slot of (wave, partition); after the staging the
+// copy-out's line table (PK_TILE / 16 lines x 2 words) in the same words | global pair index of staging slot 0 per partition | first
+// global pair index of the run per partition, then its first interior line (bits 16..) and its pairs (bits 0..15) | wave totals of
+// the partition scan, reserved slots and interior lines.
 constexpr uint32_t PK_STAGE_ROW = 0x1FFF, PK_STAGE_PARTITION_SHIFT = 13, PK_STAGE_NULL = 1u << 21;
+constexpr uint32_t PK_LINES = PK_TILE / 16;   // 128-byte output lines of 16 pairs a tile's pairs can fill
+__host__ __device__ constexpr size_t pk_wave_pairs_words(uint32_t partitions) {
+  return size_t{PK_WAVES} * partitions > 2 * size_t{PK_LINES} ? size_t{PK_WAVES} * partitions : 2 * size_t{PK_LINES};
+}
 __host__ __device__ constexpr size_t pk_emit_lds_words(uint32_t partitions) {
-  return 2 * (size_t{PK_TILE} + partitions + 2) + size_t{PK_WAVES} * partitions + 3 * size_t{partitions} + 32;
+  return 2 * (size_t{PK_TILE} + partitions + 2) + pk_wave_pairs_words(partitions) + 3 * size_t{partitions} + 32;
+}
+static_assert(PK_LINES == PK_THREADS, "the copy-out's line table is filled thread = line");
+static_assert(2 * PK_LINES <= PK_WAVES * 256, "the line table must not make 256 partitions' LDS larger");
+
+// Interior lines of a run: the 128-byte lines (16 pairs, counted on the global pair index) wholly inside [base, base + pairs).
+__device__ __forceinline__ uint32_t pk_first_line(uint32_t base) { return (base >> 4) + ((base & 15) != 0 ? 1u : 0u); }
+__device__ __forceinline__ uint32_t pk_interior_lines(uint32_t base, uint32_t pairs) {
+  const uint32_t first = pk_first_line(base), end = (base + pairs) >> 4;
+  return end > first ? end - first : 0u;
 }
 
-// STORES: 0 nontemporal | 1 write-back | 2 write-back for the two pairs that share a 128-byte line with a NEIGHBOURING tile's pairs (a
-// run's first and last line: the partial lines merge in the XCD's L2 instead of reaching HBM as two masked writes each), nontemporal
-// for the full lines in between (nothing of the 0.96 GB stays behind in the L2 for the next kernel to evict).  tools/hbm_write.hip:
-// 246 us / 187 us / 188 us for config 3's layout.  s_edge: [2][partitions] first and last line of every run.
-template <int BUILD, int STORES>
-__device__ __forceinline__ void pk_copy_out(const PkArgs& a, const u32x2_t* s_stage, const uint32_t* s_out_base, const uint32_t* s_edge, uint32_t partitions, uint32_t reserved,
-                                            uint32_t chunk, uint32_t tile_row_begin, uint32_t tid) {
+template <int BUILD>
+__device__ __forceinline__ u32x2_t pk_rank_row(const PkArgs& a, uint32_t r) {
+  if constexpr (BUILD == BUILD_IDENTITY_65535) {
+    uint32_t c = r >> 16, offset = (r & 0xFFFFu) + c;   // r = c * 65535 + (c + low): offset < 2^17
+    if (offset >= 65535u) { ++c; offset -= 65535u; }
+    if (offset >= 65535u) { ++c; offset -= 65535u; }
+    return u32x2_t{c, offset};
+  } else if constexpr (BUILD == BUILD_IDENTITY) {
+    uint32_t c = static_cast<uint32_t>(static_cast<double>(r) * a.rank.identity_inverse);
+    if (c * a.rank.identity_rows > r) --c;
+    uint32_t offset = r - c * a.rank.identity_rows;
+    if (offset >= a.rank.identity_rows) { ++c; offset -= a.rank.identity_rows; }
+    return u32x2_t{c, offset};
+  } else if constexpr (BUILD == BUILD_PACKED) {
+    const uint32_t id = a.ids32[r];
+    return u32x2_t{id >> 16, id & 0xFFFFu};
+  } else {
+    return reinterpret_cast<const u32x2_t*>(a.row_ids)[r];
+  }
+}
+
+// The build side's RowID of a staged pair (a null partner: {-1, -1}; Inner joins have none).
+template <bool INNER, int BUILD>
+__device__ __forceinline__ u32x2_t pk_build_row(const PkArgs& a, uint32_t tag, uint32_t r) {
+  if constexpr (INNER) return pk_rank_row<BUILD>(a, r);
+  u32x2_t row = {0xFFFFFFFFu, 0xFFFFFFFFu};
+  if (!(tag & PK_STAGE_NULL)) row = pk_rank_row<BUILD>(a, r);
+  return row;
+}
+
+// (e) The copy-out, by whole 128-byte output lines.  A run's interior lines are numbered across the tile's partitions (s_run[partitions + p]
+// >> 16: partition p's first); thread = line finds its partition and leaves {staging slot, global pair index} of the line's first pair in
+// s_line.  Then eight lanes copy a line: a lane's source slot and destination are affine in its position, one 16-byte nontemporal store
+// per stream, the same cache policy for every lane of an instruction, no branch on parity or validity.  The pairs before a run's first
+// interior line and after its last share a line with the neighbouring tile's run (a run shorter than two lines may be all edge): half a
+// wave per partition writes them with 8-byte write-back stores, so that the partial lines merge in the XCD's L2 instead of reaching HBM
+// as two masked writes each.  (Parity-matched staging: a line's first slot is even, its 16-byte pieces are aligned.)  The copy-out it
+// replaced picked one of three store paths per lane -- 8 stores and 73 VALU / 43 SALU for two slots a lane.
+template <bool INNER, int BUILD>
+__device__ __forceinline__ void pk_copy_out(const PkArgs& a, const u32x2_t* s_stage, u32x2_t* s_line, const uint32_t* s_out_base, const uint32_t* s_run, uint32_t partitions,
+                                            uint32_t lines, uint32_t chunk, uint32_t tile_row_begin, uint32_t tid, uint32_t lane, uint32_t wave) {
   u32x2_t* probe_out = reinterpret_cast<u32x2_t*>(a.probe_out);
   u32x2_t* build_out = reinterpret_cast<u32x2_t*>(a.build_out);
-  auto rank_row = [&](uint32_t r) -> u32x2_t {
-    if constexpr (BUILD == BUILD_IDENTITY_65535) {
-      uint32_t c = r >> 16, offset = (r & 0xFFFFu) + c;   // r = c * 65535 + (c + low): offset < 2^17
-      if (offset >= 65535u) { ++c; offset -= 65535u; }
-      if (offset >= 65535u) { ++c; offset -= 65535u; }
-      return u32x2_t{c, offset};
-    } else if constexpr (BUILD == BUILD_IDENTITY) {
-      uint32_t c = static_cast<uint32_t>(static_cast<double>(r) * a.rank.identity_inverse);
-      if (c * a.rank.identity_rows > r) --c;
-      uint32_t offset = r - c * a.rank.identity_rows;
-      if (offset >= a.rank.identity_rows) { ++c; offset -= a.rank.identity_rows; }
-      return u32x2_t{c, offset};
-    } else if constexpr (BUILD == BUILD_PACKED) {
-      const uint32_t id = a.ids32[r];
-      return u32x2_t{id >> 16, id & 0xFFFFu};
-    } else {
-      return reinterpret_cast<const u32x2_t*>(a.row_ids)[r];
+  if (tid < lines) {   // the partition of line tid: the last one whose first interior line is <= tid (it has lines: the next one starts above tid)
+    uint32_t p = 0;
+    for (uint32_t step = partitions >> 1; step; step >>= 1) p += (s_run[partitions + p + step] >> 16) <= tid ? step : 0u;
+    const uint32_t pair_index = 16 * (pk_first_line(s_run[p]) + tid - (s_run[partitions + p] >> 16));
+    s_line[tid] = u32x2_t{pair_index - s_out_base[p], pair_index};
+  }
+  // Edge pairs: half a wave per non-empty partition, lane & 31 < 16 before the interior lines, >= 16 after.  Wave w owns partitions
+  // 2w + (b & 1) + 16 (b >> 1) -- bit b of `owned` where the partition has pairs (most of a radix's partitions can be empty in a tile).
+  const uint32_t mine = 2 * wave + (lane & 1) + 16 * (lane >> 1);
+  uint64_t owned = __ballot(mine < partitions && (s_run[partitions + (mine < partitions ? mine : 0u)] & 0xFFFFu) != 0);
+  while (owned) {
+    const uint32_t first_bit = __builtin_ctzll(owned);
+    owned &= owned - 1;
+    const uint32_t second_bit = owned ? static_cast<uint32_t>(__builtin_ctzll(owned)) : 64u;
+    owned &= owned - 1;
+    const uint32_t b = lane < 32 ? first_bit : second_bit;
+    if (b == 64) continue;
+    const uint32_t p = 2 * wave + (b & 1) + 16 * (b >> 1);
+    const uint32_t base = s_run[p], pairs = s_run[partitions + p] & 0xFFFFu, i = lane & 31;
+    const uint32_t first = pk_first_line(base), end = (base + pairs) >> 4;
+    const bool interior = end > first;
+    const uint32_t pair_index = interior && i >= 16 ? 16 * end + (i - 16) : base + i;
+    const bool edge = interior ? (i < 16 ? pair_index < 16 * first : pair_index < base + pairs) : i < pairs;
+    if (edge) {
+      const u32x2_t record = s_stage[pair_index - s_out_base[p]];
+      probe_out[pair_index] = u32x2_t{chunk, tile_row_begin + (record.x & PK_STAGE_ROW)};
+      if constexpr (BUILD != BUILD_NONE) build_out[pair_index] = pk_build_row<INNER, BUILD>(a, record.x, record.y);
     }
-  };
-  auto store2 = [&](u32x2_t v, u32x2_t* at) {   // (a run's first or last pair)
-    if constexpr (STORES != 0) *at = v; else __builtin_nontemporal_store(v, at);
-  };
-  for (uint32_t slot = 2 * tid; slot < reserved; slot += 2 * PK_THREADS) {
-    const u32x4_t records = *reinterpret_cast<const u32x4_t*>(s_stage + slot);
-    const uint32_t tag0 = records.x, tag1 = slot + 1 < reserved ? records.z : STAGE_INVALID;
-    const bool valid0 = tag0 != STAGE_INVALID, valid1 = tag1 != STAGE_INVALID;
-    const uint32_t partition0 = (tag0 >> PK_STAGE_PARTITION_SHIFT) & 0xFF, partition1 = (tag1 >> PK_STAGE_PARTITION_SHIFT) & 0xFF;
-    const u32x2_t probe0 = {chunk, tile_row_begin + (tag0 & PK_STAGE_ROW)}, probe1 = {chunk, tile_row_begin + (tag1 & PK_STAGE_ROW)};
-    u32x2_t build0 = {0xFFFFFFFFu, 0xFFFFFFFFu}, build1 = {0xFFFFFFFFu, 0xFFFFFFFFu};
+  }
+  __syncthreads();   // s_line
+  for (uint32_t piece = tid; piece < 8 * lines; piece += PK_THREADS) {
+    const u32x2_t line = s_line[piece >> 3];
+    const uint32_t offset = 2 * (piece & 7);
+    const u32x4_t records = *reinterpret_cast<const u32x4_t*>(s_stage + line.x + offset);
+    const size_t pair_pos = line.y + offset;
+    __builtin_nontemporal_store(u32x4_t{chunk, tile_row_begin + (records.x & PK_STAGE_ROW), chunk, tile_row_begin + (records.z & PK_STAGE_ROW)},
+                                reinterpret_cast<u32x4_t*>(probe_out + pair_pos));
     if constexpr (BUILD != BUILD_NONE) {
-      if (valid0 && !(tag0 & PK_STAGE_NULL)) build0 = rank_row(records.y);
-      if (valid1 && !(tag1 & PK_STAGE_NULL)) build1 = rank_row(records.w);
-    }
-    if (valid0 && valid1 && partition0 == partition1) {   // both pairs of one run: its first global index has the slot's parity -> aligned
-      const uint32_t pair_index = s_out_base[partition0] + slot;
-      const size_t pair_pos = pair_index;
-      const u32x4_t probe_pairs = {probe0.x, probe0.y, probe1.x, probe1.y}, build_pairs = {build0.x, build0.y, build1.x, build1.y};
-      bool write_back = STORES == 1;
-      if constexpr (STORES == 2) write_back = (pair_index >> 4) == s_edge[partition0] || (pair_index >> 4) == s_edge[partitions + partition0];
-      if (write_back) {
-        *reinterpret_cast<u32x4_t*>(probe_out + pair_pos) = probe_pairs;
-        if constexpr (BUILD != BUILD_NONE) *reinterpret_cast<u32x4_t*>(build_out + pair_pos) = build_pairs;
-      } else {
-        __builtin_nontemporal_store(probe_pairs, reinterpret_cast<u32x4_t*>(probe_out + pair_pos));
-        if constexpr (BUILD != BUILD_NONE) __builtin_nontemporal_store(build_pairs, reinterpret_cast<u32x4_t*>(build_out + pair_pos));
-      }
-    } else {
-      if (valid0) {
-        const size_t pair_pos = static_cast<uint32_t>(s_out_base[partition0] + slot);
-        store2(probe0, probe_out + pair_pos);
-        if constexpr (BUILD != BUILD_NONE) store2(build0, build_out + pair_pos);
-      }
-      if (valid1) {
-        const size_t pair_pos = static_cast<uint32_t>(s_out_base[partition1] + slot + 1);
-        store2(probe1, probe_out + pair_pos);
-        if constexpr (BUILD != BUILD_NONE) store2(build1, build_out + pair_pos);
-      }
+      const u32x2_t build0 = pk_build_row<INNER, BUILD>(a, records.x, records.y), build1 = pk_build_row<INNER, BUILD>(a, records.z, records.w);
+      __builtin_nontemporal_store(u32x4_t{build0.x, build0.y, build1.x, build1.y}, reinterpret_cast<u32x4_t*>(build_out + pair_pos));
     }
   }
 }
@@ -764,10 +796,10 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   const uint32_t partitions = 1u << a.radix_bits;
   const uint32_t stage_slots = PK_TILE + partitions + 2;
   u32x2_t* s_stage = reinterpret_cast<u32x2_t*>(join_smem);                      // [stage_slots]
-  uint32_t* s_wave_pairs = reinterpret_cast<uint32_t*>(s_stage + stage_slots);   // [PK_WAVES][partitions]
-  uint32_t* s_out_base = s_wave_pairs + PK_WAVES * partitions;                   // [partitions]
-  uint32_t* s_edge = s_out_base + partitions;                                    // [2][partitions] first / last 128-byte line of the partition's run
-  uint32_t* s_scratch = s_edge + 2 * partitions;                                 // [4] wave totals of the partition scan, [8] reserved slots, [16 + wave] a counter for rows without a pair
+  uint32_t* s_wave_pairs = reinterpret_cast<uint32_t*>(s_stage + stage_slots);   // [PK_WAVES][partitions]; in (e) the line table [PK_LINES] of {slot, pair index}
+  uint32_t* s_out_base = s_wave_pairs + pk_wave_pairs_words(partitions);         // [partitions]
+  uint32_t* s_run = s_out_base + partitions;                                     // [2][partitions] first global pair index of the run | first interior line << 16 | pairs
+  uint32_t* s_scratch = s_run + 2 * partitions;                                  // [4] wave totals of the partition scan, [8] reserved slots | interior lines << 16, [16 + wave] a counter for rows without a pair
   const uint32_t scan_waves = partitions > 64 ? partitions / 64 : 1;
   if (a.trace && tid == 0) a.trace[tile * 6 + 0] = wall_clock64();
   for (uint32_t i = tid; i < PK_WAVES * partitions; i += PK_THREADS) s_wave_pairs[i] = 0;
@@ -777,8 +809,9 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
                                          RANKS ? a.row_ranks + static_cast<size_t>(tile) * PK_TILE : nullptr);
   __builtin_amdgcn_wave_barrier();
   if (a.trace && tid == 0) a.trace[tile * 6 + 1] = wall_clock64();
-  // (a) reserve pairs + 1 slots per non-empty partition: scan inside each wave now, across waves in (c)
-  const uint32_t reserve = cell_pairs ? cell_pairs + 1 : 0;
+  // (a) reserve pairs + 1 slots per non-empty partition, and number its interior lines: scan inside each wave now, across waves in (c)
+  // (one scan of both: the slots in bits 0..15 -- at most PK_TILE + partitions --, the lines above them)
+  const uint32_t reserve = (cell_pairs ? cell_pairs + 1 : 0) | pk_interior_lines(cell_base, cell_pairs) << 16;
   uint32_t first_in_wave = 0;
   if (wave < scan_waves) {
     const uint32_t inclusive = join_wave_inclusive_scan(reserve);
@@ -809,17 +842,14 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   __syncthreads();
   if (a.trace && tid == 0) a.trace[tile * 6 + 2] = wall_clock64();
   // (c) thread = partition: first slot of every (wave, partition) = first slot of the partition (parity of its first global pair
-  // index) + pairs of earlier waves; output base
+  // index) + pairs of earlier waves; output base; the run and its first interior line for the copy-out
   if (tid < partitions) {
-    uint32_t first = first_in_wave + (wave > 0 ? s_scratch[0] : 0u) + (wave > 1 ? s_scratch[1] : 0u) + (wave > 2 ? s_scratch[2] : 0u);
-    if (reserve) {
-      const uint32_t shift = (first ^ cell_base) & 1u;
-      s_stage[shift ? first : first + cell_pairs].x = STAGE_INVALID;   // the spare slot
-      first += shift;
-    }
+    const uint32_t scanned = first_in_wave + (wave > 0 ? s_scratch[0] : 0u) + (wave > 1 ? s_scratch[1] : 0u) + (wave > 2 ? s_scratch[2] : 0u);
+    uint32_t first = scanned & 0xFFFFu;
+    if (cell_pairs) first += (first ^ cell_base) & 1u;   // (the spare slot in front of the run or behind it: never read)
     s_out_base[tid] = cell_base - first;
-    s_edge[tid] = cell_base >> 4;
-    s_edge[partitions + tid] = (cell_base + cell_pairs - (cell_pairs ? 1u : 0u)) >> 4;
+    s_run[tid] = cell_base;
+    s_run[partitions + tid] = (scanned & 0xFFFF0000u) | cell_pairs;
     uint32_t run = first;
 #pragma unroll
     for (uint32_t w = 0; w < PK_WAVES; ++w) {
@@ -827,7 +857,7 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
       s_wave_pairs[w * partitions + tid] = run;
       run += pairs;
     }
-    if (tid == 0) s_scratch[8] = s_scratch[0] + (scan_waves > 1 ? s_scratch[1] : 0u) + (scan_waves > 2 ? s_scratch[2] : 0u) + (scan_waves > 3 ? s_scratch[3] : 0u);   // every reserved slot
+    if (tid == 0) s_scratch[8] = s_scratch[0] + (scan_waves > 1 ? s_scratch[1] : 0u) + (scan_waves > 2 ? s_scratch[2] : 0u) + (scan_waves > 3 ? s_scratch[3] : 0u);   // every reserved slot, every interior line
   }
   __syncthreads();
   if (a.trace && tid == 0) a.trace[tile * 6 + 3] = wall_clock64();
@@ -844,11 +874,9 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   if (a.trace && tid == 0) a.trace[tile * 6 + 4] = wall_clock64();
   // (e) copy out: one loop per way of turning a partner's rank into its RowID (the identity cases have no global load in the loop:
   // no `s_waitcnt vmcnt(0)` per iteration, which would also wait for every store in flight)
-  const uint32_t reserved = s_scratch[8];
+  const uint32_t lines = s_scratch[8] >> 16;
   const uint32_t chunk = view.chunk, row_begin = view.row_begin;
-  // (STORES = 2: the flavour the A/Bs of rounds 3-5 kept -- all nontemporal 356 us, all write-back 294 us but 25 us more in the kernels behind it,
-  //  mixed 302 us, profiles/r04_join_variants.txt)
-#define HY_PK_COPY(BUILD) pk_copy_out<BUILD, static_cast<int>(FIXED_JOIN_STORES)>(a, s_stage, s_out_base, s_edge, partitions, reserved, chunk, row_begin, tid)
+#define HY_PK_COPY(BUILD) pk_copy_out<INNER, BUILD>(a, s_stage, reinterpret_cast<u32x2_t*>(s_wave_pairs), s_out_base, s_run, partitions, lines, chunk, row_begin, tid, lane, wave)
   if (!a.build_out) HY_PK_COPY(BUILD_NONE);
   else if (a.rank.identity_rows == 65535u) HY_PK_COPY(BUILD_IDENTITY_65535);
   else if (a.rank.identity_rows) HY_PK_COPY(BUILD_IDENTITY);
