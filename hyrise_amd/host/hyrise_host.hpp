@@ -711,8 +711,9 @@ struct DeviceColumn {
 };
 
 // How a DictionarySegment<pmr_string> is presented to the device: the value ids alone (scans), or with a dictionary of int64
-// stand-ins for the strings -- AggregateKey names (GROUP BY) or join ids (JoinHash).
-enum class StringKeys { None, AggregateKeyNames, JoinIds };
+// stand-ins for the strings -- AggregateKey names (GROUP BY), join ids (JoinHash) or ranks among the column's distinct strings in byte
+// order (Sort; hyrise_amd/string_keys.py StringRanks).
+enum class StringKeys { None, AggregateKeyNames, JoinIds, Ranks };
 struct ColumnCache {
   std::map<std::pair<ColumnID, StringKeys>, std::shared_ptr<DeviceColumn>> columns;
 };
@@ -804,6 +805,15 @@ inline std::shared_ptr<DeviceColumn> device_column_of_chunks(const std::shared_p
   std::map<std::string, int64_t> long_strings;
   std::shared_ptr<DeviceColumn> referenced;
   size_t host_lists = 0, device_lists = 0;
+  std::vector<std::string> rank_order;   // StringKeys::Ranks: the distinct strings of the chunks' dictionaries, in byte order
+  if (string_keys == StringKeys::Ranks) {
+    for (ChunkID table_chunk = chunk_begin; table_chunk < chunk_end; ++table_chunk) {
+      if (const auto* s = dynamic_cast<const DictionarySegment<std::string>*>(table->get_chunk(table_chunk)->get_segment(column_id).get()))
+        rank_order.insert(rank_order.end(), s->dictionary().begin(), s->dictionary().end());
+    }
+    std::sort(rank_order.begin(), rank_order.end());
+    rank_order.erase(std::unique(rank_order.begin(), rank_order.end()), rank_order.end());
+  }
   for (ChunkID table_chunk = chunk_begin; table_chunk < chunk_end; ++table_chunk) {
     const ChunkID chunk_id = table_chunk - chunk_begin;
     const auto segment = table->get_chunk(table_chunk)->get_segment(column_id);
@@ -848,8 +858,10 @@ inline std::shared_ptr<DeviceColumn> device_column_of_chunks(const std::shared_p
       d.encoding = HY_ENC_DICTIONARY; d.width = s->attribute_vector().width; d.data = s->attribute_vector().bytes.data();
       d.aux_size = s->unique_values_count();
       if (string_keys != StringKeys::None) {   // GROUP BY / join key: the dictionary becomes int64 key names / join ids
-        for (const auto& entry : s->dictionary())
-          column->key_names[chunk_id].push_back(string_keys == StringKeys::JoinIds ? string_join_id(entry) : string_key_name(entry, long_strings));
+        for (const auto& entry : s->dictionary()) {
+          if (string_keys == StringKeys::Ranks) column->key_names[chunk_id].push_back(std::lower_bound(rank_order.begin(), rank_order.end(), entry) - rank_order.begin());
+          else column->key_names[chunk_id].push_back(string_keys == StringKeys::JoinIds ? string_join_id(entry) : string_key_name(entry, long_strings));
+        }
         d.aux = column->key_names[chunk_id].data();
         d.data_type = HY_TYPE_LONG;
       } else {
@@ -1578,6 +1590,8 @@ class JoinHash : public AbstractReadOnlyOperator {   // operators/join_hash.hpp:
   }
 
  private:
+  // (public: Sort writes its reference output the same way)
+ public:
   // write_output_segments (join_output_writing.cpp:95-200) over PosLists in HBM: one side of the join result.  A data input's positions
   // ARE its RowIDs -- every output chunk's PosList is a view into the join's block.  A reference input's positions are dereferenced through
   // the input's PosLists (once per group of columns that share them: hy_poslist_gather over the WHOLE pair array into another pooled
@@ -1639,6 +1653,8 @@ class JoinHash : public AbstractReadOnlyOperator {   // operators/join_hash.hpp:
     std::vector<std::vector<const AbstractPosList*>> _lists;
   };
 
+ private:
+
   // write_output_segments (join_output_writing.cpp:95-200): reference inputs are dereferenced through their pos lists.
   static void append_side(Segments& segments, const std::shared_ptr<const Table>& input, std::vector<RowID> positions) {
     if (input->type() == TableType::Data) {
@@ -1664,6 +1680,195 @@ class JoinHash : public AbstractReadOnlyOperator {   // operators/join_hash.hpp:
   ColumnIDPair _column_ids;
   std::optional<size_t> _radix_bits;
   std::vector<OperatorJoinPredicate> _secondary_predicates;
+};
+
+// Sort (operators/sort.hpp, sort.cpp:287-516): ONE stable lexicographic sort of the input's rows on the device (hy_sort), whose result -- the
+// input table's positions in sorted order -- stays in a pooled block of HBM; the output's PosLists are views into it (a data input) or into
+// one block per column cluster that hy_poslist_gather dereferences it into (a reference input: JoinHash's DeviceSide), or the rows are
+// materialised (hy_column_gather for numeric columns; string payloads stay on the host).
+class Sort : public AbstractReadOnlyOperator {
+ public:
+  enum class ForceMaterialization : bool { No = false, Yes = true };
+  Sort(std::shared_ptr<const AbstractOperator> in, std::vector<SortColumnDefinition> sort_definitions, ChunkOffset output_chunk_size = Chunk::DEFAULT_SIZE,
+       ForceMaterialization force_materialization = ForceMaterialization::No)
+      : AbstractReadOnlyOperator(std::move(in)), _sort_definitions(std::move(sort_definitions)), _output_chunk_size(output_chunk_size),
+        _force_materialization(force_materialization) {}
+  const std::string& name() const override { static const std::string n = "Sort"; return n; }
+
+ protected:
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto input = left_input_table();
+    Assert(!_sort_definitions.empty(), "Sort: no sort definition");
+    for (const auto& definition : _sort_definitions) {   // sort.cpp:290-297
+      Assert(definition.column != INVALID_COLUMN_ID, "Sort: Invalid column in sort definition");
+      Assert(definition.column < input->column_count(), "Sort: Column ID is greater than table's column count");
+      Assert(definition.sort_mode == SortMode::AscendingNullsFirst || definition.sort_mode == SortMode::DescendingNullsFirst, "Sort does not support NULLS LAST.");
+    }
+    Assert(_output_chunk_size > 0, "Sort: output_chunk_size must be positive");
+    const uint64_t rows = input->row_count();
+    if (rows == 0) {   // :299-305
+      if (_force_materialization == ForceMaterialization::Yes && input->type() == TableType::References) return std::make_shared<Table>(input->column_definitions(), TableType::Data);
+      return input;
+    }
+    // the key columns, as the device reads them (string columns: ranks); a key it cannot read where it lies becomes a temporary data column
+    std::vector<std::shared_ptr<DeviceColumn>> key_columns;
+    std::vector<std::shared_ptr<const Table>> temporaries;
+    std::vector<hy_sort_key> keys;
+    for (const auto& definition : _sort_definitions) {
+      const auto string_keys = input->column_data_type(definition.column) == DataType::String ? StringKeys::Ranks : StringKeys::None;
+      std::shared_ptr<DeviceColumn> column;
+      if (!references_several_columns(*input, definition.column)) {
+        try { column = device_column(input, definition.column, string_keys); } catch (const std::logic_error&) { column = nullptr; }
+      }
+      if (!column) {
+        temporaries.push_back(host_key_table(input, definition.column));
+        column = device_column(temporaries.back(), 0);
+      }
+      key_columns.push_back(column);
+      keys.push_back(hy_sort_key{column->handle, static_cast<uint32_t>(definition.sort_mode) + 1, 0});   // HY_SORT_* = SortMode + 1
+    }
+    const auto positions = DeviceBlock::acquire(rows * sizeof(RowID));
+    uint64_t n_out = 0;
+    check_status(hy_sort(keys.data(), static_cast<uint32_t>(keys.size()), static_cast<hy_row_id*>(positions->ptr), rows, &n_out));
+    Assert(n_out == rows, "Sort: the device sorted another number of rows");
+
+    // :339-379: materialise when asked to, or when a column references more than one table or column
+    bool must_materialize = _force_materialization == ForceMaterialization::Yes;
+    for (ColumnID c = 0; !must_materialize && c < input->column_count(); ++c) must_materialize = references_several_columns(*input, c);
+    auto output = must_materialize ? materialized_output(input, positions, rows) : reference_output(input, positions, rows);
+    for (ChunkID k = 0; k < output->chunk_count(); ++k) {   // :381-389
+      output->get_chunk(k)->set_immutable();
+      output->get_chunk(k)->set_individually_sorted_by(_sort_definitions[0]);
+    }
+    return output;
+  }
+
+ private:
+  static bool references_several_columns(const Table& input, ColumnID column_id) {
+    if (input.type() != TableType::References) return false;
+    const auto& first = static_cast<const ReferenceSegment&>(*input.get_chunk(0)->get_segment(column_id));
+    for (ChunkID k = 1; k < input.chunk_count(); ++k) {
+      const auto& segment = static_cast<const ReferenceSegment&>(*input.get_chunk(k)->get_segment(column_id));
+      if (segment.referenced_table() != first.referenced_table() || segment.referenced_column_id() != first.referenced_column_id()) return true;
+    }
+    return false;
+  }
+
+  template <typename F>
+  static void resolve_type(DataType type, F&& f) {
+    switch (type) {
+      case DataType::Int: f(int32_t{}); break;
+      case DataType::Long: f(int64_t{}); break;
+      case DataType::Float: f(float{}); break;
+      case DataType::Double: f(double{}); break;
+      case DataType::String: f(std::string{}); break;
+      default: Fail("Sort: a column of type NULL");
+    }
+  }
+
+  // A key column the device cannot read where it lies (a union's output referencing several tables, a ValueSegment<pmr_string>): its values,
+  // read through the segments, as a data table of ValueSegments with the input's chunk layout -- strings as their ranks among the column's
+  // distinct strings in byte order.
+  static std::shared_ptr<Table> host_key_table(const std::shared_ptr<const Table>& input, ColumnID column_id) {
+    const auto type = input->column_data_type(column_id);
+    std::vector<std::string> rank_order;
+    if (type == DataType::String) {
+      for (ChunkID k = 0; k < input->chunk_count(); ++k) {
+        const auto& segment = *input->get_chunk(k)->get_segment(column_id);
+        for (ChunkOffset r = 0; r < segment.size(); ++r) {
+          const auto value = segment[r];
+          if (!variant_is_null(value)) rank_order.push_back(std::get<std::string>(value));
+        }
+      }
+      std::sort(rank_order.begin(), rank_order.end());
+      rank_order.erase(std::unique(rank_order.begin(), rank_order.end()), rank_order.end());
+    }
+    auto table = std::make_shared<Table>(TableColumnDefinitions{{"key", type == DataType::String ? DataType::Long : type, true}}, TableType::Data);
+    resolve_type(type, [&](auto tag) {
+      using T = decltype(tag);
+      using Key = std::conditional_t<std::is_same_v<T, std::string>, int64_t, T>;
+      for (ChunkID k = 0; k < input->chunk_count(); ++k) {
+        const auto& segment = *input->get_chunk(k)->get_segment(column_id);
+        std::vector<Key> values(segment.size());
+        std::vector<bool> nulls(segment.size());
+        for (ChunkOffset r = 0; r < segment.size(); ++r) {
+          const auto value = segment[r];
+          nulls[r] = variant_is_null(value);
+          if (nulls[r]) continue;
+          if constexpr (std::is_same_v<T, std::string>) values[r] = std::lower_bound(rank_order.begin(), rank_order.end(), std::get<std::string>(value)) - rank_order.begin();
+          else values[r] = std::get<T>(value);
+        }
+        table->append_chunk(Segments{std::make_shared<ValueSegment<Key>>(std::move(values), std::move(nulls))});
+      }
+    });
+    return table;
+  }
+
+  // write_reference_output_table (:161-252): chunks of output_chunk_size rows, every PosList a view into one pooled block per column cluster
+  std::shared_ptr<Table> reference_output(const std::shared_ptr<const Table>& input, const std::shared_ptr<DeviceBlock>& positions, uint64_t rows) const {
+    JoinHash::DeviceSide side(input, positions, rows);
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    for (uint64_t begin = 0; begin < rows; begin += _output_chunk_size) {
+      Segments segments;
+      side.append(segments, begin, std::min<uint64_t>(rows, begin + _output_chunk_size));
+      chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+    }
+    return std::make_shared<Table>(input->column_definitions(), TableType::References, std::move(chunks));
+  }
+
+  // write_materialized_output_table (:58-150): ValueSegments of output_chunk_size rows, nullable iff the column is; numeric columns gathered on
+  // the device (hy_column_gather), strings -- and columns the device cannot read where they lie -- through the segments on the host
+  std::shared_ptr<Table> materialized_output(const std::shared_ptr<const Table>& input, const std::shared_ptr<DeviceBlock>& positions, uint64_t rows) const {
+    const uint64_t n_chunks = (rows + _output_chunk_size - 1) / _output_chunk_size;
+    std::vector<Segments> segments(n_chunks, Segments(input->column_count()));
+    for (ColumnID c = 0; c < input->column_count(); ++c) {
+      const bool nullable = input->column_is_nullable(c);
+      resolve_type(input->column_data_type(c), [&](auto tag) {
+        using T = decltype(tag);
+        hy_column* gathered = nullptr;
+        if constexpr (!std::is_same_v<T, std::string>) {
+          if (!references_several_columns(*input, c)) {
+            try {
+              const auto column = device_column(input, c);
+              check_status(hy_column_gather(column->handle, static_cast<const hy_row_id*>(positions->ptr), rows, _output_chunk_size, &gathered));
+            } catch (const std::logic_error&) {
+              gathered = nullptr;
+            }
+          }
+        }
+        for (uint64_t k = 0; k < n_chunks; ++k) {
+          const uint64_t begin = k * _output_chunk_size, size = std::min<uint64_t>(_output_chunk_size, rows - begin);
+          std::vector<T> values(size);
+          std::vector<bool> nulls(size);
+          if (gathered) {
+            if constexpr (!std::is_same_v<T, std::string>) {
+              std::vector<uint64_t> words((size + 63) / 64);
+              check_status(hy_column_read_chunk(gathered, static_cast<uint32_t>(k), values.data(), words.data()));
+              for (uint64_t r = 0; r < size; ++r) nulls[r] = (words[r / 64] >> (r % 64)) & 1;
+            }
+          } else {
+            positions->prefetch_to_host(rows);
+            const RowID* sorted = positions->host_copy();
+            for (uint64_t r = 0; r < size; ++r) {
+              const RowID p = sorted[begin + r];
+              const auto value = (*input->get_chunk(p.chunk_id)->get_segment(c))[p.chunk_offset];
+              nulls[r] = variant_is_null(value);
+              if (!nulls[r]) values[r] = std::get<T>(value);
+            }
+          }
+          segments[k][c] = std::make_shared<ValueSegment<T>>(std::move(values), nullable ? std::optional<std::vector<bool>>(std::move(nulls)) : std::nullopt);
+        }
+        if (gathered) hy_column_destroy(gathered);
+      });
+    }
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    for (auto& chunk_segments : segments) chunks.push_back(std::make_shared<Chunk>(std::move(chunk_segments)));
+    return std::make_shared<Table>(input->column_definitions(), TableType::Data, std::move(chunks));
+  }
+
+  std::vector<SortColumnDefinition> _sort_definitions;
+  ChunkOffset _output_chunk_size;
+  ForceMaterialization _force_materialization;
 };
 
 struct AggregateDefinition {   // WindowFunctionExpression over a PQPColumnExpression (INVALID_COLUMN_ID: COUNT(*))

@@ -469,3 +469,66 @@ def scan_project_aggregate(filters, groupby_columns, aggregates, group_capacity=
     result = HostAggregateResult(len(aggregates), (table[0].rows + 1) if group_capacity is None else group_capacity)
     abi.check(lib.hy_scan_project_aggregate(farr, len(filters), garr, len(groupby_columns), specs, len(aggregates), C.byref(result.c)))
     return result
+
+
+class SortedPositions:
+    """hy_sort's output: the input table's positions (chunk, offset) in sorted order, in a block of the library's result-buffer pool (device
+    memory; the next operator reads it in place).  numpy() copies it back."""
+
+    def __init__(self, rows):
+        self.lib = abi.load_library()
+        self.rows = int(rows)
+        pointer = C.c_void_p()
+        abi.check(self.lib.hy_result_pool_acquire(8 * max(1, self.rows), C.byref(pointer)))
+        self.pointer = pointer.value
+
+    def numpy(self):
+        out = np.zeros((self.rows, 2), dtype=np.uint32)
+        if self.rows:
+            abi.check(self.lib.hy_memcpy_d2h(out.ctypes.data, self.pointer, out.nbytes))
+        return out
+
+    def close(self):
+        if getattr(self, "pointer", None):
+            self.lib.hy_result_pool_release(self.pointer)
+            self.pointer = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sort(keys, modes):
+    """hy_sort: ORDER BY keys[0], keys[1], ... (DeviceColumn / ResultColumn of one table; abi.SORT_ASCENDING_NULLS_FIRST or
+    abi.SORT_DESCENDING_NULLS_FIRST each) -> SortedPositions.  A string column takes part as ranks (string_rank_column)."""
+    if len(keys) != len(modes) or not keys:
+        raise ValueError("one mode per sort key, at least one key")
+    lib = abi.load_library()
+    array = (abi.SortKey * len(keys))()
+    for i, (column, mode) in enumerate(zip(keys, modes)):
+        array[i].column, array[i].mode = column.handle, mode
+    out = SortedPositions(keys[0].rows)
+    n_out = C.c_uint64(0)
+    abi.check(lib.hy_sort(array, len(keys), out.pointer, max(1, out.rows), C.byref(n_out)))
+    assert n_out.value == out.rows
+    return out
+
+
+def column_gather(column, positions, chunk_rows=abi.CHUNK_DEFAULT_SIZE):
+    """hy_column_gather: the rows of `column` at `positions` (SortedPositions, or (device pointer, n)) as a ResultColumn of chunk_rows-row
+    unencoded chunks -- Sort's materialised output of a numeric column."""
+    pointer, n = (positions.pointer, positions.rows) if isinstance(positions, SortedPositions) else positions
+    lib = abi.load_library()
+    handle = C.c_void_p()
+    abi.check(lib.hy_column_gather(column.handle, pointer, n, chunk_rows, C.byref(handle)))
+    return ResultColumn(handle)
+
+
+def string_rank_column(segments, dictionaries):
+    """A DictionarySegment<pmr_string> column (string_keys.encode_string_column) as a sort key: the same attribute vectors over dictionaries
+    of the strings' ranks among all of the column's distinct strings in byte order (StringRanks) -> (HostColumn of int64, StringRanks)."""
+    from .string_keys import StringRanks
+    ranks = StringRanks([entry for dictionary in dictionaries for entry in dictionary])
+    return ranks.dictionary_column(segments, dictionaries), ranks

@@ -403,6 +403,32 @@ hy_status hy_poslist_translate(const hy_column* scanned, const hy_scan_result* r
  * stream. */
 hy_status hy_poslist_gather(const hy_column* reference, const hy_row_id* positions, uint64_t n, hy_row_id* out);
 
+/* ---- Sort (replaces the sorting of Sort::_on_execute, sort.cpp:287-379, and SortImpl::sort, :400-516) ------------------------------------
+ * ONE stable lexicographic sort of a table's rows by keys[0], then keys[1], ...: sort.cpp applies the definitions from the last to the first,
+ * each a stable sort (std::stable_sort, :486-505) of the order the later ones left, so ties keep input order -- chunk order, then position in
+ * the chunk (for a reference table: the position in the chunk's PosList).  NULLs come first in both directions and keep their order among
+ * themselves (:435-443); descending is std::greater with stable ties; float / double compare with std::less (-0.0 and 0.0 tie; NaN is not
+ * supported).  A key column is a data or reference column of any numeric type and encoding; a string column is passed as a column of
+ * order-preserving integer ranks (hyrise_amd/string_keys.py StringRanks).  All key columns are columns of one table: the same chunk layout.
+ * mode: HY_SORT_ASCENDING_NULLS_FIRST or HY_SORT_DESCENDING_NULLS_FIRST; the NULLS LAST modes are HY_ERR_INVALID (Sort asserts, :294-296).
+ * out: DEVICE memory with room for `capacity` RowIDs; receives the INPUT TABLE's positions (chunk, offset) in sorted order -- the adapter
+ * dereferences them through a reference input's PosLists with hy_poslist_gather once per column cluster (write_reference_output_table,
+ * :161-252).  *n_out: the table's rows (HY_ERR_CAPACITY if they do not fit).  Tables of 2^32 rows or more: HY_ERR_UNSUPPORTED (32-bit row
+ * ids).  Returns when `out` is complete. */
+typedef struct hy_sort_key {
+  const hy_column* column;
+  uint32_t mode;       /* HY_SORT_* */
+  uint32_t reserved;
+} hy_sort_key;
+hy_status hy_sort(const hy_sort_key* keys, uint32_t n_keys, hy_row_id* out, uint64_t capacity, uint64_t* n_out);
+
+/* The rows of `column` at `positions` (device memory, n RowIDs of the column's table; a NULL RowID gives a NULL row) as a new device-resident
+ * column of unencoded segments of chunk_rows rows (the last one shorter), each with a null vector, like hy_projection_arithmetic's result:
+ * the numeric columns of Sort's materialised output (write_materialized_output_table, sort.cpp:58-150, when ForceMaterialization::Yes or a
+ * column references more than one table, :339-379).  Reads any encoding, reference columns included.  hy_column_read_chunk copies a chunk
+ * back; destroy it with hy_column_destroy. */
+hy_status hy_column_gather(const hy_column* column, const hy_row_id* positions, uint64_t n, uint32_t chunk_rows, hy_column** result);
+
 /* ---- Projection arithmetic (the ArithmeticExpressions a Projection evaluates through the
  * ExpressionEvaluator, operators/projection.cpp + expression/evaluation/expression_functors.hpp:127-213) -------------------
  * result = left <op> right, element-wise over a table's rows; an operand is a column of the table (data or reference
