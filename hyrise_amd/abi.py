@@ -99,6 +99,10 @@ class Operand(C.Structure):
     _fields_ = [("column", C.c_void_p), ("literal_type", C.c_uint32), ("literal", Value)]
 
 
+UNION_FORCE_SORT = 1      # hy_union_positions flags
+UNION_MAX_CLUSTERS = 8
+
+
 class SortKey(C.Structure):
     """hy_sort_key: one ORDER BY column and its HY_SORT_* mode (NULLS FIRST modes only)."""
     _fields_ = [("column", C.c_void_p), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
@@ -218,6 +222,8 @@ SYMBOLS = [
     ("hy_poslist_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("hy_sort", C.c_int32, [C.POINTER(SortKey), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("hy_column_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("hy_union_positions", C.c_int32, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint32)]),
     ("hy_result_pool_acquire", C.c_int32, [C.c_uint64, C.POINTER(C.c_void_p)]),
     ("hy_result_pool_acquire_pair", C.c_int32, [C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("hy_result_pool_release", C.c_int32, [C.c_void_p]),

@@ -8,6 +8,7 @@
 // stable LSD radix sort of (word, row) pairs by sort_pairs_u32 (join.hip), least significant word first.  A word whose value is the same
 // in every row is skipped (a reduction over the exported column decides it), and a word sorts only the bits its range needs.
 #include "hy_device.hpp"
+#include "sort_words.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -16,8 +17,6 @@
 namespace hy {
 
 namespace {
-
-struct u32x4_t { uint32_t x, y, z, w; };
 
 // The order-preserving unsigned key of a value's bits (4- or 8-byte types; NULL rows never get here).
 template <typename U>
@@ -155,8 +154,6 @@ __global__ __launch_bounds__(256) void gather_column_rows(const U* values, const
   }
 }
 
-uint32_t grid_for(uint64_t items) { return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 4096))); }
-
 bool numeric_type(uint32_t t) { return t >= HY_TYPE_INT && t <= HY_TYPE_DOUBLE; }
 
 hy_status check_sortable(const hy_column* column, const char* entry_point) {
@@ -199,13 +196,10 @@ hy_status hy_sort(const hy_sort_key* keys, uint32_t n_keys, hy_row_id* out, uint
   const uint32_t n = static_cast<uint32_t>(rows);
   hipStream_t stream = current_stream();
 
-  DeviceBuffer perm_a, perm_b, keys_a, keys_b, values, nulls, stats_buffer;
-  uint32_t* perm = nullptr;   // nullptr: the identity (no word sorted yet)
+  DeviceBuffer values, nulls, stats_buffer;
+  WordSort order;   // order.perm == nullptr: the identity (no word sorted yet)
   if (n > 1) {
-    HY_TRY(perm_a.alloc(4 * size_t{n} + 16));
-    HY_TRY(perm_b.alloc(4 * size_t{n} + 16));
-    HY_TRY(keys_a.alloc(4 * size_t{n} + 16));
-    HY_TRY(keys_b.alloc(4 * size_t{n} + 16));
+    HY_TRY(order.alloc(n));
     HY_TRY(values.alloc(8 * size_t{n} + 16));
     HY_TRY(nulls.alloc(size_t{n} + 16));
     HY_TRY(stats_buffer.alloc(64));
@@ -230,24 +224,17 @@ hy_status hy_sort(const hy_sort_key* keys, uint32_t n_keys, hy_row_id* out, uint
       uint32_t minimum = 0, bits = 1;
       if (word < 2) {
         if (word == 1 && !wide) continue;
-        if (null_rows == n || s[word] == s[2 + word]) continue;   // the same in every row: nothing to order
-        minimum = s[word];
-        const uint32_t range = s[2 + word] - minimum;
-        bits = 32 - static_cast<uint32_t>(__builtin_clz(range));
+        if (null_rows == n || !word_range(s[word], s[2 + word], &minimum, &bits)) continue;   // the same in every row: nothing to order
       } else if (null_rows == 0 || null_rows == n) {
         continue;
       }
-      uint32_t* ids = perm ? perm : perm_a.as<uint32_t>();
-      uint32_t* spare_ids = ids == perm_a.as<uint32_t>() ? perm_b.as<uint32_t>() : perm_a.as<uint32_t>();
-      uint32_t* key_words = keys_a.as<uint32_t>();
-      if (wide) hipLaunchKernelGGL(sort_gather_word<uint64_t>, dim3(grid_for(n / 4)), dim3(256), 0, stream, values.as<uint64_t>(), nulls.as<uint8_t>(), perm, key_words, ids, n, word, is_float, descending, minimum);
-      else hipLaunchKernelGGL(sort_gather_word<uint32_t>, dim3(grid_for(n / 4)), dim3(256), 0, stream, values.as<uint32_t>(), nulls.as<uint8_t>(), perm, key_words, ids, n, word, is_float, descending, minimum);
+      if (wide) hipLaunchKernelGGL(sort_gather_word<uint64_t>, dim3(grid_for(n / 4)), dim3(256), 0, stream, values.as<uint64_t>(), nulls.as<uint8_t>(), order.perm, order.key_words(), order.ids(), n, word, is_float, descending, minimum);
+      else hipLaunchKernelGGL(sort_gather_word<uint32_t>, dim3(grid_for(n / 4)), dim3(256), 0, stream, values.as<uint32_t>(), nulls.as<uint8_t>(), order.perm, order.key_words(), order.ids(), n, word, is_float, descending, minimum);
       HY_HIP(hipGetLastError());
-      HY_TRY(sort_pairs_u32(&key_words, &ids, keys_b.as<uint32_t>(), spare_ids, n, bits, stream));
-      perm = ids;
+      HY_TRY(order.sort(n, bits, stream));
     }
   }
-  hipLaunchKernelGGL(sort_positions, dim3(grid_for(n / 2)), dim3(256), 0, stream, perm, shape->d_row_base, shape->n_chunks, n, out);
+  hipLaunchKernelGGL(sort_positions, dim3(grid_for(n / 2)), dim3(256), 0, stream, order.perm, shape->d_row_base, shape->n_chunks, n, out);
   HY_HIP(hipGetLastError());
   HY_HIP(hipStreamSynchronize(stream));   // (the temporaries go back to the pool; the caller reads `out` next)
   return HY_OK;

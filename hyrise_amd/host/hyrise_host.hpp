@@ -1871,6 +1871,138 @@ class Sort : public AbstractReadOnlyOperator {
   ForceMaterialization _force_materialization;
 };
 
+inline bool same_column_definitions(const Table& a, const Table& b) {   // TableColumnDefinition::operator== (table_column_definition.cpp)
+  if (a.column_count() != b.column_count()) return false;
+  for (ColumnID c = 0; c < a.column_count(); ++c) {
+    if (a.column_name(c) != b.column_name(c) || a.column_data_type(c) != b.column_data_type(c) || a.column_is_nullable(c) != b.column_is_nullable(c)) return false;
+  }
+  return true;
+}
+
+// operators/union_positions.hpp: the set union of two reference tables over the same data -- what PredicateSplitUpRule makes of `WHERE p OR q`
+// (two TableScans over one input and a UnionNode, SetOperationMode::Positions).  Columns that share a PosList form a column cluster; each
+// input is a matrix of one RowID per cluster and row; both are sorted and merged like std::set_union (a row m times left and n times right:
+// max(m, n) times) by hy_union_positions, which reads the inputs' PosLists where they lie and leaves the output's in HBM.
+class UnionPositions : public AbstractReadOnlyOperator {
+ public:
+  UnionPositions(std::shared_ptr<const AbstractOperator> left, std::shared_ptr<const AbstractOperator> right) : AbstractReadOnlyOperator(std::move(left), std::move(right)) {}
+  const std::string& name() const override { static const std::string n = "UnionPositions"; return n; }
+  uint32_t path() const { return _path; }   // hy_union_positions' *path: bit 0 / 1 = the left / right input was sorted
+
+ protected:
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto left = left_input_table(), right = right_input_table();
+    // _prepare_operator (union_positions.cpp:237-253): the early results
+    Assert(same_column_definitions(*left, *right), "Input tables do not have the same layout.");
+    if (left->row_count() == 0) return right;
+    if (right->row_count() == 0) return left;
+    Assert(left->type() == TableType::References && right->type() == TableType::References, "UnionPositions does not support non-reference tables yet.");
+
+    // :257-296: a cluster begins where the PosList of the first chunk changes, in either input
+    const auto reference_segment = [](const Table& table, ChunkID chunk_id, ColumnID column_id) -> const ReferenceSegment& {
+      const auto* segment = dynamic_cast<const ReferenceSegment*>(table.get_chunk(chunk_id)->get_segment(column_id).get());
+      Assert(segment != nullptr, "UnionPositions: a reference table holds ReferenceSegments only");
+      return *segment;
+    };
+    std::vector<ColumnID> cluster_offsets;
+    for (const auto* table : {left.get(), right.get()}) {
+      const AbstractPosList* current = nullptr;
+      for (ColumnID c = 0; c < table->column_count(); ++c) {
+        const auto* pos_list = reference_segment(*table, 0, c).pos_list().get();
+        if (pos_list != current) { current = pos_list; cluster_offsets.push_back(c); }
+      }
+    }
+    std::sort(cluster_offsets.begin(), cluster_offsets.end());
+    cluster_offsets.erase(std::unique(cluster_offsets.begin(), cluster_offsets.end()), cluster_offsets.end());
+    std::vector<std::shared_ptr<const Table>> referenced_tables;
+    std::vector<ColumnID> referenced_column_ids;
+    for (const auto cluster_begin : cluster_offsets) referenced_tables.push_back(reference_segment(*left, 0, cluster_begin).referenced_table());
+    for (ColumnID c = 0; c < left->column_count(); ++c) referenced_column_ids.push_back(reference_segment(*left, 0, c).referenced_column_id());
+
+    // :298-343 (a debug check there; host-side and cheap, so always): every chunk of both inputs has these clusters, tables and columns
+    for (const auto* table : {left.get(), right.get()}) {
+      for (ChunkID k = 0; k < table->chunk_count(); ++k) {
+        const AbstractPosList* current = nullptr;
+        size_t next_cluster = 0;
+        for (ColumnID c = 0; c < table->column_count(); ++c) {
+          if (next_cluster < cluster_offsets.size() && c == cluster_offsets[next_cluster]) { ++next_cluster; current = nullptr; }
+          const auto& segment = reference_segment(*table, k, c);
+          if (!current) current = segment.pos_list().get();
+          Assert(current == segment.pos_list().get(), "Different PosLists in ColumnCluster");
+          Assert(segment.referenced_table() == referenced_tables[next_cluster - 1], "ReferenceSegment (Chunk: " + std::to_string(k) + ", Column: " + std::to_string(c) + ") doesn't reference the same table as the segment at the same index in the first chunk of the left input table does");
+          Assert(segment.referenced_column_id() == referenced_column_ids[c], "ReferenceSegment (Chunk: " + std::to_string(k) + ", Column: " + std::to_string(c) + ") doesn't reference the same column as the segment at the same index in the first chunk of the left input table does");
+        }
+      }
+    }
+
+    // one reference column per cluster and side (any column of the cluster carries its PosLists), one pooled block per cluster for the output
+    const uint32_t n_clusters = static_cast<uint32_t>(cluster_offsets.size());
+    std::vector<std::shared_ptr<DeviceColumn>> columns;
+    std::vector<const hy_column*> handles[2];
+    for (size_t side = 0; side < 2; ++side) {
+      for (const auto cluster_begin : cluster_offsets) {
+        columns.push_back(device_column(side == 0 ? left : right, cluster_begin));
+        handles[side].push_back(columns.back()->handle);
+      }
+    }
+    const uint64_t capacity = left->row_count() + right->row_count();
+    std::vector<std::shared_ptr<DeviceBlock>> blocks;
+    std::vector<hy_row_id*> lists;
+    for (uint32_t c = 0; c < n_clusters; ++c) {
+      blocks.push_back(DeviceBlock::acquire(capacity * sizeof(RowID)));
+      lists.push_back(static_cast<hy_row_id*>(blocks.back()->ptr));
+    }
+    uint64_t rows = 0;
+    check_status(hy_union_positions(handles[0].data(), handles[1].data(), n_clusters, 0, lists.data(), capacity, &rows, &_path));
+
+    // :168-186: chunks of Chunk::DEFAULT_SIZE rows, one PosList per cluster and chunk, shared by the cluster's segments
+    const bool on_device = device_resident_results();
+    if (!on_device) for (const auto& block : blocks) block->prefetch_to_host(rows);
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    for (uint64_t begin = 0; begin < rows; begin += Chunk::DEFAULT_SIZE) {
+      const uint64_t size = std::min<uint64_t>(Chunk::DEFAULT_SIZE, rows - begin);
+      Segments segments;
+      for (uint32_t c = 0; c < n_clusters; ++c) {
+        std::shared_ptr<const AbstractPosList> pos_list;
+        if (on_device) pos_list = std::make_shared<DevicePosList>(blocks[c], lists[c] + begin, size);
+        else pos_list = std::make_shared<RowIDPosList>(std::vector<RowID>(blocks[c]->host_copy() + begin, blocks[c]->host_copy() + begin + size));
+        const ColumnID cluster_end = c + 1 < n_clusters ? cluster_offsets[c + 1] : left->column_count();
+        for (ColumnID column_id = cluster_offsets[c]; column_id < cluster_end; ++column_id)
+          segments.push_back(std::make_shared<ReferenceSegment>(referenced_tables[c], referenced_column_ids[column_id], pos_list));
+      }
+      chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+    }
+    return std::make_shared<Table>(left->column_definitions(), TableType::References, std::move(chunks));
+  }
+
+ private:
+  uint32_t _path = 0;
+};
+
+// operators/union_all.hpp: the other operator PredicateSplitUpRule emits (SetOperationMode::All, when the predicates exclude each other):
+// the output holds the chunks of both inputs -- their segments shared, nothing copied, nothing for the device to do.
+class UnionAll : public AbstractReadOnlyOperator {
+ public:
+  UnionAll(std::shared_ptr<const AbstractOperator> left, std::shared_ptr<const AbstractOperator> right) : AbstractReadOnlyOperator(std::move(left), std::move(right)) {}
+  const std::string& name() const override { static const std::string n = "UnionAll"; return n; }
+
+ protected:
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto left = left_input_table(), right = right_input_table();
+    Assert(same_column_definitions(*left, *right), "Input tables must have same number of columns.");
+    Assert(left->type() == right->type(), "Input tables must have the same type.");
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    for (const auto& input : {left, right}) {
+      for (ChunkID k = 0; k < input->chunk_count(); ++k) {
+        Segments segments;
+        for (ColumnID c = 0; c < input->column_count(); ++c) segments.push_back(input->get_chunk(k)->get_segment(c));
+        chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+      }
+    }
+    return std::make_shared<Table>(left->column_definitions(), left->type(), std::move(chunks));
+  }
+};
+
 struct AggregateDefinition {   // WindowFunctionExpression over a PQPColumnExpression (INVALID_COLUMN_ID: COUNT(*))
   ColumnID column_id;
   WindowFunction function;

@@ -526,6 +526,57 @@ def column_gather(column, positions, chunk_rows=abi.CHUNK_DEFAULT_SIZE):
     return ResultColumn(handle)
 
 
+class UnionedPositions:
+    """hy_union_positions' output: one PosList per column cluster, each in a block of the library's result-buffer pool (device memory; the
+    next operator reads them in place).  numpy(c) copies cluster c's list back; path: bit 0 / 1 = the left / right side was sorted."""
+
+    def __init__(self, n_clusters, capacity):
+        self.lib = abi.load_library()
+        self.capacity = max(1, int(capacity))
+        self.rows, self.path, self.pointers = 0, 0, []
+        for _ in range(n_clusters):
+            pointer = C.c_void_p()
+            abi.check(self.lib.hy_result_pool_acquire(8 * self.capacity, C.byref(pointer)))
+            self.pointers.append(pointer.value)
+
+    def numpy(self, cluster=0):
+        out = np.zeros((self.rows, 2), dtype=np.uint32)
+        if self.rows:
+            abi.check(self.lib.hy_memcpy_d2h(out.ctypes.data, self.pointers[cluster], out.nbytes))
+        return out
+
+    def close(self):
+        pointers, self.pointers = getattr(self, "pointers", []), []
+        for pointer in pointers:
+            self.lib.hy_result_pool_release(pointer)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def union_positions(left, right, force_sort=False, capacity=None):
+    """hy_union_positions: the set union (UnionPositions, max(m, n) copies of a row) of two reference tables, each given as one reference
+    DeviceColumn per column cluster -> UnionedPositions.  capacity: rows per output list (default: rows(left) + rows(right), which always fits)."""
+    if len(left) != len(right) or not left:
+        raise ValueError("one column per cluster on both sides, at least one cluster")
+    lib = abi.load_library()
+    handles = [(C.c_void_p * len(side))(*[column.handle for column in side]) for side in (left, right)]
+    out = UnionedPositions(len(left), left[0].rows + right[0].rows if capacity is None else capacity)
+    lists = (C.c_void_p * len(left))(*out.pointers)
+    n_out, path = C.c_uint64(0), C.c_uint32(0)
+    try:
+        abi.check(lib.hy_union_positions(handles[0], handles[1], len(left), abi.UNION_FORCE_SORT if force_sort else 0, lists, 0 if capacity == 0 else out.capacity,
+                                         C.byref(n_out), C.byref(path)))
+    except Exception:
+        out.close()
+        raise
+    out.rows, out.path = n_out.value, path.value
+    return out
+
+
 def string_rank_column(segments, dictionaries):
     """A DictionarySegment<pmr_string> column (string_keys.encode_string_column) as a sort key: the same attribute vectors over dictionaries
     of the strings' ranks among all of the column's distinct strings in byte order (StringRanks) -> (HostColumn of int64, StringRanks)."""

@@ -429,6 +429,29 @@ hy_status hy_sort(const hy_sort_key* keys, uint32_t n_keys, hy_row_id* out, uint
  * back; destroy it with hy_column_destroy. */
 hy_status hy_column_gather(const hy_column* column, const hy_row_id* positions, uint64_t n, uint32_t chunk_rows, hy_column** result);
 
+/* ---- UnionPositions (replaces UnionPositions::_on_execute, union_positions.cpp:71-233) ------------------------------------------------------
+ * The set union of two reference tables over the same data: what PredicateSplitUpRule (predicate_split_up_rule.cpp:174-195) makes of
+ * `WHERE p OR q`.  Columns that share a PosList form a column cluster (:257-279); per input, the clusters' PosLists concatenated over all
+ * chunks are the columns of a reference matrix, one row of n_clusters RowIDs per table row (:349-372).  Rows are ordered lexicographically
+ * over the clusters, a RowID by (chunk_id, chunk_offset) as unsigned numbers -- NULL_ROW_ID is an ordinary, largest value.  Both matrices
+ * are sorted and merged with std::set_union (:205-230): the output is ascending, and a row that the left input holds m times and the right
+ * one n times appears max(m, n) times.  Equal rows are indistinguishable, so the output is fully determined.
+ * left[c] / right[c]: one column of HY_ENC_REFERENCE segments per cluster (any column of the input that carries the cluster's PosLists, as
+ * hy_poslist_gather's `reference`; host lists, device lists and NULL = entire-chunk lists); all clusters of a side have one chunk layout.  A
+ * column without chunks is an input without rows.
+ * out[c]: DEVICE memory for `capacity` RowIDs per cluster; capacity >= rows(left) + rows(right) always suffices.  *n_out: the output rows;
+ * if they exceed `capacity` the call returns HY_ERR_CAPACITY with *n_out set (the lists then hold the first `capacity` rows).
+ * *path (may be NULL): bit 0 = the left side was sorted by the library, bit 1 = the right side was.  A side that arrives in order (every row
+ * >= its predecessor: a TableScan's output over a data table) is merged as it is; one pass over the side decides it.
+ * flags: 0 or HY_UNION_FORCE_SORT (sort both sides whatever order they arrive in: tests, A/B timing).
+ * n_clusters: 1 .. 8 (more: HY_ERR_UNSUPPORTED; 0: HY_ERR_INVALID).  rows(left) + rows(right) >= 2^32: HY_ERR_UNSUPPORTED (32-bit row ids).
+ * Null arguments, a data column, clusters of different row counts: HY_ERR_INVALID.  The early results of the operator (an input without rows
+ * returns the other input TABLE, :237-253) are the adapter's: this call then returns the other side's rows in ascending order.
+ * Returns when `out` is complete, like hy_sort. */
+enum { HY_UNION_FORCE_SORT = 1 };
+hy_status hy_union_positions(const hy_column* const* left, const hy_column* const* right, uint32_t n_clusters, uint32_t flags, hy_row_id* const* out, uint64_t capacity,
+                             uint64_t* n_out, uint32_t* path);
+
 /* ---- Projection arithmetic (the ArithmeticExpressions a Projection evaluates through the
  * ExpressionEvaluator, operators/projection.cpp + expression/evaluation/expression_functors.hpp:127-213) -------------------
  * result = left <op> right, element-wise over a table's rows; an operand is a column of the table (data or reference
