@@ -101,6 +101,7 @@ class Operand(C.Structure):
 
 UNION_FORCE_SORT = 1      # hy_union_positions flags
 UNION_MAX_CLUSTERS = 8
+SORT_LIMIT_FORCE_FULL_SORT, SORT_LIMIT_FORCE_SELECT = 1, 2   # hy_sort_limit flags
 
 
 class SortKey(C.Structure):
@@ -221,6 +222,7 @@ SYMBOLS = [
     ("hy_gather_row_ids", C.c_int32, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("hy_poslist_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     ("hy_sort", C.c_int32, [C.POINTER(SortKey), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("hy_sort_limit", C.c_int32, [C.POINTER(SortKey), C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("hy_column_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("hy_union_positions", C.c_int32, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.c_uint64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint32)]),

@@ -175,6 +175,7 @@ class DevicePosList : public AbstractPosList {
   ChunkID common_chunk_id() const override { return _single ? _common : NO_COMMON_CHUNK; }
   const hy_row_id* device_data() const { return _rows; }
   const std::shared_ptr<const DeviceBlock>& block() const { return _block; }
+  bool on_host() const { return _copied.load(std::memory_order_acquire) || _block->host_copy() || _single_fetches.load(std::memory_order_relaxed) > 0; }   // some row has crossed the link
   // begin() of the reference's interface: the rows in host memory, copied on first use (from the block's copy if somebody prefetched it)
   const RowID* host_rows() const {
     if (const auto* all = _block->host_copy()) return all + (_rows - static_cast<const hy_row_id*>(_block->ptr));
@@ -1686,14 +1687,17 @@ class JoinHash : public AbstractReadOnlyOperator {   // operators/join_hash.hpp:
 // input table's positions in sorted order -- stays in a pooled block of HBM; the output's PosLists are views into it (a data input) or into
 // one block per column cluster that hy_poslist_gather dereferences it into (a reference input: JoinHash's DeviceSide), or the rows are
 // materialised (hy_column_gather for numeric columns; string payloads stay on the host).
+// row_limit: a LimitNode over the SortNode fused into the operator -- hy_sort_limit delivers the first min(row_limit, rows)
+// positions only, and the output is built from those: the rows Limit(Sort(x), row_limit) has, as a table of Sort's own type and chunking.
 class Sort : public AbstractReadOnlyOperator {
  public:
   enum class ForceMaterialization : bool { No = false, Yes = true };
   Sort(std::shared_ptr<const AbstractOperator> in, std::vector<SortColumnDefinition> sort_definitions, ChunkOffset output_chunk_size = Chunk::DEFAULT_SIZE,
-       ForceMaterialization force_materialization = ForceMaterialization::No)
+       ForceMaterialization force_materialization = ForceMaterialization::No, std::optional<uint64_t> row_limit = std::nullopt)
       : AbstractReadOnlyOperator(std::move(in)), _sort_definitions(std::move(sort_definitions)), _output_chunk_size(output_chunk_size),
-        _force_materialization(force_materialization) {}
+        _force_materialization(force_materialization), _row_limit(row_limit) {}
   const std::string& name() const override { static const std::string n = "Sort"; return n; }
+  uint32_t path() const { return _path; }   // hy_sort_limit's *path (with a row_limit): 0 = every row was sorted, 1 = the selection ran first
 
  protected:
   std::shared_ptr<const Table> _on_execute() override {
@@ -1705,7 +1709,7 @@ class Sort : public AbstractReadOnlyOperator {
       Assert(definition.sort_mode == SortMode::AscendingNullsFirst || definition.sort_mode == SortMode::DescendingNullsFirst, "Sort does not support NULLS LAST.");
     }
     Assert(_output_chunk_size > 0, "Sort: output_chunk_size must be positive");
-    const uint64_t rows = input->row_count();
+    uint64_t rows = input->row_count();
     if (rows == 0) {   // :299-305
       if (_force_materialization == ForceMaterialization::Yes && input->type() == TableType::References) return std::make_shared<Table>(input->column_definitions(), TableType::Data);
       return input;
@@ -1727,9 +1731,12 @@ class Sort : public AbstractReadOnlyOperator {
       key_columns.push_back(column);
       keys.push_back(hy_sort_key{column->handle, static_cast<uint32_t>(definition.sort_mode) + 1, 0});   // HY_SORT_* = SortMode + 1
     }
-    const auto positions = DeviceBlock::acquire(rows * sizeof(RowID));
+    const uint64_t sorted_rows = rows;
+    if (_row_limit) rows = std::min(rows, *_row_limit);
+    const auto positions = DeviceBlock::acquire(std::max<uint64_t>(rows, 1) * sizeof(RowID));
     uint64_t n_out = 0;
-    check_status(hy_sort(keys.data(), static_cast<uint32_t>(keys.size()), static_cast<hy_row_id*>(positions->ptr), rows, &n_out));
+    if (_row_limit) check_status(hy_sort_limit(keys.data(), static_cast<uint32_t>(keys.size()), *_row_limit, 0, static_cast<hy_row_id*>(positions->ptr), rows, &n_out, &_path));
+    else check_status(hy_sort(keys.data(), static_cast<uint32_t>(keys.size()), static_cast<hy_row_id*>(positions->ptr), sorted_rows, &n_out));
     Assert(n_out == rows, "Sort: the device sorted another number of rows");
 
     // :339-379: materialise when asked to, or when a column references more than one table or column
@@ -1869,6 +1876,66 @@ class Sort : public AbstractReadOnlyOperator {
   std::vector<SortColumnDefinition> _sort_definitions;
   ChunkOffset _output_chunk_size;
   ForceMaterialization _force_materialization;
+  std::optional<uint64_t> _row_limit;
+  uint32_t _path = 0;
+};
+
+// Limit (operators/limit.hpp, limit.cpp:76-126): the input's first row_count rows, chunk by chunk until they are out, every output chunk an
+// immutable reference chunk that keeps its input chunk's individually_sorted_by.  A PosList in HBM is cut as a DevicePosList view
+// (block, offset, size) of the same pooled block -- nothing is copied or fetched to the host, the next operator reads it where it lies -- a host
+// PosList is copied by prefix, and a data chunk gets RowID{chunk, 0 .. n).  Columns that shared a PosList share the cut one.
+// The mirror has no expression classes: row_count is the evaluated count, and limit.cpp:55-71's checks (an integral type, one non-NULL row,
+// not negative) belong to the adapter that evaluates the LimitNode's expression.
+class Limit : public AbstractReadOnlyOperator {
+ public:
+  Limit(std::shared_ptr<const AbstractOperator> in, uint64_t row_count) : AbstractReadOnlyOperator(std::move(in)), _row_count(row_count) {}
+  const std::string& name() const override { static const std::string n = "Limit"; return n; }
+
+ protected:
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto input = left_input_table();
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    uint64_t index = 0;
+    for (ChunkID k = 0; index < _row_count && k < input->chunk_count(); ++k) {
+      const auto chunk = input->get_chunk(k);
+      const auto size = static_cast<ChunkOffset>(std::min<uint64_t>(chunk->size(), _row_count - index));
+      Segments segments;
+      std::map<const AbstractPosList*, std::shared_ptr<const AbstractPosList>> cut;
+      std::shared_ptr<RowIDPosList> of_data_chunk;
+      for (ColumnID c = 0; c < input->column_count(); ++c) {
+        if (const auto reference = std::dynamic_pointer_cast<const ReferenceSegment>(chunk->get_segment(c))) {
+          auto& list = cut[reference->pos_list().get()];
+          if (!list) list = prefix_of(reference->pos_list(), size);
+          segments.push_back(std::make_shared<ReferenceSegment>(reference->referenced_table(), reference->referenced_column_id(), list));
+          continue;
+        }
+        if (!of_data_chunk) {
+          of_data_chunk = std::make_shared<RowIDPosList>();
+          for (ChunkOffset r = 0; r < size; ++r) of_data_chunk->rows.push_back(RowID{k, r});
+          of_data_chunk->guarantee_single_chunk();
+        }
+        segments.push_back(std::make_shared<ReferenceSegment>(input, c, of_data_chunk));
+      }
+      index += size;
+      auto output_chunk = std::make_shared<Chunk>(std::move(segments));
+      output_chunk->set_immutable();
+      if (!chunk->individually_sorted_by().empty()) output_chunk->set_individually_sorted_by(chunk->individually_sorted_by());   // :117-122
+      chunks.push_back(std::move(output_chunk));
+    }
+    return std::make_shared<Table>(input->column_definitions(), TableType::References, std::move(chunks));
+  }
+
+ private:
+  static std::shared_ptr<const AbstractPosList> prefix_of(const std::shared_ptr<const AbstractPosList>& list, ChunkOffset size) {
+    if (const auto* on_device = dynamic_cast<const DevicePosList*>(list.get()))
+      return std::make_shared<DevicePosList>(on_device->block(), on_device->device_data(), size, on_device->references_single_chunk(), on_device->common_chunk_id());
+    auto rows = std::make_shared<RowIDPosList>();
+    for (ChunkOffset r = 0; r < size; ++r) rows->rows.push_back((*list)[r]);
+    if (list->references_single_chunk()) rows->guarantee_single_chunk();
+    return rows;
+  }
+
+  uint64_t _row_count;
 };
 
 inline bool same_column_definitions(const Table& a, const Table& b) {   // TableColumnDefinition::operator== (table_column_definition.cpp)

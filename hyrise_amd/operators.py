@@ -500,19 +500,32 @@ class SortedPositions:
             pass
 
 
-def sort(keys, modes):
+def sort(keys, modes, limit=None, flags=0):
     """hy_sort: ORDER BY keys[0], keys[1], ... (DeviceColumn / ResultColumn of one table; abi.SORT_ASCENDING_NULLS_FIRST or
-    abi.SORT_DESCENDING_NULLS_FIRST each) -> SortedPositions.  A string column takes part as ranks (string_rank_column)."""
+    abi.SORT_DESCENDING_NULLS_FIRST each) -> SortedPositions.  A string column takes part as ranks (string_rank_column).
+    limit: ORDER BY ... LIMIT limit through hy_sort_limit (flags: 0 or abi.SORT_LIMIT_FORCE_*) -> SortedPositions of min(limit, rows) rows
+    whose .path says whether every row was sorted (0) or the selection ran first (1)."""
     if len(keys) != len(modes) or not keys:
         raise ValueError("one mode per sort key, at least one key")
     lib = abi.load_library()
     array = (abi.SortKey * len(keys))()
     for i, (column, mode) in enumerate(zip(keys, modes)):
         array[i].column, array[i].mode = column.handle, mode
-    out = SortedPositions(keys[0].rows)
     n_out = C.c_uint64(0)
-    abi.check(lib.hy_sort(array, len(keys), out.pointer, max(1, out.rows), C.byref(n_out)))
+    if limit is None:
+        out = SortedPositions(keys[0].rows)
+        abi.check(lib.hy_sort(array, len(keys), out.pointer, max(1, out.rows), C.byref(n_out)))
+        assert n_out.value == out.rows
+        return out
+    out = SortedPositions(min(int(limit), keys[0].rows))
+    path = C.c_uint32(0)
+    try:
+        abi.check(lib.hy_sort_limit(array, len(keys), int(limit), flags, out.pointer, out.rows, C.byref(n_out), C.byref(path)))
+    except Exception:
+        out.close()
+        raise
     assert n_out.value == out.rows
+    out.path = path.value
     return out
 
 

@@ -422,6 +422,23 @@ typedef struct hy_sort_key {
 } hy_sort_key;
 hy_status hy_sort(const hy_sort_key* keys, uint32_t n_keys, hy_row_id* out, uint64_t capacity, uint64_t* n_out);
 
+/* ---- Sort under a Limit (replaces Sort::_on_execute / SortImpl::sort, sort.cpp:287-516, followed by Limit::_on_execute, limit.cpp:47-127) ------
+ * The first n = min(limit, rows) RowIDs of hy_sort's output, byte for byte, without sorting the rows that cannot be among them.  The sorted
+ * order is lexicographic in keys[0] (NULLs first), keys[1], ..., and last the input row number (the stable sorts' ties), so its first n rows
+ * are unique.  keys / modes / refusals: exactly hy_sort's (NULLS LAST and columns of different tables HY_ERR_INVALID, string and MVCC columns,
+ * 2^32 rows or more HY_ERR_UNSUPPORTED).
+ * out: DEVICE memory for `capacity` RowIDs; capacity >= n suffices, and nothing is written behind out[n).  *n_out = n; a smaller capacity is
+ * HY_ERR_CAPACITY with *n_out set and nothing written.  limit == 0 or a table without rows: HY_OK, *n_out = 0, out may be NULL.
+ * *path (may be NULL): 0 = every row was sorted and the result cut (hy_sort into a temporary), 1 = the selection ran first: a histogram over
+ * the most significant digits of keys[0]'s order-preserving key finds the bucket that holds the n-th row (refined digit by digit while the
+ * bucket is a large share of the table), the NULL rows, the rows below the bucket and the bucket's rows are compacted in ascending row order,
+ * and hy_sort's chain of word sorts runs over those candidates only.
+ * flags: 0 = the library chooses (limit >= rows: always path 0; a candidate set that is a large share of the table -- heavy ties on keys[0] --
+ * falls back to path 0), HY_SORT_LIMIT_FORCE_FULL_SORT / HY_SORT_LIMIT_FORCE_SELECT (tests, A/B timing; FORCE_SELECT is correct at any size).
+ * Both force flags, or any other bit: HY_ERR_INVALID.  Returns when `out` is complete. */
+enum { HY_SORT_LIMIT_FORCE_FULL_SORT = 1, HY_SORT_LIMIT_FORCE_SELECT = 2 };
+hy_status hy_sort_limit(const hy_sort_key* keys, uint32_t n_keys, uint64_t limit, uint32_t flags, hy_row_id* out, uint64_t capacity, uint64_t* n_out, uint32_t* path);
+
 /* The rows of `column` at `positions` (device memory, n RowIDs of the column's table; a NULL RowID gives a NULL row) as a new device-resident
  * column of unencoded segments of chunk_rows rows (the last one shorter), each with a null vector, like hy_projection_arithmetic's result:
  * the numeric columns of Sort's materialised output (write_materialized_output_table, sort.cpp:58-150, when ForceMaterialization::Yes or a
