@@ -145,6 +145,12 @@ class AggregateResult(C.Structure):
                 ("reserved", C.c_uint32), ("group_row_ids", C.c_void_p), ("columns", C.POINTER(AggregateColumn))]
 
 
+class AggregateColumns(C.Structure):
+    """hy_aggregate_columns: hy_aggregate_hash_columns' output table -- column handles and the representative RowIDs in device memory."""
+    _fields_ = [("skip_groupby_mask", C.c_uint64), ("n_groups", C.c_uint32), ("reserved", C.c_uint32),
+                ("aggregate_columns", C.POINTER(C.c_void_p)), ("groupby_columns", C.POINTER(C.c_void_p)), ("group_row_ids", C.c_void_p)]
+
+
 STAR_NO_OP = 0xFFFFFFFF
 MAX_STAR_DIMENSIONS, MAX_STAR_AGGREGATES = 8, 8
 
@@ -212,6 +218,8 @@ SYMBOLS = [
     ("hy_join_hash_count", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("hy_aggregate_hash", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
                                       C.POINTER(AggregateResult)]),
+    ("hy_aggregate_hash_columns", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32,
+                                              C.POINTER(AggregateColumns)]),
     ("hy_star_join_aggregate", C.c_int32, [C.POINTER(StarDimension), C.c_uint32, C.POINTER(StarColumn), C.c_uint32, C.POINTER(StarAggregate), C.c_uint32,
                                            C.POINTER(AggregateResult), C.POINTER(C.c_uint64)]),
     ("hy_scan_project_aggregate", C.c_int32, [C.POINTER(Filter), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(FusedAggregate), C.c_uint32,

@@ -2450,10 +2450,13 @@ __global__ __launch_bounds__(256) void finish_row_ids(const uint32_t* order, con
 struct FinishColumn {
   uint32_t function, out_type, is_float, primary;
 };
-__global__ __launch_bounds__(256) void finish_column(const uint32_t* order, const uint64_t* values, const uint64_t* counts, uint32_t n_groups, uint32_t n_device, FinishColumn c,
-                                                     void* out_values, uint8_t* out_null) {
-  const uint32_t o = blockIdx.x * 256 + threadIdx.x;
-  if (o >= n_groups) return;
+// (the cell of result row o: its value in the column's type and whether it is NULL)
+struct FinishedCell {
+  int64_t vi;
+  double vf;
+  bool is_null;
+};
+__device__ __forceinline__ FinishedCell finished_cell(const uint32_t* order, const uint64_t* values, const uint64_t* counts, uint32_t n_device, const FinishColumn& c, uint32_t o) {
   const size_t at = size_t{order[o]} * n_device + c.primary;
   const uint64_t bits = values[at], count = counts[at];
   bool is_null = count == 0;
@@ -2475,12 +2478,47 @@ __global__ __launch_bounds__(256) void finish_column(const uint32_t* order, cons
       } else vi = static_cast<int64_t>(bits);
       break;
   }
-  if (out_null) out_null[o] = is_null;
-  switch (c.out_type) {
-    case HY_TYPE_INT: static_cast<int32_t*>(out_values)[o] = is_null ? 0 : static_cast<int32_t>(vi); break;
-    case HY_TYPE_LONG: static_cast<int64_t*>(out_values)[o] = is_null ? 0 : vi; break;
-    case HY_TYPE_FLOAT: static_cast<float*>(out_values)[o] = is_null ? 0.f : static_cast<float>(vf); break;
-    default: static_cast<double*>(out_values)[o] = is_null ? 0.0 : vf; break;
+  return FinishedCell{vi, vf, is_null};
+}
+__device__ __forceinline__ void store_finished_cell(const FinishedCell& cell, uint32_t out_type, void* out_values, uint64_t o) {
+  switch (out_type) {
+    case HY_TYPE_INT: static_cast<int32_t*>(out_values)[o] = cell.is_null ? 0 : static_cast<int32_t>(cell.vi); break;
+    case HY_TYPE_LONG: static_cast<int64_t*>(out_values)[o] = cell.is_null ? 0 : cell.vi; break;
+    case HY_TYPE_FLOAT: static_cast<float*>(out_values)[o] = cell.is_null ? 0.f : static_cast<float>(cell.vf); break;
+    default: static_cast<double*>(out_values)[o] = cell.is_null ? 0.0 : cell.vf; break;
+  }
+}
+__global__ __launch_bounds__(256) void finish_column(const uint32_t* order, const uint64_t* values, const uint64_t* counts, uint32_t n_groups, uint32_t n_device, FinishColumn c,
+                                                     void* out_values, uint8_t* out_null) {
+  const uint32_t o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= n_groups) return;
+  const FinishedCell cell = finished_cell(order, values, counts, n_device, c, o);
+  if (out_null) out_null[o] = cell.is_null;
+  store_finished_cell(cell, c.out_type, out_values, o);
+}
+
+// hy_aggregate_hash_columns: the same cells, written where the next operator reads them -- a column of chunk_rows-row value segments in
+// hy_column_gather's layout (sort.hip): chunk k's values at out_values + k * value_stride, its null vector at out_nulls + k * null_stride
+// words.  One wave per (chunk, 64-row word) unit, as gather_column_rows walks them: chunk_rows need not be a multiple of 64, so a wave
+// that simply took 64 consecutive result rows would straddle two chunks' bitmaps.  The lanes' stores are consecutive cells of the chunk;
+// the wave's NULL flags are one word of its bitmap (lanes behind the chunk's last row vote 0: the tail bits stay zero).
+__global__ __launch_bounds__(256) void finish_column_chunks(const uint32_t* order, const uint64_t* values, const uint64_t* counts, uint32_t n_groups, uint32_t n_device, FinishColumn c,
+                                                            uint32_t chunk_rows, uint32_t words_per_chunk, uint64_t value_stride, uint64_t null_stride, char* out_values,
+                                                            uint64_t* out_nulls, uint64_t units) {
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint64_t u = (static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x) / 64; u < units; u += static_cast<uint64_t>(gridDim.x) * 4) {
+    const uint64_t chunk = u / words_per_chunk, word = u % words_per_chunk;
+    const uint64_t chunk_begin = chunk * chunk_rows;
+    const uint64_t rows_here = n_groups - chunk_begin < chunk_rows ? n_groups - chunk_begin : chunk_rows;
+    const uint64_t offset = word * 64 + lane;
+    bool is_null = false;
+    if (offset < rows_here) {
+      const FinishedCell cell = finished_cell(order, values, counts, n_device, c, static_cast<uint32_t>(chunk_begin + offset));
+      is_null = cell.is_null;
+      store_finished_cell(cell, c.out_type, out_values + chunk * value_stride, offset);
+    }
+    const uint64_t bits = __ballot(is_null);
+    if (lane == 0) out_nulls[chunk * null_stride + word] = bits;
   }
 }
 
@@ -2981,6 +3019,82 @@ static void for_each_group_range(uint32_t n, Body body) {
   for (auto& worker : workers) worker.join();
 }
 
+// ---- hy_aggregate_hash_columns: the result as device-resident columns ------------------------------------------------------------------
+// One output column in hy_column_gather's layout (sort.hip): ONE pooled arena -- chunk k's values at k * value_stride (256-byte aligned,
+// 16 spare bytes behind them), then every chunk's null vector at k * null_stride words -- which the hy_column made over it owns.
+struct ChunkedColumn {
+  uint32_t type = HY_TYPE_NULL, width = 8, chunk_rows = 0, n_chunks = 0, words_per_chunk = 0;
+  uint64_t rows = 0, value_stride = 0, null_stride = 0;
+  char* arena = nullptr;
+  size_t arena_capacity = 0;
+  ChunkedColumn() = default;
+  ChunkedColumn(const ChunkedColumn&) = delete;
+  ChunkedColumn& operator=(const ChunkedColumn&) = delete;
+  ~ChunkedColumn() { if (arena) pool_release(arena, arena_capacity); }
+  size_t bytes() const { return static_cast<size_t>(value_stride * n_chunks + 8 * null_stride * n_chunks); }
+  uint64_t* nulls() const { return reinterpret_cast<uint64_t*>(arena + value_stride * n_chunks); }
+  uint64_t units() const { return uint64_t{n_chunks} * words_per_chunk; }   // (chunk, 64-row word) pairs: a wave each
+  hy_status alloc(uint32_t data_type, uint64_t n_rows, uint32_t rows_per_chunk) {
+    type = data_type;
+    width = (type == HY_TYPE_INT || type == HY_TYPE_FLOAT) ? 4 : 8;
+    rows = n_rows;
+    chunk_rows = rows_per_chunk;
+    n_chunks = static_cast<uint32_t>((n_rows + rows_per_chunk - 1) / rows_per_chunk);
+    value_stride = align_up(uint64_t{chunk_rows} * width + 16, 256);
+    words_per_chunk = (chunk_rows + 63) / 64;
+    null_stride = align_up(words_per_chunk, 32);
+    return pool_acquire(bytes() + 256, reinterpret_cast<void**>(&arena), &arena_capacity);
+  }
+  // the column over the arena (HY_MEM_DEVICE: nothing is copied), which then owns it
+  hy_status adopt(hy_column** out) {
+    std::vector<hy_segment> segments(n_chunks ? n_chunks : 1);
+    for (uint32_t k = 0; k < n_chunks; ++k) {
+      hy_segment& s = segments[k];
+      std::memset(&s, 0, sizeof(s));
+      s.encoding = HY_ENC_UNENCODED;
+      s.data_type = type;
+      s.size = static_cast<uint32_t>(std::min<uint64_t>(chunk_rows, rows - uint64_t{k} * chunk_rows));
+      s.width = width;
+      s.data = arena + k * value_stride;
+      s.nulls = nulls() + k * null_stride;
+      s.ref_chunk_id = 0xFFFFFFFFu;
+    }
+    hy_column* column = nullptr;
+    HY_TRY(hy_column_create(segments.data(), n_chunks, HY_MEM_DEVICE, &column));
+    column->pooled.emplace_back(arena_capacity, arena);
+    arena = nullptr;
+    *out = column;
+    return HY_OK;
+  }
+};
+
+// Where run_aggregate leaves its result for hy_aggregate_hash_columns.  Device finish: the finish kernels write `columns` and `row_ids`
+// (finished = true).  Host finish: host_buffers() gives the host loops arrays of the size they turn out to need, which the entry point then
+// uploads once into the same layout.
+struct ColumnSink {
+  uint32_t chunk_rows = 0;
+  uint32_t n_groups = 0;
+  bool finished = false;            // the columns below are complete (device finish)
+  hy_column** columns = nullptr;    // [n_aggregates], the caller's; entries are NULL until made
+  hy_row_id* row_ids = nullptr;     // result-pool buffer (hy_result_pool_acquire), n_groups RowIDs
+  std::vector<std::unique_ptr<uint64_t[]>> host_values;
+  std::vector<std::unique_ptr<uint8_t[]>> host_nulls;
+  std::unique_ptr<hy_row_id[]> host_row_ids;
+  hy_status host_buffers(uint32_t groups, uint32_t n_aggregates, hy_aggregate_result* result) {
+    const size_t capacity = groups ? groups : 1;
+    host_row_ids.reset(new hy_row_id[capacity]);
+    result->group_row_ids = host_row_ids.get();
+    for (uint32_t g = 0; g < n_aggregates; ++g) {
+      host_values.emplace_back(new uint64_t[capacity]);
+      host_nulls.emplace_back(new uint8_t[capacity]);
+      result->columns[g].values = host_values[g].get();
+      result->columns[g].is_null = host_nulls[g].get();
+    }
+    result->group_capacity = groups;
+    return HY_OK;
+  }
+};
+
 // hy_scan_project_aggregate: the filters and the aggregates' input expressions, checked and typed by run_fused below.  The aggregate
 // specs then carry no columns -- input g is `inputs[g]` (n_nodes 0: COUNT(*)); inputs with the same `same_as` are one expression.
 struct FusedQuery {
@@ -2994,7 +3108,7 @@ struct FusedQuery {
 };
 
 static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_groupby, const hy_aggregate_spec* specs, uint32_t n_aggregates,
-                               hy_aggregate_result* result, const FusedQuery* fused = nullptr) {
+                               hy_aggregate_result* result, const FusedQuery* fused = nullptr, ColumnSink* sink = nullptr) {
   if (n_groupby > MAX_GROUPBY) return fail(HY_ERR_UNSUPPORTED, "more than %u GROUP BY columns stay on the CPU path", MAX_GROUPBY);
   if (n_aggregates > MAX_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "more than %u aggregates stay on the CPU path", MAX_AGGREGATES);
   const hy_column* shape = fused ? fused->shape : n_groupby ? groupby[0] : nullptr;
@@ -3151,7 +3265,7 @@ static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_group
     bool plain_functions = n_groupby > 0 && result->mem == HY_MEM_HOST && shape->rows < (1ull << 32);
     for (uint32_t g = 0; g < n_aggregates && plain_functions; ++g) {
       const uint32_t f = specs[g].function;
-      plain_functions = primary[g] >= 0 && (f == HY_AGG_COUNT || f == HY_AGG_SUM || f == HY_AGG_AVG || f == HY_AGG_MIN || f == HY_AGG_MAX) && result->columns[g].values;
+      plain_functions = primary[g] >= 0 && (f == HY_AGG_COUNT || f == HY_AGG_SUM || f == HY_AGG_AVG || f == HY_AGG_MIN || f == HY_AGG_MAX) && (sink || result->columns[g].values);
     }
     main_groups.keep_on_device = plain_functions;
     if (!fused && n_groupby) {
@@ -3301,7 +3415,7 @@ static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_group
   if (main_groups.on_device) {
     const uint32_t n_groups = main_groups.n_groups;
     result->n_groups = n_groups;
-    if (n_groups > result->group_capacity) return fail(HY_ERR_CAPACITY, "aggregate produces %u groups, capacity is %u", n_groups, result->group_capacity);
+    if (!sink && n_groups > result->group_capacity) return fail(HY_ERR_CAPACITY, "aggregate produces %u groups, capacity is %u", n_groups, result->group_capacity);
     const bool int_key = n_groupby == 1 && groupby[0]->data_type == HY_TYPE_INT;
     GroupExtent* extent_host = nullptr;
     GroupExtent* extent_dev = nullptr;
@@ -3332,6 +3446,31 @@ static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_group
       uint32_t* sorted_keys = sort_keys.as<uint32_t>();
       uint32_t* order = sort_ids.as<uint32_t>();
       HY_TRY(sort_pairs_u32(&sorted_keys, &order, sort_keys_tmp.as<uint32_t>(), sort_ids_tmp.as<uint32_t>(), n_groups, key_bits, stream));
+      if (sink) {   // hy_aggregate_hash_columns: RowIDs into a result-pool buffer, cells into the output columns' chunks; nothing comes to the host
+        const RowIdOf row_id_of(shape);
+        HY_TRY(hy_result_pool_acquire(sizeof(hy_row_id) * uint64_t{n_groups}, reinterpret_cast<void**>(&sink->row_ids)));
+        hipLaunchKernelGGL(finish_row_ids, dim3(blocks), dim3(256), 0, stream, order, immediate ? main_groups.d_last.as<uint64_t>() : main_groups.d_first.as<uint64_t>(), n_groups, shape->d_row_base,
+                           shape->n_chunks, static_cast<uint32_t>(row_id_of.size), sink->row_ids);
+        ChunkedColumn chunked[MAX_AGGREGATES];
+        for (uint32_t g = 0; g < n_aggregates; ++g) {
+          const uint32_t in_type = input_type(g);
+          result->columns[g].data_type = result_type(specs[g].function, in_type);
+          HY_TRY(chunked[g].alloc(result->columns[g].data_type, n_groups, sink->chunk_rows));
+          const FinishColumn c{specs[g].function, result->columns[g].data_type, (in_type == HY_TYPE_FLOAT || in_type == HY_TYPE_DOUBLE) ? 1u : 0u, static_cast<uint32_t>(primary[g])};
+          const uint64_t units = chunked[g].units();
+          const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((units + 3) / 4, 8192)));
+          hipLaunchKernelGGL(finish_column_chunks, dim3(grid), dim3(256), 0, stream, order, main_groups.d_values.as<uint64_t>(), main_groups.d_counts.as<uint64_t>(), n_groups, n_device, c,
+                             chunked[g].chunk_rows, chunked[g].words_per_chunk, chunked[g].value_stride, chunked[g].null_stride, chunked[g].arena, chunked[g].nulls(), units);
+        }
+        HY_HIP(hipGetLastError());
+        HY_HIP(hipStreamSynchronize(stream));   // (the accumulators and the order go back to the pool as this returns)
+        for (uint32_t g = 0; g < n_aggregates; ++g) HY_TRY(chunked[g].adopt(&sink->columns[g]));
+        sink->n_groups = n_groups;
+        sink->finished = true;
+        g_agg_finished_on_device = 1;
+        lap("finished on the device, into columns");
+        return HY_OK;
+      }
       // Results up to 16 MiB are written straight into pinned host memory by the kernels and copied out by the host (every hipMemcpyAsync
       // into pageable memory is a staged copy with ~0.2 ms of host work around it: five of them cost more than the kernels); larger ones
       // go through device arrays and one copy each.
@@ -3456,6 +3595,7 @@ static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_group
   const bool no_groupby_empty = n_groupby == 0 && n_groups == 0;   // one row of NULLs / zero counts (:1422-1432)
   const uint32_t out_groups = no_groupby_empty ? 1 : n_groups;
   result->n_groups = out_groups;
+  if (sink) HY_TRY(sink->host_buffers(out_groups, n_aggregates, result));
   if (out_groups > result->group_capacity) return fail(HY_ERR_CAPACITY, "aggregate produces %u groups, capacity is %u", out_groups, result->group_capacity);
   if (result->mem != HY_MEM_HOST) return fail(HY_ERR_UNSUPPORTED, "aggregate results are returned in host memory (they are ordered on the host)");
   std::vector<hy_row_id> representative(out_groups, hy_row_id{0, 0});
@@ -3762,6 +3902,8 @@ hy_status HY_AGG_NEXT(hy_scan_project_aggregate)(const hy_filter* filters, uint3
                                                  const hy_fused_aggregate* aggregates, uint32_t n_aggregates, hy_aggregate_result* result);
 hy_status HY_AGG_NEXT(hy_aggregate_hash)(const hy_column* const* groupby_columns, uint32_t n_groupby, const hy_aggregate_spec* aggregates, uint32_t n_aggregates,
                                          hy_aggregate_result* result);
+hy_status HY_AGG_NEXT(hy_aggregate_hash_columns)(const hy_column* const* groupby_columns, uint32_t n_groupby, const hy_aggregate_spec* aggregates, uint32_t n_aggregates,
+                                                 uint32_t chunk_rows, hy_aggregate_columns* out);
 int HY_AGG_NEXT(hy_debug_aggregate_path)(void);
 int HY_AGG_NEXT(hy_debug_aggregate_finished_on_device)(void);
 int HY_AGG_NEXT(hy_debug_aggregate_small_domain)(void);
@@ -3855,6 +3997,98 @@ hy_status HY_AGG_ENTRY(hy_aggregate_hash)(const hy_column* const* groupby_column
     }
     return HY_OK;
   });
+}
+
+// hy_aggregate_hash's result as the columns of the output table, in device memory (include/hyrise_amd.h).
+hy_status HY_AGG_ENTRY(hy_aggregate_hash_columns)(const hy_column* const* groupby_columns, uint32_t n_groupby, const hy_aggregate_spec* aggregates,
+                                                  uint32_t n_aggregates, uint32_t chunk_rows, hy_aggregate_columns* out) {
+#ifdef HY_AGG_NEXT
+  {   // (as in hy_aggregate_hash: COUNT(DISTINCT x) takes one more key word)
+    uint32_t key_columns = n_groupby;
+    for (uint32_t i = 0; aggregates && i < n_aggregates; ++i) if (aggregates[i].function == HY_AGG_COUNT_DISTINCT) key_columns = n_groupby + 1;
+    g_last_aggregate_was_wide = key_columns > MAX_GROUPBY;
+    if (g_last_aggregate_was_wide) return HY_AGG_NEXT(hy_aggregate_hash_columns)(groupby_columns, n_groupby, aggregates, n_aggregates, chunk_rows, out);
+  }
+#endif
+  if (!out || (n_groupby && (!groupby_columns || !out->groupby_columns)) || (n_aggregates && (!aggregates || !out->aggregate_columns)))
+    return fail(HY_ERR_INVALID, "hy_aggregate_hash_columns: null argument");
+  out->n_groups = 0;
+  out->group_row_ids = nullptr;
+  for (uint32_t g = 0; g < n_groupby; ++g) out->groupby_columns[g] = nullptr;
+  for (uint32_t a = 0; a < n_aggregates; ++a) out->aggregate_columns[a] = nullptr;
+  if (!chunk_rows) return fail(HY_ERR_INVALID, "hy_aggregate_hash_columns: chunk_rows == 0");
+  for (uint32_t i = 0; i < n_groupby; ++i) HY_TRY(on_this_device(groupby_columns[i], "hy_aggregate_hash_columns"));
+  for (uint32_t i = 0; i < n_aggregates; ++i) HY_TRY(on_this_device(aggregates[i].column, "hy_aggregate_hash_columns"));
+  std::vector<const hy_column*> plain_groupby(groupby_columns, groupby_columns + n_groupby);   // run-length / bit-packed segments: the decoded twins
+  for (const hy_column*& column : plain_groupby) HY_TRY(plain_column(column, &column));
+  std::vector<hy_aggregate_spec> plain_aggregates(aggregates, aggregates + n_aggregates);
+  for (hy_aggregate_spec& spec : plain_aggregates) HY_TRY(plain_column(spec.column, &spec.column));
+
+  ColumnSink sink;
+  sink.chunk_rows = chunk_rows;
+  sink.columns = out->aggregate_columns;
+  std::vector<hy_aggregate_column> host_columns(std::max<uint32_t>(1, n_aggregates));
+  std::memset(host_columns.data(), 0, sizeof(hy_aggregate_column) * host_columns.size());
+  hy_aggregate_result host{};
+  host.mem = HY_MEM_HOST;
+  host.columns = host_columns.data();
+  hipStream_t stream = current_stream();
+  const hy_status status = [&]() -> hy_status {
+    uint32_t needed = 0;
+    for (uint32_t g = 0; g < n_aggregates; ++g) needed += plain_aggregates[g].function == HY_AGG_STDDEV_SAMP ? 2u : plain_aggregates[g].function == HY_AGG_COUNT_DISTINCT ? 0u : 1u;
+    if (needed <= MAX_AGGREGATES && n_aggregates <= MAX_AGGREGATES) {
+      HY_TRY(run_aggregate(plain_groupby.data(), n_groupby, plain_aggregates.data(), n_aggregates, &host, nullptr, &sink));
+    } else {   // several passes (hy_aggregate_hash): a group per input row is the most there can be (+ 1: no GROUP BY over an empty input)
+      const hy_column* shape = n_groupby ? groupby_columns[0] : nullptr;
+      for (uint32_t g = 0; g < n_aggregates && !shape; ++g) shape = aggregates[g].column;
+      if (!shape) return fail(HY_ERR_INVALID, "hy_aggregate_hash_columns needs at least one column");
+      if (shape->rows >= 0xFFFFFFFFull) return fail(HY_ERR_UNSUPPORTED, "hy_aggregate_hash_columns: %llu rows in several passes", static_cast<unsigned long long>(shape->rows));
+      HY_TRY(sink.host_buffers(static_cast<uint32_t>(shape->rows + 1), n_aggregates, &host));   // (allocated, not touched)
+      HY_TRY(HY_AGG_ENTRY(hy_aggregate_hash)(groupby_columns, n_groupby, aggregates, n_aggregates, &host));
+    }
+    if (!sink.finished) {   // finished on the host: one upload per column into the layout the device finish writes
+      const uint32_t n_groups = host.n_groups;
+      sink.n_groups = n_groups;
+      std::vector<char> image;
+      for (uint32_t a = 0; a < n_aggregates; ++a) {
+        ChunkedColumn chunked;
+        HY_TRY(chunked.alloc(host_columns[a].data_type, n_groups, chunk_rows));
+        image.assign(chunked.bytes(), 0);
+        const char* values = static_cast<const char*>(host_columns[a].values);
+        uint64_t* null_words = reinterpret_cast<uint64_t*>(image.data() + chunked.value_stride * chunked.n_chunks);
+        for (uint32_t k = 0; k < chunked.n_chunks; ++k) {
+          const uint64_t begin = uint64_t{k} * chunk_rows, size = std::min<uint64_t>(chunk_rows, n_groups - begin);
+          std::memcpy(image.data() + k * chunked.value_stride, values + begin * chunked.width, size * chunked.width);
+          for (uint64_t i = 0; i < size; ++i) if (host_columns[a].is_null[begin + i]) null_words[k * chunked.null_stride + i / 64] |= uint64_t{1} << (i % 64);
+        }
+        if (!image.empty()) HY_HIP(hipMemcpyAsync(chunked.arena, image.data(), image.size(), hipMemcpyHostToDevice, stream));
+        HY_HIP(hipStreamSynchronize(stream));   // (`image` is used again)
+        HY_TRY(chunked.adopt(&out->aggregate_columns[a]));
+      }
+      if (n_groups) {
+        HY_TRY(hy_result_pool_acquire(sizeof(hy_row_id) * uint64_t{n_groups}, reinterpret_cast<void**>(&sink.row_ids)));
+        HY_HIP(hipMemcpyAsync(sink.row_ids, host.group_row_ids, sizeof(hy_row_id) * size_t{n_groups}, hipMemcpyHostToDevice, stream));
+        HY_HIP(hipStreamSynchronize(stream));
+      }
+    }
+    // the GROUP BY columns at the representative rows (write_groupby_output): the RowIDs are read where they lie
+    for (uint32_t g = 0; g < n_groupby; ++g) {
+      if (g < 64 && (out->skip_groupby_mask >> g & 1)) continue;
+      const uint32_t type = groupby_columns[g]->data_type;
+      if (type < HY_TYPE_INT || type > HY_TYPE_DOUBLE || groupby_columns[g]->has_dictionary_without_values) continue;   // (what hy_column_gather refuses)
+      HY_TRY(hy_column_gather(groupby_columns[g], sink.row_ids, sink.n_groups, chunk_rows, &out->groupby_columns[g]));
+    }
+    return HY_OK;
+  }();
+  if (status != HY_OK) {   // nothing is left to the caller
+    for (uint32_t g = 0; g < n_groupby; ++g) { if (out->groupby_columns[g]) (void)hy_column_destroy(out->groupby_columns[g]); out->groupby_columns[g] = nullptr; }
+    for (uint32_t a = 0; a < n_aggregates; ++a) { if (out->aggregate_columns[a]) (void)hy_column_destroy(out->aggregate_columns[a]); out->aggregate_columns[a] = nullptr; }
+    (void)hy_result_pool_release(sink.row_ids);
+    return status;
+  }
+  out->n_groups = sink.n_groups;
+  out->group_row_ids = sink.row_ids;
+  return HY_OK;
 }
 
 // debug only: which path the last hy_aggregate_hash of this process took -- 0 aggregate_rows, else the partition bits; not part of the public header

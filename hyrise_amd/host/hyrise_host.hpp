@@ -242,6 +242,52 @@ class ValueSegment : public AbstractSegment {   // storage/value_segment.hpp:15-
   std::vector<uint64_t> _null_words;
 };
 
+// A value segment whose rows lie in HBM: chunk `chunk_index` of an hy_column an operator left there (hy_aggregate_hash_columns' output
+// columns).  The next operator takes the hy_column itself (device_column_of_chunks); code that indexes the segment gets a host copy of the
+// chunk, fetched once on first use -- DevicePosList's lazy copy, for values.  The hy_column dies with its last segment.
+struct DeviceColumnOwner {
+  explicit DeviceColumnOwner(hy_column* init) : handle(init) {}
+  DeviceColumnOwner(const DeviceColumnOwner&) = delete;
+  DeviceColumnOwner& operator=(const DeviceColumnOwner&) = delete;
+  ~DeviceColumnOwner() { if (handle) hy_column_destroy(handle); }
+  hy_column* handle;
+};
+// How many DeviceValueSegments have fetched their chunk to the host so far (tests: a chain that stays in HBM leaves it alone).
+inline std::atomic<uint64_t>& device_value_segment_fetches() { static std::atomic<uint64_t> fetches{0}; return fetches; }
+
+template <typename T>
+class DeviceValueSegment : public AbstractSegment {
+ public:
+  DeviceValueSegment(std::shared_ptr<const DeviceColumnOwner> owner, uint32_t chunk_index, ChunkOffset size)
+      : AbstractSegment(data_type_of<T>()), _owner(std::move(owner)), _chunk_index(chunk_index), _size(size) {}
+  ChunkOffset size() const override { return _size; }
+  const std::shared_ptr<const DeviceColumnOwner>& owner() const { return _owner; }
+  uint32_t chunk_index() const { return _chunk_index; }
+  const std::vector<T>& values() const { fetch(); return _values; }
+  const std::vector<uint64_t>& null_words() const { fetch(); return _null_words; }
+  AllTypeVariant operator[](ChunkOffset offset) const override {
+    fetch();
+    if ((_null_words[offset / 64] >> (offset % 64)) & 1) return NullValue{};
+    return _values[offset];
+  }
+
+ private:
+  void fetch() const {
+    std::call_once(_once, [&] {
+      _values.resize(_size);
+      _null_words.assign((size_t{_size} + 63) / 64, 0);
+      if (_size) check_status(hy_column_read_chunk(_owner->handle, _chunk_index, _values.data(), _null_words.data()));
+      device_value_segment_fetches().fetch_add(1, std::memory_order_relaxed);
+    });
+  }
+  std::shared_ptr<const DeviceColumnOwner> _owner;
+  uint32_t _chunk_index;
+  ChunkOffset _size;
+  mutable std::once_flag _once;
+  mutable std::vector<T> _values;
+  mutable std::vector<uint64_t> _null_words;
+};
+
 // FixedWidthIntegerVector<u8/u16/u32> (fixed_width_integer_compressor.cpp:33-44)
 struct CompressedVector {
   uint32_t width = 4;
@@ -708,7 +754,8 @@ struct DeviceColumn {
   hy_column* handle = nullptr;
   std::vector<hy_segment> descriptors;
   std::vector<std::vector<int64_t>> key_names;   // string GROUP BY columns: AggregateKeyEntry names per chunk
-  ~DeviceColumn() { if (handle) hy_column_destroy(handle); }
+  std::shared_ptr<const DeviceColumnOwner> resident;   // `handle` is a column an operator left in HBM: its segments own it
+  ~DeviceColumn() { if (handle && !resident) hy_column_destroy(handle); }
 };
 
 // How a DictionarySegment<pmr_string> is presented to the device: the value ids alone (scans), or with a dictionary of int64
@@ -795,12 +842,23 @@ inline void describe_pos_list(const AbstractPosList& pos_list, hy_segment& d, si
   }
 }
 
+// The hy_column whose consecutive chunks 0 .. n - 1 ARE the segments [chunk_begin, chunk_end) of the column (an operator's device-resident
+// output read as a whole), or nullptr: a mixed or partial range is fetched and described like any ValueSegment.  The handle lives on the
+// device of the thread that ran the operator: a worker bound to another GPU (multi_gpu.hpp) asks for chunk ranges of its own shard, which are
+// partial and take the fetched path; the whole column of another device's operator is refused by the library (on_this_device).
+inline std::shared_ptr<const DeviceColumnOwner> resident_column_of_chunks(const Table& table, ColumnID column_id, ChunkID chunk_begin, ChunkID chunk_end);
+
 // The chunks [chunk_begin, chunk_end) of one column on the CALLING THREAD's device (not cached: the residency cache of a table holds
 // whole columns on the process's device; the shards of a DeviceGroup worker, multi_gpu.hpp, belong to that worker).
 inline std::shared_ptr<DeviceColumn> device_column_of_chunks(const std::shared_ptr<const Table>& table, ColumnID column_id, StringKeys string_keys, ChunkID chunk_begin,
                                                              ChunkID chunk_end) {
   auto column = std::make_shared<DeviceColumn>();
   const auto chunk_count = chunk_end - chunk_begin;
+  if (const auto resident = resident_column_of_chunks(*table, column_id, chunk_begin, chunk_end)) {   // every chunk of one hy_column in HBM: that handle, as it is
+    column->resident = resident;
+    column->handle = resident->handle;
+    return column;
+  }
   column->descriptors.assign(chunk_count, hy_segment{});
   column->key_names.resize(chunk_count);
   std::map<std::string, int64_t> long_strings;
@@ -843,7 +901,17 @@ inline std::shared_ptr<DeviceColumn> device_column_of_chunks(const std::shared_p
       d.aux = typed->dictionary().data(); d.aux_size = typed->unique_values_count();
       ok = true;
     };
+    const auto describe_fetched = [&](auto* typed) {   // a chunk of a device-resident column on its own: through its host copy
+      using T = std::decay_t<decltype(typed->values()[0])>;
+      d.encoding = HY_ENC_UNENCODED; d.width = sizeof(T); d.data = typed->values().data();
+      d.nulls = typed->null_words().data();
+      ok = true;
+    };
     if (const auto* s = dynamic_cast<const ValueSegment<int32_t>*>(segment.get())) describe_value(s);
+    else if (const auto* s = dynamic_cast<const DeviceValueSegment<int32_t>*>(segment.get())) describe_fetched(s);
+    else if (const auto* s = dynamic_cast<const DeviceValueSegment<int64_t>*>(segment.get())) describe_fetched(s);
+    else if (const auto* s = dynamic_cast<const DeviceValueSegment<float>*>(segment.get())) describe_fetched(s);
+    else if (const auto* s = dynamic_cast<const DeviceValueSegment<double>*>(segment.get())) describe_fetched(s);
     else if (const auto* s = dynamic_cast<const ValueSegment<int64_t>*>(segment.get())) describe_value(s);
     else if (const auto* s = dynamic_cast<const ValueSegment<float>*>(segment.get())) describe_value(s);
     else if (const auto* s = dynamic_cast<const ValueSegment<double>*>(segment.get())) describe_value(s);
@@ -893,6 +961,26 @@ inline std::shared_ptr<DeviceColumn> device_column_of_chunks(const std::shared_p
   }
   check_status(hy_column_create(column->descriptors.data(), chunk_count, device_lists && !host_lists ? HY_MEM_DEVICE : HY_MEM_HOST, &column->handle));
   return column;
+}
+
+inline std::shared_ptr<const DeviceColumnOwner> resident_column_of_chunks(const Table& table, ColumnID column_id, ChunkID chunk_begin, ChunkID chunk_end) {
+  std::shared_ptr<const DeviceColumnOwner> owner;
+  for (ChunkID k = chunk_begin; k < chunk_end; ++k) {
+    const auto* segment = table.get_chunk(k)->get_segment(column_id).get();
+    std::shared_ptr<const DeviceColumnOwner> of_segment;
+    uint32_t index = 0;
+    const auto look = [&](auto* typed) { if (typed) { of_segment = typed->owner(); index = typed->chunk_index(); } };
+    look(dynamic_cast<const DeviceValueSegment<int32_t>*>(segment));
+    look(dynamic_cast<const DeviceValueSegment<int64_t>*>(segment));
+    look(dynamic_cast<const DeviceValueSegment<float>*>(segment));
+    look(dynamic_cast<const DeviceValueSegment<double>*>(segment));
+    if (!of_segment || index != k - chunk_begin || (owner && owner != of_segment)) return nullptr;
+    owner = of_segment;
+  }
+  if (!owner) return nullptr;
+  uint32_t chunks_of_column = 0;
+  check_status(hy_column_chunk_count(owner->handle, &chunks_of_column));
+  return chunks_of_column == chunk_end - chunk_begin ? owner : nullptr;
 }
 
 inline std::shared_ptr<DeviceColumn> device_column(const std::shared_ptr<const Table>& table, ColumnID column_id, StringKeys string_keys) {
@@ -2111,6 +2199,7 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
       lone_spec.column = keep.back()->handle;
       call_specs.push_back(lone_spec);
     }
+    if (device_resident_results()) return resident_output(*input, groupby, specs, call_specs);
     // Room for a group per input row, as the one call may need -- but not TOUCHED: value-initialised vectors of that size were 0.8 GB of page
     // faults (a quarter of a second) in front of an aggregate over 26 M joined rows that produces three groups.
     const uint32_t capacity = static_cast<uint32_t>(input->row_count() + 1);
@@ -2132,15 +2221,9 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
     check_status(hy_aggregate_hash(groupby.data(), static_cast<uint32_t>(groupby.size()), call_specs.data(), static_cast<uint32_t>(call_specs.size()), &result));
     // ---- output (aggregate_hash.cpp:1301-1361): GROUP BY columns reference the input through the representative
     // rows, aggregate columns are ValueSegments; here both are materialised into one Data table of value segments.
-    TableColumnDefinitions definitions;
-    for (const auto id : _groupby) definitions.push_back(input->column_definitions()[id]);
-    static const char* names[] = {"MIN", "MAX", "SUM", "AVG", "COUNT", "COUNT DISTINCT", "STDDEV_SAMP", "ANY"};
-    for (size_t a = 0; a < specs.size(); ++a) {
-      const auto& aggregate = _aggregates[a];
-      const std::string argument = aggregate.column_id == INVALID_COLUMN_ID ? "*" : input->column_name(aggregate.column_id);
-      const bool needs_null = aggregate.function != WindowFunction::Count && aggregate.function != WindowFunction::CountDistinct;
-      definitions.push_back({std::string(names[static_cast<int>(aggregate.function)]) + "(" + argument + ")", static_cast<DataType>(columns[a].data_type), needs_null});
-    }
+    std::vector<DataType> result_types;
+    for (size_t a = 0; a < specs.size(); ++a) result_types.push_back(static_cast<DataType>(columns[a].data_type));
+    const TableColumnDefinitions definitions = output_definitions(*input, result_types);
     auto output = std::make_shared<Table>(definitions, TableType::Data, Chunk::DEFAULT_SIZE);
     for (uint32_t g = 0; g < result.n_groups; ++g) {
       std::vector<AllTypeVariant> row;
@@ -2158,6 +2241,94 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
     }
     output->finalize();
     return output;
+  }
+
+  // aggregate_hash.cpp:1301-1361: the GROUP BY columns' definitions, then "FUNCTION(argument)" per aggregate with the given result type
+  TableColumnDefinitions output_definitions(const Table& input, const std::vector<DataType>& result_types) const {
+    TableColumnDefinitions definitions;
+    for (const auto id : _groupby) definitions.push_back(input.column_definitions()[id]);
+    for (size_t a = 0; a < result_types.size(); ++a) {
+      const auto& aggregate = _aggregates[a];
+      const std::string argument = aggregate.column_id == INVALID_COLUMN_ID ? "*" : input.column_name(aggregate.column_id);
+      const bool needs_null = aggregate.function != WindowFunction::Count && aggregate.function != WindowFunction::CountDistinct;
+      definitions.push_back({std::string(function_name(aggregate.function)) + "(" + argument + ")", result_types[a], needs_null});
+    }
+    return definitions;
+  }
+  static const char* function_name(WindowFunction function) {
+    static const char* names[] = {"MIN", "MAX", "SUM", "AVG", "COUNT", "COUNT DISTINCT", "STDDEV_SAMP", "ANY"};
+    return names[static_cast<int>(function)];
+  }
+
+  // The output table in HBM (hy_aggregate_hash_columns): same column definitions and chunking as the host path below builds cell by cell, the
+  // numeric segments DeviceValueSegments over the library's output columns -- the next operator's device_column() hands the handles on.
+  // String GROUP BY columns (passed as key names: the library makes no column for them) are read on the host through the representative rows.
+  std::shared_ptr<const Table> resident_output(const Table& input, const std::vector<const hy_column*>& groupby, const std::vector<hy_aggregate_spec>& specs,
+                                               const std::vector<hy_aggregate_spec>& call_specs) const {
+    std::vector<hy_column*> aggregate_handles(std::max<size_t>(1, call_specs.size()), nullptr), groupby_handles(std::max<size_t>(1, groupby.size()), nullptr);
+    hy_aggregate_columns result{};
+    for (size_t g = 0; g < _groupby.size() && g < 64; ++g) if (input.column_data_type(_groupby[g]) == DataType::String) result.skip_groupby_mask |= uint64_t{1} << g;
+    result.aggregate_columns = aggregate_handles.data();
+    result.groupby_columns = groupby_handles.data();
+    check_status(hy_aggregate_hash_columns(groupby.data(), static_cast<uint32_t>(groupby.size()), call_specs.data(), static_cast<uint32_t>(call_specs.size()), Chunk::DEFAULT_SIZE, &result));
+    // (owners first: whatever throws below, every handle and the RowIDs are given back)
+    const auto row_ids = std::make_shared<DeviceBlock>(result.group_row_ids);
+    std::vector<std::shared_ptr<const DeviceColumnOwner>> groupby_owners, aggregate_owners;
+    for (size_t g = 0; g < groupby.size(); ++g) groupby_owners.push_back(groupby_handles[g] ? std::make_shared<const DeviceColumnOwner>(groupby_handles[g]) : nullptr);
+    for (size_t a = 0; a < call_specs.size(); ++a) aggregate_owners.push_back(std::make_shared<const DeviceColumnOwner>(aggregate_handles[a]));
+
+    // the result types are the handles' (a column without chunks has none: window_function_traits.hpp:11-77, as the library types them)
+    std::vector<DataType> result_types;
+    for (size_t a = 0; a < specs.size(); ++a) {
+      const auto& aggregate = _aggregates[a];
+      DataType type = aggregate.column_id == INVALID_COLUMN_ID ? DataType::Long : input.column_data_type(aggregate.column_id);
+      const bool is_float = type == DataType::Float || type == DataType::Double;
+      if (aggregate.function == WindowFunction::Count || aggregate.function == WindowFunction::CountDistinct) type = DataType::Long;
+      else if (aggregate.function == WindowFunction::Avg || aggregate.function == WindowFunction::StandardDeviationSample) type = DataType::Double;
+      else if (aggregate.function == WindowFunction::Sum) type = is_float ? DataType::Double : DataType::Long;
+      if (result.n_groups) type = static_cast<DataType>(hy_column_data_type(aggregate_handles[a]));
+      result_types.push_back(type);
+    }
+    TableColumnDefinitions definitions = output_definitions(input, result_types);
+    for (size_t g = 0; g < groupby.size(); ++g) {
+      if (groupby_handles[g] && result.n_groups) Assert(static_cast<DataType>(hy_column_data_type(groupby_handles[g])) == definitions[g].data_type, "AggregateHash: a gathered GROUP BY column has another type than its input column");
+    }
+    const uint64_t n_groups = result.n_groups;
+    const RowID* rows = nullptr;   // the representative rows on the host: only where a GROUP BY column has to be read through them
+    const auto host_rows = [&] {
+      if (!rows) { row_ids->prefetch_to_host(n_groups); rows = row_ids->host_copy(); }
+      return rows;
+    };
+    const auto resident_segment = [](DataType type, const std::shared_ptr<const DeviceColumnOwner>& owner, uint32_t chunk, ChunkOffset size) -> std::shared_ptr<AbstractSegment> {
+      switch (type) {
+        case DataType::Int: return std::make_shared<DeviceValueSegment<int32_t>>(owner, chunk, size);
+        case DataType::Long: return std::make_shared<DeviceValueSegment<int64_t>>(owner, chunk, size);
+        case DataType::Float: return std::make_shared<DeviceValueSegment<float>>(owner, chunk, size);
+        default: return std::make_shared<DeviceValueSegment<double>>(owner, chunk, size);
+      }
+    };
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    for (uint64_t begin = 0; begin < n_groups; begin += Chunk::DEFAULT_SIZE) {
+      const auto chunk = static_cast<uint32_t>(begin / Chunk::DEFAULT_SIZE);
+      const auto size = static_cast<ChunkOffset>(std::min<uint64_t>(Chunk::DEFAULT_SIZE, n_groups - begin));
+      Segments segments;
+      for (size_t g = 0; g < _groupby.size(); ++g) {
+        const auto& definition = definitions[g];
+        if (groupby_owners[g]) { segments.push_back(resident_segment(definition.data_type, groupby_owners[g], chunk, size)); continue; }
+        std::vector<std::vector<AllTypeVariant>> cells;
+        for (uint64_t r = begin; r < begin + size; ++r) cells.push_back({(*input.get_chunk(host_rows()[r].chunk_id)->get_segment(_groupby[g]))[host_rows()[r].chunk_offset]});
+        switch (definition.data_type) {
+          case DataType::Int: segments.push_back(make_value_segment<int32_t>(cells, ColumnID{0}, definition.nullable)); break;
+          case DataType::Long: segments.push_back(make_value_segment<int64_t>(cells, ColumnID{0}, definition.nullable)); break;
+          case DataType::Float: segments.push_back(make_value_segment<float>(cells, ColumnID{0}, definition.nullable)); break;
+          case DataType::Double: segments.push_back(make_value_segment<double>(cells, ColumnID{0}, definition.nullable)); break;
+          default: segments.push_back(make_value_segment<std::string>(cells, ColumnID{0}, definition.nullable)); break;
+        }
+      }
+      for (size_t a = 0; a < specs.size(); ++a) segments.push_back(resident_segment(definitions[_groupby.size() + a].data_type, aggregate_owners[a], chunk, size));
+      chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+    }
+    return std::make_shared<Table>(std::move(definitions), TableType::Data, std::move(chunks));
   }
 
  private:

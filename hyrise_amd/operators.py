@@ -353,6 +353,66 @@ def aggregate_hash(groupby_columns, aggregates, group_capacity=None, result=None
     return result
 
 
+class GroupRowIds:
+    """The representative rows of hy_aggregate_hash_columns' groups: RowIDs in a block of the library's result-buffer pool (device memory),
+    owned by this object.  (pointer, rows) is what column_gather and the positions arguments take; numpy() copies them back."""
+
+    def __init__(self, pointer, rows):
+        self.lib = abi.load_library()
+        self.pointer, self.rows = pointer, int(rows)
+
+    def numpy(self):
+        out = np.zeros((self.rows, 2), dtype=np.uint32)
+        if self.rows:
+            abi.check(self.lib.hy_memcpy_d2h(out.ctypes.data, self.pointer, out.nbytes))
+        return out
+
+    def close(self):
+        if getattr(self, "pointer", None):
+            self.lib.hy_result_pool_release(self.pointer)
+            self.pointer = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AggregateColumnsResult:
+    """hy_aggregate_hash_columns' output table in device memory: .aggregates[a] and .groupby[g] are ResultColumns (groupby[g] is None where
+    the library made no column: a string column passed as key names), .row_ids the GroupRowIds."""
+
+    def __init__(self, n_groups, groupby, aggregates, row_ids):
+        self.n_groups, self.groupby, self.aggregates, self.row_ids = n_groups, groupby, aggregates, row_ids
+
+    def column(self, a):
+        """Aggregate a as a list (None = NULL), like HostAggregateResult.column."""
+        values, nulls = self.aggregates[a].read()
+        return [None if nulls[i] else values[i].item() for i in range(self.n_groups)]
+
+
+def aggregate_hash_columns(groupby_columns, aggregates, chunk_rows=abi.CHUNK_DEFAULT_SIZE, key_name_columns=()):
+    """hy_aggregate_hash_columns: hy_aggregate_hash's result as device-resident columns of chunk_rows-row chunks.  aggregates as for
+    aggregate_hash; key_name_columns: indices of GROUP BY columns that hold stand-ins for strings (no output column is made for them: the
+    caller reads the strings through the representative rows)."""
+    lib = abi.load_library()
+    garr = (C.c_void_p * max(1, len(groupby_columns)))(*[c.handle for c in groupby_columns])
+    specs = (abi.AggregateSpec * max(1, len(aggregates)))()
+    for i, (function, column) in enumerate(aggregates):
+        specs[i].function = function
+        specs[i].column = column.handle if column is not None else None
+    out_aggregates = (C.c_void_p * max(1, len(aggregates)))()
+    out_groupby = (C.c_void_p * max(1, len(groupby_columns)))()
+    out = abi.AggregateColumns()
+    out.skip_groupby_mask = sum(1 << g for g in key_name_columns)
+    out.aggregate_columns, out.groupby_columns = out_aggregates, out_groupby
+    abi.check(lib.hy_aggregate_hash_columns(garr, len(groupby_columns), specs, len(aggregates), chunk_rows, C.byref(out)))
+    row_ids = GroupRowIds(out.group_row_ids, out.n_groups)
+    return AggregateColumnsResult(int(out.n_groups), [ResultColumn(C.c_void_p(out_groupby[g])) if out_groupby[g] else None for g in range(len(groupby_columns))],
+                                  [ResultColumn(C.c_void_p(out_aggregates[a])) for a in range(len(aggregates))], row_ids)
+
+
 def star_join_aggregate(dimensions, groupby, aggregates, group_capacity=4096, result=None):
     """hy_star_join_aggregate: the star join fact x dimensions -> GROUP BY -> aggregates as one call (csrc/plan.hip).
     dimensions: [(key column, filter column or None, predicate or None, fact foreign-key column)]; groupby: [(table, column)] with table 0 =

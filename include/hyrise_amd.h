@@ -605,6 +605,42 @@ typedef struct hy_aggregate_result {
 hy_status hy_aggregate_hash(const hy_column* const* groupby_columns, uint32_t n_groupby,
                             const hy_aggregate_spec* aggregates, uint32_t n_aggregates, hy_aggregate_result* result);
 
+/* ---- AggregateHash whose output table stays in HBM (aggregate_hash.cpp:248-293, 422-540, 1301-1361, 1375-1460) ----------------
+ * hy_aggregate_hash's result -- same groups, group order, values, NULL flags and representative rows as with HY_MEM_HOST on the same
+ * arguments, bit for bit: the same kernels compute them -- as the columns of the operator's output table, where the next operator reads
+ * them (a HAVING scan, Sort, a join): nothing but the group count comes to the host.
+ *   aggregate_columns[a]  one column per aggregate: unencoded value segments of the result type hy_aggregate_hash reports
+ *                         (window_function_traits.hpp), chunks of chunk_rows rows (the last one shorter; AggregateHash writes chunks of
+ *                         Chunk::DEFAULT_SIZE = 65 535, :248-293), every chunk with a null vector (bit i of word i / 64, tail bits zero;
+ *                         all zero for COUNT) -- hy_column_gather's layout: one pooled arena owned by the column, chunk values 256-byte
+ *                         aligned with 16 spare bytes.  hy_column_read_chunk copies a chunk back; the caller destroys every handle with
+ *                         hy_column_destroy.  Zero groups: columns of zero chunks.
+ *   groupby_columns[g]    GROUP BY column g at the representative rows (write_groupby_output, :422-540): hy_column_gather over
+ *                         group_row_ids, which never leave the device.  NULL where no column is made: bit g of skip_groupby_mask set (the
+ *                         caller's word for "these are stand-ins for strings -- AggregateKey names --, I materialise the strings from
+ *                         the RowIDs"), or a column hy_column_gather refuses.
+ *   group_row_ids         the representative rows, n_groups RowIDs in DEVICE memory taken from the result-buffer pool
+ *                         (hy_result_pool_acquire).  The CALLER owns the buffer and gives it back with hy_result_pool_release; NULL when
+ *                         there is no group.
+ * Two paths.  GROUP BY present, more than 4096 groups, only MIN / MAX / SUM / AVG / COUNT, fewer than 2^32 rows: the groups are ordered on
+ * the device and the finish kernels write RowIDs and cells straight into the buffers above.  Everything else -- up to 4096 groups,
+ * COUNT(DISTINCT), STDDEV_SAMP, ANY, no GROUP BY (over an empty input: the one row of NULLs / zero counts, :1422-1432), more aggregates
+ * than one pass has accumulators for -- is finished on the host as in hy_aggregate_hash and uploaded once into the same layout: such
+ * results are small, or rare where they are large.  (More aggregates than one pass holds: the passes write host arrays sized by the input's
+ * rows, not by the groups -- that path costs in proportion to the input.)
+ * More than sixteen GROUP BY columns: HY_ERR_UNSUPPORTED, like hy_aggregate_hash.  On any error no handle and no buffer is left to the
+ * caller (everything in `out` is NULL / 0).  Returns when the columns are complete. */
+typedef struct hy_aggregate_columns {
+  uint64_t skip_groupby_mask;      /* in: bit g set = no output column for GROUP BY column g                                */
+  uint32_t n_groups;               /* out */
+  uint32_t reserved;
+  hy_column** aggregate_columns;   /* out: [n_aggregates], the caller's array (may be NULL when n_aggregates == 0)          */
+  hy_column** groupby_columns;     /* out: [n_groupby], the caller's array (may be NULL when n_groupby == 0)                */
+  hy_row_id* group_row_ids;        /* out: device memory of the result-buffer pool, owned by the caller                     */
+} hy_aggregate_columns;
+hy_status hy_aggregate_hash_columns(const hy_column* const* groupby_columns, uint32_t n_groupby, const hy_aggregate_spec* aggregates,
+                                    uint32_t n_aggregates, uint32_t chunk_rows, hy_aggregate_columns* out);
+
 /* ---- fused TableScan(s) -> Projection -> AggregateHash over ONE data table --------------------
  * The plan shape of TPC-H Q1 / Q6 (tpch_queries.cpp:60-80, 206-210): a chain of ColumnVsValue / Between / IsNull / LIKE scans
  * on columns of one table (table_scan.cpp:97-240), a Projection of arithmetic expressions over the survivors
