@@ -82,6 +82,12 @@ class JoinStatus(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class SortMergeResult(C.Structure):
+    """hy_sort_merge_result: hy_join_sort_merge's two lists -- the matched pairs, then the unmatched left rows, then the unmatched right rows."""
+    _fields_ = [("mem", C.c_uint32), ("reserved", C.c_uint32), ("left_pos", C.c_void_p), ("right_pos", C.c_void_p), ("capacity", C.c_uint64),
+                ("n_pairs", C.c_uint64), ("n_matched", C.c_uint64), ("n_left_outer", C.c_uint64)]
+
+
 class JoinPredicate(C.Structure):
     """hy_join_predicate: left_column <condition> right_column, evaluated on the pairs the primary equality finds."""
     _fields_ = [("left_column", C.c_void_p), ("right_column", C.c_void_p), ("condition", C.c_uint32), ("reserved", C.c_uint32)]
@@ -216,6 +222,8 @@ SYMBOLS = [
     ("hy_join_hash_predicates", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(JoinPredicate), C.c_uint32, C.POINTER(JoinResult)]),
     ("hy_join_hash_radix_bits", C.c_int32, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
     ("hy_join_hash_count", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("hy_join_sort_merge", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(SortMergeResult)]),
+    ("hy_join_sort_merge_count", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("hy_aggregate_hash", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
                                       C.POINTER(AggregateResult)]),
     ("hy_aggregate_hash_columns", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32,

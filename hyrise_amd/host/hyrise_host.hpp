@@ -531,9 +531,13 @@ class Table : public std::enable_shared_from_this<Table> {   // storage/table.hp
       }
     return rows;
   }
+  // table.hpp: every value of these columns lies in one chunk only (JoinSortMerge's Inner + Equals output, join_sort_merge.cpp:940-958)
+  const std::vector<ColumnID>& value_clustered_by() const { return _value_clustered_by; }
+  void set_value_clustered_by(std::vector<ColumnID> columns) { _value_clustered_by = std::move(columns); }
   mutable std::shared_ptr<ColumnCache> device_columns;
 
  private:
+  std::vector<ColumnID> _value_clustered_by;
   TableColumnDefinitions _definitions;
   TableType _type;
   ChunkOffset _target_chunk_size;
@@ -1742,8 +1746,6 @@ class JoinHash : public AbstractReadOnlyOperator {   // operators/join_hash.hpp:
     std::vector<std::vector<const AbstractPosList*>> _lists;
   };
 
- private:
-
   // write_output_segments (join_output_writing.cpp:95-200): reference inputs are dereferenced through their pos lists.
   static void append_side(Segments& segments, const std::shared_ptr<const Table>& input, std::vector<RowID> positions) {
     if (input->type() == TableType::Data) {
@@ -1765,9 +1767,131 @@ class JoinHash : public AbstractReadOnlyOperator {   // operators/join_hash.hpp:
     }
   }
 
+ private:
   JoinMode _mode;
   ColumnIDPair _column_ids;
   std::optional<size_t> _radix_bits;
+  std::vector<OperatorJoinPredicate> _secondary_predicates;
+};
+
+// What the join operators' supports() read of a join (operators/abstract_join_operator.hpp:18-41).
+struct JoinConfiguration {
+  JoinMode join_mode;
+  PredicateCondition predicate_condition;
+  DataType left_data_type, right_data_type;
+  bool secondary_predicates;
+};
+
+// JoinSortMerge (operators/join_sort_merge.hpp): the join the translator takes where JoinHash does not apply -- a primary predicate <, <=, >,
+// >= or <>, or FullOuter (lqp_translator.cpp:389-410) -- as ONE hy_join_sort_merge call.  Its two lists stay in pooled blocks of HBM; the
+// output's PosLists are views into them (a data input) or into the blocks hy_poslist_gather dereferences them into (a reference input:
+// JoinHash's DeviceSide).  The matched pairs, the unmatched left rows and the unmatched right rows each start a new output chunk, and inside
+// a part a chunk holds Chunk::DEFAULT_SIZE pairs.  The order of the rows is the library's contract (include/hyrise_amd.h), not the
+// reference's, whose order depends on its cluster count: the tables agree as multisets of rows.  What the library refuses -- strings, key
+// columns of different types, Semi / Anti / Cross, <> with an outer mode -- and joins with secondary predicates stay on the stock operator.
+class JoinSortMerge : public AbstractReadOnlyOperator {
+ public:
+  JoinSortMerge(std::shared_ptr<const AbstractOperator> left, std::shared_ptr<const AbstractOperator> right, JoinMode mode, OperatorJoinPredicate primary_predicate,
+                std::vector<OperatorJoinPredicate> secondary_predicates = {})
+      : AbstractReadOnlyOperator(std::move(left), std::move(right)), _mode(mode), _primary_predicate(primary_predicate), _secondary_predicates(std::move(secondary_predicates)) {}
+  const std::string& name() const override { static const std::string n = "JoinSortMerge"; return n; }
+  // join_sort_merge.cpp:43-47
+  static bool supports(const JoinConfiguration& config) {
+    return (config.predicate_condition != PredicateCondition::NotEquals || config.join_mode == JoinMode::Inner) && config.left_data_type == config.right_data_type &&
+           config.join_mode != JoinMode::Semi && config.join_mode != JoinMode::AntiNullAsTrue && config.join_mode != JoinMode::AntiNullAsFalse;
+  }
+  uint64_t n_matched = 0, n_left_outer = 0;   // the output's three parts: matched pairs, unmatched left rows, then the unmatched right rows
+
+ protected:
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto left = left_input_table(), right = right_input_table();
+    Assert(_secondary_predicates.empty(), "JoinSortMerge: joins with secondary predicates are not run on the device");
+    const auto ids = _primary_predicate.column_ids;
+    Assert(left->column_data_type(ids.first) != DataType::String && right->column_data_type(ids.second) != DataType::String, "JoinSortMerge: string keys are not run on the device");
+    const auto left_column = device_column(left, ids.first), right_column = device_column(right, ids.second);
+    // One call: room for one partner per row of the larger input; a join that needs more reports it with HY_ERR_CAPACITY (nothing written)
+    // and runs once more with exactly that.
+    uint64_t capacity = std::max<uint64_t>(1, std::max(left->row_count(), right->row_count()));
+    const bool on_device = device_resident_results();
+    std::vector<RowID> left_positions, right_positions;
+    std::shared_ptr<DeviceBlock> left_block, right_block;
+    hy_sort_merge_result result{};
+    for (int attempt = 0;; ++attempt) {
+      result = hy_sort_merge_result{};
+      result.capacity = capacity;
+      if (on_device) {
+        left_block.reset(); right_block.reset();   // (a second attempt: the first one's blocks go back first)
+        hy_row_id* l = nullptr;
+        hy_row_id* r = nullptr;
+        check_status(hy_result_pool_acquire_pair(capacity, &l, &r));
+        left_block = std::make_shared<DeviceBlock>(l);
+        right_block = std::make_shared<DeviceBlock>(r);
+        result.mem = HY_MEM_DEVICE;
+        result.left_pos = l;
+        result.right_pos = r;
+      } else {
+        left_positions.resize(capacity);
+        right_positions.resize(capacity);
+        result.mem = HY_MEM_HOST;
+        result.left_pos = reinterpret_cast<hy_row_id*>(left_positions.data());
+        result.right_pos = reinterpret_cast<hy_row_id*>(right_positions.data());
+      }
+      const auto status = hy_join_sort_merge(left_column->handle, right_column->handle, static_cast<uint32_t>(_mode), static_cast<uint32_t>(_primary_predicate.predicate_condition), &result);
+      if (status == HY_ERR_CAPACITY && attempt == 0 && result.n_pairs > capacity) {
+        capacity = result.n_pairs;
+        continue;
+      }
+      check_status(status);   // (HY_ERR_UNSUPPORTED included: there is no CPU implementation behind this class)
+      break;
+    }
+    n_matched = result.n_matched;
+    n_left_outer = result.n_left_outer;
+    TableColumnDefinitions definitions;
+    const bool left_nullable = _mode == JoinMode::Right || _mode == JoinMode::FullOuter, right_nullable = _mode == JoinMode::Left || _mode == JoinMode::FullOuter;
+    for (const auto& d : left->column_definitions()) definitions.push_back({d.name, d.data_type, d.nullable || left_nullable});
+    for (const auto& d : right->column_definitions()) definitions.push_back({d.name, d.data_type, d.nullable || right_nullable});
+    // the chunks: every part starts a new one
+    std::vector<std::pair<uint64_t, uint64_t>> cuts;
+    const uint64_t part_ends[3] = {result.n_matched, result.n_matched + result.n_left_outer, result.n_pairs};
+    for (uint64_t begin = 0, part = 0; part < 3; ++part) {
+      for (; begin < part_ends[part]; begin = std::min<uint64_t>(begin + Chunk::DEFAULT_SIZE, part_ends[part])) cuts.emplace_back(begin, std::min<uint64_t>(begin + Chunk::DEFAULT_SIZE, part_ends[part]));
+    }
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    if (on_device) {
+      JoinHash::DeviceSide left_side(left, left_block, result.n_pairs), right_side(right, right_block, result.n_pairs);
+      for (const auto& [begin, end] : cuts) {
+        Segments segments;
+        left_side.append(segments, begin, end);
+        right_side.append(segments, begin, end);
+        chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+      }
+    } else {
+      for (const auto& [begin, end] : cuts) {
+        Segments segments;
+        JoinHash::append_side(segments, left, std::vector<RowID>(left_positions.begin() + begin, left_positions.begin() + end));
+        JoinHash::append_side(segments, right, std::vector<RowID>(right_positions.begin() + begin, right_positions.begin() + end));
+        chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+      }
+    }
+    // join_sort_merge.cpp:940-958: an Inner equi-join's chunks are sorted by both join columns and no value lies in two clusters.  The order
+    // contract gives both: the pairs ascend by the left key, which is the right key.
+    const bool sorted_output = _mode == JoinMode::Inner && _primary_predicate.predicate_condition == PredicateCondition::Equals;
+    const ColumnID right_key = static_cast<ColumnID>(left->column_count() + ids.second);
+    if (sorted_output) {
+      for (const auto& chunk : chunks) {
+        chunk->set_immutable();
+        chunk->set_individually_sorted_by(std::vector<SortColumnDefinition>{SortColumnDefinition{ids.first, SortMode::AscendingNullsFirst}, SortColumnDefinition{right_key, SortMode::AscendingNullsFirst}});
+      }
+    }
+    auto output = std::make_shared<Table>(definitions, TableType::References, std::move(chunks));
+    // (clustered means no value in two chunks: pairs cut every Chunk::DEFAULT_SIZE rows keep that only while they are one chunk)
+    if (sorted_output && output->chunk_count() <= 1) output->set_value_clustered_by({ids.first, right_key});
+    return output;
+  }
+
+ private:
+  JoinMode _mode;
+  OperatorJoinPredicate _primary_predicate;
   std::vector<OperatorJoinPredicate> _secondary_predicates;
 };
 

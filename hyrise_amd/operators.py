@@ -650,6 +650,68 @@ def union_positions(left, right, force_sort=False, capacity=None):
     return out
 
 
+class SortMergePairs:
+    """hy_join_sort_merge's output: the two PosLists in blocks of the library's result-buffer pool (device memory; the next operator reads
+    them in place) -- n_matched pairs, then n_left_outer unmatched left rows, then the unmatched right rows.  numpy() copies both back."""
+
+    def __init__(self, capacity):
+        self.lib = abi.load_library()
+        self.capacity = int(capacity)
+        self.n_pairs = self.n_matched = self.n_left_outer = 0
+        left, right = C.c_void_p(), C.c_void_p()
+        abi.check(self.lib.hy_result_pool_acquire_pair(max(1, self.capacity), C.byref(left), C.byref(right)))
+        self.left_pointer, self.right_pointer = left.value, right.value
+
+    def numpy(self):
+        left, right = np.zeros((self.n_pairs, 2), dtype=np.uint32), np.zeros((self.n_pairs, 2), dtype=np.uint32)
+        if self.n_pairs:
+            abi.check(self.lib.hy_memcpy_d2h(left.ctypes.data, self.left_pointer, left.nbytes))
+            abi.check(self.lib.hy_memcpy_d2h(right.ctypes.data, self.right_pointer, right.nbytes))
+        return left, right
+
+    def close(self):
+        for name in ("left_pointer", "right_pointer"):
+            pointer = getattr(self, name, None)
+            if pointer:
+                self.lib.hy_result_pool_release(pointer)
+                setattr(self, name, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def join_sort_merge_count(left, right, mode, condition):
+    lib = abi.load_library()
+    n = C.c_uint64(0)
+    abi.check(lib.hy_join_sort_merge_count(left.handle, right.handle, mode, condition, C.byref(n)))
+    return int(n.value)
+
+
+def join_sort_merge(left, right, mode, condition):
+    """hy_join_sort_merge: left <condition> right (abi.PRED_EQUALS .. PRED_GREATER_THAN_EQUALS) under abi.JOIN_INNER / LEFT / RIGHT /
+    FULL_OUTER -> SortMergePairs.  The lists are sized for one partner per row of the larger input; a join that needs more answers
+    HY_ERR_CAPACITY with what it needs (nothing written) and runs once more with exactly that."""
+    lib = abi.load_library()
+    capacity = max(1, left.rows, right.rows)
+    for attempt in (0, 1):
+        out = SortMergePairs(capacity)
+        result = abi.SortMergeResult()
+        result.mem, result.left_pos, result.right_pos, result.capacity = abi.MEM_DEVICE, out.left_pointer, out.right_pointer, out.capacity
+        status = lib.hy_join_sort_merge(left.handle, right.handle, mode, condition, C.byref(result))
+        if status == abi.ERR_CAPACITY and attempt == 0:
+            out.close()
+            capacity = int(result.n_pairs)
+            continue
+        if status != abi.OK:
+            out.close()
+        abi.check(status)
+        out.n_pairs, out.n_matched, out.n_left_outer = int(result.n_pairs), int(result.n_matched), int(result.n_left_outer)
+        return out
+
+
 def string_rank_column(segments, dictionaries):
     """A DictionarySegment<pmr_string> column (string_keys.encode_string_column) as a sort key: the same attribute vectors over dictionaries
     of the strings' ranks among all of the column's distinct strings in byte order (StringRanks) -> (HostColumn of int64, StringRanks)."""

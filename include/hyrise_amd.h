@@ -569,6 +569,44 @@ hy_status hy_join_hash_radix_bits(uint64_t build_rows, uint64_t probe_rows, uint
 /* Upper bound for result->capacity without running the join (Semi/Anti: probe rows; others: exact pair count). */
 hy_status hy_join_hash_count(const hy_column* left, const hy_column* right, uint32_t mode, uint64_t* n_pairs);
 
+/* ---- JoinSortMerge (replaces JoinSortMerge::_on_execute, join_sort_merge.cpp: the join the translator takes where JoinHash does not
+ * apply, lqp_translator.cpp:389-410 -- a non-equi primary predicate, or FULL OUTER) -------------------------------------------------------
+ * left <condition> right over two columns of the SAME numeric type (int, long, float, double), any encoding hy_sort reads, reference
+ * columns over host or device PosLists included.
+ *   mode       HY_JOIN_INNER, LEFT, RIGHT or FULL_OUTER
+ *   condition  HY_PRED_EQUALS, LESS_THAN, LESS_THAN_EQUALS, GREATER_THAN, GREATER_THAN_EQUALS; HY_PRED_NOT_EQUALS with HY_JOIN_INNER only
+ * A column without chunks (an input table without rows) carries no type and joins with any column.
+ * Everything else is HY_ERR_UNSUPPORTED and stays on the stock operator: Semi / Anti / Cross, <> with an outer mode, columns of different
+ * types, strings, 2^32 rows or more on one side.  Secondary predicates are not part of this call.
+ * A NULL key matches nothing.  Under LEFT / FULL_OUTER every left row without a partner (NULL keys included) appears once with right_pos =
+ * NULL_ROW_ID ({~0u, ~0u}, as hy_join_hash's outer modes write it); RIGHT / FULL_OUTER does the same for right rows.  float / double
+ * compare through hy_sort's order-preserving key, so -0.0 = +0.0.  NaN keys are outside the contract (the reference sorts them with
+ * std::sort, which is undefined behaviour).
+ * Order of the output -- the library's own contract; the reference's order depends on a cluster count derived from the row counts and on
+ * parallel jobs, and its tests compare unordered, so parity with the reference is on the multiset of pairs.  "Position" is the row number in
+ * the input column (chunk order, then offset); the written RowID is {chunk, offset} of the input table, as for hy_join_hash:
+ *   1. the n_matched pairs first: left rows in ascending key order, ties by left position;
+ *   2. under each left row its partners in ascending right key order, ties by right position;
+ *   3. for <>, the partners below the key first, then the partners above it;
+ *   4. then the n_left_outer unmatched left rows, by left position;
+ *   5. then the unmatched right rows, by right position.
+ * The result is a pure function of the inputs.  A result that does not fit `capacity` is HY_ERR_CAPACITY: nothing is written to left_pos /
+ * right_pos, and n_pairs, n_matched and n_left_outer report what is needed (the check happens after the counting passes and before any
+ * emitting kernel; hy_join_sort_merge_count runs exactly those passes).  mem = HY_MEM_DEVICE: the lists are device memory and stay in HBM
+ * for the next operator.  Returns when the lists are complete. */
+typedef struct hy_sort_merge_result {
+  uint32_t mem;            /* HY_MEM_HOST | HY_MEM_DEVICE */
+  uint32_t reserved;
+  hy_row_id* left_pos;     /* [capacity] RowIDs into the LEFT input, NULL_ROW_ID for an unmatched right row  */
+  hy_row_id* right_pos;    /* [capacity] RowIDs into the RIGHT input, NULL_ROW_ID for an unmatched left row  */
+  uint64_t capacity;
+  uint64_t n_pairs;        /* out: all rows written (or needed, with HY_ERR_CAPACITY) */
+  uint64_t n_matched;      /* out: the leading pairs that satisfy the predicate; the outer rows follow */
+  uint64_t n_left_outer;   /* out: unmatched left rows (after n_matched); the unmatched right rows follow them */
+} hy_sort_merge_result;
+hy_status hy_join_sort_merge(const hy_column* left, const hy_column* right, uint32_t mode, uint32_t condition, hy_sort_merge_result* result);
+hy_status hy_join_sort_merge_count(const hy_column* left, const hy_column* right, uint32_t mode, uint32_t condition, uint64_t* n_pairs);
+
 /* write_output_chunks' chunking of a join result (join_output_writing.cpp:245-296; JoinHash always allows the merge,
  * join_hash.cpp:563): one output chunk per non-empty PosList of slice_offsets[0 .. n_slices], after merging a PosList of fewer
  * than 1000 pairs with its successors while the sum stays below 4000.  chunk_offsets (room for n_slices + 1 values) receives
