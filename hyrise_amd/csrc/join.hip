@@ -3808,25 +3808,30 @@ static uint32_t flip_condition(uint32_t condition) {   // flip_predicate_conditi
   }
 }
 
-// Probed once per process (on the device hy_init selected): 0 unknown, 1 lane-ordered, 2 not.
+// Probed once per process (on the device hy_init selected): 0 unknown, 1 lane-ordered, 2 not.  HY_OPT_LDS_ORDERED_ATOMICS = 0 answers "not"
+// without the probe and leaves the verdict alone (the option set back to 1: the probed answer again).  g_lds_order_in_effect: the last answer.
 static std::atomic<int> g_lds_atomic_order{0};
+static std::atomic<int> g_lds_order_in_effect{0};
 static bool lds_atomics_are_lane_ordered(hipStream_t stream) {
+  if (!option(HY_OPT_LDS_ORDERED_ATOMICS)) {
+    g_lds_order_in_effect.store(2, std::memory_order_relaxed);
+    return false;
+  }
   int state = g_lds_atomic_order.load(std::memory_order_acquire);
   if (state == 0) {
     state = 2;
-    if (FIXED_JOIN_ORDERED_ATOMICS) {
-      uint32_t* failures = nullptr;
-      if (hipMalloc(reinterpret_cast<void**>(&failures), 4) == hipSuccess) {
-        uint32_t host = 1;
-        bool ok = hipMemsetAsync(failures, 0, 4, stream) == hipSuccess;
-        for (uint32_t seed = 0; ok && seed < 4; ++seed) hipLaunchKernelGGL(lds_atomic_order_probe, dim3(512), dim3(512), 0, stream, failures, seed);
-        ok = ok && hipMemcpyAsync(&host, failures, 4, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-        (void)hipFree(failures);
-        if (ok && host == 0) state = 1;
-      }
+    uint32_t* failures = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&failures), 4) == hipSuccess) {
+      uint32_t host = 1;
+      bool ok = hipMemsetAsync(failures, 0, 4, stream) == hipSuccess;
+      for (uint32_t seed = 0; ok && seed < 4; ++seed) hipLaunchKernelGGL(lds_atomic_order_probe, dim3(512), dim3(512), 0, stream, failures, seed);
+      ok = ok && hipMemcpyAsync(&host, failures, 4, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+      (void)hipFree(failures);
+      if (ok && host == 0) state = 1;
     }
     g_lds_atomic_order.store(state, std::memory_order_release);
   }
+  g_lds_order_in_effect.store(state, std::memory_order_relaxed);
   return state == 1;
 }
 
@@ -4556,6 +4561,10 @@ hy_status hy_join_hash_radix_bits(uint64_t build_rows, uint64_t probe_rows, uint
 // debug / tests only: 0 = the last join of this thread probed the sorted directory, 1 = a rank table, 2 = a rank table whose ranks are row numbers
 // debug only: 1 if rt_probe_emit ranks with lane-ordered LDS atomics on this device, 2 if the probe said no, 0 before the first join
 int hy_debug_join_lane_ordered_atomics() { return g_lds_atomic_order.load(); }
+
+// debug / tests only: what lds_atomics_are_lane_ordered last answered in this process -- 1 ordered, 2 not (the probe's verdict, or
+// HY_OPT_LDS_ORDERED_ATOMICS = 0), 0 if no operator has asked yet
+int hy_debug_lds_order_in_effect(void) { return g_lds_order_in_effect.load(); }
 
 int hy_debug_join_used_rank_table(void) { return t_last_join_used_rank_table; }
 

@@ -297,7 +297,12 @@ enum {
                                       *      shape allows; 0 = one hy_join_hash per dimension                                                      */
   HY_OPT_STAR_FUSED_FINISH = 15,     /* 1    ... and groups the survivors where it finds them (star_finish) where every GROUP BY column and aggregate input
                                       *      is an int / long column: no RowIDs, exports, projection, hy_aggregate_hash; 0 = those four steps     */
-  HY_OPT_COUNT = 16
+  HY_OPT_LDS_ORDERED_ATOMICS = 16,  /* 1    the device decides (probed once per process) whether ranking rests on lane-ordered returning LDS atomics: the
+                                      *      staged sort of sort_pairs_u32 and of the join's build side, the sort-then-fill of unsorted unique build keys,
+                                      *      the PK-FK probe kernels, rt_probe_emit's one atomic per pair; 0 = tests: answer "not ordered" without
+                                      *      asking the device -- the paths a device without that order takes (sort_scatter, rank_table_mark ..
+                                      *      rank_table_scatter_rows, the general rank-table kernels, match-any ranking)                             */
+  HY_OPT_COUNT = 17
   /* (rounds 4-5 had 33: launch shapes and store flavours whose A/B timings were flat twice are constants now -- csrc/hy_options.hpp --,
    *  the radix-partitioned join path, which lost to the rank table read in place by 1.7 x, is gone) */
 };

@@ -37,6 +37,21 @@ def test_abi_version_and_struct_sizes():
     assert C.sizeof(abi.Value) == 8
 
 
+def test_option_names_of_abi_py_are_the_header_s_enum():
+    """Every HY_OPT_* of the header has its OPT_* in abi.py with the same number, there are exactly HY_OPT_COUNT of them on both sides,
+    and every named switch of abi.py sets one of them."""
+    text = open(os.path.join(ROOT, "include", "hyrise_amd.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    header = {name: int(value) for name, value in re.findall(r"\bHY_OPT_([A-Z0-9_]+)\s*=\s*(\d+)", text)}
+    count = header.pop("COUNT")
+    assert sorted(header.values()) == list(range(count)), "the header's options are not numbered 0 .. HY_OPT_COUNT - 1"
+    mirror = {name[4:]: value for name, value in vars(abi).items() if name.startswith("OPT_") and isinstance(value, int)}
+    assert len(mirror) == count, f"abi.py names {len(mirror)} options, HY_OPT_COUNT is {count}"
+    assert mirror == header, f"header and abi.py disagree: {set(header.items()) ^ set(mirror.items())}"
+    for switch, (option_id, _) in abi._SWITCHES.items():
+        assert 0 <= option_id < count, switch
+
+
 def test_calls_without_a_device_fail_loudly():
     """No GPU in the build container: the product path must say so instead of computing anything on the CPU."""
     import ctypes as C

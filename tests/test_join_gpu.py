@@ -723,25 +723,37 @@ def test_join_rank_table_falls_back(device, options):
     assert a.left[:a.n_pairs].tobytes() == b.left[:b.n_pairs].tobytes() and a.right[:a.n_pairs].tobytes() == b.right[:b.n_pairs].tobytes()
 
 
-def test_rank_table_join_with_and_without_lane_ordered_atomics(device):
+_lane_order_case = {}   # the host columns and the oracle's result, computed once for both settings
+
+
+@pytest.mark.parametrize("ordered", [1, 0])
+def test_rank_table_join_with_and_without_lane_ordered_atomics(device, options, ordered):
     """rt_probe_emit ranks the pairs of a partition inside a wave either with one returning LDS atomic per pair (where the device
     serves the lanes of one instruction in lane order -- probed once per process) or with match-any groups; both produce the
-    oracle's bytes.  The probe's verdict is reported."""
-    rng = np.random.default_rng(77)
-    build = np.arange(0, 400_000, dtype=np.int32) * 3
-    probe = np.sort(rng.integers(0, 1_200_000, 900_000).astype(np.int32))
-    lcol, rcol = build_column(build, None, 65_535, abi.ENC_UNENCODED), build_column(probe, None, 65_535, abi.ENC_FRAME_OF_REFERENCE)
-    left, right = DeviceColumn(lcol), DeviceColumn(rcol)
-    want = oracle_join(lcol, rcol, abi.JOIN_INNER)
+    oracle's bytes.  ordered = 1: the device decides; 0: HY_OPT_LDS_ORDERED_ATOMICS forces the match-any ranking (and the general
+    rank-table kernels in front of it).  The probe's verdict and the answer in effect are reported."""
+    if not _lane_order_case:
+        rng = np.random.default_rng(77)
+        build = np.arange(0, 400_000, dtype=np.int32) * 3
+        probe = np.sort(rng.integers(0, 1_200_000, 900_000).astype(np.int32))
+        lcol, rcol = build_column(build, None, 65_535, abi.ENC_UNENCODED), build_column(probe, None, 65_535, abi.ENC_FRAME_OF_REFERENCE)
+        _lane_order_case.update(lcol=lcol, rcol=rcol, want=oracle_join(lcol, rcol, abi.JOIN_INNER))
+    lcol, rcol, want = _lane_order_case["lcol"], _lane_order_case["rcol"], _lane_order_case["want"]
+    options.set(abi.OPT_LDS_ORDERED_ATOMICS, ordered)
+    left, right = DeviceColumn(lcol), DeviceColumn(rcol)   # (fresh: a build column keeps join hints, and one setting's must not feed the other)
     got = join_hash(left, right, abi.JOIN_INNER)
     assert used_rank_table() in (1, 2)
     n = want.n_pairs
     assert got.n_pairs == n and got.left[:n].tobytes() == want.left[:n].tobytes() and got.right[:n].tobytes() == want.right[:n].tobytes()
     lib = abi.load_library()
     lib.hy_debug_join_lane_ordered_atomics.restype = int
-    verdict = lib.hy_debug_join_lane_ordered_atomics()
-    assert verdict in (1, 2)
-    print("lane-ordered LDS atomics:", "yes" if verdict == 1 else "no (match-any ranking)")
+    lib.hy_debug_lds_order_in_effect.restype = int
+    verdict, in_effect = lib.hy_debug_join_lane_ordered_atomics(), lib.hy_debug_lds_order_in_effect()
+    assert verdict in (1, 2) or (ordered == 0 and verdict == 0)   # (0: this process has run under the forced setting only -- never probed)
+    assert in_effect == (verdict if ordered else 2)
+    if ordered == 0:
+        assert used_pkfk() == 0
+    print("lane-ordered LDS atomics:", "yes" if verdict == 1 else "no (match-any ranking)", "| in effect:", in_effect, "| ordered =", ordered)
 
 
 def test_shutdown_releases_the_thread_state_and_the_library_keeps_working(device):
