@@ -3964,6 +3964,11 @@ static hy_status run_join_once(const hy_column* left, const hy_column* right, ui
   if (result && result->radix_bits != 0xFFFFFFFFu) radix_bits = result->radix_bits;
   if (radix_bits > 8) return fail(HY_ERR_INVALID, "radix_bits %u > 8", radix_bits);
   const bool host_result = !result || result->mem == HY_MEM_HOST;
+  // The emitting kernels write the caller's device lists two pairs at a time (16-byte stores at even pair indices, rt_copy_out / pk_emit):
+  // lists off a 16-byte boundary, and slice offsets off an 8-byte one, are refused before anything is launched.
+  if (!host_result && !count_only &&
+      (reinterpret_cast<uintptr_t>(result->left_pos) % 16 != 0 || reinterpret_cast<uintptr_t>(result->right_pos) % 16 != 0 || reinterpret_cast<uintptr_t>(result->slice_offsets) % 8 != 0))
+    return fail(HY_ERR_INVALID, "hy_join_hash: a device-memory result needs left_pos / right_pos on 16-byte and slice_offsets on 8-byte boundaries");
 
   // build side; its Bloom filter is applied to the probe side only when the build side is materialised first
   const bool probe_filtered = build->rows < probe->rows && !keep_nulls_probe;   // join_hash.cpp:365-381

@@ -45,6 +45,10 @@ std::mutex g_mutex;
 std::vector<Block> g_blocks;
 std::vector<Pair> g_pairs;
 
+// Readable bytes behind what a caller asked for: a list handed on as an HY_MEM_DEVICE column must not end its allocation (include/hyrise_amd.h,
+// hy_column_create).  A fresh block has 0.75 MiB or more behind the request; a reused one is only taken if it keeps this much.
+constexpr size_t RESULT_SLACK = 16;
+
 int this_device() {
   bind_thread_device();
   int device = 0;
@@ -157,7 +161,7 @@ hy_status hy_result_pool_acquire(uint64_t bytes, void** ptr) {
   int best = -1;
   for (size_t i = 0; i < g_blocks.size(); ++i) {
     const Block& b = g_blocks[i];
-    if (!b.base || b.in_use || b.paired || b.device != device || b.usable < wanted || b.usable > 2 * wanted + (size_t{8} << 20)) continue;
+    if (!b.base || b.in_use || b.paired || b.device != device || b.usable < wanted + RESULT_SLACK || b.usable > 2 * wanted + (size_t{8} << 20)) continue;
     if (best < 0 || b.usable < g_blocks[best].usable) best = static_cast<int>(i);
   }
   if (best < 0) HY_TRY(new_block(wanted, 0, false, &best));
@@ -178,7 +182,7 @@ hy_status hy_result_pool_acquire_pair(uint64_t rows, hy_row_id** left, hy_row_id
     if (pair.dead()) continue;
     const Block& l = g_blocks[pair.left];
     const Block& r = g_blocks[pair.right];
-    if (l.in_use || r.in_use || l.device != device || l.usable < bytes || r.usable < bytes) continue;
+    if (l.in_use || r.in_use || l.device != device || l.usable < bytes + RESULT_SLACK || r.usable < bytes + RESULT_SLACK) continue;
     // calibrated pairs first (by rank); among the others the tightest fit.  A pair sized for SF10's 480 MB lists is not spent on a
     // result of a few rows unless it is all there is: small results take blocks of their own (below)
     if (l.usable > 4 * bytes + (size_t{64} << 20)) continue;

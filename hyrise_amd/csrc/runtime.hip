@@ -767,6 +767,35 @@ hy_status hy_column_create(const hy_segment* segments, uint32_t n_chunks, uint32
     for (uint32_t run = 0; run < s.aux_size && s.nulls; ++run) any_null = any_null || reinterpret_cast<const uint8_t*>(s.nulls)[run] != 0;
     if (!any_null) column->host_segments[c].nulls = nullptr;
   }
+  // The same decision for run flags in the caller's device memory: they are read back -- every chunk's bytes with one copy each, behind
+  // whatever the calling thread's stream still writes into them, ONE synchronisation for the column -- because without it IS NULL / IS NOT
+  // NULL scanned such a segment row by row and reported HY_CHUNK_SCANNED where the uploaded segment reports the early-out.
+  if (mem == HY_MEM_DEVICE) {
+    size_t flag_bytes = 0;
+    for (uint32_t c = 0; c < n_chunks; ++c) if (segments[c].encoding == HY_ENC_RUN_LENGTH && segments[c].nulls) flag_bytes += segments[c].aux_size;
+    if (flag_bytes) {
+      std::vector<uint8_t> flags(flag_bytes);
+      size_t at = 0;
+      for (uint32_t c = 0; c < n_chunks; ++c) {
+        const hy_segment& s = segments[c];
+        if (s.encoding != HY_ENC_RUN_LENGTH || !s.nulls || !s.aux_size) continue;
+        const hipError_t err = hipMemcpyAsync(flags.data() + at, s.nulls, s.aux_size, hipMemcpyDeviceToHost, current_stream());
+        if (err != hipSuccess) return cleanup(fail(HY_ERR_DEVICE, "chunk %u: reading the run flags failed: %s", c, hipGetErrorString(err)));
+        at += s.aux_size;
+      }
+      const hipError_t err = hipStreamSynchronize(current_stream());
+      if (err != hipSuccess) return cleanup(fail(HY_ERR_DEVICE, "reading the run flags failed: %s", hipGetErrorString(err)));
+      at = 0;
+      for (uint32_t c = 0; c < n_chunks; ++c) {
+        const hy_segment& s = segments[c];
+        if (s.encoding != HY_ENC_RUN_LENGTH || !s.nulls || !s.aux_size) continue;
+        bool any_null = false;
+        for (uint32_t run = 0; run < s.aux_size; ++run) any_null = any_null || flags[at + run] != 0;
+        if (!any_null) column->host_segments[c].nulls = nullptr;
+        at += s.aux_size;
+      }
+    }
+  }
   // LZ4 segments: decompressed on the device, ValueSegments from here on (their values are device memory already)
   std::vector<uint8_t> on_device(n_chunks, 0);
   bool any_lz4 = false;

@@ -1913,6 +1913,9 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
   if (!host_result && !(result->flags & HY_SCAN_CHUNK_REGIONS)) return fail(HY_ERR_INVALID, "scan result: device results use the chunk-region layout; set HY_SCAN_CHUNK_REGIONS");
   if (!host_result && result->capacity < column->rows) return fail(HY_ERR_CAPACITY, "scan result: chunk regions need capacity >= %llu rows", static_cast<unsigned long long>(column->rows));
   if (result->capacity && !result->matches) return fail(HY_ERR_INVALID, "scan result: matches buffer missing");
+  // scan_slices writes the regions two RowIDs at a time (16-byte stores at even RowID indices of `matches`): refused before any launch
+  if (!host_result && (reinterpret_cast<uintptr_t>(result->matches) % 16 != 0 || reinterpret_cast<uintptr_t>(result->offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(result->counts) % 4 != 0))
+    return fail(HY_ERR_INVALID, "scan result: a device-memory result needs matches on a 16-byte, offsets on an 8-byte and counts on a 4-byte boundary");
   hipStream_t stream = current_stream();
   Scratch& sc = scratch();
 

@@ -106,9 +106,33 @@ class Comm:
         self.dist.all_to_all_single(received, counts)
         recv_counts = [int(x) for x in received.cpu().tolist()]
         staged = self._in(send).contiguous()
-        out = torch.empty((sum(recv_counts),) + tuple(send.shape[1:]), dtype=send.dtype, device=staged.device)
+        out = empty_with_slack((sum(recv_counts),) + tuple(send.shape[1:]), send.dtype, staged.device)
         self.dist.all_to_all_single(out, staged, output_split_sizes=recv_counts, input_split_sizes=[int(c) for c in send_counts])
         return out.to(send.device), recv_counts
+
+
+SLACK_BYTES = 16   # readable bytes the library wants behind every buffer of an HY_MEM_DEVICE column (include/hyrise_amd.h, hy_column_create)
+
+
+def empty_with_slack(shape, dtype, device):
+    """torch.empty(shape) whose storage goes on for SLACK_BYTES behind the last element: handed on as a column, it does not end its allocation."""
+    import torch
+    shape = tuple(int(d) for d in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+    width = torch.empty(0, dtype=dtype).element_size()
+    count = int(np.prod(shape))
+    flat = torch.empty(count + (SLACK_BYTES + width - 1) // width, dtype=dtype, device=device)
+    return flat[:count].view(shape)
+
+
+def with_slack(tensor):
+    """`tensor` (contiguous) if its storage holds SLACK_BYTES behind its last element, else a copy that does (a caller's own tensor)."""
+    tensor = tensor.contiguous()
+    behind = tensor.untyped_storage().nbytes() - (tensor.storage_offset() + tensor.numel()) * tensor.element_size()
+    if behind >= SLACK_BYTES:
+        return tensor
+    out = empty_with_slack(tuple(tensor.shape), tensor.dtype, tensor.device)
+    out.copy_(tensor)
+    return out
 
 
 # ---- the per-rank executor over the C ABI ---------------------------------------------------------------------------------
@@ -118,6 +142,7 @@ class DeviceValueColumn:
 
     def __init__(self, lib, values, chunk_rows, data_type, null_bytes=None):
         import torch
+        values = with_slack(values)   # (the last chunk must not end the allocation)
         self.lib, self.values, self.data_type = lib, values, data_type
         self.rows = int(values.shape[0])
         width = values.element_size()
@@ -142,7 +167,7 @@ class DeviceValueColumn:
                 chunk_bits = torch.zeros(((end - begin + 63) // 64) * 64, dtype=torch.uint8, device=bits.device)
                 chunk_bits[:end - begin] = bits[begin:end]
                 weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=bits.device)
-                packed = (chunk_bits.view(-1, 8).to(torch.int32) * weights).sum(dim=1).to(torch.uint8).contiguous()
+                packed = with_slack((chunk_bits.view(-1, 8).to(torch.int32) * weights).sum(dim=1).to(torch.uint8))
                 self._null_chunks.append(packed)
                 s.nulls = packed.data_ptr()
         self._segments = segments
@@ -170,10 +195,10 @@ class DeviceReferenceColumn:
         import torch
         self.lib, self.base, self.data_type = lib, base, base.data_type
         if rows.shape[0] == 0:   # an empty table still has a type: one empty chunk
-            rows = torch.zeros((1, 2), dtype=torch.int32, device=rows.device)
+            rows = torch.zeros((3, 2), dtype=torch.int32, device=rows.device)[:1]
             self.rows = 0
         else:
-            rows = rows.contiguous()
+            rows = with_slack(rows)
             self.rows = int(rows.shape[0])
         self.pos = rows
         n_chunks = max(1, (self.rows + chunk_rows - 1) // chunk_rows)
@@ -214,7 +239,7 @@ class DevicePosLists:
     references -- or mixed when base_chunk[c] is INVALID_CHUNK_ID).  The counts are the only thing the host knows of it."""
 
     def __init__(self, rows, begin, count, base_chunk):
-        self.rows, self.begin, self.count, self.base_chunk = rows, begin, count, base_chunk
+        self.rows, self.begin, self.count, self.base_chunk = with_slack(rows), begin, count, base_chunk
         self.total = int(count.sum())
 
 
@@ -233,7 +258,7 @@ class DeviceChunkedReferenceColumn:
         table["encoding"], table["data_type"], table["width"] = abi.ENC_REFERENCE, base.data_type, 8
         table["ref"] = base.handle.value if isinstance(base.handle, C.c_void_p) else int(base.handle)
         if len(keep) == 0:   # an empty table still has a type: one empty chunk
-            self._empty = pos_lists.rows.new_zeros((1, 2))
+            self._empty = pos_lists.rows.new_zeros((3, 2))[:1]
             table["data"], table["ref_chunk_id"] = self._empty.data_ptr(), abi.INVALID_CHUNK_ID
         else:
             table["size"] = pos_lists.count[keep]
@@ -323,7 +348,7 @@ class HipExecutor:
         if layout == abi.POSLIST_CHUNK_REGIONS and visibility is None and not is_reference and _is_data_column(column):
             # a scan over a DATA table in the chunk-region layout already IS the output: chunk c's RowIDs of chunk c in its region
             return regions, offsets, counts, None
-        out = torch.empty((rows, 2), dtype=torch.int32, device=self.device)
+        out = empty_with_slack((rows, 2), torch.int32, self.device)
         written = C.c_uint64(0)
         abi.check(self.lib.hy_poslist_translate(column.handle, C.byref(result), layout, out.data_ptr(), rows, C.byref(written)))
         return out, offsets, counts, int(written.value)
@@ -370,7 +395,7 @@ class HipExecutor:
 
     def export(self, column, with_nulls=True):
         torch = self.torch
-        values = torch.empty(column.rows, dtype=self._types[column.data_type], device=self.device)
+        values = empty_with_slack(column.rows, self._types[column.data_type], self.device)
         nulls = torch.zeros(column.rows, dtype=torch.uint8, device=self.device) if with_nulls else None
         abi.check(self.lib.hy_column_export(column.handle, values.data_ptr(), nulls.data_ptr() if nulls is not None else None))
         return values, nulls
@@ -406,8 +431,8 @@ class HipExecutor:
         """-> (keys tensor, RowIDs [n, 2] int32, tuples per destination)"""
         torch = self.torch
         counts = (C.c_uint64 * parts)()
-        keys = torch.empty(max(1, column.rows), dtype=self._types[column.data_type], device=self.device)
-        rows = torch.empty((max(1, column.rows), 2), dtype=torch.int32, device=self.device)
+        keys = empty_with_slack(max(1, column.rows), self._types[column.data_type], self.device)
+        rows = empty_with_slack((max(1, column.rows), 2), torch.int32, self.device)
         abi.check(self.lib.hy_repartition_pack(column.handle, parts, first_chunk, keys.data_ptr(), rows.data_ptr(), column.rows, counts))
         abi.check(self.lib.hy_synchronize())
         per = [int(c) for c in counts]
@@ -416,7 +441,7 @@ class HipExecutor:
 
     def gather_row_ids(self, table, chunk_rows, positions):
         torch = self.torch
-        out = torch.empty_like(positions)
+        out = empty_with_slack(tuple(positions.shape), positions.dtype, positions.device)
         if positions.shape[0]:
             table = table.contiguous()
             abi.check(self.lib.hy_gather_row_ids(table.data_ptr(), table.shape[0], chunk_rows, positions.contiguous().data_ptr(), positions.shape[0], out.data_ptr()))

@@ -342,7 +342,32 @@ hy_status hy_comm_all_to_all_v(hy_comm* comm, const void* send, const uint64_t* 
  * mem == HY_MEM_DEVICE: pointers are device pointers and stay owned by the caller; the call does not wait for the device: the column's
  *                       descriptor tables are complete in the order of the calling thread's stream (every entry point this thread calls
  *                       afterwards sees them; another thread synchronises with this one first -- hy_synchronize -- like for the data
- *                       the pointers name). */
+ *                       the pointers name).  (One exception: a RunLength segment that comes with run null bytes -- the call reads them
+ *                       back behind the thread's stream, to drop them where no run is NULL, as it does for host memory.)
+ *   What a caller's device buffers must satisfy (tests/test_device_memory_columns_gpu.py runs every operator over buffers laid out to
+ *   these rules and no better):
+ *     alignment  every buffer on a multiple of its element size: `data` on `width` bytes (8 for a PosList and for the words of a
+ *                BitPackingVector), `aux` on the dictionary's type width / 4 bytes (block minima, run ends, begin commit ids), `nulls` on 8
+ *                bytes (a null bitmap), 4 (end commit ids) or 1 (the null bytes of a RunLength segment).  Nothing more is needed for a correct
+ *                result: a segment whose `data` is not on a 16-byte or whose bitmap is not on an 8-byte boundary is read row by row where the
+ *                arena's layout is read in groups of eight (scans, joins' dense materialise, the aggregates' plain 4-byte inputs, projections'
+ *                plain operands take their general paths).
+ *     slack      16 readable bytes behind the last element of every buffer -- what the library's own arena (HY_MEM_HOST) keeps: the last
+ *                partial group of eight rows is fetched with full vector loads.  Their contents are never used: they may be another buffer's.
+ *                A buffer must therefore not end its allocation.
+ *     results    (audited per entry point: the widest store made at an address derived from the caller's pointer)
+ *                hy_table_scan / hy_table_scan_columns / hy_validate, mem = HY_MEM_DEVICE: `matches` is written two RowIDs per 16-byte store at
+ *                  even RowID indices -> `matches` on 16 bytes, `offsets` on 8, `counts` on 4, `chunk_state` any; otherwise HY_ERR_INVALID
+ *                  before any launch.
+ *                hy_join_hash / _predicates / _finish, mem = HY_MEM_DEVICE: two pairs per 16-byte store at even pair indices -> `left_pos` and
+ *                  `right_pos` on 16 bytes, `slice_offsets` on 8; otherwise HY_ERR_INVALID before any launch.  (hy_result_pool_acquire_pair
+ *                  and hy_result_pool_acquire hand out such blocks, with the 16 bytes of slack behind what was asked for.)
+ *                hy_aggregate_hash / hy_scan_project_aggregate / hy_star_join_aggregate, mem = HY_MEM_DEVICE: copied into place (hipMemcpy):
+ *                  any address; sensibly RowIDs on 8, values on their width.
+ *                hy_sort / hy_sort_limit `out`: 16-byte stores where `out` is on 16 bytes, RowID by RowID otherwise -> 8.
+ *                hy_join_sort_merge lists, hy_union_positions `out`: RowID by RowID -> 8, checked (HY_ERR_INVALID, nothing written).
+ *                hy_poslist_translate `out`, hy_column_export: element by element -> element size.
+ *                hy_gather_row_ids / hy_poslist_gather `out`: 16-byte stores where positions and `out` are on 16 bytes, else RowID by RowID -> 8. */
 hy_status hy_column_create(const hy_segment* segments, uint32_t n_chunks, uint32_t mem, hy_column** out);
 hy_status hy_column_destroy(hy_column* column);
 hy_status hy_column_row_count(const hy_column* column, uint64_t* rows);
