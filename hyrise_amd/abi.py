@@ -60,6 +60,15 @@ class Predicate(C.Structure):
                 ("column_is_nullable", C.c_uint32), ("reserved", C.c_uint32), ("match_words", C.c_void_p), ("match_word_offsets", C.c_void_p)]
 
 
+MAX_IN_LIST = 256
+
+
+class InList(C.Structure):
+    """hy_in_list: the literal list of `column IN (...)` / `column NOT IN (...)` (hy_table_scan_in_list)."""
+    _fields_ = [("value_type", C.c_uint32), ("n_values", C.c_uint32), ("values", C.c_void_p), ("negated", C.c_uint32), ("column_is_nullable", C.c_uint32),
+                ("per_chunk_value_ids", C.c_void_p)]
+
+
 class ScanResult(C.Structure):
     _fields_ = [("mem", C.c_uint32), ("flags", C.c_uint32), ("matches", C.c_void_p), ("capacity", C.c_uint64),
                 ("offsets", C.c_void_p), ("counts", C.c_void_p), ("chunk_state", C.c_void_p),
@@ -209,6 +218,8 @@ SYMBOLS = [
     ("hy_column_row_count", C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("hy_column_chunk_count", C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("hy_table_scan", C.c_int32, [C.c_void_p, C.POINTER(Predicate), C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
+    ("hy_table_scan_in_list", C.c_int32, [C.c_void_p, C.POINTER(InList), C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
+    ("hy_in_list_cast", C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("hy_table_scan_columns", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_projection_arithmetic", C.c_int32, [C.c_uint32, C.POINTER(Operand), C.POINTER(Operand), C.POINTER(C.c_void_p)]),
     ("hy_column_read_chunk", C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),

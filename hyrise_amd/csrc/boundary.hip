@@ -157,6 +157,24 @@ hy_status hy_predicate_cast(uint32_t condition, uint32_t column_type, uint32_t l
   return HY_OK;
 }
 
+hy_status hy_in_list_cast(uint32_t column_type, const uint32_t* literal_types, const hy_value* literals, uint32_t n, hy_value* out, uint32_t* n_out,
+                          uint32_t* has_null) {
+  if (!n_out || !has_null || (n && (!literal_types || !literals || !out))) return fail(HY_ERR_INVALID, "hy_in_list_cast: null argument");
+  *n_out = 0;
+  *has_null = 0;
+  if (column_type < HY_TYPE_INT || column_type > HY_TYPE_DOUBLE) return fail(HY_ERR_INVALID, "hy_in_list_cast: a column of type %u takes no hy_value list", column_type);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (literal_types[i] == HY_TYPE_NULL) { *has_null = 1; continue; }
+    if (literal_types[i] > HY_TYPE_STRING) return fail(HY_ERR_INVALID, "hy_in_list_cast: literal %u has unknown type %u", i, literal_types[i]);
+    // `column = literal`: only a literal the column's type holds exactly can equal a row (lossless_predicate_cast.cpp:40-73)
+    const Cast cast = cast_variant(HY_PRED_EQUALS, literal_types[i], literals[i], column_type);
+    if (!cast.ok) continue;
+    if ((column_type == HY_TYPE_FLOAT && std::isnan(cast.value.f32)) || (column_type == HY_TYPE_DOUBLE && std::isnan(cast.value.f64))) continue;   // NaN == x holds for no x
+    out[(*n_out)++] = cast.value;
+  }
+  return HY_OK;
+}
+
 hy_status hy_join_output_chunks(const uint64_t* slice_offsets, uint32_t n_slices, uint64_t* chunk_offsets, uint32_t* n_chunks) {
   if (!slice_offsets || !chunk_offsets || !n_chunks) return fail(HY_ERR_INVALID, "hy_join_output_chunks: null argument");
   constexpr uint64_t MIN_SIZE = 1000, MAX_SIZE = 4 * MIN_SIZE;

@@ -10,7 +10,9 @@ enum : uint32_t { JOB_SCAN = 0, JOB_ALL = 1, JOB_NONE = 2,
                   JOB_RANGE = 3 /* a sorted chunk: the rows [range_begin, range_end) without [hole_begin, hole_end) match, nothing is read */ };
 enum : uint32_t { KIND_U32 = 0, KIND_I64 = 1, KIND_F32 = 2, KIND_F64 = 3, KIND_NULLTEST = 4,
                   KIND_VISIBLE = 5 /* Validate: lo = snapshot commit id, span = our transaction id */,
-                  KIND_VALUE_ID_SET = 6 /* LIKE family on dictionaries: lo = device address of the chunk's match bitmap */ };
+                  KIND_VALUE_ID_SET = 6 /* LIKE family, IN / NOT IN on dictionaries: lo = device address of the chunk's match bitmap (JF_INVERT: NOT IN) */,
+                  KIND_VALUE_LIST = 7 /* IN / NOT IN on every other segment: lo = device address of the list -- 8-byte keys (list_key, scan.hip), sorted,
+                                         distinct, padded with its last key to a power of two --, span = its length; the value type is the segment's */ };
 enum : uint32_t { JF_INVERT = 1, JF_LOWER_INCL = 2, JF_UPPER_INCL = 4, JF_NEVER = 8 };
 
 struct ScanJob {
@@ -41,6 +43,10 @@ struct PredicateArgs {
   uint32_t column_is_nullable;
   uint32_t materialize_all;
   uint32_t no_ranges;                   // the caller evaluates the jobs itself and knows JOB_SCAN / JOB_ALL / JOB_NONE only (fused_rows)
+  // HY_PRED_IN / HY_PRED_NOT_IN (hy_table_scan_in_list): match_words / match_word_offsets are the value-id bitmaps build_value_id_sets made
+  const uint64_t* list_keys;            // the list as KIND_VALUE_LIST jobs take it
+  const uint32_t* list_any;             // per data chunk: != 0 if some element is in the chunk's dictionary
+  uint32_t list_size;
 };
 
 // scan.hip: checks `predicate` for `column` (a data column) like hy_table_scan does, uploads its per-chunk arrays into

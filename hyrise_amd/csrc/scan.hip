@@ -26,7 +26,10 @@
 
 #include <cmath>
 #include <cstring>
+#include <algorithm>
 #include <limits>
+#include <type_traits>
+#include <vector>
 
 namespace hy {
 
@@ -104,7 +107,7 @@ __device__ bool integer_range(uint32_t cond, Wide v, Wide v2, Wide tmin, Wide tm
 __device__ __forceinline__ bool job_searches(const DevSegment& seg, uint32_t cond, uint32_t wave) {
   // (an EMPTY dictionary -- every row NULL -- has no buffer either, but nothing to resolve: it is searched, and finds nothing)
   const bool searchable = seg.encoding == HY_ENC_DICTIONARY && (seg.aux || seg.aux_size == 0) && seg.data_type != HY_TYPE_STRING &&
-                          cond != HY_PRED_IS_NULL && cond != HY_PRED_IS_NOT_NULL;
+                          cond != HY_PRED_IS_NULL && cond != HY_PRED_IS_NOT_NULL && cond != HY_PRED_IN && cond != HY_PRED_NOT_IN;
   return searchable && (wave < 2 || is_between(cond));
 }
 
@@ -125,6 +128,21 @@ __device__ __forceinline__ void finish_job(const DevSegment& s, uint32_t c, cons
   job.lo = 0;
   job.span = 0;
   const uint32_t cond = p.condition;
+
+  if (cond == HY_PRED_IN || cond == HY_PRED_NOT_IN) {   // expression_evaluator.cpp:404-506 (hy_table_scan_in_list)
+    job.flags = cond == HY_PRED_NOT_IN ? JF_INVERT : 0;
+    if (s.encoding == HY_ENC_DICTIONARY) {   // the chunk's bitmap over its value ids (build_value_id_sets); the NULL id never matches
+      job.kind = KIND_VALUE_ID_SET;
+      job.null_vid = s.aux_size;
+      job.lo = reinterpret_cast<uint64_t>(p.match_words + p.match_word_offsets[c]);
+      if (cond == HY_PRED_IN && p.list_any[c] == 0) job.mode = JOB_NONE;   // no element is in the dictionary: exactly no row
+    } else {
+      job.kind = KIND_VALUE_LIST;
+      job.lo = reinterpret_cast<uint64_t>(p.list_keys);
+      job.span = p.list_size;
+    }
+    return;
+  }
 
   if (cond >= HY_PRED_LIKE && cond <= HY_PRED_NOT_LIKE_INSENSITIVE) {   // column_like_table_scan_impl.cpp:69-121
     const uint64_t* bitmap = p.match_words + p.match_word_offsets[c];
@@ -449,6 +467,63 @@ __global__ void prepare_visibility_jobs(const DevSegment* segments, uint32_t n_c
   const uint32_t invalid_rows = s.ref_chunk_id & 0x7FFFFFFFu, max_begin_cid = s.aux_size;
   job.mode = (can_use_chunk_shortcut && !is_mutable && snapshot >= max_begin_cid && invalid_rows == 0) ? JOB_ALL : JOB_SCAN;
   jobs[c] = job;
+}
+
+// ---- IN / NOT IN over a literal list (hy_table_scan_in_list) -----------------------------------------------------------------------
+// What it replaces: ExpressionEvaluator::_evaluate_in_expression's fast path over a list of literals of the column's type
+// (expression_evaluator.cpp:404-506: sort the literals, binary_search per row) under ExpressionEvaluatorTableScanImpl.
+// The list travels as 8-byte keys: the value's bits, zero-extended, with -0.0 folded onto 0.0 -- two non-NaN values are == iff their
+// keys are equal, and a NaN row's key equals none (the list holds no NaN).  Sorted as unsigned numbers on the host: the search needs a
+// total order, not the values' own.
+__host__ __device__ __forceinline__ uint64_t list_key_u32(uint32_t bits, bool is_float) { return is_float && (bits << 1) == 0 ? 0u : bits; }
+__host__ __device__ __forceinline__ uint64_t list_key_u64(uint64_t bits, bool is_float) { return is_float && (bits << 1) == 0 ? 0u : bits; }
+
+// The workgroup's copy of the list.
+struct LdsList {
+  const uint64_t* keys;   // [padded] in LDS: wave-uniform data, read by every lane at its own position -- an LDS gather, no vector memory
+  uint32_t padded;        // power of two >= the list's length
+};
+// Branch-free lower bound in the padded list: log2(padded) steps, at most 8, the same number for every lane.
+__device__ __forceinline__ bool key_in_list(const LdsList& list, uint64_t key) {
+  uint32_t position = 0;
+  for (uint32_t step = list.padded >> 1; step != 0; step >>= 1) position += list.keys[position + step - 1] < key ? step : 0u;
+  return list.keys[position] == key;
+}
+
+// Dictionary segments: one lane per (data chunk, element) sets the element's bit in the chunk's bitmap over its value ids.
+//   numeric dictionaries (resident): binary search for the element, == decides (so -0.0 finds 0.0)
+//   dictionaries that are not on the device (strings): the caller's per_chunk_value_ids
+// any[c] != 0 afterwards iff some element is in chunk c's dictionary.  words / any were zeroed on the stream before.
+template <typename T>
+__device__ __forceinline__ uint32_t dictionary_find(const T* dictionary, uint32_t d, T value) {
+  uint32_t low = 0, high = d;
+  while (low < high) {
+    const uint32_t middle = (low + high) / 2;
+    if (dictionary[middle] < value) low = middle + 1; else high = middle;
+  }
+  return low < d && dictionary[low] == value ? low : HY_INVALID_VALUE_ID;
+}
+__global__ __launch_bounds__(256) void build_value_id_sets(const DevSegment* __restrict__ segments, uint32_t n_chunks, const hy_value* __restrict__ values, uint32_t n_values,
+                                                           const uint32_t* __restrict__ per_chunk_value_ids, uint64_t* words, const uint64_t* __restrict__ word_offsets, uint32_t* any) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= static_cast<uint64_t>(n_chunks) * n_values) return;
+  const uint32_t c = static_cast<uint32_t>(i / n_values), e = static_cast<uint32_t>(i % n_values);
+  const DevSegment s = segments[c];
+  if (s.encoding != HY_ENC_DICTIONARY) return;
+  uint32_t vid = HY_INVALID_VALUE_ID;
+  if (s.data_type == HY_TYPE_STRING || (!s.aux && s.aux_size != 0)) {
+    if (per_chunk_value_ids) vid = per_chunk_value_ids[i];
+  } else {
+    switch (s.data_type) {
+      case HY_TYPE_INT: vid = dictionary_find<int32_t>(static_cast<const int32_t*>(s.aux), s.aux_size, values[e].i32); break;
+      case HY_TYPE_LONG: vid = dictionary_find<int64_t>(static_cast<const int64_t*>(s.aux), s.aux_size, values[e].i64); break;
+      case HY_TYPE_FLOAT: vid = dictionary_find<float>(static_cast<const float*>(s.aux), s.aux_size, values[e].f32); break;
+      default: vid = dictionary_find<double>(static_cast<const double*>(s.aux), s.aux_size, values[e].f64); break;
+    }
+  }
+  if (vid >= s.aux_size) return;   // not in this chunk (HY_INVALID_VALUE_ID), or an id the dictionary does not have
+  atomicOr(reinterpret_cast<unsigned long long*>(words + word_offsets[c] + (vid >> 6)), 1ull << (vid & 63));
+  atomicOr(any + c, 1u);
 }
 
 // ---- row evaluation ---------------------------------------------------------------------------------------------------
@@ -794,6 +869,8 @@ struct ScanArgs {
   uint32_t* overflow;              // set to 1 if capacity was exceeded (a persistent, normally-zero word of the scratch)
   uint64_t* trace;                 // debug: 4 wall-clock stamps per workgroup (HY_SCAN_TRACE), else nullptr
   uint32_t plain_stores;           // write-back stores for the RowIDs (the default; HY_SCAN_NT_STORES=1: nontemporal ones, for A/B runs with tools/scan_ab.py)
+  uint32_t list_padded;            // IN / NOT IN (the W = 32 | 40 instantiations): entries of `list`, a power of two <= HY_MAX_IN_LIST
+  const uint64_t* list;            // ... the padded key list of the KIND_VALUE_LIST jobs, copied to LDS once per workgroup
 };
 
 __device__ __forceinline__ uint64_t wave_inclusive_scan(uint64_t v, uint32_t lane) {
@@ -932,6 +1009,174 @@ __device__ __forceinline__ void fetch_four_byte_rows(const DevSegment& s, uint32
 // The column is read from HBM exactly once and every RowID is written exactly once.  Output order is (chunk, row) ascending:
 // bit-identical to the CPU loop's appends.  Chunks of more than one part chain their parts through one epoch-tagged status
 // word per part.
+// ---- IN / NOT IN: the row tests of the W = 32 | 40 instantiations of scan_slices -----------------------------------------------------
+// Such a scan meets two kinds of jobs only -- KIND_VALUE_ID_SET on dictionary segments, KIND_VALUE_LIST on every other one (JOB_SCAN, or
+// JOB_NONE) -- so it has row tests of its own instead of more cases in eval_row / eval8: every other instantiation keeps its code, and
+// these, inlined throughout (their copies of the two out-of-line helpers included), need no stack.
+__device__ __forceinline__ uint64_t value_key(const DevSegment& s, uint32_t index) {   // values[index] of an unencoded vector of the segment's type
+  const bool is_float = s.data_type == HY_TYPE_FLOAT || s.data_type == HY_TYPE_DOUBLE;
+  if (s.data_type == HY_TYPE_INT || s.data_type == HY_TYPE_FLOAT) return list_key_u32(static_cast<const uint32_t*>(s.data)[index], is_float);
+  return list_key_u64(static_cast<const uint64_t*>(s.data)[index], is_float);
+}
+template <bool COMPRESSED>
+__device__ __forceinline__ uint32_t list_load_element(const DevSegment& s, uint32_t i) {   // load_element, inlined
+  if (!COMPRESSED || !seg_is_packed(s)) return load_compressed(s.data, s.width, i);
+  const uint64_t* words = static_cast<const uint64_t*>(s.data);
+  const uint32_t bits = seg_bits(s);
+  const uint64_t at = uint64_t{i} * bits;
+  const uint32_t shift = static_cast<uint32_t>(at & 63);
+  uint64_t value = words[at >> 6] >> shift;
+  if (shift + bits > 64) value |= words[(at >> 6) + 1] << (64 - shift);
+  return static_cast<uint32_t>(value & ((1ull << bits) - 1));
+}
+__device__ __forceinline__ uint32_t list_run_of_position(const uint32_t* ends, uint32_t n_runs, uint32_t row) {   // run_of_position, inlined
+  uint32_t low = 0, high = n_runs - 1;
+  while (low < high) {
+    const uint32_t middle = (low + high) / 2;
+    if (ends[middle] >= row) high = middle; else low = middle + 1;
+  }
+  return low;
+}
+__device__ __forceinline__ bool value_id_in_set(const ScanJob& job, uint32_t vid, bool invert) {   // the NULL id (and anything above) never matches
+  const uint32_t v = vid < job.null_vid ? vid : 0;
+  const bool in = ((as_global<uint64_t>(reinterpret_cast<const void*>(job.lo))[v >> 6] >> (v & 63)) & 1) != 0;
+  return vid < job.null_vid && in != invert;
+}
+__device__ __forceinline__ bool list_run(const DevSegment& s, const ScanJob& job, uint32_t run, const LdsList& list) {   // a RunLength run, tested once
+  const bool is_null = s.nulls && reinterpret_cast<const uint8_t*>(s.nulls)[run] != 0;
+  return !is_null && key_in_list(list, value_key(s, run)) != ((job.flags & JF_INVERT) != 0);
+}
+// One row of a data segment: tails, unaligned buffers, bit-packed vectors and pos-list gathers.
+template <bool COMPRESSED>
+__device__ __forceinline__ bool list_row(const DevSegment& s, const ScanJob& job, uint32_t row, const LdsList& list) {
+  if (job.mode != JOB_SCAN) return false;
+  const bool invert = (job.flags & JF_INVERT) != 0;
+  if (COMPRESSED && s.encoding == HY_ENC_RUN_LENGTH) return list_run(s, job, list_run_of_position(static_cast<const uint32_t*>(s.aux), s.aux_size, row), list);
+  if (s.encoding == HY_ENC_DICTIONARY) return value_id_in_set(job, list_load_element<COMPRESSED>(s, row), invert);
+  if (s.nulls && ((s.nulls[row >> 6] >> (row & 63)) & 1) != 0) return false;
+  const uint64_t key = s.encoding == HY_ENC_FRAME_OF_REFERENCE   // FrameOfReference compares the decoded value
+                           ? list_load_element<COMPRESSED>(s, row) + static_cast<uint32_t>(static_cast<const int32_t*>(s.aux)[row / HY_FOR_BLOCK_SIZE])
+                           : value_key(s, row);
+  return key_in_list(list, key) != invert;
+}
+// Rows [row0, row0 + 8) of a data segment (row0 a multiple of eight, `valid` of them exist), job.mode == JOB_SCAN.
+template <bool COMPRESSED>
+__device__ __forceinline__ uint32_t list_rows8(const DevSegment& s, const ScanJob& job, uint32_t row0, uint32_t valid, const LdsList& list) {
+  uint32_t bits = 0;
+  if (valid < 8 || (s.flags & SEG_UNALIGNED) || (COMPRESSED && (seg_is_packed(s) || s.encoding == HY_ENC_RUN_LENGTH))) {
+    for (uint32_t j = 0; j < valid; ++j) bits |= (list_row<COMPRESSED>(s, job, row0 + j, list) ? 1u : 0u) << j;
+    return bits;
+  }
+  const bool invert = (job.flags & JF_INVERT) != 0;
+  const uint32_t inv = invert ? 0xFFu : 0u;
+  if (s.encoding == HY_ENC_DICTIONARY) {
+    uint32_t x[8];
+    if (s.width == 2) unpack_group<2>(load_group<2>(s.data, row0), x);
+    else if (s.width == 1) unpack_group<1>(load_group<1>(s.data, row0), x);
+    else unpack_group<4>(load_group<4>(s.data, row0), x);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bits |= (value_id_in_set(job, x[j], invert) ? 1u : 0u) << j;
+    return bits;
+  }
+  const uint32_t nullbits = s.nulls ? as_global<uint8_t>(s.nulls)[row0 >> 3] : 0u;
+  const bool is_float = s.data_type == HY_TYPE_FLOAT || s.data_type == HY_TYPE_DOUBLE;
+  if (s.encoding == HY_ENC_FRAME_OF_REFERENCE || s.data_type == HY_TYPE_INT || s.data_type == HY_TYPE_FLOAT) {
+    uint32_t x[8], bias = 0;
+    if (s.encoding == HY_ENC_FRAME_OF_REFERENCE) {   // (eight aligned rows never straddle a 2048-row block)
+      bias = as_global<uint32_t>(s.aux)[row0 / HY_FOR_BLOCK_SIZE];
+      if (s.width == 2) unpack_group<2>(load_group<2>(s.data, row0), x);
+      else if (s.width == 1) unpack_group<1>(load_group<1>(s.data, row0), x);
+      else unpack_group<4>(load_group<4>(s.data, row0), x);
+    } else {
+      unpack_group<4>(load_group<4>(s.data, row0), x);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bits |= (key_in_list(list, list_key_u32(x[j] + bias, is_float)) ? 1u : 0u) << j;
+  } else {
+    const HY_GLOBAL u32x4* p = (const HY_GLOBAL u32x4*)(as_global<uint64_t>(s.data) + row0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const u32x4 v = p[q];
+      const uint64_t a = (static_cast<uint64_t>(v.y) << 32) | v.x, b = (static_cast<uint64_t>(v.w) << 32) | v.z;
+      bits |= (key_in_list(list, list_key_u64(a, is_float)) ? 1u : 0u) << (2 * q);
+      bits |= (key_in_list(list, list_key_u64(b, is_float)) ? 1u : 0u) << (2 * q + 1);
+    }
+  }
+  return (bits ^ inv) & ~nullbits & 0xFFu;
+}
+
+template <bool COMPRESSED>
+__device__ __forceinline__ uint32_t list_data_slice(const ScanArgs& a, const Slice& slice, const DevSegment& seg, uint32_t wave, uint32_t lane, const LdsList& list) {
+  uint32_t mask = 0;   // bit (8k + j) <-> row  wave*2048 + k*512 + lane*8 + j  of the slice
+  const ScanJob job = a.jobs[slice.chunk];
+  if (job.mode != JOB_SCAN) return 0u;   // (JOB_NONE; list jobs are never JOB_ALL / JOB_RANGE)
+  if (COMPRESSED && seg.encoding == HY_ENC_RUN_LENGTH && wave * 2048 < slice.row_count) {   // run by run: each run is tested once (see evaluate_slice)
+    const uint32_t* ends = static_cast<const uint32_t*>(seg.aux);
+    const uint32_t first = __builtin_amdgcn_readfirstlane(slice.row_begin + wave * 2048);
+    const uint32_t end = __builtin_amdgcn_readfirstlane(slice.row_begin + (slice.row_count < wave * 2048 + 2048 ? slice.row_count : wave * 2048 + 2048));
+    uint32_t run = __builtin_amdgcn_readfirstlane(list_run_of_position(ends, seg.aux_size, first));
+    uint32_t cursor = first, walked_mask = 0;
+    for (uint32_t step = 0; step < 64 && cursor < end; ++step, ++run) {
+      const uint32_t run_end = ends[run] + 1 < end ? ends[run] + 1 : end;   // (exclusive)
+      if (list_run(seg, job, run, list)) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) walked_mask |= rows_in_range8(first + k * 512 + lane * 8, cursor, run_end) << (8 * k);
+      }
+      cursor = run_end;
+    }
+    if (cursor >= end) return walked_mask;
+  }
+#pragma unroll 1
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint32_t r0 = wave * 2048 + k * 512 + lane * 8;
+    if (r0 < slice.row_count) {
+      const uint32_t valid = (slice.row_count - r0 < 8) ? slice.row_count - r0 : 8;
+      mask |= list_rows8<COMPRESSED>(seg, job, slice.row_begin + r0, valid, list) << (8 * k);
+    }
+  }
+  return mask;
+}
+
+// Reference segments read the decoded twin's descriptors (COMPRESSED = false); a NULL RowID is in no list and not outside one either.
+__device__ __forceinline__ uint32_t list_reference_slice(const ScanArgs& a, const Slice& slice, const DevSegment& seg, uint32_t wave, uint32_t lane, const LdsList& list) {
+  uint32_t mask = 0;
+  if (seg.ref_chunk_id != 0xFFFFFFFFu) {   // a PosList that references ONE chunk: its segment and job are scalar, only the offsets are read
+    const ScanJob job = a.jobs[seg.ref_chunk_id];
+    if (job.mode != JOB_SCAN) return 0u;
+    const DevSegment base = seg.ref[seg.ref_chunk_id];
+    const HY_GLOBAL uint32_t* words = as_global<uint32_t>(seg.data);
+#pragma unroll 1
+    for (uint32_t k = 0; k < 4; ++k) {
+      const uint32_t r0 = wave * 2048 + k * 512 + lane * 8;
+      uint32_t offset[8];
+#pragma unroll
+      for (uint32_t j = 0; j < 8; ++j) {
+        const uint32_t row = slice.row_begin + (r0 + j < slice.row_count ? r0 + j : 0);
+        offset[j] = words ? words[2 * size_t{row} + 1] : row;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < 8; ++j) {
+        if (r0 + j < slice.row_count && offset[j] != 0xFFFFFFFFu && list_row<false>(base, job, offset[j], list)) mask |= 1u << (8 * k + j);
+      }
+    }
+    return mask;
+  }
+#pragma unroll 1
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint32_t r0 = wave * 2048 + k * 512 + lane * 8;
+    for (uint32_t j = 0; j < 8 && r0 + j < slice.row_count; ++j) {
+      const hy_row_id r = static_cast<const hy_row_id*>(seg.data)[slice.row_begin + r0 + j];
+      if (r.chunk_offset != 0xFFFFFFFFu && list_row<false>(seg.ref[r.chunk_id], a.jobs[r.chunk_id], r.chunk_offset, list)) mask |= 1u << (8 * k + j);
+    }
+  }
+  return mask;
+}
+
+template <bool COMPRESSED>
+__device__ __forceinline__ uint32_t list_slice(const ScanArgs& a, const Slice& slice, const DevSegment& seg, uint32_t wave, uint32_t lane, const LdsList& list) {
+  return seg.encoding == HY_ENC_REFERENCE ? list_reference_slice(a, slice, seg, wave, lane, list) : list_data_slice<COMPRESSED>(a, slice, seg, wave, lane, list);
+}
+
 template <bool COMPRESSED>
 __device__ __forceinline__ uint32_t evaluate_slice(const ScanArgs& a, const Slice& slice, const DevSegment& seg, uint32_t wave, uint32_t lane) {
   uint32_t mask = 0;       // bit (8k + j) <-> row  wave*2048 + k*512 + lane*8 + j  of the slice
@@ -1353,13 +1598,27 @@ __global__ __launch_bounds__(256) void scan_slices(const DevSegment* __restrict_
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (a.trace && tid == 0) a.trace[blockIdx.x * 4 + 0] = wall_clock64();   // (reading HW_ID here with s_getreg makes the register allocator spill)
 
-  constexpr bool GENERIC = W == 0 || W == 8;   // W == 8: the generic instantiation that also reads run-length segments and bit-packed vectors in place
+  constexpr bool LIST = W == 32 || W == 40;   // hy_table_scan_in_list: the generic instantiations (40: W == 8's) with the list test in their row evaluation
+  constexpr bool GENERIC = W == 0 || W == 8 || LIST;   // W == 8: the generic instantiation that also reads run-length segments and bit-packed vectors in place
+  constexpr bool IN_PLACE = W == 8 || W == 40;
   constexpr int LW = GENERIC ? 1 : W;
+  LdsList list{nullptr, 0};
+  if constexpr (LIST) {   // the list is the same for every chunk and every lane: ONE copy per workgroup, 2 KiB at most
+    __shared__ uint64_t s_list[HY_MAX_IN_LIST];
+    for (uint32_t i = tid; i < a.list_padded; i += WG_THREADS) s_list[i] = a.list[i];
+    __syncthreads();
+    list.keys = s_list;
+    list.padded = a.list_padded;
+  }
   SliceLoad<LW> next;   // streaming state: loads of the next slice to evaluate (possibly of the next part)
   uint32_t part_id = blockIdx.x;
+  // (the streaming instantiations keep the part's job in registers; the generic ones read it where they evaluate.  The list instantiations
+  // do not even carry the unused slot: it is what leaves the other generic instantiations a stack frame)
+  struct NoJob {};
+  using JobSlot = std::conditional_t<LIST, NoJob, ScanJob>;
   Part part{};
   DevSegment seg{};
-  ScanJob job{};
+  JobSlot job{};
   if (part_id < a.n_parts) {
     part = parts[part_id];
     seg = a.segments[part.chunk];
@@ -1374,7 +1633,7 @@ __global__ __launch_bounds__(256) void scan_slices(const DevSegment* __restrict_
     const uint32_t next_part_id = part_id + gridDim.x;
     Part next_part = part;
     DevSegment next_seg = seg;
-    ScanJob next_job = job;
+    JobSlot next_job = job;
     if (next_part_id < a.n_parts) {   // one part ahead: these scalar loads complete long before they are needed
       next_part = parts[next_part_id];
       next_seg = a.segments[next_part.chunk];
@@ -1388,7 +1647,8 @@ __global__ __launch_bounds__(256) void scan_slices(const DevSegment* __restrict_
       for (uint32_t i = 0; i < part.n_slices; ++i) {
         const Slice slice = part_slice(part, seg, i);
         if constexpr (GENERIC) {
-          mine += __popc(evaluate_slice<W == 8>(a, slice, seg, wave, lane));
+          if constexpr (LIST) mine += __popc(list_slice<IN_PLACE>(a, slice, seg, wave, lane, list));
+          else mine += __popc(evaluate_slice<IN_PLACE>(a, slice, seg, wave, lane));
         } else {
           SliceLoad<W> again;
           issue_loads<W>(again, seg, job, slice, wave, lane);
@@ -1446,7 +1706,8 @@ __global__ __launch_bounds__(256) void scan_slices(const DevSegment* __restrict_
       const Slice slice = part_slice(part, seg, i);
       uint32_t mask;
       if constexpr (GENERIC) {
-        mask = evaluate_slice<W == 8>(a, slice, seg, wave, lane);
+        if constexpr (LIST) mask = list_slice<IN_PLACE>(a, slice, seg, wave, lane, list);
+        else mask = evaluate_slice<IN_PLACE>(a, slice, seg, wave, lane);
       } else {
         const SliceLoad<W> current = next;
         if (i + 1 < n_slices) issue_loads<W>(next, seg, job, part_slice(part, seg, i + 1), wave, lane);
@@ -1894,8 +2155,15 @@ struct VisibilityArgs {   // hy_validate
   uint32_t our_tid, snapshot, can_use_chunk_shortcut;
 };
 
+struct InListArgs {   // hy_table_scan_in_list, checked: `predicate` carries HY_PRED_IN / HY_PRED_NOT_IN and column_is_nullable
+  const hy_in_list* list;
+  std::vector<uint64_t> keys;   // sorted, distinct, padded with the last key to a power of two
+  uint32_t n_keys;              // before the padding
+};
+
 static hy_status run_scan(const hy_column* column, const hy_column* right, const hy_predicate* predicate, uint32_t condition,
-                          const uint32_t* excluded, uint32_t n_excluded, hy_scan_result* result, const VisibilityArgs* visibility = nullptr) {
+                          const uint32_t* excluded, uint32_t n_excluded, hy_scan_result* result, const VisibilityArgs* visibility = nullptr,
+                          const InListArgs* in_list = nullptr) {
   // Run-length / bit-packed segments are read in place by a ColumnVsValue / Between / IsNull / Like scan of the data column itself; the
   // two-column scan and the scan through reference segments read the decoded twins (hy_device.hpp) -- a reference segment's `ref`
   // already points at the twin's descriptors, so the jobs are prepared from the twin as well.
@@ -1923,6 +2191,17 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
   size_t need = sizeof(ScanJob) * (n_data_chunks + 1) + 3 * 4 * (size_t{n_data_chunks} + 64) + 4 * (size_t{n_excluded} + 64) + 1024;
   const bool like = predicate && predicate->condition >= HY_PRED_LIKE && predicate->condition <= HY_PRED_NOT_LIKE_INSENSITIVE;
   if (like) need += 8 * (size_t{n_data_chunks} + 2) + 8 * (predicate->match_word_offsets[n_data_chunks] + 2) + 1024;
+  // IN / NOT IN: keys | values | caller's value ids | bitmap offsets | bitmaps + "any" words of the dictionary chunks (one zeroed block)
+  std::vector<uint64_t> set_offsets;
+  if (in_list) {
+    set_offsets.assign(size_t{n_data_chunks} + 1, 0);
+    for (uint32_t c = 0; c < n_data_chunks; ++c) {
+      const hy_segment& s = data_column->host_segments[c];
+      set_offsets[c + 1] = set_offsets[c] + (s.encoding == HY_ENC_DICTIONARY ? (uint64_t{s.aux_size} + 63) / 64 : 0);
+    }
+    need += 8 * in_list->keys.size() + 8 * size_t{in_list->list->n_values} + 4 * size_t{n_data_chunks} * in_list->list->n_values + 8 * (size_t{n_data_chunks} + 1) +
+            8 * set_offsets[n_data_chunks] + 4 * (size_t{n_data_chunks} + 1) + 8 * 256;
+  }
   if (column->multi_chunk_reference) need += sizeof(hy_row_id) * (column->rows + 1) + 256;
   if (host_result) need += 2 * sizeof(hy_row_id) * (column->rows + 1) + 3 * 8 * (size_t{n_chunks} + 2) + 4 * (size_t{n_chunks} + 1) + n_chunks + 8192;
   HY_TRY(sc.reserve(need + 16 * 256));
@@ -1934,6 +2213,7 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
   else if (!right && column->stream_width == 2) kernel = column->has_sorted ? scan_slices<2, true> : scan_slices<2>;
   else if (!right && column->stream_width == 4) kernel = column->has_sorted ? scan_slices<4, true> : scan_slices<4>;
   if (like) kernel = column->has_compressed ? scan_slices<8> : scan_slices<0>;   // value-id sets are tested by the generic instantiations
+  if (in_list) kernel = column->has_compressed ? scan_slices<40> : scan_slices<32>;
 
   PredicateArgs pa;
   std::memset(&pa, 0, sizeof(pa));
@@ -1942,7 +2222,43 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
     hipLaunchKernelGGL(prepare_visibility_jobs, dim3((n_data_chunks + 255) / 256), dim3(256), 0, stream, data_column->d_segments, n_data_chunks, visibility->our_tid,
                        visibility->snapshot, visibility->can_use_chunk_shortcut, d_jobs, d_overflow);
   }
-  if (predicate) {
+  const uint64_t* d_list_keys = nullptr;
+  if (in_list) {
+    // No host round trip: the list, the (string) value ids and the zeroed bitmaps are queued on the stream, build_value_id_sets fills the
+    // bitmaps of the dictionary chunks, prepare_jobs reads them.
+    const hy_in_list* list = in_list->list;
+    const uint32_t n_values = list->n_values;
+    const uint64_t set_words = set_offsets[n_data_chunks];
+    uint64_t* d_keys = carve<uint64_t>(sc, in_list->keys.size());
+    hy_value* d_values = carve<hy_value>(sc, n_values);
+    uint32_t* d_value_ids = list->per_chunk_value_ids ? carve<uint32_t>(sc, size_t{n_data_chunks} * n_values) : nullptr;
+    uint64_t* d_set_offsets = carve<uint64_t>(sc, size_t{n_data_chunks} + 1);
+    const size_t zeroed = align_up(8 * (set_words + 1), 256) + 4 * (size_t{n_data_chunks} + 1);
+    char* d_zeroed = static_cast<char*>(sc.carve(zeroed));
+    if (!d_keys || !d_values || !d_set_offsets || !d_zeroed || (list->per_chunk_value_ids && !d_value_ids)) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+    uint64_t* d_set_words = reinterpret_cast<uint64_t*>(d_zeroed);
+    uint32_t* d_any = reinterpret_cast<uint32_t*>(d_zeroed + align_up(8 * (set_words + 1), 256));
+    HY_HIP(hipMemcpyAsync(d_keys, in_list->keys.data(), 8 * in_list->keys.size(), hipMemcpyHostToDevice, stream));
+    if (list->values) HY_HIP(hipMemcpyAsync(d_values, list->values, sizeof(hy_value) * n_values, hipMemcpyHostToDevice, stream));
+    if (d_value_ids && n_data_chunks) HY_HIP(hipMemcpyAsync(d_value_ids, list->per_chunk_value_ids, 4 * size_t{n_data_chunks} * n_values, hipMemcpyHostToDevice, stream));
+    HY_HIP(hipMemcpyAsync(d_set_offsets, set_offsets.data(), 8 * (size_t{n_data_chunks} + 1), hipMemcpyHostToDevice, stream));
+    HY_HIP(hipMemsetAsync(d_zeroed, 0, zeroed, stream));
+    if (set_words) {
+      const uint64_t lanes = uint64_t{n_data_chunks} * n_values;
+      hipLaunchKernelGGL(build_value_id_sets, dim3(static_cast<uint32_t>((lanes + 255) / 256)), dim3(256), 0, stream, data_column->d_segments, n_data_chunks, d_values, n_values,
+                         d_value_ids, d_set_words, d_set_offsets, d_any);
+    }
+    pa.condition = predicate->condition;
+    pa.value_type = list->value_type;
+    pa.column_is_nullable = predicate->column_is_nullable;
+    pa.match_words = d_set_words;
+    pa.match_word_offsets = d_set_offsets;
+    pa.list_keys = d_keys;
+    pa.list_any = d_any;
+    pa.list_size = in_list->n_keys;
+    d_list_keys = d_keys;
+    if (n_data_chunks) hipLaunchKernelGGL(prepare_jobs, dim3(n_data_chunks), dim3(256), 0, stream, data_column->d_segments, n_data_chunks, pa, d_jobs, d_overflow);
+  } else if (predicate) {
     pa.condition = predicate->condition;
     pa.value_type = predicate->value_type;
     pa.value = predicate->value;
@@ -2026,6 +2342,8 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
     // Write-back stores: on this part a 37 : 63 read : write stream runs 13 % faster through the L2 than around it (nontemporal) --
     // tools/hbm_mix.hip shows it for the bare traffic pattern, tools/scan_ab.py for this kernel (profiles/r03_scan_stores.txt).
     a.plain_stores = FIXED_SCAN_NT_STORES ? 0u : 1u;
+    a.list = d_list_keys;
+    a.list_padded = in_list ? static_cast<uint32_t>(in_list->keys.size()) : 0u;
     if (HY_DEBUG_ENV("HY_SCAN_TRACE")) {
       static uint64_t* trace_buffer = nullptr;
       if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 4 * 4096);
@@ -2155,6 +2473,71 @@ hy_status hy_table_scan(const hy_column* column, const hy_predicate* predicate, 
     return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
   }
   return run_scan(column, nullptr, predicate, 0, excluded_chunks, n_excluded, result);
+}
+
+hy_status hy_table_scan_in_list(const hy_column* column, const hy_in_list* list, const uint32_t* excluded_chunks, uint32_t n_excluded, hy_scan_result* result) {
+  if (!column || !list || !result) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: null argument");
+  HY_TRY(on_this_device(column, "hy_table_scan_in_list"));
+  if (n_excluded && !excluded_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: excluded chunk list missing");
+  for (uint32_t i = 0; i < n_excluded; ++i) {
+    if (excluded_chunks[i] >= column->n_chunks) return fail(HY_ERR_INVALID, "excluded chunk id %u out of range", excluded_chunks[i]);
+  }
+  if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
+  if (list->n_values == 0) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: an empty list has a constant result; the caller answers it");
+  if (list->n_values > HY_MAX_IN_LIST) return fail(HY_ERR_UNSUPPORTED, "hy_table_scan_in_list: %u elements, at most %u are evaluated here (longer lists are semi joins)", list->n_values, HY_MAX_IN_LIST);
+  if (list->value_type != column->data_type) return fail(HY_ERR_INVALID, "list type %u differs from column type %u: use hy_in_list_cast first", list->value_type, column->data_type);
+  if (list->negated > 1) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: negated is 0 or 1");
+  const hy_column* data_column = column->is_reference ? column->ref : column;
+  InListArgs args;
+  args.list = list;
+  if (column->data_type == HY_TYPE_STRING) {
+    if (!list->per_chunk_value_ids) return fail(HY_ERR_INVALID, "string column IN list needs per-chunk value ids (hy_in_list.per_chunk_value_ids)");
+    for (uint32_t chunk = 0; data_column && chunk < data_column->n_chunks; ++chunk) {
+      if (data_column->host_segments[chunk].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "IN on unencoded string segments stays on the CPU path");
+    }
+    args.keys.assign(1, 0);   // (no segment takes a KIND_VALUE_LIST job)
+    args.n_keys = 1;
+  } else {
+    if (column->data_type < HY_TYPE_INT || column->data_type > HY_TYPE_DOUBLE) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: column type %u", column->data_type);
+    if (!list->values) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: values missing");
+    if (data_column && data_column->has_dictionary_without_values && !list->per_chunk_value_ids) return fail(HY_ERR_INVALID, "dictionaries that are not on the device need per-chunk value ids");
+    for (uint32_t i = 0; i < list->n_values; ++i) {
+      const hy_value& v = list->values[i];
+      switch (column->data_type) {
+        case HY_TYPE_INT: args.keys.push_back(list_key_u32(static_cast<uint32_t>(v.i32), false)); break;
+        case HY_TYPE_LONG: args.keys.push_back(list_key_u64(static_cast<uint64_t>(v.i64), false)); break;
+        case HY_TYPE_FLOAT: {
+          if (std::isnan(v.f32)) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: element %u is NaN (it equals no row: drop it)", i);
+          uint32_t bits;
+          std::memcpy(&bits, &v.f32, 4);
+          args.keys.push_back(list_key_u32(bits, true));
+          break;
+        }
+        default: {
+          if (std::isnan(v.f64)) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: element %u is NaN (it equals no row: drop it)", i);
+          uint64_t bits;
+          std::memcpy(&bits, &v.f64, 8);
+          args.keys.push_back(list_key_u64(bits, true));
+          break;
+        }
+      }
+    }
+    std::sort(args.keys.begin(), args.keys.end());
+    args.keys.erase(std::unique(args.keys.begin(), args.keys.end()), args.keys.end());
+    args.n_keys = static_cast<uint32_t>(args.keys.size());
+    size_t padded = 1;
+    while (padded < args.keys.size()) padded *= 2;
+    args.keys.resize(padded, args.keys.back());
+  }
+  if (column->multi_chunk_reference && result->mem == HY_MEM_DEVICE && !result->counts) {
+    return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
+  }
+  hy_predicate predicate;
+  std::memset(&predicate, 0, sizeof(predicate));
+  predicate.condition = list->negated ? HY_PRED_NOT_IN : HY_PRED_IN;
+  predicate.value_type = list->value_type;
+  predicate.column_is_nullable = list->column_is_nullable;
+  return run_scan(column, nullptr, &predicate, 0, excluded_chunks, n_excluded, result, nullptr, &args);
 }
 
 hy_status hy_validate(const hy_column* mvcc, uint32_t our_tid, uint32_t snapshot_commit_id, uint32_t can_use_chunk_shortcut, hy_scan_result* result) {

@@ -1161,6 +1161,12 @@ class TableScan : public AbstractReadOnlyOperator {
       : AbstractReadOnlyOperator(std::move(in)), _column_id(column_id), _condition(condition), _value(std::move(value)), _value2(std::move(value2)) {}
   TableScan(std::shared_ptr<const AbstractOperator> in, ColumnID left_column, PredicateCondition condition, ColumnID right_column, bool /*column_vs_column*/)
       : AbstractReadOnlyOperator(std::move(in)), _column_id(left_column), _condition(condition), _right_column_id(right_column) {}
+  // `column IN (list)` / `column NOT IN (list)` over literals (PredicateCondition::In / NotIn): the InExpressions the optimizer leaves
+  // to the ExpressionEvaluator (expression_evaluator.cpp:404-506), on the device through hy_table_scan_in_list
+  TableScan(std::shared_ptr<const AbstractOperator> in, ColumnID column_id, PredicateCondition condition, std::vector<AllTypeVariant> list)
+      : AbstractReadOnlyOperator(std::move(in)), _column_id(column_id), _condition(condition), _list(std::move(list)) {
+    Assert(condition == PredicateCondition::In || condition == PredicateCondition::NotIn, "A literal list belongs to In / NotIn.");
+  }
   const std::string& name() const override { static const std::string n = "TableScan"; return n; }
   std::vector<ChunkID> excluded_chunk_ids;
   size_t num_chunks_with_early_out = 0, num_chunks_with_all_rows_matching = 0;   // TableScan::PerformanceData (table_scan.hpp:56-69)
@@ -1199,7 +1205,61 @@ class TableScan : public AbstractReadOnlyOperator {
       const bool like = _condition == PredicateCondition::Like || _condition == PredicateCondition::NotLike ||
                         _condition == PredicateCondition::LikeInsensitive || _condition == PredicateCondition::NotLikeInsensitive;
       std::vector<uint64_t> match_words, match_word_offsets;
-      if (like) {
+      const bool in_list = _condition == PredicateCondition::In || _condition == PredicateCondition::NotIn;
+      if (in_list) {
+        // The ABI takes the evaluator's fast path only (a non-empty list of non-NULL literals of the column's type); what is constant is
+        // answered here: `x IN ()` is false and `x NOT IN ()` true for every row (expression_evaluator.cpp:415-419), a NULL element leaves IN
+        // as it is and makes NOT IN match nothing, a list without any element that can equal a row matches nothing (IN) / every non-NULL row.
+        const bool negated = _condition == PredicateCondition::NotIn;
+        const auto column_type = in_table->column_data_type(_column_id);
+        std::vector<hy_value> values(_list.size() + 1);
+        std::vector<uint32_t> value_ids;
+        uint32_t n_values = 0, has_null = 0;
+        if (column_type == DataType::String) {
+          std::vector<std::string> strings;
+          for (const auto& element : _list) {
+            if (variant_is_null(element)) has_null = 1;
+            else if (std::holds_alternative<std::string>(element)) strings.push_back(std::get<std::string>(element));   // (a number equals no string)
+          }
+          n_values = static_cast<uint32_t>(strings.size());
+          resolve_string_list(in_table, strings, value_ids);
+        } else {
+          std::vector<uint32_t> types;
+          std::vector<hy_value> literals;
+          for (const auto& element : _list) {
+            types.push_back(static_cast<uint32_t>(data_type_from_all_type_variant(element)));
+            literals.push_back(element.index() >= 1 && element.index() <= 4 ? to_hy_value(element) : hy_value{});
+          }
+          check_status(hy_in_list_cast(static_cast<uint32_t>(column_type), types.data(), literals.data(), static_cast<uint32_t>(_list.size()), values.data(), &n_values, &has_null));
+        }
+        enum class Constant { No, NoRows, AllRows, NotNullRows } constant = Constant::No;
+        if (chunk_count == 0) constant = Constant::NoRows;   // (a table without chunks has no rows to test, and its device column no type)
+        else if (_list.empty()) constant = negated ? Constant::AllRows : Constant::NoRows;
+        else if (negated && has_null) constant = Constant::NoRows;
+        else if (n_values == 0) constant = negated ? Constant::NotNullRows : Constant::NoRows;
+        if (constant == Constant::NoRows || constant == Constant::AllRows) {
+          on_device.reset();
+          for (ChunkID c = 0; c < chunk_count; ++c) {
+            const bool excluded = std::find(excluded_chunk_ids.begin(), excluded_chunk_ids.end(), c) != excluded_chunk_ids.end();
+            counts[c] = constant == Constant::AllRows && !excluded ? in_table->get_chunk(c)->size() : 0;
+            states[c] = counts[c] ? HY_CHUNK_ALL_MATCH : HY_CHUNK_NONE_MATCH;
+          }
+          evaluated_on_host = true;   // (nothing to evaluate: no RowIDs are needed for chunks that match entirely or not at all)
+        } else if (constant == Constant::NotNullRows) {
+          predicate.condition = HY_PRED_IS_NOT_NULL;
+        } else {
+          if (n_values > HY_MAX_IN_LIST) throw std::logic_error("TableScan: IN lists of more than HY_MAX_IN_LIST elements are semi joins (InExpressionRewriteRule)");
+          hy_in_list list{};
+          list.value_type = static_cast<uint32_t>(column_type);
+          list.n_values = n_values;
+          list.values = values.data();
+          list.negated = negated;
+          list.column_is_nullable = in_table->column_is_nullable(_column_id);
+          list.per_chunk_value_ids = column_type == DataType::String ? value_ids.data() : nullptr;
+          check_status(hy_table_scan_in_list(column->handle, &list, excluded_chunk_ids.data(), static_cast<uint32_t>(excluded_chunk_ids.size()), &result));
+          evaluated_on_host = true;   // (the scan has run)
+        }
+      } else if (like) {
         // ColumnLikeTableScanImpl (column_like_table_scan_impl.cpp:28-36)
         Assert(in_table->column_data_type(_column_id) == DataType::String, "LIKE operator only applicable on string columns.");
         Assert(std::holds_alternative<std::string>(_value), "Right parameter must be a string.");
@@ -1384,6 +1444,27 @@ class TableScan : public AbstractReadOnlyOperator {
     predicate.per_chunk_found = found.data();
   }
 
+  // DictionarySegment<pmr_string>: every element's value id in every data chunk's dictionary (lower_bound plus an equality check), or
+  // HY_INVALID_VALUE_ID -- hy_in_list::per_chunk_value_ids, [n_data_chunks x n_values]
+  void resolve_string_list(const std::shared_ptr<const Table>& in_table, const std::vector<std::string>& strings, std::vector<uint32_t>& value_ids) const {
+    auto data_table = in_table;
+    auto column_id = _column_id;
+    if (in_table->type() == TableType::References && in_table->chunk_count()) {
+      const auto ref = std::static_pointer_cast<ReferenceSegment>(in_table->get_chunk(0)->get_segment(_column_id));
+      data_table = ref->referenced_table();
+      column_id = ref->referenced_column_id();
+    }
+    for (ChunkID c = 0; c < data_table->chunk_count(); ++c) {
+      const auto* dict = dynamic_cast<const DictionarySegment<std::string>*>(data_table->get_chunk(c)->get_segment(column_id).get());
+      Assert(dict, "unencoded string segments stay on the CPU path");
+      for (const auto& value : strings) {
+        const auto lb = dict->lower_bound(value);
+        value_ids.push_back(lb != HY_INVALID_VALUE_ID && dict->dictionary()[lb] == value ? lb : HY_INVALID_VALUE_ID);
+      }
+    }
+    if (value_ids.empty()) value_ids.push_back(HY_INVALID_VALUE_ID);
+  }
+
   // _find_matches_in_dictionary per data chunk (column_like_table_scan_impl.cpp:142-159): bit i of chunk c's words says
   // whether dictionary entry i satisfies the (possibly negated) pattern; the device tests value ids against it.
   void find_matches_in_dictionaries(const std::shared_ptr<const Table>& in_table, std::vector<uint64_t>& words, std::vector<uint64_t>& word_offsets,
@@ -1417,6 +1498,7 @@ class TableScan : public AbstractReadOnlyOperator {
   AllTypeVariant _value;
   std::optional<AllTypeVariant> _value2;
   std::optional<ColumnID> _right_column_id;
+  std::vector<AllTypeVariant> _list;   // In / NotIn
 };
 
 // ---- Validate (operators/validate.hpp, validate.cpp:87-314) -------------------------------------------------------------

@@ -164,6 +164,77 @@ def table_scan(column, predicate, excluded_chunks=None, flags=0, capacity=None):
     return result
 
 
+def in_list_predicate(data_type, values, negated=False, nullable=False, per_chunk_value_ids=None):
+    """hy_in_list of `column [NOT] IN (values)`: `values` are non-NULL literals of exactly the column's type (in_list_cast makes them
+    so).  per_chunk_value_ids: [n_data_chunks][n_values] for dictionaries that are not on the device (string_in_list_predicate)."""
+    p = abi.InList()
+    p.value_type, p.n_values = data_type, len(values)
+    p.negated, p.column_is_nullable = (1 if negated else 0), (1 if nullable else 0)
+    keep = []
+    if data_type != abi.TYPE_STRING:
+        array = (abi.Value * max(1, len(values)))()
+        for i, v in enumerate(values):
+            array[i] = _literal(data_type, v)
+        keep.append(array)
+        p.values = C.addressof(array)
+    if per_chunk_value_ids is not None:
+        ids = np.ascontiguousarray(per_chunk_value_ids, dtype=np.uint32)
+        keep.append(ids)
+        p.per_chunk_value_ids = ids.ctypes.data
+    p._keepalive = keep
+    return p
+
+
+def string_in_list_predicate(dictionaries, values, negated=False, nullable=False):
+    """`string_column [NOT] IN ('a', 'b', ...)` over DictionarySegment<pmr_string> chunks: every element is resolved against every
+    chunk's (byte-wise sorted) dictionary on the host -- lower_bound plus an equality check, like string_predicate -- and the device
+    tests value ids.  `dictionaries`: per data chunk the sorted list of bytes."""
+    import bisect
+    elements = [v if isinstance(v, bytes) else str(v).encode("utf-8") for v in values]
+    ids = np.full((max(1, len(dictionaries)), max(1, len(elements))), abi.INVALID_VALUE_ID, dtype=np.uint32)
+    for c, dictionary in enumerate(dictionaries):
+        for i, element in enumerate(elements):
+            position = bisect.bisect_left(dictionary, element)
+            if position < len(dictionary) and dictionary[position] == element:
+                ids[c, i] = position
+    return in_list_predicate(abi.TYPE_STRING, elements, negated, nullable, per_chunk_value_ids=ids)
+
+
+def in_list_cast(column_type, literals):
+    """hy_in_list_cast: literals = [(HY_TYPE_*, value) | None for NULL, ...] -> (values of the column's type that can equal a row, in
+    input order; whether the list held a NULL)."""
+    lib = abi.load_library()
+    n = len(literals)
+    types = (C.c_uint32 * max(1, n))()
+    values = (abi.Value * max(1, n))()
+    for i, literal in enumerate(literals):
+        if literal is None:
+            types[i] = abi.TYPE_NULL
+        else:
+            types[i] = literal[0]
+            if literal[0] != abi.TYPE_STRING:
+                values[i] = _literal(literal[0], literal[1])
+    out = (abi.Value * max(1, n))()
+    n_out, has_null = C.c_uint32(0), C.c_uint32(0)
+    abi.check(lib.hy_in_list_cast(column_type, C.addressof(types), C.addressof(values), n, C.addressof(out), C.byref(n_out), C.byref(has_null)))
+    field = {abi.TYPE_INT: "i32", abi.TYPE_LONG: "i64", abi.TYPE_FLOAT: "f32", abi.TYPE_DOUBLE: "f64"}[column_type]
+    return [getattr(out[i], field) for i in range(n_out.value)], bool(has_null.value)
+
+
+def table_scan_in_list(column, values, negated=False, nullable=False, excluded_chunks=None, flags=0, capacity=None, predicate=None):
+    """hy_table_scan_in_list with a host-memory result: `column [NOT] IN (values)`, or a ready hy_in_list as `predicate`."""
+    lib = abi.load_library()
+    if predicate is None:
+        predicate = in_list_predicate(column.data_type, values, negated, nullable)
+    result = HostScanResult(column.n_chunks, column.rows if capacity is None else capacity, flags)
+    excluded, n_excluded = None, 0
+    if excluded_chunks is not None and len(excluded_chunks):
+        excluded = np.ascontiguousarray(excluded_chunks, dtype=np.uint32)
+        n_excluded = len(excluded)
+    abi.check(lib.hy_table_scan_in_list(column.handle, C.byref(predicate), excluded.ctypes.data if excluded is not None else None, n_excluded, C.byref(result.c)))
+    return result
+
+
 def table_scan_columns(left, right, condition, capacity=None):
     lib = abi.load_library()
     result = HostScanResult(left.n_chunks, left.rows if capacity is None else capacity)

@@ -378,6 +378,44 @@ hy_status hy_column_chunk_count(const hy_column* column, uint32_t* chunks);
  * column_is_null_table_scan_impl.cpp), over data or reference columns.  excluded_chunks may be NULL. */
 hy_status hy_table_scan(const hy_column* column, const hy_predicate* predicate, const uint32_t* excluded_chunks,
                         uint32_t n_excluded, hy_scan_result* result);
+/* `column IN (v1, ..., vk)` / `column NOT IN (...)` over a literal list -- the InExpressions that InExpressionRewriteRule leaves alone
+ * (in_expression_rewrite_rule.hpp:31,38: lists of 4 .. 19 elements, longer ones whose elements differ in type) and that the reference's
+ * TableScan hands to its ExpressionEvaluator (expression_evaluator.cpp:404-506).
+ *   IN matches a row iff it is not NULL and operator== holds against at least one element; NOT IN iff it is not NULL and no element
+ *   is equal.  Floating point compares with ==: -0.0 equals 0.0, a row that holds NaN is never IN and always NOT IN.  Order and
+ *   duplicates of the elements do not matter.
+ *   values      n_values non-NULL literals of exactly the column's type (value_type == the column's HY_TYPE_*), in host memory: the
+ *               evaluator's fast path.  Lists with NULLs or elements of other types go through hy_in_list_cast first.
+ *               n_values == 0: HY_ERR_INVALID (the reference's constant answer for an empty list is the adapter's business); more than
+ *               HY_MAX_IN_LIST: HY_ERR_UNSUPPORTED; a NaN element or another value_type than the column's: HY_ERR_INVALID.  Nothing is
+ *               written in any of these cases.
+ *   per_chunk_value_ids   dictionary segments whose dictionary is not on the device (strings; value_type = HY_TYPE_STRING, `values` is
+ *               not read): [n_data_chunks x n_values], entry [c * n_values + i] = the value id of element i in data chunk c's
+ *               dictionary (lower_bound plus an equality check, as for per_chunk_lower / per_chunk_found) or HY_INVALID_VALUE_ID.
+ *               For a reference column the data chunks are those of the referenced column.
+ * Dictionary segments are scanned against a per-chunk bitmap over their value ids that the device builds from the list (one binary
+ * search of the chunk's dictionary per element); every other segment's rows are searched in the sorted list. */
+#define HY_MAX_IN_LIST 256
+typedef struct hy_in_list {
+  uint32_t value_type;
+  uint32_t n_values;
+  const hy_value* values;
+  uint32_t negated;            /* 0: IN, 1: NOT IN */
+  uint32_t column_is_nullable;
+  const uint32_t* per_chunk_value_ids;
+} hy_in_list;
+/* Result contract, flags, alignment rules and `mem` handling: hy_table_scan's, bit for bit (data and reference columns, excluded_chunks
+ * for data columns).  chunk_state reports HY_CHUNK_NONE_MATCH only for a dictionary chunk that holds none of the elements (IN) and for
+ * excluded chunks; it never reports HY_CHUNK_ALL_MATCH. */
+hy_status hy_table_scan_in_list(const hy_column* column, const hy_in_list* list, const uint32_t* excluded_chunks, uint32_t n_excluded,
+                                hy_scan_result* result);
+/* The list handling in front of hy_table_scan_in_list (rewrite_in_list_expression ORs `=` terms, whose literals
+ * lossless_predicate_cast decides): every literal is cast to the column's type without loss; one that cannot be can equal no row and
+ * is dropped; a NULL literal (HY_TYPE_NULL) is dropped and reported in *has_null -- it leaves IN as it is and makes NOT IN match
+ * nothing.  out: room for n values; *n_out of them are written, in the order of the input.  A string literal against a numeric column
+ * (HY_TYPE_STRING) is dropped as well; a string column takes no hy_value list: HY_ERR_INVALID.  Pure host arithmetic. */
+hy_status hy_in_list_cast(uint32_t column_type, const uint32_t* literal_types, const hy_value* literals, uint32_t n, hy_value* out,
+                          uint32_t* n_out, uint32_t* has_null);
 /* ColumnVsColumn (column_vs_column_table_scan_impl.cpp:36-187): left <condition> right, both columns of one table. */
 hy_status hy_table_scan_columns(const hy_column* left, const hy_column* right, uint32_t condition,
                                 hy_scan_result* result);
