@@ -17,6 +17,30 @@ struct Value {
   double f;
 };
 
+// x <condition> y in the common C++ type of the two column types: the reference's comparator functors are generic
+// lambdas, the usual arithmetic conversions apply (int64 against float compares as float).
+__device__ __forceinline__ bool compare_typed(uint32_t condition, const Value& x, uint32_t xt, const Value& y, uint32_t yt) {
+  const bool x_float = xt == HY_TYPE_FLOAT || xt == HY_TYPE_DOUBLE, y_float = yt == HY_TYPE_FLOAT || yt == HY_TYPE_DOUBLE;
+  bool less, equal;
+  if (xt == HY_TYPE_DOUBLE || yt == HY_TYPE_DOUBLE) {
+    const double p = x_float ? x.f : static_cast<double>(x.i), q = y_float ? y.f : static_cast<double>(y.i);
+    less = p < q; equal = p == q;
+  } else if (xt == HY_TYPE_FLOAT || yt == HY_TYPE_FLOAT) {
+    const float p = x_float ? static_cast<float>(x.f) : static_cast<float>(x.i), q = y_float ? static_cast<float>(y.f) : static_cast<float>(y.i);
+    less = p < q; equal = p == q;
+  } else {
+    less = x.i < y.i; equal = x.i == y.i;
+  }
+  switch (condition) {
+    case HY_PRED_EQUALS: return equal;
+    case HY_PRED_NOT_EQUALS: return !equal;
+    case HY_PRED_LESS_THAN: return less;
+    case HY_PRED_LESS_THAN_EQUALS: return less || equal;
+    case HY_PRED_GREATER_THAN: return !less && !equal;
+    default: return !less;   // HY_PRED_GREATER_THAN_EQUALS
+  }
+}
+
 __device__ inline Value data_value(const DevSegment& s, uint32_t row) {
   Value v{false, 0, 0.0};
   const void* values = s.data;

@@ -1977,6 +1977,96 @@ class JoinSortMerge : public AbstractReadOnlyOperator {
   std::vector<OperatorJoinPredicate> _secondary_predicates;
 };
 
+// JoinNestedLoop (operators/join_nested_loop.hpp): the third join the translator tries (lqp_translator.cpp:389-410), which supports every
+// configuration -- what JoinHash and JoinSortMerge refuse ends up here -- as ONE hy_join_nested_loop call.  The rows come in the reference's
+// order (include/hyrise_amd.h), in ONE output chunk, or no chunk for an empty result (join_nested_loop.cpp:253-258); Semi / Anti outputs hold
+// the left columns only.  The lists stay in pooled blocks of HBM as JoinSortMerge's do.  String columns in a predicate are not run on the device.
+class JoinNestedLoop : public AbstractReadOnlyOperator {
+ public:
+  JoinNestedLoop(std::shared_ptr<const AbstractOperator> left, std::shared_ptr<const AbstractOperator> right, JoinMode mode, OperatorJoinPredicate primary_predicate,
+                 std::vector<OperatorJoinPredicate> secondary_predicates = {})
+      : AbstractReadOnlyOperator(std::move(left), std::move(right)), _mode(mode), _primary_predicate(primary_predicate), _secondary_predicates(std::move(secondary_predicates)) {}
+  const std::string& name() const override { static const std::string n = "JoinNestedLoop"; return n; }
+  static bool supports(const JoinConfiguration& /*config*/) { return true; }   // join_nested_loop.cpp:87-89
+
+ protected:
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto left = left_input_table(), right = right_input_table();
+    std::vector<OperatorJoinPredicate> predicates{_primary_predicate};
+    predicates.insert(predicates.end(), _secondary_predicates.begin(), _secondary_predicates.end());
+    std::vector<std::shared_ptr<DeviceColumn>> columns;   // (keeps the handles alive)
+    for (const auto& predicate : predicates) {
+      Assert(left->column_data_type(predicate.column_ids.first) != DataType::String && right->column_data_type(predicate.column_ids.second) != DataType::String,
+             "JoinNestedLoop: string columns are not run on the device");
+      columns.push_back(device_column(left, predicate.column_ids.first));
+      columns.push_back(device_column(right, predicate.column_ids.second));
+    }
+    std::vector<hy_join_predicate> secondary;
+    for (size_t p = 1; p < predicates.size(); ++p) secondary.push_back(hy_join_predicate{columns[2 * p]->handle, columns[2 * p + 1]->handle, static_cast<uint32_t>(predicates[p].predicate_condition), 0});
+    const bool semi_anti = _mode == JoinMode::Semi || _mode == JoinMode::AntiNullAsTrue || _mode == JoinMode::AntiNullAsFalse;
+    // One call: room for one partner per row of the larger input; a join that needs more reports it with HY_ERR_CAPACITY (nothing written)
+    // and runs once more with exactly that.
+    uint64_t capacity = std::max<uint64_t>(1, std::max(left->row_count(), right->row_count()));
+    const bool on_device = device_resident_results();
+    std::vector<RowID> left_positions, right_positions;
+    std::shared_ptr<DeviceBlock> left_block, right_block;
+    hy_nested_loop_result result{};
+    for (int attempt = 0;; ++attempt) {
+      result = hy_nested_loop_result{};
+      result.capacity = capacity;
+      if (on_device) {
+        left_block.reset(); right_block.reset();   // (a second attempt: the first one's blocks go back first)
+        hy_row_id* l = nullptr;
+        hy_row_id* r = nullptr;
+        check_status(hy_result_pool_acquire_pair(capacity, &l, &r));
+        left_block = std::make_shared<DeviceBlock>(l);
+        right_block = std::make_shared<DeviceBlock>(r);
+        result.mem = HY_MEM_DEVICE;
+        result.left_pos = l;
+        result.right_pos = r;
+      } else {
+        left_positions.resize(capacity);
+        right_positions.resize(capacity);
+        result.mem = HY_MEM_HOST;
+        result.left_pos = reinterpret_cast<hy_row_id*>(left_positions.data());
+        result.right_pos = reinterpret_cast<hy_row_id*>(right_positions.data());
+      }
+      const auto status = hy_join_nested_loop(columns[0]->handle, columns[1]->handle, static_cast<uint32_t>(_mode), static_cast<uint32_t>(_primary_predicate.predicate_condition), secondary.data(),
+                                              static_cast<uint32_t>(secondary.size()), &result);
+      if (status == HY_ERR_CAPACITY && attempt == 0 && result.n_pairs > capacity) {
+        capacity = result.n_pairs;
+        continue;
+      }
+      check_status(status);   // (HY_ERR_UNSUPPORTED included: there is no CPU implementation behind this class)
+      break;
+    }
+    if (semi_anti) right_block.reset();
+    TableColumnDefinitions definitions;
+    const bool left_nullable = _mode == JoinMode::Right || _mode == JoinMode::FullOuter, right_nullable = _mode == JoinMode::Left || _mode == JoinMode::FullOuter;
+    for (const auto& d : left->column_definitions()) definitions.push_back({d.name, d.data_type, d.nullable || left_nullable});
+    if (!semi_anti) for (const auto& d : right->column_definitions()) definitions.push_back({d.name, d.data_type, d.nullable || right_nullable});
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    if (result.n_pairs) {
+      Segments segments;
+      if (on_device) {
+        JoinHash::DeviceSide left_side(left, left_block, result.n_pairs), right_side(right, semi_anti ? nullptr : right_block, semi_anti ? 0 : result.n_pairs);
+        left_side.append(segments, 0, result.n_pairs);
+        if (!semi_anti) right_side.append(segments, 0, result.n_pairs);
+      } else {
+        JoinHash::append_side(segments, left, std::vector<RowID>(left_positions.begin(), left_positions.begin() + result.n_pairs));
+        if (!semi_anti) JoinHash::append_side(segments, right, std::vector<RowID>(right_positions.begin(), right_positions.begin() + result.n_pairs));
+      }
+      chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+    }
+    return std::make_shared<Table>(definitions, TableType::References, std::move(chunks));
+  }
+
+ private:
+  JoinMode _mode;
+  OperatorJoinPredicate _primary_predicate;
+  std::vector<OperatorJoinPredicate> _secondary_predicates;
+};
+
 // Sort (operators/sort.hpp, sort.cpp:287-516): ONE stable lexicographic sort of the input's rows on the device (hy_sort), whose result -- the
 // input table's positions in sorted order -- stays in a pooled block of HBM; the output's PosLists are views into it (a data input) or into
 // one block per column cluster that hy_poslist_gather dereferences it into (a reference input: JoinHash's DeviceSide), or the rows are

@@ -783,6 +783,52 @@ def join_sort_merge(left, right, mode, condition):
         return out
 
 
+class NestedLoopPairs(SortMergePairs):
+    """hy_join_nested_loop's output in blocks of the result-buffer pool, in the reference's order; Semi / Anti fill the left list only."""
+
+    def __init__(self, capacity, semi_anti=False):
+        super().__init__(capacity)
+        self.semi_anti = semi_anti
+
+    def numpy(self):
+        left, right = super().numpy() if not self.semi_anti else (np.zeros((self.n_pairs, 2), dtype=np.uint32), None)
+        if self.semi_anti and self.n_pairs:
+            abi.check(self.lib.hy_memcpy_d2h(left.ctypes.data, self.left_pointer, left.nbytes))
+        return left, right
+
+
+def join_nested_loop_count(left, right, mode, condition, secondary=None):
+    lib = abi.load_library()
+    predicates, n_secondary = join_predicates(secondary)
+    n = C.c_uint64(0)
+    abi.check(lib.hy_join_nested_loop_count(left.handle, right.handle, mode, condition, predicates, n_secondary, C.byref(n)))
+    return int(n.value)
+
+
+def join_nested_loop(left, right, mode, condition, secondary=None):
+    """hy_join_nested_loop: left <condition> right AND the secondary predicates [(left column, condition, right column), ...] under any join
+    mode but Cross -> NestedLoopPairs.  Sized for one partner per row of the larger input; a join that needs more answers HY_ERR_CAPACITY with
+    what it needs (nothing written) and runs once more with exactly that."""
+    lib = abi.load_library()
+    predicates, n_secondary = join_predicates(secondary)
+    semi_anti = mode in (abi.JOIN_SEMI, abi.JOIN_ANTI_NULL_AS_TRUE, abi.JOIN_ANTI_NULL_AS_FALSE)
+    capacity = max(1, left.rows, right.rows)
+    for attempt in (0, 1):
+        out = NestedLoopPairs(capacity, semi_anti)
+        result = abi.NestedLoopResult()
+        result.mem, result.left_pos, result.right_pos, result.capacity = abi.MEM_DEVICE, out.left_pointer, None if semi_anti else out.right_pointer, out.capacity
+        status = lib.hy_join_nested_loop(left.handle, right.handle, mode, condition, predicates, n_secondary, C.byref(result))
+        if status == abi.ERR_CAPACITY and attempt == 0:
+            out.close()
+            capacity = int(result.n_pairs)
+            continue
+        if status != abi.OK:
+            out.close()
+        abi.check(status)
+        out.n_pairs = int(result.n_pairs)
+        return out
+
+
 def string_rank_column(segments, dictionaries):
     """A DictionarySegment<pmr_string> column (string_keys.encode_string_column) as a sort key: the same attribute vectors over dictionaries
     of the strings' ranks among all of the column's distinct strings in byte order (StringRanks) -> (HostColumn of int64, StringRanks)."""

@@ -675,6 +675,47 @@ typedef struct hy_sort_merge_result {
 hy_status hy_join_sort_merge(const hy_column* left, const hy_column* right, uint32_t mode, uint32_t condition, hy_sort_merge_result* result);
 hy_status hy_join_sort_merge_count(const hy_column* left, const hy_column* right, uint32_t mode, uint32_t condition, uint64_t* n_pairs);
 
+/* ---- JoinNestedLoop (replaces JoinNestedLoop::_on_execute, join_nested_loop.cpp: the third join the translator tries,
+ * lqp_translator.cpp:389-410, whose supports() is `return true` -- every shape JoinHash and JoinSortMerge refuse) ---------------------------
+ * left <condition> right AND every secondary predicate, all pairs compared on the device.
+ *   mode       HY_JOIN_INNER, LEFT, RIGHT, FULL_OUTER, SEMI, ANTI_NULL_AS_FALSE, ANTI_NULL_AS_TRUE (HY_JOIN_CROSS is Product: HY_ERR_UNSUPPORTED)
+ *   condition  HY_PRED_EQUALS .. HY_PRED_GREATER_THAN_EQUALS, under every mode
+ *   keys       numeric columns of any two types, any encoding hy_column_export reads, reference columns over host or device PosLists; the
+ *              values are compared in their common C++ type (hy_join_predicate's rule).  NaN keys are outside the contract.
+ *   secondary  up to HY_MAX_SECONDARY_PREDICATES hy_join_predicate's, under every mode; their columns have the chunk layout of the join's
+ *              input tables (otherwise HY_ERR_INVALID)
+ * NULL rule (join_nested_loop.cpp:67-79, multi_predicate_join_evaluator.hpp:44-54): a NULL on either side of the primary or of a secondary
+ * predicate fails that predicate -- under HY_JOIN_ANTI_NULL_AS_TRUE it satisfies it instead.
+ * HY_ERR_UNSUPPORTED: string columns, MVCC columns, dictionaries without values, 2^32 rows or more on a side, rows(left) x rows(right) above
+ * HY_NLJ_MAX_COMPARISONS (a kernel on a shared device must not run for many seconds), temporaries above HY_NLJ_MAX_TEMPORARY_BYTES -- all
+ * decided before any kernel runs.
+ * Order of the output == the reference's (join_nested_loop.cpp:141-236, a single-threaded walk): parity is byte for byte.  Let O be the left
+ * input and I the right one; under HY_JOIN_RIGHT they are swapped, the primary condition and every secondary predicate flipped (:130-139).
+ *   1. for every chunk co of O, for every chunk ci of I, for every row i of co, for every row j of ci in offset order: the pair (i, j) if it
+ *      satisfies all predicates;
+ *   2. LEFT / RIGHT / FULL_OUTER: behind all pairs of co the rows of co that matched nothing, in offset order, NULL_ROW_ID on the other side;
+ *   3. FULL_OUTER: at the very end the rows of I that matched nothing, in position order, NULL_ROW_ID on the other side;
+ *   4. SEMI / ANTI_*: no pairs; the left rows that matched (SEMI) or did not (ANTI_*) in position order, in left_pos only.
+ * left_pos always holds RowIDs of the LEFT input (also under HY_JOIN_RIGHT), right_pos of the RIGHT input; a RowID is {chunk, offset} of the
+ * input column, as for hy_join_hash.
+ * A result that does not fit `capacity` is HY_ERR_CAPACITY: nothing is written and n_pairs reports what is needed (decided after the counting
+ * passes, before any emitting kernel; hy_join_nested_loop_count runs exactly those passes).  The lists lie on 8-byte boundaries (otherwise
+ * HY_ERR_INVALID, nothing written).  mem = HY_MEM_DEVICE: the lists stay in HBM for the next operator.  Returns when the lists are complete. */
+#define HY_NLJ_MAX_COMPARISONS 250000000000ull   /* rows(left) x rows(right) of one call: under 2 s at the measured 1.35 * 10^11 comparisons per second */
+#define HY_NLJ_MAX_TEMPORARY_BYTES (1ull << 31)   /* the call's exported operands, counters and offsets in device memory */
+typedef struct hy_nested_loop_result {
+  uint32_t mem;            /* HY_MEM_HOST | HY_MEM_DEVICE */
+  uint32_t reserved;
+  hy_row_id* left_pos;     /* [capacity] */
+  hy_row_id* right_pos;    /* [capacity]; Semi / Anti*: unused, may be NULL */
+  uint64_t capacity;
+  uint64_t n_pairs;        /* out: rows written, or needed with HY_ERR_CAPACITY */
+} hy_nested_loop_result;
+hy_status hy_join_nested_loop(const hy_column* left, const hy_column* right, uint32_t mode, uint32_t condition, const hy_join_predicate* secondary,
+                              uint32_t n_secondary, hy_nested_loop_result* result);
+hy_status hy_join_nested_loop_count(const hy_column* left, const hy_column* right, uint32_t mode, uint32_t condition, const hy_join_predicate* secondary,
+                                    uint32_t n_secondary, uint64_t* n_pairs);
+
 /* write_output_chunks' chunking of a join result (join_output_writing.cpp:245-296; JoinHash always allows the merge,
  * join_hash.cpp:563): one output chunk per non-empty PosList of slice_offsets[0 .. n_slices], after merging a PosList of fewer
  * than 1000 pairs with its successors while the sum stays below 4000.  chunk_offsets (room for n_slices + 1 values) receives
