@@ -14,8 +14,11 @@
 //   pk_scan    one workgroup per partition: exclusive prefix of its row of counts (elements and pairs); the workgroup
 //              that finishes last plans the output (partition origins, PosLists per group, capacity check, mailbox)
 //   pk_emit    one workgroup per tile: re-evaluates the rows (one dependent load per row: cheaper than handing 6 bytes
-//              per row from pass 1 to pass 2), ranks the pairs of a partition with ONE returning LDS atomic per pair,
-//              stages them partition by partition in LDS and writes contiguous runs with 16-byte stores.  8192-row
+//              per row from pass 1 to pass 2) in the specialisation for the tile's stored width (pk_tile_rows: 1-, 2-,
+//              4-byte words; sixteen LDS reads, one wait, sixteen table loads, no branch per round), ranks the pairs of
+//              a partition with ONE returning LDS atomic per pair on the counter whose LDS address the lookup left
+//              behind, stages them partition by partition in LDS through the same addresses and writes contiguous runs
+//              with 16-byte stores.  8192-row
 //              tiles make the runs 2 KB at config 3 (32 of the 128 partitions are populated): the tile size is the
 //              lever on the write rate, tools/hbm_write.hip
 //   pk_cuts    one workgroup per output PosList: the row of its first element
@@ -541,150 +544,204 @@ __global__ __launch_bounds__(PK_SCAN_THREADS) void pk_scan(PkArgs a) {
 // hands every lane ITS rows (row k * 64 + lane in round k: the order the ranking needs) through a wave-private LDS block.  Two
 // coalesced loads per lane instead of sixteen 2-byte ones, and a prefetched tile costs eight to sixteen registers.
 // A piece is loaded if its first row exists (a partial tile's last piece reads < 16 bytes past the rows: inside the segment's padding).
-struct PkWords { u32x4_t piece[4]; };
-__device__ __forceinline__ void pk_load_words(const SliceView& view, uint32_t wave, uint32_t lane, PkWords& words) {
-  const uint32_t width = view.kind == VIEW_FOR8 ? 1u : view.kind == VIEW_FOR16 ? 2u : 4u;
+// WIDTH: bytes per stored word (1, 2: FrameOfReference offsets; 4: 4-byte offsets or int32 values).  A tile's kind is the same for the
+// whole workgroup: pk_tile_rows picks the specialisation once, and inside it nothing asks for the kind again.
+template <uint32_t WIDTH>
+struct PkWords { u32x4_t piece[WIDTH]; };
+template <uint32_t WIDTH>
+__device__ __forceinline__ void pk_load_words(const SliceView& view, uint32_t wave, uint32_t lane, PkWords<WIDTH>& words) {
   const uint32_t first = wave * PK_WAVE_ROWS + lane * PK_ROUNDS;          // of the lane's 16 rows, in the tile
-  const char* base = static_cast<const char*>(view.data) + static_cast<size_t>(view.row_begin + first) * width;
-  const uint32_t rows_per_piece = 16 / width;
+  const char* base = static_cast<const char*>(view.data) + static_cast<size_t>(view.row_begin + first) * WIDTH;
+  constexpr uint32_t rows_per_piece = 16 / WIDTH;
 #pragma unroll
-  for (uint32_t p = 0; p < 4; ++p) {
+  for (uint32_t p = 0; p < WIDTH; ++p) {
     words.piece[p] = u32x4_t{0, 0, 0, 0};
     // (global, not flat: a flat load also counts on lgkmcnt)
     typedef const __attribute__((address_space(1))) u32x4_t* global_words;
-    if (p < width && first + p * rows_per_piece < view.row_count) words.piece[p] = *(global_words)(base + p * 16);
+    if (first + p * rows_per_piece < view.row_count) words.piece[p] = *(global_words)(base + p * 16);
   }
 }
 
 // The lane's words go into the wave's LDS block (`block`: 4 KB that belong to this wave for the moment) ...
-__device__ __forceinline__ void pk_words_to_block(const SliceView& view, const PkWords& words, uint32_t* block, uint32_t lane) {
-  const uint32_t width = view.kind == VIEW_FOR8 ? 1u : view.kind == VIEW_FOR16 ? 2u : 4u;
-  u32x4_t* mine = reinterpret_cast<u32x4_t*>(reinterpret_cast<char*>(block) + lane * PK_ROUNDS * width);
+template <uint32_t WIDTH>
+__device__ __forceinline__ void pk_words_to_block(const PkWords<WIDTH>& words, uint32_t* block, uint32_t lane) {
+  u32x4_t* mine = reinterpret_cast<u32x4_t*>(reinterpret_cast<char*>(block) + lane * PK_ROUNDS * WIDTH);
 #pragma unroll
-  for (uint32_t p = 0; p < 4; ++p) {
-    if (p < width) mine[p] = words.piece[p];
-  }
+  for (uint32_t p = 0; p < WIDTH; ++p) mine[p] = words.piece[p];
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ... and come back as the stored words of the lane's rows: row k * 64 + lane of the wave's block in round k.
-__device__ __forceinline__ uint32_t pk_block_word(const SliceView& view, const uint32_t* block, uint32_t lane, uint32_t k) {
-  if (view.kind == VIEW_FOR16) return reinterpret_cast<const uint16_t*>(block)[k * 64 + lane];
-  if (view.kind == VIEW_FOR8) return reinterpret_cast<const uint8_t*>(block)[k * 64 + lane];
-  return block[k * 64 + lane];
+// ... and come back as the stored words of the lane's rows: row k * 64 + lane of the wave's block in round k (one address register per
+// lane, the round in the instruction's offset).
+template <uint32_t WIDTH>
+__device__ __forceinline__ uint32_t pk_block_word(const uint32_t* block, uint32_t lane, uint32_t k) {
+  if constexpr (WIDTH == 2) return reinterpret_cast<const uint16_t*>(block)[k * 64 + lane];
+  else if constexpr (WIDTH == 1) return reinterpret_cast<const uint8_t*>(block)[k * 64 + lane];
+  else return block[k * 64 + lane];
 }
 
-// Keys, rank-table entries, the rows' fate -- HALVES == 2: eight rows at a time (two table round trips instead of one, half the
-// registers at the peak).
-// meta[k] = partition | null_partner << 9 | emit << 10 (INVALID_PARTITION: the row is not materialised); rank[k] = the partner's rank.
-// MASKS: pass 1 was pk_count_lds -- a row's found / materialised bits come from `tile_masks` (the tile's 2 x PK_TILE / 8 bytes), only rows
-// with a partner read their table entry (the others read entry 0: one line for all of them), the Bloom filter is not asked again.
-// RANKS (Inner joins): pass 1 was pk_count<true> -- a row's rank (or PK_NO_RANK) comes from `tile_ranks`, no table entry is read; a row
-// without a partner emits nothing in an Inner join, whether it counted as materialised is pass 1's business.
-template <bool INNER, uint32_t HALVES, bool MASKS = false, bool RANKS = false>
-__device__ __forceinline__ void pk_lookup_rows(const PkArgs& a, const SliceView& view, const uint32_t* block, uint32_t wave, uint32_t lane, uint32_t (&meta)[PK_ROUNDS],
-                                               uint32_t (&rank)[PK_ROUNDS], const uint8_t* tile_masks = nullptr, const uint32_t* tile_ranks = nullptr) {
-  constexpr uint32_t N = PK_ROUNDS / HALVES;
-  const uint32_t row_count = view.row_count;
-  const uint32_t wave_first = wave * PK_WAVE_ROWS;
-  const uint32_t bias = view.kind == VIEW_INT32 ? 0u : static_cast<uint32_t>(static_cast<const int32_t*>(view.aux)[(view.row_begin + (wave_first < row_count ? wave_first : 0u)) / HY_FOR_BLOCK_SIZE]);
-  const uint32_t origin = static_cast<uint32_t>(a.rank.key_min), range = static_cast<uint32_t>(a.rank.range);
-  const uint32_t mask = a.radix_bits ? (1u << a.radix_bits) - 1 : 0u;
-  // MASKS: the wave's 1024 rows are 32 words of found bits and 32 of materialised bits; lane l < 32 holds found word l, lane 32 + l
-  // materialised word l; row k * 64 + lane sits in word 2 k + lane / 32, bit lane % 32
-  uint32_t mask_word = 0;
-  if constexpr (MASKS) mask_word = reinterpret_cast<const uint32_t*>(tile_masks + (lane < 32 ? 0u : PK_TILE / 8))[wave * (PK_WAVE_ROWS / 32) + (lane & 31)];
-#pragma unroll
-  for (uint32_t h = 0; h < HALVES; ++h) {
-    uint32_t raw[N];
-    u32x2_t entry[N];
-    uint32_t valid = 0, found = 0;
-    if constexpr (RANKS) {
-      static_assert(INNER && !MASKS, "ranks are handed over by Inner joins on the global-table kernels");
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        const uint32_t r = wave_first + (h * N + j) * 64 + lane;
-        raw[j] = pk_block_word(view, block, lane, h * N + j) + bias;
-        rank[h * N + j] = r < row_count ? tile_ranks[r] : PK_NO_RANK;
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        if (wave_first + (h * N + j) * 64 + lane < row_count) valid |= 1u << j;
-        if (rank[h * N + j] != PK_NO_RANK) found |= 1u << j;
-      }
-    } else if constexpr (MASKS) {
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        const uint32_t k = h * N + j;
-        const uint32_t found_word = lane < 32 ? __builtin_amdgcn_readlane(mask_word, 2 * k) : __builtin_amdgcn_readlane(mask_word, 2 * k + 1);
-        const uint32_t valid_word = lane < 32 ? __builtin_amdgcn_readlane(mask_word, 32 + 2 * k) : __builtin_amdgcn_readlane(mask_word, 32 + 2 * k + 1);
-        found |= ((found_word >> (lane & 31)) & 1u) << j;
-        valid |= ((valid_word >> (lane & 31)) & 1u) << j;
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        raw[j] = pk_block_word(view, block, lane, h * N + j) + bias;
-        const uint32_t distance = raw[j] - origin;
-        entry[j] = *reinterpret_cast<const u32x2_t*>(reinterpret_cast<const char*>(a.rank.entries) + (((found >> j) & 1) ? (distance >> 5) * 8u : 0u));
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        const uint32_t bit = (raw[j] - origin) & 31;
-        rank[h * N + j] = entry[j].y + __popc(entry[j].x & ((1u << bit) - 1));
-      }
-    } else {
-#pragma unroll
-    for (uint32_t j = 0; j < N; ++j) {
-      raw[j] = pk_block_word(view, block, lane, h * N + j) + bias;   // the key's low 32 bits
-      const uint32_t distance = raw[j] - origin;                     // (32-bit: both sides' keys are int32 values, pk_path in run_join)
-      entry[j] = *reinterpret_cast<const u32x2_t*>(reinterpret_cast<const char*>(a.rank.entries) + (distance <= range ? (distance >> 5) * 8u : 0u));
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < N; ++j) {
-      const uint32_t distance = raw[j] - origin;
-      const uint32_t bit = distance & 31;
-      const bool in = wave_first + (h * N + j) * 64 + lane < row_count;
-      if (in) valid |= 1u << j;
-      if (in && distance <= range && ((entry[j].x >> bit) & 1)) found |= 1u << j;
-      rank[h * N + j] = entry[j].y + __popc(entry[j].x & ((1u << bit) - 1));
-    }
-    if (a.build_bloom && !a.keep_nulls && __any((valid & ~found) != 0)) {   // join_hash_steps.hpp:354-358
-#pragma unroll
-      for (uint32_t j = 0; j < N; ++j) {
-        if (((valid & ~found) >> j) & 1) { if (!pk_bloom_test(a, raw[j])) valid &= ~(1u << j); }
-      }
-    }
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < N; ++j) {
-      bool null_partner;
-      const bool emit = pk_emits<INNER>(a.mode, (found >> j) & 1, &null_partner);
-      meta[h * N + j] = (valid >> j) & 1 ? (raw[j] & mask) | (null_partner ? 0x200u : 0u) | (emit ? 0x400u : 0u) : INVALID_PARTITION;
-    }
-    if (h + 1 < HALVES) __builtin_amdgcn_sched_barrier(0);   // (the second half's loads must not move up: that is the point)
+// An LDS word by its 32-bit LDS address: what pk_emit keeps per row between the lookup, the ranking (b) and the staging (d), so that
+// neither forms the address of the row's (wave, partition) counter again.
+typedef __attribute__((address_space(3))) uint32_t pk_lds_word;
+__device__ __forceinline__ uint32_t pk_lds_address(uint32_t* word) { return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((pk_lds_word*)word)); }
+__device__ __forceinline__ pk_lds_word* pk_lds_pointer(uint32_t address) { return reinterpret_cast<pk_lds_word*>(static_cast<uintptr_t>(address)); }
+// pk_emit's view of its wave: where the counters of its partitions and its spare counter (rows without a pair) lie, and what comes back
+// beside the rows' counters -- bit k: the pair of round k has a null partner (outer joins).
+struct PkStageTarget { uint32_t counters, spare, null_partners; };
+
+// Bit (position & 31) of a rank-table entry's presence word, and the set bits below it: one bit-field extract each (the instruction
+// takes the low five bits of the position itself).
+__device__ __forceinline__ bool pk_bit(uint32_t word, uint32_t position) { return __builtin_amdgcn_ubfe(word, position, 1u) != 0; }
+__device__ __forceinline__ uint32_t pk_bits_below(uint32_t word, uint32_t position) { return __popc(__builtin_amdgcn_ubfe(word, 0u, position)); }
+
+// One row's fate, from what the lookup found out about it.
+// STAGE (pk_emit): meta = the LDS address of the counter the row's pair is ranked on -- (wave, partition) if the row emits a pair, the
+// wave's spare counter if it does not; whether such a row counts as materialised is pass 1's business.
+// else (the cuts): meta = partition | null_partner << 9 | emit << 10 (INVALID_PARTITION: the row is not materialised).
+template <bool INNER, bool STAGE>
+__device__ __forceinline__ uint32_t pk_row_meta(const PkArgs& a, uint32_t key, uint32_t mask, bool valid, bool found, uint32_t k, PkStageTarget& target) {
+  bool null_partner;
+  const bool emit = pk_emits<INNER>(a.mode, found, &null_partner);
+  if constexpr (STAGE) {
+    if constexpr (!INNER) target.null_partners |= null_partner ? 1u << k : 0u;   // (read for rows that emit only)
+    return (INNER ? found : valid && emit) ? target.counters + 4 * (key & mask) : target.spare;   // (Inner: a row with a partner exists)
+  } else {
+    return valid ? (key & mask) | (null_partner ? 0x200u : 0u) | (emit ? 0x400u : 0u) : INVALID_PARTITION;
   }
 }
 
-// ---- evaluation of a tile's rows (cuts) --------------------------------------------------------------------------------------
+// Keys, rank-table entries, the rows' fate: sixteen LDS reads, sixteen table loads and their evaluation as straight-line code, one
+// specialisation per stored width.  meta[k]: pk_row_meta; rank[k] = the partner's rank.
+// MASKS: pass 1 was pk_count_lds -- a row's found / materialised bits come from `tile_masks` (the tile's 2 x PK_TILE / 8 bytes), only rows
+// with a partner read their table entry (the others read entry 0: one line for all of them), the Bloom filter is not asked again.
+// RANKS (Inner joins): pass 1 was pk_count<true> -- a row's rank (or PK_NO_RANK) comes from `tile_ranks`, no table entry is read; a row
+// without a partner emits nothing in an Inner join.
+// An Inner join's pk_emit (STAGE) does not ask which partner-less rows are materialised: it has no Bloom re-test at all.  Everywhere
+// else the re-test is a cold path behind one __any.
+template <uint32_t WIDTH, bool INNER, bool STAGE, bool MASKS = false, bool RANKS = false>
+__device__ __forceinline__ void pk_lookup_rows(const PkArgs& a, const SliceView& view, const uint32_t* block, uint32_t wave, uint32_t lane, uint32_t (&meta)[PK_ROUNDS],
+                                               uint32_t (&rank)[PK_ROUNDS], PkStageTarget& target, const uint8_t* tile_masks = nullptr, const uint32_t* tile_ranks = nullptr) {
+  const uint32_t row_count = view.row_count;
+  const uint32_t wave_first = wave * PK_WAVE_ROWS;
+  // (int32 values have no block minimum, and no array of them; they share WIDTH == 4 with 4-byte offsets: one scalar branch per tile)
+  // (the block minimum is one value for the wave: through the scalar cache, as in pk_count_wave -- immutable like the views)
+  typedef __attribute__((address_space(4))) const uint32_t constant_word;
+  const uint32_t bias = WIDTH == 4 && view.kind == VIEW_INT32 ? 0u : ((constant_word*)view.aux)[__builtin_amdgcn_readfirstlane(static_cast<int>((view.row_begin + (wave_first < row_count ? wave_first : 0u)) / HY_FOR_BLOCK_SIZE))];
+  const uint32_t origin = static_cast<uint32_t>(a.rank.key_min), range = static_cast<uint32_t>(a.rank.range);
+  const uint32_t mask = a.radix_bits ? (1u << a.radix_bits) - 1 : 0u;
+  // row k * 64 + lane of the wave exists: lane < wave_rows - 64 k (signed: a tile has 8192 rows)
+  const int32_t wave_rows = __builtin_amdgcn_readfirstlane(row_count > wave_first ? static_cast<int32_t>(row_count - wave_first) : 0);
+  uint32_t raw[PK_ROUNDS];   // the keys' low 32 bits
+#pragma unroll
+  for (uint32_t k = 0; k < PK_ROUNDS; ++k) raw[k] = pk_block_word<WIDTH>(block, lane, k) + bias;
+  if constexpr (RANKS) {
+    static_assert(INNER && STAGE && !MASKS, "ranks are handed over by Inner joins on the global-table kernels, to pk_emit");
+#pragma unroll
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+      const bool in = static_cast<int32_t>(lane) < wave_rows - static_cast<int32_t>(k * 64);
+      rank[k] = in ? tile_ranks[wave_first + k * 64 + lane] : PK_NO_RANK;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) meta[k] = pk_row_meta<INNER, STAGE>(a, raw[k], mask, true, rank[k] != PK_NO_RANK, k, target);
+  } else if constexpr (MASKS) {
+    // the wave's 1024 rows are 32 words of found bits and 32 of materialised bits; lane l < 32 holds found word l, lane 32 + l
+    // materialised word l; row k * 64 + lane sits in word 2 k + lane / 32, bit lane % 32
+    const uint32_t mask_word = reinterpret_cast<const uint32_t*>(tile_masks + (lane < 32 ? 0u : PK_TILE / 8))[wave * (PK_WAVE_ROWS / 32) + (lane & 31)];
+    uint32_t valid = 0, found = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+      const uint32_t found_word = lane < 32 ? __builtin_amdgcn_readlane(mask_word, 2 * k) : __builtin_amdgcn_readlane(mask_word, 2 * k + 1);
+      const uint32_t valid_word = lane < 32 ? __builtin_amdgcn_readlane(mask_word, 32 + 2 * k) : __builtin_amdgcn_readlane(mask_word, 32 + 2 * k + 1);
+      found |= ((found_word >> (lane & 31)) & 1u) << k;
+      valid |= ((valid_word >> (lane & 31)) & 1u) << k;
+    }
+    u32x2_t entry[PK_ROUNDS];
+#pragma unroll
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+      const uint32_t distance = raw[k] - origin;
+      entry[k] = *reinterpret_cast<const u32x2_t*>(reinterpret_cast<const char*>(a.rank.entries) + (((found >> k) & 1) ? (distance >> 5) * 8u : 0u));
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+      const uint32_t bit = raw[k] - origin;   // (its low five bits count)
+      rank[k] = entry[k].y + pk_bits_below(entry[k].x, bit);
+      meta[k] = pk_row_meta<INNER, STAGE>(a, raw[k], mask, (valid >> k) & 1, (found >> k) & 1, k, target);
+    }
+  } else {
+    u32x2_t entry[PK_ROUNDS];
+#pragma unroll
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+      const uint32_t distance = raw[k] - origin;   // (32-bit: both sides' keys are int32 values, pk_path in run_join)
+      entry[k] = *reinterpret_cast<const u32x2_t*>(reinterpret_cast<const char*>(a.rank.entries) + (distance <= range ? (distance >> 5) * 8u : 0u));
+    }
+    if constexpr (INNER && STAGE) {   // a row's pair or nothing: no list of the materialised rows, no Bloom re-test
+#pragma unroll
+      for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+        const uint32_t distance = raw[k] - origin, bit = distance;   // (of a position, pk_bit and pk_bits_below take the low five bits)
+        const bool in = static_cast<int32_t>(lane) < wave_rows - static_cast<int32_t>(k * 64);
+        rank[k] = entry[k].y + pk_bits_below(entry[k].x, bit);
+        meta[k] = pk_row_meta<INNER, STAGE>(a, raw[k], mask, in, in && distance <= range && pk_bit(entry[k].x, bit), k, target);
+      }
+    } else {
+      uint32_t valid = 0, found = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+        const uint32_t distance = raw[k] - origin, bit = distance;   // (of a position, pk_bit and pk_bits_below take the low five bits)
+        const bool in = static_cast<int32_t>(lane) < wave_rows - static_cast<int32_t>(k * 64);
+        if (in) valid |= 1u << k;
+        if (in && distance <= range && pk_bit(entry[k].x, bit)) found |= 1u << k;
+        rank[k] = entry[k].y + pk_bits_below(entry[k].x, bit);
+      }
+      if (a.build_bloom && !a.keep_nulls && __any((valid & ~found) != 0)) {   // join_hash_steps.hpp:354-358
+#pragma unroll
+        for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+          if (((valid & ~found) >> k) & 1) { if (!pk_bloom_test(a, raw[k])) valid &= ~(1u << k); }
+        }
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < PK_ROUNDS; ++k) meta[k] = pk_row_meta<INNER, STAGE>(a, raw[k], mask, (valid >> k) & 1, (found >> k) & 1, k, target);
+    }
+  }
+}
+
+// ---- evaluation of a tile's rows ---------------------------------------------------------------------------------------------
 // Wave w owns rows [1024 w, 1024 (w + 1)) of the tile, row k * 64 + lane in round k: row order = (wave, round, lane).
+// From the stored words to meta / rank, for one stored width: request, hand round through the wave's LDS block, look up.
+template <uint32_t WIDTH, bool INNER, bool STAGE, bool MASKS, bool RANKS>
+__device__ __forceinline__ void pk_tile_rows_of_width(const PkArgs& a, const SliceView& view, uint32_t* block, uint32_t wave, uint32_t lane, uint32_t (&meta)[PK_ROUNDS],
+                                                      uint32_t (&rank)[PK_ROUNDS], PkStageTarget& target, const uint8_t* tile_masks, const uint32_t* tile_ranks) {
+  PkWords<WIDTH> words;
+  pk_load_words<WIDTH>(view, wave, lane, words);
+  pk_words_to_block<WIDTH>(words, block, lane);
+  pk_lookup_rows<WIDTH, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
+}
+
+// The one place that asks for the tile's kind (the same for every lane of the workgroup).
+template <bool INNER, bool STAGE, bool MASKS = false, bool RANKS = false>
+__device__ __forceinline__ void pk_tile_rows(const PkArgs& a, const SliceView& view, uint32_t* block, uint32_t wave, uint32_t lane, uint32_t (&meta)[PK_ROUNDS], uint32_t (&rank)[PK_ROUNDS],
+                                             PkStageTarget& target, const uint8_t* tile_masks = nullptr, const uint32_t* tile_ranks = nullptr) {
+  if (view.kind == VIEW_FOR8) pk_tile_rows_of_width<1, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
+  else if (view.kind == VIEW_FOR16) pk_tile_rows_of_width<2, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
+  else pk_tile_rows_of_width<4, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
+}
+
+// The cuts' evaluation: meta in the form the cuts count on.
 template <bool INNER, bool MASKS = false>
 __device__ __forceinline__ void pk_evaluate(const PkArgs& a, const SliceView& view, uint32_t* block, uint32_t wave, uint32_t lane, uint32_t (&meta)[PK_ROUNDS], uint32_t (&rank)[PK_ROUNDS],
                                             const uint8_t* tile_masks = nullptr) {
-  PkWords words;
-  pk_load_words(view, wave, lane, words);
-  pk_words_to_block(view, words, block, lane);
-  pk_lookup_rows<INNER, 1, MASKS>(a, view, block, wave, lane, meta, rank, tile_masks);
+  PkStageTarget none = {0, 0, 0};
+  pk_tile_rows<INNER, false, MASKS>(a, view, block, wave, lane, meta, rank, none, tile_masks);
 }
 
 // ---- pass 2 -------------------------------------------------------------------------------------------------------------------
-// LDS, in 4-byte words: staged pairs {row | partition << 13 | null partner << 21, partner's rank} (one spare slot per
+// LDS, in 4-byte words: staged pairs {row | null partner << 21 (never set by an Inner join), partner's rank} (one spare slot per
 // partition, see rt_probe_emit) | pairs per (wave, partition), then the first slot of (wave, partition); after the staging the
 // copy-out's line table (PK_TILE / 16 lines x 2 words) in the same words | global pair index of staging slot 0 per partition | first
 // global pair index of the run per partition, then its first interior line (bits 16..) and its pairs (bits 0..15) | wave totals of
 // the partition scan, reserved slots and interior lines.
-constexpr uint32_t PK_STAGE_ROW = 0x1FFF, PK_STAGE_PARTITION_SHIFT = 13, PK_STAGE_NULL = 1u << 21;
+constexpr uint32_t PK_STAGE_ROW = 0x1FFF, PK_STAGE_NULL = 1u << 21;
 constexpr uint32_t PK_LINES = PK_TILE / 16;   // 128-byte output lines of 16 pairs a tile's pairs can fill
 __host__ __device__ constexpr size_t pk_wave_pairs_words(uint32_t partitions) {
   return size_t{PK_WAVES} * partitions > 2 * size_t{PK_LINES} ? size_t{PK_WAVES} * partitions : 2 * size_t{PK_LINES};
@@ -791,7 +848,7 @@ __device__ __forceinline__ void pk_copy_out(const PkArgs& a, const u32x2_t* s_st
 
 // One tile from its stored words to its pairs in the output.  The five phases are separated by four workgroup barriers.
 template <bool INNER, bool MASKS = false, bool RANKS = false>
-__device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, const SliceView& view, const PkWords& words, uint32_t cell_pairs, uint32_t cell_base,
+__device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, const SliceView& view, uint32_t cell_pairs, uint32_t cell_base,
                                              uint32_t* join_smem, uint32_t tid, uint32_t lane, uint32_t wave) {
   const uint32_t partitions = 1u << a.radix_bits;
   const uint32_t stage_slots = PK_TILE + partitions + 2;
@@ -803,10 +860,14 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   const uint32_t scan_waves = partitions > 64 ? partitions / 64 : 1;
   if (a.trace && tid == 0) a.trace[tile * 6 + 0] = wall_clock64();
   for (uint32_t i = tid; i < PK_WAVES * partitions; i += PK_THREADS) s_wave_pairs[i] = 0;
-  uint32_t meta[PK_ROUNDS], rank[PK_ROUNDS];
-  pk_words_to_block(view, words, join_smem + wave * 1024, lane);   // (the staging area is not in use yet: 4 KB of it per wave)
-  pk_lookup_rows<INNER, 1, MASKS, RANKS>(a, view, join_smem + wave * 1024, wave, lane, meta, rank, MASKS ? a.row_masks + static_cast<size_t>(tile) * (2 * PK_TILE / 8) : nullptr,
-                                         RANKS ? a.row_ranks + static_cast<size_t>(tile) * PK_TILE : nullptr);
+  if (tid < PK_WAVES) s_scratch[16 + tid] = 0;   // (the spare counters: what they hand back in (b) stays below a wave's 1024 rows)
+  // counter[k]: the LDS address of the counter row k * 64 + lane is ranked on -- the wave's counter of the row's partition, or (no pair)
+  // the wave's spare counter; formed once, by the lookup, for (b) and (d)
+  uint32_t counter[PK_ROUNDS], rank[PK_ROUNDS];
+  PkStageTarget target = {pk_lds_address(s_wave_pairs + wave * partitions), pk_lds_address(s_scratch + 16 + wave), 0u};
+  // (the rows' words go round through the staging area, which is not in use yet: 4 KB of it per wave)
+  pk_tile_rows<INNER, true, MASKS, RANKS>(a, view, join_smem + wave * 1024, wave, lane, counter, rank, target, MASKS ? a.row_masks + static_cast<size_t>(tile) * (2 * PK_TILE / 8) : nullptr,
+                                          RANKS ? a.row_ranks + static_cast<size_t>(tile) * PK_TILE : nullptr);
   __builtin_amdgcn_wave_barrier();
   if (a.trace && tid == 0) a.trace[tile * 6 + 1] = wall_clock64();
   // (a) reserve pairs + 1 slots per non-empty partition, and number its interior lines: scan inside each wave now, across waves in (c)
@@ -822,22 +883,19 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   // (b) rank inside the wave: ONE returning LDS atomic per pair.  The LDS serves the lanes of one instruction that hit the same
   // counter in lane order and a wave's LDS instructions in program order (lds_atomic_order_probe checks it once per process; the
   // host takes the general kernels where it does not hold), so a lane gets back the pairs of its partition in lower lanes and
-  // earlier rounds.  The rank moves into meta[k] bits 11..
-  {
-    // (rows without a pair count on a spare counter of the wave: sixteen atomics back to back, no branch around any of them)
-    uint32_t before[PK_ROUNDS];
-    uint32_t* mine = s_wave_pairs + wave * partitions;
-    uint32_t* spare = s_scratch + 16 + wave;
-    if constexpr (MASKS) {   // (a selective join: most rows have no pair -- on one spare counter their atomics would serialise, 64 lanes deep)
+  // earlier rounds.
+  // (rows without a pair count on a spare counter of the wave: sixteen atomics back to back, no branch around any of them and no
+  //  vector instruction between them -- the addresses are the lookup's)
+  uint32_t before[PK_ROUNDS];
+  if constexpr (MASKS) {   // (a selective join: most rows have no pair -- on one spare counter their atomics would serialise, 64 lanes deep)
 #pragma unroll
-      for (uint32_t k = 0; k < PK_ROUNDS; ++k) { before[k] = 0; if (meta[k] & 0x400u) before[k] = atomicAdd(mine + (meta[k] & 0xFF), 1u); }
-      (void)spare;
-    } else {
-#pragma unroll
-    for (uint32_t k = 0; k < PK_ROUNDS; ++k) before[k] = atomicAdd((meta[k] & 0x400u) ? mine + (meta[k] & 0xFF) : spare, 1u);
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+      before[k] = 0;
+      if (counter[k] != target.spare) before[k] = __hip_atomic_fetch_add(pk_lds_pointer(counter[k]), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+  } else {
 #pragma unroll
-    for (uint32_t k = 0; k < PK_ROUNDS; ++k) meta[k] |= (meta[k] & 0x400u) ? before[k] << 11 : 0u;
+    for (uint32_t k = 0; k < PK_ROUNDS; ++k) before[k] = __hip_atomic_fetch_add(pk_lds_pointer(counter[k]), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   if (a.trace && tid == 0) a.trace[tile * 6 + 2] = wall_clock64();
@@ -859,16 +917,25 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
     }
     if (tid == 0) s_scratch[8] = s_scratch[0] + (scan_waves > 1 ? s_scratch[1] : 0u) + (scan_waves > 2 ? s_scratch[2] : 0u) + (scan_waves > 3 ? s_scratch[3] : 0u);   // every reserved slot, every interior line
   }
+  // (a spare counter becomes the "first slot" of its wave's rows without a pair: the slot behind every run, whatever (b) handed back)
+  if (tid >= PK_THREADS - PK_WAVES) s_scratch[16 + (PK_THREADS - 1 - tid)] = stage_slots - 1;
   __syncthreads();
   if (a.trace && tid == 0) a.trace[tile * 6 + 3] = wall_clock64();
   // (d) stage
-  // (rows without a pair write the slot behind every run: no branch here either)
+  // The counter a row was ranked on now holds the first slot of its (wave, partition): sixteen reads back to back, one wait, then an
+  // add and a shift per row.  Rows without a pair write the slot behind every run -- their "first slot" is that slot already, the
+  // minimum takes what (b) handed back off again: no compare, no select, no branch.  An Inner join's record is {row, rank}, the
+  // others add the null-partner bit.
+  const uint32_t first_row = wave * PK_WAVE_ROWS + lane;
+  uint32_t first_slot[PK_ROUNDS];
+#pragma unroll
+  for (uint32_t k = 0; k < PK_ROUNDS; ++k) first_slot[k] = *pk_lds_pointer(counter[k]);
 #pragma unroll
   for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
-    const uint32_t partition = meta[k] & 0xFF;
-    const uint32_t slot = (meta[k] & 0x400u) ? s_wave_pairs[wave * partitions + partition] + (meta[k] >> 11) : stage_slots - 1;
-    const uint32_t r = wave * PK_WAVE_ROWS + k * 64 + lane;
-    s_stage[slot] = u32x2_t{r | (partition << PK_STAGE_PARTITION_SHIFT) | ((meta[k] & 0x200u) ? PK_STAGE_NULL : 0u), rank[k]};
+    const uint32_t slot = first_slot[k] + before[k] < stage_slots - 1 ? first_slot[k] + before[k] : stage_slots - 1;
+    uint32_t tag = first_row + k * 64;
+    if constexpr (!INNER) tag |= ((target.null_partners >> k) & 1) ? PK_STAGE_NULL : 0u;
+    s_stage[slot] = u32x2_t{tag, rank[k]};
   }
   __syncthreads();
   if (a.trace && tid == 0) a.trace[tile * 6 + 4] = wall_clock64();
@@ -979,8 +1046,6 @@ __global__ __launch_bounds__(PK_THREADS, HY_PK_WAVES_PER_SIMD) void pk_emit(PkAr
   const size_t cell = static_cast<size_t>(tid < partitions ? tid : 0) * a.stride + tile;
   const uint32_t cell_pairs = tid < partitions ? a.counts[cell] >> 16 : 0;
   const uint32_t cell_base = static_cast<uint32_t>(a.origin_pairs[tid < partitions ? tid : 0]) + a.rel_pairs[cell];
-  PkWords words;
-  pk_load_words(view, wave, lane, words);
-  pk_emit_tile<INNER, MASKS, RANKS>(a, tile, view, words, cell_pairs, cell_base, join_smem, tid, lane, wave);
+  pk_emit_tile<INNER, MASKS, RANKS>(a, tile, view, cell_pairs, cell_base, join_smem, tid, lane, wave);
 }
 
