@@ -122,6 +122,26 @@ class Operand(C.Structure):
     _fields_ = [("column", C.c_void_p), ("literal_type", C.c_uint32), ("literal", Value)]
 
 
+# hy_projection_expression: a whole expression tree per output column
+MAX_PROJECTION_NODES, MAX_PROJECTION_DEPTH, MAX_PROJECTION_COLUMNS, MAX_PROJECTION_TESTS = 32, 6, 8, 4
+(PROJ_COLUMN, PROJ_LITERAL, PROJ_ARITHMETIC, PROJ_COMPARISON, PROJ_COLUMN_TEST, PROJ_IS_NULL, PROJ_IS_NOT_NULL, PROJ_AND, PROJ_OR, PROJ_UNARY_MINUS, PROJ_CASE,
+ PROJ_BETWEEN, PROJ_CAST, PROJ_EXTRACT, PROJ_FUNCTION, PROJ_SUBQUERY, PROJ_PARAMETER) = range(17)
+
+
+class ProjectionNode(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("op", C.c_uint32), ("index", C.c_uint32), ("literal_type", C.c_uint32), ("literal", Value)]
+
+
+class ProjectionTest(C.Structure):
+    _fields_ = [("column", C.c_void_p), ("predicate", Predicate), ("in_list", C.POINTER(InList))]
+
+
+class ProjectionProgram(C.Structure):
+    """hy_projection_program: postfix, at most MAX_PROJECTION_DEPTH stack entries."""
+    _fields_ = [("n_nodes", C.c_uint32), ("n_columns", C.c_uint32), ("n_tests", C.c_uint32), ("reserved", C.c_uint32),
+                ("columns", C.c_void_p * MAX_PROJECTION_COLUMNS), ("tests", ProjectionTest * MAX_PROJECTION_TESTS), ("nodes", ProjectionNode * MAX_PROJECTION_NODES)]
+
+
 UNION_FORCE_SORT = 1      # hy_union_positions flags
 UNION_MAX_CLUSTERS = 8
 SORT_LIMIT_FORCE_FULL_SORT, SORT_LIMIT_FORCE_SELECT = 1, 2   # hy_sort_limit flags
@@ -229,6 +249,7 @@ SYMBOLS = [
     ("hy_in_list_cast", C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("hy_table_scan_columns", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_projection_arithmetic", C.c_int32, [C.c_uint32, C.POINTER(Operand), C.POINTER(Operand), C.POINTER(C.c_void_p)]),
+    ("hy_projection_expression", C.c_int32, [C.POINTER(ProjectionProgram), C.POINTER(C.c_void_p)]),
     ("hy_column_read_chunk", C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("hy_column_data_type", C.c_uint32, [C.c_void_p]),
     ("hy_column_chunk_rows", C.c_uint32, [C.c_void_p, C.c_uint32]),

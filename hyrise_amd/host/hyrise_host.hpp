@@ -19,6 +19,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstring>
+#include <deque>
 #include <fstream>
 #include <map>
 #include <mutex>
@@ -1222,7 +1223,7 @@ class TableScan : public AbstractReadOnlyOperator {
             else if (std::holds_alternative<std::string>(element)) strings.push_back(std::get<std::string>(element));   // (a number equals no string)
           }
           n_values = static_cast<uint32_t>(strings.size());
-          resolve_string_list(in_table, strings, value_ids);
+          resolve_string_list(in_table, _column_id, strings, value_ids);
         } else {
           std::vector<uint32_t> types;
           std::vector<hy_value> literals;
@@ -1263,14 +1264,14 @@ class TableScan : public AbstractReadOnlyOperator {
         // ColumnLikeTableScanImpl (column_like_table_scan_impl.cpp:28-36)
         Assert(in_table->column_data_type(_column_id) == DataType::String, "LIKE operator only applicable on string columns.");
         Assert(std::holds_alternative<std::string>(_value), "Right parameter must be a string.");
-        find_matches_in_dictionaries(in_table, match_words, match_word_offsets, predicate);
+        find_matches_in_dictionaries(in_table, _column_id, _condition, _value, match_words, match_word_offsets, predicate);
       } else if (!null_test) {
         const auto column_type = in_table->column_data_type(_column_id);
         if (column_type == DataType::String) {
           // ColumnVsValueTableScanImpl asserts matching types (column_vs_value_table_scan_impl.cpp:34-36)
           Assert(data_type_from_all_type_variant(_value) == DataType::String, "Cannot scan: column and value data type do not match.");
           predicate.value_type = static_cast<uint32_t>(DataType::String);
-          resolve_string_literal(in_table, lower, upper, found, predicate);
+          resolve_string_literal(in_table, _column_id, _condition, _value, _value2, lower, upper, found, predicate);
         } else {
           // TableScan::create_impl casts the literal(s) to the column's type, adjusting the condition where only that is
           // lossless (table_scan.cpp:336-366, 406-448); where neither works the stock ExpressionEvaluator scan runs.
@@ -1409,10 +1410,11 @@ class TableScan : public AbstractReadOnlyOperator {
     offsets[in_table->chunk_count()] = written;
   }
 
+ public:   // (static: Projection lowers its string column tests through the same three functions)
   // DictionarySegment<pmr_string>: resolve the literal per chunk like _get_search_value_id
   // (column_vs_value_table_scan_impl.cpp:211-226) and column_between_table_scan_impl.cpp:112-124.
-  void resolve_string_literal(const std::shared_ptr<const Table>& in_table, std::vector<uint32_t>& lower, std::vector<uint32_t>& upper,
-                              std::vector<uint8_t>& found, hy_predicate& predicate) const {
+  static void resolve_string_literal(const std::shared_ptr<const Table>& in_table, ColumnID _column_id, PredicateCondition _condition, const AllTypeVariant& _value, const std::optional<AllTypeVariant>& _value2, std::vector<uint32_t>& lower,
+                                     std::vector<uint32_t>& upper, std::vector<uint8_t>& found, hy_predicate& predicate) {
     auto data_table = in_table;
     auto column_id = _column_id;
     if (in_table->type() == TableType::References && in_table->chunk_count()) {
@@ -1446,7 +1448,7 @@ class TableScan : public AbstractReadOnlyOperator {
 
   // DictionarySegment<pmr_string>: every element's value id in every data chunk's dictionary (lower_bound plus an equality check), or
   // HY_INVALID_VALUE_ID -- hy_in_list::per_chunk_value_ids, [n_data_chunks x n_values]
-  void resolve_string_list(const std::shared_ptr<const Table>& in_table, const std::vector<std::string>& strings, std::vector<uint32_t>& value_ids) const {
+  static void resolve_string_list(const std::shared_ptr<const Table>& in_table, ColumnID _column_id, const std::vector<std::string>& strings, std::vector<uint32_t>& value_ids) {
     auto data_table = in_table;
     auto column_id = _column_id;
     if (in_table->type() == TableType::References && in_table->chunk_count()) {
@@ -1467,8 +1469,8 @@ class TableScan : public AbstractReadOnlyOperator {
 
   // _find_matches_in_dictionary per data chunk (column_like_table_scan_impl.cpp:142-159): bit i of chunk c's words says
   // whether dictionary entry i satisfies the (possibly negated) pattern; the device tests value ids against it.
-  void find_matches_in_dictionaries(const std::shared_ptr<const Table>& in_table, std::vector<uint64_t>& words, std::vector<uint64_t>& word_offsets,
-                                    hy_predicate& predicate) const {
+  static void find_matches_in_dictionaries(const std::shared_ptr<const Table>& in_table, ColumnID _column_id, PredicateCondition _condition, const AllTypeVariant& _value,
+                                           std::vector<uint64_t>& words, std::vector<uint64_t>& word_offsets, hy_predicate& predicate) {
     auto data_table = in_table;
     auto column_id = _column_id;
     if (in_table->type() == TableType::References && in_table->chunk_count()) {
@@ -1493,6 +1495,7 @@ class TableScan : public AbstractReadOnlyOperator {
     predicate.match_word_offsets = word_offsets.data();
   }
 
+ private:
   ColumnID _column_id;
   PredicateCondition _condition;
   AllTypeVariant _value;
@@ -2903,6 +2906,238 @@ class StarJoinAggregate : public AbstractReadOnlyOperator {
   std::vector<StarDimension> _dimensions;
   std::vector<StarColumn> _groupby;
   std::vector<StarAggregate> _aggregates;
+};
+
+// ---- Projection (operators/projection.hpp, projection.cpp) ------------------------------------------------------------------------------
+// A minimal expression tree (expression/*.hpp): what hy_projection_expression evaluates.  A predicate between a STRING column and string
+// literals (binary, LIKE family, In / NotIn) becomes a column test, lowered through TableScan's own functions.
+enum class ExpressionType : uint8_t { Column, Value, Arithmetic, Predicate, IsNull, IsNotNull, And, Or, UnaryMinus, Case };
+struct Expression {
+  ExpressionType type;
+  ColumnID column_id = 0;                      // Column
+  AllTypeVariant value = NullValue{};          // Value
+  ArithmeticOperator arithmetic_operator = ArithmeticOperator::Addition;
+  PredicateCondition condition = PredicateCondition::Equals;
+  std::vector<std::shared_ptr<const Expression>> arguments;   // Predicate: left, right (In / NotIn: left, then the list's elements)
+};
+using ExpressionPtr = std::shared_ptr<const Expression>;
+inline ExpressionPtr column_(ColumnID column_id) { auto e = std::make_shared<Expression>(); e->type = ExpressionType::Column; e->column_id = column_id; return e; }
+inline ExpressionPtr value_(AllTypeVariant value) { auto e = std::make_shared<Expression>(); e->type = ExpressionType::Value; e->value = std::move(value); return e; }
+inline ExpressionPtr null_() { return value_(NullValue{}); }
+inline ExpressionPtr expression_of(ExpressionType type, std::vector<ExpressionPtr> arguments) {
+  auto e = std::make_shared<Expression>(); e->type = type; e->arguments = std::move(arguments); return e;
+}
+inline ExpressionPtr arithmetic_(ArithmeticOperator op, ExpressionPtr l, ExpressionPtr r) {
+  auto e = std::make_shared<Expression>(); e->type = ExpressionType::Arithmetic; e->arithmetic_operator = op; e->arguments = {std::move(l), std::move(r)}; return e;
+}
+inline ExpressionPtr predicate_(PredicateCondition condition, std::vector<ExpressionPtr> arguments) {
+  auto e = std::make_shared<Expression>(); e->type = ExpressionType::Predicate; e->condition = condition; e->arguments = std::move(arguments); return e;
+}
+inline ExpressionPtr and_(ExpressionPtr l, ExpressionPtr r) { return expression_of(ExpressionType::And, {std::move(l), std::move(r)}); }
+inline ExpressionPtr or_(ExpressionPtr l, ExpressionPtr r) { return expression_of(ExpressionType::Or, {std::move(l), std::move(r)}); }
+inline ExpressionPtr is_null_(ExpressionPtr x) { return expression_of(ExpressionType::IsNull, {std::move(x)}); }
+inline ExpressionPtr is_not_null_(ExpressionPtr x) { return expression_of(ExpressionType::IsNotNull, {std::move(x)}); }
+inline ExpressionPtr unary_minus_(ExpressionPtr x) { return expression_of(ExpressionType::UnaryMinus, {std::move(x)}); }
+inline ExpressionPtr case_(ExpressionPtr when, ExpressionPtr then, ExpressionPtr otherwise) { return expression_of(ExpressionType::Case, {std::move(when), std::move(then), std::move(otherwise)}); }
+
+class Projection : public AbstractReadOnlyOperator {
+ public:
+  Projection(std::shared_ptr<const AbstractOperator> in, std::vector<ExpressionPtr> expressions, std::vector<std::string> names = {})
+      : AbstractReadOnlyOperator(std::move(in)), _expressions(std::move(expressions)), _names(std::move(names)) {}
+  const std::string& name() const override { static const std::string n = "Projection"; return n; }
+
+ protected:
+  // projection.cpp:56-240 in its three steps: forward unmodified columns, evaluate the others, build the output table
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto in_table = left_input_table();
+    const auto chunk_count = in_table->chunk_count();
+    // ---- "ForwardUnmodifiedColumns" (projection.cpp:69-100): a PQPColumnExpression shares its segments, reference segments stay reference segments
+    bool any_computed = false;
+    for (const auto& e : _expressions) any_computed = any_computed || e->type != ExpressionType::Column;
+    // ---- evaluate (projection.cpp:129-190: one ExpressionEvaluator per chunk; here: one hy_projection_expression per computed column)
+    std::vector<std::shared_ptr<const DeviceColumnOwner>> owners(_expressions.size());
+    TableColumnDefinitions definitions;
+    for (size_t i = 0; i < _expressions.size(); ++i) {
+      const auto& e = _expressions[i];
+      const std::string name = i < _names.size() ? _names[i] : (e->type == ExpressionType::Column ? in_table->column_name(e->column_id) : "expression_" + std::to_string(i));
+      if (e->type == ExpressionType::Column) {
+        const auto type = in_table->column_data_type(e->column_id);
+        definitions.push_back({name, type, in_table->column_is_nullable(e->column_id)});
+        // ---- build (projection.cpp:192-236): the output is a data table when a column was computed; a forwarded REFERENCE segment cannot
+        // live in it (:201-215 materialises it through the evaluator).  Numeric: the column itself as a one-node program -- hy_column_gather's
+        // result with the input's chunk layout kept --, strings from the RowIDs on the host (below).
+        if (any_computed && in_table->type() == TableType::References && type != DataType::String && chunk_count) owners[i] = evaluate(in_table, e);
+        continue;
+      }
+      Assert(chunk_count > 0, "Projection: an expression over a table without chunks has no device column to read");
+      owners[i] = evaluate(in_table, e);
+      definitions.push_back({name, static_cast<DataType>(hy_column_data_type(owners[i]->handle)), true});   // (the evaluator's results carry a null vector)
+    }
+    const auto resident_segment = [](DataType type, const std::shared_ptr<const DeviceColumnOwner>& owner, uint32_t chunk, ChunkOffset size) -> std::shared_ptr<AbstractSegment> {
+      switch (type) {
+        case DataType::Int: return std::make_shared<DeviceValueSegment<int32_t>>(owner, chunk, size);
+        case DataType::Long: return std::make_shared<DeviceValueSegment<int64_t>>(owner, chunk, size);
+        case DataType::Float: return std::make_shared<DeviceValueSegment<float>>(owner, chunk, size);
+        default: return std::make_shared<DeviceValueSegment<double>>(owner, chunk, size);
+      }
+    };
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    for (ChunkID chunk_id = 0; chunk_id < chunk_count; ++chunk_id) {
+      const auto chunk_in = in_table->get_chunk(chunk_id);
+      Segments segments;
+      for (size_t i = 0; i < _expressions.size(); ++i) {
+        if (owners[i]) { segments.push_back(resident_segment(definitions[i].data_type, owners[i], chunk_id, chunk_in->size())); continue; }
+        const auto segment = chunk_in->get_segment(_expressions[i]->column_id);
+        if (!any_computed || in_table->type() == TableType::Data) { segments.push_back(segment); continue; }   // shared
+        std::vector<std::vector<AllTypeVariant>> cells;   // a string column behind a PosList, materialised from the RowIDs on the host
+        for (ChunkOffset r = 0; r < chunk_in->size(); ++r) cells.push_back({(*segment)[r]});
+        segments.push_back(make_value_segment<std::string>(cells, ColumnID{0}, true));
+        definitions[i].nullable = true;
+      }
+      chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+    }
+    const auto type = any_computed ? TableType::Data : in_table->type();   // a projection that only forwards outputs a table of the input's type
+    return std::make_shared<Table>(std::move(definitions), type, std::move(chunks));
+  }
+
+ private:
+  struct Lowered {   // the program and everything its pointers name
+    hy_projection_program program{};
+    std::vector<std::shared_ptr<DeviceColumn>> columns;
+    std::deque<std::vector<uint32_t>> words32;
+    std::deque<std::vector<uint8_t>> bytes;
+    std::deque<std::vector<uint64_t>> words64;
+    std::deque<hy_in_list> lists;
+  };
+
+  static bool is_string_column(const Table& table, const Expression& e) { return e.type == ExpressionType::Column && table.column_data_type(e.column_id) == DataType::String; }
+
+  void push(Lowered& l, const hy_projection_node& node) const {
+    if (l.program.n_nodes >= HY_MAX_PROJECTION_NODES) Fail("Projection: the expression has more than HY_MAX_PROJECTION_NODES nodes");
+    l.program.nodes[l.program.n_nodes++] = node;
+  }
+
+  void lower(const std::shared_ptr<const Table>& in_table, const Expression& e, Lowered& l) const {
+    hy_projection_node node{};
+    switch (e.type) {
+      case ExpressionType::Column: {
+        const auto column = device_column(in_table, e.column_id);
+        uint32_t index = 0;
+        while (index < l.columns.size() && l.columns[index]->handle != column->handle) ++index;
+        if (index == l.columns.size()) {
+          if (index >= HY_MAX_PROJECTION_COLUMNS) Fail("Projection: the expression reads more than HY_MAX_PROJECTION_COLUMNS columns");
+          l.columns.push_back(column);
+          l.program.columns[index] = column->handle;
+          l.program.n_columns = index + 1;
+        }
+        node.kind = HY_PROJ_COLUMN;
+        node.index = index;
+        break;
+      }
+      case ExpressionType::Value:
+        node.kind = HY_PROJ_LITERAL;
+        node.literal_type = static_cast<uint32_t>(data_type_from_all_type_variant(e.value));
+        if (e.value.index() >= 1 && e.value.index() <= 4) node.literal = to_hy_value(e.value);
+        break;
+      case ExpressionType::Predicate:
+        if (is_string_column(*in_table, *e.arguments[0])) { lower_column_test(in_table, e, l); return; }
+        if (e.condition == PredicateCondition::IsNull || e.condition == PredicateCondition::IsNotNull) {
+          lower(in_table, *e.arguments[0], l);
+          node.kind = e.condition == PredicateCondition::IsNull ? HY_PROJ_IS_NULL : HY_PROJ_IS_NOT_NULL;
+          break;
+        }
+        Assert(e.arguments.size() == 2, "Projection: a numeric predicate is binary (Between, In: HY_ERR_UNSUPPORTED on this path)");
+        lower(in_table, *e.arguments[0], l);
+        lower(in_table, *e.arguments[1], l);
+        node.kind = HY_PROJ_COMPARISON;
+        node.op = static_cast<uint32_t>(e.condition);
+        break;
+      default: {
+        if ((e.type == ExpressionType::IsNull || e.type == ExpressionType::IsNotNull) && is_string_column(*in_table, *e.arguments[0])) {   // string IS [NOT] NULL: a column test
+          Expression test;
+          test.type = ExpressionType::Predicate;
+          test.condition = e.type == ExpressionType::IsNull ? PredicateCondition::IsNull : PredicateCondition::IsNotNull;
+          test.arguments = e.arguments;
+          lower_column_test(in_table, test, l);
+          return;
+        }
+        for (const auto& argument : e.arguments) lower(in_table, *argument, l);
+        switch (e.type) {
+          case ExpressionType::Arithmetic: node.kind = HY_PROJ_ARITHMETIC; node.op = static_cast<uint32_t>(e.arithmetic_operator); break;
+          case ExpressionType::IsNull: node.kind = HY_PROJ_IS_NULL; break;
+          case ExpressionType::IsNotNull: node.kind = HY_PROJ_IS_NOT_NULL; break;
+          case ExpressionType::And: node.kind = HY_PROJ_AND; break;
+          case ExpressionType::Or: node.kind = HY_PROJ_OR; break;
+          case ExpressionType::UnaryMinus: node.kind = HY_PROJ_UNARY_MINUS; break;
+          default: node.kind = HY_PROJ_CASE; break;
+        }
+      }
+    }
+    push(l, node);
+  }
+
+  // string column <condition> 'literal' | LIKE 'pattern' | IN ('a', ...): the hy_predicate / hy_in_list TableScan makes for the same scan
+  void lower_column_test(const std::shared_ptr<const Table>& in_table, const Expression& e, Lowered& l) const {
+    const auto column_id = e.arguments[0]->column_id;
+    if (l.program.n_tests >= HY_MAX_PROJECTION_TESTS) Fail("Projection: the expression has more than HY_MAX_PROJECTION_TESTS column tests");
+    l.columns.push_back(device_column(in_table, column_id));   // (kept alive; not one of program.columns)
+    hy_projection_test& test = l.program.tests[l.program.n_tests];
+    test.column = l.columns.back()->handle;
+    test.predicate.condition = static_cast<uint32_t>(e.condition);
+    test.predicate.column_is_nullable = in_table->column_is_nullable(column_id);
+    const auto literal = [&](size_t i) -> const AllTypeVariant& {
+      Assert(e.arguments.size() > i && e.arguments[i]->type == ExpressionType::Value, "Projection: a string column is compared with literals");
+      return e.arguments[i]->value;
+    };
+    const bool like = e.condition >= PredicateCondition::Like && e.condition <= PredicateCondition::NotLikeInsensitive;
+    if (e.condition == PredicateCondition::In || e.condition == PredicateCondition::NotIn) {
+      std::vector<std::string> strings;
+      for (size_t i = 1; i < e.arguments.size(); ++i) {
+        Assert(std::holds_alternative<std::string>(literal(i)), "Projection: IN over a string column takes string literals (NULL elements: the stock evaluator)");
+        strings.push_back(std::get<std::string>(literal(i)));
+      }
+      l.words32.emplace_back();
+      TableScan::resolve_string_list(in_table, column_id, strings, l.words32.back());
+      hy_in_list list{};
+      list.value_type = HY_TYPE_STRING;
+      list.n_values = static_cast<uint32_t>(strings.size());
+      list.negated = e.condition == PredicateCondition::NotIn;
+      list.column_is_nullable = test.predicate.column_is_nullable;
+      list.per_chunk_value_ids = l.words32.back().data();
+      l.lists.push_back(list);
+      test.in_list = &l.lists.back();
+    } else if (like) {
+      Assert(std::holds_alternative<std::string>(literal(1)), "Right parameter must be a string.");
+      l.words64.emplace_back();
+      l.words64.emplace_back();
+      TableScan::find_matches_in_dictionaries(in_table, column_id, e.condition, literal(1), l.words64[l.words64.size() - 2], l.words64.back(), test.predicate);
+    } else if (e.condition != PredicateCondition::IsNull && e.condition != PredicateCondition::IsNotNull) {
+      Assert(data_type_from_all_type_variant(literal(1)) == DataType::String, "Cannot scan: column and value data type do not match.");
+      std::optional<AllTypeVariant> second;
+      if (is_between(e.condition)) second = literal(2);   // (the library refuses Between: the status reaches the caller as a Fail)
+      l.words32.emplace_back();
+      l.words32.emplace_back();
+      l.bytes.emplace_back();
+      TableScan::resolve_string_literal(in_table, column_id, e.condition, literal(1), second, l.words32[l.words32.size() - 2], l.words32.back(), l.bytes.back(), test.predicate);
+    } else {
+      test.predicate.value_type = HY_TYPE_STRING;
+    }
+    hy_projection_node node{};
+    node.kind = HY_PROJ_COLUMN_TEST;
+    node.index = l.program.n_tests++;
+    push(l, node);
+  }
+
+  std::shared_ptr<const DeviceColumnOwner> evaluate(const std::shared_ptr<const Table>& in_table, const ExpressionPtr& e) const {
+    Lowered l;
+    lower(in_table, *e, l);
+    hy_column* column = nullptr;
+    check_status(hy_projection_expression(&l.program, &column));   // HY_ERR_UNSUPPORTED is a Fail: the mirror has no CPU operators
+    return std::make_shared<const DeviceColumnOwner>(column);
+  }
+
+  std::vector<ExpressionPtr> _expressions;
+  std::vector<std::string> _names;
 };
 
 }  // namespace hyrise_amd

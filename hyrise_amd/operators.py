@@ -542,6 +542,79 @@ def expression(tree):
     return e
 
 
+class ColumnTest:
+    """`column <predicate>` as a node of a projection program: the column and what make_predicate / string_predicate / predicate_for_column
+    (an abi.Predicate) or in_list_predicate / string_in_list_predicate (an abi.InList) produce."""
+
+    def __init__(self, column, predicate):
+        self.column, self.predicate = column, predicate
+
+
+def projection_program(tree):
+    """A whole expression tree as hy_projection_program (postfix).  tree: a column (DeviceColumn / ResultColumn), a literal (HY_TYPE_*, value),
+    None (the NULL literal), a ColumnTest, or a nested tuple whose first element names the node:
+      ("arith", abi.ARITH_*, left, right)   ("cmp", abi.PRED_*, left, right)   ("and", left, right)   ("or", left, right)
+      ("is_null", x)   ("is_not_null", x)   ("neg", x)   ("case", when, then, otherwise)
+    and, to be told HY_ERR_UNSUPPORTED by the library, ("between" | "cast" | "extract" | "function" | "subquery" | "parameter", operand...).
+    -> (abi.ProjectionProgram, what it points to: keep it alive)"""
+    program = abi.ProjectionProgram()
+    nodes, columns, tests, keep = [], [], [], []
+    named = {"and": abi.PROJ_AND, "or": abi.PROJ_OR, "is_null": abi.PROJ_IS_NULL, "is_not_null": abi.PROJ_IS_NOT_NULL, "neg": abi.PROJ_UNARY_MINUS, "case": abi.PROJ_CASE,
+             "between": abi.PROJ_BETWEEN, "cast": abi.PROJ_CAST, "extract": abi.PROJ_EXTRACT, "function": abi.PROJ_FUNCTION, "subquery": abi.PROJ_SUBQUERY,
+             "parameter": abi.PROJ_PARAMETER}
+
+    def walk(t):
+        n = abi.ProjectionNode()
+        if hasattr(t, "handle"):
+            if not any(t is c for c in columns):
+                columns.append(t)
+            n.kind, n.index = abi.PROJ_COLUMN, next(i for i, c in enumerate(columns) if c is t)
+        elif isinstance(t, ColumnTest):
+            if not any(t is known for known in tests):
+                tests.append(t)
+            n.kind, n.index = abi.PROJ_COLUMN_TEST, next(i for i, known in enumerate(tests) if known is t)
+        elif t is None or not isinstance(t[0], str):
+            literal = _operand(t)
+            n.kind, n.literal_type, n.literal = abi.PROJ_LITERAL, literal.literal_type, literal.literal
+        elif t[0] in ("arith", "cmp"):
+            walk(t[2])
+            walk(t[3])
+            n.kind, n.op = (abi.PROJ_ARITHMETIC if t[0] == "arith" else abi.PROJ_COMPARISON), t[1]
+        else:
+            for operand in t[1:]:
+                walk(operand)
+            n.kind = named[t[0]]
+        nodes.append(n)
+
+    walk(tree)
+    # over a limit: the true counts go to the library, which refuses them before it reads the arrays (only what fits is filled in)
+    program.n_nodes, program.n_columns, program.n_tests = len(nodes), len(columns), len(tests)
+    nodes, columns, tests = nodes[:abi.MAX_PROJECTION_NODES], columns[:abi.MAX_PROJECTION_COLUMNS], tests[:abi.MAX_PROJECTION_TESTS]
+    for i, n in enumerate(nodes):
+        program.nodes[i] = n
+    for i, c in enumerate(columns):
+        program.columns[i] = c.handle if not isinstance(c.handle, C.c_void_p) else c.handle.value
+    for i, t in enumerate(tests):
+        handle = t.column.handle
+        program.tests[i].column = handle if not isinstance(handle, C.c_void_p) else handle.value
+        if isinstance(t.predicate, abi.InList):
+            program.tests[i].in_list = C.pointer(t.predicate)
+        else:
+            program.tests[i].predicate = t.predicate
+        keep.append(t.predicate)
+    return program, (keep, columns, tests)
+
+
+def projection_expression(tree):
+    """hy_projection_expression: the whole tree (projection_program) evaluated per row in one pass -> ResultColumn (stays on the device)."""
+    lib = abi.load_library()
+    program, keep = projection_program(tree)
+    handle = C.c_void_p()
+    abi.check(lib.hy_projection_expression(C.byref(program), C.byref(handle)))
+    del keep
+    return ResultColumn(handle)
+
+
 PAIR_LIST_PERIOD = 2 << 20          # the two output PosLists of a join are written at the same pair index at the same time: when their
 PAIR_LIST_OFFSET = 5 << 18          # addresses are congruent modulo 2 MiB the two streams meet in the same memory channels -- pk_emit takes
                                     # 306 - 315 us; 1.25 MiB apart (mod 2 MiB) 274 - 283 us (tools/join_placement.py, profiles/r03_join_placement.txt)

@@ -249,6 +249,23 @@ def q1_fused(columns, ship_to=DAY_1998_09_02):
                                   _q1_aggregates(columns["l_quantity"], columns["l_extendedprice"], columns["l_discount"], disc_price, charge), group_capacity=4096)
 
 
+def q1_charge_chain(columns):
+    """l_extendedprice * (1 - l_discount) * (1 + l_tax) as the plan's four ArithmeticExpressions, three dependent hy_projection_arithmetic
+    calls behind the two that make its operands (run_q1's projections over DeviceColumns).  -> ResultColumn"""
+    from .operators import projection_arithmetic
+    one = (abi.TYPE_INT, 1)
+    disc_price = projection_arithmetic(abi.ARITH_MUL, columns["l_extendedprice"], projection_arithmetic(abi.ARITH_SUB, one, columns["l_discount"]))
+    return projection_arithmetic(abi.ARITH_MUL, disc_price, projection_arithmetic(abi.ARITH_ADD, one, columns["l_tax"]))
+
+
+def q1_charge_program(columns):
+    """The same column as ONE program (hy_projection_expression): three columns read, one written, no intermediate.  -> ResultColumn"""
+    from .operators import projection_expression
+    one = (abi.TYPE_INT, 1)
+    return projection_expression(("arith", abi.ARITH_MUL, ("arith", abi.ARITH_MUL, columns["l_extendedprice"], ("arith", abi.ARITH_SUB, one, columns["l_discount"])),
+                                  ("arith", abi.ARITH_ADD, one, columns["l_tax"])))
+
+
 # ---- rows of the reference's own generator --------------------------------------------------------------------------------
 def convert_money(cents):
     """tpch_table_generator.cpp:90-94: float(dollars) + float(cents) / 100.0f, in float32 arithmetic."""

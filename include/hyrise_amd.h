@@ -563,6 +563,71 @@ hy_status hy_column_read_chunk(const hy_column* column, uint32_t chunk, void* va
 uint32_t hy_column_data_type(const hy_column* column);
 uint32_t hy_column_chunk_rows(const hy_column* column, uint32_t chunk);
 
+/* ---- Projection: one whole expression tree per output column, in one pass (operators/projection.cpp; the cell rules of
+ * expression/evaluation/expression_evaluator.cpp and expression/evaluation/expression_functors.hpp) ----------------------------
+ * A postfix program over the rows of one table: every node pops its operands from a stack of at most HY_MAX_PROJECTION_DEPTH
+ * values and pushes one; exactly one value is left at the end -- the output cell.  One kernel launch evaluates the program for
+ * all chunks and writes ONE result column; no intermediate column exists.  Node kinds, with the reference's semantics:
+ *   COLUMN        columns[index]: a numeric column of the table -- data or reference segments of every supported encoding, host or
+ *                 device PosLists, a NULL RowID is a NULL cell, caller-owned device columns (what hy_projection_arithmetic reads).
+ *                 All columns of a program, tested ones included, share one chunk layout (HY_ERR_INVALID otherwise).
+ *   LITERAL       literal_type / literal: Int, Long, Float, Double or HY_TYPE_NULL.
+ *   ARITHMETIC    op = HY_ARITH_*: left op right, hy_projection_arithmetic's rules cell by cell (expression_functors.hpp:127-213).
+ *   COMPARISON    op = HY_PRED_EQUALS .. HY_PRED_GREATER_THAN_EQUALS between two numeric operands.  The result is Int (the evaluator's
+ *                 Bool = int32_t) 0 or 1, computed in std::common_type_t of the operand types (expression_functors.hpp:90-116: Int against
+ *                 Float compares as float, Long against Float as float); > and >= are the swapped < and <= (expression_evaluator.cpp:73-90);
+ *                 NULL if either side is NULL.
+ *   COLUMN_TEST   tests[index]: a column and a predicate as hy_table_scan takes them (literal already cast, per-chunk value ids or match
+ *                 bitmaps for dictionary string columns), or an IN list over a dictionary string column as hy_table_scan_in_list takes it.
+ *                 Evaluated through the scan's normalised per-chunk jobs.  The result is Int 0 or 1 and NULL WHERE THE CELL IS NULL (the
+ *                 evaluator's rule; a scan drops what is not TRUE); HY_PRED_IS_NULL / IS_NOT_NULL never yield NULL.
+ *   IS_NULL / IS_NOT_NULL   of the top of the stack: Int 0 or 1, never NULL (expression_evaluator.cpp:382-402).
+ *   AND / OR      ternary logic of TernaryAndEvaluator / TernaryOrEvaluator (expression_functors.hpp:41-84); operands are Int, non-zero is true.
+ *   UNARY_MINUS   the operand's type; NULL stays NULL (expression_evaluator.cpp:965-988).
+ *   CASE          pops otherwise, then, when (pushed in the order when, then, otherwise).  Result type expression_common_type(then,
+ *                 otherwise), a NULL literal taking the other branch's type; a `when` that is NULL or 0 selects `otherwise`; the chosen
+ *                 branch's value is static_cast to the result type, the NULL flag is the chosen branch's (expression_evaluator.cpp:726-759).
+ *                 A chained CASE is a CASE in the `otherwise` position.
+ * Floating point: every operation is a single IEEE operation in the stated type, nothing is reassociated or contracted.  NaN inputs
+ * are outside the contract of COMPARISON (the swapped forms differ from the direct ones only there).
+ * HY_ERR_UNSUPPORTED (message in hy_last_error): string columns outside COLUMN_TEST; the kinds HY_PROJ_BETWEEN .. HY_PROJ_PARAMETER and
+ * Between conditions in a COLUMN_TEST (_evaluate_between_expression, expression_evaluator.cpp:590-656, yields FALSE, not NULL, for a
+ * NULL operand on its fast path and two comparisons otherwise: left out, not approximated); IN lists over other than dictionary string
+ * columns; unencoded string segments; MVCC columns; more than HY_MAX_PROJECTION_NODES nodes, HY_MAX_PROJECTION_DEPTH stack entries,
+ * HY_MAX_PROJECTION_COLUMNS distinct columns or HY_MAX_PROJECTION_TESTS tests.
+ * HY_ERR_INVALID: null arguments; a malformed program (stack underflow, not exactly one value left, an index out of range, operands of a
+ * type the node does not take, a type that cannot be deduced); a program without any column (the evaluator's one-row result is the
+ * adapter's business, as for hy_projection_arithmetic).
+ * The result is a device-resident column in hy_projection_arithmetic's layout: unencoded value segments of the result type, chunked like
+ * the input columns, every chunk with a null vector (tail bits zero; NULL cells hold T{}).  On error *result is NULL. */
+#define HY_MAX_PROJECTION_NODES 32
+#define HY_MAX_PROJECTION_DEPTH 6
+#define HY_MAX_PROJECTION_COLUMNS 8
+#define HY_MAX_PROJECTION_TESTS 4
+enum { HY_PROJ_COLUMN = 0, HY_PROJ_LITERAL = 1, HY_PROJ_ARITHMETIC = 2, HY_PROJ_COMPARISON = 3, HY_PROJ_COLUMN_TEST = 4, HY_PROJ_IS_NULL = 5,
+       HY_PROJ_IS_NOT_NULL = 6, HY_PROJ_AND = 7, HY_PROJ_OR = 8, HY_PROJ_UNARY_MINUS = 9, HY_PROJ_CASE = 10,
+       /* named so that a translated plan can hand them over and be told: HY_ERR_UNSUPPORTED */
+       HY_PROJ_BETWEEN = 11, HY_PROJ_CAST = 12, HY_PROJ_EXTRACT = 13, HY_PROJ_FUNCTION = 14, HY_PROJ_SUBQUERY = 15, HY_PROJ_PARAMETER = 16 };
+typedef struct hy_projection_node {
+  uint32_t kind;           /* HY_PROJ_* */
+  uint32_t op;             /* ARITHMETIC: HY_ARITH_*; COMPARISON: HY_PRED_* */
+  uint32_t index;          /* COLUMN: into columns[]; COLUMN_TEST: into tests[] */
+  uint32_t literal_type;   /* LITERAL */
+  hy_value literal;
+} hy_projection_node;
+typedef struct hy_projection_test {
+  const hy_column* column;
+  hy_predicate predicate;      /* read when in_list is NULL */
+  const hy_in_list* in_list;   /* or: column [NOT] IN (...) over a dictionary string column (per_chunk_value_ids) */
+} hy_projection_test;
+typedef struct hy_projection_program {
+  uint32_t n_nodes, n_columns, n_tests, reserved;
+  const hy_column* columns[HY_MAX_PROJECTION_COLUMNS];
+  hy_projection_test tests[HY_MAX_PROJECTION_TESTS];
+  hy_projection_node nodes[HY_MAX_PROJECTION_NODES];
+} hy_projection_program;
+hy_status hy_projection_expression(const hy_projection_program* program, hy_column** result);
+
 /* ---- JoinHash (replaces JoinHash::_on_execute, join_hash.cpp:116-225,270-572) ----------------------------------- */
 typedef struct hy_join_result {
   uint32_t mem;
