@@ -250,6 +250,7 @@ SYMBOLS = [
     ("hy_table_scan_columns", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_projection_arithmetic", C.c_int32, [C.c_uint32, C.POINTER(Operand), C.POINTER(Operand), C.POINTER(C.c_void_p)]),
     ("hy_projection_expression", C.c_int32, [C.POINTER(ProjectionProgram), C.POINTER(C.c_void_p)]),
+    ("hy_table_scan_expression", C.c_int32, [C.POINTER(ProjectionProgram), C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_column_read_chunk", C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("hy_column_data_type", C.c_uint32, [C.c_void_p]),
     ("hy_column_chunk_rows", C.c_uint32, [C.c_void_p, C.c_uint32]),

@@ -291,5 +291,9 @@ hy_status star_all_rows_of(const hy_column* column, DeviceBuffer& rows);   // ev
 // scan.hip: the kernels of hy_poslist_translate queued on the current stream, nothing read back -- dense_offsets: [n_chunks + 1] device words,
 // the last of them the number of RowIDs written
 hy_status poslist_translate_queued(const hy_column* scanned, const hy_scan_result* result, uint32_t layout, hy_row_id* out, uint64_t capacity, uint64_t* dense_offsets);
+// scan.hip: a scan's chunk regions in device memory -> the caller's HY_MEM_HOST result (counts, chunk states, the regions packed back to back through the
+// thread's scratch arena, behind what the scan carved from it).  d_overflow: the scan's overflow word, or nullptr
+hy_status regions_to_host_result(const hy_row_id* d_matches, const uint64_t* d_offsets, const uint32_t* d_counts, const uint8_t* d_state, uint32_t* d_overflow, uint32_t n_chunks,
+                                 bool materialize_all, hy_scan_result* result);
 
 }  // namespace hy

@@ -11,35 +11,12 @@
 // decoded once per row (the loads of all of them in flight together), the operand stack lives in registers with static indices (push
 // and pop move the slots), the node loop is uniform across the wave.  HBM-bound on data tables: bytes in (the distinct columns'
 // widths) + bytes out (the result's width) per row, no intermediate column.
-#include "hy_device.hpp"
-#include "hy_decode.hpp"
-#include "hy_arithmetic.hpp"
-#include "hy_scan_job.hpp"
+#include "hy_expression.hpp"
 
 #include <cstring>
 #include <vector>
 
 namespace hy {
-
-constexpr int PX_DEPTH = HY_MAX_PROJECTION_DEPTH, PX_COLUMNS = HY_MAX_PROJECTION_COLUMNS, PX_TESTS = HY_MAX_PROJECTION_TESTS;
-constexpr int PX_ROWS = 4;   // rows a lane evaluates side by side: row (block * PX_ROWS + i) * 256 + thread of the slice
-
-struct ExprNode {     // a node with everything the host resolved: the type it computes in and its operands' types
-  uint8_t kind;       // HY_PROJ_*
-  uint8_t op;         // HY_ARITH_* | HY_PRED_*
-  uint8_t type;       // HY_TYPE_* of the value it pushes
-  uint8_t at, bt;     // types of the operands: binary nodes left / right; CASE then / otherwise; UNARY_MINUS at
-  uint8_t index;      // COLUMN: distinct column; COLUMN_TEST: test
-  uint16_t reserved;
-  uint64_t literal;   // LITERAL: the value as the stack holds it
-};
-
-struct ExprTest {
-  const DevSegment* segments;   // the tested column (data or reference segments)
-  const ScanJob* jobs;          // per DATA chunk (prepare_scan_jobs)
-  uint32_t null_test;           // 0: a comparison / LIKE / IN; 1: IS NULL; 2: IS NOT NULL
-  uint32_t reserved;
-};
 
 struct ExprArgs {
   const DevSegment* columns[PX_COLUMNS];
@@ -52,116 +29,6 @@ struct ExprArgs {
   uint64_t* nulls;
   const uint64_t* null_base;
 };
-
-// A value on the stack: int64 (Int / Long) or the bits of a double (Float widened, Double) -- decode_rows' convention.
-__device__ __forceinline__ uint64_t value_bits(const Value& v, uint32_t type) {
-  return is_float_type(type) ? static_cast<uint64_t>(__double_as_longlong(v.f)) : static_cast<uint64_t>(v.i);
-}
-
-// One cell of a data segment against its chunk's job.  The evaluator's rule, not the scan's: *is_null where the cell is NULL, except for
-// the NULL tests themselves.
-__device__ __forceinline__ bool test_cell(const DevSegment& s, const ScanJob& job, uint32_t row, uint32_t null_test, bool* is_null) {
-  uint32_t vid = 0;
-  bool cell_null;
-  if (s.encoding == HY_ENC_DICTIONARY) {
-    vid = aload_compressed(s.data, s.width, row);
-    cell_null = vid >= s.aux_size;
-  } else {
-    cell_null = s.nulls ? ((s.nulls[row >> 6] >> (row & 63)) & 1) != 0 : false;
-  }
-  if (null_test) {   // expression_evaluator.cpp:382-402
-    *is_null = false;
-    return cell_null == (null_test == 1);
-  }
-  *is_null = cell_null;
-  if (cell_null) return false;
-  if (job.mode == JOB_ALL) return true;
-  if (job.mode == JOB_NONE || (job.flags & JF_NEVER)) return false;
-  const bool invert = job.flags & JF_INVERT;
-  bool in;
-  if (s.encoding == HY_ENC_DICTIONARY) {
-    if (job.kind == KIND_VALUE_ID_SET) return ((reinterpret_cast<const uint64_t*>(job.lo)[vid >> 6] >> (vid & 63)) & 1) != 0;
-    in = (vid - static_cast<uint32_t>(job.lo)) <= static_cast<uint32_t>(job.span);
-  } else if (s.encoding == HY_ENC_FRAME_OF_REFERENCE) {
-    const uint32_t x = aload_compressed(s.data, s.width, row) + static_cast<uint32_t>(static_cast<const int32_t*>(s.aux)[row / HY_FOR_BLOCK_SIZE]);
-    in = (x - static_cast<uint32_t>(job.lo)) <= static_cast<uint32_t>(job.span);
-  } else if (job.kind == KIND_U32) {
-    in = (static_cast<const uint32_t*>(s.data)[row] - static_cast<uint32_t>(job.lo)) <= static_cast<uint32_t>(job.span);
-  } else if (job.kind == KIND_I64) {
-    in = (static_cast<const uint64_t*>(s.data)[row] - job.lo) <= job.span;
-  } else if (job.kind == KIND_F32) {
-    const float x = static_cast<const float*>(s.data)[row];
-    const float lower = __uint_as_float(static_cast<uint32_t>(job.lo)), upper = __uint_as_float(static_cast<uint32_t>(job.span));
-    in = ((job.flags & JF_LOWER_INCL) ? x >= lower : x > lower) && ((job.flags & JF_UPPER_INCL) ? x <= upper : x < upper);
-  } else {
-    const double x = static_cast<const double*>(s.data)[row];
-    const double lower = __longlong_as_double(static_cast<long long>(job.lo)), upper = __longlong_as_double(static_cast<long long>(job.span));
-    in = ((job.flags & JF_LOWER_INCL) ? x >= lower : x > lower) && ((job.flags & JF_UPPER_INCL) ? x <= upper : x < upper);
-  }
-  return in != invert;
-}
-
-// PX_ROWS rows of a tested column: bit i of *value = the test holds, of *nulls = it is NULL.
-__device__ __forceinline__ void test_rows(const ExprTest& t, uint32_t chunk, const uint32_t (&row)[PX_ROWS], uint32_t valid, uint32_t* value, uint32_t* nulls) {
-  *value = 0;
-  *nulls = 0;
-  const DevSegment seg = t.segments[chunk];
-  if (seg.encoding != HY_ENC_REFERENCE) {   // (uniform: descriptor and job stay in scalar registers)
-    const ScanJob job = t.jobs[chunk];
-#pragma unroll
-    for (int i = 0; i < PX_ROWS; ++i) {
-      if (!((valid >> i) & 1)) continue;
-      bool is_null;
-      if (test_cell(seg, job, row[i], t.null_test, &is_null)) *value |= 1u << i;
-      if (is_null) *nulls |= 1u << i;
-    }
-    return;
-  }
-#pragma unroll 1
-  for (int i = 0; i < PX_ROWS; ++i) {   // behind a PosList: the RowID's chunk picks the job
-    if (!((valid >> i) & 1)) continue;
-    uint32_t row_i = row[0];   // (row i selected by comparisons: an index would put the rows into scratch memory)
-#pragma unroll
-    for (int j = 1; j < PX_ROWS; ++j) row_i = i == j ? row[j] : row_i;
-    hy_row_id r;
-    if (seg.data) r = static_cast<const hy_row_id*>(seg.data)[row_i];
-    else { r.chunk_id = seg.ref_chunk_id; r.chunk_offset = row_i; }
-    bool is_null = true, holds = false;
-    if (r.chunk_offset == 0xFFFFFFFFu) {   // a NULL RowID is a NULL cell
-      if (t.null_test) { is_null = false; holds = t.null_test == 1; }
-    } else {
-      holds = test_cell(seg.ref[r.chunk_id], t.jobs[r.chunk_id], r.chunk_offset, t.null_test, &is_null);
-    }
-    if (holds) *value |= 1u << i;
-    if (is_null) *nulls |= 1u << i;
-  }
-}
-
-// PX_ROWS rows of a column as (bits, NULL mask): projection.hip's operand_rows for a column.
-__device__ __forceinline__ void column_rows(const DevSegment* segments, uint32_t chunk, const uint32_t (&row)[PX_ROWS], uint32_t valid, uint64_t (&bits)[PX_ROWS], uint32_t* nulls) {
-  const uint32_t* pos_words;
-  const DevSegment segment = resolve_segment(segments[chunk], &pos_words);
-  uint32_t operand_row[PX_ROWS];
-#pragma unroll
-  for (int i = 0; i < PX_ROWS; ++i) operand_row[i] = row[i];
-  const uint32_t null_rows = pos_words ? dereference_rows<PX_ROWS>(pos_words, operand_row) : 0u;
-  if (segment.encoding == HY_ENC_REFERENCE) {   // a PosList over several chunks: RowID by RowID -- unrolled here (decode_rows walks these rows
-                                                // with an index, which would put the caller's column registers into scratch memory)
-    *nulls = 0;
-    const bool is_float = is_float_type(segment.data_type);
-#pragma unroll
-    for (int i = 0; i < PX_ROWS; ++i) {
-      bits[i] = 0;
-      if (!((valid >> i) & 1)) continue;
-      const Value v = column_value(segments, chunk, operand_row[i]);
-      if (v.is_null) *nulls |= 1u << i;
-      else bits[i] = is_float ? static_cast<uint64_t>(__double_as_longlong(v.f)) : static_cast<uint64_t>(v.i);
-    }
-  } else {
-    decode_rows<PX_ROWS>(segment, segments, chunk, operand_row, valid, bits, nulls);
-  }
-  *nulls |= null_rows;
-}
 
 // One workgroup per 8192-row slice; a thread owns rows k * 256 + tid, PX_ROWS of them at a time.  Row r of a wave's round lands in bit
 // (r % 64) of one bitmap word: a null word is one ballot.  Values are written a lane per row: consecutive lanes, consecutive cells.
@@ -186,162 +53,7 @@ __global__ __launch_bounds__(256) void projection_expression_rows(ExprArgs a) {
       if (r < slice.row_count) valid |= 1u << i;
       row[i] = slice.row_begin + (r < slice.row_count ? r : 0);
     }
-    // ---- every distinct column once, every test once ----------------------------------------------------------------------------
-    uint64_t column[PX_COLUMNS][B];
-    uint32_t column_nulls[PX_COLUMNS], test_value[PX_TESTS], test_nulls[PX_TESTS];
-#pragma unroll
-    for (int c = 0; c < PX_COLUMNS; ++c) {
-      column_nulls[c] = 0;
-#pragma unroll
-      for (int i = 0; i < B; ++i) column[c][i] = 0;
-      if (static_cast<uint32_t>(c) < a.n_columns) column_rows(a.columns[c], slice.chunk, row, valid, column[c], &column_nulls[c]);
-    }
-#pragma unroll
-    for (int t = 0; t < PX_TESTS; ++t) {
-      test_value[t] = test_nulls[t] = 0;
-      if (static_cast<uint32_t>(t) < a.n_tests && a.tests[t].segments) test_rows(a.tests[t], slice.chunk, row, valid, &test_value[t], &test_nulls[t]);
-    }
-    // ---- the program: slot 0 = top of the stack ------------------------------------------------------------------------------------
-    uint64_t s[PX_DEPTH][B];
-    uint32_t n[PX_DEPTH];
-#pragma unroll
-    for (int d = 0; d < PX_DEPTH; ++d) {
-      n[d] = 0;
-#pragma unroll
-      for (int i = 0; i < B; ++i) s[d][i] = 0;
-    }
-#pragma unroll 1
-    for (uint32_t k = 0; k < a.n_nodes; ++k) {
-      const ExprNode node = a.nodes[k];
-      const uint32_t kind = node.kind, op = node.op, type = node.type, at = node.at, bt = node.bt;
-      if (kind == HY_PROJ_COLUMN || kind == HY_PROJ_LITERAL || kind == HY_PROJ_COLUMN_TEST) {   // push
-#pragma unroll
-        for (int d = PX_DEPTH - 1; d > 0; --d) {
-          n[d] = n[d - 1];
-#pragma unroll
-          for (int i = 0; i < B; ++i) s[d][i] = s[d - 1][i];
-        }
-        if (kind == HY_PROJ_COLUMN) {
-#pragma unroll
-          for (int c = 0; c < PX_COLUMNS; ++c) {
-            if (node.index != c) continue;
-#pragma unroll
-            for (int i = 0; i < B; ++i) s[0][i] = column[c][i];
-            n[0] = column_nulls[c];
-          }
-        } else if (kind == HY_PROJ_LITERAL) {
-#pragma unroll
-          for (int i = 0; i < B; ++i) s[0][i] = node.literal;
-          n[0] = type == HY_TYPE_NULL ? 0xFFFFFFFFu : 0u;
-        } else {
-#pragma unroll
-          for (int t = 0; t < PX_TESTS; ++t) {
-            if (node.index != t) continue;
-#pragma unroll
-            for (int i = 0; i < B; ++i) s[0][i] = (test_value[t] >> i) & 1u;
-            n[0] = test_nulls[t];
-          }
-        }
-        continue;
-      }
-      if (kind == HY_PROJ_IS_NULL || kind == HY_PROJ_IS_NOT_NULL) {   // expression_evaluator.cpp:382-402: never NULL
-        const uint32_t is = kind == HY_PROJ_IS_NULL ? n[0] : ~n[0];
-#pragma unroll
-        for (int i = 0; i < B; ++i) s[0][i] = (is >> i) & 1u;
-        n[0] = 0;
-        continue;
-      }
-      if (kind == HY_PROJ_UNARY_MINUS) {   // :965-988; the NULL flags stay
-#pragma unroll
-        for (int i = 0; i < B; ++i) {
-          if (is_float_type(type)) s[0][i] ^= 0x8000000000000000ull;
-          else if (type == HY_TYPE_INT) s[0][i] = static_cast<uint64_t>(static_cast<int64_t>(static_cast<int32_t>(0u - static_cast<uint32_t>(s[0][i]))));
-          else s[0][i] = 0ull - s[0][i];
-        }
-        continue;
-      }
-      if (kind == HY_PROJ_CASE) {   // :726-759 -- when = slot 2, then = slot 1, otherwise = slot 0
-        uint32_t nulls = 0;
-#pragma unroll
-        for (int i = 0; i < B; ++i) {
-          const bool take = !((n[2] >> i) & 1) && s[2][i] != 0;
-          const Value chosen = take ? convert(as_value(s[1][i], at), at, type) : convert(as_value(s[0][i], bt), bt, type);
-          const bool is_null = ((take ? n[1] : n[0]) >> i) & 1;
-          s[0][i] = is_null ? 0 : value_bits(chosen, type);
-          if (is_null) nulls |= 1u << i;
-        }
-        n[0] = nulls;
-#pragma unroll
-        for (int d = 1; d + 2 < PX_DEPTH; ++d) {
-          n[d] = n[d + 2];
-#pragma unroll
-          for (int i = 0; i < B; ++i) s[d][i] = s[d + 2][i];
-        }
-        continue;
-      }
-      // ---- binary nodes: slot 1 <op> slot 0 -> slot 0, the slots below move up -------------------------------------------------------
-      uint32_t nulls = n[1] | n[0];
-      if (kind == HY_PROJ_ARITHMETIC) {
-        if (op <= HY_ARITH_MUL) {
-#pragma unroll
-          for (int i = 0; i < B; ++i) {
-            Value result{false, 0, 0.0};
-            if (((valid & ~nulls) >> i) & 1) arithmetic_cell(op, at, bt, type, as_value(s[1][i], at), as_value(s[0][i], bt), &result);
-            s[0][i] = value_bits(result, type);
-          }
-        } else {   // / and %: long instruction sequences -- one instance, the rows one after the other, row i selected by comparisons
-                   // (an index would put the stack into scratch memory)
-#pragma unroll 1
-          for (int i = 0; i < B; ++i) {
-            uint64_t x = s[1][0], y = s[0][0];
-#pragma unroll
-            for (int j = 1; j < B; ++j) { x = i == j ? s[1][j] : x; y = i == j ? s[0][j] : y; }
-            Value result{false, 0, 0.0};
-            bool is_null = true;
-            if (((valid & ~nulls) >> i) & 1) is_null = arithmetic_cell(op, at, bt, type, as_value(x, at), as_value(y, bt), &result);   // NULL: division / modulo by zero
-            if (is_null) nulls |= 1u << i;
-            const uint64_t bits = is_null ? 0 : value_bits(result, type);
-#pragma unroll
-            for (int j = 0; j < B; ++j) s[0][j] = i == j ? bits : s[0][j];
-          }
-        }
-      } else if (kind == HY_PROJ_COMPARISON) {   // expression_functors.hpp:90-116; > and >= are the swapped < and <= (expression_evaluator.cpp:73-90)
-        const bool swapped = op == HY_PRED_GREATER_THAN || op == HY_PRED_GREATER_THAN_EQUALS;
-        const uint32_t condition = op == HY_PRED_GREATER_THAN ? HY_PRED_LESS_THAN : op == HY_PRED_GREATER_THAN_EQUALS ? HY_PRED_LESS_THAN_EQUALS : op;
-#pragma unroll
-        for (int i = 0; i < B; ++i) {
-          const Value x = as_value(s[1][i], at), y = as_value(s[0][i], bt);
-          const bool holds = swapped ? compare_typed(condition, y, bt, x, at) : compare_typed(condition, x, at, y, bt);
-          s[0][i] = (holds && !((nulls >> i) & 1)) ? 1u : 0u;
-        }
-      } else {   // AND / OR: expression_functors.hpp:41-84
-        uint32_t a_true = 0, b_true = 0;
-#pragma unroll
-        for (int i = 0; i < B; ++i) {
-          if (s[1][i] != 0) a_true |= 1u << i;
-          if (s[0][i] != 0) b_true |= 1u << i;
-        }
-        a_true &= ~n[1];
-        b_true &= ~n[0];
-        uint32_t holds;
-        if (kind == HY_PROJ_AND) {
-          holds = a_true & b_true;
-          nulls = (n[1] & n[0]) | (a_true & n[0]) | (b_true & n[1]);
-        } else {
-          holds = a_true | b_true;
-          nulls = (n[1] | n[0]) & ~holds;
-        }
-#pragma unroll
-        for (int i = 0; i < B; ++i) s[0][i] = (holds >> i) & 1u;
-      }
-      n[0] = nulls;
-#pragma unroll
-      for (int d = 1; d + 1 < PX_DEPTH; ++d) {
-        n[d] = n[d + 1];
-#pragma unroll
-        for (int i = 0; i < B; ++i) s[d][i] = s[d + 1][i];
-      }
-    }
+#include "hy_expression_rows.hpp"
     // ---- the result: a lane per cell, a ballot per null word ---------------------------------------------------------------------------
 #pragma unroll
     for (int i = 0; i < B; ++i) {
@@ -411,27 +123,22 @@ static hy_status in_list_as_bitmaps(const hy_column* data_column, const hy_in_li
   return HY_OK;
 }
 
-}  // namespace hy
-
-using namespace hy;
-
-extern "C" {
-
-hy_status hy_projection_expression(const hy_projection_program* program, hy_column** out) {
-  if (!program || !out) return fail(HY_ERR_INVALID, "hy_projection_expression: null argument");
-  *out = nullptr;
-  if (program->n_nodes == 0) return fail(HY_ERR_INVALID, "hy_projection_expression: an empty program");
-  if (program->n_nodes > HY_MAX_PROJECTION_NODES) return fail(HY_ERR_UNSUPPORTED, "hy_projection_expression: %u nodes, at most %u are evaluated here", program->n_nodes, HY_MAX_PROJECTION_NODES);
-  if (program->n_columns > HY_MAX_PROJECTION_COLUMNS) return fail(HY_ERR_UNSUPPORTED, "hy_projection_expression: %u columns, at most %u", program->n_columns, HY_MAX_PROJECTION_COLUMNS);
-  if (program->n_tests > HY_MAX_PROJECTION_TESTS) return fail(HY_ERR_UNSUPPORTED, "hy_projection_expression: %u column tests, at most %u", program->n_tests, HY_MAX_PROJECTION_TESTS);
+// The program, checked on the host -- nothing is launched: the kernel's nodes (operand types resolved), the distinct columns, the tests'
+// predicates.  `scan`: the program is a TableScan's predicate (hy_table_scan_expression).
+hy_status check_program(const hy_projection_program* program, const char* entry, bool scan, PreparedProgram* p) {
+  if (program->n_nodes == 0) return fail(HY_ERR_INVALID, "%s: an empty program", entry);
+  if (program->n_nodes > HY_MAX_PROJECTION_NODES) return fail(HY_ERR_UNSUPPORTED, "%s: %u nodes, at most %u are evaluated here", entry, program->n_nodes, HY_MAX_PROJECTION_NODES);
+  if (program->n_columns > HY_MAX_PROJECTION_COLUMNS) return fail(HY_ERR_UNSUPPORTED, "%s: %u columns, at most %u", entry, program->n_columns, HY_MAX_PROJECTION_COLUMNS);
+  if (program->n_tests > HY_MAX_PROJECTION_TESTS) return fail(HY_ERR_UNSUPPORTED, "%s: %u column tests, at most %u", entry, program->n_tests, HY_MAX_PROJECTION_TESTS);
 
   // ---- the program, checked: a stack of types (operand types are resolved here, the kernel's nodes carry them) ------------------------
-  ExprArgs a{};
-  ExprNode nodes[HY_MAX_PROJECTION_NODES];
+  ExprNode (&nodes)[HY_MAX_PROJECTION_NODES] = p->nodes;
   std::memset(nodes, 0, sizeof(nodes));
-  const hy_column* distinct[PX_COLUMNS] = {};   // the decoded twins (plain_column) of the columns the program reads, each once
-  uint32_t n_distinct = 0;
-  const hy_column* shape = nullptr;
+  const hy_column* (&distinct)[PX_COLUMNS] = p->distinct;   // the decoded twins (plain_column) of the columns the program reads, each once
+  uint32_t& n_distinct = p->n_distinct;
+  const hy_column*& shape = p->shape;
+  uint32_t first[HY_MAX_PROJECTION_NODES];   // where node k's subtree begins (its operands are what lies between)
+  uint32_t begins[PX_DEPTH];
   uint32_t stack[PX_DEPTH];
   uint32_t depth = 0;
   bool test_used[PX_TESTS] = {};
@@ -440,20 +147,20 @@ hy_status hy_projection_expression(const hy_projection_program* program, hy_colu
     ExprNode& node = nodes[k];
     if (in.kind >= HY_PROJ_BETWEEN && in.kind <= HY_PROJ_PARAMETER) {
       static const char* const names[] = {"Between", "Cast", "Extract", "function", "subquery", "parameter"};
-      return fail(HY_ERR_UNSUPPORTED, "hy_projection_expression: %s expressions are not evaluated on the device", names[in.kind - HY_PROJ_BETWEEN]);
+      return fail(HY_ERR_UNSUPPORTED, "%s: %s expressions are not evaluated on the device", entry, names[in.kind - HY_PROJ_BETWEEN]);
     }
-    if (in.kind > HY_PROJ_PARAMETER) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u has unknown kind %u", k, in.kind);
+    if (in.kind > HY_PROJ_PARAMETER) return fail(HY_ERR_INVALID, "%s: node %u has unknown kind %u", entry, k, in.kind);
     node.kind = static_cast<uint8_t>(in.kind);
     const bool pushes = in.kind == HY_PROJ_COLUMN || in.kind == HY_PROJ_LITERAL || in.kind == HY_PROJ_COLUMN_TEST;
     const uint32_t operands = pushes ? 0 : in.kind == HY_PROJ_CASE ? 3 : (in.kind == HY_PROJ_IS_NULL || in.kind == HY_PROJ_IS_NOT_NULL || in.kind == HY_PROJ_UNARY_MINUS) ? 1 : 2;
-    if (depth < operands) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u pops %u operands, the stack holds %u", k, operands, depth);
-    if (pushes && depth == PX_DEPTH) return fail(HY_ERR_UNSUPPORTED, "hy_projection_expression: the program needs more than %u stack entries", PX_DEPTH);
+    if (depth < operands) return fail(HY_ERR_INVALID, "%s: node %u pops %u operands, the stack holds %u", entry, k, operands, depth);
+    if (pushes && depth == PX_DEPTH) return fail(HY_ERR_UNSUPPORTED, "%s: the program needs more than %u stack entries", entry, PX_DEPTH);
     uint32_t type = HY_TYPE_INT;
     switch (in.kind) {
       case HY_PROJ_COLUMN: {
-        if (in.index >= program->n_columns || !program->columns[in.index]) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u names column %u", k, in.index);
+        if (in.index >= program->n_columns || !program->columns[in.index]) return fail(HY_ERR_INVALID, "%s: node %u names column %u", entry, k, in.index);
         const hy_column* column = program->columns[in.index];
-        HY_TRY(on_this_device(column, "hy_projection_expression"));
+        HY_TRY(on_this_device(column, entry));
         if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_UNSUPPORTED, "MVCC columns are read by hy_validate only");
         if (!px_numeric(column->data_type)) return fail(HY_ERR_UNSUPPORTED, "string expressions stay on the CPU path (a string column is read by a column test only)");
         HY_TRY(plain_column(column, &column));
@@ -467,12 +174,12 @@ hy_status hy_projection_expression(const hy_projection_program* program, hy_colu
       }
       case HY_PROJ_LITERAL:
         if (in.literal_type == HY_TYPE_STRING) return fail(HY_ERR_UNSUPPORTED, "string expressions stay on the CPU path");
-        if (in.literal_type > HY_TYPE_DOUBLE) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u has literal type %u", k, in.literal_type);
+        if (in.literal_type > HY_TYPE_DOUBLE) return fail(HY_ERR_INVALID, "%s: node %u has literal type %u", entry, k, in.literal_type);
         type = in.literal_type;
         node.literal = literal_bits(type, in.literal);
         break;
       case HY_PROJ_COLUMN_TEST:
-        if (in.index >= program->n_tests || !program->tests[in.index].column) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u names column test %u", k, in.index);
+        if (in.index >= program->n_tests || !program->tests[in.index].column) return fail(HY_ERR_INVALID, "%s: node %u names column test %u", entry, k, in.index);
         test_used[in.index] = true;
         node.index = static_cast<uint8_t>(in.index);
         break;
@@ -484,8 +191,8 @@ hy_status hy_projection_expression(const hy_projection_program* program, hy_colu
         type = expression_common_type(node.at, node.bt);
         break;
       case HY_PROJ_COMPARISON:
-        if (in.op >= HY_PRED_BETWEEN_INCLUSIVE && in.op <= HY_PRED_BETWEEN_EXCLUSIVE) return fail(HY_ERR_UNSUPPORTED, "hy_projection_expression: Between expressions are not evaluated on the device");
-        if (in.op > HY_PRED_GREATER_THAN_EQUALS) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u compares with condition %u", k, in.op);
+        if (in.op >= HY_PRED_BETWEEN_INCLUSIVE && in.op <= HY_PRED_BETWEEN_EXCLUSIVE) return fail(HY_ERR_UNSUPPORTED, "%s: Between expressions are not evaluated on the device", entry);
+        if (in.op > HY_PRED_GREATER_THAN_EQUALS) return fail(HY_ERR_INVALID, "%s: node %u compares with condition %u", entry, k, in.op);
         node.at = static_cast<uint8_t>(stack[depth - 2]);
         node.bt = static_cast<uint8_t>(stack[depth - 1]);
         break;
@@ -494,16 +201,16 @@ hy_status hy_projection_expression(const hy_projection_program* program, hy_colu
         node.at = static_cast<uint8_t>(stack[depth - 2]);
         node.bt = static_cast<uint8_t>(stack[depth - 1]);
         for (uint32_t t : {uint32_t{node.at}, uint32_t{node.bt}}) {
-          if (t != HY_TYPE_INT && t != HY_TYPE_NULL) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u: AND / OR take Int operands (a predicate's result)", k);
+          if (t != HY_TYPE_INT && t != HY_TYPE_NULL) return fail(HY_ERR_INVALID, "%s: node %u: AND / OR take Int operands (a predicate's result)", entry, k);
         }
         break;
       case HY_PROJ_UNARY_MINUS:
         node.at = static_cast<uint8_t>(stack[depth - 1]);
-        if (!px_numeric(node.at)) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u negates a NULL literal", k);
+        if (!px_numeric(node.at)) return fail(HY_ERR_INVALID, "%s: node %u negates a NULL literal", entry, k);
         type = node.at;
         break;
       case HY_PROJ_CASE:
-        if (stack[depth - 3] != HY_TYPE_INT && stack[depth - 3] != HY_TYPE_NULL) return fail(HY_ERR_INVALID, "hy_projection_expression: node %u: CASE takes an Int `when` (a predicate's result)", k);
+        if (stack[depth - 3] != HY_TYPE_INT && stack[depth - 3] != HY_TYPE_NULL) return fail(HY_ERR_INVALID, "%s: node %u: CASE takes an Int `when` (a predicate's result)", entry, k);
         node.at = static_cast<uint8_t>(stack[depth - 2]);
         node.bt = static_cast<uint8_t>(stack[depth - 1]);
         if (node.at == HY_TYPE_NULL && node.bt == HY_TYPE_NULL) return fail(HY_ERR_INVALID, "Cannot deduce common type if both sides are NULL.");
@@ -513,48 +220,68 @@ hy_status hy_projection_expression(const hy_projection_program* program, hy_colu
     }
     node.op = static_cast<uint8_t>(in.op);
     node.type = static_cast<uint8_t>(type);
+    first[k] = operands ? begins[depth - operands] : k;
     depth = depth - operands + 1;
     stack[depth - 1] = type;
+    begins[depth - 1] = first[k];
   }
-  if (depth != 1) return fail(HY_ERR_INVALID, "hy_projection_expression: the program leaves %u values, not one", depth);
-  const uint32_t result_type = stack[0];
-  if (!px_numeric(result_type)) return fail(HY_ERR_INVALID, "hy_projection_expression: the result's type cannot be deduced (a NULL literal)");
+  if (depth != 1) return fail(HY_ERR_INVALID, "%s: the program leaves %u values, not one", entry, depth);
+  const uint32_t result_type = p->result_type = stack[0];
+  if (!px_numeric(result_type)) return fail(HY_ERR_INVALID, "%s: the result's type cannot be deduced (a NULL literal)", entry);
+  // ---- a scan's predicate: a boolean root; on the spine -- the root and every node all of whose ancestors are AND / OR -- FALSE and NULL
+  // both drop the row, so a column test there may carry a Between condition (test_cell evaluates the range job; below the spine
+  // _evaluate_between_expression's FALSE-for-NULL, expression_evaluator.cpp:590-656, could be seen: refused as in a projection)
+  bool between_refused[PX_TESTS] = {};
+  {
+    bool spine[HY_MAX_PROJECTION_NODES] = {};
+    const uint32_t root = program->n_nodes - 1;
+    if (scan) {
+      const uint32_t kind = nodes[root].kind;
+      if (kind != HY_PROJ_COMPARISON && kind != HY_PROJ_COLUMN_TEST && kind != HY_PROJ_IS_NULL && kind != HY_PROJ_IS_NOT_NULL && kind != HY_PROJ_AND && kind != HY_PROJ_OR)
+        return fail(HY_ERR_INVALID, "%s: Expression type cannot be evaluated to PosList (the root is a comparison, a column test, IS [NOT] NULL, AND or OR)", entry);
+      spine[root] = true;
+    }
+    for (uint32_t k = program->n_nodes; k-- > 0;) {   // a node's operands lie in front of it: parents first
+      if (spine[k] && (nodes[k].kind == HY_PROJ_AND || nodes[k].kind == HY_PROJ_OR)) spine[k - 1] = spine[first[k - 1] - 1] = true;
+      if (nodes[k].kind == HY_PROJ_COLUMN_TEST && !spine[k]) between_refused[nodes[k].index] = true;
+    }
+  }
 
   // ---- the tests' columns -----------------------------------------------------------------------------------------------------------
-  const hy_column* tested[PX_TESTS] = {};
-  const hy_column* tested_data[PX_TESTS] = {};
-  hy_predicate predicates[PX_TESTS];
-  std::vector<uint64_t> list_words[PX_TESTS], list_offsets[PX_TESTS];
+  const hy_column* (&tested)[PX_TESTS] = p->tested;
+  const hy_column* (&tested_data)[PX_TESTS] = p->tested_data;
+  hy_predicate (&predicates)[PX_TESTS] = p->predicates;
   for (uint32_t t = 0; t < program->n_tests; ++t) {
     if (!test_used[t]) continue;
     const hy_projection_test& test = program->tests[t];
     const hy_column* column = test.column;
-    HY_TRY(on_this_device(column, "hy_projection_expression"));
+    HY_TRY(on_this_device(column, entry));
     if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_UNSUPPORTED, "MVCC columns are read by hy_validate only");
     HY_TRY(plain_column(column, &column));
     const hy_column* data_column = column->is_reference ? column->ref : column;
-    if (!data_column) return fail(HY_ERR_INVALID, "hy_projection_expression: column test %u over a reference column without a referenced column", t);
+    if (!data_column) return fail(HY_ERR_INVALID, "%s: column test %u over a reference column without a referenced column", entry, t);
     HY_TRY(plain_column(data_column, &data_column));
     if (column->data_type == HY_TYPE_STRING) {
       for (uint32_t c = 0; c < data_column->n_chunks; ++c) {
         if (data_column->host_segments[c].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "column tests on unencoded string segments stay on the CPU path");
       }
     } else if (!px_numeric(column->data_type)) {
-      return fail(HY_ERR_INVALID, "hy_projection_expression: column test %u over a column of type %u", t, column->data_type);
+      return fail(HY_ERR_INVALID, "%s: column test %u over a column of type %u", entry, t, column->data_type);
     }
     if (test.in_list) {
-      HY_TRY(in_list_as_bitmaps(data_column, test.in_list, &list_words[t], &list_offsets[t], &predicates[t]));
+      HY_TRY(in_list_as_bitmaps(data_column, test.in_list, &p->list_words[t], &p->list_offsets[t], &predicates[t]));
     } else {
       predicates[t] = test.predicate;
       const uint32_t condition = predicates[t].condition;
-      if (condition >= HY_PRED_BETWEEN_INCLUSIVE && condition <= HY_PRED_BETWEEN_EXCLUSIVE) return fail(HY_ERR_UNSUPPORTED, "hy_projection_expression: Between expressions are not evaluated on the device");
-      if (condition == HY_PRED_IN || condition == HY_PRED_NOT_IN) return fail(HY_ERR_INVALID, "hy_projection_expression: an IN list is passed as hy_projection_test.in_list");
+      if (between_refused[t] && condition >= HY_PRED_BETWEEN_INCLUSIVE && condition <= HY_PRED_BETWEEN_EXCLUSIVE)
+        return fail(HY_ERR_UNSUPPORTED, "%s: Between expressions are not evaluated on the device%s", entry, scan ? " below the AND / OR spine of the predicate" : "");
+      if (condition == HY_PRED_IN || condition == HY_PRED_NOT_IN) return fail(HY_ERR_INVALID, "%s: an IN list is passed as hy_projection_test.in_list", entry);
     }
     tested[t] = column;
     tested_data[t] = data_column;
     if (!shape) shape = column;
   }
-  if (!shape) return fail(HY_ERR_INVALID, "hy_projection_expression: at least one operand must be a column");
+  if (!shape) return fail(HY_ERR_INVALID, "%s: at least one operand must be a column", entry);
   auto same_layout = [&](const hy_column* column) -> hy_status {
     if (column->n_chunks != shape->n_chunks) return fail(HY_ERR_INVALID, "operand columns do not belong to one table (chunk counts differ)");
     for (uint32_t c = 0; c < shape->n_chunks; ++c) {
@@ -566,33 +293,58 @@ hy_status hy_projection_expression(const hy_projection_program* program, hy_colu
   for (uint32_t t = 0; t < program->n_tests; ++t) {
     if (tested[t]) HY_TRY(same_layout(tested[t]));
   }
+  return HY_OK;
+}
 
-  const uint32_t width = (result_type == HY_TYPE_INT || result_type == HY_TYPE_FLOAT) ? 4 : 8;
+// The tests' per-chunk jobs (prepare_jobs, queued on the current stream), in a block that lives as long as `p`: until the kernel has run.
+hy_status prepare_program_tests(PreparedProgram* p) {
   hipStream_t stream = current_stream();
-
   // ---- the tests' per-chunk jobs, in a block that lives until the kernel has run ----------------------------------------------------------
   size_t jobs_at[PX_TESTS + 1] = {}, staging_at[PX_TESTS + 1] = {};
   size_t temporary_bytes = 0;
-  for (uint32_t t = 0; t < program->n_tests; ++t) {
-    if (!tested[t]) continue;
+  for (uint32_t t = 0; t < PX_TESTS; ++t) {
+    if (!p->tested[t]) continue;
     jobs_at[t] = temporary_bytes;
-    temporary_bytes += align_up(sizeof(ScanJob) * (size_t{tested_data[t]->n_chunks} + 1), 256);
+    temporary_bytes += align_up(sizeof(ScanJob) * (size_t{p->tested_data[t]->n_chunks} + 1), 256);
     staging_at[t] = temporary_bytes;
-    temporary_bytes += align_up(scan_jobs_staging_bytes(tested_data[t], &predicates[t]) + 256, 256);
+    temporary_bytes += align_up(scan_jobs_staging_bytes(p->tested_data[t], &p->predicates[t]) + 256, 256);
   }
-  DeviceBuffer temporary;
-  if (temporary_bytes) HY_TRY(temporary.alloc(temporary_bytes));
-  for (uint32_t t = 0; t < program->n_tests; ++t) {
-    if (!tested[t]) continue;
-    ScanJob* jobs = reinterpret_cast<ScanJob*>(temporary.as<char>() + jobs_at[t]);
-    const hy_status status = prepare_scan_jobs(tested_data[t], &predicates[t], jobs, temporary.as<char>() + staging_at[t]);
+  if (temporary_bytes) HY_TRY(p->temporary.alloc(temporary_bytes));
+  for (uint32_t t = 0; t < PX_TESTS; ++t) {
+    if (!p->tested[t]) continue;
+    ScanJob* jobs = reinterpret_cast<ScanJob*>(p->temporary.as<char>() + jobs_at[t]);
+    const hy_status status = prepare_scan_jobs(p->tested_data[t], &p->predicates[t], jobs, p->temporary.as<char>() + staging_at[t]);
     if (status != HY_OK) {
       (void)hipStreamSynchronize(stream);   // (uploads from this call's host arrays may be queued)
       return status;
     }
-    const uint32_t condition = predicates[t].condition;
-    a.tests[t] = ExprTest{tested[t]->d_segments, jobs, condition == HY_PRED_IS_NULL ? 1u : condition == HY_PRED_IS_NOT_NULL ? 2u : 0u, 0};
+    const uint32_t condition = p->predicates[t].condition;
+    p->tests[t] = ExprTest{p->tested[t]->d_segments, jobs, condition == HY_PRED_IS_NULL ? 1u : condition == HY_PRED_IS_NOT_NULL ? 2u : 0u, 0};
   }
+  return HY_OK;
+}
+
+}  // namespace hy
+
+using namespace hy;
+
+extern "C" {
+
+hy_status hy_projection_expression(const hy_projection_program* program, hy_column** out) {
+  if (!program || !out) return fail(HY_ERR_INVALID, "hy_projection_expression: null argument");
+  *out = nullptr;
+  PreparedProgram prepared;
+  HY_TRY(check_program(program, "hy_projection_expression", false, &prepared));
+  HY_TRY(prepare_program_tests(&prepared));
+  ExprArgs a{};
+  const ExprNode (&nodes)[HY_MAX_PROJECTION_NODES] = prepared.nodes;
+  const hy_column* const shape = prepared.shape;
+  const hy_column* const (&distinct)[PX_COLUMNS] = prepared.distinct;
+  const hy_column* const (&tested)[PX_TESTS] = prepared.tested;
+  const uint32_t n_distinct = prepared.n_distinct, result_type = prepared.result_type;
+  for (uint32_t t = 0; t < PX_TESTS; ++t) a.tests[t] = prepared.tests[t];
+  const uint32_t width = (result_type == HY_TYPE_INT || result_type == HY_TYPE_FLOAT) ? 4 : 8;
+  hipStream_t stream = current_stream();
 
   // ---- result buffers: hy_projection_arithmetic's layout -- one allocation, chunk c's values at value_base[c] (256-byte aligned), then all bitmaps
   const uint32_t n_chunks = shape->n_chunks;

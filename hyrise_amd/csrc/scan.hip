@@ -2161,6 +2161,43 @@ struct InListArgs {   // hy_table_scan_in_list, checked: `predicate` carries HY_
   uint32_t n_keys;              // before the padding
 };
 
+// A scan's chunk regions (device memory) as the HY_MEM_HOST result the caller asked for: counts and chunk states copied, the regions packed back
+// to back (carved from the thread's scratch arena behind what the scan carved) and copied.  d_overflow: the scan's overflow word, or nullptr.
+hy_status regions_to_host_result(const hy_row_id* d_matches, const uint64_t* d_offsets, const uint32_t* d_counts, const uint8_t* d_state, uint32_t* d_overflow, uint32_t n_chunks,
+                                 bool materialize_all, hy_scan_result* result) {
+  hipStream_t stream = current_stream();
+  Scratch& sc = scratch();
+  uint32_t overflow = 0;
+  HY_HIP(hipMemcpyAsync(result->counts, d_counts, 4 * size_t{n_chunks}, hipMemcpyDeviceToHost, stream));
+  HY_HIP(hipMemcpyAsync(result->chunk_state, d_state, size_t{n_chunks}, hipMemcpyDeviceToHost, stream));
+  if (d_overflow) HY_HIP(hipMemcpyAsync(&overflow, d_overflow, 4, hipMemcpyDeviceToHost, stream));
+  HY_HIP(hipStreamSynchronize(stream));
+  if (overflow) {
+    (void)hipMemsetAsync(d_overflow, 0, 4, stream);
+    return fail(HY_ERR_DEVICE, "scan overflowed its own region buffer (internal error)");
+  }
+  // back-to-back layout for the host: offsets[c+1] - offsets[c] = RowIDs written for chunk c
+  uint64_t total = 0;
+  for (uint32_t c = 0; c < n_chunks; ++c) {
+    result->offsets[c] = total;
+    const bool elided = result->chunk_state[c] == HY_CHUNK_ALL_MATCH && !materialize_all;
+    total += elided ? 0 : result->counts[c];
+  }
+  result->offsets[n_chunks] = total;
+  result->total_matches = total;
+  if (total > result->capacity) return fail(HY_ERR_CAPACITY, "scan produced %llu RowIDs, capacity is %llu", static_cast<unsigned long long>(total), static_cast<unsigned long long>(result->capacity));
+  if (total) {
+    uint64_t* d_dense_offsets = carve<uint64_t>(sc, size_t{n_chunks} + 2);
+    hy_row_id* d_dense = carve<hy_row_id>(sc, total);
+    if (!d_dense_offsets || !d_dense) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+    HY_HIP(hipMemcpyAsync(d_dense_offsets, result->offsets, 8 * (size_t{n_chunks} + 1), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(compact_regions, dim3(n_chunks), dim3(256), 0, stream, d_matches, d_offsets, d_dense_offsets, d_dense, n_chunks);
+    HY_HIP(hipMemcpyAsync(result->matches, d_dense, sizeof(hy_row_id) * total, hipMemcpyDeviceToHost, stream));
+    HY_HIP(hipStreamSynchronize(stream));
+  }
+  return HY_OK;
+}
+
 static hy_status run_scan(const hy_column* column, const hy_column* right, const hy_predicate* predicate, uint32_t condition,
                           const uint32_t* excluded, uint32_t n_excluded, hy_scan_result* result, const VisibilityArgs* visibility = nullptr,
                           const InListArgs* in_list = nullptr) {
@@ -2399,34 +2436,7 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
   HY_HIP(hipGetLastError());
 
   if (host_result) {
-    uint32_t overflow = 0;
-    HY_HIP(hipMemcpyAsync(result->counts, d_counts, 4 * size_t{n_chunks}, hipMemcpyDeviceToHost, stream));
-    HY_HIP(hipMemcpyAsync(result->chunk_state, d_state, size_t{n_chunks}, hipMemcpyDeviceToHost, stream));
-    HY_HIP(hipMemcpyAsync(&overflow, d_overflow, 4, hipMemcpyDeviceToHost, stream));
-    HY_HIP(hipStreamSynchronize(stream));
-    if (overflow) {
-      (void)hipMemsetAsync(d_overflow, 0, 4, stream);
-      return fail(HY_ERR_DEVICE, "scan overflowed its own region buffer (internal error)");
-    }
-    // back-to-back layout for the host: offsets[c+1] - offsets[c] = RowIDs written for chunk c
-    uint64_t total = 0;
-    for (uint32_t c = 0; c < n_chunks; ++c) {
-      result->offsets[c] = total;
-      const bool elided = result->chunk_state[c] == HY_CHUNK_ALL_MATCH && !pa.materialize_all;
-      total += elided ? 0 : result->counts[c];
-    }
-    result->offsets[n_chunks] = total;
-    result->total_matches = total;
-    if (total > result->capacity) return fail(HY_ERR_CAPACITY, "scan produced %llu RowIDs, capacity is %llu", static_cast<unsigned long long>(total), static_cast<unsigned long long>(result->capacity));
-    if (total) {
-      uint64_t* d_dense_offsets = carve<uint64_t>(sc, size_t{n_chunks} + 2);
-      hy_row_id* d_dense = carve<hy_row_id>(sc, total);
-      if (!d_dense_offsets || !d_dense) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-      HY_HIP(hipMemcpyAsync(d_dense_offsets, result->offsets, 8 * (size_t{n_chunks} + 1), hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(compact_regions, dim3(n_chunks), dim3(256), 0, stream, d_matches, d_offsets, d_dense_offsets, d_dense, n_chunks);
-      HY_HIP(hipMemcpyAsync(result->matches, d_dense, sizeof(hy_row_id) * total, hipMemcpyDeviceToHost, stream));
-      HY_HIP(hipStreamSynchronize(stream));
-    }
+    HY_TRY(regions_to_host_result(d_matches, d_offsets, d_counts, d_state, d_overflow, n_chunks, pa.materialize_all != 0, result));
   } else {
     result->total_matches = 0;
   }

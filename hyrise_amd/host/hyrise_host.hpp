@@ -21,6 +21,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <memory>
@@ -1155,8 +1156,15 @@ class LikeMatcher {
   bool _insensitive = false, _negated = false;
 };
 
+struct Expression;   // (defined with Projection, below)
+
 class TableScan : public AbstractReadOnlyOperator {
  public:
+  // A predicate expression: the scan create_impl leaves to ExpressionEvaluatorTableScanImpl (table_scan.cpp:450-451), on the device through
+  // hy_table_scan_expression (scan_expression(), defined behind Projection, whose lowering it uses)
+  TableScan(std::shared_ptr<const AbstractOperator> in, std::shared_ptr<const Expression> predicate) : AbstractReadOnlyOperator(std::move(in)), _predicate(std::move(predicate)) {
+    Assert(_predicate != nullptr, "TableScan: a predicate expression is needed");
+  }
   TableScan(std::shared_ptr<const AbstractOperator> in, ColumnID column_id, PredicateCondition condition, AllTypeVariant value = NullValue{},
             std::optional<AllTypeVariant> value2 = std::nullopt)
       : AbstractReadOnlyOperator(std::move(in)), _column_id(column_id), _condition(condition), _value(std::move(value)), _value2(std::move(value2)) {}
@@ -1176,7 +1184,7 @@ class TableScan : public AbstractReadOnlyOperator {
   std::shared_ptr<const Table> _on_execute() override {
     const auto in_table = left_input_table();
     const auto chunk_count = in_table->chunk_count();
-    const auto column = device_column(in_table, _column_id);
+    const auto column = _predicate ? nullptr : device_column(in_table, _column_id);
     // Device-resident results (the default): the PosLists stay in a pooled block of HBM, the output table's ReferenceSegments hold
     // DevicePosLists into it.  Host results: the library copies the RowIDs back (the boundary as rounds 1-5 used it).
     std::unique_ptr<DeviceScanOutput> on_device;
@@ -1194,7 +1202,9 @@ class TableScan : public AbstractReadOnlyOperator {
     result.chunk_state = states.data();
     if (on_device) result = on_device->result;
     bool evaluated_on_host = false;
-    if (_right_column_id) {
+    if (_predicate) {
+      if (!scan_expression(in_table, &result, counts, states)) on_device.reset();   // (a constant predicate: counts and states say all or nothing, no RowIDs are needed)
+    } else if (_right_column_id) {
       check_status(hy_table_scan_columns(column->handle, device_column(in_table, *_right_column_id)->handle, static_cast<uint32_t>(_condition), &result));
     } else {
       hy_predicate predicate{};
@@ -1496,12 +1506,16 @@ class TableScan : public AbstractReadOnlyOperator {
   }
 
  private:
-  ColumnID _column_id;
-  PredicateCondition _condition;
+  // _predicate through hy_table_scan_expression into `result` (true), or -- a constant predicate -- answered in counts / states (false)
+  bool scan_expression(const std::shared_ptr<const Table>& in_table, hy_scan_result* result, std::vector<uint32_t>& counts, std::vector<uint8_t>& states) const;
+
+  ColumnID _column_id = 0;
+  PredicateCondition _condition = PredicateCondition::Equals;
   AllTypeVariant _value;
   std::optional<AllTypeVariant> _value2;
   std::optional<ColumnID> _right_column_id;
   std::vector<AllTypeVariant> _list;   // In / NotIn
+  std::shared_ptr<const Expression> _predicate;
 };
 
 // ---- Validate (operators/validate.hpp, validate.cpp:87-314) -------------------------------------------------------------
@@ -3001,6 +3015,7 @@ class Projection : public AbstractReadOnlyOperator {
   }
 
  private:
+  friend class TableScan;   // (TableScan over a predicate expression lowers it with the functions below)
   struct Lowered {   // the program and everything its pointers name
     hy_projection_program program{};
     std::vector<std::shared_ptr<DeviceColumn>> columns;
@@ -3012,12 +3027,12 @@ class Projection : public AbstractReadOnlyOperator {
 
   static bool is_string_column(const Table& table, const Expression& e) { return e.type == ExpressionType::Column && table.column_data_type(e.column_id) == DataType::String; }
 
-  void push(Lowered& l, const hy_projection_node& node) const {
+  static void push(Lowered& l, const hy_projection_node& node) {
     if (l.program.n_nodes >= HY_MAX_PROJECTION_NODES) Fail("Projection: the expression has more than HY_MAX_PROJECTION_NODES nodes");
     l.program.nodes[l.program.n_nodes++] = node;
   }
 
-  void lower(const std::shared_ptr<const Table>& in_table, const Expression& e, Lowered& l) const {
+  static void lower(const std::shared_ptr<const Table>& in_table, const Expression& e, Lowered& l) {
     hy_projection_node node{};
     switch (e.type) {
       case ExpressionType::Column: {
@@ -3077,7 +3092,7 @@ class Projection : public AbstractReadOnlyOperator {
   }
 
   // string column <condition> 'literal' | LIKE 'pattern' | IN ('a', ...): the hy_predicate / hy_in_list TableScan makes for the same scan
-  void lower_column_test(const std::shared_ptr<const Table>& in_table, const Expression& e, Lowered& l) const {
+  static void lower_column_test(const std::shared_ptr<const Table>& in_table, const Expression& e, Lowered& l) {
     const auto column_id = e.arguments[0]->column_id;
     if (l.program.n_tests >= HY_MAX_PROJECTION_TESTS) Fail("Projection: the expression has more than HY_MAX_PROJECTION_TESTS column tests");
     l.columns.push_back(device_column(in_table, column_id));   // (kept alive; not one of program.columns)
@@ -3139,5 +3154,43 @@ class Projection : public AbstractReadOnlyOperator {
   std::vector<ExpressionPtr> _expressions;
   std::vector<std::string> _names;
 };
+
+// ---- TableScan over a predicate expression (table_scan.cpp:450-451 -> ExpressionEvaluator::evaluate_expression_to_pos_list) ---------------
+// The predicate is lowered like a Projection's expression and handed to hy_table_scan_expression; the PosLists land where every other scan's
+// do (DeviceScanOutput), and the output is assembled by the same code.  Answered on the host: a Value root (Int: non-zero keeps every row,
+// zero and the NULL literal none; a Long, Float, Double or String literal at the root is a Fail, "Expression type cannot be evaluated to PosList").  BETWEEN on the spine -- the root and the nodes below nothing but AND / OR -- becomes two comparisons
+// (rewrite_between_expression; over a string column it stays ONE column test with a Between condition, which the library takes there);
+// anywhere else the library refuses it, and what the library refuses is a Fail.
+inline bool TableScan::scan_expression(const std::shared_ptr<const Table>& in_table, hy_scan_result* result, std::vector<uint32_t>& counts, std::vector<uint8_t>& states) const {
+  const auto chunk_count = in_table->chunk_count();
+  const auto constant = [&](bool every_row) {
+    for (ChunkID c = 0; c < chunk_count; ++c) {
+      const bool excluded = std::find(excluded_chunk_ids.begin(), excluded_chunk_ids.end(), c) != excluded_chunk_ids.end();
+      counts[c] = every_row && !excluded ? in_table->get_chunk(c)->size() : 0;
+      states[c] = counts[c] ? HY_CHUNK_ALL_MATCH : HY_CHUNK_NONE_MATCH;
+    }
+    return false;
+  };
+  if (_predicate->type == ExpressionType::Value) {
+    if (variant_is_null(_predicate->value)) return constant(false);
+    Assert(std::holds_alternative<int32_t>(_predicate->value), "Expression type cannot be evaluated to PosList.");
+    return constant(std::get<int32_t>(_predicate->value) != 0);
+  }
+  if (chunk_count == 0) return constant(false);   // (no rows to test, and no device column to describe)
+  std::function<ExpressionPtr(const ExpressionPtr&)> spine = [&](const ExpressionPtr& e) -> ExpressionPtr {
+    if (e->type == ExpressionType::And || e->type == ExpressionType::Or) return expression_of(e->type, {spine(e->arguments[0]), spine(e->arguments[1])});
+    if (e->type == ExpressionType::Predicate && is_between(e->condition) && e->arguments.size() == 3 && !Projection::is_string_column(*in_table, *e->arguments[0])) {
+      const bool lower_inclusive = e->condition == PredicateCondition::BetweenInclusive || e->condition == PredicateCondition::BetweenUpperExclusive;
+      const bool upper_inclusive = e->condition == PredicateCondition::BetweenInclusive || e->condition == PredicateCondition::BetweenLowerExclusive;
+      return and_(predicate_(lower_inclusive ? PredicateCondition::GreaterThanEquals : PredicateCondition::GreaterThan, {e->arguments[0], e->arguments[1]}),
+                  predicate_(upper_inclusive ? PredicateCondition::LessThanEquals : PredicateCondition::LessThan, {e->arguments[0], e->arguments[2]}));
+    }
+    return e;
+  };
+  Projection::Lowered l;
+  Projection::lower(in_table, *spine(_predicate), l);
+  check_status(hy_table_scan_expression(&l.program, excluded_chunk_ids.data(), static_cast<uint32_t>(excluded_chunk_ids.size()), result));
+  return true;
+}
 
 }  // namespace hyrise_amd

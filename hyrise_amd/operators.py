@@ -615,6 +615,63 @@ def projection_expression(tree):
     return ResultColumn(handle)
 
 
+BETWEEN_BOUNDS = {abi.PRED_BETWEEN_INCLUSIVE: (abi.PRED_GREATER_THAN_EQUALS, abi.PRED_LESS_THAN_EQUALS), abi.PRED_BETWEEN_LOWER_EXCLUSIVE: (abi.PRED_GREATER_THAN, abi.PRED_LESS_THAN_EQUALS),
+                  abi.PRED_BETWEEN_UPPER_EXCLUSIVE: (abi.PRED_GREATER_THAN_EQUALS, abi.PRED_LESS_THAN), abi.PRED_BETWEEN_EXCLUSIVE: (abi.PRED_GREATER_THAN, abi.PRED_LESS_THAN)}
+
+
+def lower_between(tree, on_spine=True):
+    """A scan's predicate tree with every ("between", abi.PRED_BETWEEN_*, operand, lower, upper) replaced by `operand >= lower AND operand <=
+    upper` (> / < for the exclusive conditions): rewrite_between_expression.  Only on the spine -- the root and the nodes all of whose ancestors
+    are AND / OR -- where a row is dropped for FALSE and for NULL alike; anywhere else _evaluate_between_expression's FALSE for a NULL operand
+    (expression_evaluator.cpp:590-656) could be told from the rewrite's NULL: ValueError."""
+    if not isinstance(tree, tuple) or not tree or not isinstance(tree[0], str):
+        return tree
+    if tree[0] == "between" and len(tree) == 5:
+        if not on_spine:
+            raise ValueError("BETWEEN below the AND / OR spine of a scan's predicate is not lowered: its FALSE for a NULL operand would become NULL")
+        lower_condition, upper_condition = BETWEEN_BOUNDS[tree[1]]
+        operand, lower, upper = (lower_between(t, False) for t in tree[2:])
+        return ("and", ("cmp", lower_condition, operand, lower), ("cmp", upper_condition, operand, upper))
+    if tree[0] in ("and", "or"):
+        return (tree[0],) + tuple(lower_between(t, on_spine) for t in tree[1:])
+    first = 2 if tree[0] in ("arith", "cmp") else 1
+    return tree[:first] + tuple(lower_between(t, False) for t in tree[first:])
+
+
+def table_scan_expression(tree, excluded_chunks=None, flags=0, capacity=None, device=False):
+    """hy_table_scan_expression: TableScan over a predicate expression -- the tuple trees of projection_program plus ("between", condition,
+    operand, lower, upper) on the spine (lower_between) -- evaluated and compacted in one pass.  -> HostScanResult like table_scan, or with
+    device=True the chunk-region result in device memory: (matches [rows, 2] int32, offsets [n_chunks + 1] int64, counts [n_chunks] int32,
+    chunk_state [n_chunks] uint8) torch tensors, flags | HY_SCAN_CHUNK_REGIONS."""
+    lib = abi.load_library()
+    program, keep = projection_program(lower_between(tree))
+    shape = (keep[1] + [t.column for t in keep[2]])
+    n_chunks, rows = (shape[0].n_chunks, shape[0].rows) if shape else (0, 0)
+    excluded, n_excluded = None, 0
+    if excluded_chunks is not None and len(excluded_chunks):
+        excluded = np.ascontiguousarray(excluded_chunks, dtype=np.uint32)
+        n_excluded = len(excluded)
+    excluded_pointer = excluded.ctypes.data if excluded is not None else None
+    if not device:
+        result = HostScanResult(n_chunks, rows if capacity is None else capacity, flags)
+        abi.check(lib.hy_table_scan_expression(C.byref(program), excluded_pointer, n_excluded, C.byref(result.c)))
+        del keep
+        return result
+    import torch
+    capacity = rows if capacity is None else capacity
+    matches = torch.zeros((max(1, capacity) + 2, 2), dtype=torch.int32, device="cuda")   # (16 bytes of slack behind the last RowID)
+    offsets = torch.zeros(n_chunks + 1, dtype=torch.int64, device="cuda")
+    counts = torch.zeros(max(1, n_chunks), dtype=torch.int32, device="cuda")
+    chunk_state = torch.zeros(max(1, n_chunks), dtype=torch.uint8, device="cuda")
+    r = abi.ScanResult()
+    r.mem, r.flags = abi.MEM_DEVICE, flags | abi.SCAN_CHUNK_REGIONS
+    r.matches, r.capacity = matches.data_ptr(), capacity
+    r.offsets, r.counts, r.chunk_state = offsets.data_ptr(), counts.data_ptr(), chunk_state.data_ptr()
+    abi.check(lib.hy_table_scan_expression(C.byref(program), excluded_pointer, n_excluded, C.byref(r)))
+    del keep
+    return matches[:max(1, capacity)], offsets, counts[:n_chunks], chunk_state[:n_chunks]
+
+
 PAIR_LIST_PERIOD = 2 << 20          # the two output PosLists of a join are written at the same pair index at the same time: when their
 PAIR_LIST_OFFSET = 5 << 18          # addresses are congruent modulo 2 MiB the two streams meet in the same memory channels -- pk_emit takes
                                     # 306 - 315 us; 1.25 MiB apart (mod 2 MiB) 274 - 283 us (tools/join_placement.py, profiles/r03_join_placement.txt)

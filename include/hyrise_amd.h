@@ -628,6 +628,38 @@ typedef struct hy_projection_program {
 } hy_projection_program;
 hy_status hy_projection_expression(const hy_projection_program* program, hy_column** result);
 
+/* ---- TableScan over a predicate expression: the scan TableScan::create_impl falls back to (table_scan.cpp:312-452) when the predicate is
+ * none of ColumnVsValue / ColumnBetween / ColumnVsColumn / ColumnIsNull / ColumnLike -- ExpressionEvaluatorTableScanImpl
+ * (expression_evaluator_table_scan_impl.cpp:21-24), i.e. ExpressionEvaluator::evaluate_expression_to_pos_list
+ * (expression_evaluator.cpp:1129-1311) -- in ONE launch: the program is evaluated per row, the matching rows are compacted into PosLists;
+ * no intermediate column exists.  `l_extendedprice * (1 - l_discount) > 1000`, `a < b + 1`, `x = 1 OR y IS NULL`, `CASE ... END = 1`,
+ * `int_column = 3.1` (what hy_predicate_cast answers with HY_ERR_UNSUPPORTED), a conjunction as one pass instead of k chained scans.
+ *   program    a hy_projection_program exactly as hy_projection_expression takes it: the same node kinds, limits, type deduction and
+ *              inputs (data and reference columns of every encoding, host or device PosLists, a NULL RowID is a NULL cell, caller-owned
+ *              device columns); all columns share one chunk layout.
+ *   match rule a row matches iff the program's value is not NULL and not 0.  That is evaluate_expression_to_pos_list's list: its AND / OR
+ *              (set_intersection / set_union of the operands' lists, :1249-1265) keep exactly the rows where TernaryAnd / TernaryOr
+ *              (expression_functors.hpp:41-84) are TRUE, given that every other node's list is "value TRUE" -- and its comparison, IS
+ *              [NOT] NULL, IN and LIKE leaves append the rows whose value is neither NULL nor 0 (:1144-1247; Between goes through
+ *              rewrite_between_expression, :1200).
+ *   root       a COMPARISON, COLUMN_TEST, IS_NULL, IS_NOT_NULL, AND or OR node; anything else (arithmetic, CASE, a column, a literal,
+ *              unary minus) is HY_ERR_INVALID -- the reference Fails with "Expression type cannot be evaluated to PosList" (:1307).  A program
+ *              without any column is HY_ERR_INVALID as well (a TRUE / FALSE literal predicate is the adapter's business).
+ *   BETWEEN    on the SPINE -- the root and every node all of whose ancestors are AND / OR -- a COLUMN_TEST may carry a Between condition
+ *              (HY_PRED_BETWEEN_*, numeric, or over a dictionary string column with per_chunk_lower / per_chunk_upper): FALSE and NULL
+ *              both drop the row there, so _evaluate_between_expression's fast path and its rewrite cannot be told apart.  Below the
+ *              spine it stays HY_ERR_UNSUPPORTED, as do the node kinds HY_PROJ_BETWEEN .. HY_PROJ_PARAMETER.
+ *   result     hy_table_scan's contract, bit for bit: positions relative to the input chunk, ascending (no re-ordering by referenced
+ *              chunk: the evaluator's scan has none); HY_MEM_HOST and HY_MEM_DEVICE results; HY_SCAN_CHUNK_REGIONS as there; the
+ *              alignment rules of a device result (`matches` on 16, `offsets` on 8, `counts` on 4 bytes: HY_ERR_INVALID before any launch
+ *              -- the kernel itself stores RowID by RowID, 8 bytes); excluded_chunks for data columns; hy_poslist_translate reads the
+ *              result with any column of the program as `scanned`.  chunk_state is HY_CHUNK_NONE_MATCH for excluded chunks and
+ *              HY_CHUNK_SCANNED otherwise, NEVER HY_CHUNK_ALL_MATCH: every match is written, HY_SCAN_MATERIALIZE_ALL_MATCH changes nothing.
+ * On any error nothing is written -- with hy_table_scan's one exception: a HY_MEM_HOST result whose `matches` is too small for the scan's
+ * RowIDs (HY_ERR_CAPACITY) has its counts, chunk_state, offsets and total_matches filled in (total_matches is the capacity needed), no RowID. */
+hy_status hy_table_scan_expression(const hy_projection_program* program, const uint32_t* excluded_chunks, uint32_t n_excluded,
+                                   hy_scan_result* result);
+
 /* ---- JoinHash (replaces JoinHash::_on_execute, join_hash.cpp:116-225,270-572) ----------------------------------- */
 typedef struct hy_join_result {
   uint32_t mem;
