@@ -210,6 +210,19 @@ class StarAggregate(C.Structure):
     _fields_ = [("function", C.c_uint32), ("op", C.c_uint32), ("left", StarColumn), ("right", StarColumn)]
 
 
+MAX_STAR_FILTERS = 4
+
+
+class StarFilter(C.Structure):
+    """hy_star_filter: one test of a table's conjunction -- `predicate` as hy_table_scan takes it, or `in_list` as hy_table_scan_in_list does."""
+    _fields_ = [("column", C.c_void_p), ("predicate", Predicate), ("in_list", C.POINTER(InList))]
+
+
+class StarDimensionWhere(C.Structure):
+    """hy_star_dimension_where: a dimension of hy_star_join_aggregate_where and the filters on it."""
+    _fields_ = [("key", C.c_void_p), ("fact_key", C.c_void_p), ("filters", C.POINTER(StarFilter)), ("n_filters", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # every symbol include/hyrise_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("hy_abi_version", C.c_int32, []),
@@ -273,6 +286,8 @@ SYMBOLS = [
                                               C.POINTER(AggregateColumns)]),
     ("hy_star_join_aggregate", C.c_int32, [C.POINTER(StarDimension), C.c_uint32, C.POINTER(StarColumn), C.c_uint32, C.POINTER(StarAggregate), C.c_uint32,
                                            C.POINTER(AggregateResult), C.POINTER(C.c_uint64)]),
+    ("hy_star_join_aggregate_where", C.c_int32, [C.POINTER(StarDimensionWhere), C.c_uint32, C.POINTER(StarFilter), C.c_uint32, C.POINTER(StarColumn), C.c_uint32,
+                                                 C.POINTER(StarAggregate), C.c_uint32, C.POINTER(AggregateResult), C.POINTER(C.c_uint64)]),
     ("hy_scan_project_aggregate", C.c_int32, [C.POINTER(Filter), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(FusedAggregate), C.c_uint32,
                                               C.POINTER(AggregateResult)]),
     ("hy_column_export", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),

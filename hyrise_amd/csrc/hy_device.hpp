@@ -257,12 +257,17 @@ extern thread_local uint32_t t_aggregate_recommended, t_aggregate_next_path;
 hy_status export_column_at(const hy_column* column, void* values, uint8_t* nulls, const uint64_t* d_row_base);
 
 // ---- join_star.hpp (join.hip): the probes of a star join fused into one pass over the fact table (hy_star_join_aggregate, plan.hip) ------
+struct StarProbeFilter {       // one test of a conjunction, evaluated row by row where the table is walked anyway
+  const hy_column* column;     // a plain data column of the table (Unencoded / FrameOfReference / Dictionary segments)
+  const struct ScanJob* jobs;  // its per-chunk jobs in device memory (prepare_scan_jobs: a predicate's, or an IN list's)
+  bool in_list;                // ... an IN list's
+};
 struct StarProbeDimension {
   const hy_column* key;        // the dimension's key column (int32, unique among `rows`)
-  const hy_row_id* rows;       // the dimension rows that take part (device memory): the rows that pass its filter, or all of them -- or nullptr:
-                               // every row of the key column's table that passes `filter` (tested by the kernels that build the dimension's tables)
-  const hy_column* filter;     // rows == nullptr: the column the filter tests (a data column of the dimension's table), or nullptr: no filter
-  const struct ScanJob* filter_jobs;   // ... and its per-chunk jobs in device memory (prepare_scan_jobs)
+  const hy_row_id* rows;       // the dimension rows that take part (device memory): the rows that pass its filters, or all of them -- or nullptr:
+                               // every row of the key column's table that passes `filters` (tested by the kernels that build the dimension's tables)
+  StarProbeFilter filters[HY_MAX_STAR_FILTERS];   // rows == nullptr: the dimension's filters
+  uint32_t n_filters;          // ... 0: none
   uint64_t n_rows;             // how many -- or, with d_n_rows / a filter, at most how many
   const uint64_t* d_n_rows;    // the count in device memory (a scan's total that no host has read), or nullptr
   const hy_column* fact_key;   // the fact table's foreign key to this dimension
@@ -273,6 +278,8 @@ struct StarProbeDimension {
 // sparse, foreign-key segments the probe does not stream) -- nothing was produced.
 // The plan's Projection + AggregateHash inside the join (star_finish, join_star.hpp): asked for with `finish`, answered in `groups` --
 // groups->done: the join result was grouped where it was found (no RowIDs were written); otherwise the RowIDs are there as without it.
+// n_groupby == 0: ONE group, reduced per workgroup and added to a single accumulator row (counts[0] == 0: the join result is empty).
+// fact_filters: tests on the fact table's own columns, evaluated inside the probe pass before the dimensions are asked.
 struct StarFinishColumnSpec { uint32_t table; const hy_column* column; };   // table 0 = the fact table, d + 1 = dimension d; column nullptr: none
 struct StarFinishRequest {
   uint32_t n_groupby, n_aggregates;
@@ -286,7 +293,8 @@ struct StarFinishGroups {
   std::vector<uint64_t> keys, first, last, values, counts;   // [n][4], [n], [n], [n][8], [n]: first / last = row numbers of the join result
 };
 hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimensions, DeviceBuffer& fact_rows, std::vector<std::unique_ptr<DeviceBuffer>>& dimension_rows,
-                          uint64_t* n_rows, bool* applicable, const StarFinishRequest* finish = nullptr, StarFinishGroups* groups = nullptr);
+                          uint64_t* n_rows, bool* applicable, const StarFinishRequest* finish = nullptr, StarFinishGroups* groups = nullptr,
+                          const StarProbeFilter* fact_filters = nullptr, uint32_t n_fact_filters = 0);
 hy_status star_all_rows_of(const hy_column* column, DeviceBuffer& rows);   // every row of a data column's table as a PosList
 // scan.hip: the kernels of hy_poslist_translate queued on the current stream, nothing read back -- dense_offsets: [n_chunks + 1] device words,
 // the last of them the number of RowIDs written

@@ -54,6 +54,10 @@ struct PredicateArgs {
 // jobs[c] = the normalised test of chunk c.
 size_t scan_jobs_staging_bytes(const hy_column* column, const hy_predicate* predicate);
 hy_status prepare_scan_jobs(const hy_column* column, const hy_predicate* predicate, ScanJob* jobs, void* staging);
+// ... the same for `column [NOT] IN (list)`, checked like hy_table_scan_in_list does: KIND_VALUE_ID_SET jobs (the chunk's bitmap over its value ids)
+// for dictionary chunks, KIND_VALUE_LIST jobs (the sorted, padded key list) for every other one; bitmaps and keys live in `staging`
+size_t scan_jobs_staging_bytes(const hy_column* column, const hy_in_list* list);
+hy_status prepare_scan_jobs(const hy_column* column, const hy_in_list* list, ScanJob* jobs, void* staging);
 // ... the same for Validate (hy_validate's jobs over a column of HY_ENC_MVCC segments): KIND_VISIBLE, or JOB_ALL for entirely visible chunks
 hy_status prepare_visibility_scan_jobs(const hy_column* mvcc, uint32_t our_tid, uint32_t snapshot_commit_id, uint32_t can_use_chunk_shortcut, ScanJob* jobs, void* staging);
 

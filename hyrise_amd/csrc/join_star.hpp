@@ -20,6 +20,9 @@
 //   star_finish / star_finish_compact the plan's Projection + AggregateHash inside the join (round 6): where every GROUP BY column and
 //                                     every aggregate input is an int / long column of a joined table, the survivors are grouped where
 //                                     they are found -- no RowIDs written, no columns exported, no second pass by hy_aggregate_hash
+// hy_star_join_aggregate_where (the thirteen SSB queries): a dimension's filters -- up to four, IN lists among them -- are tested by
+// star_dim_fill<true>; the fact table's own filters at the head of a tile in star_probe_mask<L, S, StarFactFilters>; an aggregate without a
+// GROUP BY column is reduced per workgroup by star_finish<true>.  The instantiations hy_star_join_aggregate's plans take are the kernels they were.
 // HBM traffic: every foreign-key column once + 1 bit per row + 8 bytes x (1 + dimensions) per surviving row.
 #pragma once
 
@@ -71,19 +74,36 @@ struct StarDimensionJobs {
   const uint64_t* row_base[HY_MAX_STAR_DIMENSIONS];     // [n_chunks + 1] first row of every chunk of the table
   uint32_t n_chunks[HY_MAX_STAR_DIMENSIONS];
   uint32_t chunk_rows[HY_MAX_STAR_DIMENSIONS];          // rows of every chunk but the last where they agree, else 0
-  const DevSegment* filter_segments[HY_MAX_STAR_DIMENSIONS];   // nullptr: no filter
-  const ScanJob* filter_jobs[HY_MAX_STAR_DIMENSIONS];          // [n_chunks] the filter's normalised test per chunk (prepare_scan_jobs)
+  // the dimension's filters, a conjunction (hy_star_join_aggregate_where: up to HY_MAX_STAR_FILTERS; hy_star_join_aggregate: one)
+  uint32_t n_filters[HY_MAX_STAR_DIMENSIONS];                                       // 0: no filter
+  const DevSegment* filter_segments[HY_MAX_STAR_DIMENSIONS][HY_MAX_STAR_FILTERS];   // the column a filter tests
+  const ScanJob* filter_jobs[HY_MAX_STAR_DIMENSIONS][HY_MAX_STAR_FILTERS];          // [n_chunks] its normalised test per chunk (prepare_scan_jobs)
 };
 
+// Is `key` in the sorted key list of a KIND_VALUE_LIST job (hy_table_scan_in_list's: lo = the list in device memory, padded with its last key
+// to a power of two, span = its length before the padding)?  A branch-free lower bound, at most eight steps; the list is at most 2 KB that
+// every lane reads -- cache hits.
+__device__ __forceinline__ bool star_key_in_list(const ScanJob& job, uint64_t key) {
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(job.lo);
+  const uint32_t n = static_cast<uint32_t>(job.span);
+  const uint32_t padded = n <= 1 ? 1u : 1u << (32 - __clz(static_cast<int>(n - 1)));
+  uint32_t position = 0;
+  for (uint32_t step = padded >> 1; step != 0; step >>= 1) position += keys[position + step - 1] < key ? step : 0u;
+  return keys[position] == key;
+}
+
 // One row of a data segment against its chunk's job -- what scan_slices decides for the row (hy_scan_job.hpp; JOB_RANGE does not occur:
-// prepare_scan_jobs asks for none).  NULL never matches a comparison.
+// prepare_scan_jobs asks for none).  NULL never matches a comparison, nor IN, nor NOT IN.  LISTS (compile time): the jobs may be an IN list's
+// (hy_star_join_aggregate_where); without it the test is the one hy_star_join_aggregate's single predicate has always had.
+template <bool LISTS>
 __device__ __forceinline__ bool star_filter_row(const DevSegment& s, const ScanJob& job, uint32_t row) {
   if (job.mode == JOB_ALL) return true;
   if (job.mode == JOB_NONE) return false;
   const bool invert = job.flags & JF_INVERT;
   if (s.encoding == HY_ENC_DICTIONARY) {
     const uint32_t vid = aload_compressed(s.data, s.width, row);
-    if (job.kind == KIND_VALUE_ID_SET) return vid < job.null_vid && ((reinterpret_cast<const uint64_t*>(job.lo)[vid >> 6] >> (vid & 63)) & 1) != 0;
+    // (a LIKE's bitmap comes without JF_INVERT; NOT IN: the ids that are NOT in the bitmap, the NULL id excepted)
+    if (job.kind == KIND_VALUE_ID_SET) return vid < job.null_vid && (((reinterpret_cast<const uint64_t*>(job.lo)[vid >> 6] >> (vid & 63)) & 1) != 0) != (LISTS && invert);
     if (job.kind == KIND_NULLTEST) return (vid == s.aux_size) != invert;
     const bool in = (vid - static_cast<uint32_t>(job.lo)) <= static_cast<uint32_t>(job.span);
     return (in != invert) && vid != job.null_vid;
@@ -92,7 +112,15 @@ __device__ __forceinline__ bool star_filter_row(const DevSegment& s, const ScanJ
   if (job.kind == KIND_NULLTEST) return is_null != invert;
   if (is_null) return false;
   bool in;
-  if (s.encoding == HY_ENC_FRAME_OF_REFERENCE) {
+  if (LISTS && job.kind == KIND_VALUE_LIST) {   // the value's bits as the list's keys are made (scan.hip list_key_*: zero-extended, -0.0 folded onto 0.0)
+    uint64_t key;
+    if (s.encoding == HY_ENC_FRAME_OF_REFERENCE) key = aload_compressed(s.data, s.width, row) + static_cast<uint32_t>(static_cast<const int32_t*>(s.aux)[row / HY_FOR_BLOCK_SIZE]);
+    else if (s.data_type == HY_TYPE_INT || s.data_type == HY_TYPE_FLOAT) key = static_cast<const uint32_t*>(s.data)[row];
+    else key = static_cast<const uint64_t*>(s.data)[row];
+    const bool is_float = s.data_type == HY_TYPE_FLOAT || s.data_type == HY_TYPE_DOUBLE;
+    if (is_float && (s.data_type == HY_TYPE_FLOAT ? (static_cast<uint32_t>(key) << 1) == 0 : (key << 1) == 0)) key = 0;
+    in = star_key_in_list(job, key);
+  } else if (s.encoding == HY_ENC_FRAME_OF_REFERENCE) {
     const uint32_t x = aload_compressed(s.data, s.width, row) + static_cast<uint32_t>(static_cast<const int32_t*>(s.aux)[row / HY_FOR_BLOCK_SIZE]);
     in = (x - static_cast<uint32_t>(job.lo)) <= static_cast<uint32_t>(job.span);
   } else if (job.kind == KIND_U32) {
@@ -151,7 +179,9 @@ __global__ __launch_bounds__(256) void star_column_extent(const DevSegment* segm
 }
 
 // The dimensions' direct tables: bit and packed RowID of every key; *duplicate = 1 if a key comes twice.  (A dimension without a table
-// -- no rows -- has n = 0.)
+// -- no rows -- has n = 0.)  WHERE (compile time): a dimension may have several filters, IN lists among them; without it there is one predicate at
+// most, tested by the code that has always tested it.
+template <bool WHERE>
 __global__ __launch_bounds__(256) void star_dim_fill(StarDimensionJobs jobs, uint32_t* duplicate) {
   const uint32_t d = blockIdx.y, lane = threadIdx.x & 63;
   const DevSegment* segments = jobs.segments[d];
@@ -168,7 +198,11 @@ __global__ __launch_bounds__(256) void star_dim_fill(StarDimensionJobs jobs, uin
     uint32_t rel = 0;
     if (valid) {
       const hy_row_id row = rows ? rows[i] : star_row_of_table(jobs.row_base[d], jobs.n_chunks[d], jobs.chunk_rows[d], i);
-      if (!rows && jobs.filter_segments[d]) valid = star_filter_row(jobs.filter_segments[d][row.chunk_id], jobs.filter_jobs[d][row.chunk_id], row.chunk_offset);
+      if constexpr (WHERE) {   // the dimension's filters, in place: a row leaves at the first it fails
+        for (uint32_t k = 0; !rows && k < jobs.n_filters[d] && valid; ++k) valid = star_filter_row<true>(jobs.filter_segments[d][k][row.chunk_id], jobs.filter_jobs[d][k][row.chunk_id], row.chunk_offset);
+      } else {
+        if (!rows && jobs.n_filters[d]) valid = star_filter_row<false>(jobs.filter_segments[d][0][row.chunk_id], jobs.filter_jobs[d][0][row.chunk_id], row.chunk_offset);
+      }
     if (valid) {
       const Value v = column_value(segments, row.chunk_id, row.chunk_offset);
       valid = !v.is_null;
@@ -270,13 +304,39 @@ __device__ __forceinline__ void star_request_tile(const StarArgs& a, uint32_t ti
   }
 }
 
+// The fact table's own filters (hy_star_join_aggregate_where): a conjunction of up to HY_MAX_STAR_FILTERS tests on plain data columns of the fact
+// table, as per-chunk jobs (prepare_scan_jobs) -- the TableScans that come before the joins in the operator chain.
+struct StarFactFilters {
+  const DevSegment* segments[HY_MAX_STAR_FILTERS];   // [n_chunks] the column a filter tests
+  const ScanJob* jobs[HY_MAX_STAR_FILTERS];          // [n_chunks] its normalised test per chunk
+  uint32_t n;
+};
+
 // Which of the tile's rows survive every dimension -> masks[tile], counts[tile] (zeroed by the host; a wave adds its survivors: no barrier --
 // the sixteen waves of the workgroup run their tiles' loads and lookups independently of each other)
-template <uint32_t N_LDS, uint32_t N_STREAM>
+// FILTERS (compile time: nothing, or StarFactFilters; the filter-less instantiation is the kernel it was, to the instruction): the fact table's
+// filters come first -- a tile lies in one chunk, so a filter's descriptor and job are wave-uniform; the first filter looks at the lane's eight
+// rows, every further one at the rows still alive -- and a row they drop is never asked in a dimension's table in global memory.
+__device__ __forceinline__ uint32_t star_fact_filters(const StarArgs& a, uint32_t tile, uint32_t first, uint32_t alive, const StarFactFilters& filters) {
+  const SliceView fact = uniform_view(a.table[0].views + tile);
+  for (uint32_t k = 0; k < filters.n; ++k) {
+    const DevSegment& segment = filters.segments[k][fact.chunk];
+    const ScanJob& job = filters.jobs[k][fact.chunk];
+    uint32_t pending = alive;
+    while (pending) {
+      const uint32_t j = __ffs(pending) - 1;
+      pending &= pending - 1;
+      if (!star_filter_row<true>(segment, job, fact.row_begin + first + j)) alive &= ~(1u << j);
+    }
+  }
+  return alive;
+}
+template <uint32_t N_LDS, uint32_t N_STREAM, typename... FILTERS>
 __device__ __forceinline__ void star_probe_tile(const StarArgs& a, uint32_t tile, uint32_t tid, uint32_t first, const StarTileWords& t, const uint32_t (&kind)[STAR_LDS_DIMENSIONS], uint32_t rows,
-                                                const uint32_t* s_star_bits) {
+                                                const uint32_t* s_star_bits, const FILTERS&... filters) {
   const uint32_t lane = tid & 63;
   uint32_t alive = first >= rows ? 0u : (rows - first < 8 ? (1u << (rows - first)) - 1u : 0xFFu);
+  if constexpr (sizeof...(FILTERS) != 0) alive = star_fact_filters(a, tile, first, alive, filters...);
 #pragma unroll
   for (uint32_t d = 0; d < STAR_LDS_DIMENSIONS; ++d) {
     if (d >= N_LDS) continue;
@@ -343,8 +403,8 @@ __device__ __forceinline__ void star_probe_tile(const StarArgs& a, uint32_t tile
 
 // Persistent workgroups, a tile's words requested while the tile before is looked up (two fixed sets of registers, the loop unrolled by two:
 // rotating one set into the other would wait for the loads just issued).
-template <uint32_t N_LDS, uint32_t N_STREAM>
-__global__ __launch_bounds__(STAR_THREADS) void star_probe_mask(StarArgs a) {
+template <uint32_t N_LDS, uint32_t N_STREAM, typename... FILTERS>
+__global__ __launch_bounds__(STAR_THREADS) void star_probe_mask(StarArgs a, FILTERS... filters) {
   extern __shared__ __attribute__((aligned(16))) uint32_t s_star_bits[];
   const uint32_t tid = threadIdx.x;
   for (uint32_t d = 0; d < N_LDS; ++d) {
@@ -360,10 +420,10 @@ __global__ __launch_bounds__(STAR_THREADS) void star_probe_mask(StarArgs a) {
   for (uint32_t tile = blockIdx.x; tile < a.n_tiles; tile += 2 * gridDim.x) {
     const uint32_t next = tile + gridDim.x, after = tile + 2 * gridDim.x;
     star_request_tile<N_LDS + N_STREAM>(a, next < a.n_tiles ? next : last_tile, first, odd, kind_odd, &rows_odd);
-    star_probe_tile<N_LDS, N_STREAM>(a, tile, tid, first, even, kind_even, rows_even, s_star_bits);
+    star_probe_tile<N_LDS, N_STREAM>(a, tile, tid, first, even, kind_even, rows_even, s_star_bits, filters...);
     if (next >= a.n_tiles) break;
     star_request_tile<N_LDS + N_STREAM>(a, after < a.n_tiles ? after : last_tile, first, even, kind_even, &rows_even);
-    star_probe_tile<N_LDS, N_STREAM>(a, next, tid, first, odd, kind_odd, rows_odd, s_star_bits);
+    star_probe_tile<N_LDS, N_STREAM>(a, next, tid, first, odd, kind_odd, rows_odd, s_star_bits, filters...);
   }
 }
 
@@ -768,6 +828,11 @@ constexpr size_t star_finish_lds_bytes(uint32_t n_aggregates) {
          8 * size_t{STAR_FINISH_SLOTS} * (STAR_FINISH_KEYS + (n_aggregates ? n_aggregates : 1)) + 4 * size_t{STAR_FINISH_SLOTS} * 4 + 64;
 }
 
+// SINGLE (compile time; hy_star_join_aggregate_where without a GROUP BY column -- SSB Q1.x): ONE group.  A thread keeps the aggregates of the
+// survivors it looks at in registers; when the workgroup has seen its last tile the lanes of a wave are folded with shuffles, the waves meet in
+// one row of LDS, and the workgroup adds that row ONCE to row 0 of the global table (star_finish_single_init) -- no hash, no slot to claim, no
+// first / last rows (the one group's representative is the join result's first row), and star_finish_single_header instead of star_finish_compact.
+template <bool SINGLE>
 __global__ __launch_bounds__(STAR_FINISH_THREADS, 4) void star_finish(StarArgs a, StarFinishArgs f) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_star_finish[];
   uint64_t* s_keys = reinterpret_cast<uint64_t*>(s_star_finish);
@@ -784,12 +849,16 @@ __global__ __launch_bounds__(STAR_FINISH_THREADS, 4) void star_finish(StarArgs a
   static_assert(WORDS % 4 == 0 && STAR_EMIT_TILES * (HY_MAX_STAR_DIMENSIONS + STAR_FINISH_FACT_COLUMNS) <= STAR_FINISH_THREADS, "a thread's mask words are 16-byte pieces; one view per thread");
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // direct-mapped groups (star_finish_plan) or the hash table
-  const uint32_t n_codes = f.direct->n_codes;
-  const bool direct = f.direct->direct != 0;
+  const uint32_t n_codes = SINGLE ? 0u : f.direct->n_codes;   // (SINGLE: star_finish_plan has not run)
+  const bool direct = SINGLE ? false : f.direct->direct != 0;
   uint32_t stride[STAR_FINISH_KEYS];
   long long low[STAR_FINISH_KEYS];
 #pragma unroll
-  for (uint32_t g = 0; g < STAR_FINISH_KEYS; ++g) { stride[g] = f.direct->stride[g]; low[g] = f.direct->low[g]; }
+  for (uint32_t g = 0; g < STAR_FINISH_KEYS; ++g) { stride[g] = SINGLE ? 0u : f.direct->stride[g]; low[g] = SINGLE ? 0ll : f.direct->low[g]; }
+  uint64_t single_value[STAR_FINISH_AGGREGATES];
+  uint32_t single_count = 0;
+#pragma unroll
+  for (uint32_t g = 0; g < STAR_FINISH_AGGREGATES; ++g) single_value[g] = star_initial_value(f.aggregates[g < f.n_aggregates ? g : 0u].function);
   for (uint32_t i = tid; i < STAR_FINISH_SLOTS; i += STAR_FINISH_THREADS) {
     s_tags[i] = 0;
     if (direct && i < n_codes) {
@@ -939,6 +1008,19 @@ __global__ __launch_bounds__(STAR_FINISH_THREADS, 4) void star_finish(StarArgs a
           }
           return static_cast<uint64_t>(v.i);
         };
+        if constexpr (SINGLE) {
+#pragma unroll
+          for (uint32_t g = 0; g < STAR_FINISH_AGGREGATES; ++g) {
+            if (g >= f.n_aggregates || f.aggregates[g].left.kind == STAR_COLUMN_NONE) continue;
+            const uint32_t function = f.aggregates[g].function;
+            const long long input = static_cast<long long>(input_of(g, &refuse));
+            const long long held = static_cast<long long>(single_value[g]);
+            single_value[g] = static_cast<uint64_t>(function == HY_AGG_MIN ? (input < held ? input : held) : function == HY_AGG_MAX ? (input > held ? input : held) : held + input);
+          }
+          ++single_count;
+          if (refuse) s_wave[WAVES] = 1;
+          continue;
+        }
         const uint32_t hash = star_tuple_hash(tuple, f.n_groupby);
         const uint32_t position = first_tile * SLICE_ROWS + entry;   // (tile << 13 | row, tiles counted from the table's first)
         if (f.debug & 2) { if (hash == 0x12345u) s_wave[WAVES] = 1; continue; }
@@ -984,6 +1066,43 @@ __global__ __launch_bounds__(STAR_FINISH_THREADS, 4) void star_finish(StarArgs a
     }
   }
   __syncthreads();
+  if constexpr (SINGLE) {   // lanes -> the wave (shuffles) -> the workgroup's row in LDS (one atomic per wave and aggregate) -> row 0 of the global table, once
+    if (tid < STAR_FINISH_AGGREGATES) s_values[tid] = star_initial_value(f.aggregates[tid < f.n_aggregates ? tid : 0u].function);
+    if (tid == 0) s_counts[0] = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t g = 0; g < STAR_FINISH_AGGREGATES; ++g) {
+      if (g >= f.n_aggregates || f.aggregates[g].left.kind == STAR_COLUMN_NONE) continue;   // (uniform)
+      const uint32_t function = f.aggregates[g].function;
+      long long value = static_cast<long long>(single_value[g]);
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) {
+        const long long other = __shfl_xor(value, d, 64);
+        value = function == HY_AGG_MIN ? (other < value ? other : value) : function == HY_AGG_MAX ? (other > value ? other : value) : value + other;
+      }
+      if (lane == 0) {
+        if (function == HY_AGG_MIN) atomicMin(reinterpret_cast<long long*>(&s_values[g]), value);
+        else if (function == HY_AGG_MAX) atomicMax(reinterpret_cast<long long*>(&s_values[g]), value);
+        else atomicAdd(reinterpret_cast<unsigned long long*>(&s_values[g]), static_cast<unsigned long long>(value));
+      }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) single_count += __shfl_xor(single_count, d, 64);
+    if (lane == 0 && single_count) atomicAdd(&s_counts[0], single_count);
+    __syncthreads();
+    if (s_counts[0] != 0) {   // (uniform; a workgroup without a survivor adds nothing)
+      if (tid < f.n_aggregates && f.aggregates[tid].left.kind != STAR_COLUMN_NONE) {
+        const uint32_t function = f.aggregates[tid].function;
+        uint64_t* target = &f.values[tid];
+        if (function == HY_AGG_MIN) atomicMin(reinterpret_cast<long long*>(target), static_cast<long long>(s_values[tid]));
+        else if (function == HY_AGG_MAX) atomicMax(reinterpret_cast<long long*>(target), static_cast<long long>(s_values[tid]));
+        else if (function != HY_AGG_COUNT) atomicAdd(reinterpret_cast<unsigned long long*>(target), static_cast<unsigned long long>(s_values[tid]));
+      }
+      if (tid == 0) atomicAdd(&f.counts[0], s_counts[0]);
+    }
+    if (s_wave[WAVES] != 0 && tid == 0) f.flags[STAR_FLAG_REFUSED] = 1;
+    return;
+  }
   // the workgroup's groups -> the global table
   bool gave_up = s_wave[WAVES] != 0;
   for (uint32_t slot = tid; slot < STAR_FINISH_SLOTS; slot += STAR_FINISH_THREADS) {
@@ -1073,6 +1192,24 @@ __global__ __launch_bounds__(256) void star_finish_compact(StarArgs a, StarFinis
   }
 }
 
+// The group-less finish: row 0 of the global table before star_finish<true> ...
+__global__ __launch_bounds__(64) void star_finish_single_init(StarFinishArgs f) {
+  if (threadIdx.x < STAR_FINISH_AGGREGATES) f.values[threadIdx.x] = threadIdx.x < f.n_aggregates ? star_initial_value(f.aggregates[threadIdx.x].function) : 0ull;
+  if (threadIdx.x == 0) f.counts[0] = 0;
+}
+// ... and what the host reads after it (pinned memory): the header, the row's values and its count -- nothing to order, nothing to rank
+__global__ __launch_bounds__(64) void star_finish_single_header(StarArgs a, StarFinishArgs f, const uint32_t* duplicate, StarFinishHeader* header, uint64_t* out_values, uint64_t* out_counts) {
+  if (threadIdx.x < STAR_FINISH_AGGREGATES) out_values[threadIdx.x] = f.values[threadIdx.x];
+  if (threadIdx.x == 0) {
+    out_counts[0] = f.counts[0];
+    header->refused = f.flags[STAR_FLAG_REFUSED] | f.flags[STAR_FLAG_NULL_ATTRIBUTE];
+    header->n_groups = 1;
+    header->key_twice = *duplicate;
+    header->total = a.base[a.n_tiles];
+  }
+  __threadfence_system();
+}
+
 // Can the probe kernels read this column as a fact table's foreign key (int32 keys, every segment one a SliceView describes)?
 static bool star_reads_fact_key(const hy_column* column) {
   if (!column || column->is_reference || column->is_mvcc || column->has_compressed || column->data_type != HY_TYPE_INT) return false;
@@ -1091,10 +1228,11 @@ static bool star_finish_reads(const hy_column* column) {
   return column->data_type == HY_TYPE_INT || column->data_type == HY_TYPE_LONG;
 }
 
-// Is the plan's aggregate one star_finish computes?  (MIN / MAX / SUM / AVG / COUNT over int / long cells, one to four int / long GROUP BY columns)
+// Is the plan's aggregate one star_finish computes?  (MIN / MAX / SUM / AVG / COUNT over int / long cells, up to four int / long GROUP BY columns)
 static bool star_finish_applies(const StarFinishRequest* finish, uint32_t n_dimensions, const hy_column* fact_shape) {
   if (!finish || !option(HY_OPT_STAR_FUSED_FINISH)) return false;
-  if (finish->n_groupby == 0 || finish->n_groupby > STAR_FINISH_KEYS || finish->n_aggregates > STAR_FINISH_AGGREGATES) return false;
+  if (finish->n_groupby > STAR_FINISH_KEYS || finish->n_aggregates > STAR_FINISH_AGGREGATES) return false;   // (no GROUP BY column: the single-group finish)
+  if (finish->n_groupby == 0 && finish->n_aggregates == 0) return false;
   if (fact_shape->rows >= (1ull << 31) || fact_shape->n_slices >= (1u << 19)) return false;   // (positions are tile << 13 | row in 32 bits, counts 32 bits)
   auto column_ok = [&](const StarFinishColumnSpec& c) { return c.table <= n_dimensions && star_finish_reads(c.column); };
   for (uint32_t g = 0; g < finish->n_groupby; ++g) if (!column_ok(finish->groupby[g])) return false;
@@ -1109,7 +1247,7 @@ static bool star_finish_applies(const StarFinishRequest* finish, uint32_t n_dime
 }
 
 hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimensions, DeviceBuffer& fact_rows, std::vector<std::unique_ptr<DeviceBuffer>>& dimension_rows, uint64_t* n_rows,
-                          bool* applicable, const StarFinishRequest* finish, StarFinishGroups* groups) {
+                          bool* applicable, const StarFinishRequest* finish, StarFinishGroups* groups, const StarProbeFilter* fact_filters, uint32_t n_fact_filters) {
   *applicable = false;
   *n_rows = 0;
   if (groups) { groups->done = false; groups->n_groups = 0; }
@@ -1128,6 +1266,14 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
     const hy_column* rows_of = dim.key->is_reference ? dim.key->ref : dim.key;
     if (!rows_of || rows_of->n_chunks > 65536) return HY_OK;
     for (const hy_segment& s : rows_of->host_segments) if (s.size > 65536) return HY_OK;
+  }
+  // the fact table's own filters: plain data columns of the fact table, tested row by row inside the probe (star_filter_row reads 1-, 2- and 4-byte
+  // vectors: RunLength and bit-packed segments keep the chain of TableScans)
+  if (n_fact_filters > HY_MAX_STAR_FILTERS || (n_fact_filters && !fact_filters)) return HY_OK;
+  for (uint32_t k = 0; k < n_fact_filters; ++k) {
+    const hy_column* column = fact_filters[k].column;
+    if (!column || !fact_filters[k].jobs || column->is_reference || column->is_mvcc || column->has_compressed || column->n_chunks != shape->n_chunks) return HY_OK;
+    for (uint32_t c = 0; c < shape->n_chunks; ++c) if (column->host_segments[c].size != shape->host_segments[c].size) return HY_OK;
   }
   hipStream_t stream = current_stream();
   // ---- the aggregate inside the join (star_finish): which columns it reads ----------------------------------------------------------------
@@ -1202,6 +1348,7 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
   StarDimensionJobs jobs;
   std::memset(&jobs, 0, sizeof(jobs));
   uint64_t most_rows = 0;
+  bool where_fill = false;   // some dimension has several filters or an IN list: star_dim_fill<true>
   for (uint32_t d = 0; d < n_dimensions; ++d) {
     jobs.segments[d] = dimensions[d].key->d_segments;
     jobs.rows[d] = dimensions[d].rows;
@@ -1216,8 +1363,13 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
       if (key->n_chunks && key->host_segments[key->n_chunks - 1].size > size) size = 0;
       jobs.chunk_rows[d] = size;
     }
-    jobs.filter_segments[d] = dimensions[d].filter ? dimensions[d].filter->d_segments : nullptr;
-    jobs.filter_jobs[d] = dimensions[d].filter_jobs;
+    jobs.n_filters[d] = dimensions[d].rows ? 0u : std::min<uint32_t>(dimensions[d].n_filters, HY_MAX_STAR_FILTERS);
+    where_fill = where_fill || jobs.n_filters[d] > 1;
+    for (uint32_t k = 0; k < jobs.n_filters[d]; ++k) {
+      where_fill = where_fill || dimensions[d].filters[k].in_list;
+      jobs.filter_segments[d][k] = dimensions[d].filters[k].column->d_segments;
+      jobs.filter_jobs[d][k] = dimensions[d].filters[k].jobs;
+    }
     most_rows = std::max(most_rows, dimensions[d].n_rows);
   }
   // (a row per thread: a row is three dependent round trips and an atomic that is waited for -- 256 workgroups walking a million rows spent 59 us on it)
@@ -1255,7 +1407,8 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
     }
   }
   for (uint32_t d = 0; d < n_dimensions; ++d) if (built[d]->empty) { jobs.n[d] = 0; jobs.n_in_memory[d] = nullptr; }
-  if (!nothing_joins) hipLaunchKernelGGL(star_dim_fill, dim3(job_grid, n_dimensions), dim3(256), 0, stream, jobs, duplicate.as<uint32_t>());
+  if (!nothing_joins && where_fill) hipLaunchKernelGGL(star_dim_fill<true>, dim3(job_grid, n_dimensions), dim3(256), 0, stream, jobs, duplicate.as<uint32_t>());
+  else if (!nothing_joins) hipLaunchKernelGGL(star_dim_fill<false>, dim3(job_grid, n_dimensions), dim3(256), 0, stream, jobs, duplicate.as<uint32_t>());
   if (!nothing_joins && plan.on && !plan.attributes.empty()) {   // what the aggregate reads of the dimensions, per key
     StarAttributeJobs attribute_jobs;
     std::memset(&attribute_jobs, 0, sizeof(attribute_jobs));
@@ -1287,6 +1440,10 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
         groups->input_type[g] = !spec.left.column ? static_cast<uint32_t>(HY_TYPE_LONG) : spec.op == HY_STAR_NO_OP ? spec.left.column->data_type : expression_common_type(spec.left.column->data_type, spec.right.column->data_type);
       }
       groups->keys.clear(); groups->first.clear(); groups->last.clear(); groups->values.clear(); groups->counts.clear();
+      if (finish->n_groupby == 0) {   // (no GROUP BY column: one group, of no rows)
+        groups->n_groups = 1;
+        groups->keys.assign(STAR_FINISH_KEYS, 0); groups->first.assign(1, 0); groups->last.assign(1, 0); groups->values.assign(STAR_FINISH_AGGREGATES, 0); groups->counts.assign(1, 0);
+      }
       groups->done = true;
       *applicable = true;
       return HY_OK;
@@ -1339,10 +1496,14 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
   a.masks = masks.as<uint8_t>();
   a.counts = counts.as<uint32_t>();
   a.base = base.as<uint64_t>();
+  typedef void (*StarProbeKernel)(StarArgs);                        // star_probe_mask<L, S>: no fact filter
+  typedef void (*StarProbeWhereKernel)(StarArgs, StarFactFilters);   // star_probe_mask<L, S, StarFactFilters>
   static OncePerDevice lds_raised;
   uint64_t device_bit = 0;
   if (lds_raised.pending(&device_bit)) {
-#define HY_STAR_RAISE(L, S) HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(star_probe_mask<L, S>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * STAR_LDS_WORDS));
+#define HY_STAR_RAISE(L, S)                                                                                                                           \
+  HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(static_cast<StarProbeKernel>(star_probe_mask<L, S>)), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * STAR_LDS_WORDS)); \
+  HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(static_cast<StarProbeWhereKernel>(star_probe_mask<L, S, StarFactFilters>)), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * STAR_LDS_WORDS));
     HY_STAR_RAISE(0, 0) HY_STAR_RAISE(1, 0) HY_STAR_RAISE(2, 0) HY_STAR_RAISE(3, 0) HY_STAR_RAISE(4, 0)
     HY_STAR_RAISE(0, 1) HY_STAR_RAISE(1, 1) HY_STAR_RAISE(2, 1) HY_STAR_RAISE(3, 1)
 #undef HY_STAR_RAISE
@@ -1353,7 +1514,15 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
   // (instantiated per number of LDS-resident dimensions, and with or without a streamed one behind them -- the first dimension asked in
   //  global memory, if a word slot is left: the kernel requests exactly their words, unconditionally)
   const uint32_t streamed = a.n_lds < STAR_LDS_DIMENSIONS && a.n_lds < a.n_tables ? 1u : 0u;
-#define HY_STAR_LAUNCH(L, S) hipLaunchKernelGGL((star_probe_mask<L, S>), dim3(probe_grid), dim3(STAR_THREADS), 4 * size_t{lds_words}, stream, a)
+  StarFactFilters where;
+  std::memset(&where, 0, sizeof(where));
+  where.n = n_fact_filters;
+  for (uint32_t k = 0; k < n_fact_filters; ++k) { where.segments[k] = fact_filters[k].column->d_segments; where.jobs[k] = fact_filters[k].jobs; }
+#define HY_STAR_LAUNCH(L, S)                                                                                                                    \
+  {                                                                                                                                             \
+    if (where.n) hipLaunchKernelGGL(static_cast<StarProbeWhereKernel>(star_probe_mask<L, S, StarFactFilters>), dim3(probe_grid), dim3(STAR_THREADS), 4 * size_t{lds_words}, stream, a, where); \
+    else hipLaunchKernelGGL(static_cast<StarProbeKernel>(star_probe_mask<L, S>), dim3(probe_grid), dim3(STAR_THREADS), 4 * size_t{lds_words}, stream, a);                                    \
+  }
   switch (a.n_lds * 2 + streamed) {
     case 0: HY_STAR_LAUNCH(0, 0); break;
     case 1: HY_STAR_LAUNCH(0, 1); break;
@@ -1447,17 +1616,28 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
     static OncePerDevice finish_lds_raised;
     uint64_t finish_bit = 0;
     if (finish_lds_raised.pending(&finish_bit)) {
-      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(star_finish), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(star_finish_lds_bytes(STAR_FINISH_AGGREGATES))));
+      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(star_finish<false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(star_finish_lds_bytes(STAR_FINISH_AGGREGATES))));
+      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(star_finish<true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(star_finish_lds_bytes(STAR_FINISH_AGGREGATES))));
       finish_lds_raised.done(finish_bit);
     }
     const uint32_t tile_groups = (a.n_tiles + STAR_EMIT_TILES - 1) / STAR_EMIT_TILES;
-    hipLaunchKernelGGL(star_finish_plan, dim3(1), dim3(256), 0, stream, f);
-    profile_begin(stream, HY_KERNEL_AGGREGATE);
-    hipLaunchKernelGGL(star_finish, dim3(std::max(1u, std::min(tile_groups, (1024 / STAR_FINISH_THREADS) * device_cu_count()))), dim3(STAR_FINISH_THREADS), star_finish_lds_bytes(f.n_aggregates), stream, a, f);
-    profile_end(stream);
+    const dim3 finish_grid(std::max(1u, std::min(tile_groups, (1024 / STAR_FINISH_THREADS) * device_cu_count())));
+    const bool single = f.n_groupby == 0;
     uint64_t *d_keys, *d_first, *d_last, *d_values, *d_counts;
     arrays(staged_dev, &d_keys, &d_first, &d_last, &d_values, &d_counts);
-    hipLaunchKernelGGL(star_finish_compact, dim3(f.capacity / 256), dim3(256), 0, stream, a, f, duplicate.as<uint32_t>(), reinterpret_cast<StarFinishHeader*>(staged_dev), d_keys, d_first, d_last, d_values, d_counts);
+    if (single) {   // one group: reduced per workgroup, no plan, no table, nothing to compact
+      hipLaunchKernelGGL(star_finish_single_init, dim3(1), dim3(64), 0, stream, f);
+      profile_begin(stream, HY_KERNEL_AGGREGATE);
+      hipLaunchKernelGGL(star_finish<true>, finish_grid, dim3(STAR_FINISH_THREADS), star_finish_lds_bytes(f.n_aggregates), stream, a, f);
+      profile_end(stream);
+      hipLaunchKernelGGL(star_finish_single_header, dim3(1), dim3(64), 0, stream, a, f, duplicate.as<uint32_t>(), reinterpret_cast<StarFinishHeader*>(staged_dev), d_values, d_counts);
+    } else {
+      hipLaunchKernelGGL(star_finish_plan, dim3(1), dim3(256), 0, stream, f);
+      profile_begin(stream, HY_KERNEL_AGGREGATE);
+      hipLaunchKernelGGL(star_finish<false>, finish_grid, dim3(STAR_FINISH_THREADS), star_finish_lds_bytes(f.n_aggregates), stream, a, f);
+      profile_end(stream);
+      hipLaunchKernelGGL(star_finish_compact, dim3(f.capacity / 256), dim3(256), 0, stream, a, f, duplicate.as<uint32_t>(), reinterpret_cast<StarFinishHeader*>(staged_dev), d_keys, d_first, d_last, d_values, d_counts);
+    }
     HY_HIP(hipGetLastError());
     HY_HIP(hipStreamSynchronize(stream));
     StarFinishHeader header;
@@ -1469,6 +1649,7 @@ hy_status star_probe_rows(const StarProbeDimension* dimensions, uint32_t n_dimen
       arrays(staged_host, &h_keys, &h_first, &h_last, &h_values, &h_counts);
       const size_t n = header.n_groups;
       groups->n_groups = header.n_groups;
+      if (single) { std::memset(h_keys, 0, 8 * STAR_FINISH_KEYS); h_first[0] = 0; h_last[0] = 0; }   // (the one group's representative: the join result's first row)
       groups->keys.assign(h_keys, h_keys + n * STAR_FINISH_KEYS);
       groups->first.assign(h_first, h_first + n);
       groups->last.assign(h_last, h_last + n);

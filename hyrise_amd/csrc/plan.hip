@@ -149,7 +149,7 @@ static hy_status materialise(const hy_column* base, const hy_row_id* rows, uint6
 }
 
 // The rows of `filter_column` that satisfy the predicate, as one dense PosList in device memory
-static hy_status filtered_rows(const hy_column* filter_column, const hy_predicate* predicate, DeviceBuffer& rows, uint64_t* n_rows, DeviceBuffer* count_in_memory = nullptr) {
+static hy_status filtered_rows(const hy_column* filter_column, const hy_predicate* predicate, const hy_in_list* in_list, DeviceBuffer& rows, uint64_t* n_rows, DeviceBuffer* count_in_memory = nullptr) {
   DeviceBuffer regions, offsets, counts;
   const uint64_t capacity = std::max<uint64_t>(1, filter_column->rows);
   HY_TRY(regions.alloc(sizeof(hy_row_id) * capacity));
@@ -164,12 +164,33 @@ static hy_status filtered_rows(const hy_column* filter_column, const hy_predicat
   scan.capacity = capacity;
   scan.offsets = offsets.as<uint64_t>();
   scan.counts = counts.as<uint32_t>();
-  HY_TRY(hy_table_scan(filter_column, predicate, nullptr, 0, &scan));
+  if (in_list) HY_TRY(hy_table_scan_in_list(filter_column, in_list, nullptr, 0, &scan));   // column [NOT] IN (...)
+  else HY_TRY(hy_table_scan(filter_column, predicate, nullptr, 0, &scan));
   if (!count_in_memory) return hy_poslist_translate(filter_column, &scan, HY_POSLIST_DENSE, rows.as<hy_row_id>(), capacity, n_rows);
   // (the fused probe: the kernels that read the rows read their number from device memory too -- no host in between)
   HY_TRY(count_in_memory->alloc(8 * (size_t{filter_column->n_chunks} + 2)));
   *n_rows = capacity;
   return poslist_translate_queued(filter_column, &scan, HY_POSLIST_DENSE, rows.as<hy_row_id>(), capacity, count_in_memory->as<uint64_t>());
+}
+
+// The rows of a table that pass a conjunction of filters, as the chain of TableScans Hyrise runs: the first scan reads the data column, every
+// further one the next filter's column THROUGH the rows left so far (ReferenceSegments), and its matches are translated back to the table's
+// RowIDs (hy_poslist_translate) -- a NULL cell passes no filter.
+static hy_status filter_chain_rows(const hy_star_filter* filters, uint32_t n_filters, std::unique_ptr<DeviceBuffer>& rows, uint64_t* n_rows) {
+  rows = std::make_unique<DeviceBuffer>();
+  HY_TRY(filtered_rows(filters[0].column, &filters[0].predicate, filters[0].in_list, *rows, n_rows));
+  for (uint32_t k = 1; k < n_filters && *n_rows; ++k) {
+    auto through = std::make_unique<ColumnHandle>();
+    auto next = std::make_unique<DeviceBuffer>();
+    uint64_t n_next = 0;
+    hy_status status = reference_column(filters[k].column, rows->as<hy_row_id>(), *n_rows, *through);
+    if (status == HY_OK) status = filtered_rows(through->column, &filters[k].predicate, filters[k].in_list, *next, &n_next);
+    if (t_plan_done_with) t_plan_done_with->push_back(std::move(through));
+    HY_TRY(status);
+    rows = std::move(next);   // (the list it replaces goes back to this thread's pool: handed out again in stream order)
+    *n_rows = n_next;
+  }
+  return HY_OK;
 }
 
 struct JoinOutput {
@@ -220,7 +241,8 @@ static hy_status join_inner(const hy_column* build, const hy_column* probe, Join
 // join result (aggregate.hip run_aggregate): rows ordered by the groups' first rows, or by ascending key under the immediate-key shortcut
 // (one int GROUP BY column whose key range is below 1.2 x the rows, aggregate_hash.cpp:388-401, 770-804: the representative row is then the
 // group's LAST row); representative rows as RowIDs of the intermediate table the chain would have aggregated (DENSE_CHUNK rows per chunk);
-// result types of window_function_traits.hpp:11-77.  No cell is NULL (star_finish refuses NULL inputs).
+// result types of window_function_traits.hpp:11-77.  No cell is NULL (star_finish refuses NULL inputs) -- but those of the one group of an
+// aggregate without a GROUP BY column over no rows.
 static hy_status write_star_groups(const StarFinishGroups& groups, const hy_star_column* groupby, uint32_t n_groupby, const hy_star_aggregate* aggregates, uint32_t n_aggregates,
                                    uint64_t n_rows, hy_aggregate_result* result) {
   const uint32_t n = groups.n_groups;
@@ -248,8 +270,10 @@ static hy_status write_star_groups(const StarFinishGroups& groups, const hy_star
     for (uint32_t o = 0; o < n; ++o) {
       const int64_t value = static_cast<int64_t>(groups.values[size_t{order[o]} * 8 + g]);
       const uint64_t count = groups.counts[order[o]];
-      if (col.is_null) col.is_null[o] = 0;
+      const bool is_null = count == 0 && function != HY_AGG_COUNT;   // (no GROUP BY column, no row: COUNT 0, every other aggregate NULL with a zeroed value)
+      if (col.is_null) col.is_null[o] = is_null ? 1 : 0;
       if (function == HY_AGG_COUNT) static_cast<int64_t*>(col.values)[o] = static_cast<int64_t>(count);
+      else if (is_null) std::memset(static_cast<char*>(col.values) + size_t{o} * type_bytes(col.data_type), 0, type_bytes(col.data_type));
       else if (function == HY_AGG_AVG) static_cast<double*>(col.values)[o] = static_cast<double>(value) / static_cast<double>(count);   // (the chain adds doubles of integers: exact below 2^53)
       else if (col.data_type == HY_TYPE_INT) static_cast<int32_t*>(col.values)[o] = static_cast<int32_t>(value);
       else static_cast<int64_t*>(col.values)[o] = value;
@@ -262,25 +286,30 @@ static hy_status write_star_groups(const StarFinishGroups& groups, const hy_star
 
 using namespace hy;
 
-extern "C" {
-
-hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n_dimensions, const hy_star_column* groupby, uint32_t n_groupby,
-                                 const hy_star_aggregate* aggregates, uint32_t n_aggregates, hy_aggregate_result* result, uint64_t* joined_rows) {
-  if (!dimensions || !n_dimensions || n_dimensions > HY_MAX_STAR_DIMENSIONS) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: 1 .. %d dimensions", static_cast<int>(HY_MAX_STAR_DIMENSIONS));
-  if ((n_groupby && !groupby) || (n_aggregates && !aggregates) || !result) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: null argument");
-  if (n_aggregates > HY_MAX_STAR_AGGREGATES || n_groupby > HY_MAX_STAR_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "hy_star_join_aggregate: at most %d GROUP BY columns / aggregates", static_cast<int>(HY_MAX_STAR_AGGREGATES));
+// hy_star_join_aggregate (`where` false: one filter per dimension at most, no fact filter, the fused finish for grouped aggregates only) and
+// hy_star_join_aggregate_where behind their argument checks -- one plan.
+static hy_status star_join(const char* who, bool where, const hy_star_dimension_where* dimensions, uint32_t n_dimensions, const hy_star_filter* fact_filters, uint32_t n_fact_filters,
+                           const hy_star_column* groupby, uint32_t n_groupby, const hy_star_aggregate* aggregates, uint32_t n_aggregates, hy_aggregate_result* result, uint64_t* joined_rows) {
+  if (!dimensions || !n_dimensions || n_dimensions > HY_MAX_STAR_DIMENSIONS) return fail(HY_ERR_INVALID, "%s: 1 .. %d dimensions", who, static_cast<int>(HY_MAX_STAR_DIMENSIONS));
+  if ((n_groupby && !groupby) || (n_aggregates && !aggregates) || (n_fact_filters && !fact_filters) || !result) return fail(HY_ERR_INVALID, "%s: null argument", who);
+  if (n_aggregates > HY_MAX_STAR_AGGREGATES || n_groupby > HY_MAX_STAR_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "%s: at most %d GROUP BY columns / aggregates", who, static_cast<int>(HY_MAX_STAR_AGGREGATES));
+  if (n_fact_filters > HY_MAX_STAR_FILTERS) return fail(HY_ERR_UNSUPPORTED, "%s: %u filters on the fact table, at most %d are taken (scan the table first)", who, n_fact_filters, static_cast<int>(HY_MAX_STAR_FILTERS));
+  for (uint32_t d = 0; d < n_dimensions; ++d) {
+    if (dimensions[d].n_filters > HY_MAX_STAR_FILTERS) return fail(HY_ERR_UNSUPPORTED, "%s: dimension %u: %u filters, at most %d are taken (scan the table first)", who, d, dimensions[d].n_filters, static_cast<int>(HY_MAX_STAR_FILTERS));
+    if (dimensions[d].n_filters && !dimensions[d].filters) return fail(HY_ERR_INVALID, "%s: dimension %u: filters missing", who, d);
+  }
+  if (where && n_groupby == 0 && n_aggregates == 0) return fail(HY_ERR_INVALID, "%s: nothing to aggregate", who);
   auto table_ok = [&](const hy_star_column& c) { return c.column != nullptr && c.table <= n_dimensions; };
-  for (uint32_t g = 0; g < n_groupby; ++g) if (!table_ok(groupby[g])) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: GROUP BY column %u names no table of the join", g);
+  for (uint32_t g = 0; g < n_groupby; ++g) if (!table_ok(groupby[g])) return fail(HY_ERR_INVALID, "%s: GROUP BY column %u names no table of the join", who, g);
   for (uint32_t a = 0; a < n_aggregates; ++a) {
     const hy_star_aggregate& spec = aggregates[a];
-    if (spec.left.column && !table_ok(spec.left)) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: aggregate %u names no table of the join", a);
-    if (spec.op != HY_STAR_NO_OP && (!spec.left.column || !table_ok(spec.right))) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: aggregate %u: an expression needs two columns", a);
+    if (spec.left.column && !table_ok(spec.left)) return fail(HY_ERR_INVALID, "%s: aggregate %u names no table of the join", who, a);
+    if (spec.op != HY_STAR_NO_OP && (!spec.left.column || !table_ok(spec.right))) return fail(HY_ERR_INVALID, "%s: aggregate %u: an expression needs two columns", who, a);
   }
   for (uint32_t d = 0; d < n_dimensions; ++d) {
-    if (!dimensions[d].key || !dimensions[d].fact_key) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: dimension %u: key columns missing", d);
-    HY_TRY(on_this_device(dimensions[d].key, "hy_star_join_aggregate"));
-    HY_TRY(on_this_device(dimensions[d].fact_key, "hy_star_join_aggregate"));
-    if (dimensions[d].filter_column) HY_TRY(on_this_device(dimensions[d].filter_column, "hy_star_join_aggregate"));
+    if (!dimensions[d].key || !dimensions[d].fact_key) return fail(HY_ERR_INVALID, "%s: dimension %u: key columns missing", who, d);
+    HY_TRY(on_this_device(dimensions[d].key, who));
+    HY_TRY(on_this_device(dimensions[d].fact_key, who));
   }
   // RowIDs found in one column of a table index the others: the columns named for a table must agree in their chunks (the fact table: with
   // its first foreign key; dimension d: with its key) -- a mismatch would be read out of bounds by the kernels that dereference them
@@ -290,14 +319,28 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
     return true;
   };
   auto table_column = [&](uint32_t table) { return table == 0 ? dimensions[0].fact_key : dimensions[table - 1].key; };
+  // a filter: a data column of the table it filters; a string column's list carries value ids
+  auto check_filter = [&](const hy_star_filter& filter, uint32_t table, uint32_t index) -> hy_status {
+    if (!filter.column) return fail(HY_ERR_INVALID, "%s: filter %u of table %u: column missing", who, index, table);
+    HY_TRY(on_this_device(filter.column, who));
+    if (!same_table(filter.column, table_column(table))) {
+      return table ? fail(HY_ERR_INVALID, "%s: dimension %u: filter and key column are not columns of one table", who, table - 1)
+                   : fail(HY_ERR_INVALID, "%s: filter %u of the fact table is not a column of the table the foreign keys name", who, index);
+    }
+    if (filter.in_list && filter.column->data_type == HY_TYPE_STRING && !filter.in_list->per_chunk_value_ids) {
+      return fail(HY_ERR_INVALID, "%s: filter %u of table %u: a string column's list is given as per-chunk value ids, not as hy_value elements", who, index, table);
+    }
+    return HY_OK;
+  };
   for (uint32_t d = 0; d < n_dimensions; ++d) {
-    if (!same_table(dimensions[d].fact_key, dimensions[0].fact_key)) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: dimension %u: its foreign key is not a column of the fact table the others name", d);
-    if (dimensions[d].filter_column && !same_table(dimensions[d].filter_column, dimensions[d].key)) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: dimension %u: filter and key column are not columns of one table", d);
+    if (!same_table(dimensions[d].fact_key, dimensions[0].fact_key)) return fail(HY_ERR_INVALID, "%s: dimension %u: its foreign key is not a column of the fact table the others name", who, d);
+    for (uint32_t k = 0; k < dimensions[d].n_filters; ++k) HY_TRY(check_filter(dimensions[d].filters[k], d + 1, k));
   }
+  for (uint32_t k = 0; k < n_fact_filters; ++k) HY_TRY(check_filter(fact_filters[k], 0, k));
   auto check_column = [&](const hy_star_column& c, const char* what, uint32_t index) -> hy_status {
     if (!c.column) return HY_OK;
-    HY_TRY(on_this_device(c.column, "hy_star_join_aggregate"));
-    if (!same_table(c.column, table_column(c.table))) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: %s %u is not a column of table %u", what, index, c.table);
+    HY_TRY(on_this_device(c.column, who));
+    if (!same_table(c.column, table_column(c.table))) return fail(HY_ERR_INVALID, "%s: %s %u is not a column of table %u", who, what, index, c.table);
     return HY_OK;
   };
   for (uint32_t g = 0; g < n_groupby; ++g) HY_TRY(check_column(groupby[g], "GROUP BY column", g));
@@ -325,43 +368,67 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
   {
     std::vector<std::unique_ptr<DeviceBuffer>> dimension_rows(n_dimensions), counts(n_dimensions);
     std::vector<StarProbeDimension> probes(n_dimensions);
+    std::vector<std::unique_ptr<DeviceBuffer>> job_storage;   // the filters' jobs and what prepare_jobs stages of their predicates / lists
+    // A filter as the per-chunk jobs the star kernels test row by row, where its column is a plain data column; false: a scan it is (which says why)
+    auto jobs_in_place = [&](const hy_star_filter& filter, const ScanJob** jobs) -> hy_status {
+      *jobs = nullptr;
+      const hy_column* column = filter.column;
+      if (column->is_reference || column->is_mvcc || column->has_compressed) return HY_OK;
+      const size_t jobs_bytes = (sizeof(ScanJob) * (size_t{column->n_chunks} + 1) + 255) & ~size_t{255};
+      job_storage.push_back(std::make_unique<DeviceBuffer>());
+      DeviceBuffer& storage = *job_storage.back();
+      HY_TRY(storage.alloc(jobs_bytes + (filter.in_list ? scan_jobs_staging_bytes(column, filter.in_list) : scan_jobs_staging_bytes(column, &filter.predicate)) + 512));
+      char* staging = storage.as<char>() + jobs_bytes;
+      const hy_status prepared = filter.in_list ? prepare_scan_jobs(column, filter.in_list, storage.as<ScanJob>(), staging) : prepare_scan_jobs(column, &filter.predicate, storage.as<ScanJob>(), staging);
+      if (prepared == HY_OK) *jobs = storage.as<ScanJob>();
+      return HY_OK;
+    };
     bool shape_ok = true;
     for (uint32_t d = 0; d < n_dimensions && shape_ok; ++d) {
-      const hy_star_dimension& dimension = dimensions[d];
+      const hy_star_dimension_where& dimension = dimensions[d];
       if (dimension.key->is_reference || dimension.key->data_type != HY_TYPE_INT || dimension.fact_key->data_type != HY_TYPE_INT) { shape_ok = false; break; }
       dimension_rows[d] = std::make_unique<DeviceBuffer>();
       uint64_t n_dimension_rows = dimension.key->rows;
       const uint64_t* count_in_memory = nullptr;
       const hy_row_id* rows = nullptr;
-      const ScanJob* filter_jobs = nullptr;
-      // The kernels that build a dimension's tables walk the table itself and test its filter row by row (join_star.hpp: no TableScan, no
-      // PosList for a table of a few thousand to a million rows) where its columns are plain data columns; otherwise: the rows a scan leaves.
-      const bool in_place = !dimension.key->has_compressed && !dimension.key->is_mvcc &&
-                            (!dimension.filter_column || (!dimension.filter_column->is_reference && !dimension.filter_column->is_mvcc && !dimension.filter_column->has_compressed));
-      bool tested_in_place = in_place && !dimension.filter_column;
-      if (in_place && dimension.filter_column) {
-        const uint32_t n_chunks = dimension.filter_column->n_chunks;
-        const size_t jobs_bytes = (sizeof(ScanJob) * (size_t{n_chunks} + 1) + 255) & ~size_t{255};
-        counts[d] = std::make_unique<DeviceBuffer>();   // (the jobs and what prepare_jobs stages of the predicate)
-        HY_TRY(counts[d]->alloc(jobs_bytes + scan_jobs_staging_bytes(dimension.filter_column, &dimension.predicate) + 512));
-        ScanJob* jobs = counts[d]->as<ScanJob>();
-        if (prepare_scan_jobs(dimension.filter_column, &dimension.predicate, jobs, counts[d]->as<char>() + jobs_bytes) == HY_OK) {
-          filter_jobs = jobs;
-          tested_in_place = true;
-        }   // (a predicate the scan refuses: hy_table_scan below says why)
+      StarProbeDimension& probe = probes[d];
+      std::memset(&probe, 0, sizeof(probe));
+      // The kernels that build a dimension's tables walk the table itself and test its filters row by row (join_star.hpp: no TableScan, no
+      // PosList for a table of a few thousand to a million rows) where its columns are plain data columns; otherwise: the rows its scans leave.
+      bool tested_in_place = !dimension.key->has_compressed && !dimension.key->is_mvcc;
+      for (uint32_t k = 0; k < dimension.n_filters && tested_in_place; ++k) {
+        const ScanJob* jobs = nullptr;
+        HY_TRY(jobs_in_place(dimension.filters[k], &jobs));
+        if (jobs) probe.filters[probe.n_filters++] = StarProbeFilter{dimension.filters[k].column, jobs, dimension.filters[k].in_list != nullptr};
+        else tested_in_place = false;   // (a reference / compressed column, or a predicate the scan refuses: the scan below says why)
       }
       if (!tested_in_place) {
-        if (dimension.filter_column) {
+        probe.n_filters = 0;
+        if (dimension.n_filters == 1 && !dimension.filters[0].in_list) {   // (one scan: its count stays in device memory)
           counts[d] = std::make_unique<DeviceBuffer>();
-          HY_TRY(filtered_rows(dimension.filter_column, &dimension.predicate, *dimension_rows[d], &n_dimension_rows, counts[d].get()));
-          count_in_memory = counts[d]->as<uint64_t>() + dimension.filter_column->n_chunks;
-        } else HY_TRY(star_all_rows_of(dimension.key, *dimension_rows[d]));
+          HY_TRY(filtered_rows(dimension.filters[0].column, &dimension.filters[0].predicate, nullptr, *dimension_rows[d], &n_dimension_rows, counts[d].get()));
+          count_in_memory = counts[d]->as<uint64_t>() + dimension.filters[0].column->n_chunks;
+        } else if (dimension.n_filters) HY_TRY(filter_chain_rows(dimension.filters, dimension.n_filters, dimension_rows[d], &n_dimension_rows));
+        else HY_TRY(star_all_rows_of(dimension.key, *dimension_rows[d]));
         rows = dimension_rows[d]->as<hy_row_id>();
       }
       bool wanted = false;
       for (uint32_t g = 0; g < n_groupby; ++g) wanted = wanted || groupby[g].table == d + 1;
       for (uint32_t a = 0; a < n_aggregates; ++a) wanted = wanted || (aggregates[a].left.column && aggregates[a].left.table == d + 1) || (aggregates[a].op != HY_STAR_NO_OP && aggregates[a].right.table == d + 1);
-      probes[d] = StarProbeDimension{dimension.key, rows, filter_jobs ? dimension.filter_column : nullptr, filter_jobs, n_dimension_rows, count_in_memory, dimension.fact_key, wanted};
+      probe.key = dimension.key;
+      probe.rows = rows;
+      probe.n_rows = n_dimension_rows;
+      probe.d_n_rows = count_in_memory;
+      probe.fact_key = dimension.fact_key;
+      probe.want_rows = wanted;
+    }
+    // the fact table's own filters: inside the probe pass where their columns are plain data columns, else the chain below scans the table first
+    StarProbeFilter fact_tests[HY_MAX_STAR_FILTERS];
+    for (uint32_t k = 0; k < n_fact_filters && shape_ok; ++k) {
+      const ScanJob* jobs = nullptr;
+      HY_TRY(jobs_in_place(fact_filters[k], &jobs));
+      if (jobs) fact_tests[k] = StarProbeFilter{fact_filters[k].column, jobs, fact_filters[k].in_list != nullptr};
+      else shape_ok = false;
     }
     if (shape_ok) {
       auto fact_rows = std::make_unique<DeviceBuffer>();
@@ -370,7 +437,7 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
       StarFinishRequest finish;
       std::memset(&finish, 0, sizeof(finish));
       StarFinishGroups finished;
-      const bool ask = result->mem == HY_MEM_HOST && n_groupby >= 1 && n_groupby <= 4 && n_aggregates <= 8;
+      const bool ask = result->mem == HY_MEM_HOST && (n_groupby >= 1 || where) && n_groupby <= 4 && n_aggregates <= 8;   // (no GROUP BY column: the single-group finish)
       if (ask) {
         finish.n_groupby = n_groupby;
         finish.n_aggregates = n_aggregates;
@@ -382,7 +449,7 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
           finish.aggregates[g].right = StarFinishColumnSpec{aggregates[g].right.table, aggregates[g].op != HY_STAR_NO_OP ? aggregates[g].right.column : nullptr};
         }
       }
-      HY_TRY(star_probe_rows(probes.data(), n_dimensions, *fact_rows, rows_of_dimension, &n_rows, &fused, ask ? &finish : nullptr, ask ? &finished : nullptr));
+      HY_TRY(star_probe_rows(probes.data(), n_dimensions, *fact_rows, rows_of_dimension, &n_rows, &fused, ask ? &finish : nullptr, ask ? &finished : nullptr, fact_tests, n_fact_filters));
       t_last_star_was_fused = fused ? (finished.done ? 2 : 1) : 0;
       if (fused && finished.done) {
         if (joined_rows) *joined_rows = n_rows;
@@ -399,23 +466,31 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
       } else n_rows = 0;
     }
   }
+  // The chain: the fact table's filters first, as chained TableScans -- the rows they leave are what the first join probes
+  const bool fact_scanned = !fused && n_fact_filters != 0;
+  if (fact_scanned) {
+    HY_TRY(filter_chain_rows(fact_filters, n_fact_filters, carried[0], &n_rows));
+    carried_rows[0] = carried[0]->as<hy_row_id>();
+  }
   for (uint32_t d = 0; d < n_dimensions && !fused; ++d) {
-    const hy_star_dimension& dimension = dimensions[d];
-    // build side: the dimension's keys, of the rows that pass its filter
-    DeviceBuffer dimension_rows, build_keys;
+    const hy_star_dimension_where& dimension = dimensions[d];
+    const bool through_rows = d > 0 || fact_scanned;   // the probe side is a table of RowIDs (the join result so far), not the fact table itself
+    // build side: the dimension's keys, of the rows that pass its filters
+    std::unique_ptr<DeviceBuffer> dimension_rows;
+    DeviceBuffer build_keys;
     uint64_t n_dimension_rows = 0;
     ColumnHandle build;
     const hy_column* build_column = dimension.key;
-    if (dimension.filter_column) {
-      HY_TRY(filtered_rows(dimension.filter_column, &dimension.predicate, dimension_rows, &n_dimension_rows));
-      HY_TRY(materialise(dimension.key, dimension_rows.as<hy_row_id>(), n_dimension_rows, build_keys, build));
+    if (dimension.n_filters) {
+      HY_TRY(filter_chain_rows(dimension.filters, dimension.n_filters, dimension_rows, &n_dimension_rows));
+      HY_TRY(materialise(dimension.key, dimension_rows->as<hy_row_id>(), n_dimension_rows, build_keys, build));
       build_column = build.column;
     }
     // probe side: the fact table's foreign key, of the rows still in the join
     DeviceBuffer probe_keys;
     ColumnHandle probe;
     const hy_column* probe_column = dimension.fact_key;
-    if (d > 0) {
+    if (through_rows) {
       HY_TRY(materialise(dimension.fact_key, carried_rows[0], n_rows, probe_keys, probe));
       probe_column = probe.column;
     }
@@ -426,18 +501,18 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
     // what every surviving row is made of
     std::vector<std::unique_ptr<DeviceBuffer>> next(n_dimensions + 1);
     std::vector<const hy_row_id*> next_rows(n_dimensions + 1, nullptr);
-    if (d == 0) next_rows[0] = join.right;   // (positions in the fact table ARE its RowIDs: the probe column is the data column)
+    if (!through_rows) next_rows[0] = join.right;   // (positions in the fact table ARE its RowIDs: the probe column is the data column)
     for (uint32_t t = 0; t <= d; ++t) {
-      if (d == 0 || (t > 0 && !carried_rows[t])) continue;
+      if (!through_rows || !carried_rows[t]) continue;
       next[t] = std::make_unique<DeviceBuffer>();
       HY_TRY(next[t]->alloc(sizeof(hy_row_id) * std::max<uint64_t>(1, n_pairs)));
       HY_TRY(hy_gather_row_ids(carried_rows[t], n_rows, DENSE_CHUNK, join.right, n_pairs, next[t]->as<hy_row_id>()));
       next_rows[t] = next[t]->as<hy_row_id>();
     }
-    if (dimension.filter_column) {
+    if (dimension.n_filters) {
       next[d + 1] = std::make_unique<DeviceBuffer>();
       HY_TRY(next[d + 1]->alloc(sizeof(hy_row_id) * std::max<uint64_t>(1, n_pairs)));
-      HY_TRY(hy_gather_row_ids(dimension_rows.as<hy_row_id>(), n_dimension_rows, DENSE_CHUNK, join.left, n_pairs, next[d + 1]->as<hy_row_id>()));
+      HY_TRY(hy_gather_row_ids(dimension_rows->as<hy_row_id>(), n_dimension_rows, DENSE_CHUNK, join.left, n_pairs, next[d + 1]->as<hy_row_id>()));
       next_rows[d + 1] = next[d + 1]->as<hy_row_id>();
     } else next_rows[d + 1] = join.left;   // (an unfiltered dimension is joined as the data column itself)
     // The kernels that read this round's inputs are queued on this thread's stream; the buffers released here go back to its pool and are
@@ -496,7 +571,8 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
   uint64_t signature = 0x51A9E5B1ull * (n_groupby + 1) + n_dimensions;
   for (uint32_t g = 0; g < n_groupby; ++g) signature = (signature ^ reinterpret_cast<uintptr_t>(groupby[g].column)) * 0xD6E8FEB86659FD93ull;
   for (uint32_t d = 0; d < n_dimensions; ++d) {
-    const uint64_t literal = dimensions[d].filter_column ? static_cast<uint64_t>(dimensions[d].predicate.value.i64) ^ (uint64_t{dimensions[d].predicate.condition} << 56) : 0;   // (no filter: the predicate is not read)
+    const hy_star_filter* first_filter = dimensions[d].n_filters ? dimensions[d].filters : nullptr;
+    const uint64_t literal = first_filter ? static_cast<uint64_t>(first_filter->predicate.value.i64) ^ (uint64_t{first_filter->predicate.condition} << 56) : 0;   // (no filter: the predicate is not read)
     signature = (signature ^ reinterpret_cast<uintptr_t>(dimensions[d].key) ^ literal) * 0xD6E8FEB86659FD93ull;
   }
   signature |= 0x100;
@@ -511,8 +587,35 @@ hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n
   return status;
 }
 
-// debug / tests only: 1 = the calling thread's last hy_star_join_aggregate probed every dimension in one pass (csrc/join_star.hpp), 2 = and grouped
-// the survivors inside that pass (star_finish)
+extern "C" {
+
+hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n_dimensions, const hy_star_column* groupby, uint32_t n_groupby,
+                                 const hy_star_aggregate* aggregates, uint32_t n_aggregates, hy_aggregate_result* result, uint64_t* joined_rows) {
+  if (!dimensions || !n_dimensions || n_dimensions > HY_MAX_STAR_DIMENSIONS) return fail(HY_ERR_INVALID, "hy_star_join_aggregate: 1 .. %d dimensions", static_cast<int>(HY_MAX_STAR_DIMENSIONS));
+  // (one filter per dimension, none on the fact table: the same plan)
+  hy_star_filter filters[HY_MAX_STAR_DIMENSIONS];
+  hy_star_dimension_where with_filters[HY_MAX_STAR_DIMENSIONS];
+  for (uint32_t d = 0; d < n_dimensions; ++d) {
+    filters[d].column = dimensions[d].filter_column;
+    filters[d].predicate = dimensions[d].predicate;
+    filters[d].in_list = nullptr;
+    with_filters[d].key = dimensions[d].key;
+    with_filters[d].fact_key = dimensions[d].fact_key;
+    with_filters[d].filters = dimensions[d].filter_column ? &filters[d] : nullptr;
+    with_filters[d].n_filters = dimensions[d].filter_column ? 1 : 0;
+    with_filters[d].reserved = 0;
+  }
+  return star_join("hy_star_join_aggregate", false, with_filters, n_dimensions, nullptr, 0, groupby, n_groupby, aggregates, n_aggregates, result, joined_rows);
+}
+
+hy_status hy_star_join_aggregate_where(const hy_star_dimension_where* dimensions, uint32_t n_dimensions, const hy_star_filter* fact_filters, uint32_t n_fact_filters,
+                                       const hy_star_column* groupby, uint32_t n_groupby, const hy_star_aggregate* aggregates, uint32_t n_aggregates,
+                                       hy_aggregate_result* result, uint64_t* joined_rows) {
+  return star_join("hy_star_join_aggregate_where", true, dimensions, n_dimensions, fact_filters, n_fact_filters, groupby, n_groupby, aggregates, n_aggregates, result, joined_rows);
+}
+
+// debug / tests only: 1 = the calling thread's last hy_star_join_aggregate / hy_star_join_aggregate_where probed every dimension in one pass (csrc/join_star.hpp), 2 = and grouped
+// the survivors inside that pass (star_finish; without a GROUP BY column: its single-group reduction)
 int hy_debug_star_fused(void) { return t_last_star_was_fused; }
 
 }  // extern "C"

@@ -2161,6 +2161,120 @@ struct InListArgs {   // hy_table_scan_in_list, checked: `predicate` carries HY_
   uint32_t n_keys;              // before the padding
 };
 
+// hy_table_scan_in_list's checks of `list` against `column` (a data or reference column), and the list as sorted keys
+static hy_status check_in_list(const hy_column* column, const hy_in_list* list, InListArgs& args) {
+  if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
+  if (list->n_values == 0) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: an empty list has a constant result; the caller answers it");
+  if (list->n_values > HY_MAX_IN_LIST) return fail(HY_ERR_UNSUPPORTED, "hy_table_scan_in_list: %u elements, at most %u are evaluated here (longer lists are semi joins)", list->n_values, HY_MAX_IN_LIST);
+  if (list->value_type != column->data_type) return fail(HY_ERR_INVALID, "list type %u differs from column type %u: use hy_in_list_cast first", list->value_type, column->data_type);
+  if (list->negated > 1) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: negated is 0 or 1");
+  const hy_column* data_column = column->is_reference ? column->ref : column;
+  args.list = list;
+  args.keys.clear();
+  if (column->data_type == HY_TYPE_STRING) {
+    if (!list->per_chunk_value_ids) return fail(HY_ERR_INVALID, "string column IN list needs per-chunk value ids (hy_in_list.per_chunk_value_ids)");
+    for (uint32_t chunk = 0; data_column && chunk < data_column->n_chunks; ++chunk) {
+      if (data_column->host_segments[chunk].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "IN on unencoded string segments stays on the CPU path");
+    }
+    args.keys.assign(1, 0);   // (no segment takes a KIND_VALUE_LIST job)
+    args.n_keys = 1;
+    return HY_OK;
+  }
+  if (column->data_type < HY_TYPE_INT || column->data_type > HY_TYPE_DOUBLE) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: column type %u", column->data_type);
+  if (!list->values) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: values missing");
+  if (data_column && data_column->has_dictionary_without_values && !list->per_chunk_value_ids) return fail(HY_ERR_INVALID, "dictionaries that are not on the device need per-chunk value ids");
+  for (uint32_t i = 0; i < list->n_values; ++i) {
+    const hy_value& v = list->values[i];
+    switch (column->data_type) {
+      case HY_TYPE_INT: args.keys.push_back(list_key_u32(static_cast<uint32_t>(v.i32), false)); break;
+      case HY_TYPE_LONG: args.keys.push_back(list_key_u64(static_cast<uint64_t>(v.i64), false)); break;
+      case HY_TYPE_FLOAT: {
+        if (std::isnan(v.f32)) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: element %u is NaN (it equals no row: drop it)", i);
+        uint32_t bits;
+        std::memcpy(&bits, &v.f32, 4);
+        args.keys.push_back(list_key_u32(bits, true));
+        break;
+      }
+      default: {
+        if (std::isnan(v.f64)) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: element %u is NaN (it equals no row: drop it)", i);
+        uint64_t bits;
+        std::memcpy(&bits, &v.f64, 8);
+        args.keys.push_back(list_key_u64(bits, true));
+        break;
+      }
+    }
+  }
+  std::sort(args.keys.begin(), args.keys.end());
+  args.keys.erase(std::unique(args.keys.begin(), args.keys.end()), args.keys.end());
+  args.n_keys = static_cast<uint32_t>(args.keys.size());
+  size_t padded = 1;
+  while (padded < args.keys.size()) padded *= 2;
+  args.keys.resize(padded, args.keys.back());
+  return HY_OK;
+}
+
+// words of the value-id bitmaps of a data column's dictionary chunks, chunk after chunk
+static std::vector<uint64_t> value_id_set_offsets(const hy_column* data_column) {
+  const uint32_t n = data_column ? data_column->n_chunks : 0;
+  std::vector<uint64_t> offsets(size_t{n} + 1, 0);
+  for (uint32_t c = 0; c < n; ++c) {
+    const hy_segment& s = data_column->host_segments[c];
+    offsets[c + 1] = offsets[c] + (s.encoding == HY_ENC_DICTIONARY ? (uint64_t{s.aux_size} + 63) / 64 : 0);
+  }
+  return offsets;
+}
+
+// (what run_scan does for a list, for callers that evaluate the jobs themselves: the keys, the value-id bitmaps and the jobs live in `staging`)
+size_t scan_jobs_staging_bytes(const hy_column* column, const hy_in_list* list) {
+  const uint64_t set_words = value_id_set_offsets(column).back();
+  return 4 * 256 + 8 * 2 * size_t{HY_MAX_IN_LIST} + sizeof(hy_value) * size_t{list->n_values} + 4 * size_t{column->n_chunks} * list->n_values + 8 * (size_t{column->n_chunks} + 1) +
+         8 * (set_words + 1) + 4 * (size_t{column->n_chunks} + 1) + 8 * 256;
+}
+
+hy_status prepare_scan_jobs(const hy_column* column, const hy_in_list* list, ScanJob* jobs, void* staging) {
+  if (column->is_reference || column->is_mvcc) return fail(HY_ERR_INVALID, "prepare_scan_jobs: data columns only");
+  InListArgs args;
+  HY_TRY(check_in_list(column, list, args));
+  const uint32_t n_chunks = column->n_chunks, n_values = list->n_values;
+  const std::vector<uint64_t> set_offsets = value_id_set_offsets(column);
+  const uint64_t set_words = set_offsets[n_chunks];
+  hipStream_t stream = current_stream();
+  char* cursor = static_cast<char*>(staging) + 256;   // (the first block: prepare_jobs' status word)
+  auto take = [&](size_t bytes) { char* at = cursor; cursor += align_up(bytes ? bytes : 4, 256); return at; };
+  uint64_t* d_keys = reinterpret_cast<uint64_t*>(take(8 * args.keys.size()));
+  hy_value* d_values = reinterpret_cast<hy_value*>(take(sizeof(hy_value) * n_values));
+  uint32_t* d_value_ids = list->per_chunk_value_ids ? reinterpret_cast<uint32_t*>(take(4 * size_t{n_chunks} * n_values)) : nullptr;
+  uint64_t* d_set_offsets = reinterpret_cast<uint64_t*>(take(8 * (size_t{n_chunks} + 1)));
+  const size_t zeroed = align_up(8 * (set_words + 1), 256) + 4 * (size_t{n_chunks} + 1);
+  char* d_zeroed = take(zeroed);
+  uint64_t* d_set_words = reinterpret_cast<uint64_t*>(d_zeroed);
+  uint32_t* d_any = reinterpret_cast<uint32_t*>(d_zeroed + align_up(8 * (set_words + 1), 256));
+  HY_HIP(hipMemsetAsync(staging, 0, 256, stream));
+  HY_HIP(hipMemcpyAsync(d_keys, args.keys.data(), 8 * args.keys.size(), hipMemcpyHostToDevice, stream));
+  if (list->values) HY_HIP(hipMemcpyAsync(d_values, list->values, sizeof(hy_value) * n_values, hipMemcpyHostToDevice, stream));
+  if (d_value_ids && n_chunks) HY_HIP(hipMemcpyAsync(d_value_ids, list->per_chunk_value_ids, 4 * size_t{n_chunks} * n_values, hipMemcpyHostToDevice, stream));
+  HY_HIP(hipMemcpyAsync(d_set_offsets, set_offsets.data(), 8 * (size_t{n_chunks} + 1), hipMemcpyHostToDevice, stream));
+  HY_HIP(hipMemsetAsync(d_zeroed, 0, zeroed, stream));
+  if (set_words) {
+    const uint64_t lanes = uint64_t{n_chunks} * n_values;
+    hipLaunchKernelGGL(build_value_id_sets, dim3(static_cast<uint32_t>((lanes + 255) / 256)), dim3(256), 0, stream, column->d_segments, n_chunks, d_values, n_values, d_value_ids, d_set_words,
+                       d_set_offsets, d_any);
+  }
+  PredicateArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.condition = list->negated ? HY_PRED_NOT_IN : HY_PRED_IN;
+  pa.value_type = list->value_type;
+  pa.column_is_nullable = list->column_is_nullable;
+  pa.no_ranges = 1;
+  pa.match_words = d_set_words;
+  pa.match_word_offsets = d_set_offsets;
+  pa.list_keys = d_keys;
+  pa.list_any = d_any;
+  pa.list_size = args.n_keys;
+  if (n_chunks) hipLaunchKernelGGL(prepare_jobs, dim3(n_chunks), dim3(256), 0, stream, column->d_segments, n_chunks, pa, jobs, static_cast<uint32_t*>(staging));
+  return HY_OK;
+}
+
 // A scan's chunk regions (device memory) as the HY_MEM_HOST result the caller asked for: counts and chunk states copied, the regions packed back
 // to back (carved from the thread's scratch arena behind what the scan carved) and copied.  d_overflow: the scan's overflow word, or nullptr.
 hy_status regions_to_host_result(const hy_row_id* d_matches, const uint64_t* d_offsets, const uint32_t* d_counts, const uint8_t* d_state, uint32_t* d_overflow, uint32_t n_chunks,
@@ -2492,53 +2606,8 @@ hy_status hy_table_scan_in_list(const hy_column* column, const hy_in_list* list,
   for (uint32_t i = 0; i < n_excluded; ++i) {
     if (excluded_chunks[i] >= column->n_chunks) return fail(HY_ERR_INVALID, "excluded chunk id %u out of range", excluded_chunks[i]);
   }
-  if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
-  if (list->n_values == 0) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: an empty list has a constant result; the caller answers it");
-  if (list->n_values > HY_MAX_IN_LIST) return fail(HY_ERR_UNSUPPORTED, "hy_table_scan_in_list: %u elements, at most %u are evaluated here (longer lists are semi joins)", list->n_values, HY_MAX_IN_LIST);
-  if (list->value_type != column->data_type) return fail(HY_ERR_INVALID, "list type %u differs from column type %u: use hy_in_list_cast first", list->value_type, column->data_type);
-  if (list->negated > 1) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: negated is 0 or 1");
-  const hy_column* data_column = column->is_reference ? column->ref : column;
   InListArgs args;
-  args.list = list;
-  if (column->data_type == HY_TYPE_STRING) {
-    if (!list->per_chunk_value_ids) return fail(HY_ERR_INVALID, "string column IN list needs per-chunk value ids (hy_in_list.per_chunk_value_ids)");
-    for (uint32_t chunk = 0; data_column && chunk < data_column->n_chunks; ++chunk) {
-      if (data_column->host_segments[chunk].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "IN on unencoded string segments stays on the CPU path");
-    }
-    args.keys.assign(1, 0);   // (no segment takes a KIND_VALUE_LIST job)
-    args.n_keys = 1;
-  } else {
-    if (column->data_type < HY_TYPE_INT || column->data_type > HY_TYPE_DOUBLE) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: column type %u", column->data_type);
-    if (!list->values) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: values missing");
-    if (data_column && data_column->has_dictionary_without_values && !list->per_chunk_value_ids) return fail(HY_ERR_INVALID, "dictionaries that are not on the device need per-chunk value ids");
-    for (uint32_t i = 0; i < list->n_values; ++i) {
-      const hy_value& v = list->values[i];
-      switch (column->data_type) {
-        case HY_TYPE_INT: args.keys.push_back(list_key_u32(static_cast<uint32_t>(v.i32), false)); break;
-        case HY_TYPE_LONG: args.keys.push_back(list_key_u64(static_cast<uint64_t>(v.i64), false)); break;
-        case HY_TYPE_FLOAT: {
-          if (std::isnan(v.f32)) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: element %u is NaN (it equals no row: drop it)", i);
-          uint32_t bits;
-          std::memcpy(&bits, &v.f32, 4);
-          args.keys.push_back(list_key_u32(bits, true));
-          break;
-        }
-        default: {
-          if (std::isnan(v.f64)) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: element %u is NaN (it equals no row: drop it)", i);
-          uint64_t bits;
-          std::memcpy(&bits, &v.f64, 8);
-          args.keys.push_back(list_key_u64(bits, true));
-          break;
-        }
-      }
-    }
-    std::sort(args.keys.begin(), args.keys.end());
-    args.keys.erase(std::unique(args.keys.begin(), args.keys.end()), args.keys.end());
-    args.n_keys = static_cast<uint32_t>(args.keys.size());
-    size_t padded = 1;
-    while (padded < args.keys.size()) padded *= 2;
-    args.keys.resize(padded, args.keys.back());
-  }
+  HY_TRY(check_in_list(column, list, args));
   if (column->multi_chunk_reference && result->mem == HY_MEM_DEVICE && !result->counts) {
     return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
   }

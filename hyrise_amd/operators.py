@@ -513,6 +513,52 @@ def star_join_aggregate(dimensions, groupby, aggregates, group_capacity=4096, re
     return result, int(joined.value)
 
 
+def _star_filters(filters, keep):
+    """[(column, predicate or hy_in_list)] -> an hy_star_filter array (an abi.InList is an IN list, anything else a predicate)."""
+    array = (abi.StarFilter * max(1, len(filters)))()
+    for k, (column, test) in enumerate(filters):
+        array[k].column = column.handle
+        if isinstance(test, abi.InList):
+            array[k].in_list = C.pointer(test)
+        else:
+            array[k].predicate = test
+        keep.append(test)
+    keep.append(array)
+    return array
+
+
+def star_join_aggregate_where(dimensions, fact_filters, groupby, aggregates, group_capacity=4096, result=None):
+    """hy_star_join_aggregate_where: star_join_aggregate over filtered tables, as one call (csrc/plan.hip).
+    dimensions: [(key column, [(filter column, predicate or in_list_predicate(...)), ...], fact foreign-key column)] -- a dimension's filters are a
+    conjunction, an empty list leaves it unfiltered; fact_filters: [(column of the fact table, predicate or in_list_predicate(...)), ...];
+    groupby (may be empty: one result row) and aggregates as star_join_aggregate takes them.
+    -> (HostAggregateResult, rows left after the fact filters and every join)"""
+    lib = abi.load_library()
+    keep = []
+    dims = (abi.StarDimensionWhere * max(1, len(dimensions)))()
+    for d, (key, filters, fact_key) in enumerate(dimensions):
+        dims[d].key, dims[d].fact_key = key.handle, fact_key.handle
+        dims[d].n_filters = len(filters)
+        if filters:
+            dims[d].filters = _star_filters(filters, keep)
+    fact = _star_filters(fact_filters, keep)
+    groups = (abi.StarColumn * max(1, len(groupby)))()
+    for g, (table, column) in enumerate(groupby):
+        groups[g].table, groups[g].column = table, column.handle
+    specs = (abi.StarAggregate * max(1, len(aggregates)))()
+    for a, (function, left, op, right) in enumerate(aggregates):
+        specs[a].function, specs[a].op = function, abi.STAR_NO_OP if op is None else op
+        if left is not None:
+            specs[a].left.table, specs[a].left.column = left[0], left[1].handle
+        if right is not None:
+            specs[a].right.table, specs[a].right.column = right[0], right[1].handle
+    if result is None:
+        result = HostAggregateResult(len(aggregates), group_capacity)
+    joined = C.c_uint64(0)
+    abi.check(lib.hy_star_join_aggregate_where(dims, len(dimensions), fact, len(fact_filters), groups, len(groupby), specs, len(aggregates), C.byref(result.c), C.byref(joined)))
+    return result, int(joined.value)
+
+
 def expression(tree):
     """An arithmetic expression as hy_expression (postfix).  tree: a column (DeviceColumn), a literal (HY_TYPE_*, value), None (the
     NULL literal) or (abi.ARITH_*, left tree, right tree)."""

@@ -14,6 +14,10 @@ the dimensions, then one PK-FK JoinHash per dimension with the filtered dimensio
   Q4.1  sum(lo_revenue - lo_supplycost) group by d_year, c_nation
         where c_region = 'AMERICA' and s_region = 'AMERICA' and p_mfgr in ('MFGR#1', 'MFGR#2')
 
+All thirteen queries of the specification (SQL, STAR_QUERIES) run as ONE call each through hy_star_join_aggregate_where
+(star_plan(columns, query, where=True)): flight 1 filters lineorder itself and groups nothing, flights 3 and 4 put several predicates and
+IN lists on a dimension.
+
 Everything between the dimension scans and the final groups stays on the device: join outputs are PosLists in HBM, the next
 operator reads the base columns through them as ReferenceSegments (hy_column_create over device memory), and a join over
 such a reference table is dereferenced with hy_gather_row_ids exactly like write_output_chunks does for reference inputs
@@ -32,12 +36,42 @@ AMERICA = 1
 VIRTUAL_CHUNK = 65535   # operator results are presented to the next operator as tables of this chunk size
 DENSE_CHUNK = 65536     # ... and a materialised foreign-key column of the join result in chunks that start on 16-byte boundaries
 
+# The thirteen queries of the SSB specification (O'Neil et al., "Star Schema Benchmark", section 3: four flights), string literals as the integer
+# codes of SsbData: 'MFGR#12' = 12, 'MFGR#2221' = 2221, regions AFRICA .. MIDDLE EAST = 0 .. 4, nation = region * 5 + 0 .. 4 ('UNITED STATES' = 9,
+# 'UNITED KINGDOM' = 19), city = nation * 10 + 0 .. 9 ('UNITED KI1' = 191, 'UNITED KI5' = 195), d_yearmonth 'Dec1997' = d_yearmonthnum 199712.
 Q2_1_SQL = """select sum(lo_revenue), d_year, p_brand1 from lineorder, "date", part, supplier
  where lo_orderdate = d_datekey and lo_partkey = p_partkey and lo_suppkey = s_suppkey and p_category = 12 and s_region = 1
  group by d_year, p_brand1 order by d_year, p_brand1"""
 Q4_1_SQL = """select d_year, c_nation, sum(lo_revenue - lo_supplycost) as profit from "date", customer, supplier, part, lineorder
  where lo_custkey = c_custkey and lo_suppkey = s_suppkey and lo_partkey = p_partkey and lo_orderdate = d_datekey
    and c_region = 1 and s_region = 1 and (p_mfgr = 1 or p_mfgr = 2) group by d_year, c_nation order by d_year, c_nation"""
+
+
+_FLIGHT_1 = 'select sum(lo_extendedprice * lo_discount) as revenue from lineorder, "date" where lo_orderdate = d_datekey and '
+_FLIGHT_2 = """select sum(lo_revenue), d_year, p_brand1 from lineorder, "date", part, supplier
+ where lo_orderdate = d_datekey and lo_partkey = p_partkey and lo_suppkey = s_suppkey and %s group by d_year, p_brand1 order by d_year, p_brand1"""
+_FLIGHT_3 = """select %s, d_year, sum(lo_revenue) as revenue from customer, lineorder, supplier, "date"
+ where lo_custkey = c_custkey and lo_suppkey = s_suppkey and lo_orderdate = d_datekey and %s group by %s, d_year order by d_year asc, revenue desc"""
+_FLIGHT_4 = """select %s, sum(lo_revenue - lo_supplycost) as profit from "date", customer, supplier, part, lineorder
+ where lo_custkey = c_custkey and lo_suppkey = s_suppkey and lo_partkey = p_partkey and lo_orderdate = d_datekey and %s group by %s order by %s"""
+SQL = {
+    "1.1": _FLIGHT_1 + "d_year = 1993 and lo_discount between 1 and 3 and lo_quantity < 25",
+    "1.2": _FLIGHT_1 + "d_yearmonthnum = 199401 and lo_discount between 4 and 6 and lo_quantity between 26 and 35",
+    "1.3": _FLIGHT_1 + "d_weeknuminyear = 6 and d_year = 1994 and lo_discount between 5 and 7 and lo_quantity between 26 and 35",
+    "2.1": Q2_1_SQL,
+    "2.2": _FLIGHT_2 % "p_brand1 between 2221 and 2228 and s_region = 2",
+    "2.3": _FLIGHT_2 % "p_brand1 = 2221 and s_region = 3",
+    "3.1": _FLIGHT_3 % ("c_nation, s_nation", "c_region = 2 and s_region = 2 and d_year >= 1992 and d_year <= 1997", "c_nation, s_nation"),
+    "3.2": _FLIGHT_3 % ("c_city, s_city", "c_nation = 9 and s_nation = 9 and d_year >= 1992 and d_year <= 1997", "c_city, s_city"),
+    "3.3": _FLIGHT_3 % ("c_city, s_city", "(c_city = 191 or c_city = 195) and (s_city = 191 or s_city = 195) and d_year >= 1992 and d_year <= 1997", "c_city, s_city"),
+    "3.4": _FLIGHT_3 % ("c_city, s_city", "(c_city = 191 or c_city = 195) and (s_city = 191 or s_city = 195) and d_yearmonthnum = 199712", "c_city, s_city"),
+    "4.1": Q4_1_SQL,
+    "4.2": _FLIGHT_4 % ("d_year, s_nation, p_category", "c_region = 1 and s_region = 1 and (d_year = 1997 or d_year = 1998) and (p_mfgr = 1 or p_mfgr = 2)",
+                        "d_year, s_nation, p_category", "d_year, s_nation, p_category"),
+    "4.3": _FLIGHT_4 % ("d_year, s_city, p_brand1", "c_region = 1 and s_nation = 9 and (d_year = 1997 or d_year = 1998) and p_category = 14",
+                        "d_year, s_city, p_brand1", "d_year, s_city, p_brand1"),
+}
+QUERIES = tuple(SQL)
 
 
 def _date_keys():
@@ -48,9 +82,19 @@ def _date_keys():
     return (years * 10000 + months * 100 + dom).astype(np.int32), years.astype(np.int32)
 
 
+def _date_attributes():
+    """d_yearmonthnum (year * 100 + month) and d_weeknuminyear (1 .. 53: the week the day of the year falls in) of the same days."""
+    days = np.arange(np.datetime64("1992-01-01"), np.datetime64("1999-01-01"))
+    years = days.astype("datetime64[Y]").astype(int) + 1970
+    months = days.astype("datetime64[M]").astype(int) % 12 + 1
+    day_of_year = (days - days.astype("datetime64[Y]")).astype(int)
+    return (years * 100 + months).astype(np.int32), (day_of_year // 7 + 1).astype(np.int32)
+
+
 class SsbData:
     """Raw numpy columns.  Codes: p_mfgr 1..5, p_category = mfgr * 10 + 1..5 ('MFGR#12' = 12), p_brand1 = category * 100 + 1..40,
-    nation 0..24, region = nation // 5 (AMERICA = 1)."""
+    nation 0..24, region = nation // 5 (AMERICA = 1), city = nation * 10 + 0..9.  The columns Q2.1 / Q4.1 read (TABLES) come from the generator
+    seeded with `seed`; c_city / s_city from a second one, so that adding them left every earlier column as it was."""
 
     def __init__(self, scale_factor=1.0, seed=7, lineorder_rows=None):
         rng = np.random.default_rng(seed)
@@ -79,18 +123,29 @@ class SsbData:
         discount = rng.integers(0, 11, n_lineorder, dtype=np.int32)
         self.lo_revenue = (quantity * price * (100 - discount) // 100).astype(np.int32)
         self.lo_supplycost = (price * 6 // 10).astype(np.int32)
+        self.lo_quantity, self.lo_discount = quantity, discount
+        self.lo_extendedprice = (quantity * price).astype(np.int32)
         self.n_lineorder = n_lineorder
+        self.d_yearmonthnum, self.d_weeknuminyear = _date_attributes()
+        cities = np.random.default_rng([seed, 1])
+        self.c_city = (self.c_nation * 10 + cities.integers(0, 10, n_customer, dtype=np.int32)).astype(np.int32)
+        self.s_city = (self.s_nation * 10 + cities.integers(0, 10, n_supplier, dtype=np.int32)).astype(np.int32)
 
     TABLES = {"lineorder": ("lo_custkey", "lo_partkey", "lo_suppkey", "lo_orderdate", "lo_revenue", "lo_supplycost"),
               "date": ("d_datekey", "d_year"), "customer": ("c_custkey", "c_nation", "c_region"),
               "supplier": ("s_suppkey", "s_nation", "s_region"), "part": ("p_partkey", "p_mfgr", "p_category", "p_brand1")}
 
-    def host_columns(self, chunk_size=abi.CHUNK_DEFAULT_SIZE):
+    # ... and every column the thirteen queries read
+    ALL_TABLES = {"lineorder": TABLES["lineorder"] + ("lo_quantity", "lo_discount", "lo_extendedprice"),
+                  "date": TABLES["date"] + ("d_yearmonthnum", "d_weeknuminyear"), "customer": TABLES["customer"] + ("c_city",),
+                  "supplier": TABLES["supplier"] + ("s_city",), "part": TABLES["part"]}
+
+    def host_columns(self, chunk_size=abi.CHUNK_DEFAULT_SIZE, tables=None):
         """Encoded like Hyrise's automatic encoding: unique keys unencoded, other int columns FrameOfReference
-        (segment_encoding_utils.cpp:105-115)."""
+        (segment_encoding_utils.cpp:105-115).  tables: TABLES (the default: what Q2.1 / Q4.1 read) or ALL_TABLES."""
         unique = {"c_custkey", "s_suppkey", "p_partkey", "d_datekey"}
         out = {}
-        for table, names in self.TABLES.items():
+        for table, names in (self.TABLES if tables is None else tables).items():
             for name in names:
                 encoding = abi.ENC_UNENCODED if name in unique else abi.ENC_FRAME_OF_REFERENCE
                 out[name] = storage.make_column(getattr(self, name), None, encoding, chunk_size)
@@ -102,7 +157,7 @@ class SsbData:
         db = getattr(self, "_sqlite", None)
         if db is None:   # (loaded once per data set: at scale factor 1 the inserts take half a minute)
             db = sqlite3.connect(":memory:")
-            for table, names in self.TABLES.items():
+            for table, names in self.ALL_TABLES.items():
                 db.execute(f'create table "{table}" ({", ".join(n + " integer" for n in names)})')
                 rows = list(zip(*[getattr(self, n).tolist() for n in names]))
                 db.executemany(f'insert into "{table}" values ({", ".join("?" for _ in names)})', rows)
@@ -218,10 +273,68 @@ def run_query(ex, columns, query, fact_first_chunk=0, comm=None, repartitioned=(
     return [through("d_year", "date"), through("c_nation", "customer")], [(abi.AGG_SUM, profit)], joined
 
 
-def star_plan(columns, query):
+# The thirteen queries as star joins over filtered tables: {query: (dimensions, fact filters, GROUP BY columns, aggregate)} with
+#   dimensions   [(key, foreign key, [(column, condition, literal(s))])] in join order -- a dimension's filters are a conjunction; abi.PRED_IN's
+#                literal is the list
+#   aggregate    (left column, HY_ARITH_* or None, right column or None) under SUM
+_EQ, _LT, _BETWEEN, _IN = abi.PRED_EQUALS, abi.PRED_LESS_THAN, abi.PRED_BETWEEN_INCLUSIVE, abi.PRED_IN
+_DATE, _PART, _SUPPLIER, _CUSTOMER = ("d_datekey", "lo_orderdate"), ("p_partkey", "lo_partkey"), ("s_suppkey", "lo_suppkey"), ("c_custkey", "lo_custkey")
+_REVENUE_1, _REVENUE, _PROFIT = ("lo_extendedprice", abi.ARITH_MUL, "lo_discount"), ("lo_revenue", None, None), ("lo_revenue", abi.ARITH_SUB, "lo_supplycost")
+_UK_CITIES = (191, 195)
+STAR_QUERIES = {
+    "1.1": ([_DATE + ([("d_year", _EQ, 1993)],)], [("lo_discount", _BETWEEN, (1, 3)), ("lo_quantity", _LT, 25)], [], _REVENUE_1),
+    "1.2": ([_DATE + ([("d_yearmonthnum", _EQ, 199401)],)], [("lo_discount", _BETWEEN, (4, 6)), ("lo_quantity", _BETWEEN, (26, 35))], [], _REVENUE_1),
+    "1.3": ([_DATE + ([("d_weeknuminyear", _EQ, 6), ("d_year", _EQ, 1994)],)], [("lo_discount", _BETWEEN, (5, 7)), ("lo_quantity", _BETWEEN, (26, 35))], [], _REVENUE_1),
+    "2.1": ([_PART + ([("p_category", _EQ, 12)],), _SUPPLIER + ([("s_region", _EQ, AMERICA)],), _DATE + ([],)], [], ["d_year", "p_brand1"], _REVENUE),
+    "2.2": ([_PART + ([("p_brand1", _BETWEEN, (2221, 2228))],), _SUPPLIER + ([("s_region", _EQ, 2)],), _DATE + ([],)], [], ["d_year", "p_brand1"], _REVENUE),
+    "2.3": ([_PART + ([("p_brand1", _EQ, 2221)],), _SUPPLIER + ([("s_region", _EQ, 3)],), _DATE + ([],)], [], ["d_year", "p_brand1"], _REVENUE),
+    "3.1": ([_CUSTOMER + ([("c_region", _EQ, 2)],), _SUPPLIER + ([("s_region", _EQ, 2)],), _DATE + ([("d_year", _BETWEEN, (1992, 1997))],)], [],
+            ["c_nation", "s_nation", "d_year"], _REVENUE),
+    "3.2": ([_CUSTOMER + ([("c_nation", _EQ, 9)],), _SUPPLIER + ([("s_nation", _EQ, 9)],), _DATE + ([("d_year", _BETWEEN, (1992, 1997))],)], [],
+            ["c_city", "s_city", "d_year"], _REVENUE),
+    "3.3": ([_CUSTOMER + ([("c_city", _IN, _UK_CITIES)],), _SUPPLIER + ([("s_city", _IN, _UK_CITIES)],), _DATE + ([("d_year", _BETWEEN, (1992, 1997))],)], [],
+            ["c_city", "s_city", "d_year"], _REVENUE),
+    "3.4": ([_CUSTOMER + ([("c_city", _IN, _UK_CITIES)],), _SUPPLIER + ([("s_city", _IN, _UK_CITIES)],), _DATE + ([("d_yearmonthnum", _EQ, 199712)],)], [],
+            ["c_city", "s_city", "d_year"], _REVENUE),
+    "4.1": ([_SUPPLIER + ([("s_region", _EQ, AMERICA)],), _CUSTOMER + ([("c_region", _EQ, AMERICA)],), _PART + ([("p_mfgr", _IN, (1, 2))],), _DATE + ([],)], [],
+            ["d_year", "c_nation"], _PROFIT),
+    "4.2": ([_SUPPLIER + ([("s_region", _EQ, AMERICA)],), _CUSTOMER + ([("c_region", _EQ, AMERICA)],), _PART + ([("p_mfgr", _IN, (1, 2))],),
+             _DATE + ([("d_year", _IN, (1997, 1998))],)], [], ["d_year", "s_nation", "p_category"], _PROFIT),
+    "4.3": ([_SUPPLIER + ([("s_nation", _EQ, 9)],), _CUSTOMER + ([("c_region", _EQ, AMERICA)],), _PART + ([("p_category", _EQ, 14)],),
+             _DATE + ([("d_year", _BETWEEN, (1997, 1998))],)], [], ["d_year", "s_city", "p_brand1"], _PROFIT),
+}
+
+
+def _star_test(condition, literal):
+    """A filter's literal(s) as what hy_star_filter carries: a predicate, or an IN list."""
+    from .operators import in_list_predicate, make_predicate
+    if condition == abi.PRED_IN:
+        return in_list_predicate(abi.TYPE_INT, list(literal))
+    if condition == abi.PRED_BETWEEN_INCLUSIVE:
+        return make_predicate(condition, abi.TYPE_INT, literal[0], literal[1])
+    return make_predicate(condition, abi.TYPE_INT, literal)
+
+
+def _table_of(name):
+    return {"lo": "lineorder", "d": "date", "p": "part", "s": "supplier", "c": "customer"}[name.split("_")[0]]
+
+
+def star_plan(columns, query, where=False):
     """The same two queries as arguments of hy_star_join_aggregate (operators.star_join_aggregate): the plan of run_query + the aggregate
-    made by ONE call of the library (csrc/plan.hip) -- single GPU, every dimension against its full replica."""
+    made by ONE call of the library (csrc/plan.hip) -- single GPU, every dimension against its full replica.
+    where=True: any of the thirteen queries (STAR_QUERIES) as arguments of hy_star_join_aggregate_where (operators.star_join_aggregate_where)
+    -> (dimensions, fact filters, groupby, aggregates); the GROUP BY values come back as MIN() aggregates behind the SUM, as below."""
     from .operators import make_predicate
+    if where:
+        dimension_specs, fact_specs, groupby_names, (left, op, right) = STAR_QUERIES[query]
+        dimensions = [(columns[key], [(columns[name], _star_test(condition, literal)) for name, condition, literal in filters], columns[fact_key])
+                      for key, fact_key, filters in dimension_specs]
+        fact_filters = [(columns[name], _star_test(condition, literal)) for name, condition, literal in fact_specs]
+        table_index = {"lineorder": 0}
+        table_index.update({_table_of(key): d + 1 for d, (key, _, _) in enumerate(dimension_specs)})
+        groupby = [(table_index[_table_of(name)], columns[name]) for name in groupby_names]
+        aggregates = [(abi.AGG_SUM, (0, columns[left]), op, (0, columns[right]) if right is not None else None)] + [(abi.AGG_MIN, g, None, None) for g in groupby]
+        return dimensions, fact_filters, groupby, aggregates
     if query == "2.1":
         dimensions = [(columns["p_partkey"], columns["p_category"], make_predicate(abi.PRED_EQUALS, abi.TYPE_INT, 12), columns["lo_partkey"]),
                       (columns["s_suppkey"], columns["s_region"], make_predicate(abi.PRED_EQUALS, abi.TYPE_INT, AMERICA), columns["lo_suppkey"]),

@@ -974,6 +974,43 @@ typedef struct hy_star_aggregate {
 hy_status hy_star_join_aggregate(const hy_star_dimension* dimensions, uint32_t n_dimensions, const hy_star_column* groupby, uint32_t n_groupby,
                                  const hy_star_aggregate* aggregates, uint32_t n_aggregates, hy_aggregate_result* result, uint64_t* joined_rows);
 
+/* The same star join over FILTERED tables: a conjunction of up to HY_MAX_STAR_FILTERS tests per dimension, a conjunction of tests on the
+ * fact table itself, and an aggregate that may have no GROUP BY column -- the thirteen SSB queries as one call each (Q1.x filter lineorder
+ * and group nothing; Q3.x / Q4.x put two predicates or an IN list on a dimension).  The operator tree it stands for: the fact filters as
+ * chained TableScans on the fact table, run first (a NULL cell drops the row); per dimension a chain of TableScans, its filters in the order
+ * given; then the JoinHashes, the Projection and the AggregateHash of hy_star_join_aggregate.  A filter is what hy_table_scan takes
+ * (`predicate`, read where in_list is NULL) or what hy_table_scan_in_list takes (`in_list`: column [NOT] IN (...), at most HY_MAX_IN_LIST
+ * elements; a string column's list carries per-chunk value ids); its column is a DATA column of the table it filters.
+ * Where hy_star_join_aggregate's fused probe applies and every fact filter column is a plain data column (Unencoded / FrameOfReference /
+ * Dictionary segments with 1-, 2- or 4-byte vectors), the fact filters are tested inside the one pass over the fact table, before the
+ * dimensions are asked, and a dimension's filters are tested where its direct table is built; other shapes (RunLength or bit-packed filter
+ * columns, non-int32 keys, NULL foreign keys) run the chain with hy_table_scan / hy_table_scan_in_list, hy_poslist_translate and the
+ * join-by-join path -- the same groups and cells.  *joined_rows: the rows left after the fact filters and every join.  Group order: the fact
+ * table's row order on the fused probe, the last join's order otherwise (as hy_star_join_aggregate).
+ * n_groupby == 0: the result is hy_aggregate_hash's for the same rows without a GROUP BY column -- ONE row; over no rows COUNT is 0 and
+ * every other aggregate NULL.  On the fused probe with HY_OPT_STAR_FUSED_FINISH that row is reduced inside the join: per workgroup in
+ * registers and LDS, one addition per workgroup to the single accumulator row, no hash table.
+ * HY_ERR_INVALID: null arguments, n_dimensions outside 1 .. HY_MAX_STAR_DIMENSIONS, a filter column that is not a column of its table, a
+ * string column's list given as hy_value elements.  HY_ERR_UNSUPPORTED: more than HY_MAX_STAR_FILTERS filters on a table, and whatever the
+ * scan of a filter refuses.  Nothing is written on error. */
+enum { HY_MAX_STAR_FILTERS = 4 };
+typedef struct hy_star_filter {
+  const hy_column* column;         /* a DATA column of the table it filters                                                      */
+  hy_predicate predicate;          /* as hy_table_scan takes it; read when in_list is NULL                                       */
+  const hy_in_list* in_list;       /* or: column [NOT] IN (...), as hy_table_scan_in_list takes it                               */
+} hy_star_filter;
+typedef struct hy_star_dimension_where {
+  const hy_column* key;            /* the dimension's key column: the build side of its join                                     */
+  const hy_column* fact_key;       /* the fact table's foreign key to this dimension                                             */
+  const hy_star_filter* filters;   /* a conjunction; n_filters == 0: the dimension is not filtered                               */
+  uint32_t n_filters, reserved;
+} hy_star_dimension_where;
+hy_status hy_star_join_aggregate_where(const hy_star_dimension_where* dimensions, uint32_t n_dimensions,
+                                       const hy_star_filter* fact_filters, uint32_t n_fact_filters,
+                                       const hy_star_column* groupby, uint32_t n_groupby,
+                                       const hy_star_aggregate* aggregates, uint32_t n_aggregates,
+                                       hy_aggregate_result* result, uint64_t* joined_rows);
+
 /* ---- multi-GPU exchange (the reference is one process: these have no counterpart there) ----------------
  * Sharding an operator over GPUs adds one exchange step per operator (hyrise_amd/distributed.py: one process per GPU, RCCL):
  * the broadcast-build JoinHash all-gathers the build side's join column, the repartitioned JoinHash sends every (key, RowID)
