@@ -102,6 +102,12 @@ class NestedLoopResult(C.Structure):
     _fields_ = [("mem", C.c_uint32), ("reserved", C.c_uint32), ("left_pos", C.c_void_p), ("right_pos", C.c_void_p), ("capacity", C.c_uint64), ("n_pairs", C.c_uint64)]
 
 
+class ProductResult(C.Structure):
+    """hy_product_result: the two PosLists of a cross join in the reference's order; either list pointer may be None (side not wanted)."""
+    _fields_ = [("mem", C.c_uint32), ("reserved", C.c_uint32), ("left_pos", C.c_void_p), ("right_pos", C.c_void_p), ("pair_offsets", C.c_void_p),
+                ("capacity", C.c_uint64), ("n_rows", C.c_uint64)]
+
+
 class JoinPredicate(C.Structure):
     """hy_join_predicate: left_column <condition> right_column, evaluated on the pairs the primary equality finds."""
     _fields_ = [("left_column", C.c_void_p), ("right_column", C.c_void_p), ("condition", C.c_uint32), ("reserved", C.c_uint32)]
@@ -113,7 +119,7 @@ NLJ_MAX_TEMPORARY_BYTES = 1 << 31      # HY_NLJ_MAX_TEMPORARY_BYTES
 # hy_set_option (include/hyrise_amd.h HY_OPT_*): equivalent paths / launch shapes; every setting gives the same results
 (OPT_ALLOW_ANY_ARCH, OPT_JOIN_RANK_TABLE, OPT_JOIN_HINT, OPT_JOIN_BREAK_HINT, OPT_JOIN_PKFK, OPT_JOIN_LDS_BUILD, OPT_JOIN_LDS_BUILD_TILES, OPT_JOIN_FILL_WGS_PER_CU,
  OPT_JOIN_HAND_OVER_RANKS, OPT_AGG_PARTITION_BITS, OPT_AGG_SPILL_SHIFT, OPT_AGG_SMALL_DOMAIN, OPT_FUSED_SMALL_DOMAIN, OPT_SCAN_TWO_COLUMNS, OPT_STAR_FUSED_PROBE, OPT_STAR_FUSED_FINISH,
- OPT_LDS_ORDERED_ATOMICS) = range(17)
+ OPT_LDS_ORDERED_ATOMICS, OPT_PRODUCT_NONTEMPORAL) = range(18)
 KERNEL_OTHER, KERNEL_SCAN, KERNEL_JOIN_PROBE, KERNEL_JOIN_COUNT, KERNEL_JOIN_BUILD, KERNEL_AGGREGATE, KERNEL_PROJECTION = range(7)   # hy_profile_read_kernel
 ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV, ARITH_MOD = range(5)
 
@@ -280,6 +286,8 @@ SYMBOLS = [
     ("hy_join_sort_merge_count", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("hy_join_nested_loop", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(JoinPredicate), C.c_uint32, C.POINTER(NestedLoopResult)]),
     ("hy_join_nested_loop_count", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(JoinPredicate), C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("hy_product", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(ProductResult)]),
+    ("hy_product_count", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("hy_aggregate_hash", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32,
                                       C.POINTER(AggregateResult)]),
     ("hy_aggregate_hash_columns", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(AggregateSpec), C.c_uint32, C.c_uint32,

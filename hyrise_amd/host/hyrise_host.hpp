@@ -2084,6 +2084,155 @@ class JoinNestedLoop : public AbstractReadOnlyOperator {
   std::vector<OperatorJoinPredicate> _secondary_predicates;
 };
 
+// Product (operators/product.hpp, product.cpp:32-137): what the translator emits for every cross join (lqp_translator.cpp:362).  The output has
+// the left input's columns, then the right one's, and one chunk per pair of input chunks (cl, cr), cl outermost, empty pairs included; every
+// segment references the table and column the input's segment references (a data input: the input itself), and the columns of a side that
+// sat behind one input PosList share one output PosList.  hy_product writes the lists: one pooled block of HBM per side and input PosList,
+// every chunk's PosList a view (block, pair_offsets[pair], rows) -- or, with device_resident_results(false), RowIDPosLists of the same
+// contents.  DevicePosList inputs are read where they lie.  What the library refuses (and columns it cannot describe) takes the host loop.
+class Product : public AbstractReadOnlyOperator {
+ public:
+  Product(std::shared_ptr<const AbstractOperator> left, std::shared_ptr<const AbstractOperator> right) : AbstractReadOnlyOperator(std::move(left), std::move(right)) {}
+  const std::string& name() const override { static const std::string n = "Product"; return n; }
+
+ protected:
+  // One input: its columns grouped by the PosLists they sit behind (a data input: one group), and per group the output's PosLists.
+  struct Side {
+    std::shared_ptr<const Table> table;
+    std::vector<size_t> group_of_column;
+    std::vector<std::vector<ColumnID>> columns_of_group;
+    std::vector<std::vector<std::shared_ptr<const AbstractPosList>>> lists;   // [group][pair]
+
+    explicit Side(std::shared_ptr<const Table> input) : table(std::move(input)) {
+      std::map<std::vector<const AbstractPosList*>, size_t> groups;
+      for (ColumnID c = 0; c < table->column_count(); ++c) {
+        std::vector<const AbstractPosList*> key;
+        if (table->type() == TableType::References)
+          for (ChunkID k = 0; k < table->chunk_count(); ++k) key.push_back(std::static_pointer_cast<ReferenceSegment>(table->get_chunk(k)->get_segment(c))->pos_list().get());
+        const auto [it, inserted] = groups.emplace(std::move(key), columns_of_group.size());
+        group_of_column.push_back(it->second);
+        if (inserted) columns_of_group.emplace_back();
+        columns_of_group[it->second].push_back(c);
+      }
+      lists.resize(columns_of_group.size());
+    }
+    const AbstractPosList* input_list(size_t group, ChunkID chunk) const {   // nullptr: a data input
+      if (table->type() == TableType::Data) return nullptr;
+      return std::static_pointer_cast<ReferenceSegment>(table->get_chunk(chunk)->get_segment(columns_of_group[group][0]))->pos_list().get();
+    }
+    // A column of the group as the library takes it: only its chunk layout and PosLists are read, so any column the device path describes
+    // serves (one that is resident already first).  Throws std::logic_error if there is none.
+    std::shared_ptr<DeviceColumn> layout_column(size_t group) const {
+      if (table->device_columns) {
+        for (const auto& [key, column] : table->device_columns->columns)
+          if (column && group_of_column[key.first] == group) return column;
+      }
+      for (const ColumnID c : columns_of_group[group]) {
+        try { return device_column(table, c); } catch (const std::logic_error&) {}
+      }
+      Fail("Product: no column of the input is describable to the device");
+    }
+  };
+
+  // product.cpp:114-128 on the host: the fallback for what the library refuses.
+  static std::shared_ptr<RowIDPosList> host_pair_list(const Side& side, size_t group, bool is_left, ChunkID chunk, ChunkOffset left_rows, ChunkOffset right_rows) {
+    const AbstractPosList* in = side.input_list(group, chunk);
+    auto out = std::make_shared<RowIDPosList>();
+    const size_t rows = size_t{left_rows} * right_rows;
+    out->rows.reserve(rows);
+    for (size_t p = 0; p < rows; ++p) {
+      const auto offset = static_cast<ChunkOffset>(is_left ? p / right_rows : p % right_rows);
+      out->rows.push_back(in ? (*in)[offset] : RowID{chunk, offset});
+    }
+    if (!in || in->references_single_chunk()) out->guarantee_single_chunk();
+    return out;
+  }
+
+  std::shared_ptr<const Table> _on_execute() override {
+    const auto left = left_input_table(), right = right_input_table();
+    TableColumnDefinitions definitions = left->column_definitions();
+    definitions.insert(definitions.end(), right->column_definitions().begin(), right->column_definitions().end());
+    const ChunkID n_left = left->chunk_count(), n_right = right->chunk_count();
+    const size_t n_pairs = size_t{n_left} * n_right;
+    std::vector<std::shared_ptr<Chunk>> chunks;
+    if (!n_pairs) return std::make_shared<Table>(definitions, TableType::References, std::move(chunks));
+    std::vector<uint64_t> pair_offsets(n_pairs + 1, 0);
+    for (ChunkID cl = 0; cl < n_left; ++cl)
+      for (ChunkID cr = 0; cr < n_right; ++cr)
+        pair_offsets[size_t{cl} * n_right + cr + 1] = pair_offsets[size_t{cl} * n_right + cr] + uint64_t{left->get_chunk(cl)->size()} * right->get_chunk(cr)->size();
+    const uint64_t n_rows = pair_offsets[n_pairs];
+    Side sides[2] = {Side(left), Side(right)};
+    const bool on_device = device_resident_results();
+    try {
+      const auto left_layout = sides[0].layout_column(0), right_layout = sides[1].layout_column(0);   // (every call needs both inputs' chunk sizes)
+      for (size_t s = 0; s < 2; ++s) {
+        Side& side = sides[s];
+        for (size_t g = 0; g < side.lists.size(); ++g) {
+          const auto of_group = g == 0 ? (s == 0 ? left_layout : right_layout) : side.layout_column(g);
+          hy_product_result result{};
+          result.capacity = std::max<uint64_t>(1, n_rows);
+          std::shared_ptr<DeviceBlock> block;
+          std::vector<RowID> rows;
+          hy_row_id* list = nullptr;
+          if (on_device) {
+            block = DeviceBlock::acquire(result.capacity * sizeof(RowID));
+            list = static_cast<hy_row_id*>(block->ptr);
+            result.mem = HY_MEM_DEVICE;
+          } else {
+            rows.resize(result.capacity);
+            list = reinterpret_cast<hy_row_id*>(rows.data());
+            result.mem = HY_MEM_HOST;
+          }
+          (s == 0 ? result.left_pos : result.right_pos) = list;
+          check_status(hy_product(s == 0 ? of_group->handle : left_layout->handle, s == 0 ? right_layout->handle : of_group->handle, &result));
+          Assert(result.n_rows == n_rows, "Product: the library counted other rows than the chunk sizes give");
+          for (size_t pair = 0; pair < n_pairs; ++pair) {
+            const ChunkID chunk = static_cast<ChunkID>(s == 0 ? pair / n_right : pair % n_right);
+            const AbstractPosList* in = side.input_list(g, chunk);
+            const bool single = !in || in->references_single_chunk();
+            const ChunkID common = in ? in->common_chunk_id() : chunk;
+            const uint64_t begin = pair_offsets[pair], size = pair_offsets[pair + 1] - begin;
+            if (on_device) {
+              side.lists[g].push_back(std::make_shared<DevicePosList>(block, list + begin, size, single, common));
+            } else {
+              auto out = std::make_shared<RowIDPosList>(std::vector<RowID>(rows.begin() + begin, rows.begin() + begin + size));
+              if (single) out->guarantee_single_chunk();
+              side.lists[g].push_back(std::move(out));
+            }
+          }
+        }
+      }
+    } catch (const std::logic_error&) {   // HY_ERR_UNSUPPORTED, or an input no column of which the device path describes: the stock operator's loop
+      for (size_t s = 0; s < 2; ++s) {
+        for (size_t g = 0; g < sides[s].lists.size(); ++g) {
+          sides[s].lists[g].clear();
+          for (ChunkID cl = 0; cl < n_left; ++cl)
+            for (ChunkID cr = 0; cr < n_right; ++cr)
+              sides[s].lists[g].push_back(host_pair_list(sides[s], g, s == 0, s == 0 ? cl : cr, left->get_chunk(cl)->size(), right->get_chunk(cr)->size()));
+        }
+      }
+    }
+    for (size_t pair = 0; pair < n_pairs; ++pair) {
+      Segments segments;
+      for (size_t s = 0; s < 2; ++s) {
+        const Side& side = sides[s];
+        const ChunkID chunk = static_cast<ChunkID>(s == 0 ? pair / n_right : pair % n_right);
+        for (ColumnID c = 0; c < side.table->column_count(); ++c) {
+          const auto& pos_list = side.lists[side.group_of_column[c]][pair];
+          if (side.table->type() == TableType::Data) {
+            segments.push_back(std::make_shared<ReferenceSegment>(side.table, c, pos_list));
+          } else {
+            const auto in = std::static_pointer_cast<ReferenceSegment>(side.table->get_chunk(chunk)->get_segment(c));
+            segments.push_back(std::make_shared<ReferenceSegment>(in->referenced_table(), in->referenced_column_id(), pos_list));
+          }
+        }
+      }
+      chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
+    }
+    return std::make_shared<Table>(definitions, TableType::References, std::move(chunks));
+  }
+};
+
 // Sort (operators/sort.hpp, sort.cpp:287-516): ONE stable lexicographic sort of the input's rows on the device (hy_sort), whose result -- the
 // input table's positions in sorted order -- stays in a pooled block of HBM; the output's PosLists are views into it (a data input) or into
 // one block per column cluster that hy_poslist_gather dereferences it into (a reference input: JoinHash's DeviceSide), or the rows are

@@ -1005,6 +1005,50 @@ def join_nested_loop(left, right, mode, condition, secondary=None):
         return out
 
 
+class ProductLists(SortMergePairs):
+    """hy_product's output in blocks of the result-buffer pool: n_rows RowIDs per wanted side, pair (cl, cr) owning the rows
+    [pair_offsets[cl * n_right_chunks + cr], pair_offsets[cl * n_right_chunks + cr + 1]).  numpy() copies the wanted lists back (None for the other)."""
+
+    def __init__(self, capacity, want_left=True, want_right=True):
+        super().__init__(capacity)
+        self.want_left, self.want_right = want_left, want_right
+        self.n_rows, self.pair_offsets = 0, None
+
+    def numpy(self):
+        lists = []
+        for wanted, pointer in ((self.want_left, self.left_pointer), (self.want_right, self.right_pointer)):
+            rows = np.zeros((self.n_rows, 2), dtype=np.uint32) if wanted else None
+            if wanted and self.n_rows:
+                abi.check(self.lib.hy_memcpy_d2h(rows.ctypes.data, pointer, rows.nbytes))
+            lists.append(rows)
+        return tuple(lists)
+
+
+def product_count(left, right):
+    lib = abi.load_library()
+    n = C.c_uint64(0)
+    abi.check(lib.hy_product_count(left.handle, right.handle, C.byref(n)))
+    return int(n.value)
+
+
+def product(left, right, want_left=True, want_right=True):
+    """hy_product: the two PosLists of the cross join left x right (any column of each input table: only its chunk layout and, for a
+    reference column, its PosLists are read) in the reference's order -> ProductLists in device memory, sized by hy_product_count."""
+    lib = abi.load_library()
+    out = ProductLists(product_count(left, right), want_left, want_right)
+    offsets = np.zeros(left.n_chunks * right.n_chunks + 1, dtype=np.uint64)
+    result = abi.ProductResult()
+    result.mem, result.capacity, result.pair_offsets = abi.MEM_DEVICE, out.capacity, offsets.ctypes.data
+    result.left_pos, result.right_pos = out.left_pointer if want_left else None, out.right_pointer if want_right else None
+    status = lib.hy_product(left.handle, right.handle, C.byref(result))
+    if status != abi.OK:
+        out.close()
+    abi.check(status)
+    out.n_rows = out.n_pairs = int(result.n_rows)
+    out.pair_offsets = offsets
+    return out
+
+
 def string_rank_column(segments, dictionaries):
     """A DictionarySegment<pmr_string> column (string_keys.encode_string_column) as a sort key: the same attribute vectors over dictionaries
     of the strings' ranks among all of the column's distinct strings in byte order (StringRanks) -> (HostColumn of int64, StringRanks)."""

@@ -302,7 +302,9 @@ enum {
                                       *      the PK-FK probe kernels, rt_probe_emit's one atomic per pair; 0 = tests: answer "not ordered" without
                                       *      asking the device -- the paths a device without that order takes (sort_scatter, rank_table_mark ..
                                       *      rank_table_scatter_rows, the general rank-table kernels, match-any ranking)                             */
-  HY_OPT_COUNT = 17
+  HY_OPT_PRODUCT_NONTEMPORAL = 17,  /* 0    hy_product writes its 16-byte vectors with nontemporal stores (1) or through the write-back L2 (0);
+                                      *      tools/product_timing.py times one against the other in one process                                  */
+  HY_OPT_COUNT = 18
   /* (rounds 4-5 had 33: launch shapes and store flavours whose A/B timings were flat twice are constants now -- csrc/hy_options.hpp --,
    *  the radix-partitioned join path, which lost to the rank table read in place by 1.7 x, is gone) */
 };
@@ -366,6 +368,7 @@ hy_status hy_comm_all_to_all_v(hy_comm* comm, const void* send, const uint64_t* 
  *                  any address; sensibly RowIDs on 8, values on their width.
  *                hy_sort / hy_sort_limit `out`: 16-byte stores where `out` is on 16 bytes, RowID by RowID otherwise -> 8.
  *                hy_join_sort_merge lists, hy_union_positions `out`: RowID by RowID -> 8, checked (HY_ERR_INVALID, nothing written).
+ *                hy_product lists: 16-byte stores at the list's even slots, RowID by RowID at a region's odd head or tail -> 8, checked.
  *                hy_poslist_translate `out`, hy_column_export: element by element -> element size.
  *                hy_gather_row_ids / hy_poslist_gather `out`: 16-byte stores where positions and `out` are on 16 bytes, else RowID by RowID -> 8. */
 hy_status hy_column_create(const hy_segment* segments, uint32_t n_chunks, uint32_t mem, hy_column** out);
@@ -812,6 +815,39 @@ hy_status hy_join_nested_loop(const hy_column* left, const hy_column* right, uin
                               uint32_t n_secondary, hy_nested_loop_result* result);
 hy_status hy_join_nested_loop_count(const hy_column* left, const hy_column* right, uint32_t mode, uint32_t condition, const hy_join_predicate* secondary,
                                     uint32_t n_secondary, uint64_t* n_pairs);
+
+/* ---- Product (replaces Product::_on_execute / _add_product_of_two_chunks, product.cpp:32-137: what the translator emits for every cross
+ * join, lqp_translator.cpp:362 -- the one JoinMode the join operators route elsewhere) ---------------------------------------------------------
+ * Both PosLists of left x right, written on the device in ONE launch.  `left` / `right`: any column of each input table -- only its chunk
+ * layout and, for a column of HY_ENC_REFERENCE segments, its PosLists are read (host lists, device lists and NULL = entire-chunk lists, as
+ * hy_poslist_gather's `reference`); type, encoding and values do not matter, string columns included.
+ * Order of the output == the reference's, byte for byte:
+ *   1. the chunk pairs run (cl, cr) with cl outermost (product.cpp:51-61); pair (cl, cr) owns the rows
+ *      [pair_offsets[cl * n_right_chunks + cr], pair_offsets[cl * n_right_chunks + cr + 1]) of both lists -- one output chunk of the
+ *      reference (:136) --, pair_offsets being the exclusive prefix sum of rows(cl) * rows(cr); a pair with an empty side owns nothing;
+ *   2. row p of a pair pairs left offset p / rows(cr) with right offset p % rows(cr) (:119-122);
+ *   3. a data column's RowID is {chunk, offset}; a reference column's is its PosList's entry at that offset ({ref_chunk_id, offset} for an
+ *      entire-chunk list), NULL_ROW_ID entries -- an outer join's output -- included as they are (:123-127).
+ * left_pos / right_pos: either may be NULL -- that side is not wanted (an input table whose columns sit behind k PosLists needs k lists for
+ * its side, product.cpp:109-113: one more call per further list with only that side wanted); both NULL: HY_ERR_INVALID.  pair_offsets (host
+ * memory, may be NULL) is written on HY_OK only.  mem = HY_MEM_DEVICE: the lists stay in HBM for the next operator; they lie on 8-byte
+ * boundaries (otherwise HY_ERR_INVALID): two RowIDs per 16-byte store at the even slots of a list, one RowID per store where a pair's region
+ * begins or ends on an odd slot.
+ * Refusals, all decided before any kernel runs, nothing written: HY_ERR_CAPACITY with n_rows = what is needed when the result does not fit
+ * `capacity`; HY_ERR_UNSUPPORTED when some pair's rows(cl) * rows(cr) does not fit a ChunkOffset (>= 2^32 - 1, :120) and for MVCC
+ * pseudo-columns; HY_ERR_INVALID for null arguments, input PosLists or output lists off 8-byte boundaries.
+ * hy_product_count: n_rows alone (pure host arithmetic, the same refusals).  Returns when the lists are complete. */
+typedef struct hy_product_result {
+  uint32_t mem;              /* HY_MEM_HOST | HY_MEM_DEVICE */
+  uint32_t reserved;
+  hy_row_id* left_pos;       /* [capacity] or NULL: this side not wanted */
+  hy_row_id* right_pos;      /* [capacity] or NULL */
+  uint64_t* pair_offsets;    /* host, [n_left_chunks * n_right_chunks + 1], or NULL */
+  uint64_t capacity;
+  uint64_t n_rows;           /* out: rows written, or needed with HY_ERR_CAPACITY */
+} hy_product_result;
+hy_status hy_product(const hy_column* left, const hy_column* right, hy_product_result* result);
+hy_status hy_product_count(const hy_column* left, const hy_column* right, uint64_t* n_rows);
 
 /* write_output_chunks' chunking of a join result (join_output_writing.cpp:245-296; JoinHash always allows the merge,
  * join_hash.cpp:563): one output chunk per non-empty PosList of slice_offsets[0 .. n_slices], after merging a PosList of fewer
