@@ -61,6 +61,13 @@ class Predicate(C.Structure):
 
 
 MAX_IN_LIST = 256
+MAX_LIKE_PATTERN = 256                    # HY_MAX_LIKE_PATTERN
+LIKE_ANY_ONE, LIKE_ANY_RUN = 0x100, 0x200   # hy_like_tokenize's tokens for `_` and `%`
+
+
+class StringDictionaryChunk(C.Structure):
+    """hy_string_dictionary_chunk: one chunk's dictionary entries in value-id order -- offsets into chars, or (offsets None) slots of string_length bytes."""
+    _fields_ = [("n_entries", C.c_uint32), ("string_length", C.c_uint32), ("chars", C.c_void_p), ("offsets", C.c_void_p)]
 
 
 class InList(C.Structure):
@@ -120,7 +127,7 @@ NLJ_MAX_TEMPORARY_BYTES = 1 << 31      # HY_NLJ_MAX_TEMPORARY_BYTES
 (OPT_ALLOW_ANY_ARCH, OPT_JOIN_RANK_TABLE, OPT_JOIN_HINT, OPT_JOIN_BREAK_HINT, OPT_JOIN_PKFK, OPT_JOIN_LDS_BUILD, OPT_JOIN_LDS_BUILD_TILES, OPT_JOIN_FILL_WGS_PER_CU,
  OPT_JOIN_HAND_OVER_RANKS, OPT_AGG_PARTITION_BITS, OPT_AGG_SPILL_SHIFT, OPT_AGG_SMALL_DOMAIN, OPT_FUSED_SMALL_DOMAIN, OPT_SCAN_TWO_COLUMNS, OPT_STAR_FUSED_PROBE, OPT_STAR_FUSED_FINISH,
  OPT_LDS_ORDERED_ATOMICS, OPT_PRODUCT_NONTEMPORAL) = range(18)
-KERNEL_OTHER, KERNEL_SCAN, KERNEL_JOIN_PROBE, KERNEL_JOIN_COUNT, KERNEL_JOIN_BUILD, KERNEL_AGGREGATE, KERNEL_PROJECTION = range(7)   # hy_profile_read_kernel
+KERNEL_OTHER, KERNEL_SCAN, KERNEL_JOIN_PROBE, KERNEL_JOIN_COUNT, KERNEL_JOIN_BUILD, KERNEL_AGGREGATE, KERNEL_PROJECTION, KERNEL_LIKE = range(8)   # hy_profile_read_kernel
 ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV, ARITH_MOD = range(5)
 
 
@@ -265,6 +272,12 @@ SYMBOLS = [
     ("hy_column_chunk_count", C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("hy_table_scan", C.c_int32, [C.c_void_p, C.POINTER(Predicate), C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_table_scan_in_list", C.c_int32, [C.c_void_p, C.POINTER(InList), C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
+    ("hy_string_dictionary_create", C.c_int32, [C.POINTER(StringDictionaryChunk), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("hy_string_dictionary_destroy", C.c_int32, [C.c_void_p]),
+    ("hy_string_dictionary_match_layout", C.c_int32, [C.c_void_p, C.c_void_p]),
+    ("hy_like_tokenize", C.c_int32, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("hy_like_matches", C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("hy_table_scan_like", C.c_int32, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_in_list_cast", C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("hy_table_scan_columns", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_projection_arithmetic", C.c_int32, [C.c_uint32, C.POINTER(Operand), C.POINTER(Operand), C.POINTER(C.c_void_p)]),

@@ -169,6 +169,56 @@ struct hy_column {
 
 namespace hy {
 
+// ---- like.hip: string dictionaries in device memory and the LIKE matcher over them ---------------------------------------------------
+// One chunk's dictionary as the matcher reads it (32 bytes: two 16-byte scalar loads).
+struct LikeChunk {
+  const char* chars;
+  const uint32_t* offsets;     // [n_entries + 1] byte offsets into chars, or nullptr: slots of string_length bytes
+  uint32_t n_entries;
+  uint32_t string_length;
+  uint64_t first_word;         // where the chunk's bitmap words begin (hy_string_dictionary::word_offsets)
+};
+// The 256 consecutive entries a matcher workgroup owns: four bitmap words.
+struct LikeBlock {
+  uint32_t chunk;
+  uint32_t first_entry;        // a multiple of 256
+};
+// A LIKE pattern as the kernel takes it (hy_like_tokenize): one token per pattern element, runs of `%` collapsed into one.
+constexpr uint16_t LIKE_ANY_ONE = 0x100, LIKE_ANY_RUN = 0x200;
+struct LikeProgram {
+  uint16_t tokens[HY_MAX_LIKE_PATTERN];   // a literal byte (folded under the insensitive conditions) | LIKE_ANY_ONE | LIKE_ANY_RUN
+  uint32_t n_tokens;
+  uint32_t negated;
+  uint32_t insensitive;
+};
+
+}  // namespace hy
+
+// The opaque ABI type: the dictionaries of one column's DictionarySegment<pmr_string> chunks, value-id order, resident in HBM.
+struct hy_string_dictionary {
+  uint32_t n_chunks = 0;
+  uint32_t mem = HY_MEM_HOST;
+  int device = 0;
+  std::vector<hy::LikeChunk> chunks;            // (chars / offsets: device addresses)
+  std::vector<hy::LikeBlock> blocks;
+  std::vector<uint64_t> word_offsets;           // [n_chunks + 1]
+  mutable std::vector<void*> owned;             // device allocations freed with the object
+  // The three tables above in device memory, uploaded by the first launch that needs them (creating a dictionary over caller-owned
+  // device buffers is pure host work).
+  mutable std::mutex tables_mutex;
+  mutable hy::LikeChunk* d_chunks = nullptr;
+  mutable hy::LikeBlock* d_blocks = nullptr;
+  mutable uint64_t* d_word_offsets = nullptr;
+};
+
+namespace hy {
+
+int this_thread_device();   // runtime.hip: the device the calling thread is bound to
+hy_status like_program(const char* pattern, uint32_t pattern_bytes, uint32_t condition, LikeProgram* program, const char* entry_point);
+hy_status like_dictionary_tables(const hy_string_dictionary* dict);   // ensures d_chunks / d_blocks / d_word_offsets
+// queues the matcher on `stream`: d_words[word_offsets[c] + v / 64] bit v % 64 for every entry v of every chunk c (tail bits zero)
+hy_status like_launch(const hy_string_dictionary* dict, const LikeProgram& program, uint64_t* d_words, hipStream_t stream);
+
 // ---- errors ---------------------------------------------------------------------------------------------------------
 hy_status fail(hy_status code, const char* fmt, ...);
 hy_status on_this_device(const hy_column* column, const char* entry_point);   // runtime.hip: the calling thread's device holds the column

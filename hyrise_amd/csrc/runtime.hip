@@ -76,6 +76,11 @@ hy_status on_this_device(const hy_column* column, const char* entry_point) {
   return on_this_device(column->ref, entry_point);
 }
 
+int this_thread_device() {
+  bind_thread_device();
+  return t_bound_device >= 0 ? t_bound_device : 0;
+}
+
 void bind_thread_to(int device) {
   t_own_device = device;
   bind_thread_device();

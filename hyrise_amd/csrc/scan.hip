@@ -2312,9 +2312,15 @@ hy_status regions_to_host_result(const hy_row_id* d_matches, const uint64_t* d_o
   return HY_OK;
 }
 
+// hy_table_scan_like: the dictionary and the tokenised pattern whose bitmaps run_scan has the matcher write into its scratch arena
+struct DeviceLike {
+  const hy_string_dictionary* dict;
+  const LikeProgram* program;
+};
+
 static hy_status run_scan(const hy_column* column, const hy_column* right, const hy_predicate* predicate, uint32_t condition,
                           const uint32_t* excluded, uint32_t n_excluded, hy_scan_result* result, const VisibilityArgs* visibility = nullptr,
-                          const InListArgs* in_list = nullptr) {
+                          const InListArgs* in_list = nullptr, const DeviceLike* device_like = nullptr) {
   // Run-length / bit-packed segments are read in place by a ColumnVsValue / Between / IsNull / Like scan of the data column itself; the
   // two-column scan and the scan through reference segments read the decoded twins (hy_device.hpp) -- a reference segment's `ref`
   // already points at the twin's descriptors, so the jobs are prepared from the twin as well.
@@ -2341,7 +2347,8 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
   // Scratch: jobs | per_chunk arrays | excluded | overflow flag | (host results) regions + dense copy + per-chunk arrays
   size_t need = sizeof(ScanJob) * (n_data_chunks + 1) + 3 * 4 * (size_t{n_data_chunks} + 64) + 4 * (size_t{n_excluded} + 64) + 1024;
   const bool like = predicate && predicate->condition >= HY_PRED_LIKE && predicate->condition <= HY_PRED_NOT_LIKE_INSENSITIVE;
-  if (like) need += 8 * (size_t{n_data_chunks} + 2) + 8 * (predicate->match_word_offsets[n_data_chunks] + 2) + 1024;
+  if (like && device_like) need += 8 * (device_like->dict->word_offsets[n_data_chunks] + 2) + 512;   // the matcher's words; their offsets are the dictionary's
+  else if (like) need += 8 * (size_t{n_data_chunks} + 2) + 8 * (predicate->match_word_offsets[n_data_chunks] + 2) + 1024;
   // IN / NOT IN: keys | values | caller's value ids | bitmap offsets | bitmaps + "any" words of the dictionary chunks (one zeroed block)
   std::vector<uint64_t> set_offsets;
   if (in_list) {
@@ -2427,7 +2434,13 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
     HY_TRY(stage(predicate->per_chunk_lower, 4 * size_t{n_data_chunks}, &d)); pa.per_chunk_lower = static_cast<const uint32_t*>(d);
     HY_TRY(stage(predicate->per_chunk_upper, 4 * size_t{n_data_chunks}, &d)); pa.per_chunk_upper = static_cast<const uint32_t*>(d);
     HY_TRY(stage(predicate->per_chunk_found, size_t{n_data_chunks}, &d)); pa.per_chunk_found = static_cast<const uint8_t*>(d);
-    if (predicate->match_words && predicate->match_word_offsets) {
+    if (device_like) {   // hy_table_scan_like: the bitmaps are made where they are read (like.hip), in front of prepare_jobs on this stream
+      uint64_t* d_words = carve<uint64_t>(sc, device_like->dict->word_offsets[n_data_chunks] + 1);
+      if (!d_words) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+      HY_TRY(like_launch(device_like->dict, *device_like->program, d_words, stream));
+      pa.match_words = d_words;
+      pa.match_word_offsets = device_like->dict->d_word_offsets;
+    } else if (predicate->match_words && predicate->match_word_offsets) {
       const uint64_t total_words = predicate->match_word_offsets[n_data_chunks];
       HY_TRY(stage(predicate->match_word_offsets, 8 * (size_t{n_data_chunks} + 1), &d)); pa.match_word_offsets = static_cast<const uint64_t*>(d);
       HY_TRY(stage(predicate->match_words, 8 * (total_words ? total_words : 1), &d)); pa.match_words = static_cast<const uint64_t*>(d);
@@ -2597,6 +2610,43 @@ hy_status hy_table_scan(const hy_column* column, const hy_predicate* predicate, 
     return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
   }
   return run_scan(column, nullptr, predicate, 0, excluded_chunks, n_excluded, result);
+}
+
+hy_status hy_table_scan_like(const hy_column* column, const hy_string_dictionary* dict, const char* pattern, uint32_t pattern_bytes, uint32_t condition,
+                             uint32_t column_is_nullable, const uint32_t* excluded_chunks, uint32_t n_excluded, hy_scan_result* result) {
+  if (!column || !dict || !result) return fail(HY_ERR_INVALID, "hy_table_scan_like: null argument");
+  LikeProgram program;
+  HY_TRY(like_program(pattern, pattern_bytes, condition, &program, "hy_table_scan_like"));
+  HY_TRY(on_this_device(column, "hy_table_scan_like"));
+  if (dict->device != column->device) return fail(HY_ERR_INVALID, "hy_table_scan_like: the dictionary lives on device %d, the column on device %d", dict->device, column->device);
+  if (n_excluded && !excluded_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_like: excluded chunk list missing");
+  if (n_excluded && column->is_reference) return fail(HY_ERR_INVALID, "excluded chunks apply to data tables only");   // (run_scan's refusal, here in front of the matcher's launch)
+  for (uint32_t i = 0; i < n_excluded; ++i) {
+    if (excluded_chunks[i] >= column->n_chunks) return fail(HY_ERR_INVALID, "excluded chunk id %u out of range", excluded_chunks[i]);
+  }
+  if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
+  // column_like_table_scan_impl.cpp:32-36: "LIKE operator only applicable on string columns"; the dictionary is the data column's
+  const hy_column* data_column = column->is_reference ? column->ref : column;
+  if (column->data_type != HY_TYPE_STRING && column->n_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_like: LIKE is only applicable on string columns (column type %u)", column->data_type);
+  const uint32_t n_data_chunks = data_column ? data_column->n_chunks : 0;
+  for (uint32_t c = 0; c < n_data_chunks; ++c) {
+    if (data_column->host_segments[c].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "LIKE on unencoded string segments stays on the CPU path");
+  }
+  if (dict->n_chunks != n_data_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_like: the dictionary has %u chunks, the data column %u", dict->n_chunks, n_data_chunks);
+  for (uint32_t c = 0; c < n_data_chunks; ++c) {
+    if (dict->chunks[c].n_entries != data_column->host_segments[c].aux_size)
+      return fail(HY_ERR_INVALID, "hy_table_scan_like: chunk %u: the dictionary has %u entries, the segment's has %u", c, dict->chunks[c].n_entries, data_column->host_segments[c].aux_size);
+  }
+  if (column->multi_chunk_reference && result->mem == HY_MEM_DEVICE && !result->counts) {
+    return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
+  }
+  hy_predicate predicate;
+  std::memset(&predicate, 0, sizeof(predicate));
+  predicate.condition = condition;
+  predicate.value_type = HY_TYPE_STRING;
+  predicate.column_is_nullable = column_is_nullable;
+  const DeviceLike device_like{dict, &program};
+  return run_scan(column, nullptr, &predicate, 0, excluded_chunks, n_excluded, result, nullptr, nullptr, &device_like);
 }
 
 hy_status hy_table_scan_in_list(const hy_column* column, const hy_in_list* list, const uint32_t* excluded_chunks, uint32_t n_excluded, hy_scan_result* result) {

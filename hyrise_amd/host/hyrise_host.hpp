@@ -768,8 +768,14 @@ struct DeviceColumn {
 // stand-ins for the strings -- AggregateKey names (GROUP BY), join ids (JoinHash) or ranks among the column's distinct strings in byte
 // order (Sort; hyrise_amd/string_keys.py StringRanks).
 enum class StringKeys { None, AggregateKeyNames, JoinIds, Ranks };
+// The dictionaries of a string column's DictionarySegment chunks in HBM (hy_string_dictionary): what the LIKE matcher reads on the device.
+struct DeviceStringDictionary {
+  hy_string_dictionary* handle = nullptr;
+  ~DeviceStringDictionary() { if (handle) hy_string_dictionary_destroy(handle); }
+};
 struct ColumnCache {
   std::map<std::pair<ColumnID, StringKeys>, std::shared_ptr<DeviceColumn>> columns;
+  std::map<ColumnID, std::shared_ptr<DeviceStringDictionary>> string_dictionaries;
 };
 inline Table::~Table() = default;
 
@@ -996,6 +1002,44 @@ inline std::shared_ptr<DeviceColumn> device_column(const std::shared_ptr<const T
   return slot;
 }
 
+// One chunk's dictionary as hy_string_dictionary_chunk takes a pmr_vector<pmr_string>: the entries' bytes back to back, n + 1 offsets.
+inline void pack_string_dictionary(const std::vector<std::string>& dictionary, std::string& chars, std::vector<uint32_t>& offsets) {
+  chars.clear();
+  offsets.assign(1, 0);
+  for (const auto& entry : dictionary) {
+    chars.append(entry);
+    Assert(chars.size() < (uint64_t{1} << 32), "a chunk's dictionary of 4 GiB or more");
+    offsets.push_back(static_cast<uint32_t>(chars.size()));
+  }
+}
+
+// The residency cache's string dictionaries: packed and uploaded once per (data table, column), dropped with the table.
+inline std::shared_ptr<DeviceStringDictionary> device_string_dictionary(const std::shared_ptr<const Table>& table, ColumnID column_id) {
+  if (!table->device_columns) table->device_columns = std::make_shared<ColumnCache>();
+  auto& slot = table->device_columns->string_dictionaries[column_id];
+  if (slot) return slot;
+  const auto chunk_count = table->chunk_count();
+  std::vector<std::string> chars(chunk_count);
+  std::vector<std::vector<uint32_t>> offsets(chunk_count);
+  std::vector<hy_string_dictionary_chunk> chunks(chunk_count);
+  for (ChunkID c = 0; c < chunk_count; ++c) {
+    const auto* segment = dynamic_cast<const DictionarySegment<std::string>*>(table->get_chunk(c)->get_segment(column_id).get());
+    Assert(segment, "unencoded string segments stay on the CPU path");
+    pack_string_dictionary(segment->dictionary(), chars[c], offsets[c]);
+    chunks[c].n_entries = static_cast<uint32_t>(segment->dictionary().size());
+    chunks[c].string_length = 0;
+    chunks[c].chars = chars[c].data();
+    chunks[c].offsets = offsets[c].data();
+  }
+  auto dictionary = std::make_shared<DeviceStringDictionary>();
+  check_status(hy_string_dictionary_create(chunks.data(), chunk_count, HY_MEM_HOST, &dictionary->handle));
+  slot = dictionary;
+  return slot;
+}
+
+// LIKE scans match their dictionaries on the device (hy_table_scan_like); false: on the host, bitmaps through hy_predicate.match_words.
+inline bool& device_like_matching() { static bool enabled = true; return enabled; }
+
 // ---- operators ---------------------------------------------------------------------------------------------------------
 class AbstractOperator {   // operators/abstract_operator.hpp
  public:
@@ -1201,7 +1245,7 @@ class TableScan : public AbstractReadOnlyOperator {
     result.counts = counts.data();
     result.chunk_state = states.data();
     if (on_device) result = on_device->result;
-    bool evaluated_on_host = false;
+    bool scan_done = false;
     if (_predicate) {
       if (!scan_expression(in_table, &result, counts, states)) on_device.reset();   // (a constant predicate: counts and states say all or nothing, no RowIDs are needed)
     } else if (_right_column_id) {
@@ -1255,7 +1299,7 @@ class TableScan : public AbstractReadOnlyOperator {
             counts[c] = constant == Constant::AllRows && !excluded ? in_table->get_chunk(c)->size() : 0;
             states[c] = counts[c] ? HY_CHUNK_ALL_MATCH : HY_CHUNK_NONE_MATCH;
           }
-          evaluated_on_host = true;   // (nothing to evaluate: no RowIDs are needed for chunks that match entirely or not at all)
+          scan_done = true;   // (nothing to evaluate: no RowIDs are needed for chunks that match entirely or not at all)
         } else if (constant == Constant::NotNullRows) {
           predicate.condition = HY_PRED_IS_NOT_NULL;
         } else {
@@ -1268,13 +1312,32 @@ class TableScan : public AbstractReadOnlyOperator {
           list.column_is_nullable = in_table->column_is_nullable(_column_id);
           list.per_chunk_value_ids = column_type == DataType::String ? value_ids.data() : nullptr;
           check_status(hy_table_scan_in_list(column->handle, &list, excluded_chunk_ids.data(), static_cast<uint32_t>(excluded_chunk_ids.size()), &result));
-          evaluated_on_host = true;   // (the scan has run)
+          scan_done = true;   // (the scan has run)
         }
       } else if (like) {
         // ColumnLikeTableScanImpl (column_like_table_scan_impl.cpp:28-36)
         Assert(in_table->column_data_type(_column_id) == DataType::String, "LIKE operator only applicable on string columns.");
         Assert(std::holds_alternative<std::string>(_value), "Right parameter must be a string.");
-        find_matches_in_dictionaries(in_table, _column_id, _condition, _value, match_words, match_word_offsets, predicate);
+        // The dictionaries are matched where they live, in HBM (hy_table_scan_like); the host matcher keeps what the library refuses
+        // (a pattern beyond HY_MAX_LIKE_PATTERN) and everything when device_like_matching() is off.
+        if (device_like_matching() && chunk_count) {
+          auto data_table = in_table;
+          auto data_column_id = _column_id;
+          if (in_table->type() == TableType::References) {
+            const auto ref = std::static_pointer_cast<ReferenceSegment>(in_table->get_chunk(0)->get_segment(_column_id));
+            data_table = ref->referenced_table();
+            data_column_id = ref->referenced_column_id();
+          }
+          const auto dictionary = device_string_dictionary(data_table, data_column_id);
+          const auto& pattern = std::get<std::string>(_value);
+          const auto status = hy_table_scan_like(column->handle, dictionary->handle, pattern.data(), static_cast<uint32_t>(pattern.size()), static_cast<uint32_t>(_condition),
+                                                 predicate.column_is_nullable, excluded_chunk_ids.data(), static_cast<uint32_t>(excluded_chunk_ids.size()), &result);
+          if (status != HY_ERR_UNSUPPORTED) {
+            check_status(status);
+            scan_done = true;   // (the scan has run)
+          }
+        }
+        if (!scan_done) find_matches_in_dictionaries(in_table, _column_id, _condition, _value, match_words, match_word_offsets, predicate);
       } else if (!null_test) {
         const auto column_type = in_table->column_data_type(_column_id);
         if (column_type == DataType::String) {
@@ -1299,14 +1362,14 @@ class TableScan : public AbstractReadOnlyOperator {
             on_device.reset();
             matches.resize(std::max<uint64_t>(1, in_table->row_count()));
             evaluate_on_host(in_table, matches, offsets, counts, states);
-            evaluated_on_host = true;
+            scan_done = true;
           } else {
             check_status(status);
             predicate.condition = cast.condition, predicate.value_type = cast.value_type, predicate.value = cast.value, predicate.value2 = cast.value2;
           }
         }
       }
-      if (!evaluated_on_host) check_status(hy_table_scan(column->handle, &predicate, excluded_chunk_ids.data(), static_cast<uint32_t>(excluded_chunk_ids.size()), &result));
+      if (!scan_done) check_status(hy_table_scan(column->handle, &predicate, excluded_chunk_ids.data(), static_cast<uint32_t>(excluded_chunk_ids.size()), &result));
     }
     // ---- output assembly, table_scan.cpp:129-220 ----
     std::vector<size_t> group_of_column;

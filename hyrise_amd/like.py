@@ -23,7 +23,7 @@ def like_to_regex(pattern):
     for byte in _as_bytes(pattern):
         ch = bytes([byte])
         out.append(b".*" if ch == b"%" else b"." if ch == b"_" else re.escape(ch))
-    out.append(b"$")
+    out.append(b"\\Z")   # (the end of the input: `$` would also match in front of a trailing newline, which LikeMatcher does not)
     return re.compile(b"".join(out), re.DOTALL)
 
 

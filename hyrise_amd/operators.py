@@ -164,6 +164,57 @@ def table_scan(column, predicate, excluded_chunks=None, flags=0, capacity=None):
     return result
 
 
+def _pattern_bytes(pattern):
+    return pattern if isinstance(pattern, bytes) else str(pattern).encode("utf-8")
+
+
+def like_match_words(dev_dict, pattern, condition=abi.PRED_LIKE):
+    """hy_like_matches with a host result -> the bitmap words of all chunks, chunk c's from dev_dict.word_offsets[c]."""
+    lib = abi.load_library()
+    pattern = _pattern_bytes(pattern)
+    total = int(dev_dict.word_offsets[dev_dict.n_chunks])
+    words = np.zeros(max(1, total), dtype=np.uint64)
+    abi.check(lib.hy_like_matches(dev_dict.handle, pattern, len(pattern), condition, abi.MEM_HOST, words.ctypes.data))
+    return words[:total]
+
+
+def like_matches(dev_dict, pattern, condition=abi.PRED_LIKE):
+    """hy_like_matches over a storage.DeviceStringDictionary -> one bool array per chunk over that chunk's dictionary (what
+    like.dictionary_matches computes on the host)."""
+    words = like_match_words(dev_dict, pattern, condition)
+    out = []
+    for c in range(dev_dict.n_chunks):
+        chunk_words = words[int(dev_dict.word_offsets[c]):int(dev_dict.word_offsets[c + 1])]
+        out.append(np.unpackbits(chunk_words.view(np.uint8), bitorder="little")[:dev_dict.n_entries[c]].astype(bool))
+    return out
+
+
+def table_scan_like(dev_column, dev_dict, pattern, condition, nullable=False, flags=0, excluded=(), device=False):
+    """hy_table_scan_like: `column <LIKE condition> pattern` with the dictionary bitmaps made on the device -> HostScanResult like table_scan,
+    or with device=True the chunk-region result in device memory as table_scan_expression returns it."""
+    lib = abi.load_library()
+    pattern = _pattern_bytes(pattern)
+    excluded_array = np.ascontiguousarray(excluded, dtype=np.uint32) if len(excluded) else None
+    excluded_pointer, n_excluded = (excluded_array.ctypes.data, len(excluded_array)) if excluded_array is not None else (None, 0)
+    n_chunks, rows = dev_column.n_chunks, dev_column.rows
+    if not device:
+        result = HostScanResult(n_chunks, rows, flags)
+        abi.check(lib.hy_table_scan_like(dev_column.handle, dev_dict.handle, pattern, len(pattern), condition, 1 if nullable else 0, excluded_pointer, n_excluded,
+                                         C.byref(result.c)))
+        return result
+    import torch
+    matches = torch.zeros((max(1, rows) + 2, 2), dtype=torch.int32, device="cuda")   # (16 bytes of slack behind the last RowID)
+    offsets = torch.zeros(n_chunks + 1, dtype=torch.int64, device="cuda")
+    counts = torch.zeros(max(1, n_chunks), dtype=torch.int32, device="cuda")
+    chunk_state = torch.zeros(max(1, n_chunks), dtype=torch.uint8, device="cuda")
+    r = abi.ScanResult()
+    r.mem, r.flags = abi.MEM_DEVICE, flags | abi.SCAN_CHUNK_REGIONS
+    r.matches, r.capacity = matches.data_ptr(), rows
+    r.offsets, r.counts, r.chunk_state = offsets.data_ptr(), counts.data_ptr(), chunk_state.data_ptr()
+    abi.check(lib.hy_table_scan_like(dev_column.handle, dev_dict.handle, pattern, len(pattern), condition, 1 if nullable else 0, excluded_pointer, n_excluded, C.byref(r)))
+    return matches[:max(1, rows)], offsets, counts[:n_chunks], chunk_state[:n_chunks]
+
+
 def in_list_predicate(data_type, values, negated=False, nullable=False, per_chunk_value_ids=None):
     """hy_in_list of `column [NOT] IN (values)`: `values` are non-NULL literals of exactly the column's type (in_list_cast makes them
     so).  per_chunk_value_ids: [n_data_chunks][n_values] for dictionaries that are not on the device (string_in_list_predicate)."""

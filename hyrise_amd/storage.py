@@ -335,3 +335,50 @@ class DeviceColumn:
             self.close()
         except Exception:
             pass
+
+
+def pack_string_dictionary(dictionary, fixed_length=None):
+    """One chunk's dictionary (a list of byte strings in value-id order) as hy_string_dictionary_chunk takes it -> (chars uint8 array, offsets
+    uint32 array [n + 1]) or, with fixed_length = L, (chars [n * L] with every entry padded with \\0 to L bytes, None): FixedStringVector's layout."""
+    entries = [e if isinstance(e, bytes) else str(e).encode("utf-8") for e in dictionary]
+    if fixed_length is not None:
+        assert all(len(e) <= fixed_length for e in entries)
+        return np.frombuffer(b"".join(e.ljust(fixed_length, b"\0") for e in entries), dtype=np.uint8).copy(), None
+    offsets = np.zeros(len(entries) + 1, dtype=np.uint64)
+    np.cumsum([len(e) for e in entries], out=offsets[1:])
+    assert int(offsets[-1]) < 1 << 32
+    return np.frombuffer(b"".join(entries), dtype=np.uint8).copy(), offsets.astype(np.uint32)
+
+
+class DeviceStringDictionary:
+    """RAII handle of an hy_string_dictionary: the dictionaries of one string column's chunks (encode_string_dictionary's second result, per
+    chunk) uploaded once.  fixed_length = L: the fixed-slot layout.  Packing is all that happens here."""
+
+    def __init__(self, dictionaries, fixed_length=None):
+        self.lib = abi.load_library()
+        self.n_chunks = len(dictionaries)
+        self.n_entries = [len(d) for d in dictionaries]
+        self.fixed_length = fixed_length
+        self.packed = [pack_string_dictionary(d, fixed_length) for d in dictionaries]
+        chunks = (abi.StringDictionaryChunk * max(1, self.n_chunks))()
+        for c, (chars, offsets) in enumerate(self.packed):
+            chunks[c].n_entries = self.n_entries[c]
+            chunks[c].string_length = fixed_length or 0
+            chunks[c].chars = chars.ctypes.data if len(chars) else None
+            chunks[c].offsets = offsets.ctypes.data if offsets is not None else None
+        handle = C.c_void_p()
+        abi.check(self.lib.hy_string_dictionary_create(chunks, self.n_chunks, abi.MEM_HOST, C.byref(handle)))
+        self.handle = handle
+        self.word_offsets = np.zeros(self.n_chunks + 1, dtype=np.uint64)
+        abi.check(self.lib.hy_string_dictionary_match_layout(self.handle, self.word_offsets.ctypes.data))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.hy_string_dictionary_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -174,7 +174,8 @@ typedef struct hy_predicate {
   uint32_t reserved;
   /* HY_PRED_LIKE / NOT_LIKE / LIKE_INSENSITIVE / NOT_LIKE_INSENSITIVE on dictionary (incl. FixedString) segments
    * (ColumnLikeTableScanImpl::_scan_dictionary_segment, column_like_table_scan_impl.cpp:69-140): the adapter runs Hyrise's
-   * LikeMatcher over every chunk's dictionary (`_find_matches_in_dictionary`, small host work) and passes the result as
+   * LikeMatcher over every chunk's dictionary (`_find_matches_in_dictionary`: one matcher call per DISTINCT string -- a few thousand
+   * for p_type, 15 million at SF10 for o_comment; hy_table_scan_like does this pass on the device instead) and passes the result as
    * bitmaps: bit v of the words starting at match_words[match_word_offsets[c]] says whether value id v of data chunk c
    * satisfies the predicate (the matcher already applies NOT); match_word_offsets has one entry per data chunk plus the
    * end.  The device scans the attribute vectors against the bitmaps; the NULL value id never matches. */
@@ -235,7 +236,7 @@ hy_status hy_profile_read(float* total_milliseconds, uint32_t* launches);
 /* The same per kernel, without resetting: an operator chain (bench.py's TableScan + JoinHash step) reads the time of each of its
  * timed kernels separately before hy_profile_read() clears the session. */
 enum { HY_KERNEL_OTHER = 0, HY_KERNEL_SCAN = 1, HY_KERNEL_JOIN_PROBE = 2, HY_KERNEL_JOIN_COUNT = 3, HY_KERNEL_JOIN_BUILD = 4, HY_KERNEL_AGGREGATE = 5,
-       HY_KERNEL_PROJECTION = 6, HY_KERNEL_KINDS = 8 };
+       HY_KERNEL_PROJECTION = 6, HY_KERNEL_LIKE = 7 /* like_match, the dictionary matcher */, HY_KERNEL_KINDS = 8 };
 hy_status hy_profile_read_kernel(uint32_t kernel, float* total_milliseconds, uint32_t* launches);
 /* What such an event pair measures beyond the kernel itself (the pair is stamped from the dispatch packet): the elapsed time of an
  * empty kernel, median of 32 launches, measured once per process.  A profiler's per-kernel duration is shorter by about this much. */
@@ -422,6 +423,60 @@ hy_status hy_in_list_cast(uint32_t column_type, const uint32_t* literal_types, c
 /* ColumnVsColumn (column_vs_column_table_scan_impl.cpp:36-187): left <condition> right, both columns of one table. */
 hy_status hy_table_scan_columns(const hy_column* left, const hy_column* right, uint32_t condition,
                                 hy_scan_result* result);
+
+/* ---- LIKE over string dictionaries in device memory (ColumnLikeTableScanImpl, column_like_table_scan_impl.cpp:69-159) ------------------
+ * hy_predicate.match_words takes the LIKE family as bitmaps the HOST made, one matcher call per distinct string.  The entry points below
+ * keep the dictionaries of a column's DictionarySegment<pmr_string> chunks in HBM beside the attribute vectors and run the matcher there.
+ *
+ * hy_string_dictionary: per data chunk of ONE column that chunk's dictionary entries in value-id order.  A chunk comes in one of two layouts:
+ *   offsets != NULL   n_entries + 1 uint32_t byte offsets into `chars` (ascending; entry v = chars[offsets[v] .. offsets[v + 1])): what an
+ *                     adapter packs once per column from a pmr_vector<pmr_string>.  Bytes are arbitrary; a '\0' inside an entry is data.
+ *   offsets == NULL   n_entries slots of string_length bytes, read in place as FixedStringVector keeps them; an entry's length is
+ *                     strnlen(slot, string_length) (fixed_string.cpp:86-99).
+ *   n_entries == 0 is a legal chunk (the dictionary of a NULL-only segment); its pointers are not read.
+ * mem == HY_MEM_HOST: the buffers are copied to HBM once and owned by the object (ascending offsets are checked: HY_ERR_INVALID).
+ * mem == HY_MEM_DEVICE: the buffers stay the caller's, under hy_column_create's rules for caller-owned inputs: `offsets` on 4 bytes, `chars`
+ *   at ANY byte address, 16 readable bytes behind the last element of each.  Creating the object is pure host work; the object owns the
+ *   small tables the first launch uploads.  The caller's offsets are not read by the call, so a chunk with entries needs its `chars`
+ *   (NULL: HY_ERR_INVALID) even where every entry is empty; with HY_MEM_HOST `chars` may be NULL then.
+ * A chunk whose chars would take 2^32 bytes or more: HY_ERR_UNSUPPORTED.  Nothing is allocated for a dictionary that is refused. */
+typedef struct hy_string_dictionary hy_string_dictionary; /* opaque */
+typedef struct hy_string_dictionary_chunk {
+  uint32_t n_entries;
+  uint32_t string_length;    /* offsets == NULL: bytes per slot */
+  const char* chars;
+  const uint32_t* offsets;   /* [n_entries + 1], or NULL */
+} hy_string_dictionary_chunk;
+hy_status hy_string_dictionary_create(const hy_string_dictionary_chunk* chunks, uint32_t n_chunks, uint32_t mem, hy_string_dictionary** out);
+hy_status hy_string_dictionary_destroy(hy_string_dictionary* dict);
+/* The bitmap layout of hy_predicate.match_words / match_word_offsets: chunk c owns ceil(n_entries_c / 64) words from word_offsets[c];
+ * word_offsets: host memory, [n_chunks + 1].  Pure host arithmetic. */
+hy_status hy_string_dictionary_match_layout(const hy_string_dictionary* dict, uint64_t* word_offsets);
+/* The pattern language, that of the mirror's LikeMatcher and hyrise_amd/like.py (like_matcher.cpp:32-55): `%` matches any run of bytes,
+ * including none; `_` exactly one byte; everything else is literal.  Bytes, not code points.  The insensitive conditions fold ASCII A-Z on
+ * both sides: the host folds the pattern once, the kernel an entry as it reads it.
+ * hy_like_tokenize: the pattern as the kernel takes it -- one token per element: the literal byte, HY_LIKE_ANY_ONE or HY_LIKE_ANY_RUN (a run
+ * of `%` is one token).  tokens: room for HY_MAX_LIKE_PATTERN.  Pure host work.  A condition outside HY_PRED_LIKE .. NOT_LIKE_INSENSITIVE:
+ * HY_ERR_INVALID; a pattern of more than HY_MAX_LIKE_PATTERN bytes: HY_ERR_UNSUPPORTED (the adapter keeps its host matcher for it). */
+#define HY_MAX_LIKE_PATTERN 256
+#define HY_LIKE_ANY_ONE 0x100u
+#define HY_LIKE_ANY_RUN 0x200u
+hy_status hy_like_tokenize(const char* pattern, uint32_t pattern_bytes, uint32_t condition, uint16_t* tokens, uint32_t* n_tokens);
+/* The matcher, one launch: bit v % 64 of match_words[word_offsets[c] + v / 64] is set iff entry v of chunk c satisfies the condition (NOT
+ * applied); the tail bits of a chunk's last word are zero, under the NOT forms too.  mem == HY_MEM_DEVICE: the words stay in the caller's
+ * device buffer (on 8 bytes, otherwise HY_ERR_INVALID; one 8-byte store per word), complete in the order of the calling thread's stream.
+ * mem == HY_MEM_HOST: copied back; the call returns when they are there.  All refusals come before any launch. */
+hy_status hy_like_matches(const hy_string_dictionary* dict, const char* pattern, uint32_t pattern_bytes, uint32_t condition, uint32_t mem,
+                          uint64_t* match_words);
+/* hy_table_scan for `column <LIKE condition> pattern` with the bitmaps made on the device: the matcher runs on the calling thread's stream
+ * into the scratch arena, the scan reads the words where they are.  The result is hy_table_scan's for the same predicate with host-made
+ * bitmaps, bit for bit (matches, offsets, counts, chunk states, every HY_SCAN_* flag, either result->mem; excluded_chunks for data columns).
+ * `column` may be a reference column; `dict` then belongs to the referenced data column.  HY_ERR_INVALID when the column is no string column
+ * or dict's chunk count or any n_entries differs from the data column's dictionary segments (aux_size); HY_ERR_UNSUPPORTED for unencoded
+ * string segments and for patterns beyond HY_MAX_LIKE_PATTERN.  Nothing is launched or written in any of these cases. */
+hy_status hy_table_scan_like(const hy_column* column, const hy_string_dictionary* dict, const char* pattern, uint32_t pattern_bytes,
+                             uint32_t condition, uint32_t column_is_nullable, const uint32_t* excluded_chunks, uint32_t n_excluded,
+                             hy_scan_result* result);
 
 /* ---- Validate (replaces Validate::_on_execute / _validate_chunks, validate.cpp:32-55,87-314) ----
  * The MVCC visibility filter that sits in front of every TableScan of an SQL-driven plan.  The table's MvccData
