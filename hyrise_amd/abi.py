@@ -127,7 +127,7 @@ NLJ_MAX_TEMPORARY_BYTES = 1 << 31      # HY_NLJ_MAX_TEMPORARY_BYTES
 (OPT_ALLOW_ANY_ARCH, OPT_JOIN_RANK_TABLE, OPT_JOIN_HINT, OPT_JOIN_BREAK_HINT, OPT_JOIN_PKFK, OPT_JOIN_LDS_BUILD, OPT_JOIN_LDS_BUILD_TILES, OPT_JOIN_FILL_WGS_PER_CU,
  OPT_JOIN_HAND_OVER_RANKS, OPT_AGG_PARTITION_BITS, OPT_AGG_SPILL_SHIFT, OPT_AGG_SMALL_DOMAIN, OPT_FUSED_SMALL_DOMAIN, OPT_SCAN_TWO_COLUMNS, OPT_STAR_FUSED_PROBE, OPT_STAR_FUSED_FINISH,
  OPT_LDS_ORDERED_ATOMICS, OPT_PRODUCT_NONTEMPORAL) = range(18)
-KERNEL_OTHER, KERNEL_SCAN, KERNEL_JOIN_PROBE, KERNEL_JOIN_COUNT, KERNEL_JOIN_BUILD, KERNEL_AGGREGATE, KERNEL_PROJECTION, KERNEL_LIKE = range(8)   # hy_profile_read_kernel
+KERNEL_OTHER, KERNEL_SCAN, KERNEL_JOIN_PROBE, KERNEL_JOIN_COUNT, KERNEL_JOIN_BUILD, KERNEL_AGGREGATE, KERNEL_PROJECTION, KERNEL_LIKE, KERNEL_STRING_RANK = range(9)   # hy_profile_read_kernel
 ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV, ARITH_MOD = range(5)
 
 
@@ -280,6 +280,8 @@ SYMBOLS = [
     ("hy_table_scan_like", C.c_int32, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_in_list_cast", C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("hy_table_scan_columns", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
+    ("hy_string_dictionary_ranks", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("hy_table_scan_columns_strings", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_projection_arithmetic", C.c_int32, [C.c_uint32, C.POINTER(Operand), C.POINTER(Operand), C.POINTER(C.c_void_p)]),
     ("hy_projection_expression", C.c_int32, [C.POINTER(ProjectionProgram), C.POINTER(C.c_void_p)]),
     ("hy_table_scan_expression", C.c_int32, [C.POINTER(ProjectionProgram), C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),

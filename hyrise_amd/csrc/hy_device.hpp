@@ -202,6 +202,7 @@ struct hy_string_dictionary {
   std::vector<hy::LikeChunk> chunks;            // (chars / offsets: device addresses)
   std::vector<hy::LikeBlock> blocks;
   std::vector<uint64_t> word_offsets;           // [n_chunks + 1]
+  std::vector<uint64_t> entry_offsets;          // [n_chunks + 1] prefix sum of n_entries: where a chunk's ranks begin (string_order.hip)
   mutable std::vector<void*> owned;             // device allocations freed with the object
   // The three tables above in device memory, uploaded by the first launch that needs them (creating a dictionary over caller-owned
   // device buffers is pure host work).
@@ -209,15 +210,36 @@ struct hy_string_dictionary {
   mutable hy::LikeChunk* d_chunks = nullptr;
   mutable hy::LikeBlock* d_blocks = nullptr;
   mutable uint64_t* d_word_offsets = nullptr;
+  mutable uint64_t* d_entry_offsets = nullptr;
 };
 
 namespace hy {
 
 int this_thread_device();   // runtime.hip: the device the calling thread is bound to
 hy_status like_program(const char* pattern, uint32_t pattern_bytes, uint32_t condition, LikeProgram* program, const char* entry_point);
-hy_status like_dictionary_tables(const hy_string_dictionary* dict);   // ensures d_chunks / d_blocks / d_word_offsets
+hy_status like_dictionary_tables(const hy_string_dictionary* dict);   // ensures d_chunks / d_blocks / d_word_offsets / d_entry_offsets
 // queues the matcher on `stream`: d_words[word_offsets[c] + v / 64] bit v % 64 for every entry v of every chunk c (tail bits zero)
 hy_status like_launch(const hy_string_dictionary* dict, const LikeProgram& program, uint64_t* d_words, hipStream_t stream);
+
+// ---- string_order.hip: one column's dictionaries ordered against another's, chunk by chunk (hy_string_dictionary_ranks) --------------
+// Refusals of a (left, right) pair, before any launch: chunk counts, devices, a right chunk of 2^30 entries or more.
+hy_status string_order_check(const hy_string_dictionary* left, const hy_string_dictionary* right, const char* entry_point);
+// queues the ranking on `stream`: d_ranks[left->entry_offsets[c] + v] for every entry v of every chunk c of `left`
+hy_status string_order_launch(const hy_string_dictionary* left, const hy_string_dictionary* right, int32_t* d_ranks, hipStream_t stream);
+// The int32 stand-ins of a pair of string columns (hy_table_scan_columns_strings): every segment descriptor of the data columns copied with
+// data_type int32 and `aux` = the chunk's ranks (left) / the table 0, 2, 4, ... (right, filled here: n_evens entries); the descriptors of
+// reference columns (null: a data column) copied with `ref` = those copies.  One launch on `stream`.
+struct StringTwins {
+  const DevSegment* left_data; const DevSegment* right_data;   // [n_data_chunks]
+  DevSegment* left_data_twin; DevSegment* right_data_twin;
+  const DevSegment* left_reference; const DevSegment* right_reference;   // [n_chunks] or nullptr
+  DevSegment* left_reference_twin; DevSegment* right_reference_twin;
+  const uint64_t* entry_offsets;   // the left dictionary's, device memory
+  const int32_t* ranks;
+  int32_t* evens;
+  uint32_t n_data_chunks, n_chunks, n_evens;
+};
+hy_status string_twins_launch(const StringTwins& twins, hipStream_t stream);
 
 // ---- errors ---------------------------------------------------------------------------------------------------------
 hy_status fail(hy_status code, const char* fmt, ...);

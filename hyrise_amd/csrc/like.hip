@@ -140,10 +140,11 @@ hy_status like_dictionary_tables(const hy_string_dictionary* dict) {
   const size_t chunk_bytes = align_up(sizeof(LikeChunk) * std::max<size_t>(1, dict->chunks.size()), 256);
   const size_t block_bytes = align_up(sizeof(LikeBlock) * std::max<size_t>(1, dict->blocks.size()), 256);
   const size_t offset_bytes = 8 * dict->word_offsets.size();
-  std::vector<char> image(chunk_bytes + block_bytes + offset_bytes, 0);
+  std::vector<char> image(chunk_bytes + block_bytes + 2 * offset_bytes, 0);
   if (!dict->chunks.empty()) std::memcpy(image.data(), dict->chunks.data(), sizeof(LikeChunk) * dict->chunks.size());
   if (!dict->blocks.empty()) std::memcpy(image.data() + chunk_bytes, dict->blocks.data(), sizeof(LikeBlock) * dict->blocks.size());
   std::memcpy(image.data() + chunk_bytes + block_bytes, dict->word_offsets.data(), offset_bytes);
+  std::memcpy(image.data() + chunk_bytes + block_bytes + offset_bytes, dict->entry_offsets.data(), offset_bytes);
   bind_thread_device();
   char* tables = nullptr;
   HY_HIP(hipMalloc(reinterpret_cast<void**>(&tables), image.size()));
@@ -151,6 +152,7 @@ hy_status like_dictionary_tables(const hy_string_dictionary* dict) {
   HY_HIP(hipMemcpy(tables, image.data(), image.size(), hipMemcpyHostToDevice));   // (complete before any stream of any thread reads it)
   dict->d_chunks = reinterpret_cast<LikeChunk*>(tables);
   dict->d_blocks = reinterpret_cast<LikeBlock*>(tables + chunk_bytes);
+  dict->d_entry_offsets = reinterpret_cast<uint64_t*>(tables + chunk_bytes + block_bytes + offset_bytes);
   dict->d_word_offsets = reinterpret_cast<uint64_t*>(tables + chunk_bytes + block_bytes);
   return HY_OK;
 }
@@ -221,6 +223,7 @@ hy_status hy_string_dictionary_create(const hy_string_dictionary_chunk* chunks, 
   dict->device = this_thread_device();
   dict->chunks.resize(n_chunks);
   dict->word_offsets.assign(size_t{n_chunks} + 1, 0);
+  dict->entry_offsets.assign(size_t{n_chunks} + 1, 0);
   dict->blocks.reserve(n_blocks);
   char* cursor = nullptr;
   if (mem == HY_MEM_HOST && allocation) {
@@ -237,6 +240,7 @@ hy_status hy_string_dictionary_create(const hy_string_dictionary_chunk* chunks, 
     d.string_length = chunk.offsets ? 0 : chunk.string_length;
     d.first_word = dict->word_offsets[c];
     dict->word_offsets[c + 1] = dict->word_offsets[c] + (uint64_t{n} + 63) / 64;
+    dict->entry_offsets[c + 1] = dict->entry_offsets[c] + n;
     for (uint32_t first = 0; first < n; first += LIKE_WG) dict->blocks.push_back(LikeBlock{c, first});
     if (!n) continue;
     if (mem == HY_MEM_DEVICE) {

@@ -2318,9 +2318,16 @@ struct DeviceLike {
   const LikeProgram* program;
 };
 
+// hy_table_scan_columns_strings: the dictionaries of the two (referenced) data columns; run_scan has string_order.hip rank them into its
+// scratch arena and scans the int32 stand-ins it describes there
+struct StringPair {
+  const hy_string_dictionary* left;
+  const hy_string_dictionary* right;
+};
+
 static hy_status run_scan(const hy_column* column, const hy_column* right, const hy_predicate* predicate, uint32_t condition,
                           const uint32_t* excluded, uint32_t n_excluded, hy_scan_result* result, const VisibilityArgs* visibility = nullptr,
-                          const InListArgs* in_list = nullptr, const DeviceLike* device_like = nullptr) {
+                          const InListArgs* in_list = nullptr, const DeviceLike* device_like = nullptr, const StringPair* strings = nullptr) {
   // Run-length / bit-packed segments are read in place by a ColumnVsValue / Between / IsNull / Like scan of the data column itself; the
   // two-column scan and the scan through reference segments read the decoded twins (hy_device.hpp) -- a reference segment's `ref`
   // already points at the twin's descriptors, so the jobs are prepared from the twin as well.
@@ -2361,10 +2368,43 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
             8 * set_offsets[n_data_chunks] + 4 * (size_t{n_data_chunks} + 1) + 8 * 256;
   }
   if (column->multi_chunk_reference) need += sizeof(hy_row_id) * (column->rows + 1) + 256;
+  uint32_t n_evens = 0;   // string columns: ranks | 0, 2, 4, ... | the descriptors of the stand-ins
+  if (strings) {
+    for (const LikeChunk& chunk : strings->right->chunks) n_evens = std::max(n_evens, chunk.n_entries);
+    need += 4 * (strings->left->entry_offsets[n_data_chunks] + n_evens + 8) + 2 * sizeof(DevSegment) * (size_t{n_data_chunks} + n_chunks + 2) + 6 * 256;
+  }
   if (host_result) need += 2 * sizeof(hy_row_id) * (column->rows + 1) + 3 * 8 * (size_t{n_chunks} + 2) + 4 * (size_t{n_chunks} + 1) + n_chunks + 8192;
   HY_TRY(sc.reserve(need + 16 * 256));
   ScanJob* d_jobs = carve<ScanJob>(sc, n_data_chunks + 1);
   uint32_t* d_overflow = sc.ticket + 16;   // persistent word, zero unless a scan overflowed (an internal error)
+  const DevSegment *left_segments = column->d_segments, *right_segments = right ? right->d_segments : nullptr;
+  if (strings) {   // queued in front of the scan on this stream: the ranks, then the descriptors that point at them
+    const hy_column* right_data = right->is_reference ? right->ref : right;
+    if (right->is_reference) HY_TRY(plain_column(right_data, &right_data));
+    StringTwins twins;
+    std::memset(&twins, 0, sizeof(twins));
+    int32_t* d_ranks = carve<int32_t>(sc, strings->left->entry_offsets[n_data_chunks] + 4);
+    twins.evens = carve<int32_t>(sc, size_t{n_evens} + 4);
+    twins.left_data_twin = carve<DevSegment>(sc, n_data_chunks + 1);
+    twins.right_data_twin = carve<DevSegment>(sc, n_data_chunks + 1);
+    if (column->is_reference) twins.left_reference_twin = carve<DevSegment>(sc, n_chunks + 1);
+    if (right->is_reference) twins.right_reference_twin = carve<DevSegment>(sc, n_chunks + 1);
+    if (!d_ranks || !twins.evens || !twins.left_data_twin || !twins.right_data_twin || (column->is_reference && !twins.left_reference_twin) ||
+        (right->is_reference && !twins.right_reference_twin)) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+    HY_TRY(string_order_launch(strings->left, strings->right, d_ranks, stream));
+    twins.left_data = data_column->d_segments;
+    twins.right_data = right_data->d_segments;
+    twins.left_reference = column->is_reference ? column->d_segments : nullptr;
+    twins.right_reference = right->is_reference ? right->d_segments : nullptr;
+    twins.entry_offsets = strings->left->d_entry_offsets;
+    twins.ranks = d_ranks;
+    twins.n_data_chunks = n_data_chunks;
+    twins.n_chunks = n_chunks;
+    twins.n_evens = n_evens;
+    HY_TRY(string_twins_launch(twins, stream));
+    left_segments = column->is_reference ? twins.left_reference_twin : twins.left_data_twin;
+    right_segments = right->is_reference ? twins.right_reference_twin : twins.right_data_twin;
+  }
   ScanKernel kernel = !right && column->has_compressed ? scan_slices<8> : scan_slices<0>;
   if (!right && column->stream_width == 16) kernel = column->has_sorted ? scan_slices<16, true> : scan_slices<16>;   // bit-packed vectors of at most 16 bits
   else if (!right && column->stream_width == 1) kernel = column->has_sorted ? scan_slices<1, true> : scan_slices<1>;
@@ -2484,8 +2524,8 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
     HY_TRY(sc.begin_launch(column->n_parts, 0));
     ScanArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.segments = column->d_segments;
-    a.right = right ? right->d_segments : nullptr;
+    a.segments = left_segments;
+    a.right = right_segments;
     a.slices = column->d_slices;
     a.jobs = d_jobs;
     a.n_slices = column->n_slices;
@@ -2520,14 +2560,14 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
     // ColumnVsColumn over two data columns of one 4-byte type whose segments are all W-byte vectors: the two-stream kernel, the chunks'
     // dictionaries staged in LDS when the largest pair fits 48 KB (scan_two_columns)
     uint32_t two_width = right && !column->is_reference && !right->is_reference && column->stream_width == right->stream_width && column->data_type == right->data_type &&
-                                 (column->data_type == HY_TYPE_INT || column->data_type == HY_TYPE_FLOAT) && !column->has_compressed && !right->has_compressed &&
+                                 (column->data_type == HY_TYPE_INT || column->data_type == HY_TYPE_FLOAT || strings) && !column->has_compressed && !right->has_compressed &&
                                  option(HY_OPT_SCAN_TWO_COLUMNS)
                              ? column->stream_width : 0;
     uint32_t dict_words = 0;
     for (uint32_t c = 0; c < n_chunks && two_width; ++c) {   // every segment: a W-byte vector of 4-byte values (stream_width says W bytes and aligned)
       for (const hy_segment* seg : {&column->host_segments[c], &right->host_segments[c]}) {
         const bool shape = seg->encoding == HY_ENC_UNENCODED ? two_width == 4 : (seg->encoding == HY_ENC_DICTIONARY || seg->encoding == HY_ENC_FRAME_OF_REFERENCE) && seg->width == two_width;
-        if (!shape || (seg->data_type != HY_TYPE_INT && seg->data_type != HY_TYPE_FLOAT)) two_width = 0;
+        if (!shape || (seg->data_type != HY_TYPE_INT && seg->data_type != HY_TYPE_FLOAT && !strings)) two_width = 0;   // (string segments: scanned as their int32 stand-ins)
         if (seg->encoding == HY_ENC_DICTIONARY) dict_words = std::max(dict_words, seg->aux_size);
       }
     }
@@ -2688,8 +2728,51 @@ hy_status hy_table_scan_columns(const hy_column* left, const hy_column* right, u
   for (uint32_t c = 0; c < left->n_chunks; ++c) {
     if (left->host_segments[c].size != right->host_segments[c].size) return fail(HY_ERR_INVALID, "chunk %u: segment sizes differ", c);
   }
-  if (left->data_type == HY_TYPE_STRING || right->data_type == HY_TYPE_STRING) return fail(HY_ERR_UNSUPPORTED, "string ColumnVsColumn scans stay on the CPU path");
+  if (left->data_type == HY_TYPE_STRING || right->data_type == HY_TYPE_STRING)
+    return fail(HY_ERR_UNSUPPORTED, "string ColumnVsColumn scans need the columns' dictionaries: hy_table_scan_columns_strings");
   return run_scan(left, right, nullptr, condition, nullptr, 0, result);
+}
+
+hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_dictionary* left_dict, const hy_column* right, const hy_string_dictionary* right_dict,
+                                        uint32_t condition, hy_scan_result* result) {
+  const char* name = "hy_table_scan_columns_strings";
+  if (!left || !left_dict || !right || !right_dict || !result) return fail(HY_ERR_INVALID, "%s: null argument", name);
+  HY_TRY(on_this_device(left, name));
+  HY_TRY(on_this_device(right, name));
+  if (left->is_mvcc || right->is_mvcc || (left->ref && left->ref->is_mvcc) || (right->ref && right->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
+  if (condition > HY_PRED_GREATER_THAN_EQUALS) return fail(HY_ERR_INVALID, "ColumnVsColumn supports binary comparisons only");
+  if (left->n_chunks != right->n_chunks) return fail(HY_ERR_INVALID, "columns of one table must have the same chunk count");
+  for (uint32_t c = 0; c < left->n_chunks; ++c) {
+    if (left->host_segments[c].size != right->host_segments[c].size) return fail(HY_ERR_INVALID, "chunk %u: segment sizes differ", c);
+  }
+  // column_vs_column_table_scan_impl.cpp:153-155
+  if ((left->data_type != HY_TYPE_STRING || right->data_type != HY_TYPE_STRING) && left->n_chunks)
+    return fail(HY_ERR_INVALID, "%s: trying to compare strings and non-strings (column types %u and %u)", name, left->data_type, right->data_type);
+  if (left->is_reference != right->is_reference) return fail(HY_ERR_INVALID, "%s: a data column against a reference column", name);
+  // (the ranks pair data chunk k with data chunk k: a table's reference columns hold the same PosList per chunk, each column its own copy)
+  for (uint32_t c = 0; c < left->n_chunks && left->is_reference; ++c) {
+    const hy_segment &l = left->host_segments[c], &r = right->host_segments[c];
+    if (l.ref_chunk_id != r.ref_chunk_id || !l.data != !r.data) return fail(HY_ERR_INVALID, "%s: chunk %u: the reference columns hold different PosLists", name, c);
+  }
+  const hy_column* data_columns[2] = {left->is_reference ? left->ref : left, right->is_reference ? right->ref : right};
+  const hy_string_dictionary* dicts[2] = {left_dict, right_dict};
+  for (int side = 0; side < 2; ++side) {
+    const hy_column* data_column = data_columns[side];
+    const uint32_t n_data_chunks = data_column ? data_column->n_chunks : 0;
+    for (uint32_t c = 0; c < n_data_chunks; ++c) {
+      if (data_column->host_segments[c].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "%s: unencoded string segments stay on the CPU path", name);
+    }
+    if (dicts[side]->device != left->device) return fail(HY_ERR_INVALID, "%s: a dictionary lives on device %d, the columns on device %d", name, dicts[side]->device, left->device);
+    if (dicts[side]->n_chunks != n_data_chunks) return fail(HY_ERR_INVALID, "%s: the %s dictionary has %u chunks, the data column %u", name, side ? "right" : "left", dicts[side]->n_chunks, n_data_chunks);
+    for (uint32_t c = 0; c < n_data_chunks; ++c) {
+      if (dicts[side]->chunks[c].n_entries != data_column->host_segments[c].aux_size)
+        return fail(HY_ERR_INVALID, "%s: chunk %u: the %s dictionary has %u entries, the segment's has %u", name, c, side ? "right" : "left", dicts[side]->chunks[c].n_entries,
+                    data_column->host_segments[c].aux_size);
+    }
+  }
+  HY_TRY(string_order_check(left_dict, right_dict, name));
+  const StringPair strings{left_dict, right_dict};
+  return run_scan(left, right, nullptr, condition, nullptr, 0, result, nullptr, nullptr, nullptr, &strings);
 }
 
 hy_status hy_poslist_translate(const hy_column* scanned, const hy_scan_result* result, uint32_t layout, hy_row_id* out, uint64_t capacity, uint64_t* n_out) {

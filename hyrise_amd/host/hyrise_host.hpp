@@ -1249,7 +1249,30 @@ class TableScan : public AbstractReadOnlyOperator {
     if (_predicate) {
       if (!scan_expression(in_table, &result, counts, states)) on_device.reset();   // (a constant predicate: counts and states say all or nothing, no RowIDs are needed)
     } else if (_right_column_id) {
-      check_status(hy_table_scan_columns(column->handle, device_column(in_table, *_right_column_id)->handle, static_cast<uint32_t>(_condition), &result));
+      const bool left_is_string = in_table->column_data_type(_column_id) == DataType::String;
+      const bool right_is_string = in_table->column_data_type(*_right_column_id) == DataType::String;
+      // column_vs_column_table_scan_impl.cpp:153-155
+      Assert(left_is_string == right_is_string, "Trying to compare strings and non-strings");
+      const auto right_column = device_column(in_table, *_right_column_id);
+      if (left_is_string && chunk_count) {
+        // Two string columns: their dictionaries are ordered against each other where they live, in HBM, and the row pass is the numeric
+        // one (hy_table_scan_columns_strings).  The dictionaries are the data table's, as for LIKE.
+        auto data_table = in_table;
+        auto left_data_column_id = _column_id, right_data_column_id = *_right_column_id;
+        if (in_table->type() == TableType::References) {
+          const auto left_ref = std::static_pointer_cast<ReferenceSegment>(in_table->get_chunk(0)->get_segment(_column_id));
+          const auto right_ref = std::static_pointer_cast<ReferenceSegment>(in_table->get_chunk(0)->get_segment(*_right_column_id));
+          Assert(left_ref->referenced_table() == right_ref->referenced_table(), "string ColumnVsColumn scans over columns of two referenced tables stay on the CPU path");
+          data_table = left_ref->referenced_table();
+          left_data_column_id = left_ref->referenced_column_id();
+          right_data_column_id = right_ref->referenced_column_id();
+        }
+        const auto left_dictionary = device_string_dictionary(data_table, left_data_column_id);
+        const auto right_dictionary = device_string_dictionary(data_table, right_data_column_id);
+        check_status(hy_table_scan_columns_strings(column->handle, left_dictionary->handle, right_column->handle, right_dictionary->handle, static_cast<uint32_t>(_condition), &result));
+      } else {
+        check_status(hy_table_scan_columns(column->handle, right_column->handle, static_cast<uint32_t>(_condition), &result));
+      }
     } else {
       hy_predicate predicate{};
       predicate.condition = static_cast<uint32_t>(_condition);

@@ -293,6 +293,40 @@ def table_scan_columns(left, right, condition, capacity=None):
     return result
 
 
+def string_dictionary_ranks(left_dict, right_dict):
+    """hy_string_dictionary_ranks with a host result over two storage.DeviceStringDictionary -> per chunk the int32 ranks of the left
+    chunk's entries against the right chunk's: 2 * lower_bound, minus one where the right dictionary does not hold the entry."""
+    lib = abi.load_library()
+    total = sum(left_dict.n_entries)
+    ranks = np.zeros(max(1, total), dtype=np.int32)
+    abi.check(lib.hy_string_dictionary_ranks(left_dict.handle, right_dict.handle, abi.MEM_HOST, ranks.ctypes.data))
+    bounds = np.concatenate([[0], np.cumsum(left_dict.n_entries, dtype=np.int64)]).astype(np.int64)
+    return [ranks[int(bounds[c]):int(bounds[c + 1])] for c in range(left_dict.n_chunks)]
+
+
+def table_scan_columns_strings(left, left_dict, right, right_dict, condition, flags=0, device=False):
+    """hy_table_scan_columns_strings: `left <condition> right` over two string columns of one table and their dictionaries (for reference
+    columns: the referenced data columns') -> HostScanResult like table_scan_columns, or with device=True the chunk-region result in
+    device memory as table_scan_like returns it."""
+    lib = abi.load_library()
+    n_chunks, rows = left.n_chunks, left.rows
+    if not device:
+        result = HostScanResult(n_chunks, rows, flags)
+        abi.check(lib.hy_table_scan_columns_strings(left.handle, left_dict.handle, right.handle, right_dict.handle, condition, C.byref(result.c)))
+        return result
+    import torch
+    matches = torch.zeros((max(1, rows) + 2, 2), dtype=torch.int32, device="cuda")   # (16 bytes of slack behind the last RowID)
+    offsets = torch.zeros(n_chunks + 1, dtype=torch.int64, device="cuda")
+    counts = torch.zeros(max(1, n_chunks), dtype=torch.int32, device="cuda")
+    chunk_state = torch.zeros(max(1, n_chunks), dtype=torch.uint8, device="cuda")
+    r = abi.ScanResult()
+    r.mem, r.flags = abi.MEM_DEVICE, flags | abi.SCAN_CHUNK_REGIONS
+    r.matches, r.capacity = matches.data_ptr(), rows
+    r.offsets, r.counts, r.chunk_state = offsets.data_ptr(), counts.data_ptr(), chunk_state.data_ptr()
+    abi.check(lib.hy_table_scan_columns_strings(left.handle, left_dict.handle, right.handle, right_dict.handle, condition, C.byref(r)))
+    return matches[:max(1, rows)], offsets, counts[:n_chunks], chunk_state[:n_chunks]
+
+
 def validate(mvcc, our_tid, snapshot_commit_id, can_use_chunk_shortcut=True, flags=0):
     """Validate (MVCC visibility) over a DeviceColumn of MVCC segments or of reference segments into one."""
     lib = abi.load_library()

@@ -236,7 +236,8 @@ hy_status hy_profile_read(float* total_milliseconds, uint32_t* launches);
 /* The same per kernel, without resetting: an operator chain (bench.py's TableScan + JoinHash step) reads the time of each of its
  * timed kernels separately before hy_profile_read() clears the session. */
 enum { HY_KERNEL_OTHER = 0, HY_KERNEL_SCAN = 1, HY_KERNEL_JOIN_PROBE = 2, HY_KERNEL_JOIN_COUNT = 3, HY_KERNEL_JOIN_BUILD = 4, HY_KERNEL_AGGREGATE = 5,
-       HY_KERNEL_PROJECTION = 6, HY_KERNEL_LIKE = 7 /* like_match, the dictionary matcher */, HY_KERNEL_KINDS = 8 };
+       HY_KERNEL_PROJECTION = 6, HY_KERNEL_LIKE = 7 /* like_match, the dictionary matcher */,
+       HY_KERNEL_STRING_RANK = 8 /* string_rank, one string dictionary ordered against another */, HY_KERNEL_KINDS = 9 };
 hy_status hy_profile_read_kernel(uint32_t kernel, float* total_milliseconds, uint32_t* launches);
 /* What such an event pair measures beyond the kernel itself (the pair is stamped from the dispatch packet): the elapsed time of an
  * empty kernel, median of 32 launches, measured once per process.  A profiler's per-kernel duration is shorter by about this much. */
@@ -420,7 +421,8 @@ hy_status hy_table_scan_in_list(const hy_column* column, const hy_in_list* list,
  * (HY_TYPE_STRING) is dropped as well; a string column takes no hy_value list: HY_ERR_INVALID.  Pure host arithmetic. */
 hy_status hy_in_list_cast(uint32_t column_type, const uint32_t* literal_types, const hy_value* literals, uint32_t n, hy_value* out,
                           uint32_t* n_out, uint32_t* has_null);
-/* ColumnVsColumn (column_vs_column_table_scan_impl.cpp:36-187): left <condition> right, both columns of one table. */
+/* ColumnVsColumn (column_vs_column_table_scan_impl.cpp:36-187): left <condition> right, both columns of one table.  String columns:
+ * HY_ERR_UNSUPPORTED here -- the call has no dictionaries to read; hy_table_scan_columns_strings takes them. */
 hy_status hy_table_scan_columns(const hy_column* left, const hy_column* right, uint32_t condition,
                                 hy_scan_result* result);
 
@@ -477,6 +479,40 @@ hy_status hy_like_matches(const hy_string_dictionary* dict, const char* pattern,
 hy_status hy_table_scan_like(const hy_column* column, const hy_string_dictionary* dict, const char* pattern, uint32_t pattern_bytes,
                              uint32_t condition, uint32_t column_is_nullable, const uint32_t* excluded_chunks, uint32_t n_excluded,
                              hy_scan_result* result);
+
+/* ---- ColumnVsColumn on two string columns (column_vs_column_table_scan_impl.cpp:145-187 with pmr_string on both sides) ----------------
+ * Per chunk the left column's dictionary L is ordered against the right column's R (both sorted and duplicate-free, as DictionarySegment
+ * keeps them), n_r = R's entry count:
+ *     lo(v)   = number of right entries < L[v]                     (lower_bound)
+ *     eq(v)   = lo(v) < n_r && R[lo(v)] == L[v]
+ *     rank(v) = 2 * lo(v) - (eq(v) ? 0 : 1)                        (int32_t; -1 for an entry below every right entry that equals none)
+ * The rank of right entry r is 2 * r, and L[v] <cond> R[r] holds iff rank(v) <cond> 2 * r for each of the six comparisons: with eq(v),
+ * L[v] = R[lo] and 2lo against 2r decides; without, R[lo - 1] < L[v] < R[lo] and the odd 2lo - 1 lies strictly between 2(lo - 1) and 2lo.
+ * Order is std::string's: bytes compared as unsigned, the shorter string first when it is the other's prefix; a '\0' inside an entry of
+ * the offsets layout is data, an entry of the fixed-length layout ends at strnlen(slot, string_length).  A chunk without entries on
+ * either side is legal (every lo is 0, eq false).  A right dictionary that is not sorted gives unspecified ranks; no byte outside the two
+ * chunks' chars is read even then (entries are read exactly, the 16 bytes of slack are not touched).
+ *
+ * hy_string_dictionary_ranks: one launch for all chunks of the pair.  ranks: the sum of left's n_entries int32_t; chunk c's ranks start at
+ * the sum of left's n_entries before c.  mem == HY_MEM_DEVICE: ranks stay in the caller's device buffer (on 4 bytes, otherwise
+ * HY_ERR_INVALID), complete in the order of the calling thread's stream, no host round trip.  mem == HY_MEM_HOST: copied back; the call
+ * returns when they are there.  HY_ERR_INVALID: dictionaries with different chunk counts, on different devices, or not on the calling
+ * thread's device.  HY_ERR_UNSUPPORTED: a right chunk of 2^30 entries or more (2 * lo would overflow).  All refusals come before any launch. */
+hy_status hy_string_dictionary_ranks(const hy_string_dictionary* left, const hy_string_dictionary* right, uint32_t mem, int32_t* ranks);
+/* hy_table_scan_columns for two string columns of one table: the ranking above runs on the calling thread's stream into the scratch arena,
+ * both columns get an int32 dictionary stand-in for the length of the call (the ranks on the left, 0, 2, 4, ... on the right, over the
+ * caller's attribute vectors and with the caller's NULL value ids -- for reference columns behind the same PosLists), and the row pass is
+ * hy_table_scan_columns' own.  Result contract, flags, alignment rules and `mem` handling: hy_table_scan_columns', bit for bit.  The six
+ * binary conditions only; a NULL on either side matches nothing.  Both columns are data columns, or both are reference columns whose
+ * chunks hold the same PosLists (one reference table's columns: the caller's guarantee, as for hy_table_scan_columns); the dictionaries belong to the referenced data columns.  Passing the same column and
+ * dictionary on both sides is legal.
+ * HY_ERR_INVALID: a column that is no string column ("Trying to compare strings and non-strings"); a data column against a reference
+ * column; a dictionary whose chunk count or any n_entries differs from its data column's
+ * dictionary segments (aux_size); the refusals of hy_table_scan_columns and of hy_string_dictionary_ranks.  HY_ERR_UNSUPPORTED: unencoded
+ * or LZ4 string segments, a right chunk of 2^30 entries or more.  Nothing is launched or written in any of these cases.
+ * Ranks are not kept between calls. */
+hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_dictionary* left_dict, const hy_column* right,
+                                        const hy_string_dictionary* right_dict, uint32_t condition, hy_scan_result* result);
 
 /* ---- Validate (replaces Validate::_on_execute / _validate_chunks, validate.cpp:32-55,87-314) ----
  * The MVCC visibility filter that sits in front of every TableScan of an SQL-driven plan.  The table's MvccData
