@@ -243,6 +243,7 @@ hy_status string_twins_launch(const StringTwins& twins, hipStream_t stream);
 
 // ---- errors ---------------------------------------------------------------------------------------------------------
 hy_status fail(hy_status code, const char* fmt, ...);
+void clear_error();   // a refusal that the caller answered itself: hy_last_error is empty again
 hy_status on_this_device(const hy_column* column, const char* entry_point);   // runtime.hip: the calling thread's device holds the column
 hy_status plain_column(const hy_column* column, const hy_column** plain);      // runtime.hip: `column` itself, or its decoded twin (see hy_column::plain)
 #define HY_HIP(expr)                                                                                      \
@@ -297,6 +298,28 @@ inline T* carve(Scratch& s, size_t count) {
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// A bump allocator of 256-byte aligned device blocks over one of three backers: the thread's Scratch, a caller's block (whose size is the
+// caller's promise), or no memory at all -- then it only counts, and `used` is what the same takes need: sizing is a dry run of the layout.
+// A block that does not fit is recorded, not returned: one check of `failed` behind the last take.
+struct Carver {
+  Scratch* arena = nullptr;
+  char* block = nullptr;
+  size_t used = 0;       // bytes from the first block's begin to the last block's end
+  bool failed = false;
+  void* take_bytes(size_t bytes) {
+    const size_t offset = align_up(used, 256);
+    used = offset + bytes;
+    if (arena) {
+      void* at = arena->carve(bytes);
+      failed |= at == nullptr;
+      return at;
+    }
+    return block ? block + offset : nullptr;
+  }
+  template <typename T>
+  T* take(size_t count) { return static_cast<T*>(take_bytes(sizeof(T) * (count ? count : 1))); }
+};
 
 
 // Temporary device buffers come from a per-thread pool of power-of-two blocks that is reused across calls in stream
@@ -371,8 +394,22 @@ hy_status star_all_rows_of(const hy_column* column, DeviceBuffer& rows);   // ev
 // scan.hip: the kernels of hy_poslist_translate queued on the current stream, nothing read back -- dense_offsets: [n_chunks + 1] device words,
 // the last of them the number of RowIDs written
 hy_status poslist_translate_queued(const hy_column* scanned, const hy_scan_result* result, uint32_t layout, hy_row_id* out, uint64_t capacity, uint64_t* dense_offsets);
+// scan.hip: the chunk regions a scan with a HY_MEM_HOST result writes in device memory, and what regions_to_host_result takes behind them
+// (`total` RowIDs: at most the scanned column's rows) -- laid out from the caller's Carver, for sizing and for carving alike
+struct ScanRegions {
+  hy_row_id* matches;
+  uint64_t* offsets;
+  uint32_t* counts;
+  uint8_t* state;
+};
+struct DenseRegions {
+  uint64_t* offsets;
+  hy_row_id* matches;
+};
+void scan_regions_layout(Carver& carver, uint32_t n_chunks, uint64_t rows, ScanRegions& regions);
+void dense_regions_layout(Carver& carver, uint32_t n_chunks, uint64_t total, DenseRegions& dense);
 // scan.hip: a scan's chunk regions in device memory -> the caller's HY_MEM_HOST result (counts, chunk states, the regions packed back to back through the
-// thread's scratch arena, behind what the scan carved from it).  d_overflow: the scan's overflow word, or nullptr
+// thread's scratch arena, behind what the scan carved from it: dense_regions_layout).  d_overflow: the scan's overflow word, or nullptr
 hy_status regions_to_host_result(const hy_row_id* d_matches, const uint64_t* d_offsets, const uint32_t* d_counts, const uint8_t* d_state, uint32_t* d_overflow, uint32_t n_chunks,
                                  bool materialize_all, hy_scan_result* result);
 

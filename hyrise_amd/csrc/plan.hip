@@ -381,6 +381,7 @@ static hy_status star_join(const char* who, bool where, const hy_star_dimension_
       char* staging = storage.as<char>() + jobs_bytes;
       const hy_status prepared = filter.in_list ? prepare_scan_jobs(column, filter.in_list, storage.as<ScanJob>(), staging) : prepare_scan_jobs(column, &filter.predicate, storage.as<ScanJob>(), staging);
       if (prepared == HY_OK) *jobs = storage.as<ScanJob>();
+      else clear_error();   // (answered here: the filter is scanned, and that scan reports what it refuses)
       return HY_OK;
     };
     bool shape_ok = true;

@@ -51,6 +51,7 @@ hy_status fail(hy_status code, const char* fmt, ...) {
   t_error = buffer;
   return code;
 }
+void clear_error() { t_error.clear(); }
 
 // The device hy_init chose, for every thread of the process: hipSetDevice only binds the CALLING thread, and the operators
 // run on Hyrise's scheduler workers (abstract_scheduler.cpp:53-63), not on the thread that loaded the plugin.  Every thread

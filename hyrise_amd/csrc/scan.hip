@@ -2101,53 +2101,46 @@ static hy_status cached_scan_jobs(const hy_column* column, const PredicateArgs& 
   return HY_OK;
 }
 
-size_t scan_jobs_staging_bytes(const hy_column* column, const hy_predicate* predicate) {
-  size_t bytes = 4 * 256 + 9 * (size_t{column->n_chunks} + 64);   // prepare_jobs' status word | the per-chunk arrays, 256-byte aligned
-  if (predicate->match_words && predicate->match_word_offsets) bytes += 2 * 256 + 8 * (size_t{column->n_chunks} + 2) + 8 * (predicate->match_word_offsets[column->n_chunks] + 2);
-  return bytes;
+// ---- refusals the scan entry points share: all of them come before the first launch ----------------------------------------------------
+static hy_status refuse_mvcc(const hy_column* column) {
+  return column->is_mvcc || (column->ref && column->ref->is_mvcc) ? fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only") : HY_OK;
 }
-
-// (what run_scan does for its own predicate, for callers that evaluate the jobs themselves)
-hy_status prepare_scan_jobs(const hy_column* column, const hy_predicate* predicate, ScanJob* jobs, void* staging) {
-  if (column->is_reference || column->is_mvcc) return fail(HY_ERR_INVALID, "prepare_scan_jobs: data columns only");
-  HY_TRY(validate_predicate(column, predicate));
-  const uint32_t n_chunks = column->n_chunks;
-  hipStream_t stream = current_stream();
-  PredicateArgs pa;
-  std::memset(&pa, 0, sizeof(pa));
-  pa.condition = predicate->condition;
-  pa.value_type = predicate->value_type;
-  pa.value = predicate->value;
-  pa.value2 = predicate->value2;
-  pa.column_is_nullable = predicate->column_is_nullable;
-  pa.no_ranges = 1;   // (fused_rows evaluates JOB_SCAN / JOB_ALL / JOB_NONE)
-  char* cursor = static_cast<char*>(staging) + 256;
-  auto stage = [&](const void* host, size_t bytes, const void** dev) -> hy_status {
-    *dev = nullptr;
-    if (!host) return HY_OK;
-    if (bytes) HY_HIP(hipMemcpyAsync(cursor, host, bytes, hipMemcpyHostToDevice, stream));
-    *dev = cursor;
-    cursor += align_up(bytes ? bytes : 4, 256);
-    return HY_OK;
-  };
-  const void* d;
-  HY_TRY(stage(predicate->per_chunk_lower, 4 * size_t{n_chunks}, &d)); pa.per_chunk_lower = static_cast<const uint32_t*>(d);
-  HY_TRY(stage(predicate->per_chunk_upper, 4 * size_t{n_chunks}, &d)); pa.per_chunk_upper = static_cast<const uint32_t*>(d);
-  HY_TRY(stage(predicate->per_chunk_found, size_t{n_chunks}, &d)); pa.per_chunk_found = static_cast<const uint8_t*>(d);
-  if (predicate->match_words && predicate->match_word_offsets) {
-    const uint64_t total_words = predicate->match_word_offsets[n_chunks];
-    HY_TRY(stage(predicate->match_word_offsets, 8 * (size_t{n_chunks} + 1), &d)); pa.match_word_offsets = static_cast<const uint64_t*>(d);
-    HY_TRY(stage(predicate->match_words, 8 * (total_words ? total_words : 1), &d)); pa.match_words = static_cast<const uint64_t*>(d);
+static hy_status check_excluded(const hy_column* column, const uint32_t* excluded, uint32_t n_excluded, const char* entry_point) {
+  if (n_excluded && !excluded) return fail(HY_ERR_INVALID, "%s: excluded chunk list missing", entry_point);
+  if (n_excluded && column->is_reference) return fail(HY_ERR_INVALID, "excluded chunks apply to data tables only");
+  for (uint32_t i = 0; i < n_excluded; ++i) {
+    if (excluded[i] >= column->n_chunks) return fail(HY_ERR_INVALID, "excluded chunk id %u out of range", excluded[i]);
   }
-  if (n_chunks) hipLaunchKernelGGL(prepare_jobs, dim3(n_chunks), dim3(256), 0, stream, column->d_segments, n_chunks, pa, jobs, static_cast<uint32_t*>(staging));
+  return HY_OK;
+}
+static hy_status check_reorder_counts(const hy_column* column, const hy_scan_result* result) {
+  if (!column->multi_chunk_reference || result->mem != HY_MEM_DEVICE || result->counts) return HY_OK;
+  return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
+}
+static hy_status check_column_pair(const hy_column* left, const hy_column* right, uint32_t condition) {   // ColumnVsColumn: two columns of one table
+  HY_TRY(refuse_mvcc(left));
+  HY_TRY(refuse_mvcc(right));
+  if (condition > HY_PRED_GREATER_THAN_EQUALS) return fail(HY_ERR_INVALID, "ColumnVsColumn supports binary comparisons only");
+  if (left->n_chunks != right->n_chunks) return fail(HY_ERR_INVALID, "columns of one table must have the same chunk count");
+  for (uint32_t c = 0; c < left->n_chunks; ++c) {
+    if (left->host_segments[c].size != right->host_segments[c].size) return fail(HY_ERR_INVALID, "chunk %u: segment sizes differ", c);
+  }
   return HY_OK;
 }
 
-hy_status prepare_visibility_scan_jobs(const hy_column* mvcc, uint32_t our_tid, uint32_t snapshot_commit_id, uint32_t can_use_chunk_shortcut, ScanJob* jobs, void* staging) {
-  if (!mvcc || !mvcc->is_mvcc || mvcc->is_reference) return fail(HY_ERR_INVALID, "a Validate filter needs the table's column of HY_ENC_MVCC segments");
-  const uint32_t n_chunks = mvcc->n_chunks;
-  if (n_chunks) hipLaunchKernelGGL(prepare_visibility_jobs, dim3((n_chunks + 255) / 256), dim3(256), 0, current_stream(), mvcc->d_segments, n_chunks, our_tid, snapshot_commit_id, can_use_chunk_shortcut,
-                                   jobs, static_cast<uint32_t*>(staging));
+// `dict` is the string dictionary of `column`'s data column, chunk by chunk, on `column`'s device; `which`: "", "left " or "right "
+static hy_status check_dictionary(const hy_string_dictionary* dict, const hy_column* column, const char* which, const char* entry_point) {
+  const hy_column* data_column = column->is_reference ? column->ref : column;
+  const uint32_t n_data_chunks = data_column ? data_column->n_chunks : 0;
+  if (dict->device != column->device) return fail(HY_ERR_INVALID, "%s: the %sdictionary lives on device %d, the column on device %d", entry_point, which, dict->device, column->device);
+  for (uint32_t c = 0; c < n_data_chunks; ++c) {
+    if (data_column->host_segments[c].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "%s: unencoded string segments stay on the CPU path", entry_point);
+  }
+  if (dict->n_chunks != n_data_chunks) return fail(HY_ERR_INVALID, "%s: the %sdictionary has %u chunks, the data column %u", entry_point, which, dict->n_chunks, n_data_chunks);
+  for (uint32_t c = 0; c < n_data_chunks; ++c) {
+    if (dict->chunks[c].n_entries != data_column->host_segments[c].aux_size)
+      return fail(HY_ERR_INVALID, "%s: chunk %u: the %sdictionary has %u entries, the segment's has %u", entry_point, c, which, dict->chunks[c].n_entries, data_column->host_segments[c].aux_size);
+  }
   return HY_OK;
 }
 
@@ -2163,7 +2156,7 @@ struct InListArgs {   // hy_table_scan_in_list, checked: `predicate` carries HY_
 
 // hy_table_scan_in_list's checks of `list` against `column` (a data or reference column), and the list as sorted keys
 static hy_status check_in_list(const hy_column* column, const hy_in_list* list, InListArgs& args) {
-  if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
+  HY_TRY(refuse_mvcc(column));
   if (list->n_values == 0) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: an empty list has a constant result; the caller answers it");
   if (list->n_values > HY_MAX_IN_LIST) return fail(HY_ERR_UNSUPPORTED, "hy_table_scan_in_list: %u elements, at most %u are evaluated here (longer lists are semi joins)", list->n_values, HY_MAX_IN_LIST);
   if (list->value_type != column->data_type) return fail(HY_ERR_INVALID, "list type %u differs from column type %u: use hy_in_list_cast first", list->value_type, column->data_type);
@@ -2224,63 +2217,214 @@ static std::vector<uint64_t> value_id_set_offsets(const hy_column* data_column) 
   return offsets;
 }
 
-// (what run_scan does for a list, for callers that evaluate the jobs themselves: the keys, the value-id bitmaps and the jobs live in `staging`)
+// hy_table_scan_like: the dictionary and the tokenised pattern whose bitmaps the matcher (like.hip) writes where prepare_jobs reads them
+struct DeviceLike {
+  const hy_string_dictionary* dict;
+  const LikeProgram* program;
+};
+
+// hy_table_scan_columns_strings: the dictionaries of the two (referenced) data columns; string_order.hip ranks them and the scan reads the
+// int32 stand-ins described beside the ranks
+struct StringPair {
+  const hy_string_dictionary* left;
+  const hy_string_dictionary* right;
+};
+
+// ---- job sources ----------------------------------------------------------------------------------------------------------------------
+// A predicate (with the caller's bitmaps, with the device LIKE matcher's, or plain), an IN list and Validate each fill the per-chunk job
+// table.  Every source has a *_layout that takes its device blocks from a Carver and a *_queue that queues its copies and launches into
+// those blocks; sizing runs the same layout against a Carver without memory.  run_scan carves from the thread's Scratch, the fused
+// consumers (prepare_scan_jobs) from their own staging block.
+static void queue_prepare_jobs(const hy_column* data_column, const PredicateArgs& pa, ScanJob* jobs, uint32_t* overflow, hipStream_t stream) {
+  const uint32_t n_chunks = data_column ? data_column->n_chunks : 0;
+  if (n_chunks) hipLaunchKernelGGL(prepare_jobs, dim3(n_chunks), dim3(256), 0, stream, data_column->d_segments, n_chunks, pa, jobs, overflow);
+}
+
+struct PredicateBlocks { uint32_t *lower, *upper; uint8_t* found; uint64_t *word_offsets, *words; };
+
+static bool has_host_bitmaps(const hy_predicate* p) { return p->match_words && p->match_word_offsets; }
+
+static void predicate_layout(Carver& carver, const hy_predicate* p, uint32_t n_chunks, const DeviceLike* like, PredicateBlocks& b) {
+  b = PredicateBlocks{};
+  if (p->per_chunk_lower) b.lower = carver.take<uint32_t>(n_chunks);
+  if (p->per_chunk_upper) b.upper = carver.take<uint32_t>(n_chunks);
+  if (p->per_chunk_found) b.found = carver.take<uint8_t>(n_chunks);
+  if (like) {   // the matcher's words; their offsets are the dictionary's
+    b.words = carver.take<uint64_t>(like->dict->word_offsets[n_chunks] + 1);
+  } else if (has_host_bitmaps(p)) {
+    b.word_offsets = carver.take<uint64_t>(size_t{n_chunks} + 1);
+    b.words = carver.take<uint64_t>(p->match_word_offsets[n_chunks]);
+  }
+}
+
+// pa: the predicate as prepare_jobs takes it (no_ranges and materialize_all stay the caller's)
+static hy_status predicate_queue(const hy_predicate* p, uint32_t n_chunks, const DeviceLike* like, const PredicateBlocks& b, hipStream_t stream, PredicateArgs& pa) {
+  auto upload = [&](void* device, const void* host, size_t bytes) -> hy_status {
+    if (host && bytes) HY_HIP(hipMemcpyAsync(device, host, bytes, hipMemcpyHostToDevice, stream));
+    return HY_OK;
+  };
+  pa.condition = p->condition;
+  pa.value_type = p->value_type;
+  pa.value = p->value;
+  pa.value2 = p->value2;
+  pa.column_is_nullable = p->column_is_nullable;
+  HY_TRY(upload(b.lower, p->per_chunk_lower, 4 * size_t{n_chunks}));
+  HY_TRY(upload(b.upper, p->per_chunk_upper, 4 * size_t{n_chunks}));
+  HY_TRY(upload(b.found, p->per_chunk_found, size_t{n_chunks}));
+  pa.per_chunk_lower = b.lower;
+  pa.per_chunk_upper = b.upper;
+  pa.per_chunk_found = b.found;
+  if (like) {   // the bitmaps are made where they are read, in front of prepare_jobs on this stream
+    HY_TRY(like_launch(like->dict, *like->program, b.words, stream));
+    pa.match_words = b.words;
+    pa.match_word_offsets = like->dict->d_word_offsets;
+  } else if (has_host_bitmaps(p)) {
+    HY_TRY(upload(b.word_offsets, p->match_word_offsets, 8 * (size_t{n_chunks} + 1)));
+    HY_TRY(upload(b.words, p->match_words, 8 * p->match_word_offsets[n_chunks]));
+    pa.match_word_offsets = b.word_offsets;
+    pa.match_words = b.words;
+  }
+  return HY_OK;
+}
+
+// IN / NOT IN: keys | values | the caller's value ids | bitmap offsets | bitmaps + "any" words of the dictionary chunks (one zeroed block)
+struct ListBlocks {
+  uint64_t* keys; hy_value* values; uint32_t* value_ids; uint64_t* set_offsets; char* zeroed;
+  size_t any_at, zeroed_bytes;   // the "any" words begin `any_at` bytes into the zeroed block
+};
+
+static void list_layout(Carver& carver, const hy_in_list* list, uint32_t n_chunks, size_t n_padded_keys, uint64_t set_words, ListBlocks& b) {
+  b.keys = carver.take<uint64_t>(n_padded_keys);
+  b.values = carver.take<hy_value>(list->n_values);
+  b.value_ids = list->per_chunk_value_ids ? carver.take<uint32_t>(size_t{n_chunks} * list->n_values) : nullptr;
+  b.set_offsets = carver.take<uint64_t>(size_t{n_chunks} + 1);
+  b.any_at = align_up(8 * (set_words + 1), 256);
+  b.zeroed_bytes = b.any_at + 4 * (size_t{n_chunks} + 1);
+  b.zeroed = carver.take<char>(b.zeroed_bytes);
+}
+
+// No host round trip: the list, the (string) value ids and the zeroed bitmaps are queued on the stream, build_value_id_sets fills the
+// bitmaps of the dictionary chunks, prepare_jobs reads them.
+static hy_status list_queue(const hy_column* data_column, const InListArgs& args, const std::vector<uint64_t>& set_offsets, const ListBlocks& b, hipStream_t stream, PredicateArgs& pa) {
+  const hy_in_list* list = args.list;
+  const uint32_t n_chunks = data_column ? data_column->n_chunks : 0, n_values = list->n_values;
+  uint64_t* d_set_words = reinterpret_cast<uint64_t*>(b.zeroed);
+  uint32_t* d_any = reinterpret_cast<uint32_t*>(b.zeroed + b.any_at);
+  HY_HIP(hipMemcpyAsync(b.keys, args.keys.data(), 8 * args.keys.size(), hipMemcpyHostToDevice, stream));
+  if (list->values) HY_HIP(hipMemcpyAsync(b.values, list->values, sizeof(hy_value) * n_values, hipMemcpyHostToDevice, stream));
+  if (b.value_ids && n_chunks) HY_HIP(hipMemcpyAsync(b.value_ids, list->per_chunk_value_ids, 4 * size_t{n_chunks} * n_values, hipMemcpyHostToDevice, stream));
+  HY_HIP(hipMemcpyAsync(b.set_offsets, set_offsets.data(), 8 * (size_t{n_chunks} + 1), hipMemcpyHostToDevice, stream));
+  HY_HIP(hipMemsetAsync(b.zeroed, 0, b.zeroed_bytes, stream));
+  if (set_offsets[n_chunks]) {
+    const uint64_t lanes = uint64_t{n_chunks} * n_values;
+    hipLaunchKernelGGL(build_value_id_sets, dim3(static_cast<uint32_t>((lanes + 255) / 256)), dim3(256), 0, stream, data_column->d_segments, n_chunks, b.values, n_values, b.value_ids,
+                       d_set_words, b.set_offsets, d_any);
+  }
+  pa.condition = list->negated ? HY_PRED_NOT_IN : HY_PRED_IN;
+  pa.value_type = list->value_type;
+  pa.column_is_nullable = list->column_is_nullable;
+  pa.match_words = d_set_words;
+  pa.match_word_offsets = b.set_offsets;
+  pa.list_keys = b.keys;
+  pa.list_any = d_any;
+  pa.list_size = args.n_keys;
+  return HY_OK;
+}
+
+// Validate takes no block: its jobs come from the MVCC segments alone
+static void visibility_queue(const hy_column* mvcc_data, const VisibilityArgs& v, ScanJob* jobs, uint32_t* overflow, hipStream_t stream) {
+  const uint32_t n_chunks = mvcc_data ? mvcc_data->n_chunks : 0;
+  if (n_chunks) hipLaunchKernelGGL(prepare_visibility_jobs, dim3((n_chunks + 255) / 256), dim3(256), 0, stream, mvcc_data->d_segments, n_chunks, v.our_tid, v.snapshot, v.can_use_chunk_shortcut,
+                                   jobs, overflow);
+}
+
+// ---- the job sources for callers that evaluate the jobs themselves (hy_scan_job.hpp) ----------------------------------------------------
+// Their staging block: prepare_jobs' status word (it is the overflow word of those launches), then the source's blocks.  The jobs know
+// JOB_SCAN / JOB_ALL / JOB_NONE only (no_ranges).  prepare_jobs and prepare_visibility_jobs zero the status word themselves and no caller
+// reads it; the list overload also zeroes its block from the host side, as it always has (with no chunk there is no launch to do it).
+static uint32_t* staging_status_word(Carver& carver) { return carver.take<uint32_t>(64); }
+
+size_t scan_jobs_staging_bytes(const hy_column* column, const hy_predicate* predicate) {
+  Carver sizing;
+  PredicateBlocks blocks;
+  staging_status_word(sizing);
+  predicate_layout(sizing, predicate, column->n_chunks, nullptr, blocks);
+  return sizing.used;
+}
+
+hy_status prepare_scan_jobs(const hy_column* column, const hy_predicate* predicate, ScanJob* jobs, void* staging) {
+  if (column->is_reference || column->is_mvcc) return fail(HY_ERR_INVALID, "prepare_scan_jobs: data columns only");
+  HY_TRY(validate_predicate(column, predicate));
+  hipStream_t stream = current_stream();
+  Carver carver{nullptr, static_cast<char*>(staging)};
+  uint32_t* status = staging_status_word(carver);
+  PredicateBlocks blocks;
+  predicate_layout(carver, predicate, column->n_chunks, nullptr, blocks);
+  PredicateArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.no_ranges = 1;
+  HY_TRY(predicate_queue(predicate, column->n_chunks, nullptr, blocks, stream, pa));
+  queue_prepare_jobs(column, pa, jobs, status, stream);
+  return HY_OK;
+}
+
+static size_t padded_keys_at_most(uint32_t n_values) {   // check_in_list drops duplicates, then pads to a power of two
+  size_t padded = 1;
+  while (padded < n_values) padded *= 2;
+  return padded;
+}
+
 size_t scan_jobs_staging_bytes(const hy_column* column, const hy_in_list* list) {
-  const uint64_t set_words = value_id_set_offsets(column).back();
-  return 4 * 256 + 8 * 2 * size_t{HY_MAX_IN_LIST} + sizeof(hy_value) * size_t{list->n_values} + 4 * size_t{column->n_chunks} * list->n_values + 8 * (size_t{column->n_chunks} + 1) +
-         8 * (set_words + 1) + 4 * (size_t{column->n_chunks} + 1) + 8 * 256;
+  Carver sizing;
+  ListBlocks blocks;
+  staging_status_word(sizing);
+  list_layout(sizing, list, column->n_chunks, padded_keys_at_most(list->n_values), value_id_set_offsets(column).back(), blocks);
+  return sizing.used;
 }
 
 hy_status prepare_scan_jobs(const hy_column* column, const hy_in_list* list, ScanJob* jobs, void* staging) {
   if (column->is_reference || column->is_mvcc) return fail(HY_ERR_INVALID, "prepare_scan_jobs: data columns only");
   InListArgs args;
   HY_TRY(check_in_list(column, list, args));
-  const uint32_t n_chunks = column->n_chunks, n_values = list->n_values;
   const std::vector<uint64_t> set_offsets = value_id_set_offsets(column);
-  const uint64_t set_words = set_offsets[n_chunks];
   hipStream_t stream = current_stream();
-  char* cursor = static_cast<char*>(staging) + 256;   // (the first block: prepare_jobs' status word)
-  auto take = [&](size_t bytes) { char* at = cursor; cursor += align_up(bytes ? bytes : 4, 256); return at; };
-  uint64_t* d_keys = reinterpret_cast<uint64_t*>(take(8 * args.keys.size()));
-  hy_value* d_values = reinterpret_cast<hy_value*>(take(sizeof(hy_value) * n_values));
-  uint32_t* d_value_ids = list->per_chunk_value_ids ? reinterpret_cast<uint32_t*>(take(4 * size_t{n_chunks} * n_values)) : nullptr;
-  uint64_t* d_set_offsets = reinterpret_cast<uint64_t*>(take(8 * (size_t{n_chunks} + 1)));
-  const size_t zeroed = align_up(8 * (set_words + 1), 256) + 4 * (size_t{n_chunks} + 1);
-  char* d_zeroed = take(zeroed);
-  uint64_t* d_set_words = reinterpret_cast<uint64_t*>(d_zeroed);
-  uint32_t* d_any = reinterpret_cast<uint32_t*>(d_zeroed + align_up(8 * (set_words + 1), 256));
-  HY_HIP(hipMemsetAsync(staging, 0, 256, stream));
-  HY_HIP(hipMemcpyAsync(d_keys, args.keys.data(), 8 * args.keys.size(), hipMemcpyHostToDevice, stream));
-  if (list->values) HY_HIP(hipMemcpyAsync(d_values, list->values, sizeof(hy_value) * n_values, hipMemcpyHostToDevice, stream));
-  if (d_value_ids && n_chunks) HY_HIP(hipMemcpyAsync(d_value_ids, list->per_chunk_value_ids, 4 * size_t{n_chunks} * n_values, hipMemcpyHostToDevice, stream));
-  HY_HIP(hipMemcpyAsync(d_set_offsets, set_offsets.data(), 8 * (size_t{n_chunks} + 1), hipMemcpyHostToDevice, stream));
-  HY_HIP(hipMemsetAsync(d_zeroed, 0, zeroed, stream));
-  if (set_words) {
-    const uint64_t lanes = uint64_t{n_chunks} * n_values;
-    hipLaunchKernelGGL(build_value_id_sets, dim3(static_cast<uint32_t>((lanes + 255) / 256)), dim3(256), 0, stream, column->d_segments, n_chunks, d_values, n_values, d_value_ids, d_set_words,
-                       d_set_offsets, d_any);
-  }
+  Carver carver{nullptr, static_cast<char*>(staging)};
+  uint32_t* status = staging_status_word(carver);
+  ListBlocks blocks;
+  list_layout(carver, list, column->n_chunks, args.keys.size(), set_offsets.back(), blocks);
+  HY_HIP(hipMemsetAsync(status, 0, 256, stream));
   PredicateArgs pa;
   std::memset(&pa, 0, sizeof(pa));
-  pa.condition = list->negated ? HY_PRED_NOT_IN : HY_PRED_IN;
-  pa.value_type = list->value_type;
-  pa.column_is_nullable = list->column_is_nullable;
   pa.no_ranges = 1;
-  pa.match_words = d_set_words;
-  pa.match_word_offsets = d_set_offsets;
-  pa.list_keys = d_keys;
-  pa.list_any = d_any;
-  pa.list_size = args.n_keys;
-  if (n_chunks) hipLaunchKernelGGL(prepare_jobs, dim3(n_chunks), dim3(256), 0, stream, column->d_segments, n_chunks, pa, jobs, static_cast<uint32_t*>(staging));
+  HY_TRY(list_queue(column, args, set_offsets, blocks, stream, pa));
+  queue_prepare_jobs(column, pa, jobs, status, stream);
   return HY_OK;
 }
 
+hy_status prepare_visibility_scan_jobs(const hy_column* mvcc, uint32_t our_tid, uint32_t snapshot_commit_id, uint32_t can_use_chunk_shortcut, ScanJob* jobs, void* staging) {
+  if (!mvcc || !mvcc->is_mvcc || mvcc->is_reference) return fail(HY_ERR_INVALID, "a Validate filter needs the table's column of HY_ENC_MVCC segments");
+  visibility_queue(mvcc, VisibilityArgs{our_tid, snapshot_commit_id, can_use_chunk_shortcut}, jobs, static_cast<uint32_t*>(staging), current_stream());
+  return HY_OK;
+}
+
+// ---- host results ------------------------------------------------------------------------------------------------------------------------
+void scan_regions_layout(Carver& carver, uint32_t n_chunks, uint64_t rows, ScanRegions& regions) {
+  regions.matches = carver.take<hy_row_id>(rows + 1);
+  regions.offsets = carver.take<uint64_t>(size_t{n_chunks} + 2);
+  regions.counts = carver.take<uint32_t>(size_t{n_chunks} + 1);
+  regions.state = carver.take<uint8_t>(size_t{n_chunks} + 1);
+}
+
+void dense_regions_layout(Carver& carver, uint32_t n_chunks, uint64_t total, DenseRegions& dense) {
+  dense.offsets = carver.take<uint64_t>(size_t{n_chunks} + 2);
+  dense.matches = carver.take<hy_row_id>(total);
+}
+
 // A scan's chunk regions (device memory) as the HY_MEM_HOST result the caller asked for: counts and chunk states copied, the regions packed back
-// to back (carved from the thread's scratch arena behind what the scan carved) and copied.  d_overflow: the scan's overflow word, or nullptr.
+// to back (dense_regions_layout, from the thread's scratch arena behind what the scan carved) and copied.  d_overflow: the scan's overflow word, or nullptr.
 hy_status regions_to_host_result(const hy_row_id* d_matches, const uint64_t* d_offsets, const uint32_t* d_counts, const uint8_t* d_state, uint32_t* d_overflow, uint32_t n_chunks,
                                  bool materialize_all, hy_scan_result* result) {
   hipStream_t stream = current_stream();
-  Scratch& sc = scratch();
   uint32_t overflow = 0;
   HY_HIP(hipMemcpyAsync(result->counts, d_counts, 4 * size_t{n_chunks}, hipMemcpyDeviceToHost, stream));
   HY_HIP(hipMemcpyAsync(result->chunk_state, d_state, size_t{n_chunks}, hipMemcpyDeviceToHost, stream));
@@ -2301,44 +2445,86 @@ hy_status regions_to_host_result(const hy_row_id* d_matches, const uint64_t* d_o
   result->total_matches = total;
   if (total > result->capacity) return fail(HY_ERR_CAPACITY, "scan produced %llu RowIDs, capacity is %llu", static_cast<unsigned long long>(total), static_cast<unsigned long long>(result->capacity));
   if (total) {
-    uint64_t* d_dense_offsets = carve<uint64_t>(sc, size_t{n_chunks} + 2);
-    hy_row_id* d_dense = carve<hy_row_id>(sc, total);
-    if (!d_dense_offsets || !d_dense) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-    HY_HIP(hipMemcpyAsync(d_dense_offsets, result->offsets, 8 * (size_t{n_chunks} + 1), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(compact_regions, dim3(n_chunks), dim3(256), 0, stream, d_matches, d_offsets, d_dense_offsets, d_dense, n_chunks);
-    HY_HIP(hipMemcpyAsync(result->matches, d_dense, sizeof(hy_row_id) * total, hipMemcpyDeviceToHost, stream));
+    Carver carver{&scratch()};
+    DenseRegions dense;
+    dense_regions_layout(carver, n_chunks, total, dense);
+    if (carver.failed) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+    HY_HIP(hipMemcpyAsync(dense.offsets, result->offsets, 8 * (size_t{n_chunks} + 1), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(compact_regions, dim3(n_chunks), dim3(256), 0, stream, d_matches, d_offsets, dense.offsets, dense.matches, n_chunks);
+    HY_HIP(hipMemcpyAsync(result->matches, dense.matches, sizeof(hy_row_id) * total, hipMemcpyDeviceToHost, stream));
     HY_HIP(hipStreamSynchronize(stream));
   }
   return HY_OK;
 }
 
-// hy_table_scan_like: the dictionary and the tokenised pattern whose bitmaps run_scan has the matcher write into its scratch arena
-struct DeviceLike {
-  const hy_string_dictionary* dict;
-  const LikeProgram* program;
+// ---- string columns: the fourth stage of that shape ----------------------------------------------------------------------------------------
+// ranks | 0, 2, 4, ... | the descriptors of the int32 stand-ins, per data column and, over reference columns, per reference column
+struct TwinBlocks { int32_t *ranks, *evens; DevSegment *left_data, *right_data, *left_reference, *right_reference; uint32_t n_evens; };
+
+static void twins_layout(Carver& carver, const StringPair& strings, const hy_column* column, const hy_column* right, uint32_t n_data_chunks, TwinBlocks& b) {
+  b = TwinBlocks{};
+  for (const LikeChunk& chunk : strings.right->chunks) b.n_evens = std::max(b.n_evens, chunk.n_entries);
+  b.ranks = carver.take<int32_t>(strings.left->entry_offsets[n_data_chunks] + 4);
+  b.evens = carver.take<int32_t>(size_t{b.n_evens} + 4);
+  b.left_data = carver.take<DevSegment>(size_t{n_data_chunks} + 1);
+  b.right_data = carver.take<DevSegment>(size_t{n_data_chunks} + 1);
+  if (column->is_reference) b.left_reference = carver.take<DevSegment>(size_t{column->n_chunks} + 1);
+  if (right->is_reference) b.right_reference = carver.take<DevSegment>(size_t{column->n_chunks} + 1);
+}
+
+// Queued in front of the scan on this stream: the ranks, then the descriptors that point at them.  *left / *right: what the scan reads.
+static hy_status twins_queue(const StringPair& strings, const hy_column* column, const hy_column* right, const hy_column* data_column, const TwinBlocks& b, hipStream_t stream,
+                             const DevSegment** left, const DevSegment** right_out) {
+  const hy_column* right_data = right->is_reference ? right->ref : right;
+  if (right->is_reference) HY_TRY(plain_column(right_data, &right_data));
+  HY_TRY(string_order_launch(strings.left, strings.right, b.ranks, stream));
+  StringTwins twins;
+  std::memset(&twins, 0, sizeof(twins));
+  twins.left_data = data_column->d_segments;
+  twins.right_data = right_data->d_segments;
+  twins.left_data_twin = b.left_data;
+  twins.right_data_twin = b.right_data;
+  twins.left_reference = column->is_reference ? column->d_segments : nullptr;
+  twins.right_reference = right->is_reference ? right->d_segments : nullptr;
+  twins.left_reference_twin = b.left_reference;
+  twins.right_reference_twin = b.right_reference;
+  twins.entry_offsets = strings.left->d_entry_offsets;
+  twins.ranks = b.ranks;
+  twins.evens = b.evens;
+  twins.n_data_chunks = data_column->n_chunks;
+  twins.n_chunks = column->n_chunks;
+  twins.n_evens = b.n_evens;
+  HY_TRY(string_twins_launch(twins, stream));
+  *left = column->is_reference ? b.left_reference : b.left_data;
+  *right_out = right->is_reference ? b.right_reference : b.right_data;
+  return HY_OK;
+}
+
+// ---- one scan ----------------------------------------------------------------------------------------------------------------------------
+enum class ScanSource { Predicate, DeviceLike, InList, Visibility, TwoColumns, TwoStringColumns };
+
+struct ScanRequest {
+  const hy_column* column;
+  const uint32_t* excluded;       // chunks of a data column that take JOB_NONE
+  uint32_t n_excluded;
+  ScanSource source;              // exactly one of:
+  const hy_predicate* predicate;  //   Predicate, DeviceLike (its condition and nullability)
+  DeviceLike like;                //   DeviceLike
+  const InListArgs* in_list;      //   InList
+  VisibilityArgs visibility;      //   Visibility
+  const hy_column* right;         //   TwoColumns, TwoStringColumns: column <condition> right
+  uint32_t condition;
+  StringPair strings;             //   TwoStringColumns
 };
 
-// hy_table_scan_columns_strings: the dictionaries of the two (referenced) data columns; run_scan has string_order.hip rank them into its
-// scratch arena and scans the int32 stand-ins it describes there
-struct StringPair {
-  const hy_string_dictionary* left;
-  const hy_string_dictionary* right;
-};
+static const DeviceLike* like_of(const ScanRequest& rq) { return rq.source == ScanSource::DeviceLike ? &rq.like : nullptr; }
+static ScanRequest scan_request(const hy_column* column, ScanSource source, const uint32_t* excluded = nullptr, uint32_t n_excluded = 0) {
+  ScanRequest rq{};
+  rq.column = column; rq.source = source; rq.excluded = excluded; rq.n_excluded = n_excluded;
+  return rq;
+}
 
-static hy_status run_scan(const hy_column* column, const hy_column* right, const hy_predicate* predicate, uint32_t condition,
-                          const uint32_t* excluded, uint32_t n_excluded, hy_scan_result* result, const VisibilityArgs* visibility = nullptr,
-                          const InListArgs* in_list = nullptr, const DeviceLike* device_like = nullptr, const StringPair* strings = nullptr) {
-  // Run-length / bit-packed segments are read in place by a ColumnVsValue / Between / IsNull / Like scan of the data column itself; the
-  // two-column scan and the scan through reference segments read the decoded twins (hy_device.hpp) -- a reference segment's `ref`
-  // already points at the twin's descriptors, so the jobs are prepared from the twin as well.
-  if (right) {
-    HY_TRY(plain_column(column, &column));
-    HY_TRY(plain_column(right, &right));
-  }
-  const uint32_t n_chunks = column->n_chunks;
-  const hy_column* data_column = column->is_reference ? column->ref : column;
-  if (column->is_reference) HY_TRY(plain_column(data_column, &data_column));
-  const uint32_t n_data_chunks = data_column ? data_column->n_chunks : 0;
+static hy_status check_scan_result(const hy_column* column, const hy_scan_result* result) {
   const bool host_result = result->mem == HY_MEM_HOST;
   if (!result->offsets) return fail(HY_ERR_INVALID, "scan result: offsets array missing");
   if (host_result && (!result->counts || !result->chunk_state)) return fail(HY_ERR_INVALID, "scan result: host results need counts and chunk_state");
@@ -2348,179 +2534,196 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
   // scan_slices writes the regions two RowIDs at a time (16-byte stores at even RowID indices of `matches`): refused before any launch
   if (!host_result && (reinterpret_cast<uintptr_t>(result->matches) % 16 != 0 || reinterpret_cast<uintptr_t>(result->offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(result->counts) % 4 != 0))
     return fail(HY_ERR_INVALID, "scan result: a device-memory result needs matches on a 16-byte, offsets on an 8-byte and counts on a 4-byte boundary");
+  return HY_OK;
+}
+
+// The request with its columns resolved: run-length / bit-packed segments are read in place by a ColumnVsValue / Between / IsNull / Like scan
+// of the data column itself; the two-column scan and the scan through reference segments read the decoded twins (hy_device.hpp) -- a
+// reference segment's `ref` already points at the twin's descriptors, so the jobs are prepared from the twin as well.
+struct ResolvedScan {
+  const hy_column *column, *right, *data_column;
+  uint32_t n_chunks, n_data_chunks;
+  bool host_result;
+  bool reorders;        // matches of PosLists that span chunks are put in referenced-chunk order (Validate keeps position order, validate.cpp:236-253)
+  uint64_t set_words;   // InList: words of the value-id bitmaps
+};
+
+// Everything a scan takes from the thread's Scratch, in the order it is taken
+struct ScanBlocks { ScanJob* jobs; TwinBlocks twins; PredicateBlocks predicate; ListBlocks list; uint32_t* excluded; ScanRegions regions; hy_row_id* reorder_temp; };
+
+static void scan_layout(Carver& carver, const ScanRequest& rq, const ResolvedScan& rs, ScanBlocks& b) {
+  b.jobs = carver.take<ScanJob>(size_t{rs.n_data_chunks} + 1);
+  if (rq.source == ScanSource::TwoStringColumns) twins_layout(carver, rq.strings, rs.column, rs.right, rs.n_data_chunks, b.twins);
+  if (rq.predicate) predicate_layout(carver, rq.predicate, rs.n_data_chunks, like_of(rq), b.predicate);
+  if (rq.source == ScanSource::InList) list_layout(carver, rq.in_list->list, rs.n_data_chunks, rq.in_list->keys.size(), rs.set_words, b.list);
+  b.excluded = rq.n_excluded ? carver.take<uint32_t>(rq.n_excluded) : nullptr;
+  if (rs.host_result) scan_regions_layout(carver, rs.n_chunks, rs.column->rows, b.regions);
+  b.reorder_temp = rs.reorders ? carver.take<hy_row_id>(rs.column->rows + 1) : nullptr;
+}
+
+// Which kernel scans the column: a scan_slices instantiation, or (two_width != 0) scan_two_columns<two_width> with `dict_words` 8-byte
+// words of LDS for the chunks' dictionaries
+struct ScanLaunch { ScanKernel slices; uint32_t two_width, dict_words; };
+
+static ScanLaunch pick_kernel(const ScanRequest& rq, const ResolvedScan& rs) {
+  const hy_column *column = rs.column, *right = rs.right;
+  ScanLaunch launch{scan_slices<0>, 0, 0};
+  if (right) {
+    // ColumnVsColumn over two data columns of one 4-byte type whose segments are all W-byte vectors: the two-stream kernel, the chunks'
+    // dictionaries staged in LDS when the largest pair fits 48 KB (scan_two_columns); string segments are scanned as their int32 stand-ins
+    const bool strings = rq.source == ScanSource::TwoStringColumns;
+    uint32_t two_width = !column->is_reference && !right->is_reference && column->stream_width == right->stream_width && column->data_type == right->data_type &&
+                                 (column->data_type == HY_TYPE_INT || column->data_type == HY_TYPE_FLOAT || strings) && !column->has_compressed && !right->has_compressed &&
+                                 option(HY_OPT_SCAN_TWO_COLUMNS)
+                             ? column->stream_width : 0;
+    uint32_t dict_words = 0;
+    for (uint32_t c = 0; c < rs.n_chunks && two_width; ++c) {   // every segment: a W-byte vector of 4-byte values (stream_width says W bytes and aligned)
+      for (const hy_segment* seg : {&column->host_segments[c], &right->host_segments[c]}) {
+        const bool shape = seg->encoding == HY_ENC_UNENCODED ? two_width == 4 : (seg->encoding == HY_ENC_DICTIONARY || seg->encoding == HY_ENC_FRAME_OF_REFERENCE) && seg->width == two_width;
+        if (!shape || (seg->data_type != HY_TYPE_INT && seg->data_type != HY_TYPE_FLOAT && !strings)) two_width = 0;
+        if (seg->encoding == HY_ENC_DICTIONARY) dict_words = std::max(dict_words, seg->aux_size);
+      }
+    }
+    for (uint32_t c = 0; c < rs.n_chunks && two_width; ++c) if (column->host_segments[c].size > PART_SLICES * SLICE_ROWS) two_width = 0;   // (a chunk of several parts)
+    if (two_width == 1 || two_width == 2 || two_width == 4) {
+      dict_words = (dict_words + 3) & ~3u;
+      if (8 * size_t{dict_words} > 48 * 1024) dict_words = 0;   // (dictionaries that large stay in global memory: cache hits at best)
+      launch.two_width = two_width;
+      launch.dict_words = dict_words;
+    }
+    return launch;
+  }
+  if (rq.predicate && rq.predicate->condition >= HY_PRED_LIKE && rq.predicate->condition <= HY_PRED_NOT_LIKE_INSENSITIVE) {
+    launch.slices = column->has_compressed ? scan_slices<8> : scan_slices<0>;   // value-id sets are tested by the generic instantiations
+  } else if (rq.source == ScanSource::InList) {
+    launch.slices = column->has_compressed ? scan_slices<40> : scan_slices<32>;
+  } else if (column->stream_width == 16) { launch.slices = column->has_sorted ? scan_slices<16, true> : scan_slices<16>;   // bit-packed vectors of at most 16 bits
+  } else if (column->stream_width == 1) { launch.slices = column->has_sorted ? scan_slices<1, true> : scan_slices<1>;
+  } else if (column->stream_width == 2) { launch.slices = column->has_sorted ? scan_slices<2, true> : scan_slices<2>;
+  } else if (column->stream_width == 4) { launch.slices = column->has_sorted ? scan_slices<4, true> : scan_slices<4>;
+  } else if (column->has_compressed) {
+    launch.slices = scan_slices<8>;
+  }
+  return launch;
+}
+
+static hy_status launch_scan(const ScanLaunch& launch, const hy_column* column, ScanArgs& a, hipStream_t stream) {
+  const uint32_t grid = scan_grid(launch.slices, column->n_parts);
+  if (HY_DEBUG_ENV("HY_SCAN_TRACE")) {
+    static uint64_t* trace_buffer = nullptr;
+    if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 4 * 4096);
+    a.trace = trace_buffer;
+    g_trace_buffer = trace_buffer;
+    g_trace_grid = grid;
+  }
+  hipEvent_t started = nullptr, stopped = nullptr;
+  profile_events(&started, &stopped, HY_KERNEL_SCAN);
+  if (!launch.two_width) {
+    hipExtLaunchKernelGGL(launch.slices, dim3(grid), dim3(WG_THREADS), SCAN_LDS_BYTES, stream, started, stopped, 0, a.segments, a.right, a.slices, a.jobs, column->d_parts, a);
+    return HY_OK;
+  }
+  const uint32_t dict_words = launch.dict_words;
+  const size_t lds = SCAN_LDS_BYTES + 8 * size_t{dict_words};
+  const bool is_float = column->data_type == HY_TYPE_FLOAT;
+  int device = 0, cus = 256;
+  (void)hipGetDevice(&device);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  auto two = [&](auto kernel_of_shape) -> hy_status {
+    int per_cu = 0;
+    HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel_of_shape), WG_THREADS, lds));
+    const uint32_t resident = static_cast<uint32_t>(cus) * static_cast<uint32_t>(std::max(1, std::min(per_cu, 8)));
+    hipExtLaunchKernelGGL(kernel_of_shape, dim3(std::max(1u, std::min(column->n_parts, resident))), dim3(WG_THREADS), lds, stream, started, stopped, 0, a.segments, a.right,
+                          column->d_parts, a, dict_words);
+    return HY_OK;
+  };
+  if (launch.two_width == 1) return is_float ? two(scan_two_columns<1, true>) : two(scan_two_columns<1, false>);
+  if (launch.two_width == 2) return is_float ? two(scan_two_columns<2, true>) : two(scan_two_columns<2, false>);
+  return is_float ? two(scan_two_columns<4, true>) : two(scan_two_columns<4, false>);
+}
+
+static hy_status run_scan(const ScanRequest& rq, hy_scan_result* result) {
+  // 1. the result, 2. the columns
+  HY_TRY(check_scan_result(rq.column, result));
+  ResolvedScan rs{};
+  rs.column = rq.column;
+  rs.right = rq.right;
+  if (rs.right) {
+    HY_TRY(plain_column(rs.column, &rs.column));
+    HY_TRY(plain_column(rs.right, &rs.right));
+  }
+  const hy_column* column = rs.column;
+  rs.data_column = column->is_reference ? column->ref : column;
+  if (column->is_reference) HY_TRY(plain_column(rs.data_column, &rs.data_column));
+  rs.n_chunks = column->n_chunks;
+  rs.n_data_chunks = rs.data_column ? rs.data_column->n_chunks : 0;
+  rs.host_result = result->mem == HY_MEM_HOST;
+  const bool by_predicate = rq.source == ScanSource::Predicate || rq.source == ScanSource::DeviceLike || rq.source == ScanSource::InList;
+  rs.reorders = column->multi_chunk_reference && by_predicate && rs.n_chunks && (rs.host_result || result->counts);
+  std::vector<uint64_t> set_offsets;
+  if (rq.source == ScanSource::InList) {
+    set_offsets = value_id_set_offsets(rs.data_column);
+    rs.set_words = set_offsets.back();
+  }
   hipStream_t stream = current_stream();
   Scratch& sc = scratch();
 
-  // Scratch: jobs | per_chunk arrays | excluded | overflow flag | (host results) regions + dense copy + per-chunk arrays
-  size_t need = sizeof(ScanJob) * (n_data_chunks + 1) + 3 * 4 * (size_t{n_data_chunks} + 64) + 4 * (size_t{n_excluded} + 64) + 1024;
-  const bool like = predicate && predicate->condition >= HY_PRED_LIKE && predicate->condition <= HY_PRED_NOT_LIKE_INSENSITIVE;
-  if (like && device_like) need += 8 * (device_like->dict->word_offsets[n_data_chunks] + 2) + 512;   // the matcher's words; their offsets are the dictionary's
-  else if (like) need += 8 * (size_t{n_data_chunks} + 2) + 8 * (predicate->match_word_offsets[n_data_chunks] + 2) + 1024;
-  // IN / NOT IN: keys | values | caller's value ids | bitmap offsets | bitmaps + "any" words of the dictionary chunks (one zeroed block)
-  std::vector<uint64_t> set_offsets;
-  if (in_list) {
-    set_offsets.assign(size_t{n_data_chunks} + 1, 0);
-    for (uint32_t c = 0; c < n_data_chunks; ++c) {
-      const hy_segment& s = data_column->host_segments[c];
-      set_offsets[c + 1] = set_offsets[c] + (s.encoding == HY_ENC_DICTIONARY ? (uint64_t{s.aux_size} + 63) / 64 : 0);
-    }
-    need += 8 * in_list->keys.size() + 8 * size_t{in_list->list->n_values} + 4 * size_t{n_data_chunks} * in_list->list->n_values + 8 * (size_t{n_data_chunks} + 1) +
-            8 * set_offsets[n_data_chunks] + 4 * (size_t{n_data_chunks} + 1) + 8 * 256;
-  }
-  if (column->multi_chunk_reference) need += sizeof(hy_row_id) * (column->rows + 1) + 256;
-  uint32_t n_evens = 0;   // string columns: ranks | 0, 2, 4, ... | the descriptors of the stand-ins
-  if (strings) {
-    for (const LikeChunk& chunk : strings->right->chunks) n_evens = std::max(n_evens, chunk.n_entries);
-    need += 4 * (strings->left->entry_offsets[n_data_chunks] + n_evens + 8) + 2 * sizeof(DevSegment) * (size_t{n_data_chunks} + n_chunks + 2) + 6 * 256;
-  }
-  if (host_result) need += 2 * sizeof(hy_row_id) * (column->rows + 1) + 3 * 8 * (size_t{n_chunks} + 2) + 4 * (size_t{n_chunks} + 1) + n_chunks + 8192;
-  HY_TRY(sc.reserve(need + 16 * 256));
-  ScanJob* d_jobs = carve<ScanJob>(sc, n_data_chunks + 1);
+  // 3. size by a dry run of the layout (the dense copy of a host result at its largest), reserve, and lay out for real
+  ScanBlocks blocks{};
+  DenseRegions dense;
+  Carver sizing;
+  scan_layout(sizing, rq, rs, blocks);
+  if (rs.host_result) dense_regions_layout(sizing, rs.n_chunks, column->rows, dense);
+  HY_TRY(sc.reserve(sizing.used));
+  Carver carver{&sc};
+  scan_layout(carver, rq, rs, blocks);
+  if (carver.failed) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
   uint32_t* d_overflow = sc.ticket + 16;   // persistent word, zero unless a scan overflowed (an internal error)
-  const DevSegment *left_segments = column->d_segments, *right_segments = right ? right->d_segments : nullptr;
-  if (strings) {   // queued in front of the scan on this stream: the ranks, then the descriptors that point at them
-    const hy_column* right_data = right->is_reference ? right->ref : right;
-    if (right->is_reference) HY_TRY(plain_column(right_data, &right_data));
-    StringTwins twins;
-    std::memset(&twins, 0, sizeof(twins));
-    int32_t* d_ranks = carve<int32_t>(sc, strings->left->entry_offsets[n_data_chunks] + 4);
-    twins.evens = carve<int32_t>(sc, size_t{n_evens} + 4);
-    twins.left_data_twin = carve<DevSegment>(sc, n_data_chunks + 1);
-    twins.right_data_twin = carve<DevSegment>(sc, n_data_chunks + 1);
-    if (column->is_reference) twins.left_reference_twin = carve<DevSegment>(sc, n_chunks + 1);
-    if (right->is_reference) twins.right_reference_twin = carve<DevSegment>(sc, n_chunks + 1);
-    if (!d_ranks || !twins.evens || !twins.left_data_twin || !twins.right_data_twin || (column->is_reference && !twins.left_reference_twin) ||
-        (right->is_reference && !twins.right_reference_twin)) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-    HY_TRY(string_order_launch(strings->left, strings->right, d_ranks, stream));
-    twins.left_data = data_column->d_segments;
-    twins.right_data = right_data->d_segments;
-    twins.left_reference = column->is_reference ? column->d_segments : nullptr;
-    twins.right_reference = right->is_reference ? right->d_segments : nullptr;
-    twins.entry_offsets = strings->left->d_entry_offsets;
-    twins.ranks = d_ranks;
-    twins.n_data_chunks = n_data_chunks;
-    twins.n_chunks = n_chunks;
-    twins.n_evens = n_evens;
-    HY_TRY(string_twins_launch(twins, stream));
-    left_segments = column->is_reference ? twins.left_reference_twin : twins.left_data_twin;
-    right_segments = right->is_reference ? twins.right_reference_twin : twins.right_data_twin;
-  }
-  ScanKernel kernel = !right && column->has_compressed ? scan_slices<8> : scan_slices<0>;
-  if (!right && column->stream_width == 16) kernel = column->has_sorted ? scan_slices<16, true> : scan_slices<16>;   // bit-packed vectors of at most 16 bits
-  else if (!right && column->stream_width == 1) kernel = column->has_sorted ? scan_slices<1, true> : scan_slices<1>;
-  else if (!right && column->stream_width == 2) kernel = column->has_sorted ? scan_slices<2, true> : scan_slices<2>;
-  else if (!right && column->stream_width == 4) kernel = column->has_sorted ? scan_slices<4, true> : scan_slices<4>;
-  if (like) kernel = column->has_compressed ? scan_slices<8> : scan_slices<0>;   // value-id sets are tested by the generic instantiations
-  if (in_list) kernel = column->has_compressed ? scan_slices<40> : scan_slices<32>;
 
+  // 4. the source's jobs, or the stand-ins of two string columns
+  ScanJob* d_jobs = blocks.jobs;
+  const DevSegment *left_segments = column->d_segments, *right_segments = rs.right ? rs.right->d_segments : nullptr;
   PredicateArgs pa;
   std::memset(&pa, 0, sizeof(pa));
   pa.materialize_all = (result->flags & HY_SCAN_MATERIALIZE_ALL_MATCH) ? 1 : 0;
-  if (visibility && n_data_chunks) {
-    hipLaunchKernelGGL(prepare_visibility_jobs, dim3((n_data_chunks + 255) / 256), dim3(256), 0, stream, data_column->d_segments, n_data_chunks, visibility->our_tid,
-                       visibility->snapshot, visibility->can_use_chunk_shortcut, d_jobs, d_overflow);
-  }
-  const uint64_t* d_list_keys = nullptr;
-  if (in_list) {
-    // No host round trip: the list, the (string) value ids and the zeroed bitmaps are queued on the stream, build_value_id_sets fills the
-    // bitmaps of the dictionary chunks, prepare_jobs reads them.
-    const hy_in_list* list = in_list->list;
-    const uint32_t n_values = list->n_values;
-    const uint64_t set_words = set_offsets[n_data_chunks];
-    uint64_t* d_keys = carve<uint64_t>(sc, in_list->keys.size());
-    hy_value* d_values = carve<hy_value>(sc, n_values);
-    uint32_t* d_value_ids = list->per_chunk_value_ids ? carve<uint32_t>(sc, size_t{n_data_chunks} * n_values) : nullptr;
-    uint64_t* d_set_offsets = carve<uint64_t>(sc, size_t{n_data_chunks} + 1);
-    const size_t zeroed = align_up(8 * (set_words + 1), 256) + 4 * (size_t{n_data_chunks} + 1);
-    char* d_zeroed = static_cast<char*>(sc.carve(zeroed));
-    if (!d_keys || !d_values || !d_set_offsets || !d_zeroed || (list->per_chunk_value_ids && !d_value_ids)) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-    uint64_t* d_set_words = reinterpret_cast<uint64_t*>(d_zeroed);
-    uint32_t* d_any = reinterpret_cast<uint32_t*>(d_zeroed + align_up(8 * (set_words + 1), 256));
-    HY_HIP(hipMemcpyAsync(d_keys, in_list->keys.data(), 8 * in_list->keys.size(), hipMemcpyHostToDevice, stream));
-    if (list->values) HY_HIP(hipMemcpyAsync(d_values, list->values, sizeof(hy_value) * n_values, hipMemcpyHostToDevice, stream));
-    if (d_value_ids && n_data_chunks) HY_HIP(hipMemcpyAsync(d_value_ids, list->per_chunk_value_ids, 4 * size_t{n_data_chunks} * n_values, hipMemcpyHostToDevice, stream));
-    HY_HIP(hipMemcpyAsync(d_set_offsets, set_offsets.data(), 8 * (size_t{n_data_chunks} + 1), hipMemcpyHostToDevice, stream));
-    HY_HIP(hipMemsetAsync(d_zeroed, 0, zeroed, stream));
-    if (set_words) {
-      const uint64_t lanes = uint64_t{n_data_chunks} * n_values;
-      hipLaunchKernelGGL(build_value_id_sets, dim3(static_cast<uint32_t>((lanes + 255) / 256)), dim3(256), 0, stream, data_column->d_segments, n_data_chunks, d_values, n_values,
-                         d_value_ids, d_set_words, d_set_offsets, d_any);
+  switch (rq.source) {
+    case ScanSource::Visibility:
+      visibility_queue(rs.data_column, rq.visibility, d_jobs, d_overflow, stream);
+      break;
+    case ScanSource::InList:
+      HY_TRY(list_queue(rs.data_column, *rq.in_list, set_offsets, blocks.list, stream, pa));
+      queue_prepare_jobs(rs.data_column, pa, d_jobs, d_overflow, stream);
+      break;
+    case ScanSource::Predicate:
+    case ScanSource::DeviceLike: {
+      HY_TRY(predicate_queue(rq.predicate, rs.n_data_chunks, like_of(rq), blocks.predicate, stream, pa));
+      // a literal predicate over a data column whose jobs this column remembers (hy_scan_job_cache): no launch
+      const bool cacheable = FIXED_SCAN_JOB_CACHE && !rq.n_excluded && rs.n_data_chunks && !pa.per_chunk_lower && !pa.per_chunk_upper && !pa.per_chunk_found && !pa.match_words &&
+                             !pa.match_word_offsets;
+      ScanJob* cached = nullptr;
+      if (cacheable) HY_TRY(cached_scan_jobs(rs.data_column, pa, stream, &cached));
+      if (cached) d_jobs = cached;
+      else queue_prepare_jobs(rs.data_column, pa, d_jobs, d_overflow, stream);
+      break;
     }
-    pa.condition = predicate->condition;
-    pa.value_type = list->value_type;
-    pa.column_is_nullable = predicate->column_is_nullable;
-    pa.match_words = d_set_words;
-    pa.match_word_offsets = d_set_offsets;
-    pa.list_keys = d_keys;
-    pa.list_any = d_any;
-    pa.list_size = in_list->n_keys;
-    d_list_keys = d_keys;
-    if (n_data_chunks) hipLaunchKernelGGL(prepare_jobs, dim3(n_data_chunks), dim3(256), 0, stream, data_column->d_segments, n_data_chunks, pa, d_jobs, d_overflow);
-  } else if (predicate) {
-    pa.condition = predicate->condition;
-    pa.value_type = predicate->value_type;
-    pa.value = predicate->value;
-    pa.value2 = predicate->value2;
-    pa.column_is_nullable = predicate->column_is_nullable;
-    auto stage = [&](const void* host, size_t bytes, const void** dev) -> hy_status {
-      *dev = nullptr;
-      if (!host) return HY_OK;
-      void* d = sc.carve(bytes ? bytes : 4);
-      HY_HIP(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream));
-      *dev = d;
-      return HY_OK;
-    };
-    const void* d;
-    HY_TRY(stage(predicate->per_chunk_lower, 4 * size_t{n_data_chunks}, &d)); pa.per_chunk_lower = static_cast<const uint32_t*>(d);
-    HY_TRY(stage(predicate->per_chunk_upper, 4 * size_t{n_data_chunks}, &d)); pa.per_chunk_upper = static_cast<const uint32_t*>(d);
-    HY_TRY(stage(predicate->per_chunk_found, size_t{n_data_chunks}, &d)); pa.per_chunk_found = static_cast<const uint8_t*>(d);
-    if (device_like) {   // hy_table_scan_like: the bitmaps are made where they are read (like.hip), in front of prepare_jobs on this stream
-      uint64_t* d_words = carve<uint64_t>(sc, device_like->dict->word_offsets[n_data_chunks] + 1);
-      if (!d_words) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-      HY_TRY(like_launch(device_like->dict, *device_like->program, d_words, stream));
-      pa.match_words = d_words;
-      pa.match_word_offsets = device_like->dict->d_word_offsets;
-    } else if (predicate->match_words && predicate->match_word_offsets) {
-      const uint64_t total_words = predicate->match_word_offsets[n_data_chunks];
-      HY_TRY(stage(predicate->match_word_offsets, 8 * (size_t{n_data_chunks} + 1), &d)); pa.match_word_offsets = static_cast<const uint64_t*>(d);
-      HY_TRY(stage(predicate->match_words, 8 * (total_words ? total_words : 1), &d)); pa.match_words = static_cast<const uint64_t*>(d);
-    }
-    // a literal predicate over a data column whose jobs this column remembers (hy_scan_job_cache): no launch
-    const bool cacheable = FIXED_SCAN_JOB_CACHE && !visibility && !n_excluded && n_data_chunks && !pa.per_chunk_lower && !pa.per_chunk_upper && !pa.per_chunk_found &&
-                           !pa.match_words && !pa.match_word_offsets;
-    ScanJob* cached = nullptr;
-    if (cacheable) HY_TRY(cached_scan_jobs(data_column, pa, stream, &cached));
-    if (cached) {
-      d_jobs = cached;
-    } else if (n_data_chunks) {
-      hipLaunchKernelGGL(prepare_jobs, dim3(n_data_chunks), dim3(256), 0, stream, data_column->d_segments, n_data_chunks, pa, d_jobs, d_overflow);
-    }
-  }
-  if (n_excluded) {
-    if (column->is_reference) return fail(HY_ERR_INVALID, "excluded chunks apply to data tables only");
-    uint32_t* d_excluded = carve<uint32_t>(sc, n_excluded);
-    HY_HIP(hipMemcpyAsync(d_excluded, excluded, 4 * size_t{n_excluded}, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(exclude_chunks, dim3((n_excluded + 255) / 256), dim3(256), 0, stream, d_jobs, d_excluded, n_excluded);
+    case ScanSource::TwoColumns:
+      break;
+    case ScanSource::TwoStringColumns:
+      HY_TRY(twins_queue(rq.strings, column, rs.right, rs.data_column, blocks.twins, stream, &left_segments, &right_segments));
+      break;
   }
 
-  hy_row_id* d_matches = result->matches;
-  uint64_t* d_offsets = result->offsets;
-  uint32_t* d_counts = result->counts;
-  uint8_t* d_state = result->chunk_state;
-  uint64_t device_capacity = result->capacity;
-  if (host_result) {
-    device_capacity = column->rows;
-    d_matches = carve<hy_row_id>(sc, device_capacity + 1);
-    d_offsets = carve<uint64_t>(sc, size_t{n_chunks} + 2);
-    d_counts = carve<uint32_t>(sc, size_t{n_chunks} + 1);
-    d_state = carve<uint8_t>(sc, size_t{n_chunks} + 1);
-    if (!d_matches || !d_offsets || !d_counts || !d_state) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  // 5. the exclusions
+  if (rq.n_excluded) {
+    HY_HIP(hipMemcpyAsync(blocks.excluded, rq.excluded, 4 * size_t{rq.n_excluded}, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(exclude_chunks, dim3((rq.n_excluded + 255) / 256), dim3(256), 0, stream, d_jobs, blocks.excluded, rq.n_excluded);
   }
 
-  if (n_chunks == 0) {
-    HY_HIP(hipMemsetAsync(d_offsets, 0, 8, stream));
+  // 6. the kernel, 7. its launch
+  ScanRegions out{result->matches, result->offsets, result->counts, result->chunk_state};
+  if (rs.host_result) out = blocks.regions;
+  if (rs.n_chunks == 0) {
+    HY_HIP(hipMemsetAsync(out.offsets, 0, 8, stream));
   } else {
-    const uint32_t grid = scan_grid(kernel, column->n_parts);
     HY_TRY(sc.begin_launch(column->n_parts, 0));
     ScanArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -2530,83 +2733,34 @@ static hy_status run_scan(const hy_column* column, const hy_column* right, const
     a.jobs = d_jobs;
     a.n_slices = column->n_slices;
     a.n_parts = column->n_parts;
-    a.n_chunks = n_chunks;
-    a.condition = condition;
+    a.n_chunks = rs.n_chunks;
+    a.condition = rq.condition;
     a.materialize_all = pa.materialize_all;
-    a.is_null_scan = predicate && predicate->condition == HY_PRED_IS_NULL;
+    a.is_null_scan = rq.predicate && rq.predicate->condition == HY_PRED_IS_NULL;
     a.epoch = sc.epoch;
     a.status = sc.status;
-    a.matches = d_matches;
-    a.capacity = device_capacity;
-    a.offsets = d_offsets;
-    a.counts = d_counts;
-    a.chunk_state = d_state;
+    a.matches = out.matches;
+    a.capacity = rs.host_result ? column->rows : result->capacity;
+    a.offsets = out.offsets;
+    a.counts = out.counts;
+    a.chunk_state = out.state;
     a.overflow = d_overflow;
     a.trace = nullptr;
     // Write-back stores: on this part a 37 : 63 read : write stream runs 13 % faster through the L2 than around it (nontemporal) --
     // tools/hbm_mix.hip shows it for the bare traffic pattern, tools/scan_ab.py for this kernel (profiles/r03_scan_stores.txt).
     a.plain_stores = FIXED_SCAN_NT_STORES ? 0u : 1u;
-    a.list = d_list_keys;
-    a.list_padded = in_list ? static_cast<uint32_t>(in_list->keys.size()) : 0u;
-    if (HY_DEBUG_ENV("HY_SCAN_TRACE")) {
-      static uint64_t* trace_buffer = nullptr;
-      if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 4 * 4096);
-      a.trace = trace_buffer;
-      g_trace_buffer = trace_buffer;
-      g_trace_grid = grid;
-    }
-    hipEvent_t started = nullptr, stopped = nullptr;
-    profile_events(&started, &stopped, HY_KERNEL_SCAN);
-    // ColumnVsColumn over two data columns of one 4-byte type whose segments are all W-byte vectors: the two-stream kernel, the chunks'
-    // dictionaries staged in LDS when the largest pair fits 48 KB (scan_two_columns)
-    uint32_t two_width = right && !column->is_reference && !right->is_reference && column->stream_width == right->stream_width && column->data_type == right->data_type &&
-                                 (column->data_type == HY_TYPE_INT || column->data_type == HY_TYPE_FLOAT || strings) && !column->has_compressed && !right->has_compressed &&
-                                 option(HY_OPT_SCAN_TWO_COLUMNS)
-                             ? column->stream_width : 0;
-    uint32_t dict_words = 0;
-    for (uint32_t c = 0; c < n_chunks && two_width; ++c) {   // every segment: a W-byte vector of 4-byte values (stream_width says W bytes and aligned)
-      for (const hy_segment* seg : {&column->host_segments[c], &right->host_segments[c]}) {
-        const bool shape = seg->encoding == HY_ENC_UNENCODED ? two_width == 4 : (seg->encoding == HY_ENC_DICTIONARY || seg->encoding == HY_ENC_FRAME_OF_REFERENCE) && seg->width == two_width;
-        if (!shape || (seg->data_type != HY_TYPE_INT && seg->data_type != HY_TYPE_FLOAT && !strings)) two_width = 0;   // (string segments: scanned as their int32 stand-ins)
-        if (seg->encoding == HY_ENC_DICTIONARY) dict_words = std::max(dict_words, seg->aux_size);
-      }
-    }
-    for (uint32_t c = 0; c < n_chunks && two_width; ++c) if (column->host_segments[c].size > PART_SLICES * SLICE_ROWS) two_width = 0;   // (a chunk of several parts)
-    if (two_width == 1 || two_width == 2 || two_width == 4) {
-      dict_words = (dict_words + 3) & ~3u;
-      if (8 * size_t{dict_words} > 48 * 1024) dict_words = 0;   // (dictionaries that large stay in global memory: cache hits at best)
-      const size_t lds = SCAN_LDS_BYTES + 8 * size_t{dict_words};
-      const bool is_float = column->data_type == HY_TYPE_FLOAT;
-      int device = 0, cus = 256;
-      (void)hipGetDevice(&device);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-      auto launch = [&](auto kernel_of_shape) -> hy_status {
-        int per_cu = 0;
-        HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel_of_shape), WG_THREADS, lds));
-        const uint32_t resident = static_cast<uint32_t>(cus) * static_cast<uint32_t>(std::max(1, std::min(per_cu, 8)));
-        hipExtLaunchKernelGGL(kernel_of_shape, dim3(std::max(1u, std::min(column->n_parts, resident))), dim3(WG_THREADS), lds, stream, started, stopped, 0, a.segments, a.right,
-                              column->d_parts, a, dict_words);
-        return HY_OK;
-      };
-      if (two_width == 1) HY_TRY(is_float ? launch(scan_two_columns<1, true>) : launch(scan_two_columns<1, false>));
-      else if (two_width == 2) HY_TRY(is_float ? launch(scan_two_columns<2, true>) : launch(scan_two_columns<2, false>));
-      else HY_TRY(is_float ? launch(scan_two_columns<4, true>) : launch(scan_two_columns<4, false>));
-    } else
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(WG_THREADS), SCAN_LDS_BYTES, stream, started, stopped, 0, a.segments, a.right, a.slices, a.jobs,
-                          column->d_parts, a);
+    a.list = rq.source == ScanSource::InList ? blocks.list.keys : nullptr;
+    a.list_padded = rq.source == ScanSource::InList ? static_cast<uint32_t>(rq.in_list->keys.size()) : 0u;
+    HY_TRY(launch_scan(pick_kernel(rq, rs), column, a, stream));
   }
-  if (column->multi_chunk_reference && predicate && n_chunks && d_counts) {   // (Validate keeps position order, validate.cpp:236-253)
-    hy_row_id* d_temp = carve<hy_row_id>(sc, column->rows + 1);
-    if (!d_temp) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-    hipLaunchKernelGGL(reorder_by_referenced_chunk, dim3(n_chunks), dim3(64), 0, stream, column->d_segments, d_matches, d_offsets, d_counts, d_temp, n_data_chunks);
-  }
+
+  // 8. PosLists that span chunks: the matches by referenced chunk
+  if (rs.reorders) hipLaunchKernelGGL(reorder_by_referenced_chunk, dim3(rs.n_chunks), dim3(64), 0, stream, column->d_segments, out.matches, out.offsets, out.counts, blocks.reorder_temp, rs.n_data_chunks);
   HY_HIP(hipGetLastError());
 
-  if (host_result) {
-    HY_TRY(regions_to_host_result(d_matches, d_offsets, d_counts, d_state, d_overflow, n_chunks, pa.materialize_all != 0, result));
-  } else {
-    result->total_matches = 0;
-  }
+  // 9. the result
+  if (rs.host_result) return regions_to_host_result(out.matches, out.offsets, out.counts, out.state, d_overflow, rs.n_chunks, pa.materialize_all != 0, result);
+  result->total_matches = 0;
   return HY_OK;
 }
 
@@ -2640,81 +2794,58 @@ hy_status hy_table_scan(const hy_column* column, const hy_predicate* predicate, 
                         uint32_t n_excluded, hy_scan_result* result) {
   if (!column || !predicate || !result) return fail(HY_ERR_INVALID, "hy_table_scan: null argument");
   HY_TRY(on_this_device(column, "hy_table_scan"));
-  if (n_excluded && !excluded_chunks) return fail(HY_ERR_INVALID, "hy_table_scan: excluded chunk list missing");
-  for (uint32_t i = 0; i < n_excluded; ++i) {
-    if (excluded_chunks[i] >= column->n_chunks) return fail(HY_ERR_INVALID, "excluded chunk id %u out of range", excluded_chunks[i]);
-  }
-  if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
+  HY_TRY(check_excluded(column, excluded_chunks, n_excluded, "hy_table_scan"));
+  HY_TRY(refuse_mvcc(column));
   HY_TRY(validate_predicate(column, predicate));
-  if (column->multi_chunk_reference && result->mem == HY_MEM_DEVICE && !result->counts) {
-    return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
-  }
-  return run_scan(column, nullptr, predicate, 0, excluded_chunks, n_excluded, result);
+  HY_TRY(check_reorder_counts(column, result));
+  ScanRequest request = scan_request(column, ScanSource::Predicate, excluded_chunks, n_excluded);
+  request.predicate = predicate;
+  return run_scan(request, result);
 }
 
 hy_status hy_table_scan_like(const hy_column* column, const hy_string_dictionary* dict, const char* pattern, uint32_t pattern_bytes, uint32_t condition,
                              uint32_t column_is_nullable, const uint32_t* excluded_chunks, uint32_t n_excluded, hy_scan_result* result) {
-  if (!column || !dict || !result) return fail(HY_ERR_INVALID, "hy_table_scan_like: null argument");
+  const char* name = "hy_table_scan_like";
+  if (!column || !dict || !result) return fail(HY_ERR_INVALID, "%s: null argument", name);
   LikeProgram program;
-  HY_TRY(like_program(pattern, pattern_bytes, condition, &program, "hy_table_scan_like"));
-  HY_TRY(on_this_device(column, "hy_table_scan_like"));
-  if (dict->device != column->device) return fail(HY_ERR_INVALID, "hy_table_scan_like: the dictionary lives on device %d, the column on device %d", dict->device, column->device);
-  if (n_excluded && !excluded_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_like: excluded chunk list missing");
-  if (n_excluded && column->is_reference) return fail(HY_ERR_INVALID, "excluded chunks apply to data tables only");   // (run_scan's refusal, here in front of the matcher's launch)
-  for (uint32_t i = 0; i < n_excluded; ++i) {
-    if (excluded_chunks[i] >= column->n_chunks) return fail(HY_ERR_INVALID, "excluded chunk id %u out of range", excluded_chunks[i]);
-  }
-  if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
+  HY_TRY(like_program(pattern, pattern_bytes, condition, &program, name));
+  HY_TRY(on_this_device(column, name));
+  HY_TRY(check_excluded(column, excluded_chunks, n_excluded, name));
+  HY_TRY(refuse_mvcc(column));
   // column_like_table_scan_impl.cpp:32-36: "LIKE operator only applicable on string columns"; the dictionary is the data column's
-  const hy_column* data_column = column->is_reference ? column->ref : column;
-  if (column->data_type != HY_TYPE_STRING && column->n_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_like: LIKE is only applicable on string columns (column type %u)", column->data_type);
-  const uint32_t n_data_chunks = data_column ? data_column->n_chunks : 0;
-  for (uint32_t c = 0; c < n_data_chunks; ++c) {
-    if (data_column->host_segments[c].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "LIKE on unencoded string segments stays on the CPU path");
-  }
-  if (dict->n_chunks != n_data_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_like: the dictionary has %u chunks, the data column %u", dict->n_chunks, n_data_chunks);
-  for (uint32_t c = 0; c < n_data_chunks; ++c) {
-    if (dict->chunks[c].n_entries != data_column->host_segments[c].aux_size)
-      return fail(HY_ERR_INVALID, "hy_table_scan_like: chunk %u: the dictionary has %u entries, the segment's has %u", c, dict->chunks[c].n_entries, data_column->host_segments[c].aux_size);
-  }
-  if (column->multi_chunk_reference && result->mem == HY_MEM_DEVICE && !result->counts) {
-    return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
-  }
+  if (column->data_type != HY_TYPE_STRING && column->n_chunks) return fail(HY_ERR_INVALID, "%s: LIKE is only applicable on string columns (column type %u)", name, column->data_type);
+  HY_TRY(check_dictionary(dict, column, "", name));
+  HY_TRY(check_reorder_counts(column, result));
   hy_predicate predicate;
   std::memset(&predicate, 0, sizeof(predicate));
   predicate.condition = condition;
   predicate.value_type = HY_TYPE_STRING;
   predicate.column_is_nullable = column_is_nullable;
-  const DeviceLike device_like{dict, &program};
-  return run_scan(column, nullptr, &predicate, 0, excluded_chunks, n_excluded, result, nullptr, nullptr, &device_like);
+  ScanRequest request = scan_request(column, ScanSource::DeviceLike, excluded_chunks, n_excluded);
+  request.predicate = &predicate;
+  request.like = DeviceLike{dict, &program};
+  return run_scan(request, result);
 }
 
 hy_status hy_table_scan_in_list(const hy_column* column, const hy_in_list* list, const uint32_t* excluded_chunks, uint32_t n_excluded, hy_scan_result* result) {
   if (!column || !list || !result) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: null argument");
   HY_TRY(on_this_device(column, "hy_table_scan_in_list"));
-  if (n_excluded && !excluded_chunks) return fail(HY_ERR_INVALID, "hy_table_scan_in_list: excluded chunk list missing");
-  for (uint32_t i = 0; i < n_excluded; ++i) {
-    if (excluded_chunks[i] >= column->n_chunks) return fail(HY_ERR_INVALID, "excluded chunk id %u out of range", excluded_chunks[i]);
-  }
+  HY_TRY(check_excluded(column, excluded_chunks, n_excluded, "hy_table_scan_in_list"));
   InListArgs args;
   HY_TRY(check_in_list(column, list, args));
-  if (column->multi_chunk_reference && result->mem == HY_MEM_DEVICE && !result->counts) {
-    return fail(HY_ERR_INVALID, "scans of pos lists that span several chunks need result->counts (their matches are re-ordered by referenced chunk)");
-  }
-  hy_predicate predicate;
-  std::memset(&predicate, 0, sizeof(predicate));
-  predicate.condition = list->negated ? HY_PRED_NOT_IN : HY_PRED_IN;
-  predicate.value_type = list->value_type;
-  predicate.column_is_nullable = list->column_is_nullable;
-  return run_scan(column, nullptr, &predicate, 0, excluded_chunks, n_excluded, result, nullptr, &args);
+  HY_TRY(check_reorder_counts(column, result));
+  ScanRequest request = scan_request(column, ScanSource::InList, excluded_chunks, n_excluded);
+  request.in_list = &args;
+  return run_scan(request, result);
 }
 
 hy_status hy_validate(const hy_column* mvcc, uint32_t our_tid, uint32_t snapshot_commit_id, uint32_t can_use_chunk_shortcut, hy_scan_result* result) {
   if (!mvcc || !result) return fail(HY_ERR_INVALID, "hy_validate: null argument");
   const hy_column* data = mvcc->is_reference ? mvcc->ref : mvcc;
   if (!data || !data->is_mvcc) return fail(HY_ERR_INVALID, "hy_validate needs a column of HY_ENC_MVCC segments (or reference segments into one)");
-  const VisibilityArgs visibility{our_tid, snapshot_commit_id, can_use_chunk_shortcut};
-  return run_scan(mvcc, nullptr, nullptr, 0, nullptr, 0, result, &visibility);
+  ScanRequest request = scan_request(mvcc, ScanSource::Visibility);
+  request.visibility = VisibilityArgs{our_tid, snapshot_commit_id, can_use_chunk_shortcut};
+  return run_scan(request, result);
 }
 
 hy_status hy_table_scan_columns(const hy_column* left, const hy_column* right, uint32_t condition,
@@ -2722,15 +2853,13 @@ hy_status hy_table_scan_columns(const hy_column* left, const hy_column* right, u
   if (!left || !right || !result) return fail(HY_ERR_INVALID, "hy_table_scan_columns: null argument");
   HY_TRY(on_this_device(left, "hy_table_scan_columns"));
   HY_TRY(on_this_device(right, "hy_table_scan_columns"));
-  if (left->is_mvcc || right->is_mvcc || (left->ref && left->ref->is_mvcc) || (right->ref && right->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
-  if (condition > HY_PRED_GREATER_THAN_EQUALS) return fail(HY_ERR_INVALID, "ColumnVsColumn supports binary comparisons only");
-  if (left->n_chunks != right->n_chunks) return fail(HY_ERR_INVALID, "columns of one table must have the same chunk count");
-  for (uint32_t c = 0; c < left->n_chunks; ++c) {
-    if (left->host_segments[c].size != right->host_segments[c].size) return fail(HY_ERR_INVALID, "chunk %u: segment sizes differ", c);
-  }
+  HY_TRY(check_column_pair(left, right, condition));
   if (left->data_type == HY_TYPE_STRING || right->data_type == HY_TYPE_STRING)
     return fail(HY_ERR_UNSUPPORTED, "string ColumnVsColumn scans need the columns' dictionaries: hy_table_scan_columns_strings");
-  return run_scan(left, right, nullptr, condition, nullptr, 0, result);
+  ScanRequest request = scan_request(left, ScanSource::TwoColumns);
+  request.right = right;
+  request.condition = condition;
+  return run_scan(request, result);
 }
 
 hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_dictionary* left_dict, const hy_column* right, const hy_string_dictionary* right_dict,
@@ -2739,12 +2868,7 @@ hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_d
   if (!left || !left_dict || !right || !right_dict || !result) return fail(HY_ERR_INVALID, "%s: null argument", name);
   HY_TRY(on_this_device(left, name));
   HY_TRY(on_this_device(right, name));
-  if (left->is_mvcc || right->is_mvcc || (left->ref && left->ref->is_mvcc) || (right->ref && right->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
-  if (condition > HY_PRED_GREATER_THAN_EQUALS) return fail(HY_ERR_INVALID, "ColumnVsColumn supports binary comparisons only");
-  if (left->n_chunks != right->n_chunks) return fail(HY_ERR_INVALID, "columns of one table must have the same chunk count");
-  for (uint32_t c = 0; c < left->n_chunks; ++c) {
-    if (left->host_segments[c].size != right->host_segments[c].size) return fail(HY_ERR_INVALID, "chunk %u: segment sizes differ", c);
-  }
+  HY_TRY(check_column_pair(left, right, condition));
   // column_vs_column_table_scan_impl.cpp:153-155
   if ((left->data_type != HY_TYPE_STRING || right->data_type != HY_TYPE_STRING) && left->n_chunks)
     return fail(HY_ERR_INVALID, "%s: trying to compare strings and non-strings (column types %u and %u)", name, left->data_type, right->data_type);
@@ -2754,25 +2878,14 @@ hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_d
     const hy_segment &l = left->host_segments[c], &r = right->host_segments[c];
     if (l.ref_chunk_id != r.ref_chunk_id || !l.data != !r.data) return fail(HY_ERR_INVALID, "%s: chunk %u: the reference columns hold different PosLists", name, c);
   }
-  const hy_column* data_columns[2] = {left->is_reference ? left->ref : left, right->is_reference ? right->ref : right};
-  const hy_string_dictionary* dicts[2] = {left_dict, right_dict};
-  for (int side = 0; side < 2; ++side) {
-    const hy_column* data_column = data_columns[side];
-    const uint32_t n_data_chunks = data_column ? data_column->n_chunks : 0;
-    for (uint32_t c = 0; c < n_data_chunks; ++c) {
-      if (data_column->host_segments[c].encoding != HY_ENC_DICTIONARY) return fail(HY_ERR_UNSUPPORTED, "%s: unencoded string segments stay on the CPU path", name);
-    }
-    if (dicts[side]->device != left->device) return fail(HY_ERR_INVALID, "%s: a dictionary lives on device %d, the columns on device %d", name, dicts[side]->device, left->device);
-    if (dicts[side]->n_chunks != n_data_chunks) return fail(HY_ERR_INVALID, "%s: the %s dictionary has %u chunks, the data column %u", name, side ? "right" : "left", dicts[side]->n_chunks, n_data_chunks);
-    for (uint32_t c = 0; c < n_data_chunks; ++c) {
-      if (dicts[side]->chunks[c].n_entries != data_column->host_segments[c].aux_size)
-        return fail(HY_ERR_INVALID, "%s: chunk %u: the %s dictionary has %u entries, the segment's has %u", name, c, side ? "right" : "left", dicts[side]->chunks[c].n_entries,
-                    data_column->host_segments[c].aux_size);
-    }
-  }
+  HY_TRY(check_dictionary(left_dict, left, "left ", name));
+  HY_TRY(check_dictionary(right_dict, right, "right ", name));
   HY_TRY(string_order_check(left_dict, right_dict, name));
-  const StringPair strings{left_dict, right_dict};
-  return run_scan(left, right, nullptr, condition, nullptr, 0, result, nullptr, nullptr, nullptr, &strings);
+  ScanRequest request = scan_request(left, ScanSource::TwoStringColumns);
+  request.right = right;
+  request.condition = condition;
+  request.strings = StringPair{left_dict, right_dict};
+  return run_scan(request, result);
 }
 
 hy_status hy_poslist_translate(const hy_column* scanned, const hy_scan_result* result, uint32_t layout, hy_row_id* out, uint64_t capacity, uint64_t* n_out) {

@@ -141,28 +141,33 @@ hy_status hy_table_scan_expression(const hy_projection_program* program, const u
 
   hipStream_t stream = current_stream();
   Scratch& sc = scratch();
-  // Scratch: nodes | excluded flags | (host results) regions + per-chunk arrays + the dense copy regions_to_host_result carves
-  size_t need = sizeof(prepared.nodes) + n_chunks + 4 * 256;
-  if (host_result) need += 2 * sizeof(hy_row_id) * (shape->rows + 1) + 3 * 8 * (size_t{n_chunks} + 2) + 4 * (size_t{n_chunks} + 1) + n_chunks + 8192;
-  HY_TRY(sc.reserve(need + 16 * 256));
+  // Scratch: nodes | excluded flags | (host results) the regions, and the dense copy regions_to_host_result takes behind them -- sized by
+  // a dry run of the layout
+  ExprNode* d_nodes = nullptr;
+  uint8_t* d_excluded = nullptr;
+  ScanRegions regions{result->matches, result->offsets, result->counts, result->chunk_state};
+  auto layout = [&](Carver& carver) {
+    d_nodes = carver.take<ExprNode>(HY_MAX_PROJECTION_NODES);
+    d_excluded = n_excluded ? carver.take<uint8_t>(n_chunks) : nullptr;
+    if (host_result) scan_regions_layout(carver, n_chunks, shape->rows, regions);
+  };
+  Carver sizing;
+  DenseRegions dense;
+  layout(sizing);
+  if (host_result) dense_regions_layout(sizing, n_chunks, shape->rows, dense);
+  HY_TRY(sc.reserve(sizing.used));
   auto drain = [&](hy_status status) { (void)hipStreamSynchronize(stream); return status; };   // (uploads from this call's host arrays may be queued)
   {
     const hy_status status = prepare_program_tests(&prepared);
     if (status != HY_OK) return drain(status);
   }
-  ExprNode* d_nodes = carve<ExprNode>(sc, HY_MAX_PROJECTION_NODES);
-  uint8_t* d_excluded = n_excluded ? carve<uint8_t>(sc, n_chunks) : nullptr;
-  hy_row_id* d_matches = result->matches;
-  uint64_t* d_offsets = result->offsets;
-  uint32_t* d_counts = result->counts;
-  uint8_t* d_state = result->chunk_state;
-  if (host_result) {
-    d_matches = carve<hy_row_id>(sc, shape->rows + 1);
-    d_offsets = carve<uint64_t>(sc, size_t{n_chunks} + 2);
-    d_counts = carve<uint32_t>(sc, size_t{n_chunks} + 1);
-    d_state = carve<uint8_t>(sc, size_t{n_chunks} + 1);
-  }
-  if (!d_nodes || (n_excluded && !d_excluded) || (host_result && (!d_matches || !d_offsets || !d_counts || !d_state))) return drain(fail(HY_ERR_DEVICE, "scratch arena exhausted"));
+  Carver carver{&sc};
+  layout(carver);
+  if (carver.failed) return drain(fail(HY_ERR_DEVICE, "scratch arena exhausted"));
+  hy_row_id* d_matches = regions.matches;
+  uint64_t* d_offsets = regions.offsets;
+  uint32_t* d_counts = regions.counts;
+  uint8_t* d_state = regions.state;
   if (hipMemcpyAsync(d_nodes, prepared.nodes, sizeof(prepared.nodes), hipMemcpyHostToDevice, stream) != hipSuccess ||
       (n_excluded && hipMemcpyAsync(d_excluded, excluded.data(), n_chunks, hipMemcpyHostToDevice, stream) != hipSuccess)) {
     return drain(fail(HY_ERR_DEVICE, "hy_table_scan_expression: upload of the program failed"));

@@ -1072,7 +1072,8 @@ hy_status hy_scan_project_aggregate(const hy_filter* filters, uint32_t n_filters
  * without NULLs) every dimension is probed in ONE pass over the fact table instead (csrc/join_star.hpp, HY_OPT_STAR_FUSED_PROBE): the join
  * result's rows -- and with them the groups, ordered by their first row -- then come in the fact table's row order, not in the order the
  * last JoinHash of the chain would leave them in.  Where, in addition, every GROUP BY column (one to four) and every aggregate input (at most
- * four aggregates: MIN / MAX / SUM / AVG / COUNT) is an int / long column, the Projection and the AggregateHash happen inside that join
+ * eight aggregates: MIN / MAX / SUM / AVG / COUNT) is an int / long column -- at most four distinct columns of the fact table and four of
+ * the dimensions among them, and at most 4096 groups --, the Projection and the AggregateHash happen inside that join
  * (HY_OPT_STAR_FUSED_FINISH): the rows that survive every dimension are grouped where they are found; same groups, order, cells and
  * representative rows as the steps it replaces.
  * Columns are named as (table, column): table 0 = the fact table, d + 1 = dimension d; every column is a DATA column (numeric, or a
