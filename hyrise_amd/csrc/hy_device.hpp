@@ -339,6 +339,11 @@ struct DeviceBuffer {
   DeviceBuffer& operator=(const DeviceBuffer&) = delete;
   template <typename T> T* as() const { return static_cast<T*>(ptr); }
 };
+inline void swap(DeviceBuffer& a, DeviceBuffer& b) {   // the blocks change owners, nothing is given back
+  std::swap(a.ptr, b.ptr);
+  std::swap(a.capacity, b.capacity);
+  std::swap(a.borrowed, b.borrowed);
+}
 
 
 // ---- aggregate.hip: which path a GROUP BY should take, for callers whose input columns do not live long enough to remember it themselves

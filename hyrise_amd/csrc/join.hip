@@ -3265,439 +3265,500 @@ struct BuildSide {
   bool any_null = false;
 };
 
-// Materialise + (sort) + directory.  `bloom_in` (device) filters the build side (no observable effect, kept for the
-// reference's element counts); `bloom_out` receives the build side's filter if wanted.
-// `existence_only`: the join only asks whether a key exists (Semi / Anti without secondary predicates -- the reference's
-// ExistenceOnly hash table, join_hash_steps.hpp:97-236): a sorted dense build column WITH duplicates still gets a rank table, of
-// which only the presence bits mean anything.
-// `bit_filter_ok`: whoever probes reads the Bloom filter as 2^20 bits (the kernels of join_pkfk.hpp) -- what the one-pass hinted build
-// produces; everything else reads one byte per bit.
-static hy_status prepare_build(const hy_column* build, bool keep_nulls, bool want_bloom, bool want_ids32, uint32_t hashed_type, bool allow_rank_table, bool existence_only,
-                               bool bit_filter_ok, BuildSide& b, hipStream_t stream) {
-  const uint32_t n_slices = build->n_slices;
-  DeviceBuffer counts, offsets;
-  HY_TRY(counts.alloc(4 * size_t{n_slices + 1}));
-  HY_TRY(offsets.alloc(8 * size_t{n_slices + 2}));
-  HY_TRY(b.flags.alloc(64));
-  // (decided here, before anything is launched: a hinted build zeroes its table and the Bloom filter with one launch)
-  bool dense = hashed_type == 0;   // a column whose segments cannot hold NULLs; float / double keys go through the generic decoder
-  for (uint32_t c = 0; c < build->n_chunks && dense; ++c) {
-    const hy_segment& seg = build->host_segments[c];
-    dense = (seg.encoding == HY_ENC_UNENCODED || seg.encoding == HY_ENC_FRAME_OF_REFERENCE) && seg.nulls == nullptr;
+// One instantiation per (key width, RowID width) of a materialised build side: f(BuildTypes<KEY32, ID32>{}) with the stored types as T::Key / T::Row
+template <bool KEY32, bool ID32>
+struct BuildTypes {
+  static constexpr bool key32 = KEY32, id32 = ID32;
+  using Key = typename BuildKey<KEY32>::type;
+  using Row = typename BuildRow<ID32>::type;
+};
+template <typename F>
+static auto with_build_types(bool key32, bool id32, F&& f) {
+  if (key32 && id32) return f(BuildTypes<true, true>{});
+  if (key32) return f(BuildTypes<true, false>{});
+  if (id32) return f(BuildTypes<false, true>{});
+  return f(BuildTypes<false, false>{});
+}
+template <typename F>
+static auto with_key_type(bool key32, F&& f) {   // ... and where only the keys are read: f(uint32_t{}) or f(uint64_t{})
+  return key32 ? f(uint32_t{}) : f(uint64_t{});
+}
+
+static hy_status raise_sort_scatter_staged_lds() {
+  static OncePerDevice raised;
+  uint64_t device_bit = 0;
+  if (raised.pending(&device_bit)) {
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sort_scatter_staged), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sort_staged_lds_bytes())));
+    raised.done(device_bit);
   }
-  bool uniform_chunks = dense && build->n_chunks > 0;
-  for (uint32_t c = 1; c < build->n_chunks && uniform_chunks; ++c) {
+  return HY_OK;
+}
+
+// Stable LSD radix sort of n (key, row) pairs by key, one pass per byte whose bit is set in `moving_bytes` (bit i: key bits 8 i .. 8 i + 7).
+// *keys / *rows point at the sorted arrays on return: the inputs or the temporaries.  `staged`: 32-bit keys and rows on a device with
+// lane-ordered LDS atomics (sort_scatter_staged: 8192-element tiles, runs instead of scattered stores).
+static hy_status lsd_sort_passes(bool key32, bool id32, bool staged, void** keys, void** rows, void* keys_tmp, void* rows_tmp, uint64_t n, uint32_t moving_bytes, hipStream_t stream) {
+  const uint32_t n_tiles = static_cast<uint32_t>(staged ? (n + SORT_BIG_TILE - 1) / SORT_BIG_TILE : (n + SORT_TILE - 1) / SORT_TILE);
+  if (staged) HY_TRY(raise_sort_scatter_staged_lds());
+  DeviceBuffer hist, bases;
+  HY_TRY(hist.alloc(4 * size_t{256} * n_tiles));
+  HY_TRY(bases.alloc(8 * (size_t{256} * n_tiles + 1)));
+  void *src_keys = *keys, *src_rows = *rows, *dst_keys = keys_tmp, *dst_rows = rows_tmp;
+  for (uint32_t shift = 0; shift < (key32 ? 32u : 64u); shift += 8) {
+    if (!((moving_bytes >> (shift / 8)) & 1)) continue;
+    if (staged) hipLaunchKernelGGL(sort_histogram_big, dim3(n_tiles), dim3(SORT_BIG_THREADS), 0, stream, static_cast<const uint32_t*>(src_keys), n, shift, hist.as<uint32_t>(), n_tiles);
+    else with_key_type(key32, [&](auto key) {
+      hipLaunchKernelGGL(sort_histogram<decltype(key)>, dim3(n_tiles), dim3(256), 0, stream, static_cast<const decltype(key)*>(src_keys), n, shift, hist.as<uint32_t>(), n_tiles);
+    });
+    HY_TRY(exclusive_scan(hist.as<uint32_t>(), bases.as<uint64_t>(), uint64_t{256} * n_tiles, stream));
+    if (staged) hipLaunchKernelGGL(sort_scatter_staged, dim3(n_tiles), dim3(SORT_BIG_THREADS), sort_staged_lds_bytes(), stream, static_cast<const uint32_t*>(src_keys), static_cast<const uint32_t*>(src_rows),
+                                   static_cast<uint32_t*>(dst_keys), static_cast<uint32_t*>(dst_rows), n, shift, bases.as<uint64_t>(), n_tiles);
+    else with_build_types(key32, id32, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((sort_scatter<typename T::Key, typename T::Row>), dim3(n_tiles), dim3(256), 0, stream, static_cast<const typename T::Key*>(src_keys), static_cast<const typename T::Row*>(src_rows),
+                         static_cast<typename T::Key*>(dst_keys), static_cast<typename T::Row*>(dst_rows), n, shift, bases.as<uint64_t>(), n_tiles);
+    });
+    std::swap(src_keys, dst_keys);
+    std::swap(src_rows, dst_rows);
+  }
+  *keys = src_keys;
+  *rows = src_rows;
+  return HY_OK;
+}
+
+// ---- the build side, step by step ---------------------------------------------------------------------------------------------------------
+// What the caller wants of it.  `bloom`: the build side's filter is applied to the probe side (no observable effect, kept for the
+// reference's element counts).  `existence_only`: the join only asks whether a key exists (Semi / Anti without secondary predicates -- the
+// reference's ExistenceOnly hash table, join_hash_steps.hpp:97-236): a sorted dense build column WITH duplicates still gets a rank table,
+// of which only the presence bits mean anything.  `bit_filter_ok`: whoever probes reads the Bloom filter as 2^20 bits (the kernels of
+// join_pkfk.hpp) -- what the one-pass hinted build produces; everything else reads one byte per bit.
+struct BuildWants {
+  bool keep_nulls, bloom, ids32, allow_rank_table, existence_only, bit_filter_ok;
+  uint32_t hashed_type;
+};
+
+// What the host knows of the column before anything is launched (a hinted build zeroes its table and the Bloom filter with one launch).
+struct BuildPlan {
+  bool dense = false;               // no segment can hold NULLs (value / FrameOfReference segments without a null vector): every row is materialised
+  bool uniform_chunks = false;      // ... and the chunks are equally long (the last may be shorter), none empty: the build row of rank r is row r of the table
+  bool identity_candidate = false;  // ... and the column may be a primary key: look at it in place first
+  bool hinted = false;              // ... and an earlier join left its key range behind: fill the table in one pass that checks it
+  bool key32 = false, id32 = false; // the materialised arrays' element widths
+};
+
+static BuildPlan plan_build(const hy_column* build, const BuildWants& wants) {
+  BuildPlan plan;
+  plan.dense = wants.hashed_type == 0;   // (float / double keys go through the generic decoder)
+  for (uint32_t c = 0; c < build->n_chunks && plan.dense; ++c) {
+    const hy_segment& seg = build->host_segments[c];
+    plan.dense = (seg.encoding == HY_ENC_UNENCODED || seg.encoding == HY_ENC_FRAME_OF_REFERENCE) && seg.nulls == nullptr;
+  }
+  plan.uniform_chunks = plan.dense && build->n_chunks > 0 && build->host_segments[0].size > 0;
+  for (uint32_t c = 1; c < build->n_chunks && plan.uniform_chunks; ++c) {
     const uint32_t size = build->host_segments[c].size, first_size = build->host_segments[0].size;
-    uniform_chunks = first_size > 0 && (c + 1 == build->n_chunks ? size <= first_size : size == first_size);
+    plan.uniform_chunks = c + 1 == build->n_chunks ? size <= first_size : size == first_size;
   }
-  const bool identity_candidate = dense && build->rows && uniform_chunks && build->host_segments[0].size > 0 && allow_rank_table && option(HY_OPT_JOIN_RANK_TABLE) &&
-                                  FIXED_JOIN_IDENTITY;
-  bool hinted = identity_candidate && bit_filter_ok && build->join_hint.state.load(std::memory_order_acquire) == 1 &&
-                (existence_only || build->join_hint.unique.load(std::memory_order_relaxed)) && option(HY_OPT_JOIN_HINT);
-  for (uint32_t c = 0; c < build->n_chunks && hinted; ++c) {   // rank_table_fill_checked reads int32 keys through SliceViews, 16 bytes per load
+  plan.identity_candidate = plan.uniform_chunks && build->rows && wants.allow_rank_table && option(HY_OPT_JOIN_RANK_TABLE) && FIXED_JOIN_IDENTITY;
+  plan.hinted = plan.identity_candidate && wants.bit_filter_ok && build->join_hint.state.load(std::memory_order_acquire) == 1 &&
+                (wants.existence_only || build->join_hint.unique.load(std::memory_order_relaxed)) && option(HY_OPT_JOIN_HINT);
+  for (uint32_t c = 0; c < build->n_chunks && plan.hinted; ++c) {   // the hinted fills read int32 keys through SliceViews, 16 bytes per load
     const hy_segment& seg = build->host_segments[c];
-    hinted = reinterpret_cast<uintptr_t>(seg.data) % 16 == 0 && ((seg.encoding == HY_ENC_UNENCODED && seg.data_type == HY_TYPE_INT) || seg.encoding == HY_ENC_FRAME_OF_REFERENCE);
+    plan.hinted = reinterpret_cast<uintptr_t>(seg.data) % 16 == 0 && ((seg.encoding == HY_ENC_UNENCODED && seg.data_type == HY_TYPE_INT) || seg.encoding == HY_ENC_FRAME_OF_REFERENCE);
   }
-  if (want_bloom) {
-    HY_TRY(b.bloom.alloc(BLOOM_BITS));
-    if (!hinted) HY_HIP(hipMemsetAsync(b.bloom.ptr, 0, BLOOM_BITS, stream));
-  }
+  plan.key32 = build->data_type == HY_TYPE_INT && wants.hashed_type == 0;
+  plan.id32 = wants.ids32;
+  return plan;
+}
+
+// One build side under construction: what the steps below hand to each other.
+struct BuildJob {
+  const hy_column* column;
+  BuildWants wants;
+  BuildPlan plan;
+  BuildSide& b;
+  hipStream_t stream;
   MaterializeArgs m{};
-  m.segments = build->d_segments;
-  m.views = build->d_slice_views;
-  m.slices = build->d_slices;
-  m.n_slices = n_slices;
-  m.keep_nulls = keep_nulls;
-  m.bloom_in = nullptr;
-  m.bloom_out = want_bloom ? b.bloom.as<uint8_t>() : nullptr;
-  m.slice_counts = counts.as<uint32_t>();
-  m.any_null = b.flags.as<uint32_t>() + 2;
-  m.hashed_type = hashed_type;
-  uint64_t total = 0;
-  // A column whose segments cannot hold NULLs (value / FrameOfReference segments without a null vector) materialises
-  // every row: slice offsets are row numbers, no counting pass and no host round trip.
-  if (n_slices && dense) {
-    m.row_base = build->d_row_base;
-    total = build->rows;
-  } else if (n_slices) {
-    hipLaunchKernelGGL((join_materialize<0, false, false>), dim3(n_slices), dim3(256), 0, stream, m);
-    hipLaunchKernelGGL(scan_counts, dim3(1), dim3(1024), 0, stream, counts.as<uint32_t>(), offsets.as<uint64_t>(), n_slices);
-    HY_HIP(hipMemcpyAsync(&total, offsets.as<uint64_t>() + n_slices, 8, hipMemcpyDeviceToHost, stream));
-    HY_HIP(hipStreamSynchronize(stream));
+  DeviceBuffer counts, offsets;
+  uint64_t total = 0;   // rows that are materialised
+};
+
+static void identity_table(BuildJob& job, u32x2_t* entries, uint64_t key_min, uint64_t key_max) {
+  BuildSide& b = job.b;
+  b.rank.entries = entries;
+  b.rank.key_min = key_min;
+  b.rank.range = key_max - key_min;
+  b.rank.identity_rows = job.column->host_segments[0].size;
+  b.rank.identity_inverse = 1.0 / static_cast<double>(b.rank.identity_rows);
+  Directory& d = b.directory;   // nothing but the extent: the probe needs neither keys nor RowIDs
+  d = Directory{};
+  d.n = job.total;
+  d.key_min = key_min;
+  d.key_max = key_max;
+  d.n_buckets = 1;
+}
+
+// The table and the filter of a hinted wave fill: one of the thread's two zeroed blocks (ZeroedBlocks), whose partner this join's pk_emit
+// clears.  All transitions of t_zeroed happen here and in block_cleaning_queued.  *taken = false: the blocks do not apply (a table of 2^31
+// vectors) -- the caller zeroes a block of its own.
+static hy_status take_zeroed_block(BuildJob& job, size_t table_vectors, size_t bloom_vectors, bool* taken) {
+  BuildSide& b = job.b;
+  hipStream_t stream = job.stream;
+  *taken = false;
+  if (!FIXED_JOIN_CLEAN_TABLES || table_vectors + bloom_vectors >= (1ull << 31)) return HY_OK;
+  if ((t_zeroed[0].table && t_zeroed[0].stream != stream) || (t_zeroed[1].table && t_zeroed[1].stream != stream)) {   // another stream: start over
+    HY_HIP(hipDeviceSynchronize());
+    free_zeroed_blocks();
   }
-  b.n = total;
-  // A dense column that may be a primary key: look at it in place first (statistics), and if it is sorted, duplicate-free
-  // and not too sparse fill the rank table from it -- no key array, no RowID array (a key's rank is its row number).
-  if (identity_candidate && total) {
-    auto identity_table = [&](u32x2_t* entries, uint64_t key_min, uint64_t key_max) {
-      b.rank.entries = entries;
-      b.rank.key_min = key_min;
-      b.rank.range = key_max - key_min;
-      b.rank.identity_rows = build->host_segments[0].size;
-      b.rank.identity_inverse = 1.0 / static_cast<double>(b.rank.identity_rows);
-      Directory& d = b.directory;   // nothing but the extent: the probe needs neither keys nor RowIDs
-      d = Directory{};
-      d.n = total;
-      d.key_min = key_min;
-      d.key_max = key_max;
-      d.n_buckets = 1;
-    };
-    if (hinted) {
-      const MaterializeArgs& m_in = m;
-      // an earlier join over this column found a primary key in [key_min, key_max]: one pass fills the table and checks every key
-      const uint64_t key_min = build->join_hint.key_min.load(std::memory_order_relaxed);
-      uint64_t key_max = build->join_hint.key_max.load(std::memory_order_relaxed);
-      if (option(HY_OPT_JOIN_BREAK_HINT) && key_max - key_min > 64) key_max -= 64;   // tests: a hint that does not hold
-      const uint64_t origin = key_min & ~uint64_t{31};   // (the table starts at a multiple of 32: a key's bit in its table word is its bit in the Bloom filter's word)
-      const uint64_t words = ((key_max - origin) >> 5) + 1;
-      const size_t ticket_bytes = 128 * (size_t{CHECKED_FILL_TICKETS} + 1);
-      const size_t table_bytes = 8 * (words + 2) + ticket_bytes + 64;   // the table | the arrival counters | the verdict
-      const size_t table_vectors = (table_bytes + 15) / 16, bloom_vectors = want_bloom ? BLOOM_BITS / 8 / 16 : 0;   // (the filter as bits: 128 KB)
-      const uint32_t stream_width = build->stream_width == 1 || build->stream_width == 2 || build->stream_width == 4 ? build->stream_width : 0;
-      const bool wave_fill = stream_width && option(HY_OPT_JOIN_FILL_WGS_PER_CU) > 0;
-      HY_TRY(b.partials.alloc(32 * (size_t{n_slices} * FW_STEPS_PER_SLICE / 4 + 1)));   // one record per workgroup: per slice (rank_table_fill_checked), or per four waves of >= 1 step (rank_table_fill_waves)
-      // The table and the filter: one of the thread's two zeroed blocks (ZeroedBlocks), whose partner this join's pk_emit clears -- or,
-      // where that does not apply (the first joins of a thread, a table that outgrew its block, the per-slice fill kernel), a block
-      // zeroed by a launch of its own.
-      FillCleaning cleaning{nullptr, nullptr, 0, 0};
-      ZeroedBlocks* cleaned = nullptr;
-      bool zeroed = false;
-      if (wave_fill && FIXED_JOIN_CLEAN_TABLES && table_vectors + bloom_vectors < (1ull << 31)) {
-        if ((t_zeroed[0].table && t_zeroed[0].stream != stream) || (t_zeroed[1].table && t_zeroed[1].stream != stream)) {   // another stream: start over
-          HY_HIP(hipDeviceSynchronize());
-          free_zeroed_blocks();
-        }
-        int mine = -1;
-        for (int i = 0; i < 2; ++i) if (t_zeroed[i].clean && t_zeroed[i].table_capacity >= 16 * table_vectors) mine = i;
-        if (mine < 0) {   // a block that is not waiting to be cleaned by this launch: (re)allocate it, zeroed by zero_vectors below
-          mine = !t_zeroed[0].table ? 0 : !t_zeroed[1].table ? 1 : t_zeroed[1].clean && !t_zeroed[0].clean ? 1 : 0;   // (both in use and neither cleared -- the join before took other kernels: block 0, cleared by a launch)
-          if (mine >= 0 && t_zeroed[mine].table_capacity < 16 * table_vectors) {
-            ZeroedBlocks& z = t_zeroed[mine];
-            if (z.table) { HY_HIP(hipStreamSynchronize(stream)); HY_HIP(hipFree(z.table)); z.table = nullptr; }
-            z.table_capacity = (16 * table_vectors * 5 / 4 + 4095) & ~size_t{4095};
-            HY_HIP(hipMalloc(&z.table, z.table_capacity));
-            if (!z.filter) HY_HIP(hipMalloc(&z.filter, BLOOM_BITS / 8));
-            z.stream = stream;
-            z.clean = false;
-            z.dirty_table = z.table_capacity;   // (never written: all of it is cleared once)
-            z.dirty_filter = BLOOM_BITS / 8;
-          }
-        }
-        if (mine >= 0) {
-          ZeroedBlocks& z = t_zeroed[mine];
-          ZeroedBlocks& other = t_zeroed[1 - mine];
-          if (!z.clean) {
-            hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>(std::min<size_t>(2048, (z.dirty_table / 16 + z.dirty_filter / 16 + 255) / 256))), dim3(256), 0, stream,
-                               static_cast<u32x4_t*>(z.table), z.dirty_table / 16, static_cast<u32x4_t*>(z.filter), z.dirty_filter / 16);
-          }
-          if (other.table && !other.clean) {   // this join's pk_emit clears what the join before left in the other block
-            cleaning = FillCleaning{static_cast<u32x4_t*>(other.table), static_cast<u32x4_t*>(other.filter), static_cast<uint32_t>(other.dirty_table / 16), static_cast<uint32_t>(other.dirty_filter / 16)};
-            cleaned = &other;   // (clean once the fill kernel is queued, below)
-          }
-          z.clean = false;
-          z.dirty_table = 16 * table_vectors;
-          z.dirty_filter = 16 * bloom_vectors;
-          b.rank_entries.borrow(z.table);
-          if (want_bloom) { b.bloom.borrow(z.filter); m.bloom_out = b.bloom.as<uint8_t>(); }
-          zeroed = true;
-        }
-      }
-      if (!zeroed) {
-        HY_TRY(b.rank_entries.alloc(table_bytes));
-        hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>(std::min<size_t>(2048, (table_vectors + bloom_vectors + 255) / 256))), dim3(256), 0, stream,
-                           b.rank_entries.as<u32x4_t>(), table_vectors, b.bloom.as<u32x4_t>(), bloom_vectors);
-      }
-      u32x2_t* entries = b.rank_entries.as<u32x2_t>();
-      BuildVerdict* verdict = reinterpret_cast<BuildVerdict*>(reinterpret_cast<char*>(entries + words + 2) + ticket_bytes);
-      MaterializeArgs m = m_in;
-      if (const char* debug = HY_DEBUG_ENV("HY_JOIN_FILL_DEBUG")) {   // timing experiments only (results are wrong): 1 no filter, 2 no table either
-        if (atoi(debug) & 1) m.bloom_out = nullptr;
-        if (atoi(debug) >= 2 && !option(HY_OPT_JOIN_FILL_WGS_PER_CU)) m.keep_nulls = 0xFFFFFFFFu;   // (rank_table_fill_checked: loads and extent only)
-      }
-      hipEvent_t fill_started = nullptr, fill_stopped = nullptr;
-      profile_events(&fill_started, &fill_stopped, HY_KERNEL_JOIN_BUILD);
-      // rank_table_fill_waves: as many waves as stay resident (at most the option's workgroups per CU), each with the same number of consecutive batches
-      uint32_t fill_waves = 0;
-      if (wave_fill) {
-        int per_cu = 0;
-        const void* kernel = stream_width == 4 ? reinterpret_cast<const void*>(rank_table_fill_waves<4>) : stream_width == 2 ? reinterpret_cast<const void*>(rank_table_fill_waves<2>) : reinterpret_cast<const void*>(rank_table_fill_waves<1>);
-        HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
-        fill_waves = 4 * device_cu_count() * static_cast<uint32_t>(std::max<int64_t>(1, std::min<int64_t>(per_cu, option(HY_OPT_JOIN_FILL_WGS_PER_CU))));
-      }
-      uint32_t fill_debug = 0;
-      if (const char* debug = HY_DEBUG_ENV("HY_JOIN_FILL_DEBUG")) fill_debug = static_cast<uint32_t>(atoi(debug));   // (wave kernel: 1 no filter, 2 no table stores, 4 no LDS work, 8 loads and checks only)
-      if (fill_waves) {
-        const uint32_t n_steps = n_slices * FW_STEPS_PER_SLICE, n_batches = (n_steps + FW_BATCH - 1) / FW_BATCH;
-        const uint32_t batches_per_wave = (n_batches + fill_waves - 1) / fill_waves, waves = (n_batches + batches_per_wave - 1) / batches_per_wave, groups = (waves + 3) / 4;
-        b.fill_records = b.partials.as<uint64_t>();
-        b.n_fill_records = groups;
-        if (stream_width == 4) hipExtLaunchKernelGGL(rank_table_fill_waves<4>, dim3(groups), dim3(256), 0, stream, fill_started, fill_stopped, 0, m, origin, key_max - origin, entries, b.partials.as<uint64_t>(), build->host_segments[0].size, batches_per_wave, n_steps, fill_debug);
-        else if (stream_width == 2) hipExtLaunchKernelGGL(rank_table_fill_waves<2>, dim3(groups), dim3(256), 0, stream, fill_started, fill_stopped, 0, m, origin, key_max - origin, entries, b.partials.as<uint64_t>(), build->host_segments[0].size, batches_per_wave, n_steps, fill_debug);
-        else hipExtLaunchKernelGGL(rank_table_fill_waves<1>, dim3(groups), dim3(256), 0, stream, fill_started, fill_stopped, 0, m, origin, key_max - origin, entries, b.partials.as<uint64_t>(), build->host_segments[0].size, batches_per_wave, n_steps, fill_debug);
-        b.cleaning = cleaning;   // (pk_emit clears the other block: run_join_once marks it clean when that launch is queued)
-        b.cleaned = cleaned;
-      } else
-      hipExtLaunchKernelGGL(rank_table_fill_checked, dim3(n_slices), dim3(256), 0, stream, fill_started, fill_stopped, 0, m, origin, key_max - origin, entries,
-                            b.partials.as<uint64_t>(), reinterpret_cast<uint32_t*>(entries + words + 2), verdict);
-      b.verdict = b.n_fill_records ? nullptr : verdict;
-      identity_table(entries, origin, key_max);
-      b.directory.key_min = key_min;
-      b.bloom_is_bits = want_bloom;
-      b.hinted = true;
-      b.hint_allows_duplicates = existence_only;
-      b.hint_min = key_min;
-      b.hint_max = key_max;
-      return HY_OK;
+  int mine = -1;
+  for (int i = 0; i < 2; ++i) if (t_zeroed[i].clean && t_zeroed[i].table_capacity >= 16 * table_vectors) mine = i;
+  if (mine < 0) {   // a block that is not waiting to be cleaned by this launch: (re)allocate it, zeroed by zero_vectors below
+    mine = !t_zeroed[0].table ? 0 : !t_zeroed[1].table ? 1 : t_zeroed[1].clean && !t_zeroed[0].clean ? 1 : 0;   // (both in use and neither cleared -- the join before took other kernels: block 0, cleared by a launch)
+    ZeroedBlocks& z = t_zeroed[mine];
+    if (z.table_capacity < 16 * table_vectors) {
+      if (z.table) { HY_HIP(hipStreamSynchronize(stream)); HY_HIP(hipFree(z.table)); z.table = nullptr; }
+      z.table_capacity = (16 * table_vectors * 5 / 4 + 4095) & ~size_t{4095};
+      HY_HIP(hipMalloc(&z.table, z.table_capacity));
+      if (!z.filter) HY_HIP(hipMalloc(&z.filter, BLOOM_BITS / 8));
+      z.stream = stream;
+      z.clean = false;
+      z.dirty_table = z.table_capacity;   // (never written: all of it is cleared once)
+      z.dirty_filter = BLOOM_BITS / 8;
     }
-    uint32_t first_slice = 0, last_slice = 0;   // slices with rows (the host knows the chunk sizes: slices are per chunk, in order)
-    {
-      std::vector<uint32_t> rows_of_slice;
-      for (uint32_t c = 0; c < build->n_chunks; ++c) {
-        const uint32_t size = build->host_segments[c].size;
-        const uint32_t chunk_slices = (size + SLICE_ROWS - 1) / SLICE_ROWS;
-        for (uint32_t i = 0; i < (chunk_slices ? chunk_slices : 1); ++i) rows_of_slice.push_back(size > i * SLICE_ROWS ? std::min(SLICE_ROWS, size - i * SLICE_ROWS) : 0);
-      }
-      if (rows_of_slice.size() != n_slices) return fail(HY_ERR_DEVICE, "join: slice table of the build column is inconsistent");
-      first_slice = n_slices;
-      for (uint32_t i = 0; i < n_slices; ++i) if (rows_of_slice[i]) { if (first_slice == n_slices) first_slice = i; last_slice = i; }
-    }
-    JoinMailbox* mailbox = nullptr;
-    JoinMailbox* mailbox_dev = nullptr;
-    HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
-    DeviceBuffer partials;
-    HY_TRY(partials.alloc(32 * size_t{n_slices}));
-    hipLaunchKernelGGL(dense_key_stats, dim3(n_slices), dim3(256), 0, stream, m, partials.as<uint64_t>());
-    hipLaunchKernelGGL(publish_dense_flags, dim3(1), dim3(256), 0, stream, partials.as<uint64_t>(), m, first_slice, last_slice, mailbox_dev);
-    HY_HIP(hipStreamSynchronize(stream));
-    const uint64_t key_min = mailbox->key_min, range = mailbox->key_max - mailbox->key_min;
-    const uint64_t words = (range >> 5) + 1;
-    if (HY_DEBUG_ENV("HY_JOIN_TIMING")) fprintf(stderr, "  dense stats: min %lld max %lld unsorted %u signed %u equal %u total %llu\n", (long long)mailbox->key_min, (long long)mailbox->key_max, mailbox->unsorted, mailbox->unsorted_signed, mailbox->equal_neighbours, (unsigned long long)total);
-    if (!mailbox->unsorted_signed && (!mailbox->equal_neighbours || existence_only) && range < 0xFFFFFF00ull && (words <= 2 * total + 4096 || words <= 65536)) {
-      HY_TRY(b.rank_entries.alloc(8 * (words + 1)));
-      u32x2_t* entries = b.rank_entries.as<u32x2_t>();
-      HY_HIP(hipMemsetAsync(entries, 0, 8 * (words + 1), stream));
-      hipLaunchKernelGGL(rank_table_fill_dense, dim3(n_slices), dim3(256), 0, stream, m, key_min, entries);
-      identity_table(entries, mailbox->key_min, mailbox->key_max);
-      if (build->join_hint.state.load(std::memory_order_acquire) == 0) {   // the next join over this column fills its table in one pass
-        build->join_hint.key_min.store(mailbox->key_min, std::memory_order_relaxed);
-        build->join_hint.key_max.store(mailbox->key_max, std::memory_order_relaxed);
-        build->join_hint.unique.store(mailbox->equal_neighbours ? 0u : 1u, std::memory_order_relaxed);
-        build->join_hint.state.store(1, std::memory_order_release);
-      }
-      return HY_OK;
-    }
-    // (not a primary key after all: materialise as usual)
   }
+  ZeroedBlocks& z = t_zeroed[mine];
+  ZeroedBlocks& other = t_zeroed[1 - mine];
+  if (!z.clean) {
+    hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>(std::min<size_t>(2048, (z.dirty_table / 16 + z.dirty_filter / 16 + 255) / 256))), dim3(256), 0, stream,
+                       static_cast<u32x4_t*>(z.table), z.dirty_table / 16, static_cast<u32x4_t*>(z.filter), z.dirty_filter / 16);
+  }
+  if (other.table && !other.clean) {   // this join's pk_emit clears what the join before left in the other block
+    b.cleaning = FillCleaning{static_cast<u32x4_t*>(other.table), static_cast<u32x4_t*>(other.filter), static_cast<uint32_t>(other.dirty_table / 16), static_cast<uint32_t>(other.dirty_filter / 16)};
+    b.cleaned = &other;   // (clean once pk_emit is queued: block_cleaning_queued)
+  }
+  z.clean = false;
+  z.dirty_table = 16 * table_vectors;
+  z.dirty_filter = 16 * bloom_vectors;
+  b.rank_entries.borrow(z.table);
+  if (job.wants.bloom) { b.bloom.borrow(z.filter); job.m.bloom_out = b.bloom.as<uint8_t>(); }
+  *taken = true;
+  return HY_OK;
+}
+
+static void block_cleaning_queued(BuildSide& b) {   // the join's last kernel, which clears b.cleaning, is in the stream
+  if (b.cleaned) { b.cleaned->clean = true; b.cleaned->dirty_table = b.cleaned->dirty_filter = 0; }
+}
+
+// rank_table_fill_waves<W> over a column whose segments are aligned W-byte vectors -- as many waves as stay resident (at most the option's
+// workgroups per CU), each with the same number of consecutive batches, one record per workgroup -- or rank_table_fill_checked, one
+// workgroup and one record per slice, its verdict behind the table's arrival counters.
+static hy_status launch_hinted_fill(BuildJob& job, uint32_t stream_width, uint64_t origin, uint64_t hint_range, u32x2_t* entries, uint32_t* tickets, BuildVerdict* verdict) {
+  BuildSide& b = job.b;
+  MaterializeArgs m = job.m;
+  const uint32_t n_slices = job.column->n_slices;
+  uint32_t fill_debug = 0;
+  if (const char* debug = HY_DEBUG_ENV("HY_JOIN_FILL_DEBUG")) {   // timing experiments only (results are wrong): 1 no filter, 2 no table either (wave kernel: 4 no LDS work, 8 loads and checks only)
+    fill_debug = static_cast<uint32_t>(atoi(debug));
+    if (fill_debug & 1) m.bloom_out = nullptr;
+    if (atoi(debug) >= 2 && !option(HY_OPT_JOIN_FILL_WGS_PER_CU)) m.keep_nulls = 0xFFFFFFFFu;   // (rank_table_fill_checked: loads and extent only)
+  }
+  hipEvent_t fill_started = nullptr, fill_stopped = nullptr;
+  profile_events(&fill_started, &fill_stopped, HY_KERNEL_JOIN_BUILD);
+  if (!stream_width) {
+    hipExtLaunchKernelGGL(rank_table_fill_checked, dim3(n_slices), dim3(256), 0, job.stream, fill_started, fill_stopped, 0, m, origin, hint_range, entries, b.partials.as<uint64_t>(), tickets, verdict);
+    b.verdict = verdict;
+    return HY_OK;
+  }
+  auto with_width = [&](auto f) { return stream_width == 4 ? f(std::integral_constant<uint32_t, 4>{}) : stream_width == 2 ? f(std::integral_constant<uint32_t, 2>{}) : f(std::integral_constant<uint32_t, 1>{}); };
+  int per_cu = 0;
+  HY_TRY(with_width([&](auto w) -> hy_status {
+    HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(rank_table_fill_waves<decltype(w)::value>), 256, 0));
+    return HY_OK;
+  }));
+  const uint32_t fill_waves = 4 * device_cu_count() * static_cast<uint32_t>(std::max<int64_t>(1, std::min<int64_t>(per_cu, option(HY_OPT_JOIN_FILL_WGS_PER_CU))));
+  const uint32_t n_steps = n_slices * FW_STEPS_PER_SLICE, n_batches = (n_steps + FW_BATCH - 1) / FW_BATCH;
+  const uint32_t batches_per_wave = (n_batches + fill_waves - 1) / fill_waves, waves = (n_batches + batches_per_wave - 1) / batches_per_wave, groups = (waves + 3) / 4;
+  b.fill_records = b.partials.as<uint64_t>();
+  b.n_fill_records = groups;
+  with_width([&](auto w) {
+    hipExtLaunchKernelGGL(rank_table_fill_waves<decltype(w)::value>, dim3(groups), dim3(256), 0, job.stream, fill_started, fill_stopped, 0, m, origin, hint_range, entries, b.partials.as<uint64_t>(),
+                          job.column->host_segments[0].size, batches_per_wave, n_steps, fill_debug);
+    return HY_OK;
+  });
+  return HY_OK;
+}
+
+// An earlier join over this column found a primary key in [key_min, key_max]: one pass fills the table and checks every key; pk_plan
+// compares the verdict with the hint when the join's kernels have run.
+static hy_status fill_hinted(BuildJob& job) {
+  BuildSide& b = job.b;
+  const hy_column* build = job.column;
+  const uint64_t key_min = build->join_hint.key_min.load(std::memory_order_relaxed);
+  uint64_t key_max = build->join_hint.key_max.load(std::memory_order_relaxed);
+  if (option(HY_OPT_JOIN_BREAK_HINT) && key_max - key_min > 64) key_max -= 64;   // tests: a hint that does not hold
+  const uint64_t origin = key_min & ~uint64_t{31};   // (the table starts at a multiple of 32: a key's bit in its table word is its bit in the Bloom filter's word)
+  const uint64_t words = ((key_max - origin) >> 5) + 1;
+  const size_t ticket_bytes = 128 * (size_t{CHECKED_FILL_TICKETS} + 1);
+  const size_t table_bytes = 8 * (words + 2) + ticket_bytes + 64;   // the table | the arrival counters | the verdict
+  const size_t table_vectors = (table_bytes + 15) / 16, bloom_vectors = job.wants.bloom ? BLOOM_BITS / 8 / 16 : 0;   // (the filter as bits: 128 KB)
+  uint32_t stream_width = build->stream_width == 1 || build->stream_width == 2 || build->stream_width == 4 ? build->stream_width : 0;
+  if (option(HY_OPT_JOIN_FILL_WGS_PER_CU) <= 0) stream_width = 0;   // (the per-slice fill)
+  HY_TRY(b.partials.alloc(32 * (size_t{build->n_slices} * FW_STEPS_PER_SLICE / 4 + 1)));   // one record per workgroup: per slice (rank_table_fill_checked), or per four waves of >= 1 step (rank_table_fill_waves)
+  // zeroed: by the join before (the wave fill's blocks) -- or, where that does not apply (the first joins of a thread, a table that outgrew
+  // its block, the per-slice fill kernel), by a launch of its own
+  bool zeroed = false;
+  if (stream_width) HY_TRY(take_zeroed_block(job, table_vectors, bloom_vectors, &zeroed));
+  if (!zeroed) {
+    HY_TRY(b.rank_entries.alloc(table_bytes));
+    hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>(std::min<size_t>(2048, (table_vectors + bloom_vectors + 255) / 256))), dim3(256), 0, job.stream,
+                       b.rank_entries.as<u32x4_t>(), table_vectors, b.bloom.as<u32x4_t>(), bloom_vectors);
+  }
+  u32x2_t* entries = b.rank_entries.as<u32x2_t>();
+  uint32_t* tickets = reinterpret_cast<uint32_t*>(entries + words + 2);
+  HY_TRY(launch_hinted_fill(job, stream_width, origin, key_max - origin, entries, tickets, reinterpret_cast<BuildVerdict*>(reinterpret_cast<char*>(tickets) + ticket_bytes)));
+  identity_table(job, entries, origin, key_max);
+  b.directory.key_min = key_min;
+  b.bloom_is_bits = job.wants.bloom;
+  b.hinted = true;
+  b.hint_allows_duplicates = job.wants.existence_only;
+  b.hint_min = key_min;
+  b.hint_max = key_max;
+  return HY_OK;
+}
+
+// A dense column that may be a primary key: look at it in place (statistics), and if it is sorted, duplicate-free and not too sparse fill
+// the rank table from it -- no key array, no RowID array (a key's rank is its row number) -- and leave its extent behind as the column's
+// key hint.  *built = false: not a primary key after all, materialise as usual.
+static hy_status fill_identity(BuildJob& job, bool* built) {
+  BuildSide& b = job.b;
+  const hy_column* build = job.column;
+  const uint32_t n_slices = build->n_slices;
+  *built = false;
+  uint32_t first_slice = n_slices, last_slice = 0, slice = 0;   // slices with rows (the host knows the chunk sizes: slices are per chunk, in order)
+  for (uint32_t c = 0; c < build->n_chunks; ++c) {
+    const uint32_t size = build->host_segments[c].size;
+    const uint32_t chunk_slices = std::max<uint32_t>(1, (size + SLICE_ROWS - 1) / SLICE_ROWS);
+    for (uint32_t i = 0; i < chunk_slices; ++i, ++slice) {
+      if (size <= i * SLICE_ROWS) continue;
+      if (first_slice == n_slices) first_slice = slice;
+      last_slice = slice;
+    }
+  }
+  if (slice != n_slices) return fail(HY_ERR_DEVICE, "join: slice table of the build column is inconsistent");
+  JoinMailbox* mailbox = nullptr;
+  JoinMailbox* mailbox_dev = nullptr;
+  HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
+  DeviceBuffer partials;
+  HY_TRY(partials.alloc(32 * size_t{n_slices}));
+  hipLaunchKernelGGL(dense_key_stats, dim3(n_slices), dim3(256), 0, job.stream, job.m, partials.as<uint64_t>());
+  hipLaunchKernelGGL(publish_dense_flags, dim3(1), dim3(256), 0, job.stream, partials.as<uint64_t>(), job.m, first_slice, last_slice, mailbox_dev);
+  HY_HIP(hipStreamSynchronize(job.stream));
+  const uint64_t key_min = mailbox->key_min, range = mailbox->key_max - mailbox->key_min;
+  const uint64_t words = (range >> 5) + 1;
+  if (HY_DEBUG_ENV("HY_JOIN_TIMING")) fprintf(stderr, "  dense stats: min %lld max %lld unsorted %u signed %u equal %u total %llu\n", (long long)mailbox->key_min, (long long)mailbox->key_max, mailbox->unsorted, mailbox->unsorted_signed, mailbox->equal_neighbours, (unsigned long long)job.total);
+  if (mailbox->unsorted_signed || (mailbox->equal_neighbours && !job.wants.existence_only) || range >= 0xFFFFFF00ull || !(words <= 2 * job.total + 4096 || words <= 65536)) return HY_OK;
+  HY_TRY(b.rank_entries.alloc(8 * (words + 1)));
+  u32x2_t* entries = b.rank_entries.as<u32x2_t>();
+  HY_HIP(hipMemsetAsync(entries, 0, 8 * (words + 1), job.stream));
+  hipLaunchKernelGGL(rank_table_fill_dense, dim3(n_slices), dim3(256), 0, job.stream, job.m, key_min, entries);
+  identity_table(job, entries, mailbox->key_min, mailbox->key_max);
+  if (build->join_hint.state.load(std::memory_order_acquire) == 0) {   // the next join over this column fills its table in one pass
+    build->join_hint.key_min.store(mailbox->key_min, std::memory_order_relaxed);
+    build->join_hint.key_max.store(mailbox->key_max, std::memory_order_relaxed);
+    build->join_hint.unique.store(mailbox->equal_neighbours ? 0u : 1u, std::memory_order_relaxed);
+    build->join_hint.state.store(1, std::memory_order_release);
+  }
+  *built = true;
+  return HY_OK;
+}
+
+// check_sorted + publish_build_flags over the materialised keys, and the round trip: the mailbox holds order, neighbours, extent and ends
+static hy_status look_at_keys(BuildJob& job, JoinMailbox* mailbox_dev) {
+  BuildSide& b = job.b;
+  const dim3 check_grid(static_cast<uint32_t>(std::min<uint64_t>((job.total + 1023) / 1024, 1024)));
+  with_key_type(job.plan.key32, [&](auto key) {
+    using K = decltype(key);
+    hipLaunchKernelGGL(check_sorted<K>, check_grid, dim3(1024), 0, job.stream, b.keys.as<K>(), job.total, b.flags.as<uint32_t>());
+    hipLaunchKernelGGL(publish_build_flags<K>, dim3(1), dim3(1), 0, job.stream, b.flags.as<uint32_t>(), b.keys.as<K>(), job.total, mailbox_dev);
+  });
+  HY_HIP(hipStreamSynchronize(job.stream));
+  return HY_OK;
+}
+
+// (key, RowID) of every row that takes part, in row order (32-bit keys: four entries of padding for the probe's 16-byte loads), and a
+// first look at them.  Nothing is launched for a build side without rows.
+static hy_status materialise_keys(BuildJob& job, JoinMailbox** mailbox, JoinMailbox** mailbox_dev) {
+  BuildSide& b = job.b;
+  const bool key32 = job.plan.key32, id32 = job.plan.id32;
+  HY_HIP(hipMemsetAsync(b.flags.ptr, 0, 64, job.stream));
+  HY_HIP(hipMemsetAsync(b.flags.as<uint32_t>() + 6, 0xFF, 8, job.stream));   // the running minimum
+  HY_TRY(b.keys.alloc((key32 ? 4 : 8) * (job.total + 4)));
+  HY_TRY(b.rows.alloc((id32 ? 4 : 8) * job.total));
+  if (!job.total) return HY_OK;
+  job.m.slice_offsets = job.offsets.as<uint64_t>();
+  job.m.keys = b.keys.ptr;
+  job.m.row_ids = b.rows.ptr;
+  const dim3 grid(job.column->n_slices);
+  with_build_types(key32, id32, [&](auto t) {
+    using T = decltype(t);
+    if (job.plan.dense) hipLaunchKernelGGL((join_materialize_dense<T::key32, T::id32>), grid, dim3(256), 0, job.stream, job.m);
+    else hipLaunchKernelGGL((join_materialize<1, T::key32, T::id32>), grid, dim3(256), 0, job.stream, job.m);
+  });
+  if (key32) HY_HIP(hipMemsetAsync(b.keys.as<uint32_t>() + job.total, 0, 16, job.stream));
+  HY_TRY(join_mailbox(mailbox, mailbox_dev));
+  HY_TRY(look_at_keys(job, *mailbox_dev));
+  b.any_null = (*mailbox)->any_null != 0;
+  return HY_OK;
+}
+
+// Unsorted unique 32-bit keys, 65 536 of them or more: SORT the (key - smallest key, RowID) pairs (the LSD radix sort: tiles staged in LDS,
+// runs instead of scattered stores) and fill the table from the sorted keys -- the RowIDs then already stand in rank order.  Marking 15 M
+// shuffled keys with device-scope atomicOr and scattering their RowIDs to their ranks took 0.56 + 0.41 ms.  A key that stands twice shows
+// after the sort: the keys go back to what they were, for the directory.
+static hy_status rank_table_sort_then_fill(BuildJob& job, JoinMailbox* mailbox, JoinMailbox* mailbox_dev, uint64_t key_min, uint64_t range, u32x2_t* entries, bool* built) {
+  BuildSide& b = job.b;
+  hipStream_t stream = job.stream;
+  const uint64_t total = job.total;
+  const dim3 key_grid(static_cast<uint32_t>((total + 255) / 256));
+  uint32_t key_bits = 1;
+  while (key_bits < 32 && (range >> key_bits) != 0) ++key_bits;
+  HY_TRY(b.keys_tmp.alloc(4 * (total + 4)));
+  HY_TRY(b.rows_tmp.alloc(4 * total));
+  // (read BEFORE anything below is queued: publish_build_flags writes these pinned fields again, with distances instead of keys)
+  const uint64_t remembered_min = mailbox->key_min, remembered_max = mailbox->key_max, remembered_or = mailbox->key_or;
+  hipLaunchKernelGGL(shift_keys, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, 0u - static_cast<uint32_t>(key_min));
+  uint32_t* sorted_keys = b.keys.as<uint32_t>();
+  uint32_t* sorted_rows = b.rows.as<uint32_t>();
+  HY_TRY(sort_pairs_u32(&sorted_keys, &sorted_rows, b.keys_tmp.as<uint32_t>(), b.rows_tmp.as<uint32_t>(), total, key_bits, stream));
+  if (sorted_keys != b.keys.as<uint32_t>()) { swap(b.keys, b.keys_tmp); swap(b.rows, b.rows_tmp); }
   HY_HIP(hipMemsetAsync(b.flags.ptr, 0, 64, stream));
-  HY_HIP(hipMemsetAsync(b.flags.as<uint32_t>() + 6, 0xFF, 8, stream));   // the running minimum
-  const bool key32 = build->data_type == HY_TYPE_INT && hashed_type == 0, id32 = want_ids32;
-  const size_t key_bytes = key32 ? 4 : 8, row_bytes = id32 ? 4 : 8;
-  uint64_t first_key = 0, last_key = 0;
-  bool keys_were_sorted = false;
-  HY_TRY(b.keys.alloc(key_bytes * (total + 4)));   // (32-bit keys: four entries of padding for the probe's 16-byte loads)
-  HY_TRY(b.rows.alloc(row_bytes * total));
-  // one instantiation per (key width, RowID width)
-#define HY_JOIN_BUILD_KERNEL(KERNEL, GRID, BLOCK, ...)                                                                  \
-  do {                                                                                                                  \
-    if (key32 && id32) hipLaunchKernelGGL((KERNEL<true, true>), GRID, BLOCK, 0, stream, __VA_ARGS__);                 \
-    else if (key32) hipLaunchKernelGGL((KERNEL<true, false>), GRID, BLOCK, 0, stream, __VA_ARGS__);                   \
-    else if (id32) hipLaunchKernelGGL((KERNEL<false, true>), GRID, BLOCK, 0, stream, __VA_ARGS__);                    \
-    else hipLaunchKernelGGL((KERNEL<false, false>), GRID, BLOCK, 0, stream, __VA_ARGS__);                             \
-  } while (0)
-  if (total) {
-    m.slice_offsets = offsets.as<uint64_t>();
-    m.keys = b.keys.ptr;
-    m.row_ids = b.rows.ptr;
-    if (dense) {
-      HY_JOIN_BUILD_KERNEL(join_materialize_dense, dim3(n_slices), dim3(256), m);
-    } else if (key32 && id32) {
-      hipLaunchKernelGGL((join_materialize<1, true, true>), dim3(n_slices), dim3(256), 0, stream, m);
-    } else if (key32) {
-      hipLaunchKernelGGL((join_materialize<1, true, false>), dim3(n_slices), dim3(256), 0, stream, m);
-    } else if (id32) {
-      hipLaunchKernelGGL((join_materialize<1, false, true>), dim3(n_slices), dim3(256), 0, stream, m);
-    } else {
-      hipLaunchKernelGGL((join_materialize<1, false, false>), dim3(n_slices), dim3(256), 0, stream, m);
-    }
-    if (key32) HY_HIP(hipMemsetAsync(b.keys.as<uint32_t>() + total, 0, 16, stream));
-    JoinMailbox* mailbox = nullptr;
-    JoinMailbox* mailbox_dev = nullptr;
-    HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
-    const dim3 check_grid(static_cast<uint32_t>(std::min<uint64_t>((total + 1023) / 1024, 1024)));
-    if (key32) {
-      hipLaunchKernelGGL(check_sorted<uint32_t>, check_grid, dim3(1024), 0, stream, b.keys.as<uint32_t>(), total, b.flags.as<uint32_t>());
-      hipLaunchKernelGGL(publish_build_flags<uint32_t>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<uint32_t>(), total, mailbox_dev);
-    } else {
-      hipLaunchKernelGGL(check_sorted<uint64_t>, check_grid, dim3(1024), 0, stream, b.keys.as<uint64_t>(), total, b.flags.as<uint32_t>());
-      hipLaunchKernelGGL(publish_build_flags<uint64_t>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<uint64_t>(), total, mailbox_dev);
-    }
-    HY_HIP(hipStreamSynchronize(stream));
-    b.any_null = mailbox->any_null != 0;
-    keys_were_sorted = mailbox->unsorted == 0;
-    first_key = mailbox->first_key;   // min / max if the keys are already sorted
-    last_key = mailbox->last_key;
-    // Unique integer keys that are not too sparse: the rank table (struct RankTable) instead of sort + directory.
-    bool rank_table = false;
-    {
-      const uint64_t key_min = mailbox->key_min, range = mailbox->key_max - mailbox->key_min;
-      const uint64_t words = (range >> 5) + 1;
-      if (allow_rank_table && hashed_type == 0 && !b.any_null && !mailbox->equal_neighbours && range < 0xFFFFFF00ull && (words <= 2 * total + 4096 || words <= 65536) &&
-          option(HY_OPT_JOIN_RANK_TABLE) && !build->join_hint.has_duplicates.load(std::memory_order_relaxed)) {   // (a column in which an earlier join met a key twice: no second try)
-        HY_TRY(b.rank_entries.alloc(8 * (words + 1)));
-        u32x2_t* entries = b.rank_entries.as<u32x2_t>();
-        HY_HIP(hipMemsetAsync(entries, 0, 8 * (words + 1), stream));
-        const dim3 key_grid(static_cast<uint32_t>((total + 255) / 256));
-        const bool sorted_signed = mailbox->unsorted_signed == 0;
-        if (sorted_signed) {
-          if (key32) hipLaunchKernelGGL(rank_table_fill_sorted<uint32_t>, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, key_min, entries);
-          else hipLaunchKernelGGL(rank_table_fill_sorted<uint64_t>, key_grid, dim3(256), 0, stream, b.keys.as<uint64_t>(), total, key_min, entries);
-          rank_table = true;
-        } else if (key32 && id32 && range < 0xFFFFFFF0ull && total >= 65536 && lds_atomics_are_lane_ordered(stream)) {
-          // Unsorted 32-bit keys, many of them: SORT the (key - smallest key, RowID) pairs (the LSD radix sort below: tiles staged in LDS, runs
-          // instead of scattered stores) and fill the table from the sorted keys -- the RowIDs then already stand in rank order.  Marking
-          // 15 M shuffled keys with device-scope atomicOr and scattering their RowIDs to their ranks took 0.56 + 0.41 ms.
-          uint32_t key_bits = 1;
-          while (key_bits < 32 && (range >> key_bits) != 0) ++key_bits;
-          HY_TRY(b.keys_tmp.alloc(key_bytes * (total + 4)));
-          HY_TRY(b.rows_tmp.alloc(row_bytes * total));
-          // (read BEFORE anything below is queued: publish_build_flags writes these pinned fields again, with distances instead of keys)
-          const uint64_t remembered_min = mailbox->key_min, remembered_max = mailbox->key_max, remembered_or = mailbox->key_or;
-          hipLaunchKernelGGL(shift_keys, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, 0u - static_cast<uint32_t>(key_min));
-          uint32_t* sorted_keys = b.keys.as<uint32_t>();
-          uint32_t* sorted_rows = b.rows.as<uint32_t>();
-          HY_TRY(sort_pairs_u32(&sorted_keys, &sorted_rows, b.keys_tmp.as<uint32_t>(), b.rows_tmp.as<uint32_t>(), total, key_bits, stream));
-          if (sorted_keys != b.keys.as<uint32_t>()) {
-            std::swap(b.keys.ptr, b.keys_tmp.ptr);
-            std::swap(b.keys.capacity, b.keys_tmp.capacity);
-            std::swap(b.rows.ptr, b.rows_tmp.ptr);
-            std::swap(b.rows.capacity, b.rows_tmp.capacity);
-          }
-          HY_HIP(hipMemsetAsync(b.flags.ptr, 0, 64, stream));
-          hipLaunchKernelGGL(check_sorted<uint32_t>, check_grid, dim3(1024), 0, stream, b.keys.as<uint32_t>(), total, b.flags.as<uint32_t>());
-          hipLaunchKernelGGL(publish_build_flags<uint32_t>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<uint32_t>(), total, mailbox_dev);
-          HY_HIP(hipStreamSynchronize(stream));
-          const bool duplicates = mailbox->equal_neighbours != 0;
-          mailbox->key_min = remembered_min;   // (the second look saw distances, not keys)
-          mailbox->key_max = remembered_max;
-          mailbox->key_or = remembered_or;
-          if (duplicates) {   // not unique after all: the keys again as they were, for the directory below -- which wants them in the order of
-            // their sign-extended bits (negative keys last): sorted already if there is no negative key, else its own sort runs (stable: equal
-            // keys keep the build-row order they have now)
-            build->join_hint.has_duplicates.store(1, std::memory_order_relaxed);
-            hipLaunchKernelGGL(shift_keys, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, static_cast<uint32_t>(key_min));
-            HY_HIP(hipMemsetAsync(b.keys.as<uint32_t>() + total, 0, 16, stream));
-            mailbox->unsorted = static_cast<int64_t>(key_min) < 0 ? 1 : 0;
-            mailbox->equal_neighbours = 1;
-          } else {
-            hipLaunchKernelGGL(rank_table_fill_sorted<uint32_t>, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, uint64_t{0}, entries);
-            rank_table = true;
-          }
-        } else {
-          if (key32) {
-            hipLaunchKernelGGL(rank_table_mark<uint32_t>, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, key_min, entries, b.flags.as<uint32_t>() + 10);
-            hipLaunchKernelGGL(publish_build_flags<uint32_t>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<uint32_t>(), total, mailbox_dev);
-          } else {
-            hipLaunchKernelGGL(rank_table_mark<uint64_t>, key_grid, dim3(256), 0, stream, b.keys.as<uint64_t>(), total, key_min, entries, b.flags.as<uint32_t>() + 10);
-            hipLaunchKernelGGL(publish_build_flags<uint64_t>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<uint64_t>(), total, mailbox_dev);
-          }
-          HY_HIP(hipStreamSynchronize(stream));
-          if (mailbox->duplicate) build->join_hint.has_duplicates.store(1, std::memory_order_relaxed);
-          if (!mailbox->duplicate) {   // bases by a scan over the words' population counts, then every RowID goes to its key's rank
-            const uint32_t n_blocks = static_cast<uint32_t>((words + RANK_BLOCK - 1) / RANK_BLOCK);
-            DeviceBuffer sums;
-            HY_TRY(sums.alloc(8 * (size_t{n_blocks} + 1)));
-            hipLaunchKernelGGL(rank_table_block_sums, dim3(n_blocks), dim3(256), 0, stream, entries, words, sums.as<uint64_t>());
-            hipLaunchKernelGGL(scan_block_offsets, dim3(1), dim3(1024), 0, stream, sums.as<uint64_t>(), n_blocks, 0xFFFFFFFFu, sums.as<uint64_t>() + n_blocks);
-            hipLaunchKernelGGL(rank_table_bases, dim3(n_blocks), dim3(256), 0, stream, entries, words, sums.as<uint64_t>());
-            HY_TRY(b.rows_tmp.alloc(row_bytes * total));
-            if (key32 && id32) hipLaunchKernelGGL((rank_table_scatter_rows<uint32_t, uint32_t>), key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), b.rows.as<uint32_t>(), b.rows_tmp.as<uint32_t>(), total, key_min, entries);
-            else if (key32) hipLaunchKernelGGL((rank_table_scatter_rows<uint32_t, hy_row_id>), key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), b.rows.as<hy_row_id>(), b.rows_tmp.as<hy_row_id>(), total, key_min, entries);
-            else if (id32) hipLaunchKernelGGL((rank_table_scatter_rows<uint64_t, uint32_t>), key_grid, dim3(256), 0, stream, b.keys.as<uint64_t>(), b.rows.as<uint32_t>(), b.rows_tmp.as<uint32_t>(), total, key_min, entries);
-            else hipLaunchKernelGGL((rank_table_scatter_rows<uint64_t, hy_row_id>), key_grid, dim3(256), 0, stream, b.keys.as<uint64_t>(), b.rows.as<hy_row_id>(), b.rows_tmp.as<hy_row_id>(), total, key_min, entries);
-            std::swap(b.rows.ptr, b.rows_tmp.ptr);
-            std::swap(b.rows.capacity, b.rows_tmp.capacity);
-            rank_table = true;
-          }
-        }
-        if (rank_table) {
-          b.rank.entries = entries;
-          b.rank.key_min = key_min;
-          b.rank.range = range;
-          // a dense, sorted build column with equally sized chunks: the build row of rank r is row r of the table
-          bool uniform = dense && sorted_signed && build->n_chunks > 0 && build->host_segments[0].size > 0;
-          for (uint32_t c = 1; c < build->n_chunks && uniform; ++c) {
-            const uint32_t size = build->host_segments[c].size, first_size = build->host_segments[0].size;
-            uniform = c + 1 == build->n_chunks ? size <= first_size : size == first_size;
-          }
-          if (uniform && FIXED_JOIN_IDENTITY) {
-            b.rank.identity_rows = build->host_segments[0].size;
-            b.rank.identity_inverse = 1.0 / static_cast<double>(b.rank.identity_rows);
-          }
-        }
-      }
-    }
-    if (rank_table) {
-      Directory& d = b.directory;   // only the RowIDs by rank
-      d.keys = nullptr;
-      d.keys32 = nullptr;
-      d.row_ids = id32 ? nullptr : b.rows.as<hy_row_id>();
-      d.ids32 = id32 ? b.rows.as<uint32_t>() : nullptr;
-      d.n = total;
-      d.key_min = mailbox->key_min;
-      d.key_max = mailbox->key_max;
-      d.shift = 0;
-      d.n_buckets = 1;
-      d.dir = nullptr;
-      return HY_OK;
-    }
-    if (mailbox->unsorted) {   // not sorted: stable LSD radix sort, only over the bytes that are not constant zero
-      const uint64_t key_bits_or = mailbox->key_or;
-      HY_TRY(b.keys_tmp.alloc(key_bytes * (total + 4)));
-      HY_TRY(b.rows_tmp.alloc(row_bytes * total));
-      const bool staged = key32 && id32 && lds_atomics_are_lane_ordered(stream);   // (sort_scatter_staged: 8192-element tiles, runs instead of scattered stores)
-      const uint32_t n_tiles = static_cast<uint32_t>(staged ? (total + SORT_BIG_TILE - 1) / SORT_BIG_TILE : (total + SORT_TILE - 1) / SORT_TILE);
-      if (staged) {
-        static OncePerDevice sort_lds_raised;
-        uint64_t sort_device_bit = 0;
-        if (sort_lds_raised.pending(&sort_device_bit)) {
-          HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sort_scatter_staged), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sort_staged_lds_bytes())));
-          sort_lds_raised.done(sort_device_bit);
-        }
-      }
-      DeviceBuffer hist, bases;
-      HY_TRY(hist.alloc(4 * size_t{256} * n_tiles));
-      HY_TRY(bases.alloc(8 * (size_t{256} * n_tiles + 1)));
-      void* src_keys = b.keys.ptr;
-      void* src_rows = b.rows.ptr;
-      void* dst_keys = b.keys_tmp.ptr;
-      void* dst_rows = b.rows_tmp.ptr;
-      for (uint32_t shift = 0; shift < (key32 ? 32u : 64u); shift += 8) {
-        // a byte that is zero in every key does not move anything (64-bit keys: unless one is negative -- then the sign
-        // extension is part of the order)
-        if (((key_bits_or >> shift) & 0xFF) == 0 && (key32 || !(key_bits_or >> 63))) continue;
-        if (staged) hipLaunchKernelGGL(sort_histogram_big, dim3(n_tiles), dim3(SORT_BIG_THREADS), 0, stream, static_cast<const uint32_t*>(src_keys), total, shift, hist.as<uint32_t>(), n_tiles);
-        else if (key32) hipLaunchKernelGGL(sort_histogram<uint32_t>, dim3(n_tiles), dim3(256), 0, stream, static_cast<const uint32_t*>(src_keys), total, shift, hist.as<uint32_t>(), n_tiles);
-        else hipLaunchKernelGGL(sort_histogram<uint64_t>, dim3(n_tiles), dim3(256), 0, stream, static_cast<const uint64_t*>(src_keys), total, shift, hist.as<uint32_t>(), n_tiles);
-        HY_TRY(exclusive_scan(hist.as<uint32_t>(), bases.as<uint64_t>(), uint64_t{256} * n_tiles, stream));
-        if (staged) hipLaunchKernelGGL(sort_scatter_staged, dim3(n_tiles), dim3(SORT_BIG_THREADS), sort_staged_lds_bytes(), stream, static_cast<const uint32_t*>(src_keys), static_cast<const uint32_t*>(src_rows), static_cast<uint32_t*>(dst_keys), static_cast<uint32_t*>(dst_rows), total, shift, bases.as<uint64_t>(), n_tiles);
-        else if (key32 && id32) hipLaunchKernelGGL((sort_scatter<uint32_t, uint32_t>), dim3(n_tiles), dim3(256), 0, stream, static_cast<const uint32_t*>(src_keys), static_cast<const uint32_t*>(src_rows), static_cast<uint32_t*>(dst_keys), static_cast<uint32_t*>(dst_rows), total, shift, bases.as<uint64_t>(), n_tiles);
-        else if (key32) hipLaunchKernelGGL((sort_scatter<uint32_t, hy_row_id>), dim3(n_tiles), dim3(256), 0, stream, static_cast<const uint32_t*>(src_keys), static_cast<const hy_row_id*>(src_rows), static_cast<uint32_t*>(dst_keys), static_cast<hy_row_id*>(dst_rows), total, shift, bases.as<uint64_t>(), n_tiles);
-        else if (id32) hipLaunchKernelGGL((sort_scatter<uint64_t, uint32_t>), dim3(n_tiles), dim3(256), 0, stream, static_cast<const uint64_t*>(src_keys), static_cast<const uint32_t*>(src_rows), static_cast<uint64_t*>(dst_keys), static_cast<uint32_t*>(dst_rows), total, shift, bases.as<uint64_t>(), n_tiles);
-        else hipLaunchKernelGGL((sort_scatter<uint64_t, hy_row_id>), dim3(n_tiles), dim3(256), 0, stream, static_cast<const uint64_t*>(src_keys), static_cast<const hy_row_id*>(src_rows), static_cast<uint64_t*>(dst_keys), static_cast<hy_row_id*>(dst_rows), total, shift, bases.as<uint64_t>(), n_tiles);
-        std::swap(src_keys, dst_keys);
-        std::swap(src_rows, dst_rows);
-      }
-      if (src_keys != b.keys.ptr) {
-        std::swap(b.keys.ptr, b.keys_tmp.ptr);
-        std::swap(b.keys.capacity, b.keys_tmp.capacity);
-        std::swap(b.rows.ptr, b.rows_tmp.ptr);
-        std::swap(b.rows.capacity, b.rows_tmp.capacity);
-      }
-      if (key32) HY_HIP(hipMemsetAsync(b.keys.as<uint32_t>() + total, 0, 16, stream));
-    }
+  HY_TRY(look_at_keys(job, mailbox_dev));
+  const bool duplicates = mailbox->equal_neighbours != 0;
+  mailbox->key_min = remembered_min;   // (the second look saw distances, not keys)
+  mailbox->key_max = remembered_max;
+  mailbox->key_or = remembered_or;
+  if (duplicates) {   // the directory wants the keys in the order of their sign-extended bits (negative keys last): sorted already if there is
+    // no negative key, else its own sort runs (stable: equal keys keep the build-row order they have now)
+    job.column->join_hint.has_duplicates.store(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(shift_keys, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, static_cast<uint32_t>(key_min));
+    HY_HIP(hipMemsetAsync(b.keys.as<uint32_t>() + total, 0, 16, stream));
+    mailbox->unsorted = static_cast<int64_t>(key_min) < 0 ? 1 : 0;
+    mailbox->equal_neighbours = 1;
+    return HY_OK;
   }
-#undef HY_JOIN_BUILD_KERNEL
-  // directory
+  hipLaunchKernelGGL(rank_table_fill_sorted<uint32_t>, key_grid, dim3(256), 0, stream, b.keys.as<uint32_t>(), total, uint64_t{0}, entries);
+  *built = true;
+  return HY_OK;
+}
+
+// Unsorted keys otherwise: every key marks its bit (a bit marked twice is a duplicate: the directory takes over), bases by a scan over the
+// words' population counts, then every RowID goes to its key's rank.
+static hy_status rank_table_mark_and_scatter(BuildJob& job, JoinMailbox* mailbox, JoinMailbox* mailbox_dev, uint64_t key_min, uint64_t words, u32x2_t* entries, bool* built) {
+  BuildSide& b = job.b;
+  hipStream_t stream = job.stream;
+  const uint64_t total = job.total;
+  const dim3 key_grid(static_cast<uint32_t>((total + 255) / 256));
+  with_key_type(job.plan.key32, [&](auto key) {
+    using K = decltype(key);
+    hipLaunchKernelGGL(rank_table_mark<K>, key_grid, dim3(256), 0, stream, b.keys.as<K>(), total, key_min, entries, b.flags.as<uint32_t>() + 10);
+    hipLaunchKernelGGL(publish_build_flags<K>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<K>(), total, mailbox_dev);
+  });
+  HY_HIP(hipStreamSynchronize(stream));
+  if (mailbox->duplicate) {
+    job.column->join_hint.has_duplicates.store(1, std::memory_order_relaxed);
+    return HY_OK;
+  }
+  const uint32_t n_blocks = static_cast<uint32_t>((words + RANK_BLOCK - 1) / RANK_BLOCK);
+  DeviceBuffer sums;
+  HY_TRY(sums.alloc(8 * (size_t{n_blocks} + 1)));
+  hipLaunchKernelGGL(rank_table_block_sums, dim3(n_blocks), dim3(256), 0, stream, entries, words, sums.as<uint64_t>());
+  hipLaunchKernelGGL(scan_block_offsets, dim3(1), dim3(1024), 0, stream, sums.as<uint64_t>(), n_blocks, 0xFFFFFFFFu, sums.as<uint64_t>() + n_blocks);
+  hipLaunchKernelGGL(rank_table_bases, dim3(n_blocks), dim3(256), 0, stream, entries, words, sums.as<uint64_t>());
+  HY_TRY(b.rows_tmp.alloc((job.plan.id32 ? 4 : 8) * total));
+  with_build_types(job.plan.key32, job.plan.id32, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((rank_table_scatter_rows<typename T::Key, typename T::Row>), key_grid, dim3(256), 0, stream, b.keys.as<typename T::Key>(), b.rows.as<typename T::Row>(),
+                       b.rows_tmp.as<typename T::Row>(), total, key_min, entries);
+  });
+  swap(b.rows, b.rows_tmp);
+  *built = true;
+  return HY_OK;
+}
+
+// Unique integer keys that are not too sparse: the rank table (struct RankTable) instead of sort + directory, from the materialised keys --
+// sorted ones fill it directly, the other two variants are above.  *built = false: the directory (the mailbox says whether the keys are
+// sorted as they stand now).
+static hy_status rank_table_from_keys(BuildJob& job, JoinMailbox* mailbox, JoinMailbox* mailbox_dev, bool* built) {
+  BuildSide& b = job.b;
+  const hy_column* build = job.column;
+  const uint64_t total = job.total, key_min = mailbox->key_min, range = mailbox->key_max - mailbox->key_min;
+  const uint64_t words = (range >> 5) + 1;
+  *built = false;
+  if (!(job.wants.allow_rank_table && job.wants.hashed_type == 0 && !b.any_null && !mailbox->equal_neighbours && range < 0xFFFFFF00ull && (words <= 2 * total + 4096 || words <= 65536) &&
+        option(HY_OPT_JOIN_RANK_TABLE) && !build->join_hint.has_duplicates.load(std::memory_order_relaxed)))   // (a column in which an earlier join met a key twice: no second try)
+    return HY_OK;
+  HY_TRY(b.rank_entries.alloc(8 * (words + 1)));
+  u32x2_t* entries = b.rank_entries.as<u32x2_t>();
+  HY_HIP(hipMemsetAsync(entries, 0, 8 * (words + 1), job.stream));
+  const bool sorted_signed = mailbox->unsorted_signed == 0;
+  if (sorted_signed) {
+    const dim3 key_grid(static_cast<uint32_t>((total + 255) / 256));
+    with_key_type(job.plan.key32, [&](auto key) {
+      using K = decltype(key);
+      hipLaunchKernelGGL(rank_table_fill_sorted<K>, key_grid, dim3(256), 0, job.stream, b.keys.as<K>(), total, key_min, entries);
+    });
+    *built = true;
+  } else if (job.plan.key32 && job.plan.id32 && range < 0xFFFFFFF0ull && total >= 65536 && lds_atomics_are_lane_ordered(job.stream)) {
+    HY_TRY(rank_table_sort_then_fill(job, mailbox, mailbox_dev, key_min, range, entries, built));
+  } else {
+    HY_TRY(rank_table_mark_and_scatter(job, mailbox, mailbox_dev, key_min, words, entries, built));
+  }
+  if (!*built) return HY_OK;
+  b.rank.entries = entries;
+  b.rank.key_min = key_min;
+  b.rank.range = range;
+  if (job.plan.uniform_chunks && sorted_signed && FIXED_JOIN_IDENTITY) {   // the build row of rank r is row r of the table
+    b.rank.identity_rows = build->host_segments[0].size;
+    b.rank.identity_inverse = 1.0 / static_cast<double>(b.rank.identity_rows);
+  }
+  Directory& d = b.directory;   // only the RowIDs by rank
+  d.keys = nullptr;
+  d.keys32 = nullptr;
+  d.row_ids = job.plan.id32 ? nullptr : b.rows.as<hy_row_id>();
+  d.ids32 = job.plan.id32 ? b.rows.as<uint32_t>() : nullptr;
+  d.n = total;
+  d.key_min = mailbox->key_min;
+  d.key_max = mailbox->key_max;
+  d.shift = 0;
+  d.n_buckets = 1;
+  d.dir = nullptr;
+  return HY_OK;
+}
+
+// Keys that are not sorted: the stable LSD radix sort, only over the bytes that are not zero in every key (64-bit keys: unless one is
+// negative -- then the sign extension is part of the order).
+static hy_status sort_build_keys(BuildJob& job, uint64_t key_bits_or) {
+  BuildSide& b = job.b;
+  const bool key32 = job.plan.key32, id32 = job.plan.id32;
+  HY_TRY(b.keys_tmp.alloc((key32 ? 4 : 8) * (job.total + 4)));
+  HY_TRY(b.rows_tmp.alloc((id32 ? 4 : 8) * job.total));
+  const bool staged = key32 && id32 && lds_atomics_are_lane_ordered(job.stream);
+  uint32_t moving_bytes = 0;
+  for (uint32_t byte = 0; byte < 8; ++byte)
+    if (((key_bits_or >> (8 * byte)) & 0xFF) != 0 || (!key32 && (key_bits_or >> 63))) moving_bytes |= 1u << byte;
+  void* keys = b.keys.ptr;
+  void* rows = b.rows.ptr;
+  HY_TRY(lsd_sort_passes(key32, id32, staged, &keys, &rows, b.keys_tmp.ptr, b.rows_tmp.ptr, job.total, moving_bytes, job.stream));
+  if (keys != b.keys.ptr) { swap(b.keys, b.keys_tmp); swap(b.rows, b.rows_tmp); }
+  if (key32) HY_HIP(hipMemsetAsync(b.keys.as<uint32_t>() + job.total, 0, 16, job.stream));
+  return HY_OK;
+}
+
+// The order-preserving bucket directory over the sorted keys.  `ends_known`: first_key / last_key are the sorted keys' ends (they were sorted
+// as materialised); otherwise one more look.
+static hy_status build_directory(BuildJob& job, bool ends_known, uint64_t first_key, uint64_t last_key) {
+  BuildSide& b = job.b;
+  const bool key32 = job.plan.key32, id32 = job.plan.id32;
+  const uint64_t total = job.total;
   Directory& d = b.directory;
   d.keys = key32 ? nullptr : b.keys.as<uint64_t>();
   d.keys32 = key32 ? b.keys.as<uint32_t>() : nullptr;
@@ -3708,19 +3769,20 @@ static hy_status prepare_build(const hy_column* build, bool keep_nulls, bool wan
   d.shift = 0;
   d.n_buckets = 1;
   if (total) {
-    if (keys_were_sorted) {
-      d.key_min = first_key;
-      d.key_max = last_key;
-    } else {   // the ends of the sorted keys
+    if (!ends_known) {
       JoinMailbox* mailbox = nullptr;
       JoinMailbox* mailbox_dev = nullptr;
       HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
-      if (key32) hipLaunchKernelGGL(publish_build_flags<uint32_t>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<uint32_t>(), total, mailbox_dev);
-      else hipLaunchKernelGGL(publish_build_flags<uint64_t>, dim3(1), dim3(1), 0, stream, b.flags.as<uint32_t>(), b.keys.as<uint64_t>(), total, mailbox_dev);
-      HY_HIP(hipStreamSynchronize(stream));
-      d.key_min = mailbox->first_key;
-      d.key_max = mailbox->last_key;
+      with_key_type(key32, [&](auto key) {
+        using K = decltype(key);
+        hipLaunchKernelGGL(publish_build_flags<K>, dim3(1), dim3(1), 0, job.stream, b.flags.as<uint32_t>(), b.keys.as<K>(), total, mailbox_dev);
+      });
+      HY_HIP(hipStreamSynchronize(job.stream));
+      first_key = mailbox->first_key;
+      last_key = mailbox->last_key;
     }
+    d.key_min = first_key;
+    d.key_max = last_key;
     uint32_t buckets = 1;
     while (buckets < total && buckets < (1u << 27)) buckets <<= 1;   // 1-2 keys per bucket on uniform keys: one probe of four keys
     const uint64_t range = d.key_max - d.key_min;
@@ -3731,14 +3793,73 @@ static hy_status prepare_build(const hy_column* build, bool keep_nulls, bool wan
   }
   HY_TRY(b.dir.alloc(4 * (size_t{d.n_buckets} + 2)));
   d.dir = b.dir.as<uint32_t>();
-  if (total) {
-    const dim3 grid(static_cast<uint32_t>((total + 255) / 256));
-    if (key32) hipLaunchKernelGGL(directory_fill<uint32_t>, grid, dim3(256), 0, stream, d.keys32, total, d.key_min, d.shift, d.n_buckets, b.dir.as<uint32_t>());
-    else hipLaunchKernelGGL(directory_fill<uint64_t>, grid, dim3(256), 0, stream, d.keys, total, d.key_min, d.shift, d.n_buckets, b.dir.as<uint32_t>());
-  } else {
-    HY_HIP(hipMemsetAsync(b.dir.ptr, 0, 4 * (size_t{d.n_buckets} + 2), stream));
+  if (!total) {
+    HY_HIP(hipMemsetAsync(b.dir.ptr, 0, 4 * (size_t{d.n_buckets} + 2), job.stream));
+    return HY_OK;
   }
+  const dim3 grid(static_cast<uint32_t>((total + 255) / 256));
+  with_key_type(key32, [&](auto key) {
+    using K = decltype(key);
+    hipLaunchKernelGGL(directory_fill<K>, grid, dim3(256), 0, job.stream, b.keys.as<K>(), total, d.key_min, d.shift, d.n_buckets, b.dir.as<uint32_t>());
+  });
   return HY_OK;
+}
+
+// The build side of one join: the host-only plan, then the first step that applies -- hinted fill, identity table, rank table from
+// materialised keys -- or (sort and) directory.
+static hy_status prepare_build(const hy_column* build, const BuildWants& wants, BuildSide& b, hipStream_t stream) {
+  BuildJob job{build, wants, plan_build(build, wants), b, stream};
+  const uint32_t n_slices = build->n_slices;
+  HY_TRY(job.counts.alloc(4 * size_t{n_slices + 1}));
+  HY_TRY(job.offsets.alloc(8 * size_t{n_slices + 2}));
+  HY_TRY(b.flags.alloc(64));
+  if (wants.bloom) {
+    HY_TRY(b.bloom.alloc(BLOOM_BITS));
+    if (!job.plan.hinted) HY_HIP(hipMemsetAsync(b.bloom.ptr, 0, BLOOM_BITS, stream));
+  }
+  MaterializeArgs& m = job.m;
+  m.segments = build->d_segments;
+  m.views = build->d_slice_views;
+  m.slices = build->d_slices;
+  m.n_slices = n_slices;
+  m.keep_nulls = wants.keep_nulls;
+  m.bloom_in = nullptr;
+  m.bloom_out = wants.bloom ? b.bloom.as<uint8_t>() : nullptr;
+  m.slice_counts = job.counts.as<uint32_t>();
+  m.any_null = b.flags.as<uint32_t>() + 2;
+  m.hashed_type = wants.hashed_type;
+  // A dense column materialises every row: slice offsets are row numbers, no counting pass and no host round trip.
+  if (n_slices && job.plan.dense) {
+    m.row_base = build->d_row_base;
+    job.total = build->rows;
+  } else if (n_slices) {
+    hipLaunchKernelGGL((join_materialize<0, false, false>), dim3(n_slices), dim3(256), 0, stream, m);
+    hipLaunchKernelGGL(scan_counts, dim3(1), dim3(1024), 0, stream, job.counts.as<uint32_t>(), job.offsets.as<uint64_t>(), n_slices);
+    HY_HIP(hipMemcpyAsync(&job.total, job.offsets.as<uint64_t>() + n_slices, 8, hipMemcpyDeviceToHost, stream));
+    HY_HIP(hipStreamSynchronize(stream));
+  }
+  b.n = job.total;
+  if (job.plan.identity_candidate && job.total) {
+    if (job.plan.hinted) return fill_hinted(job);
+    bool built = false;
+    HY_TRY(fill_identity(job, &built));
+    if (built) return HY_OK;
+  }
+  JoinMailbox* mailbox = nullptr;
+  JoinMailbox* mailbox_dev = nullptr;
+  HY_TRY(materialise_keys(job, &mailbox, &mailbox_dev));
+  bool ends_known = false;
+  uint64_t first_key = 0, last_key = 0;
+  if (job.total) {
+    ends_known = mailbox->unsorted == 0;
+    first_key = mailbox->first_key;   // min / max if the keys are already sorted
+    last_key = mailbox->last_key;
+    bool rank_table = false;
+    HY_TRY(rank_table_from_keys(job, mailbox, mailbox_dev, &rank_table));
+    if (rank_table) return HY_OK;
+    if (mailbox->unsorted) HY_TRY(sort_build_keys(job, mailbox->key_or));
+  }
+  return build_directory(job, ends_known, first_key, last_key);
 }
 
 // Persistent waves that take one tile at a time (rt_stream_count), STREAM_WAVES per workgroup: as many as fit the device at once
@@ -3818,31 +3939,12 @@ static bool lds_atomics_are_lane_ordered(hipStream_t stream) {
 // or the temporaries).
 hy_status sort_pairs_u32(uint32_t** keys, uint32_t** ids, uint32_t* keys_tmp, uint32_t* ids_tmp, uint64_t n, uint32_t key_bits, hipStream_t stream) {
   if (n < 2) return HY_OK;
-  const bool staged = lds_atomics_are_lane_ordered(stream);
-  const uint32_t n_tiles = static_cast<uint32_t>(staged ? (n + SORT_BIG_TILE - 1) / SORT_BIG_TILE : (n + SORT_TILE - 1) / SORT_TILE);
-  if (staged) {
-    static OncePerDevice lds_raised;
-    uint64_t device_bit = 0;
-    if (lds_raised.pending(&device_bit)) {
-      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sort_scatter_staged), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sort_staged_lds_bytes())));
-      lds_raised.done(device_bit);
-    }
-  }
-  DeviceBuffer hist, bases;
-  HY_TRY(hist.alloc(4 * size_t{256} * n_tiles));
-  HY_TRY(bases.alloc(8 * (size_t{256} * n_tiles + 1)));
-  uint32_t *src_keys = *keys, *src_ids = *ids, *dst_keys = keys_tmp, *dst_ids = ids_tmp;
-  for (uint32_t shift = 0; shift < 32 && shift < key_bits; shift += 8) {
-    if (staged) hipLaunchKernelGGL(sort_histogram_big, dim3(n_tiles), dim3(SORT_BIG_THREADS), 0, stream, src_keys, n, shift, hist.as<uint32_t>(), n_tiles);
-    else hipLaunchKernelGGL(sort_histogram<uint32_t>, dim3(n_tiles), dim3(256), 0, stream, src_keys, n, shift, hist.as<uint32_t>(), n_tiles);
-    HY_TRY(exclusive_scan(hist.as<uint32_t>(), bases.as<uint64_t>(), uint64_t{256} * n_tiles, stream));
-    if (staged) hipLaunchKernelGGL(sort_scatter_staged, dim3(n_tiles), dim3(SORT_BIG_THREADS), sort_staged_lds_bytes(), stream, src_keys, src_ids, dst_keys, dst_ids, n, shift, bases.as<uint64_t>(), n_tiles);
-    else hipLaunchKernelGGL((sort_scatter<uint32_t, uint32_t>), dim3(n_tiles), dim3(256), 0, stream, src_keys, src_ids, dst_keys, dst_ids, n, shift, bases.as<uint64_t>(), n_tiles);
-    std::swap(src_keys, dst_keys);
-    std::swap(src_ids, dst_ids);
-  }
-  *keys = src_keys;
-  *ids = src_ids;
+  const uint32_t moving_bytes = (1u << std::min<uint32_t>(4, (key_bits + 7) / 8)) - 1;
+  void* sorted_keys = *keys;
+  void* sorted_ids = *ids;
+  HY_TRY(lsd_sort_passes(true, true, lds_atomics_are_lane_ordered(stream), &sorted_keys, &sorted_ids, keys_tmp, ids_tmp, n, moving_bytes, stream));
+  *keys = static_cast<uint32_t*>(sorted_keys);
+  *ids = static_cast<uint32_t*>(sorted_ids);
   return HY_OK;
 }
 
@@ -3899,8 +4001,41 @@ static hy_status probe_keys_lack_locality(const hy_column* probe, hipStream_t st
   return HY_OK;
 }
 
-static hy_status run_join_once(const hy_column* left, const hy_column* right, uint32_t mode, hy_join_result* result, bool count_only, uint64_t* count_out,
-                               const hy_join_predicate* secondary, uint32_t n_secondary, bool* retry) {
+// ---- one join call, resolved once ------------------------------------------------------------------------------------------------------------
+struct JoinRequest {
+  const hy_column* build;
+  const hy_column* probe;
+  bool build_right;             // the build side is the right input
+  uint32_t mode;
+  bool semi_anti;
+  bool keep_nulls_build;        // join_hash.cpp:284-286
+  bool keep_nulls_probe;
+  uint32_t hashed_type;         // JoinHashTraits (join_hash_traits.hpp:15-40): the type both sides are cast to; 0 = an integer type (std::hash is the identity)
+  bool general;                 // the <true> instantiations of the probe kernels: secondary predicates, float / double keys
+  uint32_t radix_bits;
+  bool host_result;
+  bool count_only;
+  bool async;                   // HY_JOIN_ASYNC: no host round trip at all -- pk_plan leaves in device memory what the host would read from the mailbox
+  bool probe_filtered;          // the build side's Bloom filter is applied to the probe side (join_hash.cpp:365-381)
+  bool pack_build_ids;          // RowID -> chunk_id << 16 | chunk_offset: both below 2^16 (every table with Hyrise's default chunk size)
+  hy_join_result* result;       // nullptr: count_only
+  uint64_t* count_out;
+  hy_row_id* user_build;        // the caller's lists and slice offsets (count_only: none)
+  hy_row_id* user_probe;
+  uint64_t* user_slice_offsets;
+  uint64_t capacity;            // ... and what they hold (count_only: no limit)
+  uint32_t slice_capacity;
+  uint32_t n_secondary;
+  SecondaryPredicate secondary[HY_MAX_SECONDARY_PREDICATES];   // as the probe sees them: build <condition> probe (join_hash.cpp:158-165)
+};
+
+static bool builds_over_right_input(const hy_column* left, const hy_column* right, uint32_t mode) {   // side selection (join_hash.cpp:139-155)
+  return mode == HY_JOIN_LEFT || mode == HY_JOIN_ANTI_NULL_AS_TRUE || mode == HY_JOIN_ANTI_NULL_AS_FALSE || mode == HY_JOIN_SEMI || (mode == HY_JOIN_INNER && left->rows > right->rows);
+}
+
+// Every refusal of the call, before anything is allocated or launched.
+static hy_status resolve_join_request(const hy_column* left, const hy_column* right, uint32_t mode, hy_join_result* result, bool count_only, uint64_t* count_out,
+                                      const hy_join_predicate* secondary, uint32_t n_secondary, JoinRequest* request) {
   if (mode == HY_JOIN_FULL_OUTER || mode == HY_JOIN_CROSS || mode > HY_JOIN_ANTI_NULL_AS_FALSE) return fail(HY_ERR_UNSUPPORTED, "JoinHash does not support join mode %u (join_hash.cpp:38-44)", mode);
   if (n_secondary > HY_MAX_SECONDARY_PREDICATES) return fail(HY_ERR_UNSUPPORTED, "more than %u secondary join predicates stay on the CPU path", HY_MAX_SECONDARY_PREDICATES);
   if (n_secondary && mode == HY_JOIN_ANTI_NULL_AS_TRUE) return fail(HY_ERR_UNSUPPORTED, "JoinHash does not support secondary predicates with AntiNullAsTrue (join_hash.cpp:39-44)");
@@ -3919,459 +4054,535 @@ static hy_status run_join_once(const hy_column* left, const hy_column* right, ui
     if (column->is_mvcc || (column->ref && column->ref->is_mvcc)) return fail(HY_ERR_INVALID, "MVCC columns are read by hy_validate only");
     if (column->data_type < HY_TYPE_INT || column->data_type > HY_TYPE_DOUBLE) return fail(HY_ERR_UNSUPPORTED, "string join keys stay on the CPU path");
   }
-  // JoinHashTraits (join_hash_traits.hpp:15-40): the type both sides are cast to; 0 = an integer type (std::hash is the identity)
-  uint32_t hashed_type = 0;
-  {
-    const uint32_t l = left->data_type, r = right->data_type;
-    const bool l_float = l == HY_TYPE_FLOAT || l == HY_TYPE_DOUBLE, r_float = r == HY_TYPE_FLOAT || r == HY_TYPE_DOUBLE;
-    if (l_float && r_float) hashed_type = (l == HY_TYPE_DOUBLE || r == HY_TYPE_DOUBLE) ? HY_TYPE_DOUBLE : HY_TYPE_FLOAT;
-    else if (l_float || r_float) hashed_type = l_float ? l : r;
-  }
-  const bool general = n_secondary != 0 || hashed_type != 0;   // the <true> instantiations of the probe kernels
-  hipStream_t stream = current_stream();
-  // side selection (join_hash.cpp:139-155)
-  const bool build_right = mode == HY_JOIN_LEFT || mode == HY_JOIN_ANTI_NULL_AS_TRUE || mode == HY_JOIN_ANTI_NULL_AS_FALSE || mode == HY_JOIN_SEMI ||
-                           (mode == HY_JOIN_INNER && left->rows > right->rows);
-  const hy_column* build = build_right ? right : left;
-  const hy_column* probe = build_right ? left : right;
-  const bool semi_anti = mode == HY_JOIN_SEMI || mode == HY_JOIN_ANTI_NULL_AS_TRUE || mode == HY_JOIN_ANTI_NULL_AS_FALSE;
-  const bool keep_nulls_build = mode == HY_JOIN_ANTI_NULL_AS_TRUE;   // join_hash.cpp:284-286
-  const bool keep_nulls_probe = mode == HY_JOIN_LEFT || mode == HY_JOIN_RIGHT || mode == HY_JOIN_ANTI_NULL_AS_TRUE || mode == HY_JOIN_ANTI_NULL_AS_FALSE;
-  uint32_t radix_bits = calculate_radix_bits(build->rows);
-  if (result && result->radix_bits != 0xFFFFFFFFu) radix_bits = result->radix_bits;
-  if (radix_bits > 8) return fail(HY_ERR_INVALID, "radix_bits %u > 8", radix_bits);
-  const bool host_result = !result || result->mem == HY_MEM_HOST;
+  JoinRequest& q = *request;
+  q = JoinRequest{};
+  const uint32_t l = left->data_type, r = right->data_type;
+  const bool l_float = l == HY_TYPE_FLOAT || l == HY_TYPE_DOUBLE, r_float = r == HY_TYPE_FLOAT || r == HY_TYPE_DOUBLE;
+  if (l_float && r_float) q.hashed_type = (l == HY_TYPE_DOUBLE || r == HY_TYPE_DOUBLE) ? HY_TYPE_DOUBLE : HY_TYPE_FLOAT;
+  else if (l_float || r_float) q.hashed_type = l_float ? l : r;
+  q.general = n_secondary != 0 || q.hashed_type != 0;
+  q.mode = mode;
+  q.build_right = builds_over_right_input(left, right, mode);
+  q.build = q.build_right ? right : left;
+  q.probe = q.build_right ? left : right;
+  q.semi_anti = mode == HY_JOIN_SEMI || mode == HY_JOIN_ANTI_NULL_AS_TRUE || mode == HY_JOIN_ANTI_NULL_AS_FALSE;
+  q.keep_nulls_build = mode == HY_JOIN_ANTI_NULL_AS_TRUE;
+  q.keep_nulls_probe = mode == HY_JOIN_LEFT || mode == HY_JOIN_RIGHT || mode == HY_JOIN_ANTI_NULL_AS_TRUE || mode == HY_JOIN_ANTI_NULL_AS_FALSE;
+  q.radix_bits = calculate_radix_bits(q.build->rows);
+  if (result && result->radix_bits != 0xFFFFFFFFu) q.radix_bits = result->radix_bits;
+  if (q.radix_bits > 8) return fail(HY_ERR_INVALID, "radix_bits %u > 8", q.radix_bits);
+  q.result = result;
+  q.count_only = count_only;
+  q.count_out = count_out;
+  q.host_result = !result || result->mem == HY_MEM_HOST;
+  q.async = !count_only && !q.host_result && (result->flags & HY_JOIN_ASYNC) && result->status;
+  q.capacity = count_only ? ~0ull : result->capacity;
+  q.slice_capacity = count_only ? 0xFFFFFFFFu : result->slice_capacity;
   // The emitting kernels write the caller's device lists two pairs at a time (16-byte stores at even pair indices, rt_copy_out / pk_emit):
-  // lists off a 16-byte boundary, and slice offsets off an 8-byte one, are refused before anything is launched.
-  if (!host_result && !count_only &&
+  // lists off a 16-byte boundary, and slice offsets off an 8-byte one, are refused.
+  if (!q.host_result && !count_only &&
       (reinterpret_cast<uintptr_t>(result->left_pos) % 16 != 0 || reinterpret_cast<uintptr_t>(result->right_pos) % 16 != 0 || reinterpret_cast<uintptr_t>(result->slice_offsets) % 8 != 0))
     return fail(HY_ERR_INVALID, "hy_join_hash: a device-memory result needs left_pos / right_pos on 16-byte and slice_offsets on 8-byte boundaries");
+  if (!count_only) {
+    q.user_build = q.build_right ? result->right_pos : result->left_pos;
+    q.user_probe = q.build_right ? result->left_pos : result->right_pos;
+    q.user_slice_offsets = result->slice_offsets;
+    if (!q.user_probe && result->capacity) return fail(HY_ERR_INVALID, "join result: PosList buffer for the probe side missing");
+    if (!q.semi_anti && !q.user_build && result->capacity) return fail(HY_ERR_INVALID, "join result: PosList buffer for the build side missing");
+    if (!q.user_slice_offsets) return fail(HY_ERR_INVALID, "join result: slice_offsets missing");
+  }
+  q.probe_filtered = q.build->rows < q.probe->rows && !q.keep_nulls_probe;   // (only when the build side is materialised first)
+  q.pack_build_ids = !q.semi_anti && !count_only && q.build->n_chunks <= 65536;
+  for (uint32_t c = 0; c < q.build->n_chunks && q.pack_build_ids; ++c) q.pack_build_ids = q.build->host_segments[c].size <= 65536;
+  q.n_secondary = n_secondary;
+  for (uint32_t p = 0; p < n_secondary; ++p) {
+    q.secondary[p].build = (q.build_right ? secondary[p].right_column : secondary[p].left_column)->d_segments;
+    q.secondary[p].probe = (q.build_right ? secondary[p].left_column : secondary[p].right_column)->d_segments;
+    q.secondary[p].condition = q.build_right ? flip_condition(secondary[p].condition) : secondary[p].condition;
+  }
+  return HY_OK;
+}
 
-  // build side; its Bloom filter is applied to the probe side only when the build side is materialised first
-  const bool probe_filtered = build->rows < probe->rows && !keep_nulls_probe;   // join_hash.cpp:365-381
-  // RowID -> chunk_id << 16 | chunk_offset needs both below 2^16 (every table with Hyrise's default chunk size)
-  bool pack_build_ids = !semi_anti && !count_only && build->n_chunks <= 65536;
-  for (uint32_t c = 0; c < build->n_chunks && pack_build_ids; ++c) pack_build_ids = build->host_segments[c].size <= 65536;
+// Will the probe side take the kernels of join_pkfk.hpp if the build side turns out to be a rank table?  (Everything that does not depend
+// on the build side: probe segments that SliceViews describe -- int32 values / FrameOfReference offsets, no NULLs, 16-byte aligned --,
+// counts and pair indices in 32 bits, lane-ordered LDS atomics.)  *probe_views: the first of these, which the general rank-table
+// kernels ask for too (pass 1 is then the wave-per-tile kernel with wide loads).
+static bool probe_takes_pk_kernels(const JoinRequest& q, hipStream_t stream, bool* probe_views) {
+  const hy_column* probe = q.probe;
+  bool views = !probe->is_reference && probe->n_slices > 0 && FIXED_JOIN_FETCH_AHEAD;
+  for (uint32_t c = 0; c < probe->n_chunks && views; ++c) {
+    const hy_segment& seg = probe->host_segments[c];
+    views = !seg.nulls && reinterpret_cast<uintptr_t>(seg.data) % 16 == 0 && ((seg.encoding == HY_ENC_UNENCODED && seg.data_type == HY_TYPE_INT) || seg.encoding == HY_ENC_FRAME_OF_REFERENCE);
+  }
+  *probe_views = views;
+  return views && q.hashed_type == 0 && q.n_secondary == 0 && probe->rows < 0xFFFF0000ull && option(HY_OPT_JOIN_PKFK) && (q.count_only || q.capacity <= 0xFFFFFFFFull) &&
+         lds_atomics_are_lane_ordered(stream);
+}
+
+// A rank table filled from the build column's key hint is confirmed when the join's kernels have finished (after the stream synchronise
+// that makes pk_plan's mailbox visible): if the column is not what the hint said, the hint is dropped, whatever the join wrote is
+// discarded and the caller runs it again.
+static bool hint_confirmed(const JoinRequest& q, const BuildSide& b, const JoinMailbox* mailbox, bool* retry) {
+  if (!b.hinted || !mailbox->build_unconfirmed) return true;
+  q.build->join_hint.state.store(2, std::memory_order_release);
+  *retry = true;
+  return false;
+}
+
+static uint64_t* attach_join_trace(uint32_t n_tiles) {   // HY_JOIN_TRACE (debug): the buffer the probe kernels stamp, or nullptr
+  if (!HY_DEBUG_ENV("HY_JOIN_TRACE")) return nullptr;
+  static uint64_t* trace_buffer = nullptr;
+  if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 6 * JOIN_TRACE_TILES);
+  if (n_tiles > JOIN_TRACE_TILES) return nullptr;
+  g_join_trace = trace_buffer;
+  g_join_trace_tiles = n_tiles;
+  return trace_buffer;
+}
+
+// Where the probe kernels write: the caller's device buffers, or device stand-ins for a host result -- slice offsets up front (the host
+// knows an upper bound), the pair lists once pass 1 has counted the pairs.
+struct JoinOutput {
+  DeviceBuffer d_build, d_probe, d_slice_offsets;
+  hy_row_id* build = nullptr;     // (Semi / Anti: none)
+  hy_row_id* probe = nullptr;
+  uint64_t* slice_offsets = nullptr;
+};
+
+static hy_status begin_output(const JoinRequest& q, uint32_t max_slices, JoinOutput& out) {
+  out.build = q.semi_anti ? nullptr : q.user_build;
+  out.probe = q.user_probe;
+  out.slice_offsets = q.user_slice_offsets;
+  if (q.count_only || !q.host_result) return HY_OK;
+  HY_TRY(out.d_slice_offsets.alloc(8 * (size_t{max_slices} + 2)));
+  out.slice_offsets = out.d_slice_offsets.as<uint64_t>();
+  return HY_OK;
+}
+
+static hy_status size_output_lists(const JoinRequest& q, const JoinMailbox* mailbox, hipStream_t stream, StageClock& clock, JoinOutput& out) {
+  if (!q.host_result) return HY_OK;
+  HY_HIP(hipStreamSynchronize(stream));   // the staging buffers are sized by the pair count: ask now
+  clock.mark("pass 1 done");
+  if (!mailbox->fits) return HY_OK;
+  if (!q.semi_anti) {
+    HY_TRY(out.d_build.alloc(8 * mailbox->n_pairs));
+    out.build = out.d_build.as<hy_row_id>();
+  }
+  HY_TRY(out.d_probe.alloc(8 * mailbox->n_pairs));
+  out.probe = out.d_probe.as<hy_row_id>();
+  return HY_OK;
+}
+
+static hy_status copy_output_back(const JoinRequest& q, const JoinMailbox* mailbox, hipStream_t stream, const JoinOutput& out) {
+  if (!q.host_result || !mailbox->fits) return HY_OK;
+  if (mailbox->n_pairs) {
+    HY_HIP(hipMemcpyAsync(q.user_probe, out.probe, 8 * mailbox->n_pairs, hipMemcpyDeviceToHost, stream));
+    if (!q.semi_anti) HY_HIP(hipMemcpyAsync(q.user_build, out.build, 8 * mailbox->n_pairs, hipMemcpyDeviceToHost, stream));
+  }
+  HY_HIP(hipMemcpyAsync(q.user_slice_offsets, out.slice_offsets, 8 * (size_t{mailbox->n_slices} + 1), hipMemcpyDeviceToHost, stream));
+  return HY_OK;
+}
+
+// What a finished join tells its caller: the sizes (also of a result that did not fit: what to retry with) and the errors they imply.
+static hy_status report_join_result(hy_join_result* result, uint64_t n_pairs, uint32_t n_slices, uint32_t error) {
+  result->n_slices = n_slices;
+  result->n_pairs = n_pairs;
+  if (n_slices > result->slice_capacity) return fail(HY_ERR_CAPACITY, "join produces %u output PosLists, slice capacity is %u", n_slices, result->slice_capacity);
+  if (n_pairs > result->capacity) return fail(HY_ERR_CAPACITY, "join produces %llu pairs, capacity is %llu", static_cast<unsigned long long>(n_pairs), static_cast<unsigned long long>(result->capacity));
+  if (error) return fail(HY_ERR_UNSUPPORTED, "a probe row matches more than 4 194 303 build rows");
+  return HY_OK;
+}
+
+// ---- the primary-key / foreign-key probe (join_pkfk.hpp) ---------------------------------------------------------------------------------------
+static hy_status raise_pk_count_lds() {
+  static OncePerDevice raised;
+  uint64_t device_bit = 0;
+  if (raised.pending(&device_bit)) {
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_count_lds), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(pk_count_lds_bytes(PK_LDS_KEYS - 1, PK_LDS_MAX_PARTITIONS))));
+    raised.done(device_bit);
+  }
+  return HY_OK;
+}
+
+static hy_status raise_pk_emit_lds() {
+  static OncePerDevice raised;
+  uint64_t device_bit = 0;
+  if (raised.pending(&device_bit)) {
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
+    raised.done(device_bit);
+  }
+  return HY_OK;
+}
+
+struct PkBuffers {
+  DeviceBuffer cells, small, row_masks, row_ranks;
+};
+
+// Everything pk_count / pk_scan read: the probe tiles, the build side, the cells of pass 1, where the plan and the verdict go.
+static hy_status pk_arguments(const JoinRequest& q, const BuildSide& b, JoinMailbox* mailbox_dev, const JoinOutput& out, uint32_t n_groups, PkBuffers& buffers, PkArgs& k) {
+  const uint32_t n_tiles = q.probe->n_slices * PK_TILES_PER_SLICE, partitions = 1u << q.radix_bits;
+  const uint32_t stride = (n_tiles + 1 + 3) & ~3u;
+  HY_TRY(buffers.cells.alloc(size_t{12} * partitions * stride));
+  const size_t at_origin = align_up(8 * size_t{partitions}, 8), at_slice_base = at_origin + 8 * (size_t{partitions} + 1), at_words = align_up(at_slice_base + 4 * (size_t{n_groups} + 1), 8);
+  HY_TRY(buffers.small.alloc(at_words + 64));
+  k.views = q.probe->d_slice_views;
+  k.n_tiles = n_tiles;
+  k.stride = stride;
+  k.mode = q.mode;
+  k.radix_bits = q.radix_bits;
+  k.keep_nulls = q.keep_nulls_probe;
+  k.n_groups = n_groups;
+  k.build_bloom = q.probe_filtered ? b.bloom.as<uint8_t>() : nullptr;
+  k.bloom_is_bits = b.bloom_is_bits ? 1u : 0u;
+  k.rank = b.rank;
+  k.ids32 = b.directory.ids32;
+  k.row_ids = b.directory.row_ids;
+  k.counts = buffers.cells.as<uint32_t>();
+  k.rel_elements = k.counts + size_t{partitions} * stride;
+  k.rel_pairs = k.rel_elements + size_t{partitions} * stride;
+  char* small_base = buffers.small.as<char>();
+  k.totals = reinterpret_cast<uint32_t*>(small_base);
+  k.origin_pairs = reinterpret_cast<uint64_t*>(small_base + at_origin);
+  k.slice_base = reinterpret_cast<uint32_t*>(small_base + at_slice_base);
+  k.group_first_tile = q.probe->d_first_slice;
+  k.ticket = reinterpret_cast<uint32_t*>(small_base + at_words);
+  k.plan = reinterpret_cast<JoinPlan*>(small_base + at_words + 16);
+  k.mailbox = mailbox_dev;
+  k.capacity = q.capacity;
+  k.slice_capacity = q.slice_capacity;
+  if (uint64_t* trace = attach_join_trace(n_tiles)) k.trace = trace;
+  k.slice_offsets = out.slice_offsets;
+  k.status = q.async ? q.result->status : nullptr;
+  k.verdict = b.hinted ? b.verdict : nullptr;
+  k.fill_records = b.hinted ? b.fill_records : nullptr;
+  k.n_fill_records = b.hinted ? b.n_fill_records : 0;
+  k.hint_min = b.hint_min;
+  k.hint_max = b.hint_max;
+  k.hint_allows_duplicates = b.hint_allows_duplicates ? 1u : 0u;
+  return HY_OK;
+}
+
+// Pass 1, one of three: the build side staged in LDS (pk_count_lds: a rank table over fewer than 2^20 key values, enough tiles for
+// persistent workgroups to pay for staging it once per CU), a wave per tile that hands every row's partner rank to pass 2 (pk_count<true>:
+// probe keys without locality, an Inner join over a million rows or more, a table of a megabyte or more -- random lookups in a smaller one
+// stay in the L2), or a wave per tile that does not (pk_count<false>).
+static hy_status launch_pk_count(const JoinRequest& q, const BuildSide& b, PkBuffers& buffers, PkArgs& k, bool* build_in_lds, bool* hand_over_ranks, hipStream_t stream) {
+  const uint32_t n_tiles = k.n_tiles, partitions = 1u << q.radix_bits;
+  *hand_over_ranks = false;
+  *build_in_lds = b.rank.range < PK_LDS_KEYS && partitions <= PK_LDS_MAX_PARTITIONS && n_tiles >= static_cast<uint64_t>(option(HY_OPT_JOIN_LDS_BUILD_TILES)) && option(HY_OPT_JOIN_LDS_BUILD);   // (tests lower the bar)
+  hipEvent_t count_started = nullptr, count_stopped = nullptr;
+  if (*build_in_lds) {
+    HY_TRY(buffers.row_masks.alloc(size_t{n_tiles} * (2 * PK_TILE / 8)));
+    k.row_masks = buffers.row_masks.as<uint8_t>();
+    HY_TRY(raise_pk_count_lds());
+    const uint32_t groups = std::min<uint32_t>(device_cu_count(), (n_tiles + PK_LDS_SUBTILES - 1) / PK_LDS_SUBTILES);
+    profile_events(&count_started, &count_stopped, HY_KERNEL_JOIN_COUNT);
+    hipExtLaunchKernelGGL(pk_count_lds, dim3(groups), dim3(1024), pk_count_lds_bytes(b.rank.range, partitions), stream, count_started, count_stopped, 0, k);
+    return HY_OK;
+  }
+  profile_events(&count_started, &count_stopped, HY_KERNEL_JOIN_COUNT);
+  const int64_t hand_over_from = option(HY_OPT_JOIN_HAND_OVER_RANKS);
+  if (q.mode == HY_JOIN_INNER && !q.count_only && hand_over_from > 0 && q.probe->rows >= static_cast<uint64_t>(hand_over_from) && (b.rank.range >> 5) * 8 >= (hand_over_from == 1 ? 0u : (1u << 20)))
+    HY_TRY(probe_keys_lack_locality(q.probe, stream, hand_over_ranks));
+  const uint32_t tile_grid = 8 * ((n_tiles + 7) / 8);
+  if (*hand_over_ranks) {
+    HY_TRY(buffers.row_ranks.alloc(4 * size_t{n_tiles} * PK_TILE));
+    k.row_ranks = buffers.row_ranks.as<uint32_t>();
+    hipExtLaunchKernelGGL(pk_count<true>, dim3(tile_grid), dim3(PK_COUNT_THREADS), 0, stream, count_started, count_stopped, 0, k);
+  } else hipExtLaunchKernelGGL(pk_count<false>, dim3(tile_grid), dim3(PK_COUNT_THREADS), 0, stream, count_started, count_stopped, 0, k);
+  return HY_OK;
+}
+
+// Pass 2: the flavour of pk_emit that matches pass 1 (the rows' found / materialised bits of pk_count_lds, the ranks of pk_count<true>),
+// Inner or not; its first workgroups cut the PosLists, and it clears the zeroed block the join before used (FillCleaning).
+static hy_status launch_pk_emit(const JoinRequest& q, BuildSide& b, PkArgs& k, bool build_in_lds, bool hand_over_ranks, uint32_t max_slices, hipStream_t stream) {
+  HY_TRY(raise_pk_emit_lds());
+  hipEvent_t started = nullptr, stopped = nullptr;   // (stamped from the dispatch packet itself)
+  profile_events(&started, &stopped, HY_KERNEL_JOIN_PROBE);
+  const uint32_t cut_grid = std::min<uint32_t>(max_slices, q.slice_capacity);
+  const int64_t group = FIXED_JOIN_EMIT_TILE_GROUP;
+  k.emit_group_shift = 32;
+  if (group > 0) { k.emit_group_shift = 0; while (k.emit_group_shift < 16 && (int64_t{1} << (k.emit_group_shift + 1)) <= group) ++k.emit_group_shift; }
+  k.cut_blocks = (cut_grid + 7) / 8 * 8;   // (pk_cut_slice returns at once for slices the plan does not have)
+  k.cleaning = b.cleaning;
+  const dim3 grid(k.cut_blocks + 8 * ((k.n_tiles + 7) / 8));
+  const size_t lds_bytes = 4 * pk_emit_lds_words(1u << q.radix_bits);
+  const bool inner = q.mode == HY_JOIN_INNER;
+  if (build_in_lds && inner) hipExtLaunchKernelGGL((pk_emit<true, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  else if (build_in_lds) hipExtLaunchKernelGGL((pk_emit<false, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  else if (hand_over_ranks) hipExtLaunchKernelGGL((pk_emit<true, false, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  else if (inner) hipExtLaunchKernelGGL(pk_emit<true>, grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  else hipExtLaunchKernelGGL(pk_emit<false>, grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  HY_HIP(hipGetLastError());
+  block_cleaning_queued(b);
+  t_last_join_used_pkfk = build_in_lds ? 2 : 1;   // debug / tests: the primary-key / foreign-key kernels ran (2: with the build side's bits staged in LDS)
+  return HY_OK;
+}
+
+// Rank table, probe segments that SliceViews describe, keys of both sides int32 values (32-bit distances), counts and pair indices in
+// 32 bits, lane-ordered LDS atomics: pk_count, pk_scan (which plans the output), pk_emit.
+static hy_status probe_pkfk(const JoinRequest& q, BuildSide& b, StageClock& clock, bool* retry, hipStream_t stream) {
+  const uint32_t partitions = 1u << q.radix_bits;
+  const uint32_t n_groups = q.radix_bits ? partitions : q.probe->n_chunks;
+  const uint32_t max_slices = static_cast<uint32_t>(q.probe->rows / PROBE_SIZE_PER_CHUNK) + n_groups + 1;
+  JoinMailbox* mailbox = nullptr;
+  JoinMailbox* mailbox_dev = nullptr;
+  HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
+  JoinOutput out;
+  HY_TRY(begin_output(q, max_slices, out));
+  PkBuffers buffers;
+  PkArgs k{};
+  HY_TRY(pk_arguments(q, b, mailbox_dev, out, n_groups, buffers, k));
+  bool build_in_lds = false, hand_over_ranks = false;
+  HY_TRY(launch_pk_count(q, b, buffers, k, &build_in_lds, &hand_over_ranks, stream));
+  hipLaunchKernelGGL(pk_scan, dim3(partitions), dim3(PK_SCAN_THREADS), 0, stream, k);
+  clock.mark("pass 1 launched");
+  if (q.count_only) {
+    HY_HIP(hipStreamSynchronize(stream));
+    if (hint_confirmed(q, b, mailbox, retry) && q.count_out) *q.count_out = mailbox->n_pairs;
+    return HY_OK;
+  }
+  HY_TRY(size_output_lists(q, mailbox, stream, clock, out));
+  k.build_out = out.build;
+  k.probe_out = out.probe;
+  HY_TRY(launch_pk_emit(q, b, k, build_in_lds, hand_over_ranks, max_slices, stream));
+  clock.mark("pass 2 launched");
+  HY_TRY(copy_output_back(q, mailbox, stream, out));
+  if (q.async) {   // the temporaries go back to this thread's pool: whatever takes them next is queued behind these kernels on the same stream
+    t_join_returned_async = true;
+    return HY_OK;
+  }
+  HY_HIP(hipStreamSynchronize(stream));   // the temporaries above are freed on return
+  clock.mark("pass 2 done");
+  if (!hint_confirmed(q, b, mailbox, retry)) return HY_OK;
+  return report_join_result(q.result, mailbox->n_pairs, mailbox->n_slices, mailbox->error);
+}
+
+// ---- the general probe: sorted directory, or a rank table whose probe side the kernels above do not take ------------------------------------------
+static hy_status raise_probe_emit_lds() {   // (joins run from any thread; setting the attributes twice is harmless)
+  static OncePerDevice raised;
+  uint64_t device_bit = 0;
+  if (raised.pending(&device_bit)) {
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(probe_emit_cached), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * probe_emit_cached_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(probe_emit_generic<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * probe_emit_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(probe_emit_generic<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * probe_emit_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rt_probe_emit), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * rt_probe_emit_lds_words(MAX_PARTITIONS)));
+    raised.done(device_bit);
+  }
+  return HY_OK;
+}
+
+struct ProbeBuffers {
+  DeviceBuffer hist, base, partner, meta, uncached, words, first_cell, origin, slice_base;
+  std::vector<uint64_t> group_first_cell;   // (source of an asynchronous upload: lives until the join returns)
+  uint64_t second_at = 0, cells = 0;        // pass 1's per-(partition, tile) counts: elements | zeros up to a scan-block boundary (second_at) | pairs -- one buffer, one scan
+  JoinPlan* plan = nullptr;
+};
+
+// Everything pass 1 reads and writes; zero_two clears the zeros between its two count arrays and the words behind them.
+static hy_status probe_arguments(const JoinRequest& q, const BuildSide& b, JoinMailbox* mailbox_dev, ProbeBuffers& buffers, ProbeArgs& a, hipStream_t stream) {
+  const uint32_t n_tiles = q.probe->n_slices * (SLICE_ROWS / JOIN_TILE);
+  const uint64_t cells = uint64_t{1u << q.radix_bits} * n_tiles;
+  const uint64_t second_at = (cells + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK * SCAN_BLOCK;
+  buffers.cells = cells;
+  buffers.second_at = second_at;
+  HY_TRY(buffers.hist.alloc(4 * (second_at + cells + 1)));
+  HY_TRY(buffers.base.alloc(8 * (second_at + cells + 2)));
+  a.segments = q.probe->d_segments;
+  a.slices = q.probe->d_slices;
+  a.views = q.probe->d_slice_views;
+  a.n_tiles = n_tiles;
+  a.mode = q.mode;
+  a.radix_bits = q.radix_bits;
+  a.keep_nulls = q.keep_nulls_probe;
+  a.build_rows_zero = q.build->rows == 0;
+  a.build_bloom = q.probe_filtered ? b.bloom.as<uint8_t>() : nullptr;
+  a.dir = b.directory;
+  a.rank = b.rank;
+  a.trace = attach_join_trace(n_tiles);
+  a.pack_build_ids = b.directory.ids32 ? 1 : 0;
+  a.hashed_type = q.hashed_type;
+  a.n_secondary = q.n_secondary;
+  for (uint32_t p = 0; p < q.n_secondary; ++p) a.secondary[p] = q.secondary[p];
+  a.hist_elements = buffers.hist.as<uint32_t>();
+  a.hist_pairs = buffers.hist.as<uint32_t>() + second_at;
+  a.base_elements = buffers.base.as<uint64_t>();
+  a.base_pairs = buffers.base.as<uint64_t>() + second_at;
+  if (!q.count_only && n_tiles && !b.rank.entries) {   // pass 2 follows: let pass 1 leave its lookup results behind (6 B per probe row; a rank table is looked up again)
+    HY_TRY(buffers.partner.alloc(4 * size_t{n_tiles} * JOIN_TILE));
+    HY_TRY(buffers.meta.alloc(2 * size_t{n_tiles} * JOIN_TILE));
+    HY_TRY(buffers.uncached.alloc(4 * size_t{n_tiles} * 2));   // flags | work list of probe_emit_generic
+    a.uncached_tiles = buffers.uncached.as<uint32_t>() + n_tiles;
+    a.row_partner = buffers.partner.as<uint32_t>();
+    a.row_meta = buffers.meta.as<uint32_t>();
+    a.tile_uncached = buffers.uncached.as<uint32_t>();
+  }
+  HY_TRY(buffers.words.alloc(256));   // [0] pass 1's error flag (unused), [1] tiles with multi-partner rows, [8..15] XCD tickets, [16..17] JoinPlan
+  uint32_t* words = buffers.words.as<uint32_t>();
+  hipLaunchKernelGGL(zero_two, dim3(static_cast<uint32_t>(std::min<uint64_t>(64, (second_at - cells + 32 + 255) / 256))), dim3(256), 0, stream, buffers.hist.as<uint32_t>() + cells, size_t{second_at - cells},
+                     words, size_t{32});
+  a.error = &mailbox_dev->error;
+  a.n_uncached = words + 1;
+  a.xcd_tickets = words + 8;
+  buffers.plan = reinterpret_cast<JoinPlan*>(words + 16);
+  a.plan = buffers.plan;
+  return HY_OK;
+}
+
+// Groups of the output: the radix partitions (group g starts at cell g * n_tiles: no table), or -- no radix partitioning -- the probe chunks
+// (their tiles are consecutive).  Every 131 070 materialised elements of a group start a new output PosList.
+static hy_status output_groups(const JoinRequest& q, ProbeBuffers& buffers, uint32_t n_groups, const uint64_t** dev_first_cell, hipStream_t stream) {
+  *dev_first_cell = nullptr;
+  HY_TRY(buffers.origin.alloc(8 * (size_t{n_groups} + 1)));
+  HY_TRY(buffers.slice_base.alloc(4 * (size_t{n_groups} + 1)));
+  if (q.radix_bits) return HY_OK;
+  std::vector<uint64_t>& first_cell = buffers.group_first_cell;
+  first_cell.assign(size_t{n_groups} + 1, 0);
+  uint64_t tile = 0;
+  for (uint32_t c = 0; c < q.probe->n_chunks; ++c) {
+    const uint32_t chunk_slices = (q.probe->host_segments[c].size + SLICE_ROWS - 1) / SLICE_ROWS;
+    first_cell[c] = tile;
+    tile += (chunk_slices ? chunk_slices : 1) * (SLICE_ROWS / JOIN_TILE);   // the tiles of each of its slices, consecutive
+  }
+  first_cell[n_groups] = tile;
+  HY_TRY(buffers.first_cell.alloc(8 * (size_t{n_groups} + 1)));
+  HY_HIP(hipMemcpyAsync(buffers.first_cell.ptr, first_cell.data(), 8 * (size_t{n_groups} + 1), hipMemcpyHostToDevice, stream));
+  *dev_first_cell = buffers.first_cell.as<uint64_t>();
+  return HY_OK;
+}
+
+// Pass 1 -- rt_stream_count (a rank table, probe segments that SliceViews describe: a wave per tile, wide loads), rt_probe_count (any other
+// probe side of a rank table) or probe_count (the directory) --, the scan of its counts, the plan of the output: no host round trip in between.
+static hy_status launch_probe_count(const JoinRequest& q, bool rank_path, bool fetch_ahead, const ProbeArgs& a, ProbeBuffers& buffers, const JoinOutput& out, const uint64_t* dev_first_cell,
+                                    uint32_t n_groups, JoinMailbox* mailbox_dev, hipStream_t stream) {
+  const uint32_t n_tiles = a.n_tiles, partitions = 1u << q.radix_bits;
+  const uint64_t cells = buffers.cells, second_at = buffers.second_at;
+  if (!n_tiles) {
+    HY_HIP(hipMemsetAsync(buffers.base.ptr, 0, 8 * (second_at + cells + 2), stream));
+  } else {
+    if (rank_path && fetch_ahead) {
+      int per_cu = 0;
+      HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(rt_stream_count), 64 * STREAM_WAVES, 4 * stream_count_lds_words(partitions)));
+      hipLaunchKernelGGL(rt_stream_count, dim3(stream_grid(n_tiles, per_cu)), dim3(64 * STREAM_WAVES), 4 * stream_count_lds_words(partitions), stream, a);
+    } else if (rank_path) hipLaunchKernelGGL(rt_probe_count, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 0, stream, a);
+    else if (q.general) hipLaunchKernelGGL(probe_count<true>, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL(probe_count<false>, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 0, stream, a);
+    HY_TRY(exclusive_scan(buffers.hist.as<uint32_t>(), buffers.base.as<uint64_t>(), second_at + cells, stream, second_at));
+  }
+  hipLaunchKernelGGL(plan_output, dim3(1), dim3(256), 0, stream, a.base_elements, a.base_pairs, dev_first_cell, n_groups, n_tiles, cells, q.capacity, q.slice_capacity,
+                     buffers.origin.as<uint64_t>(), buffers.slice_base.as<uint32_t>(), out.slice_offsets, n_tiles && a.row_meta ? a.n_uncached : nullptr, buffers.plan, mailbox_dev);
+  return HY_OK;
+}
+
+// Pass 2 (every kernel returns at once if the plan says that the result does not fit): rt_probe_emit + rt_probe_cuts over a rank table;
+// over the directory probe_emit_cached (persistent workgroups over what pass 1 left behind) + probe_cuts, and probe_emit_generic for the
+// tiles pass 1 listed (usually none: the workgroups read the list's length and leave).
+static hy_status launch_probe_emit(const JoinRequest& q, bool rank_path, ProbeArgs& a, const uint64_t* dev_first_cell, uint32_t n_groups, uint32_t max_slices, const JoinMailbox* mailbox,
+                                   hipStream_t stream) {
+  const uint32_t n_tiles = a.n_tiles, partitions = 1u << q.radix_bits;
+  if (!n_tiles) return HY_OK;
+  HY_TRY(raise_probe_emit_lds());
+  const uint32_t cut_grid = std::min<uint32_t>(max_slices, q.slice_capacity);
+  if (rank_path) {
+    a.lane_ordered_atomics = lds_atomics_are_lane_ordered(stream) ? 1u : 0u;
+    hipEvent_t started = nullptr, stopped = nullptr;   // (stamped from the dispatch packet itself: event records around the launch add the gaps to its neighbours)
+    profile_events(&started, &stopped, HY_KERNEL_JOIN_PROBE);
+    hipExtLaunchKernelGGL(rt_probe_emit, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 4 * rt_probe_emit_lds_words(partitions), stream, started, stopped, 0, a);
+    if (cut_grid) hipLaunchKernelGGL(rt_probe_cuts, dim3(cut_grid), dim3(JOIN_THREADS), 0, stream, a, dev_first_cell, n_groups);
+    return HY_OK;
+  }
+  int per_cu = 0;
+  HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(probe_emit_cached), JOIN_THREADS, 4 * probe_emit_cached_lds_words(partitions)));
+  uint32_t workgroups_per_cu = per_cu > 0 ? static_cast<uint32_t>(per_cu) : 1;
+  if (FIXED_JOIN_WGS_PER_CU > 0) workgroups_per_cu = static_cast<uint32_t>(FIXED_JOIN_WGS_PER_CU);
+  // persistent workgroups: as many as fit the device at once (a multiple of the 8 XCDs), never more than tiles
+  const uint32_t resident = device_cu_count() * workgroups_per_cu / 8 * 8;
+  const uint32_t cached_grid = std::max<uint32_t>(8, std::min<uint32_t>(resident, probe_grid(n_tiles)));
+  profile_begin(stream, HY_KERNEL_JOIN_PROBE);
+  hipLaunchKernelGGL(probe_emit_cached, dim3(cached_grid), dim3(JOIN_THREADS), 4 * probe_emit_cached_lds_words(partitions), stream, a);
+  profile_end(stream);
+  if (cut_grid) hipLaunchKernelGGL(probe_cuts, dim3(cut_grid), dim3(64), 0, stream, a, dev_first_cell, n_groups);
+  if (!q.host_result || mailbox->n_uncached) {
+    const dim3 generic_grid(std::min<uint32_t>(n_tiles, device_cu_count() * 2));
+    if (q.general) hipLaunchKernelGGL(probe_emit_generic<true>, generic_grid, dim3(JOIN_THREADS), 4 * probe_emit_lds_words(partitions), stream, a);
+    else hipLaunchKernelGGL(probe_emit_generic<false>, generic_grid, dim3(JOIN_THREADS), 4 * probe_emit_lds_words(partitions), stream, a);
+  }
+  return HY_OK;
+}
+
+static hy_status probe_general(const JoinRequest& q, const BuildSide& b, bool fetch_ahead, StageClock& clock, hipStream_t stream) {
+  const bool rank_path = b.rank.entries != nullptr;
+  JoinMailbox* mailbox = nullptr;
+  JoinMailbox* mailbox_dev = nullptr;
+  HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
+  ProbeBuffers buffers;
+  ProbeArgs a{};
+  HY_TRY(probe_arguments(q, b, mailbox_dev, buffers, a, stream));
+  const uint32_t n_groups = q.radix_bits ? 1u << q.radix_bits : q.probe->n_chunks;
+  const uint64_t* dev_first_cell = nullptr;
+  HY_TRY(output_groups(q, buffers, n_groups, &dev_first_cell, stream));
+  const uint32_t max_slices = static_cast<uint32_t>(q.probe->rows / PROBE_SIZE_PER_CHUNK) + n_groups + 1;   // what the host knows without asking
+  JoinOutput out;
+  HY_TRY(begin_output(q, max_slices, out));
+  HY_TRY(launch_probe_count(q, rank_path, fetch_ahead, a, buffers, out, dev_first_cell, n_groups, mailbox_dev, stream));
+  clock.mark("pass 1 launched");
+  if (q.count_only) {
+    HY_HIP(hipStreamSynchronize(stream));
+    if (mailbox->error) return fail(HY_ERR_UNSUPPORTED, "a probe row matches more than 4 194 303 build rows");   // (pass 1 clamped its count)
+    if (q.count_out) *q.count_out = mailbox->n_pairs;
+    return HY_OK;
+  }
+  HY_TRY(size_output_lists(q, mailbox, stream, clock, out));
+  a.partition_element_origin = buffers.origin.as<uint64_t>();
+  a.partition_slice_base = buffers.slice_base.as<uint32_t>();
+  a.build_out = out.build;
+  a.probe_out = out.probe;
+  a.slice_offsets = out.slice_offsets;
+  HY_TRY(launch_probe_emit(q, rank_path, a, dev_first_cell, n_groups, max_slices, mailbox, stream));
+  HY_HIP(hipGetLastError());
+  clock.mark("pass 2 launched");
+  HY_TRY(copy_output_back(q, mailbox, stream, out));
+  HY_HIP(hipStreamSynchronize(stream));   // the temporaries above are freed on return
+  clock.mark("pass 2 done");
+  return report_join_result(q.result, mailbox->n_pairs, mailbox->n_slices, mailbox->error);
+}
+
+// One attempt at the join.  *retry: the build column contradicted its key hint -- the hint is dropped, nothing the call wrote counts.
+static hy_status run_join_once(const hy_column* left, const hy_column* right, uint32_t mode, hy_join_result* result, bool count_only, uint64_t* count_out,
+                               const hy_join_predicate* secondary, uint32_t n_secondary, bool* retry) {
+  JoinRequest q;
+  HY_TRY(resolve_join_request(left, right, mode, result, count_only, count_out, secondary, n_secondary, &q));
+  hipStream_t stream = current_stream();
   BuildSide b;
   StageClock clock;
-  // Will the probe side take the kernels of join_pkfk.hpp if the build side turns out to be a rank table?  (Everything that does not
-  // depend on the build side: probe segments that SliceViews describe -- int32 values / FrameOfReference offsets, no NULLs, 16-byte
-  // aligned --, counts and pair indices in 32 bits, lane-ordered LDS atomics.)
-  bool probe_views = !probe->is_reference && probe->n_slices > 0 && FIXED_JOIN_FETCH_AHEAD;
-  for (uint32_t c = 0; c < probe->n_chunks && probe_views; ++c) {
-    const hy_segment& seg = probe->host_segments[c];
-    probe_views = !seg.nulls && reinterpret_cast<uintptr_t>(seg.data) % 16 == 0 &&
-                  ((seg.encoding == HY_ENC_UNENCODED && seg.data_type == HY_TYPE_INT) || seg.encoding == HY_ENC_FRAME_OF_REFERENCE);
-  }
-  const bool probe_takes_pk = probe_views && hashed_type == 0 && n_secondary == 0 && probe->rows < 0xFFFF0000ull && option(HY_OPT_JOIN_PKFK) &&
-                              (count_only || result->capacity <= 0xFFFFFFFFull) && lds_atomics_are_lane_ordered(stream);
-  HY_TRY(prepare_build(build, keep_nulls_build, probe_filtered, pack_build_ids, hashed_type, n_secondary == 0, semi_anti && n_secondary == 0, probe_takes_pk, b, stream));
+  bool probe_views = false;
+  const bool probe_takes_pk = probe_takes_pk_kernels(q, stream, &probe_views);
+  const BuildWants wants{q.keep_nulls_build, q.probe_filtered, q.pack_build_ids, q.n_secondary == 0, q.semi_anti && q.n_secondary == 0, probe_takes_pk, q.hashed_type};
+  HY_TRY(prepare_build(q.build, wants, b, stream));
   const bool rank_path = b.rank.entries != nullptr;
-  // A rank table filled from the build column's key hint (rank_table_fill_checked) is confirmed when the join's kernels have finished:
-  // if the column is not what the hint said, the hint is dropped, whatever the join wrote is discarded and the caller runs it again.
-  auto hint_confirmed = [&](const JoinMailbox* mailbox) {   // (after the stream synchronise that makes pk_plan's mailbox visible)
-    if (!b.hinted || !mailbox->build_unconfirmed) return true;
-    build->join_hint.state.store(2, std::memory_order_release);
-    *retry = true;
-    return false;
-  };
-  const bool fetch_ahead = rank_path && probe_views;   // pass 1 of the general rank-table kernels is the wave-per-tile kernel with wide loads
   t_last_join_used_rank_table = rank_path ? (b.rank.identity_rows ? 2 : 1) : 0;
   t_last_join_used_pkfk = 0;
   t_last_join_hinted_attempt = b.hinted ? 1 : 0;
   clock.mark("build side launched");
-
   if (result) {
-    result->radix_bits = radix_bits;
-    result->left_is_build = build_right ? 0 : 1;
+    result->radix_bits = q.radix_bits;
+    result->left_is_build = q.build_right ? 0 : 1;
     result->n_slices = 0;
     result->n_pairs = 0;
   }
   if (mode == HY_JOIN_ANTI_NULL_AS_TRUE && b.any_null) {   // join_hash.cpp:483-494
     if (count_out) *count_out = 0;
-    if (result && result->slice_offsets && host_result) result->slice_offsets[0] = 0;
-    if (result && result->slice_offsets && !host_result) HY_HIP(hipMemsetAsync(result->slice_offsets, 0, 8, stream));
+    if (result && result->slice_offsets && q.host_result) result->slice_offsets[0] = 0;
+    if (result && result->slice_offsets && !q.host_result) HY_HIP(hipMemsetAsync(result->slice_offsets, 0, 8, stream));
     return HY_OK;
   }
-
-  // The primary-key / foreign-key probe (join_pkfk.hpp): rank table, probe segments that SliceViews describe, keys of both sides
-  // int32 values (32-bit distances), counts and pair indices in 32 bits, lane-ordered LDS atomics.
   const bool pk_path = rank_path && probe_takes_pk && static_cast<int64_t>(b.rank.key_min) >= INT32_MIN && static_cast<int64_t>(b.rank.key_min + b.rank.range) <= INT32_MAX;
   if (b.bloom_is_bits && !pk_path) return fail(HY_ERR_DEVICE, "join: a bit filter was built for kernels that do not run");   // (cannot happen: a hinted build has int32 keys)
-  if (pk_path) {
-    const uint32_t n_tiles = probe->n_slices * PK_TILES_PER_SLICE, partitions = 1u << radix_bits;
-    const uint32_t stride = (n_tiles + 1 + 3) & ~3u;
-    const uint32_t n_groups = radix_bits ? partitions : probe->n_chunks;
-    const uint32_t max_slices = static_cast<uint32_t>(probe->rows / PROBE_SIZE_PER_CHUNK) + n_groups + 1;
-    DeviceBuffer cells, small;
-    HY_TRY(cells.alloc(size_t{12} * partitions * stride));
-    const size_t at_origin = align_up(8 * size_t{partitions}, 8), at_slice_base = at_origin + 8 * (size_t{partitions} + 1), at_words = align_up(at_slice_base + 4 * (size_t{n_groups} + 1), 8);
-    HY_TRY(small.alloc(at_words + 64));
-    JoinMailbox* mailbox = nullptr;
-    JoinMailbox* mailbox_dev = nullptr;
-    HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
-    hy_row_id* user_build = nullptr;
-    hy_row_id* user_probe = nullptr;
-    if (!count_only) {
-      user_build = result->left_is_build ? result->left_pos : result->right_pos;
-      user_probe = result->left_is_build ? result->right_pos : result->left_pos;
-      if (!user_probe && result->capacity) return fail(HY_ERR_INVALID, "join result: PosList buffer for the probe side missing");
-      if (!semi_anti && !user_build && result->capacity) return fail(HY_ERR_INVALID, "join result: PosList buffer for the build side missing");
-      if (!result->slice_offsets) return fail(HY_ERR_INVALID, "join result: slice_offsets missing");
-    }
-    DeviceBuffer d_build_out, d_probe_out, d_slice_offsets;
-    uint64_t* dev_slice_offsets = count_only ? nullptr : result->slice_offsets;
-    if (!count_only && host_result) {
-      HY_TRY(d_slice_offsets.alloc(8 * (size_t{max_slices} + 2)));
-      dev_slice_offsets = d_slice_offsets.as<uint64_t>();
-    }
-    PkArgs k{};
-    k.views = probe->d_slice_views;
-    k.n_tiles = n_tiles;
-    k.stride = stride;
-    k.mode = mode;
-    k.radix_bits = radix_bits;
-    k.keep_nulls = keep_nulls_probe;
-    k.n_groups = n_groups;
-    k.build_bloom = probe_filtered ? b.bloom.as<uint8_t>() : nullptr;
-    k.bloom_is_bits = b.bloom_is_bits ? 1u : 0u;
-    k.rank = b.rank;
-    k.ids32 = b.directory.ids32;
-    k.row_ids = b.directory.row_ids;
-    k.counts = cells.as<uint32_t>();
-    k.rel_elements = k.counts + size_t{partitions} * stride;
-    k.rel_pairs = k.rel_elements + size_t{partitions} * stride;
-    char* small_base = small.as<char>();
-    k.totals = reinterpret_cast<uint32_t*>(small_base);
-    k.origin_pairs = reinterpret_cast<uint64_t*>(small_base + at_origin);
-    k.slice_base = reinterpret_cast<uint32_t*>(small_base + at_slice_base);
-    k.group_first_tile = probe->d_first_slice;
-    k.ticket = reinterpret_cast<uint32_t*>(small_base + at_words);
-    k.plan = reinterpret_cast<JoinPlan*>(small_base + at_words + 16);
-    k.mailbox = mailbox_dev;
-    k.capacity = count_only ? ~0ull : result->capacity;
-    k.slice_capacity = count_only ? 0xFFFFFFFFu : result->slice_capacity;
-    if (HY_DEBUG_ENV("HY_JOIN_TRACE")) {
-      static uint64_t* trace_buffer = nullptr;
-      if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 6 * JOIN_TRACE_TILES);
-      if (n_tiles <= JOIN_TRACE_TILES) { k.trace = trace_buffer; g_join_trace = trace_buffer; g_join_trace_tiles = n_tiles; }
-    }
-    k.slice_offsets = dev_slice_offsets;
-    // HY_JOIN_ASYNC: no host round trip at all -- pk_plan leaves in device memory what the host would read from the mailbox
-    const bool async = !count_only && !host_result && (result->flags & HY_JOIN_ASYNC) && result->status;
-    k.status = async ? result->status : nullptr;
-    k.verdict = b.hinted ? b.verdict : nullptr;
-    k.fill_records = b.hinted ? b.fill_records : nullptr;
-    k.n_fill_records = b.hinted ? b.n_fill_records : 0;
-    k.hint_min = b.hint_min;
-    k.hint_max = b.hint_max;
-    k.hint_allows_duplicates = b.hint_allows_duplicates ? 1u : 0u;
-    const uint32_t tile_grid = 8 * ((n_tiles + 7) / 8);
-    // The build side staged in LDS (pk_count_lds, join_pkfk.hpp): a rank table over fewer than 2^20 key values, enough tiles for
-    // persistent workgroups to pay for staging it once per CU.
-    DeviceBuffer row_masks, row_ranks;
-    bool hand_over_ranks = false;
-    const bool build_in_lds = b.rank.range < PK_LDS_KEYS && partitions <= PK_LDS_MAX_PARTITIONS && n_tiles >= static_cast<uint64_t>(option(HY_OPT_JOIN_LDS_BUILD_TILES)) && option(HY_OPT_JOIN_LDS_BUILD);   // (tests lower the bar)
-    if (build_in_lds) {
-      HY_TRY(row_masks.alloc(size_t{n_tiles} * (2 * PK_TILE / 8)));
-      k.row_masks = row_masks.as<uint8_t>();
-      static OncePerDevice count_lds_raised;
-      uint64_t device_bit = 0;
-      if (count_lds_raised.pending(&device_bit)) {
-        HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_count_lds), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(pk_count_lds_bytes(PK_LDS_KEYS - 1, PK_LDS_MAX_PARTITIONS))));
-        count_lds_raised.done(device_bit);
-      }
-      int device = 0, cus = 256;
-      (void)hipGetDevice(&device);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-      const uint32_t groups = std::min<uint32_t>(static_cast<uint32_t>(cus), (n_tiles + PK_LDS_SUBTILES - 1) / PK_LDS_SUBTILES);
-      hipEvent_t count_started = nullptr, count_stopped = nullptr;
-      profile_events(&count_started, &count_stopped, HY_KERNEL_JOIN_COUNT);
-      hipExtLaunchKernelGGL(pk_count_lds, dim3(groups), dim3(1024), pk_count_lds_bytes(b.rank.range, partitions), stream, count_started, count_stopped, 0, k);
-    } else {
-      hipEvent_t count_started = nullptr, count_stopped = nullptr;
-      profile_events(&count_started, &count_stopped, HY_KERNEL_JOIN_COUNT);
-      // Probe keys without locality, an Inner join over a million rows or more: pass 1 hands every row's partner rank to pass 2 (pk_count_wave RANKS)
-      // (... and a table of a megabyte or more: random lookups in a smaller one stay in the L2)
-      if (mode == HY_JOIN_INNER && !count_only && option(HY_OPT_JOIN_HAND_OVER_RANKS) > 0 && probe->rows >= static_cast<uint64_t>(option(HY_OPT_JOIN_HAND_OVER_RANKS)) &&
-          (b.rank.range >> 5) * 8 >= (option(HY_OPT_JOIN_HAND_OVER_RANKS) == 1 ? 0u : (1u << 20)))
-        HY_TRY(probe_keys_lack_locality(probe, stream, &hand_over_ranks));
-      if (hand_over_ranks) {
-        HY_TRY(row_ranks.alloc(4 * size_t{n_tiles} * PK_TILE));
-        k.row_ranks = row_ranks.as<uint32_t>();
-        hipExtLaunchKernelGGL(pk_count<true>, dim3(tile_grid), dim3(PK_COUNT_THREADS), 0, stream, count_started, count_stopped, 0, k);
-      } else hipExtLaunchKernelGGL(pk_count<false>, dim3(tile_grid), dim3(PK_COUNT_THREADS), 0, stream, count_started, count_stopped, 0, k);
-    }
-    hipLaunchKernelGGL(pk_scan, dim3(partitions), dim3(PK_SCAN_THREADS), 0, stream, k);
-    clock.mark("pass 1 launched");
-    if (count_only) {
-      HY_HIP(hipStreamSynchronize(stream));
-      if (!hint_confirmed(mailbox)) return HY_OK;
-      if (count_out) *count_out = mailbox->n_pairs;
-      return HY_OK;
-    }
-    hy_row_id* dev_build = user_build;
-    hy_row_id* dev_probe = user_probe;
-    if (host_result) {   // the staging buffers are sized by the pair count: ask now
-      HY_HIP(hipStreamSynchronize(stream));
-      clock.mark("pass 1 done");
-      if (mailbox->fits) {
-        if (!semi_anti) { HY_TRY(d_build_out.alloc(8 * mailbox->n_pairs)); dev_build = d_build_out.as<hy_row_id>(); }
-        HY_TRY(d_probe_out.alloc(8 * mailbox->n_pairs));
-        dev_probe = d_probe_out.as<hy_row_id>();
-      }
-    }
-    k.build_out = semi_anti ? nullptr : dev_build;
-    k.probe_out = dev_probe;
-    static OncePerDevice pk_lds_raised;
-    uint64_t pk_device_bit = 0;
-    if (pk_lds_raised.pending(&pk_device_bit)) {
-      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
-      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
-      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
-      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
-      HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
-      pk_lds_raised.done(pk_device_bit);
-    }
-    hipEvent_t started = nullptr, stopped = nullptr;   // (stamped from the dispatch packet itself)
-    profile_events(&started, &stopped, HY_KERNEL_JOIN_PROBE);
-    const uint32_t cut_grid = std::min<uint32_t>(max_slices, result->slice_capacity);
-    {
-      const int64_t group = FIXED_JOIN_EMIT_TILE_GROUP;
-      k.emit_group_shift = 32;
-      if (group > 0) { k.emit_group_shift = 0; while (k.emit_group_shift < 16 && (int64_t{1} << (k.emit_group_shift + 1)) <= group) ++k.emit_group_shift; }
-    }
-    k.cut_blocks = (cut_grid + 7) / 8 * 8;   // (pk_cut_slice returns at once for slices the plan does not have)
-    k.cleaning = b.cleaning;
-    if (build_in_lds) {   // (pass 2 reads the rows' found / materialised bits pass 1 left behind)
-      if (mode == HY_JOIN_INNER) hipExtLaunchKernelGGL((pk_emit<true, true>), dim3(k.cut_blocks + tile_grid), dim3(PK_THREADS), 4 * pk_emit_lds_words(partitions), stream, started, stopped, 0, k);
-      else hipExtLaunchKernelGGL((pk_emit<false, true>), dim3(k.cut_blocks + tile_grid), dim3(PK_THREADS), 4 * pk_emit_lds_words(partitions), stream, started, stopped, 0, k);
-    } else if (hand_over_ranks) hipExtLaunchKernelGGL((pk_emit<true, false, true>), dim3(k.cut_blocks + tile_grid), dim3(PK_THREADS), 4 * pk_emit_lds_words(partitions), stream, started, stopped, 0, k);
-    else if (mode == HY_JOIN_INNER) hipExtLaunchKernelGGL(pk_emit<true>, dim3(k.cut_blocks + tile_grid), dim3(PK_THREADS), 4 * pk_emit_lds_words(partitions), stream, started, stopped, 0, k);
-    else hipExtLaunchKernelGGL(pk_emit<false>, dim3(k.cut_blocks + tile_grid), dim3(PK_THREADS), 4 * pk_emit_lds_words(partitions), stream, started, stopped, 0, k);
-    HY_HIP(hipGetLastError());
-    if (b.cleaned) { b.cleaned->clean = true; b.cleaned->dirty_table = b.cleaned->dirty_filter = 0; }
-    clock.mark("pass 2 launched");
-    t_last_join_used_pkfk = build_in_lds ? 2 : 1;   // debug / tests: the primary-key / foreign-key kernels ran (2: with the build side's bits staged in LDS)
-    if (host_result) {
-      if (mailbox->fits && mailbox->n_pairs) {
-        HY_HIP(hipMemcpyAsync(user_probe, dev_probe, 8 * mailbox->n_pairs, hipMemcpyDeviceToHost, stream));
-        if (!semi_anti) HY_HIP(hipMemcpyAsync(user_build, dev_build, 8 * mailbox->n_pairs, hipMemcpyDeviceToHost, stream));
-      }
-      if (mailbox->fits) HY_HIP(hipMemcpyAsync(result->slice_offsets, dev_slice_offsets, 8 * (size_t{mailbox->n_slices} + 1), hipMemcpyDeviceToHost, stream));
-    }
-    if (async) {   // the temporaries go back to this thread's pool: whatever takes them next is queued behind these kernels on the same stream
-      t_join_returned_async = true;
-      return HY_OK;
-    }
-    HY_HIP(hipStreamSynchronize(stream));   // the temporaries above are freed on return
-    clock.mark("pass 2 done");
-    if (!hint_confirmed(mailbox)) return HY_OK;
-    result->n_slices = mailbox->n_slices;
-    result->n_pairs = mailbox->n_pairs;
-    if (mailbox->n_slices > result->slice_capacity) return fail(HY_ERR_CAPACITY, "join produces %u output PosLists, slice capacity is %u", mailbox->n_slices, result->slice_capacity);
-    if (mailbox->n_pairs > result->capacity) return fail(HY_ERR_CAPACITY, "join produces %llu pairs, capacity is %llu", static_cast<unsigned long long>(mailbox->n_pairs), static_cast<unsigned long long>(result->capacity));
-    return HY_OK;
-  }
-
-  // probe pass 1
-  const uint32_t n_tiles = probe->n_slices * (SLICE_ROWS / JOIN_TILE);
-  const uint32_t partitions = 1u << radix_bits;
-  const size_t cells = size_t{partitions} * n_tiles;
-  // pass 1's per-(partition, tile) counts: elements | zeros up to a scan-block boundary | pairs -- one buffer, one scan
-  const uint64_t second_at = (uint64_t{cells} + 1 + SCAN_BLOCK - 1) / SCAN_BLOCK * SCAN_BLOCK;
-  DeviceBuffer hist, base;
-  HY_TRY(hist.alloc(4 * (second_at + cells + 1)));
-  HY_TRY(base.alloc(8 * (second_at + cells + 2)));
-  ProbeArgs a{};
-  a.segments = probe->d_segments;
-  a.slices = probe->d_slices;
-  a.views = probe->d_slice_views;
-  a.n_tiles = n_tiles;
-  a.mode = mode;
-  a.radix_bits = radix_bits;
-  a.keep_nulls = keep_nulls_probe;
-  a.build_rows_zero = build->rows == 0;
-  a.build_bloom = probe_filtered ? b.bloom.as<uint8_t>() : nullptr;
-  a.dir = b.directory;
-  a.rank = b.rank;
-  a.trace = nullptr;
-  if (HY_DEBUG_ENV("HY_JOIN_TRACE")) {
-    static uint64_t* trace_buffer = nullptr;
-    if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 6 * JOIN_TRACE_TILES);
-    if (n_tiles <= JOIN_TRACE_TILES) { a.trace = trace_buffer; g_join_trace = trace_buffer; g_join_trace_tiles = n_tiles; }
-  }
-  a.pack_build_ids = b.directory.ids32 ? 1 : 0;
-  a.hashed_type = hashed_type;
-  a.n_secondary = n_secondary;
-  for (uint32_t p = 0; p < n_secondary; ++p) {   // as the probe sees them: build <condition> probe (join_hash.cpp:158-165)
-    a.secondary[p].build = (build_right ? secondary[p].right_column : secondary[p].left_column)->d_segments;
-    a.secondary[p].probe = (build_right ? secondary[p].left_column : secondary[p].right_column)->d_segments;
-    a.secondary[p].condition = build_right ? flip_condition(secondary[p].condition) : secondary[p].condition;
-  }
-  a.hist_elements = hist.as<uint32_t>();
-  a.hist_pairs = hist.as<uint32_t>() + second_at;
-  a.base_elements = base.as<uint64_t>();
-  a.base_pairs = base.as<uint64_t>() + second_at;
-  DeviceBuffer d_partner, d_meta, d_uncached;
-  if (!count_only && n_tiles && !rank_path) {   // pass 2 follows: let pass 1 leave its lookup results behind (6 B per probe row; a rank table is looked up again)
-    HY_TRY(d_partner.alloc(4 * size_t{n_tiles} * JOIN_TILE));
-    HY_TRY(d_meta.alloc(2 * size_t{n_tiles} * JOIN_TILE));
-    HY_TRY(d_uncached.alloc(4 * size_t{n_tiles} * 2));   // flags | work list of probe_emit_generic
-    a.uncached_tiles = d_uncached.as<uint32_t>() + n_tiles;
-    a.row_partner = d_partner.as<uint32_t>();
-    a.row_meta = d_meta.as<uint32_t>();
-    a.tile_uncached = d_uncached.as<uint32_t>();
-  }
-  JoinMailbox* mailbox = nullptr;
-  JoinMailbox* mailbox_dev = nullptr;
-  HY_TRY(join_mailbox(&mailbox, &mailbox_dev));
-  DeviceBuffer d_words;   // [0] pass 1's error flag (unused), [1] tiles with multi-partner rows, [8..15] XCD tickets, [16..17] JoinPlan
-  HY_TRY(d_words.alloc(256));
-  hipLaunchKernelGGL(zero_two, dim3(static_cast<uint32_t>(std::min<uint64_t>(64, (second_at - cells + 32 + 255) / 256))), dim3(256), 0, stream, hist.as<uint32_t>() + cells, size_t{second_at - cells},
-                     d_words.as<uint32_t>(), size_t{32});   // the zeros between pass 1's two count arrays | the words above
-  a.error = &mailbox_dev->error;
-  a.n_uncached = d_words.as<uint32_t>() + 1;
-  a.xcd_tickets = d_words.as<uint32_t>() + 8;
-  JoinPlan* d_plan = reinterpret_cast<JoinPlan*>(d_words.as<uint32_t>() + 16);
-  a.plan = d_plan;
-
-  // Groups of the output: the radix partitions, or -- no radix partitioning -- the probe chunks (their tiles are
-  // consecutive).  Every 131 070 materialised elements of a group start a new output PosList.
-  const uint32_t n_groups = radix_bits ? partitions : probe->n_chunks;
-  DeviceBuffer d_first_cell, d_origin, d_slice_base;
-  HY_TRY(d_origin.alloc(8 * (size_t{n_groups} + 1)));
-  HY_TRY(d_slice_base.alloc(4 * (size_t{n_groups} + 1)));
-  std::vector<uint64_t> group_first_cell;   // (source of an asynchronous upload: lives until the join returns)
-  const uint64_t* dev_first_cell = nullptr;   // radix partitions: group g starts at cell g * n_tiles
-  if (!radix_bits) {
-    group_first_cell.assign(size_t{n_groups} + 1, 0);
-    uint64_t tile = 0;
-    for (uint32_t c = 0; c < probe->n_chunks; ++c) {
-      const uint32_t chunk_slices = (probe->host_segments[c].size + SLICE_ROWS - 1) / SLICE_ROWS;
-      group_first_cell[c] = tile;
-      tile += (chunk_slices ? chunk_slices : 1) * (SLICE_ROWS / JOIN_TILE);   // the tiles of each of its slices, consecutive
-    }
-    group_first_cell[n_groups] = tile;
-    HY_TRY(d_first_cell.alloc(8 * (size_t{n_groups} + 1)));
-    HY_HIP(hipMemcpyAsync(d_first_cell.ptr, group_first_cell.data(), 8 * (size_t{n_groups} + 1), hipMemcpyHostToDevice, stream));
-    dev_first_cell = d_first_cell.as<uint64_t>();
-  }
-  const uint32_t max_slices = static_cast<uint32_t>(probe->rows / PROBE_SIZE_PER_CHUNK) + n_groups + 1;   // what the host knows without asking
-
-  // the caller's buffers
-  hy_row_id* user_build = nullptr;
-  hy_row_id* user_probe = nullptr;
-  if (!count_only) {
-    user_build = result->left_is_build ? result->left_pos : result->right_pos;
-    user_probe = result->left_is_build ? result->right_pos : result->left_pos;
-    if (!user_probe && result->capacity) return fail(HY_ERR_INVALID, "join result: PosList buffer for the probe side missing");
-    if (!semi_anti && !user_build && result->capacity) return fail(HY_ERR_INVALID, "join result: PosList buffer for the build side missing");
-    if (!result->slice_offsets) return fail(HY_ERR_INVALID, "join result: slice_offsets missing");
-  }
-  DeviceBuffer d_build_out, d_probe_out, d_slice_offsets;
-  uint64_t* dev_slice_offsets = count_only ? nullptr : result->slice_offsets;
-  if (!count_only && host_result) {
-    HY_TRY(d_slice_offsets.alloc(8 * (size_t{max_slices} + 2)));
-    dev_slice_offsets = d_slice_offsets.as<uint64_t>();
-  }
-
-  // pass 1, the scan of its counts, the plan of the output -- no host round trip in between
-  if (n_tiles) {
-    if (rank_path && fetch_ahead) {
-      int per_cu = 0;
-      HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(rt_stream_count), 64 * STREAM_WAVES, 4 * stream_count_lds_words(partitions)));
-      hipLaunchKernelGGL(rt_stream_count, dim3(stream_grid(n_tiles, per_cu)), dim3(64 * STREAM_WAVES), 4 * stream_count_lds_words(partitions), stream, a);
-    } else if (rank_path) {
-      hipLaunchKernelGGL(rt_probe_count, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 0, stream, a);
-    } else if (general) hipLaunchKernelGGL(probe_count<true>, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL(probe_count<false>, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 0, stream, a);
-    HY_TRY(exclusive_scan(hist.as<uint32_t>(), base.as<uint64_t>(), second_at + cells, stream, second_at));
-  } else {
-    HY_HIP(hipMemsetAsync(base.ptr, 0, 8 * (second_at + cells + 2), stream));
-  }
-  hipLaunchKernelGGL(plan_output, dim3(1), dim3(256), 0, stream, a.base_elements, a.base_pairs, dev_first_cell, n_groups, n_tiles, uint64_t{cells},
-                     count_only ? ~0ull : result->capacity, count_only ? 0xFFFFFFFFu : result->slice_capacity, d_origin.as<uint64_t>(), d_slice_base.as<uint32_t>(),
-                     dev_slice_offsets, n_tiles && a.row_meta ? a.n_uncached : nullptr, d_plan, mailbox_dev);
-  clock.mark("pass 1 launched");
-  if (count_only) {
-    HY_HIP(hipStreamSynchronize(stream));
-    if (mailbox->error) return fail(HY_ERR_UNSUPPORTED, "a probe row matches more than 4 194 303 build rows");   // (pass 1 clamped its count)
-    if (count_out) *count_out = mailbox->n_pairs;
-    return HY_OK;
-  }
-  hy_row_id* dev_build = user_build;
-  hy_row_id* dev_probe = user_probe;
-  if (host_result) {   // the staging buffers are sized by the pair count: ask now
-    HY_HIP(hipStreamSynchronize(stream));
-    clock.mark("pass 1 done");
-    if (mailbox->fits) {
-      if (!semi_anti) { HY_TRY(d_build_out.alloc(8 * mailbox->n_pairs)); dev_build = d_build_out.as<hy_row_id>(); }
-      HY_TRY(d_probe_out.alloc(8 * mailbox->n_pairs));
-      dev_probe = d_probe_out.as<hy_row_id>();
-    }
-  }
-  a.partition_element_origin = d_origin.as<uint64_t>();
-  a.partition_slice_base = d_slice_base.as<uint32_t>();
-  a.build_out = semi_anti ? nullptr : dev_build;
-  a.probe_out = dev_probe;
-  a.slice_offsets = dev_slice_offsets;
-  static OncePerDevice lds_raised;   // (joins run from any thread; setting the attributes twice is harmless)
-  uint64_t lds_device_bit = 0;
-  if (n_tiles && lds_raised.pending(&lds_device_bit)) {
-    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(probe_emit_cached), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * probe_emit_cached_lds_words(MAX_PARTITIONS)));
-    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(probe_emit_generic<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * probe_emit_lds_words(MAX_PARTITIONS)));
-    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(probe_emit_generic<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * probe_emit_lds_words(MAX_PARTITIONS)));
-    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rt_probe_emit), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * rt_probe_emit_lds_words(MAX_PARTITIONS)));
-    lds_raised.done(lds_device_bit);
-  }
-  if (n_tiles && rank_path) {   // (every pass 2 kernel returns at once if the plan says that the result does not fit)
-    a.lane_ordered_atomics = lds_atomics_are_lane_ordered(stream) ? 1u : 0u;
-    hipEvent_t started = nullptr, stopped = nullptr;   // (stamped from the dispatch packet itself: event records around the launch add the gaps to its neighbours)
-    profile_events(&started, &stopped, HY_KERNEL_JOIN_PROBE);
-    hipExtLaunchKernelGGL(rt_probe_emit, dim3(probe_grid(n_tiles)), dim3(JOIN_THREADS), 4 * rt_probe_emit_lds_words(partitions), stream, started, stopped, 0, a);
-    const uint32_t cut_grid = std::min<uint32_t>(max_slices, result->slice_capacity);
-    if (cut_grid) hipLaunchKernelGGL(rt_probe_cuts, dim3(cut_grid), dim3(JOIN_THREADS), 0, stream, a, dev_first_cell, n_groups);
-  } else if (n_tiles) {
-    uint32_t workgroups_per_cu = 1;
-    {
-      int per_cu = 0;
-      HY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(probe_emit_cached), JOIN_THREADS, 4 * probe_emit_cached_lds_words(partitions)));
-      workgroups_per_cu = per_cu > 0 ? static_cast<uint32_t>(per_cu) : 1;
-    }
-    if (FIXED_JOIN_WGS_PER_CU > 0) workgroups_per_cu = static_cast<uint32_t>(FIXED_JOIN_WGS_PER_CU);
-    // persistent workgroups: as many as fit the device at once (a multiple of the 8 XCDs), never more than tiles
-    const uint32_t resident = device_cu_count() * workgroups_per_cu / 8 * 8;
-    const uint32_t cached_grid = std::max<uint32_t>(8, std::min<uint32_t>(resident, probe_grid(n_tiles)));
-    profile_begin(stream, HY_KERNEL_JOIN_PROBE);
-    hipLaunchKernelGGL(probe_emit_cached, dim3(cached_grid), dim3(JOIN_THREADS), 4 * probe_emit_cached_lds_words(partitions), stream, a);
-    profile_end(stream);
-    const uint32_t cut_grid = std::min<uint32_t>(max_slices, result->slice_capacity);
-    if (cut_grid) hipLaunchKernelGGL(probe_cuts, dim3(cut_grid), dim3(64), 0, stream, a, dev_first_cell, n_groups);
-    // the tiles pass 1 listed (usually none: the workgroups read the list's length and leave)
-    if (!host_result || mailbox->n_uncached) {
-      const dim3 generic_grid(std::min<uint32_t>(n_tiles, device_cu_count() * 2));
-      if (general) hipLaunchKernelGGL(probe_emit_generic<true>, generic_grid, dim3(JOIN_THREADS), 4 * probe_emit_lds_words(partitions), stream, a);
-      else hipLaunchKernelGGL(probe_emit_generic<false>, generic_grid, dim3(JOIN_THREADS), 4 * probe_emit_lds_words(partitions), stream, a);
-    }
-  }
-  HY_HIP(hipGetLastError());
-  clock.mark("pass 2 launched");
-  if (host_result) {
-    if (mailbox->fits && mailbox->n_pairs) {
-      HY_HIP(hipMemcpyAsync(user_probe, dev_probe, 8 * mailbox->n_pairs, hipMemcpyDeviceToHost, stream));
-      if (!semi_anti) HY_HIP(hipMemcpyAsync(user_build, dev_build, 8 * mailbox->n_pairs, hipMemcpyDeviceToHost, stream));
-    }
-    if (mailbox->fits) HY_HIP(hipMemcpyAsync(result->slice_offsets, dev_slice_offsets, 8 * (size_t{mailbox->n_slices} + 1), hipMemcpyDeviceToHost, stream));
-  }
-  HY_HIP(hipStreamSynchronize(stream));   // the temporaries above are freed on return
-  clock.mark("pass 2 done");
-  result->n_slices = mailbox->n_slices;
-  result->n_pairs = mailbox->n_pairs;
-  if (mailbox->n_slices > result->slice_capacity) return fail(HY_ERR_CAPACITY, "join produces %u output PosLists, slice capacity is %u", mailbox->n_slices, result->slice_capacity);
-  if (mailbox->n_pairs > result->capacity) return fail(HY_ERR_CAPACITY, "join produces %llu pairs, capacity is %llu", static_cast<unsigned long long>(mailbox->n_pairs), static_cast<unsigned long long>(result->capacity));
-  if (mailbox->error) return fail(HY_ERR_UNSUPPORTED, "a probe row matches more than 4 194 303 build rows");
-  return HY_OK;
+  if (pk_path) return probe_pkfk(q, b, clock, retry, stream);
+  return probe_general(q, b, rank_path && probe_views, clock, stream);
 }
 
 // JoinHash materialises its inputs (join_hash_steps.hpp:274-330): a reference input -- the output of a scan or of an earlier join, 8 bytes of
@@ -4480,29 +4691,21 @@ hy_status hy_join_hash_finish(const hy_column* left, const hy_column* right, uin
   HY_HIP(hipMemcpyAsync(host, result->status, sizeof(hy_join_status), hipMemcpyDeviceToHost, stream));
   HY_HIP(hipStreamSynchronize(stream));
   const hy_join_status seen = *static_cast<const hy_join_status*>(host);
-  if (!seen.build_confirmed) {   // the build column contradicted its key hint: nothing was written -- drop the hint, run the join again (two-pass build)
-    HY_TRY(plain_column(left, &left));
-    HY_TRY(plain_column(right, &right));
-    const bool build_right = mode == HY_JOIN_LEFT || mode == HY_JOIN_ANTI_NULL_AS_TRUE || mode == HY_JOIN_ANTI_NULL_AS_FALSE || mode == HY_JOIN_SEMI ||
-                             (mode == HY_JOIN_INNER && left->rows > right->rows);   // (side selection of run_join_once)
-    (build_right ? right : left)->join_hint.state.store(2, std::memory_order_release);
-    const uint32_t flags = result->flags;
-    result->flags = flags & ~HY_JOIN_ASYNC;   // (radix_bits: the first attempt left the value it used)
-    const hy_status status = run_join(left, right, mode, result, false, nullptr);
-    result->flags = flags;
-    t_last_join_hinted = 2;
-    if (status == HY_OK || status == HY_ERR_CAPACITY) {
-      hipLaunchKernelGGL(publish_join_status, dim3(1), dim3(1), 0, stream, result->status, result->n_pairs, result->n_slices, status == HY_OK ? 1u : 0u);
-      HY_HIP(hipStreamSynchronize(stream));
-    }
-    return status;
+  if (seen.build_confirmed) return report_join_result(result, seen.n_pairs, seen.n_slices, seen.error);
+  // the build column contradicted its key hint: nothing was written -- drop the hint, run the join again (two-pass build)
+  HY_TRY(plain_column(left, &left));
+  HY_TRY(plain_column(right, &right));
+  (builds_over_right_input(left, right, mode) ? right : left)->join_hint.state.store(2, std::memory_order_release);
+  const uint32_t flags = result->flags;
+  result->flags = flags & ~HY_JOIN_ASYNC;   // (radix_bits: the first attempt left the value it used)
+  const hy_status status = run_join(left, right, mode, result, false, nullptr);
+  result->flags = flags;
+  t_last_join_hinted = 2;
+  if (status == HY_OK || status == HY_ERR_CAPACITY) {
+    hipLaunchKernelGGL(publish_join_status, dim3(1), dim3(1), 0, stream, result->status, result->n_pairs, result->n_slices, status == HY_OK ? 1u : 0u);
+    HY_HIP(hipStreamSynchronize(stream));
   }
-  result->n_pairs = seen.n_pairs;
-  result->n_slices = seen.n_slices;
-  if (seen.error) return fail(HY_ERR_UNSUPPORTED, "a probe row matches more than 4 194 303 build rows");
-  if (seen.n_slices > result->slice_capacity) return fail(HY_ERR_CAPACITY, "join produces %u output PosLists, slice capacity is %u", seen.n_slices, result->slice_capacity);
-  if (seen.n_pairs > result->capacity) return fail(HY_ERR_CAPACITY, "join produces %llu pairs, capacity is %llu", static_cast<unsigned long long>(seen.n_pairs), static_cast<unsigned long long>(result->capacity));
-  return HY_OK;
+  return status;
 }
 
 hy_status hy_join_hash_predicates(const hy_column* left, const hy_column* right, uint32_t mode, const hy_join_predicate* secondary, uint32_t n_secondary,
@@ -4540,7 +4743,6 @@ hy_status hy_join_hash_radix_bits(uint64_t build_rows, uint64_t probe_rows, uint
   return HY_OK;
 }
 
-// debug / tests only: 0 = the last join of this thread probed the sorted directory, 1 = a rank table, 2 = a rank table whose ranks are row numbers
 // debug only: 1 if rt_probe_emit ranks with lane-ordered LDS atomics on this device, 2 if the probe said no, 0 before the first join
 int hy_debug_join_lane_ordered_atomics() { return g_lds_atomic_order.load(); }
 
@@ -4548,6 +4750,7 @@ int hy_debug_join_lane_ordered_atomics() { return g_lds_atomic_order.load(); }
 // HY_OPT_LDS_ORDERED_ATOMICS = 0), 0 if no operator has asked yet
 int hy_debug_lds_order_in_effect(void) { return g_lds_order_in_effect.load(); }
 
+// debug / tests only: 0 = the last join of this thread probed the sorted directory, 1 = a rank table, 2 = a rank table whose ranks are row numbers
 int hy_debug_join_used_rank_table(void) { return t_last_join_used_rank_table; }
 
 // debug / tests only: see t_last_join_hinted
