@@ -27,7 +27,7 @@ constexpr int64_t FIXED_JOIN_IDENTITY = 1;          // a sorted build column of 
 constexpr int64_t FIXED_JOIN_FETCH_AHEAD = 1;       // probe segments are read through SliceViews (wide loads)
 constexpr int64_t FIXED_JOIN_WGS_PER_CU = 0;        // persistent probe kernels: what the occupancy query says
 constexpr int64_t FIXED_JOIN_EMIT_TILE_GROUP = 64;  // pk_emit: consecutive tiles per XCD (one front of 8 x 64 tiles moves through the probe side)
-constexpr int64_t FIXED_JOIN_CLEAN_TABLES = 1;      // a hinted build's table and filter come zeroed: the join before cleared them
+constexpr int64_t FIXED_JOIN_CLEAN_TABLES = 1;      // a hinted wave fill's filter comes zeroed: the join before cleared it (the table needs no zeroing)
 constexpr int64_t FIXED_SCAN_JOB_CACHE = 1;         // a data column remembers the per-chunk jobs of its last four literal predicates
 constexpr int64_t FIXED_AGG_PARTITIONS = 1;         // many groups take the hash-partitioned path
 constexpr int64_t FIXED_AGG_LDS_BUDGET = 32768;     // bytes of LDS a partition table may take

@@ -2468,17 +2468,13 @@ struct BuildVerdict {
   uint32_t unsorted_signed, equal_neighbours, outside_hint, done;
 };
 
-// The rank table and the filter of a hinted build must start out as zeros (whole words are stored, the words two waves share and the
-// filter's words are OR-ed with atomics): zero_vectors in front of every fill was a launch of 6 us.  A thread keeps TWO blocks instead
-// and hands them out alternately, zeroed: the LAST kernel of join n (pk_emit, bound by its 0.96 GB of stores: 4 MB more do not show; in the
-// fill kernel's prologue they cost what zero_vectors did) clears -- one 16-byte store per thread of its first workgroups -- the block join
-// n - 1 used, which nothing reads any more when join n's kernels run (same stream).  A block is `clean` from the moment such
-// a launch is queued; `dirty_*` = what its last user may have written (table words, arrival counters, verdict; the filter's 128 KB).
+// The filter of a hinted wave fill must start out as zeros (its words are OR-ed with atomics; the rank table needs no such thing: every
+// word of it is stored, rank_table_fill_waves): zero_vectors in front of every fill was a launch of 6 us.  A thread keeps TWO filters
+// instead and hands them out alternately, zeroed: the LAST kernel of join n (pk_emit; in the fill kernel's prologue the stores cost what
+// zero_vectors did) clears -- one 16-byte store per thread of its first workgroups -- the filter join n - 1 used, which nothing reads any
+// more when join n's kernels run (same stream).  A filter is `clean` from the moment such a launch is queued.
 struct ZeroedBlocks {
-  void* table = nullptr;
-  size_t table_capacity = 0;
   void* filter = nullptr;   // BLOOM_BITS / 8 bytes
-  size_t dirty_table = 0, dirty_filter = 0;
   bool clean = false;
   hipStream_t stream = nullptr;
 };
@@ -2486,7 +2482,6 @@ static thread_local ZeroedBlocks t_zeroed[2];
 
 static void free_zeroed_blocks() {
   for (ZeroedBlocks& z : t_zeroed) {
-    if (z.table) (void)hipFree(z.table);
     if (z.filter) (void)hipFree(z.filter);
     z = ZeroedBlocks{};
   }
@@ -2784,20 +2779,31 @@ __global__ __launch_bounds__(256, 5) void rank_table_fill_checked(MaterializeArg
 // The same pass, wave by wave: rank_table_fill_checked spends ~130 vector instructions per key (runs of keys per table word found
 // with per-key branches, five workgroup barriers per slice) and is bound by exactly that -- its time falls with the number of resident
 // workgroups, not with the loads' latency (tools/join_bench.py: 1 / 2 / 3 persistent workgroups per CU 102 / 60 / 47 us).  Here a wave
-// owns a run of consecutive 512-row steps (eight consecutive rows per lane: one or two 16-byte loads, requested a step ahead) and builds
-// a step's table words in a window of LDS that belongs to it alone: a key is ONE ds_or (its bit) and ONE ds_min (its rank: the smallest
-// rank of a word is its base) -- no run detection, no workgroup barrier, uniform control flow.  The window is [word of the step's first
-// key, word of its last key]: sorted keys stay inside, and a step whose keys are not sorted (or span more than FW_WINDOW words: a very
-// sparse stretch) takes one global atomic per key instead.  A step's first and last word may be shared with the neighbouring steps: their
-// bits leave with a global atomicOr, and the base is written by the step that holds the word's first key.  The checks of
-// rank_table_fill_checked (order, equal neighbours, extent, keys outside the hint) run on the same registers; a workgroup hands in one
-// record.  Columns whose segments all have stored words of WIDTH bytes (hy_column::stream_width); partials: [gridDim.x][4].
+// takes a run of consecutive 512-row steps (eight consecutive rows per lane: one or two 16-byte loads, requested a batch ahead) and builds
+// a batch's table words in a window of LDS that belongs to it alone: a key is ONE ds_or (its bit), a word's base -- the rank of its first
+// key -- a running sum of population counts; no run detection, no workgroup barrier, uniform control flow.
+// Every table word is written once, by the wave that OWNS it, with plain stores -- no atomic touches the table, and nothing of it has to
+// be zero beforehand.  With word(k) = (k - origin) >> 5, a wave owns the words from the first one that starts in its rows (the word of a
+// key whose predecessor, key_in_front_of_step, lies in another word) through the word of its last key, and the empty words behind that up
+// to, not including, the word of the next key in a later word; the wave with the column's first row owns the words from 0, the one with
+// its last row those up to range >> 5.  These spans tile the table.  To close its last word and find the next key a wave reads at most 32
+// rows behind its own (fill_close_span): in a column of ascending unique keys at most 31 further keys share a word.  A table of which only
+// the presence bits are read (existence-only joins: the keys may repeat) looks up to FW_MAX_AHEAD rows ahead instead.  Keys that contradict
+// the hint end the wave's stores (fill_process_batch), so that every store stays inside the table; what has been written is then wrong and
+// not used.  The checks of rank_table_fill_checked (order, equal neighbours, extent, keys outside the hint) run on the same registers; a
+// workgroup hands in one record.  Columns whose segments all have stored words of WIDTH bytes (hy_column::stream_width), at most
+// FW_SPARSE_WORDS_PER_KEY table words per key and a range below FW_RANGE_LIMIT (fill_hinted); partials: [gridDim.x][4].
 constexpr uint32_t FW_STEP = 512;                        // rows per step: eight consecutive rows per lane
 constexpr uint32_t FW_STEPS_PER_SLICE = SLICE_ROWS / FW_STEP;
-constexpr uint32_t FW_WINDOW = 2048;                     // table words a batch (or a step) may span to be built in LDS (8 KB per wave)
+constexpr uint32_t FW_WINDOW = 2048;                     // table words a wave builds in LDS at a time (8 KB per wave); a batch that spans more takes several pieces
 static_assert(HY_FOR_BLOCK_SIZE % FW_STEP == 0, "a step lies in one FrameOfReference block");
 
 constexpr uint32_t FW_BATCH = 4;                          // steps a wave builds in one window and requests at once, a batch ahead (2 x 8 loads of 16 bytes per lane in flight for 4-byte keys)
+constexpr uint64_t FW_SPARSE_WORDS_PER_KEY = 2;            // sparser tables than this take the per-slice fill (fill_hinted)
+// fill_process_batch takes a key relative to a piece of the window (FW_WINDOW words of 32 keys): a key in front of the piece must stay a
+// 32-bit distance no word of the piece has -- ranges that reach into the last FW_WINDOW * 32 values take the per-slice fill
+constexpr uint64_t FW_RANGE_LIMIT = (uint64_t{1} << 32) - uint64_t{FW_WINDOW} * 32;
+static_assert(FW_STEPS_PER_SLICE % FW_BATCH == 0 && FW_WINDOW % 2 == 0, "a batch lies in one slice; the window leaves in pairs of words");
 
 // What a wave carries from step to step (all of it uniform).
 struct FillWaveState {
@@ -2806,6 +2812,10 @@ struct FillWaveState {
   bool any_rows = false;
   int32_t carry = 0;           // the key in front of the next step ...
   bool has_carry = false;      // ... if there is one
+  // the wave's span of table words (see rank_table_fill_waves): everything it owns in front of `cursor` is stored
+  bool started = false;        // a table word has started in the wave's rows (or the wave holds the column's first row: its span starts at word 0)
+  uint32_t cursor = 0;         // started: the word of the last key so far, not stored yet; else the word behind the one of the key in front of the wave
+  uint32_t pending_bits = 0, pending_base = 0;   // what the batches so far know of word `cursor`: its keys, the rank of its first
 };
 
 template <uint32_t WIDTH>
@@ -2834,162 +2844,11 @@ __device__ __forceinline__ bool key_in_front_of_step(const MaterializeArgs& a, u
   return false;
 }
 
-// The window of a batch's table words goes out: presence bits, and for every word the rank of its first key.
-// A word's base is the rank of its first key: the batch's rows are consecutive and its keys ascend without repeats (anything else is
-// flagged and ends the use of this table; a table for existence-only joins, which may hold repeats, is never asked for a base),
-// so that rank is the batch's first rank plus the keys of the batch in the words before -- a running sum of population counts.
-__device__ __forceinline__ void fill_flush_window(const uint32_t* bits_window, uint32_t span, uint32_t first_word, uint32_t origin_word, uint32_t first_rank, bool first_is_leader, uint32_t lane,
-                                                  u32x2_entry_t* entries, uint32_t* bloom_words, uint32_t debug) {
-  uint32_t keys_before = 0;
-  for (uint32_t begin = 0; begin < span; begin += 64) {
-    const uint32_t i = begin + lane;
-    const uint32_t bits = i < span ? bits_window[i] : 0u;
-    const uint32_t count = __popc(bits);
-    uint32_t inclusive = count;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t other = __shfl_up(inclusive, d, 64);
-      if (lane >= static_cast<uint32_t>(d)) inclusive += other;
-    }
-    const uint32_t base = first_rank + keys_before + inclusive - count;
-    keys_before += __builtin_amdgcn_readlane(inclusive, 63);
-    if (i >= span) continue;
-    const uint32_t table_word = first_word + i;
-    if (bits && bloom_words) atomicOr(bloom_words + ((table_word + origin_word) & (BLOOM_BITS / 32 - 1)), bits);
-#ifdef HY_DEBUG_SWITCHES
-    if (debug & 2) { if (bits == 0xDEADBEEFu && base == 0x12345678u) entries[0] = u32x2_entry_t{bits, base}; continue; }
-#endif
-    if (i == 0 || i + 1 == span) {   // may be shared with a neighbouring batch: add the bits; the base comes from the batch with the word's first key
-      if (bits) atomicOr(reinterpret_cast<uint32_t*>(entries + table_word), bits);
-      if (bits && (i != 0 || first_is_leader)) reinterpret_cast<uint32_t*>(entries + table_word)[1] = base;
-    } else {
-      entries[table_word] = u32x2_entry_t{bits, bits ? base : 0u};
-    }
-  }
-}
-
-// K consecutive steps from registers (K = 1: one step; K = FW_BATCH: a wave's batch -- one window for all of them, a quarter of the LDS
-// round trips and of the shared edge words): step k has rows[k] rows (uniform; the steps with rows come first, a step with fewer than
-// FW_STEP rows is the last with rows) whose first has rank first_rank[k]; the lane's eight consecutive keys of step k are a[k] / b[k] +
-// bias[k].  Returns false -- nothing done -- if the keys of K > 1 steps do not fit one window (the caller then takes them step by step).
-template <uint32_t WIDTH, uint32_t K>
-__device__ __forceinline__ bool fill_process_steps(FillWaveState& w, const u32x4_t (&a)[K], const u32x4_t (&b)[K], const uint32_t (&bias)[K], const uint32_t (&rows)[K],
-                                                   const uint32_t (&first_rank)[K], uint32_t lane, uint32_t origin, uint32_t range, u32x2_entry_t* entries, uint32_t* bloom_words,
-                                                   uint32_t* bits_window, uint32_t debug) {
-  // (debug: timing experiments of a -DHY_DEBUG_SWITCHES build, results are wrong then -- 2 no table stores, 4 no LDS work, 8 keys are only looked at)
-  const uint32_t origin_word = origin >> 5;
-  if (rows[0] == 0) return true;
-  int32_t key[K][8];
-  uint32_t lane_rows[K];
-  int32_t first_key = 0, last_key = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < K; ++k) {
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j) key[k][j] = fill_step_key<WIDTH>(a[k], b[k], bias[k], j);
-    lane_rows[k] = lane * 8 < rows[k] ? (rows[k] - lane * 8 < 8 ? rows[k] - lane * 8 : 8) : 0;   // rows of this lane (8 unless the step is the last of its slice)
-    if (rows[k] != 0) {   // the step's last key (uniform): lane (rows - 1) / 8, element (rows - 1) % 8
-      const uint32_t last_lane = (rows[k] - 1) >> 3, last_j = (rows[k] - 1) & 7;
-      int32_t mine = key[k][0];
-#pragma unroll
-      for (uint32_t j = 1; j < 8; ++j) mine = last_j == j ? key[k][j] : mine;
-      last_key = __builtin_amdgcn_readlane(mine, last_lane);
-    }
-    if (k == 0) first_key = __builtin_amdgcn_readfirstlane(key[0][0]);
-  }
-  // the window of table words: [word of the first key, word of the last key]
-  const uint32_t first_rel = static_cast<uint32_t>(first_key) - origin, last_rel = static_cast<uint32_t>(last_key) - origin;
-  const uint32_t first_word = first_rel >> 5;
-  const bool windowed = first_rel <= range && last_rel <= range && last_rel >= first_rel && (last_rel >> 5) - first_word < FW_WINDOW;
-  if (K > 1 && !windowed) return false;
-  const uint32_t span = windowed ? (last_rel >> 5) - first_word + 1 : 0;
-  if (!w.any_rows) w.low = first_key;
-  w.high = last_key;
-  w.any_rows = true;
-  // order: every key against its predecessor (lane 0's first key of a step against the last key of the step before)
-  int32_t before[K];
-  bool first_has_before[K];
-  {
-    int32_t carry = w.carry;
-    bool has_carry = w.has_carry;
-#pragma unroll
-    for (uint32_t k = 0; k < K; ++k) {
-      before[k] = __shfl_up(key[k][7], 1, 64);
-      if (lane == 0) before[k] = carry;
-      first_has_before[k] = lane != 0 || has_carry;
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) {
-        const int32_t previous = j == 0 ? before[k] : key[k][j - 1];
-        const bool checked = j < lane_rows[k] && (j != 0 || first_has_before[k]);
-        w.unsorted |= __ballot(checked && key[k][j] < previous);
-        w.equal |= __ballot(checked && key[k][j] == previous);
-      }
-      if (rows[k] != 0) {   // (a full step's last key sits in lane 63; only the last step with rows may be shorter, and nothing follows it)
-        carry = __builtin_amdgcn_readlane(key[k][7], 63);
-        has_carry = true;
-      }
-    }
-  }
-  // does the batch hold the first key of its first word?  (else an earlier step writes that word's base)
-  const uint32_t carry_rel = static_cast<uint32_t>(w.carry) - origin;
-  const bool first_is_leader = !w.has_carry || carry_rel > range || (carry_rel >> 5) != first_word;
-  w.carry = last_key;
-  w.has_carry = true;
-  // keys outside the hinted range: sorted keys lie between the first and the last (and keys that are not sorted are flagged above)
-  if (first_rel > range || last_rel > range) w.outside = 1;
-#ifdef HY_DEBUG_SWITCHES
-  if (debug & 8) return true;
-#endif
-  if (windowed) {
-#ifdef HY_DEBUG_SWITCHES
-    if (debug & 4) return true;
-#endif
-    for (uint32_t i = lane; i < span; i += 64) bits_window[i] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (uint32_t k = 0; k < K; ++k) {
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) {
-        const uint32_t rel = static_cast<uint32_t>(key[k][j]) - origin;
-        const uint32_t at = (rel >> 5) - first_word;
-        // (at >= span: the keys are not sorted -- flagged above, the join will not use this table; at < span: the word lies inside the table)
-        if (j < lane_rows[k] && at < span) atomicOr(&bits_window[at], 1u << (rel & 31));
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    fill_flush_window(bits_window, span, first_word, origin_word, first_rank[0], first_is_leader, lane, entries, bloom_words, debug);
-    __builtin_amdgcn_wave_barrier();   // (the window is read before the next batch clears it)
-  } else {
-    // a step outside any window (K == 1): one global atomic per key; a key that starts a table word writes the word's base
-#pragma unroll
-    for (uint32_t k = 0; k < K; ++k) {
-      const uint32_t lane_rank = first_rank[k] + lane * 8;
-#pragma unroll
-      for (uint32_t j = 0; j < 8; ++j) {
-        const uint32_t rel = static_cast<uint32_t>(key[k][j]) - origin;
-        const int32_t previous = j == 0 ? before[k] : key[k][j - 1];
-        const bool has_previous = j != 0 || first_has_before[k];
-        w.outside |= __ballot(j < lane_rows[k] && rel > range);
-        if (j < lane_rows[k] && rel <= range) {
-          const uint32_t table_word = rel >> 5, bits = 1u << (rel & 31);
-          atomicOr(reinterpret_cast<uint32_t*>(entries + table_word), bits);
-          const uint32_t previous_rel = static_cast<uint32_t>(previous) - origin;
-          if (!has_previous || previous_rel > range || (previous_rel >> 5) != table_word) reinterpret_cast<uint32_t*>(entries + table_word)[1] = lane_rank + j;
-          if (bloom_words) atomicOr(bloom_words + ((table_word + origin_word) & (BLOOM_BITS / 32 - 1)), bits);
-        }
-      }
-    }
-  }
-  return true;
-}
-
 // What a wave requests at once: the stored words of FW_BATCH steps and what it needs to know about them.
 template <uint32_t WIDTH>
 struct FillBatch {
   u32x4_t a[FW_BATCH], b[FW_BATCH];
-  uint32_t bias[FW_BATCH], rows[FW_BATCH], first_rank[FW_BATCH];
+  uint32_t bias[FW_BATCH], rows[FW_BATCH], first_rank;   // first_rank: the rank of the batch's first row (its rows are consecutive rows of one slice)
 };
 
 template <uint32_t WIDTH>
@@ -3009,7 +2868,7 @@ __device__ __forceinline__ void load_fill_batch(const MaterializeArgs& a, uint32
     const SliceView& view = second ? view1 : view0;
     const uint32_t offset = (step % FW_STEPS_PER_SLICE) * FW_STEP;
     batch.rows[k] = step < end_step && view.row_count > offset ? (view.row_count - offset < FW_STEP ? view.row_count - offset : FW_STEP) : 0;
-    batch.first_rank[k] = (second ? rank1 : rank0) + offset;
+    if (k == 0) batch.first_rank = (second ? rank1 : rank0) + offset;
     batch.a[k] = u32x4_t{0, 0, 0, 0};
     batch.b[k] = u32x4_t{0, 0, 0, 0};
     batch.bias[k] = 0;
@@ -3031,16 +2890,265 @@ __device__ __forceinline__ void load_fill_batch(const MaterializeArgs& a, uint32
   }
 }
 
-struct FillCleaning {   // two regions this launch leaves zeroed (16-byte vectors): the blocks of the join before (ZeroedBlocks)
-  u32x4_t* first;
-  u32x4_t* second;
-  uint32_t first_vectors, second_vectors;
+// Table words [lo, hi) are empty: the wave's 64 lanes store them, 16 bytes each (8 at an odd end).
+__device__ __forceinline__ void fill_store_zeros(u32x2_entry_t* entries, uint32_t lo, uint32_t hi, uint32_t lane) {
+  if (lo >= hi) return;
+  if (lo & 1) {
+    if (lane == 0) entries[lo] = u32x2_entry_t{0, 0};
+    ++lo;
+  }
+  const uint32_t pairs = (hi - lo) >> 1;
+  u32x4_t* vectors = reinterpret_cast<u32x4_t*>(entries + lo);   // (the table is a 16-byte aligned block, lo is even)
+  for (uint32_t i = lane; i < pairs; i += 64) vectors[i] = u32x4_t{0, 0, 0, 0};
+  if (((hi - lo) & 1) && lane == 0) entries[hi - 1] = u32x2_entry_t{0, 0};
+}
+
+// One table word leaves on its own (lane 0): the word a wave's span ends with, or one that keys of several batches share.
+__device__ __forceinline__ void fill_store_word(u32x2_entry_t* entries, uint32_t* bloom_words, uint32_t table_word, uint32_t origin_word, uint32_t bits, uint32_t base, uint32_t lane) {
+  if (lane != 0) return;
+  entries[table_word] = u32x2_entry_t{bits, bits ? base : 0u};
+  if (bits && bloom_words) atomicOr(bloom_words + ((table_word + origin_word) & (BLOOM_BITS / 32 - 1)), bits);
+}
+
+// A piece of a batch's window goes out: window word i is table word piece + i (piece is even), two words per lane.  Stored are the
+// words in [lo, hi) up to which the batch has at least `need` keys (a wave that has not started owns nothing in front of the first key
+// behind the word of the key in front of it), as pairs of 16 bytes where both words of a pair are the wave's.  A word's base is the rank
+// of its first key: the batch's rows are consecutive and its keys ascend without repeats (anything else is flagged and ends the use of
+// this table), so that rank is the batch's first rank plus the keys of the batch in the words before -- a running sum of population
+// counts, *keys_before of it from the pieces before.  Word lo may hold keys of earlier batches (pending_bits, the first at pending_base).
+__device__ __forceinline__ void fill_flush_piece(const uint32_t* bits_window, uint32_t span, uint32_t piece, uint32_t lo, uint32_t hi, uint32_t need, uint32_t* keys_before, uint32_t first_rank,
+                                                 uint32_t pending_bits, uint32_t pending_base, uint32_t origin_word, uint32_t lane, u32x2_entry_t* entries, uint32_t* bloom_words, uint32_t debug) {
+#ifdef HY_DEBUG_SWITCHES
+  const bool wide = !(debug & 2);   // (a counting experiment: 8-byte stores only; the table is the same)
+#else
+  constexpr bool wide = true;
+#endif
+  for (uint32_t begin = 0; begin < span; begin += 128) {
+    const uint32_t i = begin + 2 * lane;
+    const u32x2_t own = i < span ? *reinterpret_cast<const u32x2_t*>(bits_window + i) : u32x2_t{0, 0};   // (the window is cleared up to an even count)
+    const uint32_t count0 = __popc(own.x), count = count0 + __popc(own.y);
+    uint32_t inclusive = count;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t other = __shfl_up(inclusive, d, 64);
+      if (lane >= static_cast<uint32_t>(d)) inclusive += other;
+    }
+    const uint32_t before = *keys_before + inclusive - count;   // keys of the batch in front of this lane's two words
+    *keys_before += __builtin_amdgcn_readlane(inclusive, 63);
+    const uint32_t word0 = piece + i, word1 = word0 + 1;
+    uint32_t bits0 = own.x, base0 = first_rank + before, bits1 = own.y, base1 = first_rank + before + count0;
+    if (pending_bits && word0 == lo) { bits0 |= pending_bits; base0 = pending_base; }
+    if (pending_bits && word1 == lo) { bits1 |= pending_bits; base1 = pending_base; }
+    const bool mine0 = word0 >= lo && word0 < hi && before + count0 >= need, mine1 = word1 >= lo && word1 < hi && before + count >= need;
+    if (wide && mine0 && mine1) *reinterpret_cast<u32x4_t*>(entries + word0) = u32x4_t{bits0, bits0 ? base0 : 0u, bits1, bits1 ? base1 : 0u};
+    else {
+      if (mine0) entries[word0] = u32x2_entry_t{bits0, bits0 ? base0 : 0u};
+      if (mine1) entries[word1] = u32x2_entry_t{bits1, bits1 ? base1 : 0u};
+    }
+    if (bloom_words) {
+      // The filter's atomics leave lane by lane over consecutive words, 64 at a time: the words come back from the lanes that hold them in
+      // pairs (an atomic per lane on its own two words would be two instructions over every other word: twice the lines touched).
+      const uint32_t fold0 = mine0 ? bits0 : 0u, fold1 = mine1 ? bits1 : 0u;
+#pragma unroll
+      for (uint32_t half = 0; half < 2; ++half) {
+        const uint32_t holder = half * 32 + (lane >> 1);
+        const uint32_t even = __shfl(fold0, holder, 64), odd = __shfl(fold1, holder, 64);
+        const uint32_t folded = lane & 1 ? odd : even;
+        if (folded) atomicOr(bloom_words + ((piece + begin + half * 64 + lane + origin_word) & (BLOOM_BITS / 32 - 1)), folded);
+      }
+    }
+  }
+}
+
+// A batch of FW_BATCH consecutive steps from registers: step k has rows[k] rows (uniform; the steps with rows come first, a step with
+// fewer than FW_STEP rows is the last with rows) the first of which has rank first_rank; the lane's eight consecutive keys of step k are
+// a[k] / b[k] + bias[k].  The batch stores the words of the wave's span from w.cursor up to, not including, the word of its last key --
+// that word stays pending: the next batch, or the rows behind the wave (fill_close_span), may hold more of its keys.  The words are built
+// in the wave's window of LDS, FW_WINDOW at a time: a batch whose keys lie further apart goes through several pieces, and a piece
+// without keys is stored as zeros without the window.  Once the wave has met keys that contradict the hint it stores nothing more: the
+// table will not be used, and only ascending keys inside the range keep every store inside it.
+template <uint32_t WIDTH>
+__device__ __forceinline__ void fill_process_batch(FillWaveState& w, const FillBatch<WIDTH>& batch, uint32_t lane, uint32_t origin, uint32_t range, u32x2_entry_t* entries,
+                                                   uint32_t* bloom_words, uint32_t* bits_window, uint32_t debug) {
+  // (debug: experiments of a -DHY_DEBUG_SWITCHES build -- 2 the window leaves in 8-byte stores only; results are wrong with 4 no LDS work and no stores, 8 keys are only looked at)
+  constexpr uint32_t K = FW_BATCH;
+  const uint32_t origin_word = origin >> 5;
+  const uint32_t (&rows)[K] = batch.rows;
+  if (rows[0] == 0) return;
+  int32_t key[K][8];
+  uint32_t lane_rows[K];
+  int32_t first_key = 0, last_key = 0;
+  uint32_t total = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) key[k][j] = fill_step_key<WIDTH>(batch.a[k], batch.b[k], batch.bias[k], j);
+    lane_rows[k] = lane * 8 < rows[k] ? (rows[k] - lane * 8 < 8 ? rows[k] - lane * 8 : 8) : 0;   // rows of this lane (8 unless the step is the last of its slice)
+    total += rows[k];
+    if (rows[k] != 0) {   // the step's last key (uniform): lane (rows - 1) / 8, element (rows - 1) % 8
+      const uint32_t last_lane = (rows[k] - 1) >> 3, last_j = (rows[k] - 1) & 7;
+      int32_t mine = key[k][0];
+#pragma unroll
+      for (uint32_t j = 1; j < 8; ++j) mine = last_j == j ? key[k][j] : mine;
+      last_key = __builtin_amdgcn_readlane(mine, last_lane);
+    }
+    if (k == 0) first_key = __builtin_amdgcn_readfirstlane(key[0][0]);
+  }
+  const uint32_t first_rel = static_cast<uint32_t>(first_key) - origin, last_rel = static_cast<uint32_t>(last_key) - origin;
+  if (!w.any_rows) w.low = first_key;
+  w.high = last_key;
+  w.any_rows = true;
+  // order: every key against its predecessor (lane 0's first key of a step against the last key of the step before)
+  {
+    int32_t carry = w.carry;
+    bool has_carry = w.has_carry;
+#pragma unroll
+    for (uint32_t k = 0; k < K; ++k) {
+      int32_t before = __shfl_up(key[k][7], 1, 64);
+      if (lane == 0) before = carry;
+      const bool first_has_before = lane != 0 || has_carry;
+#pragma unroll
+      for (uint32_t j = 0; j < 8; ++j) {
+        const int32_t previous = j == 0 ? before : key[k][j - 1];
+        const bool checked = j < lane_rows[k] && (j != 0 || first_has_before);
+        w.unsorted |= __ballot(checked && key[k][j] < previous);
+        w.equal |= __ballot(checked && key[k][j] == previous);
+      }
+      if (rows[k] != 0) {   // (a full step's last key sits in lane 63; only the last step with rows may be shorter, and nothing follows it)
+        carry = __builtin_amdgcn_readlane(key[k][7], 63);
+        has_carry = true;
+      }
+    }
+  }
+  w.carry = last_key;
+  w.has_carry = true;
+  // keys outside the hinted range: sorted keys lie between the first and the last (and keys that are not sorted are flagged above)
+  if (first_rel > range || last_rel > range) w.outside = 1;
+  if (w.unsorted | w.outside) return;
+#ifdef HY_DEBUG_SWITCHES
+  if (debug & 12) return;
+#endif
+  // From here on: key in front <= first key <= ... <= last key, all inside the range -- no key's word lies in front of the wave's cursor
+  // (not started: in front of the word before it, the one of the key in front), none behind last_word <= range >> 5.
+  const uint32_t first_word = first_rel >> 5, last_word = last_rel >> 5;
+  if (w.started && w.pending_bits && first_word > w.cursor) {   // nothing more comes for the pending word
+    fill_store_word(entries, bloom_words, w.cursor, origin_word, w.pending_bits, w.pending_base, lane);
+    w.pending_bits = 0;
+    ++w.cursor;
+  }
+  const uint32_t front_word = w.cursor - 1;   // (not started)
+  uint32_t keys_before = 0, need = w.started ? 0u : 1u;
+  uint32_t piece = (w.started ? w.cursor : front_word) & ~1u;
+  for (bool first_piece = true;; first_piece = false, piece += FW_WINDOW) {
+    const uint32_t span = last_word - piece < FW_WINDOW ? last_word - piece + 1 : FW_WINDOW;   // the piece's words up to the batch's last
+    // may the piece hold a key?  A lane's eight keys of a step ascend: its first and its last say so (a lane with fewer rows: its first;
+    // a piece taken for one with keys and without any is stored as the zeros it holds all the same)
+    const uint32_t piece_key = origin + (piece << 5);   // the key of the piece's first bit: keys are taken relative to it (in front of the piece: huge)
+    bool holds = false;
+#pragma unroll
+    for (uint32_t k = 0; k < K; ++k) {
+      const uint32_t lowest = (static_cast<uint32_t>(key[k][0]) - origin) >> 5, highest = (static_cast<uint32_t>(key[k][7]) - origin) >> 5;
+      holds = holds || (lane_rows[k] != 0 && lowest < piece + span && (lane_rows[k] < 8 || highest >= piece));
+    }
+    if (__ballot(holds)) {
+      for (uint32_t i = lane; i < ((span + 1) & ~1u); i += 64) bits_window[i] = 0;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (uint32_t k = 0; k < K; ++k) {
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) {
+          const uint32_t rel = static_cast<uint32_t>(key[k][j]) - piece_key;   // (origin and piece_key are multiples of 32: the key's bit in its word is rel & 31)
+          const uint32_t at = rel >> 5;
+          if (j < lane_rows[k] && at < span) atomicOr(&bits_window[at], 1u << (rel & 31));
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      // not started: the batch's keys in the word of the key in front belong to the wave that owns that word
+      if (!w.started && first_piece) need = __popc(bits_window[front_word - piece]) + 1;
+      fill_flush_piece(bits_window, span, piece, w.cursor, last_word, need, &keys_before, batch.first_rank, w.pending_bits, w.pending_base, origin_word, lane, entries, bloom_words, debug);
+      if (last_word - piece < FW_WINDOW) break;   // (the window keeps the last word's bits for below)
+      __builtin_amdgcn_wave_barrier();             // (the window is read before the next piece clears it)
+    } else if (keys_before >= need) {
+      fill_store_zeros(entries, piece > w.cursor ? piece : w.cursor, piece + span, lane);   // (the batch's last word is not here: it holds a key)
+    }
+  }
+  // the word of the last key: pending, together with what earlier batches knew of it
+  const uint32_t last_bits = __builtin_amdgcn_readfirstlane(bits_window[last_word - piece]);
+  __builtin_amdgcn_wave_barrier();   // (the window is read before the next batch clears it)
+  if (!w.started && last_word == front_word) return;   // all of the batch in the word of the key in front: still not started
+  if (!(w.pending_bits && last_word == w.cursor)) {
+    w.pending_bits = 0;
+    w.pending_base = batch.first_rank + total - __popc(last_bits);
+  }
+  w.pending_bits |= last_bits;
+  w.started = true;
+  w.cursor = last_word;
+}
+
+// The end of a wave's span.  The word of its last key may hold keys of the rows behind the wave -- at most 31 in a column of ascending
+// unique keys -- and the empty words behind it, up to the next key's, are the wave's too: it looks at the rows that follow its own,
+// wherever they lie (the next step, slice or chunk), 64 at a time and max_ahead at the most -- 32 for a hint of unique keys; a table of
+// which only the presence bits are read (existence-only joins) may hold a key in any number of rows: FW_MAX_AHEAD.  No row follows: the
+// span ends with the table.  max_ahead rows without a key in a later word: the span ends with the pending word, and the wave reports keys
+// that do not fit the hint (flag 4) -- for unique keys the waves that own those rows do so anyway; repeats beyond FW_MAX_AHEAD rows per
+// table word make the join run without the hint.
+constexpr uint32_t FW_MAX_AHEAD = 4096;   // rows a wave of an existence-only table looks behind its own for the end of its last word
+__device__ __forceinline__ void fill_close_span(const MaterializeArgs& a, FillWaveState& w, uint32_t end_step, uint32_t max_ahead, uint32_t lane, uint32_t origin, uint32_t range,
+                                                u32x2_entry_t* entries, uint32_t* bloom_words) {
+  if (!w.any_rows || !w.started || (w.unsorted | w.outside)) return;
+  const uint32_t table_end = (range >> 5) + 1;
+  uint32_t slice = end_step / FW_STEPS_PER_SLICE, offset = (end_step % FW_STEPS_PER_SLICE) * FW_STEP;
+  uint32_t bits = 0, next = w.cursor + 1;
+  bool closed = false;
+  for (uint32_t seen = 0; !closed && seen < max_ahead;) {
+    const uint32_t want = max_ahead - seen < 64 ? max_ahead - seen : 64;
+    int32_t key = 0;
+    bool have = false;
+    uint32_t got = 0;
+    while (got < want && slice < a.n_slices) {
+      const SliceView view = a.views[slice];
+      const uint32_t rows = view.row_count > offset ? view.row_count - offset : 0, take = rows < want - got ? rows : want - got;
+      if (lane >= got && lane < got + take) {
+        key = view_key(view, view.row_begin + offset + (lane - got));
+        have = true;
+      }
+      got += take;
+      offset += take;
+      if (offset >= view.row_count) { ++slice; offset = 0; }
+    }
+    const uint32_t rel = static_cast<uint32_t>(key) - origin, table_word = rel >> 5;
+    const bool inside = have && rel <= range;
+    bits |= inside && table_word == w.cursor ? 1u << (rel & 31) : 0u;
+    const uint64_t later = __ballot(inside && table_word > w.cursor);
+    if (later) {
+      next = __shfl(table_word, __ffsll(static_cast<long long>(later)) - 1, 64);
+      closed = true;
+    } else if (got < want) {   // the column ends here
+      next = table_end;
+      closed = true;
+    }
+    seen += got;
+  }
+  if (!closed) w.outside = 1;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) bits |= __shfl_xor(bits, d, 64);
+  next = next < table_end ? next : table_end;
+  fill_store_word(entries, bloom_words, w.cursor, origin >> 5, w.pending_bits | bits, w.pending_base, lane);
+  fill_store_zeros(entries, w.cursor + 1, next, lane);
+}
+
+struct FillCleaning {   // the region this launch leaves zeroed (16-byte vectors): the filter of the join before (ZeroedBlocks)
+  u32x4_t* filter;
+  uint32_t vectors;
 };
 
 template <uint32_t WIDTH>
 __global__ __launch_bounds__(256, 4) void rank_table_fill_waves(MaterializeArgs a, uint64_t key_min, uint64_t hint_range, u32x2_entry_t* entries, uint64_t* partials, uint32_t chunk_rows,
-                                                             uint32_t batches_per_wave, uint32_t n_steps, uint32_t debug) {
-  __shared__ uint32_t s_window[4][FW_WINDOW];   // per wave: the presence bits of the batch's table words
+                                                             uint32_t batches_per_wave, uint32_t n_steps, uint32_t max_ahead, uint32_t debug) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_window[4][FW_WINDOW];   // per wave: the presence bits of the batch's table words
   __shared__ uint64_t s_min[4], s_max[4];
   __shared__ uint32_t s_flags;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -3061,25 +3169,19 @@ __global__ __launch_bounds__(256, 4) void rank_table_fill_waves(MaterializeArgs 
     if (lane == 0) has_front = key_in_front_of_step(a, first_step, &front) ? 1u : 0u;
     w.carry = __builtin_amdgcn_readfirstlane(front);
     w.has_carry = __builtin_amdgcn_readfirstlane(has_front) != 0;
+    // where the wave's span starts: at word 0 for the wave with the column's first row, else at the first word that starts in its rows --
+    // one behind the word of the key in front at the earliest (a key in front outside the range: nothing is stored, the table is not used)
+    const uint32_t front_rel = static_cast<uint32_t>(w.carry) - origin;
+    w.started = !w.has_carry;
+    if (w.has_carry && front_rel > range) w.outside = 1;
+    w.cursor = w.has_carry ? (front_rel >> 5) + 1 : 0;
   }
   for (uint32_t batch_step = first_step; batch_step < end_step; batch_step += FW_BATCH) {
     if (batch_step + FW_BATCH < end_step) load_fill_batch<WIDTH>(a, batch_step + FW_BATCH, end_step, chunk_rows, lane, ahead);   // (in flight while this batch is built)
-    // steps with rows come first inside a slice; a batch that straddles two slices (never, as FW_BATCH divides a slice's steps) or whose
-    // keys do not fit one window goes step by step
-    bool packed = true;
-#pragma unroll
-    for (uint32_t k = 1; k < FW_BATCH; ++k) packed = packed && (current.rows[k] == 0 || current.rows[k - 1] == FW_STEP);
-    if (!packed || !fill_process_steps<WIDTH, FW_BATCH>(w, current.a, current.b, current.bias, current.rows, current.first_rank, lane, origin, range, entries, bloom_words, bits_window,
-                                                        debug)) {
-#pragma unroll
-      for (uint32_t k = 0; k < FW_BATCH; ++k) {
-        const u32x4_t one_a[1] = {current.a[k]}, one_b[1] = {current.b[k]};
-        const uint32_t one_bias[1] = {current.bias[k]}, one_rows[1] = {current.rows[k]}, one_rank[1] = {current.first_rank[k]};
-        fill_process_steps<WIDTH, 1>(w, one_a, one_b, one_bias, one_rows, one_rank, lane, origin, range, entries, bloom_words, bits_window, debug);
-      }
-    }
+    fill_process_batch<WIDTH>(w, current, lane, origin, range, entries, bloom_words, bits_window, debug);   // (a batch lies in one slice: its steps with rows come first)
     current = ahead;
   }
+  fill_close_span(a, w, end_step, max_ahead, lane, origin, range, entries, bloom_words);
   const uint64_t unsorted = w.unsorted, equal = w.equal, outside = w.outside;
   const int32_t low = w.low, high = w.high;
   const bool any_rows = w.any_rows;
@@ -3250,7 +3352,7 @@ static bool lds_atomics_are_lane_ordered(hipStream_t stream);
 
 struct BuildSide {
   DeviceBuffer keys, rows, keys_tmp, rows_tmp, dir, bloom, flags, rank_entries, partials;
-  FillCleaning cleaning{nullptr, nullptr, 0, 0};   // the thread's other zeroed block (ZeroedBlocks), for the join's last kernel to clear ...
+  FillCleaning cleaning{nullptr, 0};               // the thread's other zeroed filter (ZeroedBlocks), for the join's last kernel to clear ...
   ZeroedBlocks* cleaned = nullptr;                 // ... and to mark clean when that kernel is queued
   bool hint_allows_duplicates = false;
   bool bloom_is_bits = false;    // the filter is 2^20 BITS (rank_table_fill_checked folds the table's presence words into it), not one byte per bit
@@ -3397,55 +3499,42 @@ static void identity_table(BuildJob& job, u32x2_t* entries, uint64_t key_min, ui
   d.n_buckets = 1;
 }
 
-// The table and the filter of a hinted wave fill: one of the thread's two zeroed blocks (ZeroedBlocks), whose partner this join's pk_emit
-// clears.  All transitions of t_zeroed happen here and in block_cleaning_queued.  *taken = false: the blocks do not apply (a table of 2^31
-// vectors) -- the caller zeroes a block of its own.
-static hy_status take_zeroed_block(BuildJob& job, size_t table_vectors, size_t bloom_vectors, bool* taken) {
+// The filter of a hinted wave fill: one of the thread's two zeroed filters (ZeroedBlocks), whose partner this join's pk_emit clears.  All
+// transitions of t_zeroed happen here and in block_cleaning_queued.  *taken = false: the filters are switched off -- the caller zeroes
+// the build side's own.
+static hy_status take_zeroed_block(BuildJob& job, bool* taken) {
   BuildSide& b = job.b;
   hipStream_t stream = job.stream;
+  constexpr size_t filter_vectors = BLOOM_BITS / 8 / 16;
   *taken = false;
-  if (!FIXED_JOIN_CLEAN_TABLES || table_vectors + bloom_vectors >= (1ull << 31)) return HY_OK;
-  if ((t_zeroed[0].table && t_zeroed[0].stream != stream) || (t_zeroed[1].table && t_zeroed[1].stream != stream)) {   // another stream: start over
+  if (!FIXED_JOIN_CLEAN_TABLES) return HY_OK;
+  if ((t_zeroed[0].filter && t_zeroed[0].stream != stream) || (t_zeroed[1].filter && t_zeroed[1].stream != stream)) {   // another stream: start over
     HY_HIP(hipDeviceSynchronize());
     free_zeroed_blocks();
   }
-  int mine = -1;
-  for (int i = 0; i < 2; ++i) if (t_zeroed[i].clean && t_zeroed[i].table_capacity >= 16 * table_vectors) mine = i;
-  if (mine < 0) {   // a block that is not waiting to be cleaned by this launch: (re)allocate it, zeroed by zero_vectors below
-    mine = !t_zeroed[0].table ? 0 : !t_zeroed[1].table ? 1 : t_zeroed[1].clean && !t_zeroed[0].clean ? 1 : 0;   // (both in use and neither cleared -- the join before took other kernels: block 0, cleared by a launch)
+  int mine = t_zeroed[0].clean ? 0 : t_zeroed[1].clean ? 1 : -1;
+  if (mine < 0) {   // no filter that a pk_emit has cleared: a new one, or (both in use -- the join before took other kernels) filter 0, zeroed by a launch
+    mine = !t_zeroed[0].filter ? 0 : !t_zeroed[1].filter ? 1 : 0;
     ZeroedBlocks& z = t_zeroed[mine];
-    if (z.table_capacity < 16 * table_vectors) {
-      if (z.table) { HY_HIP(hipStreamSynchronize(stream)); HY_HIP(hipFree(z.table)); z.table = nullptr; }
-      z.table_capacity = (16 * table_vectors * 5 / 4 + 4095) & ~size_t{4095};
-      HY_HIP(hipMalloc(&z.table, z.table_capacity));
-      if (!z.filter) HY_HIP(hipMalloc(&z.filter, BLOOM_BITS / 8));
-      z.stream = stream;
-      z.clean = false;
-      z.dirty_table = z.table_capacity;   // (never written: all of it is cleared once)
-      z.dirty_filter = BLOOM_BITS / 8;
-    }
+    if (!z.filter) HY_HIP(hipMalloc(&z.filter, 16 * filter_vectors));
+    z.stream = stream;
+    hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>((filter_vectors + 255) / 256)), dim3(256), 0, stream, static_cast<u32x4_t*>(z.filter), filter_vectors, static_cast<u32x4_t*>(nullptr), size_t{0});
   }
   ZeroedBlocks& z = t_zeroed[mine];
   ZeroedBlocks& other = t_zeroed[1 - mine];
-  if (!z.clean) {
-    hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>(std::min<size_t>(2048, (z.dirty_table / 16 + z.dirty_filter / 16 + 255) / 256))), dim3(256), 0, stream,
-                       static_cast<u32x4_t*>(z.table), z.dirty_table / 16, static_cast<u32x4_t*>(z.filter), z.dirty_filter / 16);
-  }
-  if (other.table && !other.clean) {   // this join's pk_emit clears what the join before left in the other block
-    b.cleaning = FillCleaning{static_cast<u32x4_t*>(other.table), static_cast<u32x4_t*>(other.filter), static_cast<uint32_t>(other.dirty_table / 16), static_cast<uint32_t>(other.dirty_filter / 16)};
+  if (other.filter && !other.clean) {   // this join's pk_emit clears what the join before left in the other filter
+    b.cleaning = FillCleaning{static_cast<u32x4_t*>(other.filter), static_cast<uint32_t>(filter_vectors)};
     b.cleaned = &other;   // (clean once pk_emit is queued: block_cleaning_queued)
   }
   z.clean = false;
-  z.dirty_table = 16 * table_vectors;
-  z.dirty_filter = 16 * bloom_vectors;
-  b.rank_entries.borrow(z.table);
-  if (job.wants.bloom) { b.bloom.borrow(z.filter); job.m.bloom_out = b.bloom.as<uint8_t>(); }
+  b.bloom.borrow(z.filter);
+  job.m.bloom_out = b.bloom.as<uint8_t>();
   *taken = true;
   return HY_OK;
 }
 
 static void block_cleaning_queued(BuildSide& b) {   // the join's last kernel, which clears b.cleaning, is in the stream
-  if (b.cleaned) { b.cleaned->clean = true; b.cleaned->dirty_table = b.cleaned->dirty_filter = 0; }
+  if (b.cleaned) b.cleaned->clean = true;
 }
 
 // rank_table_fill_waves<W> over a column whose segments are aligned W-byte vectors -- as many waves as stay resident (at most the option's
@@ -3456,7 +3545,7 @@ static hy_status launch_hinted_fill(BuildJob& job, uint32_t stream_width, uint64
   MaterializeArgs m = job.m;
   const uint32_t n_slices = job.column->n_slices;
   uint32_t fill_debug = 0;
-  if (const char* debug = HY_DEBUG_ENV("HY_JOIN_FILL_DEBUG")) {   // timing experiments only (results are wrong): 1 no filter, 2 no table either (wave kernel: 4 no LDS work, 8 loads and checks only)
+  if (const char* debug = HY_DEBUG_ENV("HY_JOIN_FILL_DEBUG")) {   // timing experiments only (results are wrong): 1 no filter; rank_table_fill_checked: 2 loads and extent only; wave kernel: 2 8-byte table stores only (results stay right), 4 or 8 keys are only looked at
     fill_debug = static_cast<uint32_t>(atoi(debug));
     if (fill_debug & 1) m.bloom_out = nullptr;
     if (atoi(debug) >= 2 && !option(HY_OPT_JOIN_FILL_WGS_PER_CU)) m.keep_nulls = 0xFFFFFFFFu;   // (rank_table_fill_checked: loads and extent only)
@@ -3481,7 +3570,7 @@ static hy_status launch_hinted_fill(BuildJob& job, uint32_t stream_width, uint64
   b.n_fill_records = groups;
   with_width([&](auto w) {
     hipExtLaunchKernelGGL(rank_table_fill_waves<decltype(w)::value>, dim3(groups), dim3(256), 0, job.stream, fill_started, fill_stopped, 0, m, origin, hint_range, entries, b.partials.as<uint64_t>(),
-                          job.column->host_segments[0].size, batches_per_wave, n_steps, fill_debug);
+                          job.column->host_segments[0].size, batches_per_wave, n_steps, job.wants.existence_only ? FW_MAX_AHEAD : 32u, fill_debug);
     return HY_OK;
   });
   return HY_OK;
@@ -3502,15 +3591,20 @@ static hy_status fill_hinted(BuildJob& job) {
   const size_t table_vectors = (table_bytes + 15) / 16, bloom_vectors = job.wants.bloom ? BLOOM_BITS / 8 / 16 : 0;   // (the filter as bits: 128 KB)
   uint32_t stream_width = build->stream_width == 1 || build->stream_width == 2 || build->stream_width == 4 ? build->stream_width : 0;
   if (option(HY_OPT_JOIN_FILL_WGS_PER_CU) <= 0) stream_width = 0;   // (the per-slice fill)
+  // A table of more than FW_SPARSE_WORDS_PER_KEY words per key (a filtered dimension: 1 000 keys in 31 250 words): the few waves with rows
+  // would store all of it, window piece by window piece -- the per-slice fill sets a bit per key in a table zero_vectors cleared with the
+  // whole device.  (job.total: the column's rows -- a hinted column is dense.)
+  if (words > FW_SPARSE_WORDS_PER_KEY * job.total) stream_width = 0;
+  if (key_max - origin >= FW_RANGE_LIMIT) stream_width = 0;
   HY_TRY(b.partials.alloc(32 * (size_t{build->n_slices} * FW_STEPS_PER_SLICE / 4 + 1)));   // one record per workgroup: per slice (rank_table_fill_checked), or per four waves of >= 1 step (rank_table_fill_waves)
-  // zeroed: by the join before (the wave fill's blocks) -- or, where that does not apply (the first joins of a thread, a table that outgrew
-  // its block, the per-slice fill kernel), by a launch of its own
+  HY_TRY(b.rank_entries.alloc(table_bytes));
+  // The wave fill stores every word of its table and wants only a zeroed filter: cleared by the join before (ZeroedBlocks) -- or, where that
+  // does not apply (the first joins of a thread), by a launch.  The per-slice fill wants table, counters and filter zeroed: a launch.
   bool zeroed = false;
-  if (stream_width) HY_TRY(take_zeroed_block(job, table_vectors, bloom_vectors, &zeroed));
-  if (!zeroed) {
-    HY_TRY(b.rank_entries.alloc(table_bytes));
-    hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>(std::min<size_t>(2048, (table_vectors + bloom_vectors + 255) / 256))), dim3(256), 0, job.stream,
-                       b.rank_entries.as<u32x4_t>(), table_vectors, b.bloom.as<u32x4_t>(), bloom_vectors);
+  if (stream_width && job.wants.bloom) HY_TRY(take_zeroed_block(job, &zeroed));
+  if (!stream_width || (job.wants.bloom && !zeroed)) {
+    hipLaunchKernelGGL(zero_vectors, dim3(static_cast<uint32_t>(std::min<size_t>(2048, ((stream_width ? 0 : table_vectors) + bloom_vectors + 255) / 256))), dim3(256), 0, job.stream,
+                       b.rank_entries.as<u32x4_t>(), stream_width ? size_t{0} : table_vectors, b.bloom.as<u32x4_t>(), bloom_vectors);
   }
   u32x2_t* entries = b.rank_entries.as<u32x2_t>();
   uint32_t* tickets = reinterpret_cast<uint32_t*>(entries + words + 2);
@@ -4297,7 +4391,7 @@ static hy_status launch_pk_count(const JoinRequest& q, const BuildSide& b, PkBuf
 }
 
 // Pass 2: the flavour of pk_emit that matches pass 1 (the rows' found / materialised bits of pk_count_lds, the ranks of pk_count<true>),
-// Inner or not; its first workgroups cut the PosLists, and it clears the zeroed block the join before used (FillCleaning).
+// Inner or not; its first workgroups cut the PosLists, and it clears the zeroed filter the join before used (FillCleaning).
 static hy_status launch_pk_emit(const JoinRequest& q, BuildSide& b, PkArgs& k, bool build_in_lds, bool hand_over_ranks, uint32_t max_slices, hipStream_t stream) {
   HY_TRY(raise_pk_emit_lds());
   hipEvent_t started = nullptr, stopped = nullptr;   // (stamped from the dispatch packet itself)

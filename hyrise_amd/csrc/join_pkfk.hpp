@@ -89,7 +89,7 @@ struct PkArgs {
   uint64_t hint_min, hint_max;
   uint32_t hint_allows_duplicates;
   hy_join_status* status;          // HY_JOIN_ASYNC: what the host would read from the mailbox, in device memory; else nullptr
-  FillCleaning cleaning;           // pk_emit: two regions its first workgroups zero (the rank table and filter of the join BEFORE: ZeroedBlocks in join.hip)
+  FillCleaning cleaning;           // pk_emit: the region its first workgroups zero (the filter of the join BEFORE: ZeroedBlocks in join.hip)
 };
 constexpr uint32_t PK_LDS_KEYS = 1u << 20;                       // the table's range must be smaller: then the Bloom filter (bit = key & 0xFFFFF) is the presence bit
 constexpr uint32_t PK_LDS_WORDS = PK_LDS_KEYS / 32;              // 32 768 presence words = 128 KB
@@ -1022,9 +1022,7 @@ __global__ __launch_bounds__(PK_THREADS, HY_PK_WAVES_PER_SIMD) void pk_emit(PkAr
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // The first cut_blocks workgroups (a multiple of 8: the others keep their XCD) find the PosList cuts while the rest emits: a launch
   // of its own behind this kernel was 13 us of an otherwise idle device.
-  for (uint32_t i = blockIdx.x * PK_THREADS + tid; i < a.cleaning.first_vectors + a.cleaning.second_vectors; i += gridDim.x * PK_THREADS) {
-    if (i < a.cleaning.first_vectors) a.cleaning.first[i] = u32x4_t{0, 0, 0, 0}; else a.cleaning.second[i - a.cleaning.first_vectors] = u32x4_t{0, 0, 0, 0};
-  }
+  for (uint32_t i = blockIdx.x * PK_THREADS + tid; i < a.cleaning.vectors; i += gridDim.x * PK_THREADS) a.cleaning.filter[i] = u32x4_t{0, 0, 0, 0};
   if (blockIdx.x < a.cut_blocks) { pk_cut_slice<MASKS>(a, blockIdx.x, join_smem, tid, lane, wave); return; }
   const uint32_t block = blockIdx.x - a.cut_blocks;
   // Which tile: the device works on one front of tiles that moves through the probe side -- workgroups arrive at the XCDs in turn (block b
