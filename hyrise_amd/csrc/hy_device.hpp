@@ -165,6 +165,7 @@ struct hy_column {
   bool has_sorted = false;                  // some chunk is flagged as sorted by this column (hy_segment::sorted_by): its scan may take JOB_RANGE jobs
   mutable std::mutex plain_mutex;
   mutable hy_column* plain = nullptr;       // owned
+  hy_column* stand_in = nullptr;            // owned: the data stand-in a reference column of hy_column_string_ranks reads through (`ref`)
 };
 
 namespace hy {
@@ -240,6 +241,8 @@ struct StringTwins {
   uint32_t n_data_chunks, n_chunks, n_evens;
 };
 hy_status string_twins_launch(const StringTwins& twins, hipStream_t stream);
+// scan.hip: `dict` is the string dictionary of `column`'s data column, chunk by chunk, on `column`'s device; `which`: "", "left " or "right "
+hy_status check_dictionary(const hy_string_dictionary* dict, const hy_column* column, const char* which, const char* entry_point);
 
 // ---- errors ---------------------------------------------------------------------------------------------------------
 hy_status fail(hy_status code, const char* fmt, ...);

@@ -1203,6 +1203,7 @@ hy_status hy_column_destroy(hy_column* column) {
   const bool foreign = t_bound_device >= 0 && column->device != t_bound_device;
   if (column->descriptors_pooled && !foreign) (void)hipStreamSynchronize(t_stream);
   if (column->plain) (void)hy_column_destroy(column->plain);
+  if (column->stand_in) (void)hy_column_destroy(column->stand_in);
   for (void* p : column->owned) (void)hipFree(p);
   for (auto& block : column->pooled) {
     if (foreign) (void)hipFree(block.second);

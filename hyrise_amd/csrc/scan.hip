@@ -2129,7 +2129,7 @@ static hy_status check_column_pair(const hy_column* left, const hy_column* right
 }
 
 // `dict` is the string dictionary of `column`'s data column, chunk by chunk, on `column`'s device; `which`: "", "left " or "right "
-static hy_status check_dictionary(const hy_string_dictionary* dict, const hy_column* column, const char* which, const char* entry_point) {
+hy_status check_dictionary(const hy_string_dictionary* dict, const hy_column* column, const char* which, const char* entry_point) {
   const hy_column* data_column = column->is_reference ? column->ref : column;
   const uint32_t n_data_chunks = data_column ? data_column->n_chunks : 0;
   if (dict->device != column->device) return fail(HY_ERR_INVALID, "%s: the %sdictionary lives on device %d, the column on device %d", entry_point, which, dict->device, column->device);

@@ -126,7 +126,165 @@ __global__ __launch_bounds__(256) void string_twins(StringTwins t) {
   }
 }
 
+// ---- one column's global string order (hy_string_dictionary_order) ----------------------------------------------------------------------
+// Every chunk's dictionary is a sorted run already: the runs are merged pairwise in ceil(log2(n_chunks)) rounds, rank-based.  An element
+// is a packed word (chunk << 32 | value id); position p of a buffer is entry_offsets[c] + v for the (c, v) that lies there before round 0
+// (order_identity).  In round r a run is 2^r consecutive chunks, and the merged pair takes exactly the positions its two runs had, so every
+// boundary comes from entry_offsets.  A workgroup owns the 256 positions of one LikeBlock, a lane one position: it reads its element,
+// binary-searches the sibling run (lower_bound for an element of the left run, upper_bound for one of the right: equal strings keep the
+// left one first) and stores the element at its merged position in the other buffer -- one plain 8-byte store, no atomics, no LDS, nothing
+// that depends on lane order.  A run without a sibling finds an empty one and stays where it is.
+// Then: a head flag per position (the element differs from its predecessor), counted inclusively inside a workgroup's 256 positions
+// (order_heads), the workgroups' totals scanned by one workgroup (order_scan_tiles), and rank = heads at or before the position - 1
+// scattered to ranks[entry_offsets[c] + v] (order_scatter).
+// Robustness: an element read from a buffer is clamped to a chunk and an entry that exist, offsets to the chunk's bytes; merged positions
+// are run begin + own index + a count of at most the sibling's length, so they stay inside the pair.  Dictionaries that are not sorted
+// leave positions unwritten and others written twice: unspecified ranks, nothing outside the buffers, no loop whose length is data.
+constexpr uint32_t ORDER_WG = 256;       // = LIKE_WG: the block table is the matcher's
+constexpr uint32_t ORDER_SCAN_WG = 1024;
+
+struct OrderArgs {
+  const LikeChunk* chunks;
+  const LikeBlock* blocks;
+  const uint64_t* entry_offsets;    // [n_chunks + 1]
+  uint32_t n_chunks;
+};
+
+__device__ __forceinline__ Entry element_entry(const OrderArgs& a, uint64_t element) {
+  const uint32_t c = min(static_cast<uint32_t>(element >> 32), a.n_chunks - 1);
+  const LikeChunk chunk = a.chunks[c];
+  if (chunk.n_entries == 0) return Entry{nullptr, 0};
+  return entry_of(chunk, min(static_cast<uint32_t>(element), chunk.n_entries - 1), chunk_bytes(chunk));
+}
+
+__global__ __launch_bounds__(ORDER_WG) void order_identity(OrderArgs a, uint64_t* elements) {
+  const LikeBlock block = a.blocks[blockIdx.x];
+  const uint32_t v = block.first_entry + threadIdx.x;
+  if (v >= a.chunks[block.chunk].n_entries) return;
+  elements[a.entry_offsets[block.chunk] + v] = uint64_t{block.chunk} << 32 | v;
+}
+
+__global__ __launch_bounds__(ORDER_WG) void order_merge(OrderArgs a, const uint64_t* in, uint64_t* out, uint32_t round) {
+  const LikeBlock block = a.blocks[blockIdx.x];
+  const uint32_t v = block.first_entry + threadIdx.x;
+  if (v >= a.chunks[block.chunk].n_entries) return;
+  // the pair of runs the position lies in: chunks [first, middle) and [middle, last)
+  const uint64_t run = uint64_t{1} << round;
+  const uint64_t first = (block.chunk >> round & ~1u) * run;
+  const uint64_t middle = min(first + run, uint64_t{a.n_chunks}), last = min(first + 2 * run, uint64_t{a.n_chunks});
+  const uint64_t left_begin = a.entry_offsets[first], right_begin = a.entry_offsets[middle], right_end = a.entry_offsets[last];
+  const uint64_t position = a.entry_offsets[block.chunk] + v;
+  const uint64_t element = in[position];
+  const Entry mine = element_entry(a, element);
+  const bool in_left = position < right_begin;
+  // left: the sibling's entries < mine; right: the sibling's entries <= mine
+  uint64_t lo = in_left ? right_begin : left_begin, hi = in_left ? right_end : right_begin;
+  const uint64_t sibling_begin = lo;
+  while (lo < hi) {
+    const uint64_t at = lo + (hi - lo) / 2;
+    const int order = compare_entries(element_entry(a, in[at]), mine);
+    if (in_left ? order < 0 : order <= 0) lo = at + 1;
+    else hi = at;
+  }
+  const uint64_t own = position - (in_left ? left_begin : right_begin);
+  out[left_begin + own + (lo - sibling_begin)] = element;
+}
+
+// local[p] = heads among the positions of p's workgroup up to and including p; tile_heads[workgroup] = its heads
+__global__ __launch_bounds__(ORDER_WG) void order_heads(OrderArgs a, const uint64_t* sorted, uint64_t n, uint32_t* local, uint32_t* tile_heads) {
+  __shared__ uint32_t s_wave_heads[ORDER_WG / 64];
+  const uint64_t p = uint64_t{blockIdx.x} * ORDER_WG + threadIdx.x;
+  bool head = false;
+  if (p < n) head = p == 0 || compare_entries(element_entry(a, sorted[p - 1]), element_entry(a, sorted[p])) != 0;
+  const uint64_t ballot = __ballot(head);
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) s_wave_heads[wave] = __popcll(ballot);
+  __syncthreads();
+  uint32_t before = 0;
+  for (uint32_t w = 0; w < wave; ++w) before += s_wave_heads[w];
+  if (p < n) local[p] = before + __popcll(ballot & (~0ull >> (63 - lane)));
+  if (threadIdx.x == ORDER_WG - 1) tile_heads[blockIdx.x] = before + s_wave_heads[wave];
+}
+
+// tile_heads becomes its own exclusive prefix sum; *n_distinct = the total.  One workgroup: a thread sums a contiguous share, the shares' sums
+// are scanned in LDS, the thread walks its share again.
+__global__ __launch_bounds__(ORDER_SCAN_WG) void order_scan_tiles(uint32_t* tile_heads, uint32_t n_tiles, uint32_t* n_distinct) {
+  __shared__ uint32_t s_sums[ORDER_SCAN_WG];
+  const uint32_t share = (n_tiles + ORDER_SCAN_WG - 1) / ORDER_SCAN_WG;
+  const uint32_t begin = min(threadIdx.x * share, n_tiles), end = min(begin + share, n_tiles);
+  uint32_t sum = 0;
+  for (uint32_t i = begin; i < end; ++i) sum += tile_heads[i];
+  s_sums[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t step = 1; step < ORDER_SCAN_WG; step <<= 1) {   // Hillis-Steele, inclusive
+    const uint32_t add = threadIdx.x >= step ? s_sums[threadIdx.x - step] : 0;
+    __syncthreads();
+    s_sums[threadIdx.x] += add;
+    __syncthreads();
+  }
+  uint32_t running = s_sums[threadIdx.x] - sum;
+  for (uint32_t i = begin; i < end; ++i) {
+    const uint32_t heads = tile_heads[i];
+    tile_heads[i] = running;
+    running += heads;
+  }
+  if (threadIdx.x == ORDER_SCAN_WG - 1) *n_distinct = s_sums[ORDER_SCAN_WG - 1];
+}
+
+__global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uint64_t* sorted, uint64_t n, const uint32_t* local, const uint32_t* tile_heads, int32_t* ranks) {
+  const uint64_t p = uint64_t{blockIdx.x} * ORDER_WG + threadIdx.x;
+  if (p >= n) return;
+  const uint64_t element = sorted[p];
+  const uint32_t c = min(static_cast<uint32_t>(element >> 32), a.n_chunks - 1);
+  const uint32_t n_entries = a.chunks[c].n_entries;
+  if (n_entries == 0) return;
+  const uint32_t v = min(static_cast<uint32_t>(element), n_entries - 1);
+  ranks[a.entry_offsets[c] + v] = static_cast<int32_t>(tile_heads[blockIdx.x] + local[p] - 1);   // (position 0 is a head: never below 0)
+}
+
 }  // namespace
+
+// What hy_string_dictionary_order takes from the scratch arena for a dictionary of `total` entries
+static size_t order_scratch_bytes(uint64_t total) {
+  const uint64_t tiles = (total + ORDER_WG - 1) / ORDER_WG;
+  return 2 * align_up(8 * total, 256) + align_up(4 * tiles, 256) + 256 + 4096;
+}
+
+// Queues the whole sequence on `stream`: d_ranks[entry_offsets[c] + v] and *d_n_distinct (device memory, carved here: d_ranks may be a
+// block of the arena that the caller carved BEFORE this call).  total = entry_offsets[n_chunks] > 0.
+static hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream) {
+  HY_TRY(like_dictionary_tables(dict));
+  const uint64_t total = dict->entry_offsets[dict->n_chunks];
+  const uint32_t n_blocks = static_cast<uint32_t>(dict->blocks.size());
+  const uint32_t n_tiles = static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG);
+  uint64_t* ping = carve<uint64_t>(sc, total);
+  uint64_t* pong = carve<uint64_t>(sc, total);
+  uint32_t* tile_heads = carve<uint32_t>(sc, n_tiles);
+  *d_n_distinct = carve<uint32_t>(sc, 1);
+  if (!ping || !pong || !tile_heads || !*d_n_distinct) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks};
+  profile_begin(stream, HY_KERNEL_STRING_RANK);
+  hipLaunchKernelGGL(order_identity, dim3(n_blocks), dim3(ORDER_WG), 0, stream, args, ping);
+  for (uint32_t round = 0; (uint64_t{1} << round) < dict->n_chunks; ++round) {
+    hipLaunchKernelGGL(order_merge, dim3(n_blocks), dim3(ORDER_WG), 0, stream, args, ping, pong, round);
+    std::swap(ping, pong);
+  }
+  uint32_t* local = reinterpret_cast<uint32_t*>(pong);   // (the buffer the last round read: free again)
+  hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads);
+  hipLaunchKernelGGL(order_scan_tiles, dim3(1), dim3(ORDER_SCAN_WG), 0, stream, tile_heads, n_tiles, *d_n_distinct);
+  hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads, d_ranks);
+  profile_end(stream);
+  HY_HIP(hipGetLastError());
+  return HY_OK;
+}
+
+// The refusals of a dictionary that is to be ordered, before any launch and any allocation
+static hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point) {
+  if (dict->device != this_thread_device()) return fail(HY_ERR_INVALID, "%s: the dictionary lives on device %d, the calling thread works on device %d", entry_point, dict->device, this_thread_device());
+  const uint64_t total = dict->entry_offsets[dict->n_chunks];
+  if (total >= (uint64_t{1} << 31)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu dictionary entries do not fit int32 ranks", entry_point, static_cast<unsigned long long>(total));
+  return HY_OK;
+}
 
 hy_status string_order_check(const hy_string_dictionary* left, const hy_string_dictionary* right, const char* entry_point) {
   if (left->n_chunks != right->n_chunks) return fail(HY_ERR_INVALID, "%s: the left dictionary has %u chunks, the right one %u", entry_point, left->n_chunks, right->n_chunks);
@@ -180,6 +338,93 @@ hy_status hy_string_dictionary_ranks(const hy_string_dictionary* left, const hy_
   HY_TRY(string_order_launch(left, right, d_ranks, stream));
   HY_HIP(hipMemcpyAsync(ranks, d_ranks, 4 * total, hipMemcpyDeviceToHost, stream));
   HY_HIP(hipStreamSynchronize(stream));
+  return HY_OK;
+}
+
+hy_status hy_string_dictionary_order(const hy_string_dictionary* dict, uint32_t mem, int32_t* ranks, uint32_t* n_distinct) {
+  const char* name = "hy_string_dictionary_order";
+  if (!dict || !ranks) return fail(HY_ERR_INVALID, "%s: null argument", name);
+  if (mem != HY_MEM_HOST && mem != HY_MEM_DEVICE) return fail(HY_ERR_INVALID, "%s: bad memory space %u", name, mem);
+  HY_TRY(column_order_check(dict, name));
+  if (mem == HY_MEM_DEVICE && reinterpret_cast<uintptr_t>(ranks) % 4 != 0) return fail(HY_ERR_INVALID, "%s: ranks not on a 4-byte boundary", name);
+  const uint64_t total = dict->entry_offsets[dict->n_chunks];
+  if (!total) {
+    if (n_distinct) *n_distinct = 0;
+    return HY_OK;
+  }
+  hipStream_t stream = current_stream();
+  Scratch& sc = scratch();
+  HY_TRY(sc.reserve(order_scratch_bytes(total) + (mem == HY_MEM_HOST ? align_up(4 * total, 256) : 0)));
+  int32_t* d_ranks = mem == HY_MEM_DEVICE ? ranks : carve<int32_t>(sc, total);
+  if (!d_ranks) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  uint32_t* d_n_distinct = nullptr;
+  HY_TRY(column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream));
+  if (mem == HY_MEM_HOST) HY_HIP(hipMemcpyAsync(ranks, d_ranks, 4 * total, hipMemcpyDeviceToHost, stream));
+  if (n_distinct) HY_HIP(hipMemcpyAsync(n_distinct, d_n_distinct, 4, hipMemcpyDeviceToHost, stream));
+  if (mem == HY_MEM_HOST || n_distinct) HY_HIP(hipStreamSynchronize(stream));   // (else: complete in the order of the calling thread's stream)
+  return HY_OK;
+}
+
+hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictionary* dict, hy_column** out) {
+  const char* name = "hy_column_string_ranks";
+  if (!out) return fail(HY_ERR_INVALID, "%s: null output", name);
+  *out = nullptr;
+  if (!column || !dict) return fail(HY_ERR_INVALID, "%s: null argument", name);
+  HY_TRY(on_this_device(column, name));
+  if (column->is_mvcc || (column->data_type != HY_TYPE_STRING && column->n_chunks)) return fail(HY_ERR_INVALID, "%s: not a string column (type %u)", name, column->data_type);
+  HY_TRY(check_dictionary(dict, column, "", name));
+  HY_TRY(column_order_check(dict, name));
+  const hy_column* data_column = column->is_reference ? column->ref : column;
+  const uint32_t n_data_chunks = data_column->n_chunks;
+  const uint64_t total = dict->entry_offsets[dict->n_chunks];
+
+  // the ranks: a buffer the stand-in owns (16 bytes of slack behind the last rank, like every dictionary of a column)
+  hipStream_t stream = current_stream();
+  int32_t* d_ranks = nullptr;
+  HY_HIP(hipMalloc(reinterpret_cast<void**>(&d_ranks), align_up(4 * total + 16, 256)));
+  auto give_up = [&](hy_status status) {
+    (void)hipStreamSynchronize(stream);
+    (void)hipFree(d_ranks);
+    return status;
+  };
+  if (total) {
+    Scratch& sc = scratch();
+    hy_status status = sc.reserve(order_scratch_bytes(total));
+    uint32_t* d_n_distinct = nullptr;
+    if (status == HY_OK) status = column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream);
+    if (status != HY_OK) return give_up(status);
+  }
+  // the data stand-in: DictionarySegment<int32> over the caller's attribute vectors, whatever their width or packing
+  std::vector<hy_segment> segments(data_column->host_segments);
+  for (uint32_t c = 0; c < n_data_chunks; ++c) {
+    segments[c].data_type = HY_TYPE_INT;
+    segments[c].aux = d_ranks + dict->entry_offsets[c];
+  }
+  hy_column* stand_in = nullptr;
+  hy_status status = hy_column_create(segments.data(), n_data_chunks, HY_MEM_DEVICE, &stand_in);
+  if (status != HY_OK) return give_up(status);
+  stand_in->owned.push_back(d_ranks);
+  hy_column* result = stand_in;
+  if (column->is_reference) {   // the same PosLists over the stand-in
+    segments = column->host_segments;
+    for (hy_segment& segment : segments) {
+      segment.data_type = HY_TYPE_INT;
+      segment.ref = stand_in;
+    }
+    status = hy_column_create(segments.data(), column->n_chunks, HY_MEM_DEVICE, &result);
+    if (status != HY_OK) {
+      (void)hy_column_destroy(stand_in);
+      return status;
+    }
+    result->stand_in = stand_in;
+  }
+  // (the dictionary may die as soon as the call has returned: nothing queued reads it any more)
+  const hipError_t err = hipStreamSynchronize(stream);
+  if (err != hipSuccess) {
+    (void)hy_column_destroy(result);
+    return fail(HY_ERR_DEVICE, "%s: ranking failed: %s", name, hipGetErrorString(err));
+  }
+  *out = result;
   return HY_OK;
 }
 

@@ -761,12 +761,15 @@ struct DeviceColumn {
   std::vector<hy_segment> descriptors;
   std::vector<std::vector<int64_t>> key_names;   // string GROUP BY columns: AggregateKeyEntry names per chunk
   std::shared_ptr<const DeviceColumnOwner> resident;   // `handle` is a column an operator left in HBM: its segments own it
+  std::shared_ptr<DeviceColumn> strings;   // `handle` is hy_column_string_ranks' stand-in of this column, whose buffers it reads: destroyed before it
+  bool device_ranking = true;              // StringKeys::Ranks: what device_string_ranking() said when the column was made
   ~DeviceColumn() { if (handle && !resident) hy_column_destroy(handle); }
 };
 
 // How a DictionarySegment<pmr_string> is presented to the device: the value ids alone (scans), or with a dictionary of int64
 // stand-ins for the strings -- AggregateKey names (GROUP BY), join ids (JoinHash) or ranks among the column's distinct strings in byte
-// order (Sort; hyrise_amd/string_keys.py StringRanks).
+// order (Sort; hyrise_amd/string_keys.py StringRanks).  The ranks of a whole dictionary-encoded column are made on the device and are int32
+// (device_string_rank_column); the host makes them, as int64, for everything else.
 enum class StringKeys { None, AggregateKeyNames, JoinIds, Ranks };
 // The dictionaries of a string column's DictionarySegment chunks in HBM (hy_string_dictionary): what the LIKE matcher reads on the device.
 struct DeviceStringDictionary {
@@ -995,10 +998,20 @@ inline std::shared_ptr<const DeviceColumnOwner> resident_column_of_chunks(const 
   return chunks_of_column == chunk_end - chunk_begin ? owner : nullptr;
 }
 
+// StringKeys::Ranks of a whole column: ranked on the device (hy_column_string_ranks); false: on the host, by sorting the dictionaries' entries
+// (tests and tools/string_order_time.py run both).
+inline bool& device_string_ranking() { static bool enabled = true; return enabled; }
+inline std::shared_ptr<DeviceColumn> device_string_rank_column(const std::shared_ptr<const Table>& table, ColumnID column_id);
+
 inline std::shared_ptr<DeviceColumn> device_column(const std::shared_ptr<const Table>& table, ColumnID column_id, StringKeys string_keys) {
   if (!table->device_columns) table->device_columns = std::make_shared<ColumnCache>();
   auto& slot = table->device_columns->columns[{column_id, string_keys}];
-  if (!slot) slot = device_column_of_chunks(table, column_id, string_keys, 0, table->chunk_count());
+  if (slot && string_keys == StringKeys::Ranks && slot->device_ranking != device_string_ranking()) slot = nullptr;   // (made under the other setting)
+  if (!slot && string_keys == StringKeys::Ranks && device_string_ranking()) slot = device_string_rank_column(table, column_id);
+  if (!slot) {
+    slot = device_column_of_chunks(table, column_id, string_keys, 0, table->chunk_count());
+    slot->device_ranking = device_string_ranking();
+  }
   return slot;
 }
 
@@ -1035,6 +1048,34 @@ inline std::shared_ptr<DeviceStringDictionary> device_string_dictionary(const st
   check_status(hy_string_dictionary_create(chunks.data(), chunk_count, HY_MEM_HOST, &dictionary->handle));
   slot = dictionary;
   return slot;
+}
+
+// A string column as a sort key without any string work on the host: every chunk a DictionarySegment<pmr_string>, or a ReferenceSegment over
+// one column of such chunks.  The column goes to the device as it does for a scan (value ids alone, or PosLists over them), its data
+// column's dictionaries as they do for LIKE, and hy_column_string_ranks orders them in HBM and hands back the int32 stand-in, which reads the
+// string column's buffers in place.  nullptr: not such a column, or the library refused it -- the caller ranks on the host.
+inline std::shared_ptr<DeviceColumn> device_string_rank_column(const std::shared_ptr<const Table>& table, ColumnID column_id) {
+  const auto chunk_count = table->chunk_count();
+  if (chunk_count == 0 || table->column_data_type(column_id) != DataType::String) return nullptr;
+  std::shared_ptr<const Table> data_table = table;
+  ColumnID data_column_id = column_id;
+  if (const auto* first = dynamic_cast<const ReferenceSegment*>(table->get_chunk(0)->get_segment(column_id).get())) {
+    data_table = first->referenced_table();
+    data_column_id = first->referenced_column_id();
+    for (ChunkID k = 0; k < chunk_count; ++k) {
+      const auto* segment = dynamic_cast<const ReferenceSegment*>(table->get_chunk(k)->get_segment(column_id).get());
+      if (!segment || segment->referenced_table() != data_table || segment->referenced_column_id() != data_column_id) return nullptr;
+    }
+  }
+  if (data_table->chunk_count() == 0) return nullptr;
+  for (ChunkID k = 0; k < data_table->chunk_count(); ++k) {
+    if (!dynamic_cast<const DictionarySegment<std::string>*>(data_table->get_chunk(k)->get_segment(data_column_id).get())) return nullptr;
+  }
+  auto column = std::make_shared<DeviceColumn>();
+  column->strings = device_column(table, column_id, StringKeys::None);
+  const auto dictionary = device_string_dictionary(data_table, data_column_id);
+  if (hy_column_string_ranks(column->strings->handle, dictionary->handle, &column->handle) != HY_OK) return nullptr;
+  return column;
 }
 
 // LIKE scans match their dictionaries on the device (hy_table_scan_like); false: on the host, bitmaps through hy_predicate.match_words.

@@ -304,6 +304,51 @@ def string_dictionary_ranks(left_dict, right_dict):
     return [ranks[int(bounds[c]):int(bounds[c + 1])] for c in range(left_dict.n_chunks)]
 
 
+def string_dictionary_order(dev_dict):
+    """hy_string_dictionary_order with a host result over one storage.DeviceStringDictionary -> (per chunk the int32 dense ranks of the
+    chunk's entries among the distinct strings of ALL chunks in byte order, the number of distinct strings): what StringRanks computes on
+    the host, made in HBM."""
+    lib = abi.load_library()
+    total = sum(dev_dict.n_entries)
+    ranks = np.zeros(max(1, total), dtype=np.int32)
+    n_distinct = C.c_uint32(0xFFFFFFFF)
+    abi.check(lib.hy_string_dictionary_order(dev_dict.handle, abi.MEM_HOST, ranks.ctypes.data, C.byref(n_distinct)))
+    bounds = np.concatenate([[0], np.cumsum(dev_dict.n_entries, dtype=np.int64)]).astype(np.int64)
+    return [ranks[int(bounds[c]):int(bounds[c + 1])] for c in range(dev_dict.n_chunks)], int(n_distinct.value)
+
+
+class StringRankColumn:
+    """hy_column_string_ranks' int32 stand-in of a string column: usable wherever a DeviceColumn is (a sort key, hy_column_export, ...).  It
+    reads the string column's attribute vectors and PosLists in place, so it keeps that column alive, and is destroyed before it."""
+
+    def __init__(self, handle, parents):
+        self.lib = abi.load_library()
+        self.handle = handle
+        self.parents = parents
+        self.rows, self.n_chunks, self.data_type = parents[0].rows, parents[0].n_chunks, abi.TYPE_INT
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.hy_column_destroy(self.handle)
+            self.handle = None
+        self.parents = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def column_string_ranks(dev_column, dev_dict):
+    """hy_column_string_ranks: a string DeviceColumn (data or reference column) and the DeviceStringDictionary of its data column -> the
+    column of each row's rank among the column's distinct strings (StringRankColumn), ranks made and kept in HBM."""
+    lib = abi.load_library()
+    handle = C.c_void_p()
+    abi.check(lib.hy_column_string_ranks(dev_column.handle, dev_dict.handle, C.byref(handle)))
+    return StringRankColumn(handle, (dev_column, dev_dict))
+
+
 def table_scan_columns_strings(left, left_dict, right, right_dict, condition, flags=0, device=False):
     """hy_table_scan_columns_strings: `left <condition> right` over two string columns of one table and their dictionaries (for reference
     columns: the referenced data columns') -> HostScanResult like table_scan_columns, or with device=True the chunk-region result in

@@ -237,7 +237,7 @@ hy_status hy_profile_read(float* total_milliseconds, uint32_t* launches);
  * timed kernels separately before hy_profile_read() clears the session. */
 enum { HY_KERNEL_OTHER = 0, HY_KERNEL_SCAN = 1, HY_KERNEL_JOIN_PROBE = 2, HY_KERNEL_JOIN_COUNT = 3, HY_KERNEL_JOIN_BUILD = 4, HY_KERNEL_AGGREGATE = 5,
        HY_KERNEL_PROJECTION = 6, HY_KERNEL_LIKE = 7 /* like_match, the dictionary matcher */,
-       HY_KERNEL_STRING_RANK = 8 /* string_rank, one string dictionary ordered against another */, HY_KERNEL_KINDS = 9 };
+       HY_KERNEL_STRING_RANK = 8 /* string_rank, one string dictionary ordered against another; the launch sequence of hy_string_dictionary_order */, HY_KERNEL_KINDS = 9 };
 hy_status hy_profile_read_kernel(uint32_t kernel, float* total_milliseconds, uint32_t* launches);
 /* What such an event pair measures beyond the kernel itself (the pair is stamped from the dispatch packet): the elapsed time of an
  * empty kernel, median of 32 launches, measured once per process.  A profiler's per-kernel duration is shorter by about this much. */
@@ -514,6 +514,45 @@ hy_status hy_string_dictionary_ranks(const hy_string_dictionary* left, const hy_
 hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_dictionary* left_dict, const hy_column* right,
                                         const hy_string_dictionary* right_dict, uint32_t condition, hy_scan_result* result);
 
+/* ---- One string column's global order (what Sort, and later MIN / MAX and JoinSortMerge, need of a pmr_string column) -------------------
+ * hy_string_dictionary_ranks orders chunk c of one column against chunk c of another.  The entry points below order ALL chunks of ONE
+ * column against each other: for entry v of chunk c
+ *     rank(c, v) = the number of DISTINCT strings, over all chunks of `dict`, that are smaller than the entry        (dense rank)
+ * Equal strings in different chunks get equal ranks; ranks run 0 .. n_distinct - 1; a chunk's ranks ascend strictly with v (its dictionary
+ * is sorted and duplicate-free).  Order is std::string's, as above: bytes compared as unsigned, a prefix first, a '\0' inside an entry of
+ * the offsets layout is data, an entry of the fixed-length layout ends at strnlen(slot, string_length); the two layouts may be mixed across
+ * chunks.  These are the numbers hyrise_amd/string_keys.py StringRanks and the mirror's host ranking produce, bit for bit.
+ * On the device the chunks' dictionaries -- sorted runs already -- are merged pairwise in ceil(log2(n_chunks)) rounds (one launch each, one
+ * binary search of the sibling run per entry), then a head flag per merged position, a prefix sum and a scatter: nothing crosses to the host.
+ * A dictionary that is not sorted gives unspecified ranks; no byte outside the call's buffers is read or written even then.
+ *
+ * hy_string_dictionary_order   ranks: E = the sum of all n_entries int32_t; chunk c's ranks start at the sum of n_entries before c (the
+ *   layout of hy_string_dictionary_ranks).  mem == HY_MEM_DEVICE: ranks stay in the caller's device buffer (on 4 bytes, otherwise
+ *   HY_ERR_INVALID), complete in the order of the calling thread's stream.  mem == HY_MEM_HOST: copied back; the call returns when they are
+ *   there.  n_distinct: HOST memory, may be NULL; when it is given the call waits for the stream.  E == 0: HY_OK, nothing is launched,
+ *   *n_distinct = 0.  HY_ERR_INVALID: a null dict / ranks, a bad mem, a dictionary of another device than the calling thread's.
+ *   HY_ERR_UNSUPPORTED: E >= 2^31.  All refusals come before any launch and any allocation.  Temporaries (16 bytes per entry) come from the
+ *   thread's scratch arena; the launches are timed under HY_KERNEL_STRING_RANK.
+ *
+ * hy_column_string_ranks   the int32 stand-in of a string column: *out is a column of HY_TYPE_INT with `column`'s chunk layout whose row r
+ *   holds the rank of row r's string (NULL where row r is NULL).  `column`: a data column of string dictionary segments, or a reference
+ *   column over one; `dict`: the dictionaries of the DATA column (chunk count and every n_entries equal to the segments' aux_size, as for
+ *   hy_table_scan_like).
+ *     data column       *out has dictionary segments over the SAME attribute vectors -- the buffers are shared, not copied, whatever their
+ *                       width or packing -- with aux = the chunk's ranks in HBM and the NULL value id still aux_size: a well-formed
+ *                       DictionarySegment<int32>.  *out owns the rank buffer.
+ *     reference column  *out is a reference column over the same PosLists (shared: host-uploaded, caller-owned device lists, entire-chunk
+ *                       lists) whose referenced column is such a data stand-in, owned by *out.
+ *   *out is an ordinary column for hy_sort, hy_sort_limit, hy_column_export, hy_column_gather and every other reader of int32 dictionary
+ *   columns: ORDER BY a string column is hy_sort over it.  Lifetime: `column` (and the column it references) must outlive *out, as a
+ *   referenced column outlives a reference column; `dict` may be destroyed as soon as the call has returned (the call waits for the
+ *   ranking); hy_column_destroy(*out) frees the ranks.
+ *   HY_ERR_INVALID: a null argument, a column that is no string column, a dictionary that disagrees with the data column's segments or lives
+ *   on another device.  HY_ERR_UNSUPPORTED: unencoded or LZ4 string segments, E >= 2^31.  On any error *out is NULL and nothing stays
+ *   allocated.  Ranks are not cached inside `dict`: every call ranks again. */
+hy_status hy_string_dictionary_order(const hy_string_dictionary* dict, uint32_t mem, int32_t* ranks, uint32_t* n_distinct);
+hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictionary* dict, hy_column** out);
+
 /* ---- Validate (replaces Validate::_on_execute / _validate_chunks, validate.cpp:32-55,87-314) ----
  * The MVCC visibility filter that sits in front of every TableScan of an SQL-driven plan.  The table's MvccData
  * (storage/mvcc_data.hpp) is passed as one "column" of HY_ENC_MVCC segments, one per chunk:
@@ -571,7 +610,7 @@ hy_status hy_poslist_gather(const hy_column* reference, const hy_row_id* positio
  * the chunk (for a reference table: the position in the chunk's PosList).  NULLs come first in both directions and keep their order among
  * themselves (:435-443); descending is std::greater with stable ties; float / double compare with std::less (-0.0 and 0.0 tie; NaN is not
  * supported).  A key column is a data or reference column of any numeric type and encoding; a string column is passed as a column of
- * order-preserving integer ranks (hyrise_amd/string_keys.py StringRanks).  All key columns are columns of one table: the same chunk layout.
+ * order-preserving integer ranks (hy_column_string_ranks makes it in HBM; hyrise_amd/string_keys.py StringRanks on the host).  All key columns are columns of one table: the same chunk layout.
  * mode: HY_SORT_ASCENDING_NULLS_FIRST or HY_SORT_DESCENDING_NULLS_FIRST; the NULLS LAST modes are HY_ERR_INVALID (Sort asserts, :294-296).
  * out: DEVICE memory with room for `capacity` RowIDs; receives the INPUT TABLE's positions (chunk, offset) in sorted order -- the adapter
  * dereferences them through a reference input's PosLists with hy_poslist_gather once per column cluster (write_reference_output_table,
