@@ -284,6 +284,10 @@ SYMBOLS = [
     ("hy_table_scan_columns_strings", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_string_dictionary_order", C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("hy_column_string_ranks", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("hy_string_column_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("hy_string_ranks_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("hy_string_dictionary_chunk_size", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    ("hy_string_dictionary_read_chunk", C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("hy_projection_arithmetic", C.c_int32, [C.c_uint32, C.POINTER(Operand), C.POINTER(Operand), C.POINTER(C.c_void_p)]),
     ("hy_projection_expression", C.c_int32, [C.POINTER(ProjectionProgram), C.POINTER(C.c_void_p)]),
     ("hy_table_scan_expression", C.c_int32, [C.POINTER(ProjectionProgram), C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),

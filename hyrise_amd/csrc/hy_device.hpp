@@ -205,6 +205,7 @@ struct hy_string_dictionary {
   std::vector<uint64_t> word_offsets;           // [n_chunks + 1]
   std::vector<uint64_t> entry_offsets;          // [n_chunks + 1] prefix sum of n_entries: where a chunk's ranks begin (string_order.hip)
   mutable std::vector<void*> owned;             // device allocations freed with the object
+  mutable std::vector<uint64_t> chars_bytes;    // [n_chunks] bytes of an offsets chunk's chars (offsets[n_entries]); ~0: caller-owned offsets nobody has read yet
   // The three tables above in device memory, uploaded by the first launch that needs them (creating a dictionary over caller-owned
   // device buffers is pure host work).
   mutable std::mutex tables_mutex;
@@ -241,6 +242,17 @@ struct StringTwins {
   uint32_t n_data_chunks, n_chunks, n_evens;
 };
 hy_status string_twins_launch(const StringTwins& twins, hipStream_t stream);
+// One column's global string order (hy_string_dictionary_order) for the other translation units: what the launches take from the scratch arena
+// for `total` entries; the refusals of a dictionary (device, E >= 2^31) and of a string column with its dictionary (hy_column_string_ranks'),
+// before any launch; the launch sequence itself -- d_ranks[entry_offsets[c] + v] and *d_n_distinct, carved from `sc`, total > 0.
+struct Scratch;
+size_t order_scratch_bytes(uint64_t total);
+hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point);
+hy_status string_column_check(const hy_column* column, const hy_string_dictionary* dict, const char* entry_point);
+hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream);
+// The int32 stand-in of a string column over a table of E int32_t in device memory (entry v of data chunk c reads d_table[entry_offsets[c] + v]):
+// the caller's attribute vectors and PosLists, shared.  A reference column's stand-in owns its data stand-in; the table stays the caller's.
+hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, int32_t* d_table, hy_column** out);
 // scan.hip: `dict` is the string dictionary of `column`'s data column, chunk by chunk, on `column`'s device; `which`: "", "left " or "right "
 hy_status check_dictionary(const hy_string_dictionary* dict, const hy_column* column, const char* which, const char* entry_point);
 

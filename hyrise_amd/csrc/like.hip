@@ -224,6 +224,8 @@ hy_status hy_string_dictionary_create(const hy_string_dictionary_chunk* chunks, 
   dict->chunks.resize(n_chunks);
   dict->word_offsets.assign(size_t{n_chunks} + 1, 0);
   dict->entry_offsets.assign(size_t{n_chunks} + 1, 0);
+  dict->chars_bytes.assign(n_chunks, ~0ull);
+  for (uint32_t c = 0; c < n_chunks; ++c) if (mem == HY_MEM_HOST || !chunks[c].n_entries) dict->chars_bytes[c] = char_bytes[c];
   dict->blocks.reserve(n_blocks);
   char* cursor = nullptr;
   if (mem == HY_MEM_HOST && allocation) {

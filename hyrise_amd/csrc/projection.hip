@@ -439,7 +439,8 @@ hy_status hy_column_read_chunk(const hy_column* column, uint32_t chunk, void* va
   if (chunk >= column->n_chunks) return fail(HY_ERR_INVALID, "chunk %u out of range", chunk);
   HY_TRY(plain_column(column, &column));
   const hy_segment& s = column->host_segments[chunk];
-  if (s.encoding != HY_ENC_UNENCODED) return fail(HY_ERR_UNSUPPORTED, "hy_column_read_chunk reads unencoded value segments");
+  // (a string dictionary segment: its attribute vector, s.width bytes per value id -- the columns hy_string_column_gather makes are read so)
+  if (s.encoding != HY_ENC_UNENCODED && !(s.encoding == HY_ENC_DICTIONARY && s.data_type == HY_TYPE_STRING)) return fail(HY_ERR_UNSUPPORTED, "hy_column_read_chunk reads unencoded value segments and attribute vectors");
   hipStream_t stream = current_stream();
   if (s.size) HY_HIP(hipMemcpyAsync(values, s.data, size_t{s.width} * s.size, hipMemcpyDeviceToHost, stream));
   if (null_words) {

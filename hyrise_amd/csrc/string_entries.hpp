@@ -1,0 +1,59 @@
+// string_entries.hpp -- one dictionary entry as the kernels over string dictionaries read it (string_order.hip: the rankings; string_gather.hip:
+// the gather): where its bytes lie and how many they are, in either chunk layout, and std::string's order of two entries.  Every translation
+// unit that includes this gets its own copy (anonymous namespace).
+#pragma once
+
+#include "hy_device.hpp"
+
+namespace hy {
+
+namespace {
+
+struct Entry {
+  const uint8_t* bytes;
+  uint32_t length;
+};
+
+// bytes in the chunk's chars: what the entries may be read from
+__device__ __forceinline__ uint32_t chunk_bytes(const LikeChunk& chunk) {
+  if (chunk.n_entries == 0) return 0;
+  return chunk.offsets ? chunk.offsets[chunk.n_entries] : chunk.n_entries * chunk.string_length;
+}
+
+__device__ __forceinline__ Entry entry_of(const LikeChunk& chunk, uint32_t v, uint32_t end) {
+  const uint8_t* chars = reinterpret_cast<const uint8_t*>(chunk.chars);
+  if (chunk.offsets) {
+    const uint32_t from = min(chunk.offsets[v], end);
+    const uint32_t to = min(max(chunk.offsets[v + 1], from), end);
+    return Entry{chars + from, to - from};
+  }
+  const uint8_t* slot = chars + size_t{v} * chunk.string_length;   // FixedString: strnlen(slot, L), fixed_string.cpp:86-99
+  uint32_t length = 0;
+  while (length < chunk.string_length && slot[length] != 0) ++length;
+  return Entry{slot, length};
+}
+
+__device__ __forceinline__ uint32_t load_word(const uint8_t* p) {   // four bytes at any address, first byte most significant
+  uint32_t w;
+  __builtin_memcpy(&w, p, 4);
+  return __builtin_bswap32(w);
+}
+
+// < 0, 0, > 0 as x.compare(y) of two std::strings
+__device__ __forceinline__ int compare_entries(const Entry& x, const Entry& y) {
+  const uint32_t common = min(x.length, y.length);
+  uint32_t i = 0;
+  for (; i + 4 <= common; i += 4) {
+    const uint32_t p = load_word(x.bytes + i), q = load_word(y.bytes + i);
+    if (p != q) return p < q ? -1 : 1;
+  }
+  for (; i < common; ++i) {
+    const uint32_t p = x.bytes[i], q = y.bytes[i];
+    if (p != q) return p < q ? -1 : 1;
+  }
+  return x.length == y.length ? 0 : x.length < y.length ? -1 : 1;
+}
+
+}  // namespace
+
+}  // namespace hy

@@ -18,6 +18,7 @@
 // Offsets are clamped to the chunk's byte range [0, offsets[n_entries]] on both sides: a dictionary that is not sorted, or offsets that do
 // not ascend, give unspecified ranks and no read outside the two chunks' bytes.
 #include "hy_device.hpp"
+#include "string_entries.hpp"
 
 #include <algorithm>
 
@@ -34,51 +35,6 @@ struct RankArgs {
   const uint64_t* entry_offsets;    // of the left dictionary
   int32_t* ranks;
 };
-
-struct Entry {
-  const uint8_t* bytes;
-  uint32_t length;
-};
-
-// bytes in the chunk's chars: what the entries may be read from
-__device__ __forceinline__ uint32_t chunk_bytes(const LikeChunk& chunk) {
-  if (chunk.n_entries == 0) return 0;
-  return chunk.offsets ? chunk.offsets[chunk.n_entries] : chunk.n_entries * chunk.string_length;
-}
-
-__device__ __forceinline__ Entry entry_of(const LikeChunk& chunk, uint32_t v, uint32_t end) {
-  const uint8_t* chars = reinterpret_cast<const uint8_t*>(chunk.chars);
-  if (chunk.offsets) {
-    const uint32_t from = min(chunk.offsets[v], end);
-    const uint32_t to = min(max(chunk.offsets[v + 1], from), end);
-    return Entry{chars + from, to - from};
-  }
-  const uint8_t* slot = chars + size_t{v} * chunk.string_length;   // FixedString: strnlen(slot, L), fixed_string.cpp:86-99
-  uint32_t length = 0;
-  while (length < chunk.string_length && slot[length] != 0) ++length;
-  return Entry{slot, length};
-}
-
-__device__ __forceinline__ uint32_t load_word(const uint8_t* p) {   // four bytes at any address, first byte most significant
-  uint32_t w;
-  __builtin_memcpy(&w, p, 4);
-  return __builtin_bswap32(w);
-}
-
-// < 0, 0, > 0 as x.compare(y) of two std::strings
-__device__ __forceinline__ int compare_entries(const Entry& x, const Entry& y) {
-  const uint32_t common = min(x.length, y.length);
-  uint32_t i = 0;
-  for (; i + 4 <= common; i += 4) {
-    const uint32_t p = load_word(x.bytes + i), q = load_word(y.bytes + i);
-    if (p != q) return p < q ? -1 : 1;
-  }
-  for (; i < common; ++i) {
-    const uint32_t p = x.bytes[i], q = y.bytes[i];
-    if (p != q) return p < q ? -1 : 1;
-  }
-  return x.length == y.length ? 0 : x.length < y.length ? -1 : 1;
-}
 
 __global__ __launch_bounds__(RANK_WG) void string_rank(RankArgs a) {
   const LikeBlock block = a.blocks[blockIdx.x];
@@ -245,14 +201,14 @@ __global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uin
 }  // namespace
 
 // What hy_string_dictionary_order takes from the scratch arena for a dictionary of `total` entries
-static size_t order_scratch_bytes(uint64_t total) {
+size_t order_scratch_bytes(uint64_t total) {
   const uint64_t tiles = (total + ORDER_WG - 1) / ORDER_WG;
   return 2 * align_up(8 * total, 256) + align_up(4 * tiles, 256) + 256 + 4096;
 }
 
 // Queues the whole sequence on `stream`: d_ranks[entry_offsets[c] + v] and *d_n_distinct (device memory, carved here: d_ranks may be a
 // block of the arena that the caller carved BEFORE this call).  total = entry_offsets[n_chunks] > 0.
-static hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream) {
+hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream) {
   HY_TRY(like_dictionary_tables(dict));
   const uint64_t total = dict->entry_offsets[dict->n_chunks];
   const uint32_t n_blocks = static_cast<uint32_t>(dict->blocks.size());
@@ -279,11 +235,19 @@ static hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& 
 }
 
 // The refusals of a dictionary that is to be ordered, before any launch and any allocation
-static hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point) {
+hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point) {
   if (dict->device != this_thread_device()) return fail(HY_ERR_INVALID, "%s: the dictionary lives on device %d, the calling thread works on device %d", entry_point, dict->device, this_thread_device());
   const uint64_t total = dict->entry_offsets[dict->n_chunks];
   if (total >= (uint64_t{1} << 31)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu dictionary entries do not fit int32 ranks", entry_point, static_cast<unsigned long long>(total));
   return HY_OK;
+}
+
+// The refusals of a string column and the dictionaries of its data column, before any launch and any allocation
+hy_status string_column_check(const hy_column* column, const hy_string_dictionary* dict, const char* entry_point) {
+  HY_TRY(on_this_device(column, entry_point));
+  if (column->is_mvcc || (column->data_type != HY_TYPE_STRING && column->n_chunks)) return fail(HY_ERR_INVALID, "%s: not a string column (type %u)", entry_point, column->data_type);
+  HY_TRY(check_dictionary(dict, column, "", entry_point));
+  return column_order_check(dict, entry_point);
 }
 
 hy_status string_order_check(const hy_string_dictionary* left, const hy_string_dictionary* right, const char* entry_point) {
@@ -305,6 +269,42 @@ hy_status string_order_launch(const hy_string_dictionary* left, const hy_string_
   profile_events(&started, &stopped, HY_KERNEL_STRING_RANK);
   hipExtLaunchKernelGGL(string_rank, dim3(static_cast<uint32_t>(left->blocks.size())), dim3(RANK_WG), 0, stream, started, stopped, 0, args);
   HY_HIP(hipGetLastError());
+  return HY_OK;
+}
+
+// The int32 stand-in of a string column (a data column, or a reference column over one) over a table of E int32_t in device memory: entry v
+// of data chunk c reads table[entry_offsets[c] + v].  The data stand-in has DictionarySegment<int32> chunks over the caller's attribute
+// vectors, whatever their width or packing, with the NULL value id still aux_size; a reference column gets the same PosLists over it, and
+// owns it (hy_column::stand_in).  The table stays the caller's.
+hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, int32_t* d_table, hy_column** out) {
+  *out = nullptr;
+  const hy_column* data_column = column->is_reference ? column->ref : column;
+  const uint32_t n_data_chunks = data_column->n_chunks;
+  std::vector<hy_segment> segments(data_column->host_segments);
+  for (uint32_t c = 0; c < n_data_chunks; ++c) {
+    segments[c].data_type = HY_TYPE_INT;
+    segments[c].aux = d_table + dict->entry_offsets[c];
+  }
+  hy_column* stand_in = nullptr;
+  HY_TRY(hy_column_create(segments.data(), n_data_chunks, HY_MEM_DEVICE, &stand_in));
+  hy_column* result = stand_in;
+  if (column->is_reference) {   // the same PosLists over the stand-in
+    segments = column->host_segments;
+    for (hy_segment& segment : segments) {
+      segment.data_type = HY_TYPE_INT;
+      segment.ref = stand_in;
+      // (an uploaded PosList without rows has no device buffer: as a descriptor over device memory it reads as an entire-chunk list, whose
+      // chunk id must exist -- of no rows, so which chunk does not matter)
+      if (!segment.data && !segment.size && n_data_chunks && segment.ref_chunk_id >= n_data_chunks) segment.ref_chunk_id = 0;
+    }
+    const hy_status status = hy_column_create(segments.data(), column->n_chunks, HY_MEM_DEVICE, &result);
+    if (status != HY_OK) {
+      (void)hy_column_destroy(stand_in);
+      return status;
+    }
+    result->stand_in = stand_in;
+  }
+  *out = result;
   return HY_OK;
 }
 
@@ -370,12 +370,7 @@ hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictio
   if (!out) return fail(HY_ERR_INVALID, "%s: null output", name);
   *out = nullptr;
   if (!column || !dict) return fail(HY_ERR_INVALID, "%s: null argument", name);
-  HY_TRY(on_this_device(column, name));
-  if (column->is_mvcc || (column->data_type != HY_TYPE_STRING && column->n_chunks)) return fail(HY_ERR_INVALID, "%s: not a string column (type %u)", name, column->data_type);
-  HY_TRY(check_dictionary(dict, column, "", name));
-  HY_TRY(column_order_check(dict, name));
-  const hy_column* data_column = column->is_reference ? column->ref : column;
-  const uint32_t n_data_chunks = data_column->n_chunks;
+  HY_TRY(string_column_check(column, dict, name));
   const uint64_t total = dict->entry_offsets[dict->n_chunks];
 
   // the ranks: a buffer the stand-in owns (16 bytes of slack behind the last rank, like every dictionary of a column)
@@ -394,30 +389,10 @@ hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictio
     if (status == HY_OK) status = column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream);
     if (status != HY_OK) return give_up(status);
   }
-  // the data stand-in: DictionarySegment<int32> over the caller's attribute vectors, whatever their width or packing
-  std::vector<hy_segment> segments(data_column->host_segments);
-  for (uint32_t c = 0; c < n_data_chunks; ++c) {
-    segments[c].data_type = HY_TYPE_INT;
-    segments[c].aux = d_ranks + dict->entry_offsets[c];
-  }
-  hy_column* stand_in = nullptr;
-  hy_status status = hy_column_create(segments.data(), n_data_chunks, HY_MEM_DEVICE, &stand_in);
+  hy_column* result = nullptr;
+  hy_status status = string_stand_in(column, dict, d_ranks, &result);
   if (status != HY_OK) return give_up(status);
-  stand_in->owned.push_back(d_ranks);
-  hy_column* result = stand_in;
-  if (column->is_reference) {   // the same PosLists over the stand-in
-    segments = column->host_segments;
-    for (hy_segment& segment : segments) {
-      segment.data_type = HY_TYPE_INT;
-      segment.ref = stand_in;
-    }
-    status = hy_column_create(segments.data(), column->n_chunks, HY_MEM_DEVICE, &result);
-    if (status != HY_OK) {
-      (void)hy_column_destroy(stand_in);
-      return status;
-    }
-    result->stand_in = stand_in;
-  }
+  (result->stand_in ? result->stand_in : result)->owned.push_back(d_ranks);
   // (the dictionary may die as soon as the call has returned: nothing queued reads it any more)
   const hipError_t err = hipStreamSynchronize(stream);
   if (err != hipSuccess) {

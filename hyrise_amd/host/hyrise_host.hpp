@@ -157,6 +157,9 @@ struct DeviceBlock {
 // Hands every operator's device results to the next operator without a host copy (default).  false: the operators ask the library for
 // HY_MEM_HOST results, as rounds 1-5 did -- tests compare the two.
 inline bool& device_resident_results() { static bool enabled = true; return enabled; }
+// AggregateHash's string outputs -- string GROUP BY columns, MIN / MAX / ANY over a string column -- are made in HBM (hy_string_column_gather,
+// hy_string_ranks_gather) where the column is wholly dictionary-encoded; false: on the host, from the representative RowIDs and the ranks.
+inline bool& device_string_results() { static bool enabled = true; return enabled; }
 
 class DevicePosList : public AbstractPosList {
  public:
@@ -310,27 +313,77 @@ class DictionarySegment : public AbstractSegment {   // storage/dictionary_segme
   DictionarySegment(std::vector<T> dictionary, CompressedVector attribute_vector, ChunkOffset size)
       : AbstractSegment(data_type_of<T>()), _dictionary(std::move(dictionary)), _attribute_vector(std::move(attribute_vector)), _size(size) {}
   ChunkOffset size() const override { return _size; }
-  const std::vector<T>& dictionary() const { return _dictionary; }
-  const CompressedVector& attribute_vector() const { return _attribute_vector; }
-  uint32_t unique_values_count() const { return static_cast<uint32_t>(_dictionary.size()); }
+  const std::vector<T>& dictionary() const { materialize(); return _dictionary; }
+  const CompressedVector& attribute_vector() const { materialize(); return _attribute_vector; }
+  uint32_t unique_values_count() const { materialize(); return static_cast<uint32_t>(_dictionary.size()); }
   uint32_t lower_bound(const T& value) const {   // dictionary_segment.cpp:94-106
+    materialize();
     const auto it = std::lower_bound(_dictionary.begin(), _dictionary.end(), value);
     return it == _dictionary.end() ? HY_INVALID_VALUE_ID : static_cast<uint32_t>(it - _dictionary.begin());
   }
   uint32_t upper_bound(const T& value) const {   // :108-119
+    materialize();
     const auto it = std::upper_bound(_dictionary.begin(), _dictionary.end(), value);
     return it == _dictionary.end() ? HY_INVALID_VALUE_ID : static_cast<uint32_t>(it - _dictionary.begin());
   }
   AllTypeVariant operator[](ChunkOffset offset) const override {
+    materialize();
     const auto vid = _attribute_vector.get(offset);
     if (vid >= _dictionary.size()) return NullValue{};
     return _dictionary[vid];
   }
 
- private:
-  std::vector<T> _dictionary;
-  CompressedVector _attribute_vector;
+ protected:
+  virtual void materialize() const {}   // (DeviceStringDictionarySegment: the dictionary and the attribute vector are fetched on first use)
+  mutable std::vector<T> _dictionary;
+  mutable CompressedVector _attribute_vector;
   ChunkOffset _size;
+};
+
+// A DictionarySegment<pmr_string> whose attribute vector and dictionary lie in HBM: chunk `chunk_index` of the pair that hy_string_column_gather /
+// hy_string_ranks_gather made (AggregateHash's string outputs).  The next operator takes the two handles (device_column_of_chunks,
+// device_string_dictionary) and uploads nothing; code that reads the segment as a DictionarySegment gets a host copy, fetched once on first
+// use and counted.  Both handles die with the last segment.
+struct DeviceStringResult {
+  DeviceStringResult(hy_column* column_handle, hy_string_dictionary* dictionary_handle) : column(std::make_shared<const DeviceColumnOwner>(column_handle)), dictionary(dictionary_handle) {}
+  DeviceStringResult(const DeviceStringResult&) = delete;
+  DeviceStringResult& operator=(const DeviceStringResult&) = delete;
+  ~DeviceStringResult() { if (dictionary) hy_string_dictionary_destroy(dictionary); }
+  std::shared_ptr<const DeviceColumnOwner> column;
+  hy_string_dictionary* dictionary;
+};
+inline std::atomic<uint64_t>& device_string_segment_fetches() { static std::atomic<uint64_t> fetches{0}; return fetches; }
+
+class DeviceStringDictionarySegment : public DictionarySegment<std::string> {
+ public:
+  DeviceStringDictionarySegment(std::shared_ptr<const DeviceStringResult> result, uint32_t chunk_index, ChunkOffset size)
+      : DictionarySegment<std::string>({}, CompressedVector{}, size), _result(std::move(result)), _chunk_index(chunk_index) {}
+  const std::shared_ptr<const DeviceStringResult>& result() const { return _result; }
+  const std::shared_ptr<const DeviceColumnOwner>& owner() const { return _result->column; }
+  uint32_t chunk_index() const { return _chunk_index; }
+
+ protected:
+  void materialize() const override {
+    std::call_once(_once, [&] {
+      uint32_t n_entries = 0;
+      uint64_t chars_bytes = 0;
+      check_status(hy_string_dictionary_chunk_size(_result->dictionary, _chunk_index, &n_entries, &chars_bytes));
+      std::string chars(chars_bytes, '\0');
+      std::vector<uint32_t> offsets(size_t{n_entries} + 1, 0), value_ids(std::max<size_t>(1, _size), 0);
+      check_status(hy_string_dictionary_read_chunk(_result->dictionary, _chunk_index, chars.data(), offsets.data()));
+      if (_size) check_status(hy_column_read_chunk(_result->column->handle, _chunk_index, value_ids.data(), nullptr));
+      value_ids.resize(_size);
+      _dictionary.clear();
+      for (uint32_t v = 0; v < n_entries; ++v) _dictionary.emplace_back(chars, offsets[v], offsets[v + 1] - offsets[v]);
+      _attribute_vector = CompressedVector::compress(value_ids, n_entries);
+      device_string_segment_fetches().fetch_add(1, std::memory_order_relaxed);
+    });
+  }
+
+ private:
+  std::shared_ptr<const DeviceStringResult> _result;
+  uint32_t _chunk_index;
+  mutable std::once_flag _once;
 };
 
 class FrameOfReferenceSegment : public AbstractSegment {   // storage/frame_of_reference_segment.hpp:37-98
@@ -774,7 +827,8 @@ enum class StringKeys { None, AggregateKeyNames, JoinIds, Ranks };
 // The dictionaries of a string column's DictionarySegment chunks in HBM (hy_string_dictionary): what the LIKE matcher reads on the device.
 struct DeviceStringDictionary {
   hy_string_dictionary* handle = nullptr;
-  ~DeviceStringDictionary() { if (handle) hy_string_dictionary_destroy(handle); }
+  std::shared_ptr<const DeviceStringResult> resident;   // `handle` is the dictionary of a column an operator left in HBM: its segments own it
+  ~DeviceStringDictionary() { if (handle && !resident) hy_string_dictionary_destroy(handle); }
 };
 struct ColumnCache {
   std::map<std::pair<ColumnID, StringKeys>, std::shared_ptr<DeviceColumn>> columns;
@@ -869,7 +923,9 @@ inline std::shared_ptr<DeviceColumn> device_column_of_chunks(const std::shared_p
                                                              ChunkID chunk_end) {
   auto column = std::make_shared<DeviceColumn>();
   const auto chunk_count = chunk_end - chunk_begin;
-  if (const auto resident = resident_column_of_chunks(*table, column_id, chunk_begin, chunk_end)) {   // every chunk of one hy_column in HBM: that handle, as it is
+  // (a string column whose dictionary is to be replaced by key names, join ids or host ranks is read through its segments, fetched)
+  const bool as_it_is = string_keys == StringKeys::None || table->column_data_type(column_id) != DataType::String;
+  if (const auto resident = as_it_is ? resident_column_of_chunks(*table, column_id, chunk_begin, chunk_end) : nullptr) {   // every chunk of one hy_column in HBM: that handle, as it is
     column->resident = resident;
     column->handle = resident->handle;
     return column;
@@ -989,6 +1045,7 @@ inline std::shared_ptr<const DeviceColumnOwner> resident_column_of_chunks(const 
     look(dynamic_cast<const DeviceValueSegment<int64_t>*>(segment));
     look(dynamic_cast<const DeviceValueSegment<float>*>(segment));
     look(dynamic_cast<const DeviceValueSegment<double>*>(segment));
+    look(dynamic_cast<const DeviceStringDictionarySegment*>(segment));
     if (!of_segment || index != k - chunk_begin || (owner && owner != of_segment)) return nullptr;
     owner = of_segment;
   }
@@ -1032,6 +1089,24 @@ inline std::shared_ptr<DeviceStringDictionary> device_string_dictionary(const st
   auto& slot = table->device_columns->string_dictionaries[column_id];
   if (slot) return slot;
   const auto chunk_count = table->chunk_count();
+  {   // every chunk of one gathered column: its dictionary, where it lies
+    std::shared_ptr<const DeviceStringResult> resident;
+    bool whole = chunk_count > 0;
+    for (ChunkID c = 0; c < chunk_count && whole; ++c) {
+      const auto* segment = dynamic_cast<const DeviceStringDictionarySegment*>(table->get_chunk(c)->get_segment(column_id).get());
+      whole = segment && segment->chunk_index() == c && (!resident || resident == segment->result());
+      if (whole) resident = segment->result();
+    }
+    uint32_t chunks_of_column = 0;
+    if (whole) check_status(hy_column_chunk_count(resident->column->handle, &chunks_of_column));
+    if (whole && chunks_of_column == chunk_count) {
+      auto dictionary = std::make_shared<DeviceStringDictionary>();
+      dictionary->handle = resident->dictionary;
+      dictionary->resident = resident;
+      slot = dictionary;
+      return slot;
+    }
+  }
   std::vector<std::string> chars(chunk_count);
   std::vector<std::vector<uint32_t>> offsets(chunk_count);
   std::vector<hy_string_dictionary_chunk> chunks(chunk_count);
@@ -1054,23 +1129,32 @@ inline std::shared_ptr<DeviceStringDictionary> device_string_dictionary(const st
 // one column of such chunks.  The column goes to the device as it does for a scan (value ids alone, or PosLists over them), its data
 // column's dictionaries as they do for LIKE, and hy_column_string_ranks orders them in HBM and hands back the int32 stand-in, which reads the
 // string column's buffers in place.  nullptr: not such a column, or the library refused it -- the caller ranks on the host.
-inline std::shared_ptr<DeviceColumn> device_string_rank_column(const std::shared_ptr<const Table>& table, ColumnID column_id) {
+// Is the column a string column whose every chunk is a DictionarySegment<pmr_string>, or a ReferenceSegment over one column of such chunks?
+// Then data_table / data_column_id name the column that holds the dictionaries.
+inline bool string_dictionary_column(const std::shared_ptr<const Table>& table, ColumnID column_id, std::shared_ptr<const Table>& data_table, ColumnID& data_column_id) {
   const auto chunk_count = table->chunk_count();
-  if (chunk_count == 0 || table->column_data_type(column_id) != DataType::String) return nullptr;
-  std::shared_ptr<const Table> data_table = table;
-  ColumnID data_column_id = column_id;
+  if (chunk_count == 0 || table->column_data_type(column_id) != DataType::String) return false;
+  data_table = table;
+  data_column_id = column_id;
   if (const auto* first = dynamic_cast<const ReferenceSegment*>(table->get_chunk(0)->get_segment(column_id).get())) {
     data_table = first->referenced_table();
     data_column_id = first->referenced_column_id();
     for (ChunkID k = 0; k < chunk_count; ++k) {
       const auto* segment = dynamic_cast<const ReferenceSegment*>(table->get_chunk(k)->get_segment(column_id).get());
-      if (!segment || segment->referenced_table() != data_table || segment->referenced_column_id() != data_column_id) return nullptr;
+      if (!segment || segment->referenced_table() != data_table || segment->referenced_column_id() != data_column_id) return false;
     }
   }
-  if (data_table->chunk_count() == 0) return nullptr;
+  if (data_table->chunk_count() == 0) return false;
   for (ChunkID k = 0; k < data_table->chunk_count(); ++k) {
-    if (!dynamic_cast<const DictionarySegment<std::string>*>(data_table->get_chunk(k)->get_segment(data_column_id).get())) return nullptr;
+    if (!dynamic_cast<const DictionarySegment<std::string>*>(data_table->get_chunk(k)->get_segment(data_column_id).get())) return false;
   }
+  return true;
+}
+
+inline std::shared_ptr<DeviceColumn> device_string_rank_column(const std::shared_ptr<const Table>& table, ColumnID column_id) {
+  std::shared_ptr<const Table> data_table;
+  ColumnID data_column_id = column_id;
+  if (!string_dictionary_column(table, column_id, data_table, data_column_id)) return nullptr;
   auto column = std::make_shared<DeviceColumn>();
   column->strings = device_column(table, column_id, StringKeys::None);
   const auto dictionary = device_string_dictionary(data_table, data_column_id);
@@ -2765,6 +2849,7 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
     std::vector<const hy_column*> groupby;
     for (const auto id : _groupby) { keep.push_back(device_column(input, id, input->column_data_type(id) == DataType::String ? StringKeys::AggregateKeyNames : StringKeys::None)); groupby.push_back(keep.back()->handle); }
     std::vector<hy_aggregate_spec> specs;
+    bool string_aggregates = false;   // MIN / MAX / ANY over a string column: their output segments are made by resident_output
     for (const auto& aggregate : _aggregates) {
       hy_aggregate_spec spec{};
       spec.function = static_cast<uint32_t>(aggregate.function);
@@ -2772,8 +2857,19 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
         // SUM / AVG / STDDEV_SAMP of strings are invalid (aggregate_test.cpp:232-262 expects std::logic_error)
         const bool arithmetic = aggregate.function == WindowFunction::Sum || aggregate.function == WindowFunction::Avg || aggregate.function == WindowFunction::StandardDeviationSample;
         Assert(!(arithmetic && input->column_data_type(aggregate.column_id) == DataType::String), "Aggregate function not available for strings.");
-        keep.push_back(device_column(input, aggregate.column_id));
-        spec.column = keep.back()->handle;
+        const bool of_strings = input->column_data_type(aggregate.column_id) == DataType::String;
+        if (of_strings && (aggregate.function == WindowFunction::Min || aggregate.function == WindowFunction::Max)) {
+          // MIN / MAX of strings are MIN / MAX of their ranks among the column's distinct strings (made in HBM, or on the host: device_string_ranking)
+          keep.push_back(device_column(input, aggregate.column_id, StringKeys::Ranks));
+          spec.column = keep.back()->handle;
+          string_aggregates = true;
+        } else if (of_strings && aggregate.function == WindowFunction::Any) {
+          spec.function = HY_AGG_COUNT;   // (a placeholder, COUNT(*): ANY is the value at the group's representative row)
+          string_aggregates = true;
+        } else {
+          keep.push_back(device_column(input, aggregate.column_id));
+          spec.column = keep.back()->handle;
+        }
       } else {
         Assert(aggregate.function == WindowFunction::Count, "Only COUNT may have an invalid ColumnID.");   // aggregate_hash.cpp:1002
       }
@@ -2788,7 +2884,7 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
       lone_spec.column = keep.back()->handle;
       call_specs.push_back(lone_spec);
     }
-    if (device_resident_results()) return resident_output(*input, groupby, specs, call_specs);
+    if (device_resident_results() || string_aggregates) return resident_output(input, groupby, specs, call_specs);
     // Room for a group per input row, as the one call may need -- but not TOUCHED: value-initialised vectors of that size were 0.8 GB of page
     // faults (a quarter of a second) in front of an aggregate over 26 M joined rows that produces three groups.
     const uint32_t capacity = static_cast<uint32_t>(input->row_count() + 1);
@@ -2852,8 +2948,14 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
   // The output table in HBM (hy_aggregate_hash_columns): same column definitions and chunking as the host path below builds cell by cell, the
   // numeric segments DeviceValueSegments over the library's output columns -- the next operator's device_column() hands the handles on.
   // String GROUP BY columns (passed as key names: the library makes no column for them) are read on the host through the representative rows.
-  std::shared_ptr<const Table> resident_output(const Table& input, const std::vector<const hy_column*>& groupby, const std::vector<hy_aggregate_spec>& specs,
+  std::shared_ptr<const Table> resident_output(const std::shared_ptr<const Table>& input_table, const std::vector<const hy_column*>& groupby, const std::vector<hy_aggregate_spec>& specs,
                                                const std::vector<hy_aggregate_spec>& call_specs) const {
+    const Table& input = *input_table;
+    const auto string_aggregate = [&](size_t a) {
+      const auto& aggregate = _aggregates[a];
+      return aggregate.column_id != INVALID_COLUMN_ID && input.column_data_type(aggregate.column_id) == DataType::String &&
+             (aggregate.function == WindowFunction::Min || aggregate.function == WindowFunction::Max || aggregate.function == WindowFunction::Any);
+    };
     std::vector<hy_column*> aggregate_handles(std::max<size_t>(1, call_specs.size()), nullptr), groupby_handles(std::max<size_t>(1, groupby.size()), nullptr);
     hy_aggregate_columns result{};
     for (size_t g = 0; g < _groupby.size() && g < 64; ++g) if (input.column_data_type(_groupby[g]) == DataType::String) result.skip_groupby_mask |= uint64_t{1} << g;
@@ -2876,6 +2978,7 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
       else if (aggregate.function == WindowFunction::Avg || aggregate.function == WindowFunction::StandardDeviationSample) type = DataType::Double;
       else if (aggregate.function == WindowFunction::Sum) type = is_float ? DataType::Double : DataType::Long;
       if (result.n_groups) type = static_cast<DataType>(hy_column_data_type(aggregate_handles[a]));
+      if (string_aggregate(a)) type = DataType::String;   // (the handle holds ranks, or ANY's placeholder)
       result_types.push_back(type);
     }
     TableColumnDefinitions definitions = output_definitions(input, result_types);
@@ -2896,6 +2999,53 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
         default: return std::make_shared<DeviceValueSegment<double>>(owner, chunk, size);
       }
     };
+    // String outputs made in HBM (device_string_results): a column of the input at the representative rows (a string GROUP BY column, ANY),
+    // or the strings behind an aggregate's ranks (MIN / MAX).  nullptr: the host makes the column -- the switch is off, the column is not
+    // wholly dictionary-encoded, or the library refused.
+    const auto gathered_at_rows = [&](ColumnID column_id) -> std::shared_ptr<const DeviceStringResult> {
+      std::shared_ptr<const Table> data_table;
+      ColumnID data_column_id = column_id;
+      if (!device_string_results() || !n_groups || !string_dictionary_column(input_table, column_id, data_table, data_column_id)) return nullptr;
+      const auto column = device_column(input_table, column_id);
+      const auto dictionary = device_string_dictionary(data_table, data_column_id);
+      hy_column* made = nullptr;
+      hy_string_dictionary* made_dictionary = nullptr;
+      const auto status = hy_string_column_gather(column->handle, dictionary->handle, result.group_row_ids, n_groups, Chunk::DEFAULT_SIZE, &made, &made_dictionary);
+      if (status == HY_ERR_UNSUPPORTED) return nullptr;
+      check_status(status);
+      return std::make_shared<const DeviceStringResult>(made, made_dictionary);
+    };
+    const auto strings_of_ranks = [&](ColumnID column_id, const hy_column* ranks) -> std::shared_ptr<const DeviceStringResult> {
+      std::shared_ptr<const Table> data_table;
+      ColumnID data_column_id = column_id;
+      if (!device_string_results() || !n_groups || !string_dictionary_column(input_table, column_id, data_table, data_column_id)) return nullptr;
+      if (hy_column_data_type(ranks) != HY_TYPE_INT) return nullptr;   // (int64 ranks the host made: device_string_ranking() is off)
+      const auto dictionary = device_string_dictionary(data_table, data_column_id);
+      hy_column* made = nullptr;
+      hy_string_dictionary* made_dictionary = nullptr;
+      const auto status = hy_string_ranks_gather(dictionary->handle, ranks, &made, &made_dictionary);
+      if (status == HY_ERR_UNSUPPORTED) return nullptr;
+      check_status(status);
+      return std::make_shared<const DeviceStringResult>(made, made_dictionary);
+    };
+    std::vector<std::shared_ptr<const DeviceStringResult>> groupby_strings(_groupby.size()), aggregate_strings(specs.size());
+    std::vector<std::vector<std::string>> rank_orders(specs.size());   // MIN / MAX on the host: the distinct strings of the column, in byte order
+    for (size_t g = 0; g < _groupby.size(); ++g) if (!groupby_owners[g] && definitions[g].data_type == DataType::String) groupby_strings[g] = gathered_at_rows(_groupby[g]);
+    for (size_t a = 0; a < specs.size(); ++a) {
+      if (!string_aggregate(a)) continue;
+      const bool any = _aggregates[a].function == WindowFunction::Any;
+      aggregate_strings[a] = any ? gathered_at_rows(_aggregates[a].column_id) : strings_of_ranks(_aggregates[a].column_id, aggregate_handles[a]);
+      if (aggregate_strings[a] || any) continue;
+      std::shared_ptr<const Table> data_table;
+      ColumnID data_column_id = _aggregates[a].column_id;
+      Assert(string_dictionary_column(input_table, _aggregates[a].column_id, data_table, data_column_id) || !n_groups, "MIN / MAX over strings: unencoded string segments stay on the CPU path");
+      for (ChunkID k = 0; n_groups && k < data_table->chunk_count(); ++k) {
+        const auto& dictionary = static_cast<const DictionarySegment<std::string>&>(*data_table->get_chunk(k)->get_segment(data_column_id)).dictionary();
+        rank_orders[a].insert(rank_orders[a].end(), dictionary.begin(), dictionary.end());
+      }
+      std::sort(rank_orders[a].begin(), rank_orders[a].end());
+      rank_orders[a].erase(std::unique(rank_orders[a].begin(), rank_orders[a].end()), rank_orders[a].end());
+    }
     std::vector<std::shared_ptr<Chunk>> chunks;
     for (uint64_t begin = 0; begin < n_groups; begin += Chunk::DEFAULT_SIZE) {
       const auto chunk = static_cast<uint32_t>(begin / Chunk::DEFAULT_SIZE);
@@ -2904,6 +3054,7 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
       for (size_t g = 0; g < _groupby.size(); ++g) {
         const auto& definition = definitions[g];
         if (groupby_owners[g]) { segments.push_back(resident_segment(definition.data_type, groupby_owners[g], chunk, size)); continue; }
+        if (groupby_strings[g]) { segments.push_back(std::make_shared<DeviceStringDictionarySegment>(groupby_strings[g], chunk, size)); continue; }
         std::vector<std::vector<AllTypeVariant>> cells;
         for (uint64_t r = begin; r < begin + size; ++r) cells.push_back({(*input.get_chunk(host_rows()[r].chunk_id)->get_segment(_groupby[g]))[host_rows()[r].chunk_offset]});
         switch (definition.data_type) {
@@ -2914,7 +3065,25 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
           default: segments.push_back(make_value_segment<std::string>(cells, ColumnID{0}, definition.nullable)); break;
         }
       }
-      for (size_t a = 0; a < specs.size(); ++a) segments.push_back(resident_segment(definitions[_groupby.size() + a].data_type, aggregate_owners[a], chunk, size));
+      for (size_t a = 0; a < specs.size(); ++a) {
+        if (!string_aggregate(a)) { segments.push_back(resident_segment(definitions[_groupby.size() + a].data_type, aggregate_owners[a], chunk, size)); continue; }
+        if (aggregate_strings[a]) { segments.push_back(std::make_shared<DeviceStringDictionarySegment>(aggregate_strings[a], chunk, size)); continue; }
+        std::vector<std::vector<AllTypeVariant>> cells;
+        if (_aggregates[a].function == WindowFunction::Any) {
+          for (uint64_t r = begin; r < begin + size; ++r) cells.push_back({(*input.get_chunk(host_rows()[r].chunk_id)->get_segment(_aggregates[a].column_id))[host_rows()[r].chunk_offset]});
+        } else {   // the chunk's ranks (int32 made on the device, int64 made on the host) read back, every rank its string
+          const bool wide = static_cast<DataType>(hy_column_data_type(aggregate_handles[a])) == DataType::Long;
+          std::vector<int64_t> ranks(size);
+          std::vector<uint64_t> null_words((size_t{size} + 63) / 64, 0);
+          check_status(hy_column_read_chunk(aggregate_handles[a], chunk, ranks.data(), null_words.data()));
+          for (ChunkOffset r = 0; r < size; ++r) {
+            const int64_t rank = wide ? ranks[r] : reinterpret_cast<const int32_t*>(ranks.data())[r];
+            if ((null_words[r / 64] >> (r % 64)) & 1) cells.push_back({AllTypeVariant{NullValue{}}});
+            else cells.push_back({AllTypeVariant{rank_orders[a].at(static_cast<size_t>(rank))}});
+          }
+        }
+        segments.push_back(make_value_segment<std::string>(cells, ColumnID{0}, true));
+      }
       chunks.push_back(std::make_shared<Chunk>(std::move(segments)));
     }
     return std::make_shared<Table>(std::move(definitions), TableType::Data, std::move(chunks));

@@ -349,6 +349,82 @@ def column_string_ranks(dev_column, dev_dict):
     return StringRankColumn(handle, (dev_column, dev_dict))
 
 
+class StringResultColumn:
+    """A dictionary-encoded string column the library made in HBM (hy_string_column_gather / hy_string_ranks_gather) with the
+    DeviceStringDictionary that belongs to it: usable wherever a string DeviceColumn and its dictionary are."""
+
+    def __init__(self, handle, dict_handle):
+        from .storage import DeviceStringDictionary
+        self.lib = abi.load_library()
+        self.handle = handle
+        rows, chunks = C.c_uint64(0), C.c_uint32(0)
+        abi.check(self.lib.hy_column_row_count(handle, C.byref(rows)))
+        abi.check(self.lib.hy_column_chunk_count(handle, C.byref(chunks)))
+        self.rows, self.n_chunks, self.data_type = int(rows.value), int(chunks.value), abi.TYPE_STRING
+        self.dictionary = DeviceStringDictionary.adopt(dict_handle, self.n_chunks)
+
+    def read_value_ids(self):
+        """Per chunk the uint32 attribute vector, copied back."""
+        out = []
+        for chunk in range(self.n_chunks):
+            ids = np.zeros(int(self.lib.hy_column_chunk_rows(self.handle, chunk)), dtype=np.uint32)
+            abi.check(self.lib.hy_column_read_chunk(self.handle, chunk, ids.ctypes.data if len(ids) else np.zeros(1, np.uint32).ctypes.data, None))
+            out.append(ids)
+        return out
+
+    def read(self):
+        """The rows as Python bytes, None for NULL: every chunk's dictionary and attribute vector copied back."""
+        rows = []
+        for chunk, ids in enumerate(self.read_value_ids()):
+            entries = self.dictionary.read_chunk(chunk)[0]
+            rows += [entries[v] if v < len(entries) else None for v in ids.tolist()]
+        return rows
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.hy_column_destroy(self.handle)
+            self.handle = None
+        if getattr(self, "dictionary", None):
+            self.dictionary.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def string_column_gather(column, dictionary, positions, chunk_rows):
+    """hy_string_column_gather: the rows of a string DeviceColumn (data or reference column; `dictionary`: the DeviceStringDictionary of its
+    data column) at `positions` -- an (n, 2) uint32 array of RowIDs, uploaded, or (device pointer, n) -- as a StringResultColumn."""
+    lib = abi.load_library()
+    handle, dict_handle = C.c_void_p(), C.c_void_p()
+    if isinstance(positions, tuple):
+        pointer, n = positions
+        abi.check(lib.hy_string_column_gather(column.handle, dictionary.handle, pointer, n, chunk_rows, C.byref(handle), C.byref(dict_handle)))
+        return StringResultColumn(handle, dict_handle)
+    positions = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1, 2)
+    n = len(positions)
+    pointer = C.c_void_p()
+    abi.check(lib.hy_device_malloc(C.byref(pointer), max(16, 8 * n)))
+    try:
+        if n:
+            abi.check(lib.hy_memcpy_h2d(pointer, positions.ctypes.data, 8 * n))
+        abi.check(lib.hy_string_column_gather(column.handle, dictionary.handle, pointer, n, chunk_rows, C.byref(handle), C.byref(dict_handle)))
+    finally:
+        lib.hy_device_free(pointer)
+    return StringResultColumn(handle, dict_handle)
+
+
+def string_ranks_gather(dictionary, ranks):
+    """hy_string_ranks_gather: the strings that an int32 column of dense ranks over `dictionary` stands for (MIN / MAX over a stand-in of
+    column_string_ranks) as a StringResultColumn with `ranks`' chunk layout."""
+    lib = abi.load_library()
+    handle, dict_handle = C.c_void_p(), C.c_void_p()
+    abi.check(lib.hy_string_ranks_gather(dictionary.handle, ranks.handle, C.byref(handle), C.byref(dict_handle)))
+    return StringResultColumn(handle, dict_handle)
+
+
 def table_scan_columns_strings(left, left_dict, right, right_dict, condition, flags=0, device=False):
     """hy_table_scan_columns_strings: `left <condition> right` over two string columns of one table and their dictionaries (for reference
     columns: the referenced data columns') -> HostScanResult like table_scan_columns, or with device=True the chunk-region result in

@@ -372,6 +372,31 @@ class DeviceStringDictionary:
         self.word_offsets = np.zeros(self.n_chunks + 1, dtype=np.uint64)
         abi.check(self.lib.hy_string_dictionary_match_layout(self.handle, self.word_offsets.ctypes.data))
 
+    @classmethod
+    def adopt(cls, handle, n_chunks):
+        """A handle the library made (hy_string_column_gather / hy_string_ranks_gather): n_chunks offsets-layout chunks whose buffers it owns."""
+        self = cls.__new__(cls)
+        self.lib = abi.load_library()
+        self.handle, self.fixed_length, self.packed, self.n_chunks = handle, None, None, n_chunks
+        n_entries, chars_bytes = C.c_uint32(0), C.c_uint64(0)
+        self.n_entries = []
+        for chunk in range(n_chunks):
+            abi.check(self.lib.hy_string_dictionary_chunk_size(handle, chunk, C.byref(n_entries), C.byref(chars_bytes)))
+            self.n_entries.append(int(n_entries.value))
+        self.word_offsets = np.zeros(n_chunks + 1, dtype=np.uint64)
+        abi.check(self.lib.hy_string_dictionary_match_layout(handle, self.word_offsets.ctypes.data))
+        return self
+
+    def read_chunk(self, chunk):
+        """hy_string_dictionary_read_chunk: the entries of an offsets-layout chunk as a list of bytes, plus the raw (chars, offsets) arrays."""
+        n_entries, chars_bytes = C.c_uint32(0), C.c_uint64(0)
+        abi.check(self.lib.hy_string_dictionary_chunk_size(self.handle, chunk, C.byref(n_entries), C.byref(chars_bytes)))
+        chars = np.zeros(int(chars_bytes.value), dtype=np.uint8)
+        offsets = np.zeros(int(n_entries.value) + 1, dtype=np.uint32)
+        abi.check(self.lib.hy_string_dictionary_read_chunk(self.handle, chunk, chars.ctypes.data if len(chars) else None, offsets.ctypes.data))
+        raw = chars.tobytes()
+        return [raw[offsets[v]:offsets[v + 1]] for v in range(int(n_entries.value))], chars, offsets
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.hy_string_dictionary_destroy(self.handle)

@@ -553,6 +553,47 @@ hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_d
 hy_status hy_string_dictionary_order(const hy_string_dictionary* dict, uint32_t mem, int32_t* ranks, uint32_t* n_distinct);
 hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictionary* dict, hy_column** out);
 
+/* ---- String columns made on the device (what AggregateHash's string GROUP BY columns, MIN / MAX / ANY over strings, and the materialised
+ * string columns of Sort / Projection need: the way from RowIDs, or from ranks, back to strings) ----------------------------------------
+ * Both calls write a NEW dictionary-encoded string column in HBM: *result is a column of HY_TYPE_STRING dictionary segments whose attribute
+ * vectors are FixedWidthInteger uint32_t (a NULL row holds value id n_entries of its chunk, dictionary_segment.cpp:139-141), in one pooled
+ * arena owned by the column under hy_column_gather's alignment rules; *result_dict has one offsets-layout chunk per output chunk: the
+ * DISTINCT strings of that chunk's non-NULL rows in std::string order (bytes as unsigned, a prefix first, a '\0' inside an entry is data;
+ * entries of fixed-slot source chunks end at strnlen).  Equal strings that sit in different source chunks are ONE output entry; an output
+ * chunk of NULL rows only has n_entries == 0.  The pair is what hy_table_scan (value ids), hy_table_scan_like, hy_column_string_ranks and
+ * hy_table_scan_columns_strings read.  *result_dict is owned by the library (hy_string_dictionary_destroy) and depends on none of the
+ * inputs after the call has returned.  The output is fully determined by the input, byte for byte.
+ * On the device: the source dictionary is ranked (hy_string_dictionary_order's launches), the rows are ordered by (output chunk, rank) with
+ * two stable word sorts, head flags and a prefix sum give value ids and each chunk's entries, a 64-bit scan of the entries' lengths gives the
+ * offsets, and a byte-parallel copy (16 output bytes per lane) writes the chars.  The host learns per output chunk the entry count and the
+ * chars' bytes, in one copy of 16 bytes per chunk: no string byte and no per-row word crosses to it.  Temporaries come from the thread's
+ * scratch arena and buffer pool; the launches are timed under HY_KERNEL_STRING_RANK.
+ *
+ * hy_string_column_gather   the rows of `column` at `positions`.  `column`: a data column of string dictionary segments, or a reference
+ *   column over one; `dict`: the dictionaries of the DATA column, checked as hy_column_string_ranks checks them; positions: n RowIDs of
+ *   `column`'s table in device memory, on 8 bytes (a NULL RowID, or one outside the table -- every RowID into a table without rows --, gives a NULL row).
+ *   *result has ceil(n / chunk_rows) chunks, the last one shorter.  n == 0: HY_OK, a column and a dictionary of zero chunks, no launch.
+ *   HY_ERR_INVALID: a null argument, chunk_rows == 0, a column that is no string column, a dictionary that disagrees with the
+ *   data column's segments or lives on another device, positions off an 8-byte boundary.  HY_ERR_UNSUPPORTED: unencoded or LZ4 string
+ *   segments, E >= 2^31 dictionary entries, n >= 2^32, an output chunk whose chars would take 2^32 bytes or more (known only after the
+ *   lengths are summed on the device: the call then frees everything it took).  All other refusals come before any launch and any
+ *   allocation.  On every error both out pointers are NULL and nothing stays allocated.
+ *
+ * hy_string_ranks_gather   the strings an int32 column of dense ranks stands for: `ranks` is an HY_TYPE_INT data column of unencoded
+ *   segments (what hy_aggregate_hash_columns writes for MIN / MAX over a stand-in of hy_column_string_ranks), `dict` the dictionaries the
+ *   ranks were made from.  *result has `ranks`' chunk layout; row r is NULL where `ranks` is NULL or holds a value outside
+ *   0 .. n_distinct - 1 (nothing outside the buffers is read for it), else a string whose dense rank in `dict` is that value.  The refusals
+ *   mirror those above. */
+hy_status hy_string_column_gather(const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, uint32_t chunk_rows,
+                                  hy_column** result, hy_string_dictionary** result_dict);
+hy_status hy_string_ranks_gather(const hy_string_dictionary* dict, const hy_column* ranks, hy_column** result, hy_string_dictionary** result_dict);
+/* An offsets-layout chunk of a dictionary read back, whether the library owns its buffers (an upload, a gather's result) or the caller:
+ * chunk_size gives n_entries and the bytes of its chars (offsets[n_entries]); read_chunk copies the n_entries + 1 offsets as they are and the
+ * chars' bytes [0, offsets[n_entries]) to host memory (chars may be NULL when there are none).  A fixed-slot chunk with entries:
+ * HY_ERR_UNSUPPORTED from both (the caller holds those bytes).  A chunk index past the end or a null pointer: HY_ERR_INVALID. */
+hy_status hy_string_dictionary_chunk_size(const hy_string_dictionary* dict, uint32_t chunk, uint32_t* n_entries, uint64_t* chars_bytes);
+hy_status hy_string_dictionary_read_chunk(const hy_string_dictionary* dict, uint32_t chunk, char* chars, uint32_t* offsets);
+
 /* ---- Validate (replaces Validate::_on_execute / _validate_chunks, validate.cpp:32-55,87-314) ----
  * The MVCC visibility filter that sits in front of every TableScan of an SQL-driven plan.  The table's MvccData
  * (storage/mvcc_data.hpp) is passed as one "column" of HY_ENC_MVCC segments, one per chunk:
@@ -691,7 +732,9 @@ typedef struct hy_operand {
 } hy_operand;
 hy_status hy_projection_arithmetic(uint32_t op, const hy_operand* left, const hy_operand* right, hy_column** result);
 /* Copies one chunk of an unencoded device-resident column to host memory: values[rows] of the column's type and, if
- * null_words is not NULL, the null bitmap (bit i of word i/64; rows/64 rounded up words). */
+ * null_words is not NULL, the null bitmap (bit i of word i/64; rows/64 rounded up words).  A chunk of a dictionary-encoded STRING column
+ * gives its attribute vector instead: rows value ids of 1, 2 or 4 bytes (hy_string_column_gather's results: 4), NULL rows as the NULL
+ * value id and the bitmap zero. */
 hy_status hy_column_read_chunk(const hy_column* column, uint32_t chunk, void* values, uint64_t* null_words);
 uint32_t hy_column_data_type(const hy_column* column);
 uint32_t hy_column_chunk_rows(const hy_column* column, uint32_t chunk);
