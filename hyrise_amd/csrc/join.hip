@@ -3976,6 +3976,7 @@ static uint32_t device_cu_count() {
 #include "join_star.hpp"
 
 static thread_local int t_last_join_used_rank_table = 0;   // debug / tests: which lookup structure the thread's last join built
+static thread_local int t_last_join_compact_stage = 0;     // ... with 4-byte staged records in pk_emit
 static thread_local int t_last_join_used_pkfk = 0;         // ... and whether the kernels of join_pkfk.hpp probed it
 static thread_local int t_last_join_hinted_attempt = 0;
 static thread_local int t_last_join_hinted = 0;            // ... 1: the build side was filled from the column's key hint, 2: that attempt was discarded and the join ran again
@@ -4306,6 +4307,8 @@ static hy_status raise_pk_emit_lds() {
     HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
     HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
     HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS, true)));
+    HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pk_emit<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * pk_emit_lds_words(MAX_PARTITIONS, true)));
     raised.done(device_bit);
   }
   return HY_OK;
@@ -4390,8 +4393,22 @@ static hy_status launch_pk_count(const JoinRequest& q, const BuildSide& b, PkBuf
   return HY_OK;
 }
 
+// May pk_emit stage 4-byte records (join_pk_stage.hpp)?  Only over the rank table in memory, and only where EVERY segment of the probe
+// column is FrameOfReference with offsets of 1 or 2 bytes: then a wave's keys, and with them its partners' ranks, span fewer than 65 536
+// values whatever the data is.  One 4-byte or unencoded segment anywhere keeps the whole launch on the 8-byte records.
+static bool probe_stages_compact(const JoinRequest& q, bool build_in_lds, bool hand_over_ranks) {
+  if (build_in_lds || hand_over_ranks || !option(HY_OPT_JOIN_COMPACT_STAGE) || q.radix_bits > PK_COMPACT_MAX_RADIX_BITS) return false;
+  const hy_column* probe = q.probe;
+  for (uint32_t c = 0; c < probe->n_chunks; ++c) {
+    const hy_segment& seg = probe->host_segments[c];
+    if (seg.encoding != HY_ENC_FRAME_OF_REFERENCE || (seg.width != 1 && seg.width != 2)) return false;
+  }
+  return probe->n_chunks > 0;
+}
+
 // Pass 2: the flavour of pk_emit that matches pass 1 (the rows' found / materialised bits of pk_count_lds, the ranks of pk_count<true>),
-// Inner or not; its first workgroups cut the PosLists, and it clears the zeroed filter the join before used (FillCleaning).
+// Inner or not, with 4-byte staged records where the probe column allows; its first workgroups cut the PosLists, and it clears the zeroed
+// filter the join before used (FillCleaning).
 static hy_status launch_pk_emit(const JoinRequest& q, BuildSide& b, PkArgs& k, bool build_in_lds, bool hand_over_ranks, uint32_t max_slices, hipStream_t stream) {
   HY_TRY(raise_pk_emit_lds());
   hipEvent_t started = nullptr, stopped = nullptr;   // (stamped from the dispatch packet itself)
@@ -4403,15 +4420,19 @@ static hy_status launch_pk_emit(const JoinRequest& q, BuildSide& b, PkArgs& k, b
   k.cut_blocks = (cut_grid + 7) / 8 * 8;   // (pk_cut_slice returns at once for slices the plan does not have)
   k.cleaning = b.cleaning;
   const dim3 grid(k.cut_blocks + 8 * ((k.n_tiles + 7) / 8));
-  const size_t lds_bytes = 4 * pk_emit_lds_words(1u << q.radix_bits);
+  const bool compact = probe_stages_compact(q, build_in_lds, hand_over_ranks);
+  const size_t lds_bytes = 4 * pk_emit_lds_words(1u << q.radix_bits, compact);
   const bool inner = q.mode == HY_JOIN_INNER;
-  if (build_in_lds && inner) hipExtLaunchKernelGGL((pk_emit<true, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  if (compact && inner) hipExtLaunchKernelGGL((pk_emit<true, false, false, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  else if (compact) hipExtLaunchKernelGGL((pk_emit<false, false, false, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
+  else if (build_in_lds && inner) hipExtLaunchKernelGGL((pk_emit<true, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
   else if (build_in_lds) hipExtLaunchKernelGGL((pk_emit<false, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
   else if (hand_over_ranks) hipExtLaunchKernelGGL((pk_emit<true, false, true>), grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
   else if (inner) hipExtLaunchKernelGGL(pk_emit<true>, grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
   else hipExtLaunchKernelGGL(pk_emit<false>, grid, dim3(PK_THREADS), lds_bytes, stream, started, stopped, 0, k);
   HY_HIP(hipGetLastError());
   block_cleaning_queued(b);
+  t_last_join_compact_stage = compact ? 1 : 0;
   t_last_join_used_pkfk = build_in_lds ? 2 : 1;   // debug / tests: the primary-key / foreign-key kernels ran (2: with the build side's bits staged in LDS)
   return HY_OK;
 }
@@ -4659,6 +4680,7 @@ static hy_status run_join_once(const hy_column* left, const hy_column* right, ui
   const bool rank_path = b.rank.entries != nullptr;
   t_last_join_used_rank_table = rank_path ? (b.rank.identity_rows ? 2 : 1) : 0;
   t_last_join_used_pkfk = 0;
+  t_last_join_compact_stage = 0;
   t_last_join_hinted_attempt = b.hinted ? 1 : 0;
   clock.mark("build side launched");
   if (result) {
@@ -4852,6 +4874,9 @@ int hy_debug_join_build_was_hinted(void) { return t_last_join_hinted; }
 
 // debug / tests only: 1 = the last join of this thread ran pk_count / pk_scan / pk_emit / pk_cuts (join_pkfk.hpp), 2 = pk_count_lds / pk_emit<., true>
 int hy_debug_join_used_pkfk(void) { return t_last_join_used_pkfk; }
+
+// debug / tests only: 1 = the last join of this thread ran pk_emit's compact flavour (4-byte staged records, three workgroups per CU), else 0
+int hy_debug_join_compact_stage(void) { return t_last_join_compact_stage; }
 
 // debug only (HY_JOIN_TRACE): the per-tile phase stamps of the last join's probe_emit; not part of the public header
 int hy_debug_join_trace(uint64_t* out, uint32_t capacity_tiles) {

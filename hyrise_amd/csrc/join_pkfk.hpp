@@ -25,18 +25,9 @@
 // HBM traffic at config 3: 2 x probe keys + 16 B per pair + 3 x 4 B per (partition, tile) cell.
 #pragma once
 
-#ifndef HY_PK_TILE
-#define HY_PK_TILE 8192
-#endif
-#ifndef HY_PK_WAVES_PER_SIMD
-#define HY_PK_WAVES_PER_SIMD 4   // pk_emit: workgroups per CU x waves per workgroup / 4 (the register budget: 512 / this)
-#endif
-constexpr uint32_t PK_TILE = HY_PK_TILE;                 // rows per probe tile: a slice (8192) or half a slice (-DHY_PK_TILE=4096: A/B builds)
+#include "join_pk_stage.hpp"   // PK_TILE .. PK_WAVE_ROWS, pk_emit's LDS footprint, the compact staged record
+
 constexpr uint32_t PK_TILES_PER_SLICE = SLICE_ROWS / PK_TILE;
-constexpr uint32_t PK_ROUNDS = 16;                       // rows per lane
-constexpr uint32_t PK_THREADS = PK_TILE / PK_ROUNDS;     // 512
-constexpr uint32_t PK_WAVES = PK_THREADS / 64;           // 8
-constexpr uint32_t PK_WAVE_ROWS = PK_TILE / PK_WAVES;    // 1024 consecutive rows per wave
 constexpr uint32_t PK_COUNT_WAVE_ROWS = 2048;            // pk_count: one FrameOfReference block per wave
 constexpr uint32_t PK_COUNT_THREADS = 64 * (PK_TILE / PK_COUNT_WAVE_ROWS);   // 256
 constexpr uint32_t PK_COUNT_BATCHES = PK_COUNT_WAVE_ROWS / 512;              // 4 batches of 512 rows, eight consecutive rows per lane
@@ -44,7 +35,6 @@ constexpr uint32_t PK_SCAN_THREADS = 512;
 constexpr uint32_t PK_SCAN_CHUNK = 8192;                 // tiles per pass of pk_scan's loop (config 3's 7 323 tiles: one pass)
 static_assert(SLICE_ROWS % PK_TILE == 0 && HY_FOR_BLOCK_SIZE % PK_WAVE_ROWS == 0 && HY_FOR_BLOCK_SIZE == PK_COUNT_WAVE_ROWS && PK_TILE % PK_COUNT_WAVE_ROWS == 0,
               "a wave's rows must lie in one FrameOfReference block");
-static_assert(PK_TILE <= (1u << 13), "a staged pair keeps its row in 13 bits");
 
 struct PkArgs {
   const SliceView* views;          // the probe column's slices; a tile is a slice or (PK_TILES_PER_SLICE == 2) half of one
@@ -718,12 +708,13 @@ __device__ __forceinline__ void pk_tile_rows_of_width(const PkArgs& a, const Sli
   pk_lookup_rows<WIDTH, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
 }
 
-// The one place that asks for the tile's kind (the same for every lane of the workgroup).
-template <bool INNER, bool STAGE, bool MASKS = false, bool RANKS = false>
+// The one place that asks for the tile's kind (the same for every lane of the workgroup).  NARROW: the host has seen that every segment
+// of the column is stored 1 or 2 bytes wide (pk_emit's compact flavour) -- the 4-byte specialisation is not instantiated.
+template <bool INNER, bool STAGE, bool MASKS = false, bool RANKS = false, bool NARROW = false>
 __device__ __forceinline__ void pk_tile_rows(const PkArgs& a, const SliceView& view, uint32_t* block, uint32_t wave, uint32_t lane, uint32_t (&meta)[PK_ROUNDS], uint32_t (&rank)[PK_ROUNDS],
                                              PkStageTarget& target, const uint8_t* tile_masks = nullptr, const uint32_t* tile_ranks = nullptr) {
   if (view.kind == VIEW_FOR8) pk_tile_rows_of_width<1, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
-  else if (view.kind == VIEW_FOR16) pk_tile_rows_of_width<2, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
+  else if (NARROW || view.kind == VIEW_FOR16) pk_tile_rows_of_width<2, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
   else pk_tile_rows_of_width<4, INNER, STAGE, MASKS, RANKS>(a, view, block, wave, lane, meta, rank, target, tile_masks, tile_ranks);
 }
 
@@ -736,21 +727,10 @@ __device__ __forceinline__ void pk_evaluate(const PkArgs& a, const SliceView& vi
 }
 
 // ---- pass 2 -------------------------------------------------------------------------------------------------------------------
-// LDS, in 4-byte words: staged pairs {row | null partner << 21 (never set by an Inner join), partner's rank} (one spare slot per
-// partition, see rt_probe_emit) | pairs per (wave, partition), then the first slot of (wave, partition); after the staging the
-// copy-out's line table (PK_TILE / 16 lines x 2 words) in the same words | global pair index of staging slot 0 per partition | first
-// global pair index of the run per partition, then its first interior line (bits 16..) and its pairs (bits 0..15) | wave totals of
-// the partition scan, reserved slots and interior lines.
+// Its LDS and the two forms of a staged pair: join_pk_stage.hpp.  The 8-byte form is {row | null partner << 21 (never set by an Inner
+// join), partner's rank} (one spare slot per partition, see rt_probe_emit).
 constexpr uint32_t PK_STAGE_ROW = 0x1FFF, PK_STAGE_NULL = 1u << 21;
-constexpr uint32_t PK_LINES = PK_TILE / 16;   // 128-byte output lines of 16 pairs a tile's pairs can fill
-__host__ __device__ constexpr size_t pk_wave_pairs_words(uint32_t partitions) {
-  return size_t{PK_WAVES} * partitions > 2 * size_t{PK_LINES} ? size_t{PK_WAVES} * partitions : 2 * size_t{PK_LINES};
-}
-__host__ __device__ constexpr size_t pk_emit_lds_words(uint32_t partitions) {
-  return 2 * (size_t{PK_TILE} + partitions + 2) + pk_wave_pairs_words(partitions) + 3 * size_t{partitions} + 32;
-}
-static_assert(PK_LINES == PK_THREADS, "the copy-out's line table is filled thread = line");
-static_assert(2 * PK_LINES <= PK_WAVES * 256, "the line table must not make 256 partitions' LDS larger");
+static_assert(MAX_PARTITIONS == 1u << PK_COMPACT_MAX_RADIX_BITS, "join_pk_stage.hpp sizes the compact flavour's LDS for the widest radix");
 
 // Interior lines of a run: the 128-byte lines (16 pairs, counted on the global pair index) wholly inside [base, base + pairs).
 __device__ __forceinline__ uint32_t pk_first_line(uint32_t base) { return (base >> 4) + ((base & 15) != 0 ? 1u : 0u); }
@@ -782,10 +762,10 @@ __device__ __forceinline__ u32x2_t pk_rank_row(const PkArgs& a, uint32_t r) {
 
 // The build side's RowID of a staged pair (a null partner: {-1, -1}; Inner joins have none).
 template <bool INNER, int BUILD>
-__device__ __forceinline__ u32x2_t pk_build_row(const PkArgs& a, uint32_t tag, uint32_t r) {
+__device__ __forceinline__ u32x2_t pk_build_row(const PkArgs& a, bool null_partner, uint32_t r) {
   if constexpr (INNER) return pk_rank_row<BUILD>(a, r);
   u32x2_t row = {0xFFFFFFFFu, 0xFFFFFFFFu};
-  if (!(tag & PK_STAGE_NULL)) row = pk_rank_row<BUILD>(a, r);
+  if (!null_partner) row = pk_rank_row<BUILD>(a, r);
   return row;
 }
 
@@ -797,8 +777,16 @@ __device__ __forceinline__ u32x2_t pk_build_row(const PkArgs& a, uint32_t tag, u
 // wave per partition writes them with 8-byte write-back stores, so that the partial lines merge in the XCD's L2 instead of reaching HBM
 // as two masked writes each.  (Parity-matched staging: a line's first slot is even, its 16-byte pieces are aligned.)  The copy-out it
 // replaced picked one of three store paths per lane -- 8 stores and 73 VALU / 43 SALU for two slots a lane.
-template <bool INNER, int BUILD>
-__device__ __forceinline__ void pk_copy_out(const PkArgs& a, const u32x2_t* s_stage, u32x2_t* s_line, const uint32_t* s_out_base, const uint32_t* s_run, uint32_t partitions,
+// COMPACT: the staged records are 4 bytes (join_pk_stage.hpp), a two-record piece is 8 aligned bytes, and a record's rank is its delta
+// on the rank base of the wave that staged it -- s_wave_base[row >> 10], one LDS read over eight addresses.
+struct PkStagedPair { uint32_t row; bool null_partner; uint32_t rank; };
+template <bool COMPACT>
+__device__ __forceinline__ PkStagedPair pk_staged_pair(uint32_t first, uint32_t second, const uint32_t* s_wave_base) {
+  if constexpr (COMPACT) return PkStagedPair{pk_compact_row(first), pk_compact_null(first), pk_compact_rank(first, s_wave_base[pk_compact_wave(first)])};
+  else return PkStagedPair{first & PK_STAGE_ROW, (first & PK_STAGE_NULL) != 0, second};
+}
+template <bool INNER, int BUILD, bool COMPACT>
+__device__ __forceinline__ void pk_copy_out(const PkArgs& a, const std::conditional_t<COMPACT, uint32_t, u32x2_t>* s_stage, const uint32_t* s_wave_base, u32x2_t* s_line, const uint32_t* s_out_base, const uint32_t* s_run, uint32_t partitions,
                                             uint32_t lines, uint32_t chunk, uint32_t tile_row_begin, uint32_t tid, uint32_t lane, uint32_t wave) {
   u32x2_t* probe_out = reinterpret_cast<u32x2_t*>(a.probe_out);
   u32x2_t* build_out = reinterpret_cast<u32x2_t*>(a.build_out);
@@ -826,37 +814,76 @@ __device__ __forceinline__ void pk_copy_out(const PkArgs& a, const u32x2_t* s_st
     const uint32_t pair_index = interior && i >= 16 ? 16 * end + (i - 16) : base + i;
     const bool edge = interior ? (i < 16 ? pair_index < 16 * first : pair_index < base + pairs) : i < pairs;
     if (edge) {
-      const u32x2_t record = s_stage[pair_index - s_out_base[p]];
-      probe_out[pair_index] = u32x2_t{chunk, tile_row_begin + (record.x & PK_STAGE_ROW)};
-      if constexpr (BUILD != BUILD_NONE) build_out[pair_index] = pk_build_row<INNER, BUILD>(a, record.x, record.y);
+      PkStagedPair pair;
+      if constexpr (COMPACT) pair = pk_staged_pair<true>(s_stage[pair_index - s_out_base[p]], 0u, s_wave_base);
+      else { const u32x2_t record = s_stage[pair_index - s_out_base[p]]; pair = pk_staged_pair<false>(record.x, record.y, nullptr); }
+      probe_out[pair_index] = u32x2_t{chunk, tile_row_begin + pair.row};
+      if constexpr (BUILD != BUILD_NONE) build_out[pair_index] = pk_build_row<INNER, BUILD>(a, pair.null_partner, pair.rank);
     }
   }
   __syncthreads();   // s_line
   for (uint32_t piece = tid; piece < 8 * lines; piece += PK_THREADS) {
     const u32x2_t line = s_line[piece >> 3];
     const uint32_t offset = 2 * (piece & 7);
-    const u32x4_t records = *reinterpret_cast<const u32x4_t*>(s_stage + line.x + offset);
+    PkStagedPair pair0, pair1;
+    if constexpr (COMPACT) {
+      const u32x2_t records = *reinterpret_cast<const u32x2_t*>(s_stage + line.x + offset);
+      pair0 = pk_staged_pair<true>(records.x, 0u, s_wave_base);
+      pair1 = pk_staged_pair<true>(records.y, 0u, s_wave_base);
+    } else {
+      const u32x4_t records = *reinterpret_cast<const u32x4_t*>(s_stage + line.x + offset);
+      pair0 = pk_staged_pair<false>(records.x, records.y, nullptr);
+      pair1 = pk_staged_pair<false>(records.z, records.w, nullptr);
+    }
     const size_t pair_pos = line.y + offset;
-    __builtin_nontemporal_store(u32x4_t{chunk, tile_row_begin + (records.x & PK_STAGE_ROW), chunk, tile_row_begin + (records.z & PK_STAGE_ROW)},
-                                reinterpret_cast<u32x4_t*>(probe_out + pair_pos));
+    __builtin_nontemporal_store(u32x4_t{chunk, tile_row_begin + pair0.row, chunk, tile_row_begin + pair1.row}, reinterpret_cast<u32x4_t*>(probe_out + pair_pos));
     if constexpr (BUILD != BUILD_NONE) {
-      const u32x2_t build0 = pk_build_row<INNER, BUILD>(a, records.x, records.y), build1 = pk_build_row<INNER, BUILD>(a, records.z, records.w);
+      const u32x2_t build0 = pk_build_row<INNER, BUILD>(a, pair0.null_partner, pair0.rank), build1 = pk_build_row<INNER, BUILD>(a, pair1.null_partner, pair1.rank);
       __builtin_nontemporal_store(u32x4_t{build0.x, build0.y, build1.x, build1.y}, reinterpret_cast<u32x4_t*>(build_out + pair_pos));
     }
   }
 }
 
 // One tile from its stored words to its pairs in the output.  The five phases are separated by four workgroup barriers.
-template <bool INNER, bool MASKS = false, bool RANKS = false>
+// The rank base of a wave's compact records: the smallest rank among the wave's rows that have a partner -- a minimum per lane over the
+// sixteen rounds, four DPP steps inside the rows of 16 lanes, the four rows' values through the scalar unit.  (Not the rank the block
+// minimum would have: the table keeps an entry only for words that hold a key, so a key that is absent has no rank to ask for.)
+// Rows with a partner: ranked on a (wave, partition) counter and no null partner.  An Anti join's rows pass too, with whatever their
+// lookup left as a rank: it writes no build side, nothing reads the base.  No such row in the wave: 0xFFFFFFFF, equally unread.
+__device__ __forceinline__ uint32_t pk_wave_min(uint32_t v) {
+#define HY_PK_MIN_STEP(CTRL) v = min(v, static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(v), static_cast<int>(v), CTRL, 0xF, 0xF, false)))
+  HY_PK_MIN_STEP(0xB1);    // quad_perm [1, 0, 3, 2]
+  HY_PK_MIN_STEP(0x4E);    // quad_perm [2, 3, 0, 1]
+  HY_PK_MIN_STEP(0x141);   // row_half_mirror
+  HY_PK_MIN_STEP(0x140);   // row_mirror
+#undef HY_PK_MIN_STEP
+  const uint32_t row01 = min(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 0)), static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 16)));
+  const uint32_t row23 = min(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 32)), static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 48)));
+  return min(row01, row23);
+}
+template <bool INNER>
+__device__ __forceinline__ uint32_t pk_wave_rank_base(const uint32_t (&counter)[PK_ROUNDS], const uint32_t (&rank)[PK_ROUNDS], const PkStageTarget& target) {
+  uint32_t lowest = 0xFFFFFFFFu;
+#pragma unroll
+  for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
+    const bool partner = counter[k] != target.spare && (INNER || !((target.null_partners >> k) & 1));
+    lowest = min(lowest, partner ? rank[k] : 0xFFFFFFFFu);
+  }
+  return pk_wave_min(lowest);
+}
+
+template <bool INNER, bool MASKS = false, bool RANKS = false, bool COMPACT = false>
 __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, const SliceView& view, uint32_t cell_pairs, uint32_t cell_base,
                                              uint32_t* join_smem, uint32_t tid, uint32_t lane, uint32_t wave) {
   const uint32_t partitions = 1u << a.radix_bits;
   const uint32_t stage_slots = PK_TILE + partitions + 2;
-  u32x2_t* s_stage = reinterpret_cast<u32x2_t*>(join_smem);                      // [stage_slots]
-  uint32_t* s_wave_pairs = reinterpret_cast<uint32_t*>(s_stage + stage_slots);   // [PK_WAVES][partitions]; in (e) the line table [PK_LINES] of {slot, pair index}
+  static_assert(!COMPACT || (!MASKS && !RANKS), "compact records: the rank table in memory (a table staged in LDS reaches 2^20 ranks under one base)");
+  typedef std::conditional_t<COMPACT, uint32_t, u32x2_t> staged_record;
+  staged_record* s_stage = reinterpret_cast<staged_record*>(join_smem);          // [stage_slots]
+  uint32_t* s_wave_pairs = join_smem + pk_stage_words(partitions, COMPACT);      // [PK_WAVES][partitions]; in (e) the line table [PK_LINES] of {slot, pair index}
   uint32_t* s_out_base = s_wave_pairs + pk_wave_pairs_words(partitions);         // [partitions]
   uint32_t* s_run = s_out_base + partitions;                                     // [2][partitions] first global pair index of the run | first interior line << 16 | pairs
-  uint32_t* s_scratch = s_run + 2 * partitions;                                  // [4] wave totals of the partition scan, [8] reserved slots | interior lines << 16, [16 + wave] a counter for rows without a pair
+  uint32_t* s_scratch = s_run + 2 * partitions;                                  // [4] wave totals of the partition scan, [8] reserved slots | interior lines << 16, [16 + wave] a counter for rows without a pair, [24 + wave] (COMPACT) the wave's rank base
   const uint32_t scan_waves = partitions > 64 ? partitions / 64 : 1;
   if (a.trace && tid == 0) a.trace[tile * 6 + 0] = wall_clock64();
   for (uint32_t i = tid; i < PK_WAVES * partitions; i += PK_THREADS) s_wave_pairs[i] = 0;
@@ -866,8 +893,10 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   uint32_t counter[PK_ROUNDS], rank[PK_ROUNDS];
   PkStageTarget target = {pk_lds_address(s_wave_pairs + wave * partitions), pk_lds_address(s_scratch + 16 + wave), 0u};
   // (the rows' words go round through the staging area, which is not in use yet: 4 KB of it per wave)
-  pk_tile_rows<INNER, true, MASKS, RANKS>(a, view, join_smem + wave * 1024, wave, lane, counter, rank, target, MASKS ? a.row_masks + static_cast<size_t>(tile) * (2 * PK_TILE / 8) : nullptr,
+  pk_tile_rows<INNER, true, MASKS, RANKS, COMPACT>(a, view, join_smem + wave * 1024, wave, lane, counter, rank, target, MASKS ? a.row_masks + static_cast<size_t>(tile) * (2 * PK_TILE / 8) : nullptr,
                                           RANKS ? a.row_ranks + static_cast<size_t>(tile) * PK_TILE : nullptr);
+  uint32_t rank_base = 0;
+  if constexpr (COMPACT) rank_base = pk_wave_rank_base<INNER>(counter, rank, target);
   __builtin_amdgcn_wave_barrier();
   if (a.trace && tid == 0) a.trace[tile * 6 + 1] = wall_clock64();
   // (a) reserve pairs + 1 slots per non-empty partition, and number its interior lines: scan inside each wave now, across waves in (c)
@@ -926,16 +955,26 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   // add and a shift per row.  Rows without a pair write the slot behind every run -- their "first slot" is that slot already, the
   // minimum takes what (b) handed back off again: no compare, no select, no branch.  An Inner join's record is {row, rank}, the
   // others add the null-partner bit.
+  // COMPACT: one word a record -- the rank as its delta on the wave's rank base, which the copy-out finds in s_scratch[24 + wave].
   const uint32_t first_row = wave * PK_WAVE_ROWS + lane;
+  if constexpr (COMPACT) { if (lane == 0) s_scratch[24 + wave] = rank_base; }
   uint32_t first_slot[PK_ROUNDS];
 #pragma unroll
   for (uint32_t k = 0; k < PK_ROUNDS; ++k) first_slot[k] = *pk_lds_pointer(counter[k]);
 #pragma unroll
   for (uint32_t k = 0; k < PK_ROUNDS; ++k) {
     const uint32_t slot = first_slot[k] + before[k] < stage_slots - 1 ? first_slot[k] + before[k] : stage_slots - 1;
-    uint32_t tag = first_row + k * 64;
-    if constexpr (!INNER) tag |= ((target.null_partners >> k) & 1) ? PK_STAGE_NULL : 0u;
-    s_stage[slot] = u32x2_t{tag, rank[k]};
+    if constexpr (COMPACT) {
+      const uint32_t null_partner = INNER ? 0u : (target.null_partners >> k) & 1;
+#ifdef HY_DEBUG_SWITCHES   // 0 <= rank - base < 65 536 for every row with a partner (join_pk_stage.hpp); Semi / Anti joins write no build side
+      if (!(slot == stage_slots - 1 || null_partner || !a.build_out || rank[k] - rank_base < 65536u)) __builtin_trap();
+#endif
+      s_stage[slot] = pk_compact_pack(first_row + k * 64, null_partner, rank[k] - rank_base);
+    } else {
+      uint32_t tag = first_row + k * 64;
+      if constexpr (!INNER) tag |= ((target.null_partners >> k) & 1) ? PK_STAGE_NULL : 0u;
+      s_stage[slot] = u32x2_t{tag, rank[k]};
+    }
   }
   __syncthreads();
   if (a.trace && tid == 0) a.trace[tile * 6 + 4] = wall_clock64();
@@ -943,7 +982,7 @@ __device__ __forceinline__ void pk_emit_tile(const PkArgs& a, uint32_t tile, con
   // no `s_waitcnt vmcnt(0)` per iteration, which would also wait for every store in flight)
   const uint32_t lines = s_scratch[8] >> 16;
   const uint32_t chunk = view.chunk, row_begin = view.row_begin;
-#define HY_PK_COPY(BUILD) pk_copy_out<INNER, BUILD>(a, s_stage, reinterpret_cast<u32x2_t*>(s_wave_pairs), s_out_base, s_run, partitions, lines, chunk, row_begin, tid, lane, wave)
+#define HY_PK_COPY(BUILD) pk_copy_out<INNER, BUILD, COMPACT>(a, s_stage, s_scratch + 24, reinterpret_cast<u32x2_t*>(s_wave_pairs), s_out_base, s_run, partitions, lines, chunk, row_begin, tid, lane, wave)
   if (!a.build_out) HY_PK_COPY(BUILD_NONE);
   else if (a.rank.identity_rows == 65535u) HY_PK_COPY(BUILD_IDENTITY_65535);
   else if (a.rank.identity_rows) HY_PK_COPY(BUILD_IDENTITY);
@@ -1014,9 +1053,11 @@ __global__ __launch_bounds__(PK_THREADS) void pk_cuts(PkArgs a) {
   pk_cut_slice(a, blockIdx.x, s_cut, tid, tid & 63, __builtin_amdgcn_readfirstlane(tid >> 6));
 }
 
-// One tile per workgroup (2 workgroups per CU overlap each other's phases).
-template <bool INNER, bool MASKS = false, bool RANKS = false>
-__global__ __launch_bounds__(PK_THREADS, HY_PK_WAVES_PER_SIMD) void pk_emit(PkArgs a) {
+// One tile per workgroup (2 workgroups per CU overlap each other's phases; 3 of the Inner COMPACT flavour, whose LDS is a good half and
+// whose 73 VGPRs fit the budget of 80.  The other modes' COMPACT flavour spills three registers to scratch under that budget: it keeps
+// the two workgroups its 8-byte form has, and the narrower LDS instructions.)
+template <bool INNER, bool MASKS = false, bool RANKS = false, bool COMPACT = false>
+__global__ __launch_bounds__(PK_THREADS, COMPACT && INNER ? HY_PK_COMPACT_WAVES_PER_SIMD : HY_PK_WAVES_PER_SIMD) void pk_emit(PkArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t join_smem[];
   const uint32_t partitions = 1u << a.radix_bits;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1044,6 +1085,6 @@ __global__ __launch_bounds__(PK_THREADS, HY_PK_WAVES_PER_SIMD) void pk_emit(PkAr
   const size_t cell = static_cast<size_t>(tid < partitions ? tid : 0) * a.stride + tile;
   const uint32_t cell_pairs = tid < partitions ? a.counts[cell] >> 16 : 0;
   const uint32_t cell_base = static_cast<uint32_t>(a.origin_pairs[tid < partitions ? tid : 0]) + a.rel_pairs[cell];
-  pk_emit_tile<INNER, MASKS, RANKS>(a, tile, view, cell_pairs, cell_base, join_smem, tid, lane, wave);
+  pk_emit_tile<INNER, MASKS, RANKS, COMPACT>(a, tile, view, cell_pairs, cell_base, join_smem, tid, lane, wave);
 }
 

@@ -34,6 +34,7 @@ struct OptionDefaults {
     set(HY_OPT_STAR_FUSED_PROBE, 1);
     set(HY_OPT_STAR_FUSED_FINISH, 1);
     set(HY_OPT_LDS_ORDERED_ATOMICS, 1);
+    set(HY_OPT_JOIN_COMPACT_STAGE, 1);
   }
 };
 OptionDefaults g_option_defaults;   // (static initialisation: before any entry point can run)

@@ -306,7 +306,10 @@ enum {
                                       *      rank_table_scatter_rows, the general rank-table kernels, match-any ranking)                             */
   HY_OPT_PRODUCT_NONTEMPORAL = 17,  /* 0    hy_product writes its 16-byte vectors with nontemporal stores (1) or through the write-back L2 (0);
                                       *      tools/product_timing.py times one against the other in one process                                  */
-  HY_OPT_COUNT = 18
+  HY_OPT_JOIN_COMPACT_STAGE = 18,   /* 1    pk_emit stages 4-byte records (row, null partner, rank as a 16-bit delta on its wave's rank base) where every
+                                      *      segment of the probe column is stored 1 or 2 bytes wide: three workgroups per CU instead of two;
+                                      *      0 = the 8-byte records everywhere                                                                  */
+  HY_OPT_COUNT = 19
   /* (rounds 4-5 had 33: launch shapes and store flavours whose A/B timings were flat twice are constants now -- csrc/hy_options.hpp --,
    *  the radix-partitioned join path, which lost to the rank table read in place by 1.7 x, is gone) */
 };
