@@ -19,7 +19,8 @@
 //                    is 4 groups x 6 aggregates per workgroup instead of 8192 x 6 global atomics.  Rows whose group
 //                    does not fit the LDS table go to the global table directly.
 //   compact_groups   occupied global slots -> dense arrays.
-// The host then orders the groups exactly like the reference (first-row rank, or key order) and derives AVG.
+// The host then orders the groups exactly like the reference (first-row rank, or key order) and derives AVG (finish_on_host; large results
+// of plain aggregates: finish_on_device).  Host side: resolve_aggregate_request -> main_groups / device_groups -> a finish.
 // SUM/AVG over float/double columns use f64 atomics: the additions happen in a different order than the reference's
 // sequential loop, so those results are compared with a stated tolerance (1e-9 relative); everything else is exact.
 #include "hy_device.hpp"
@@ -2523,14 +2524,16 @@ __global__ __launch_bounds__(256) void finish_column_chunks(const uint32_t* orde
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
+static bool is_float_type(uint32_t type) { return type == HY_TYPE_FLOAT || type == HY_TYPE_DOUBLE; }
+static size_t value_width(uint32_t type) { return type == HY_TYPE_INT || type == HY_TYPE_FLOAT ? 4 : 8; }
+
 static uint32_t result_type(uint32_t function, uint32_t input_type) {   // window_function_traits.hpp:11-77
-  const bool is_float = input_type == HY_TYPE_FLOAT || input_type == HY_TYPE_DOUBLE;
   switch (function) {
     case HY_AGG_COUNT:
     case HY_AGG_COUNT_DISTINCT: return HY_TYPE_LONG;
     case HY_AGG_AVG:
     case HY_AGG_STDDEV_SAMP: return HY_TYPE_DOUBLE;
-    case HY_AGG_SUM: return is_float ? HY_TYPE_DOUBLE : HY_TYPE_LONG;
+    case HY_AGG_SUM: return is_float_type(input_type) ? HY_TYPE_DOUBLE : HY_TYPE_LONG;
     default: return input_type;
   }
 }
@@ -2562,160 +2565,200 @@ struct RowIdOf {
   }
 };
 
+// (a group's accumulator arrays hold one entry where there is no aggregate: DISTINCT, COUNT(DISTINCT)'s inner grouping)
+static uint32_t accumulators_per_group(uint32_t n_aggregates) { return n_aggregates ? n_aggregates : 1; }
+// one slot of a workgroup's LDS table: tuple, first / last row, accumulators (value, count as 32 bits), tag
+static size_t lds_slot_bytes(uint32_t words, uint32_t n_aggregates) { return 8 * size_t{words} + 16 + 12 * size_t{n_aggregates} + 4; }
+
 // What the device table holds after one pass over the table: the groups' tuples, first / last rows and accumulators.
 struct DeviceGroups {
   uint32_t n_groups = 0;
   uint64_t passed_rows = 0;   // fused_rows: rows that passed the filters
   std::vector<uint64_t> keys, first, last, values, counts;
-  // Large results whose caller finishes them on the device (finish_groups_on_device): the same five arrays stay in device memory.
-  bool keep_on_device = false;   // in: leave more than STAGED_GROUPS groups where they are
-  bool on_device = false;        // out
+  // Large results whose caller finishes them on the device (finish kernels above): the same five arrays stay in device memory.
+  bool on_device = false;
   DeviceBuffer d_keys, d_first, d_last, d_values, d_counts;
-  // in: the column whose aggregate_hint remembers the path (nullptr: none) and the signature of this GROUP BY
-  const hy_column* hint_owner = nullptr;
-  uint64_t hint_signature = 0;
 };
 
-// DeviceGroups::on_device -> the host vectors (the host finish after all)
-static hy_status download_groups(DeviceGroups& groups, uint32_t words, uint32_t n_aggregates, hipStream_t stream) {
-  const uint32_t n_groups = groups.n_groups;
-  const size_t per_group = n_aggregates ? n_aggregates : 1;
-  groups.keys.resize(size_t{n_groups} * words);
+// The five arrays of `n_groups` groups -> the host vectors: out of device memory (one copy each, waited for) or out of the pinned block.
+struct GroupArrays { const void *keys, *first, *last, *values, *counts; };
+static hy_status fetch_groups(DeviceGroups& groups, const GroupArrays& from, bool from_device, uint32_t words, uint32_t n_aggregates, hipStream_t stream) {
+  const size_t n_groups = groups.n_groups, per_group = accumulators_per_group(n_aggregates);
+  groups.keys.resize(n_groups * words);
   groups.first.resize(n_groups);
   groups.last.resize(n_groups);
   groups.values.resize(n_groups * per_group);
   groups.counts.resize(n_groups * per_group);
-  HY_HIP(hipMemcpyAsync(groups.keys.data(), groups.d_keys.ptr, 8 * groups.keys.size(), hipMemcpyDeviceToHost, stream));
-  HY_HIP(hipMemcpyAsync(groups.first.data(), groups.d_first.ptr, 8 * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
-  HY_HIP(hipMemcpyAsync(groups.last.data(), groups.d_last.ptr, 8 * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
-  if (n_aggregates) {
-    HY_HIP(hipMemcpyAsync(groups.values.data(), groups.d_values.ptr, 8 * groups.values.size(), hipMemcpyDeviceToHost, stream));
-    HY_HIP(hipMemcpyAsync(groups.counts.data(), groups.d_counts.ptr, 8 * groups.counts.size(), hipMemcpyDeviceToHost, stream));
+  if (!n_groups) return HY_OK;
+  const std::pair<void*, const void*> copies[5] = {{groups.keys.data(), from.keys}, {groups.first.data(), from.first}, {groups.last.data(), from.last},
+                                                   {groups.values.data(), from.values}, {groups.counts.data(), from.counts}};
+  const size_t bytes[5] = {8 * groups.keys.size(), 8 * n_groups, 8 * n_groups, 8 * groups.values.size(), 8 * groups.counts.size()};
+  for (int i = 0; i < (n_aggregates ? 5 : 3); ++i) {
+    if (from_device) HY_HIP(hipMemcpyAsync(copies[i].first, copies[i].second, bytes[i], hipMemcpyDeviceToHost, stream));
+    else std::memcpy(copies[i].first, copies[i].second, bytes[i]);
   }
-  HY_HIP(hipStreamSynchronize(stream));
+  if (from_device) HY_HIP(hipStreamSynchronize(stream));
+  return HY_OK;
+}
+
+// DeviceGroups::on_device -> the host vectors (the host finish after all)
+static hy_status download_groups(DeviceGroups& groups, uint32_t words, uint32_t n_aggregates, hipStream_t stream) {
+  HY_TRY(fetch_groups(groups, GroupArrays{groups.d_keys.ptr, groups.d_first.ptr, groups.d_last.ptr, groups.d_values.ptr, groups.d_counts.ptr}, true, words, n_aggregates, stream));
   groups.on_device = false;
   return HY_OK;
 }
 
-// Runs aggregate_rows + compact_groups for the columns wired into `a` (GROUP BY and device accumulators), retrying with a
-// larger global table when it overflows.
 static uint64_t* g_agg_trace = nullptr;
 static uint32_t g_agg_trace_slices = 0;
+static uint32_t g_agg_path = 0;   // debug: 0 = aggregate_rows, otherwise the partition bits of the partitioned path (last call of this process)
+static uint32_t g_agg_finished_on_device = 0;   // debug: 1 = the last call's result was ordered and written by the finish kernels
+static uint32_t g_agg_small = 0;  // debug: 1 = the last call's groups came from aggregate_small_domain, 2 = from fused_small_domain
+
+// HY_AGG_TIMING: wall-clock laps on stderr
+struct Laps {
+  const bool on = HY_DEBUG_ENV("HY_AGG_TIMING") != nullptr;
+  const std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now();
+  std::chrono::steady_clock::time_point last = start;
+  void since_start(const char* what) const {
+    if (on) std::fprintf(stderr, "[aggregate] %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - start).count());
+  }
+  void since_last(const char* what, int round) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[aggregate]   round %d %-18s +%8.3f ms\n", round, what, std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
+  }
+};
+
+// More dynamic LDS than a workgroup gets without asking: asked for once per device and kernel.
+template <auto Kernel>
+static hipError_t raise_dynamic_lds(size_t bytes) {
+  static OncePerDevice raised;
+  uint64_t device_bit = 0;
+  if (!raised.pending(&device_bit)) return hipSuccess;
+  const hipError_t error = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+  if (error == hipSuccess) raised.done(device_bit);
+  return error;
+}
+
+// f(std::integral_constant<int, W>) for a tuple of `words` words: the partitioning kernels are instantiated per tuple size
+template <typename F>
+static void with_tuple_words(uint32_t words, F&& f) {
+  switch (words) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+#if HY_MAX_GROUPBY > 4
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+#endif
+    default: f(std::integral_constant<int, MAX_GROUPBY + 1>{}); break;
+  }
+}
 
 template <bool SCATTER, int WORDS, bool NARROW>
 static void launch_partition_rows_as(uint32_t grid, size_t lds, hipStream_t stream, const AggArgs& a, const PartitionArgs& pa) {
-  static OncePerDevice lds_raised;   // 2^14 partitions: 64 KiB of counters, the most a workgroup gets without asking
-  uint64_t device_bit = 0;
-  if (lds_raised.pending(&device_bit)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(partition_rows<SCATTER, WORDS, NARROW>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    lds_raised.done(device_bit);
-  }
+  (void)raise_dynamic_lds<partition_rows<SCATTER, WORDS, NARROW>>(65536);   // 2^14 partitions: 64 KiB of counters, the most a workgroup gets without asking
   hipLaunchKernelGGL((partition_rows<SCATTER, WORDS, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa);
 }
-template <bool SCATTER, bool NARROW>
-static void launch_partition_rows_of(uint32_t words, uint32_t grid, size_t lds, hipStream_t stream, const AggArgs& a, const PartitionArgs& pa) {
-  switch (words) {
-    case 1: launch_partition_rows_as<SCATTER, 1, NARROW>(grid, lds, stream, a, pa); break;
-    case 2: launch_partition_rows_as<SCATTER, 2, NARROW>(grid, lds, stream, a, pa); break;
-    case 3: launch_partition_rows_as<SCATTER, 3, NARROW>(grid, lds, stream, a, pa); break;
-    case 4: launch_partition_rows_as<SCATTER, 4, NARROW>(grid, lds, stream, a, pa); break;
-#if HY_MAX_GROUPBY > 4
-    case 5: launch_partition_rows_as<SCATTER, 5, NARROW>(grid, lds, stream, a, pa); break;
-    case 6: launch_partition_rows_as<SCATTER, 6, NARROW>(grid, lds, stream, a, pa); break;
-    case 7: launch_partition_rows_as<SCATTER, 7, NARROW>(grid, lds, stream, a, pa); break;
-    case 8: launch_partition_rows_as<SCATTER, 8, NARROW>(grid, lds, stream, a, pa); break;
-#endif
-    default: launch_partition_rows_as<SCATTER, MAX_GROUPBY + 1, NARROW>(grid, lds, stream, a, pa); break;
-  }
-}
 static void launch_partition_rows(bool scatter, uint32_t words, uint32_t grid, size_t lds, hipStream_t stream, const AggArgs& a, const PartitionArgs& pa) {
-  if (!scatter) launch_partition_rows_of<false, false>(words, grid, lds, stream, a, pa);   // (counting does not build records)
-  else if (pa.narrow) launch_partition_rows_of<true, true>(words, grid, lds, stream, a, pa);
-  else launch_partition_rows_of<true, false>(words, grid, lds, stream, a, pa);
+  with_tuple_words(words, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    if (!scatter) launch_partition_rows_as<false, W, false>(grid, lds, stream, a, pa);   // (counting does not build records)
+    else if (pa.narrow) launch_partition_rows_as<true, W, true>(grid, lds, stream, a, pa);
+    else launch_partition_rows_as<true, W, false>(grid, lds, stream, a, pa);
+  });
 }
-template <bool NARROW>
 static void launch_aggregate_partitions(uint32_t words, uint32_t grid, size_t lds, hipStream_t stream, const AggArgs& a, const PartitionArgs& pa, const DirectGroups& direct) {
-  switch (words) {
-    case 1: hipLaunchKernelGGL((aggregate_partitions<1, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-    case 2: hipLaunchKernelGGL((aggregate_partitions<2, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-    case 3: hipLaunchKernelGGL((aggregate_partitions<3, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-    case 4: hipLaunchKernelGGL((aggregate_partitions<4, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-#if HY_MAX_GROUPBY > 4
-    case 5: hipLaunchKernelGGL((aggregate_partitions<5, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-    case 6: hipLaunchKernelGGL((aggregate_partitions<6, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-    case 7: hipLaunchKernelGGL((aggregate_partitions<7, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-    case 8: hipLaunchKernelGGL((aggregate_partitions<8, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-#endif
-    default: hipLaunchKernelGGL((aggregate_partitions<MAX_GROUPBY + 1, NARROW>), dim3(grid), dim3(256), lds, stream, a, pa, direct); break;
-  }
+  with_tuple_words(words, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    if (pa.narrow) hipLaunchKernelGGL((aggregate_partitions<W, true>), dim3(grid), dim3(256), lds, stream, a, pa, direct);
+    else hipLaunchKernelGGL((aggregate_partitions<W, false>), dim3(grid), dim3(256), lds, stream, a, pa, direct);
+  });
 }
-
-static uint32_t g_agg_path = 0;   // debug: 0 = aggregate_rows, otherwise the partition bits of the partitioned path (last call of this process)
-static uint32_t g_agg_finished_on_device = 0;   // debug: 1 = the last call's result was ordered and written by the finish kernels
-static uint32_t g_agg_small = 0;  // debug: 1 = the last call's groups came from aggregate_small_domain
 
 static uint32_t fused_lds_slots(uint32_t n_groupby) { return n_groupby ? FUSED_LDS_SLOTS : 8u; }
 
-// (`fused`: the device copy of a FusedPlan -- fused_rows takes the place of aggregate_rows; its accumulators' inputs are expressions, which
-//  the partitioned path cannot carry.)
-static hy_status device_groups(AggArgs a, const hy_column* shape, DeviceGroups& out, const FusedPlan* fused = nullptr, const SmallDomainPlan* small = nullptr,
-                               const FusedSmallPlan* fused_small = nullptr) {
-  hipStream_t stream = current_stream();
-  const uint32_t words = a.n_groupby + 1;
-  const uint32_t n_aggregates = a.n_aggregates;
-  const size_t lds_bytes = size_t{LDS_SLOTS} * (8 * words + 16 + 12 * n_aggregates + 4 + 4) + 4 * DENSE_GROUPS + 64 + 64 + SLICE_ROWS + (a.pos_cache ? SLICE_ROWS : 0);   // (+ aggregate_rows' PosList offsets, one word per four rows)
+// ---- device_groups: one pass over the table, on whichever route takes it -----------------------------------------------------------------
+// The partitioned path (tables with many groups): entered when aggregate_rows gives up; 2^bits partitions of about 64 Ki rows,
+// then -- if even those hold more groups than a workgroup's table -- the most the partitioning kernels take.
+constexpr uint32_t MAX_PARTITION_BITS = 14;
+constexpr uint32_t STAGED_GROUPS = 4096;   // results up to this size reach the host through the pinned block
+
+// One device_groups call: what runs (the wired columns and, for the routes that have one, their plan), what the caller wants back, and where
+// the retries stand.
+struct GroupsRun {
+  AggArgs a;
+  const hy_column* shape = nullptr;
+  const FusedPlan* fused = nullptr;               // device copy: fused_rows takes the place of aggregate_rows; its accumulators' inputs are
+                                                  // expressions, which the partitioned path cannot carry
+  const SmallDomainPlan* small = nullptr;         // sd_groups (+ sd_wide) first
+  const FusedSmallPlan* fused_small = nullptr;    // fused_small_domain first
+  bool keep_on_device = false;                    // leave more than STAGED_GROUPS groups where they are
+  const hy_column* hint_owner = nullptr;          // the column whose aggregate_hint remembers the path (nullptr: none) ...
+  uint64_t hint_signature = 0;                    // ... and the signature of this GROUP BY
+  // derived once
+  hipStream_t stream = nullptr;
+  uint32_t words = 0;
   uint64_t two_per_row = 1024;
-  while (two_per_row < 2 * shape->rows + 1024) two_per_row <<= 1;
-  // the number of groups is not known: 64 Ki slots, then 2 Mi, then 32 Mi, then two slots per row (never overflows)
-  const uint64_t ladder[4] = {std::max<uint64_t>(1u << 16, 2 * uint64_t{LDS_SLOTS}), 1u << 21, 1u << 25, two_per_row};
-  int rung = 0;
-  // The partitioned path (tables with many groups): entered when aggregate_rows gives up; 2^bits partitions of about 64 Ki rows,
-  // then -- if even those hold more groups than a workgroup's table -- the most the partitioning kernels take.
-  constexpr uint32_t MAX_PARTITION_BITS = 14;
-  // (the seventeen-word build -- nine to sixteen GROUP BY columns -- keeps to aggregate_rows and the global table: the partitioning kernels
-  //  are instantiated per tuple size, and eight more sizes of them for plans this rare would double the library's build time)
-  const bool can_partition = !fused && a.n_groupby > 0 && shape->rows < (1ull << 32) && FIXED_AGG_PARTITIONS && MAX_GROUPBY <= 8;
-  uint32_t first_bits = 6;
-  while (first_bits < MAX_PARTITION_BITS && (shape->rows >> first_bits) > 65536) ++first_bits;
+  bool can_partition = false;
+  // where the retries stand
   uint32_t partition_bits = 0;   // 0: aggregate_rows
-  if (can_partition && option(HY_OPT_AGG_PARTITION_BITS) > 0) partition_bits = std::min<uint32_t>(MAX_PARTITION_BITS, static_cast<uint32_t>(option(HY_OPT_AGG_PARTITION_BITS)));   // (tests: force the path)
-  // A GROUP BY over the same columns ended on the partitioned path before: start there (the attempt aggregate_rows abandons at one row in
-  // eight outside its tables costs about as much as the partitioned path itself; columns do not change, neither does the outcome).
-  if (can_partition && partition_bits == 0 && !small && t_aggregate_next_path > 1) partition_bits = std::min<uint32_t>(MAX_PARTITION_BITS, t_aggregate_next_path - 1);   // (the caller knows how this GROUP BY went before)
-  t_aggregate_next_path = 0;
-  t_aggregate_recommended = 0;
-  const bool hinted = can_partition && partition_bits == 0 && out.hint_owner && !small;
-  if (hinted) {
-    const uint64_t hint = out.hint_owner->aggregate_hint.load(std::memory_order_relaxed);
-    if (hint >> 8 == out.hint_signature >> 8 && (hint & 0xFF) > 1) partition_bits = std::min<uint32_t>(MAX_PARTITION_BITS, static_cast<uint32_t>(hint & 0xFF) - 1);
-  }
+  int rung = 0;                  // of the table-size ladder
   bool unlimited = false, partitions_ready = false;
-  DeviceBuffer part_offsets, part_rows, part_sums;
   PartitionArgs pa;
-  std::memset(&pa, 0, sizeof(pa));
-  const bool timing = HY_DEBUG_ENV("HY_AGG_TIMING") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what, int round) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[aggregate]   round %d %-18s +%8.3f ms\n", round, what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  for (int round = 0; round < 12; ++round) {
-    if (partition_bits && rung == 0) rung = 1;   // many groups are a given on this path
-    const uint64_t capacity = std::min(ladder[rung], two_per_row);
-    if (capacity > (1ull << 31)) return fail(HY_ERR_UNSUPPORTED, "too many rows for the device group table");
-    DeviceBuffer tags, keys, first, last, values, counts, flags, small_nibbles, small_slots;
+  DeviceBuffer part_offsets, part_rows, part_sums;
+  Laps laps;
+};
+
+// Where a call starts: the option (tests: force the path), what the caller knows about this GROUP BY (t_aggregate_next_path), what the first
+// GROUP BY column remembers.  A GROUP BY over the same columns ended on the partitioned path before: start there (the attempt aggregate_rows
+// abandons at one row in eight outside its tables costs about as much as the partitioned path itself; columns do not change, neither does
+// the outcome).
+static uint32_t starting_partition_bits(const GroupsRun& run) {
+  if (!run.can_partition) return 0;
+  if (option(HY_OPT_AGG_PARTITION_BITS) > 0) return std::min<uint32_t>(MAX_PARTITION_BITS, static_cast<uint32_t>(option(HY_OPT_AGG_PARTITION_BITS)));
+  if (run.small) return 0;
+  if (t_aggregate_next_path > 1) return std::min<uint32_t>(MAX_PARTITION_BITS, t_aggregate_next_path - 1);
+  if (!run.hint_owner) return 0;
+  const uint64_t hint = run.hint_owner->aggregate_hint.load(std::memory_order_relaxed);
+  if (hint >> 8 == run.hint_signature >> 8 && (hint & 0xFF) > 1) return std::min<uint32_t>(MAX_PARTITION_BITS, static_cast<uint32_t>(hint & 0xFF) - 1);
+  return 0;
+}
+
+// One rung's memory: the open-addressed global table, the dense arrays the groups are compacted into (compact_groups; aggregate_partitions
+// with DirectGroups), the flags, and the pinned block header | keys | first | last | values | counts for up to STAGED_GROUPS groups.
+struct GroupTable {
+  uint64_t capacity = 0;
+  uint32_t out_capacity = 0, words = 0, per_group = 0;
+  DeviceBuffer tags, keys, first, last, values, counts, flags;
+  DeviceBuffer c_keys, c_first, c_last, c_values, c_counts;
+  DeviceBuffer small_nibbles, small_slots;   // launch_small_domain's, between its two kernels
+  void* pinned_host = nullptr;
+  void* pinned_dev = nullptr;
+
+  hy_status alloc(uint64_t table_capacity, uint32_t dense_capacity, uint32_t tuple_words, uint32_t accumulators, hipStream_t stream) {
+    capacity = table_capacity, out_capacity = dense_capacity, words = tuple_words, per_group = accumulators;
     HY_TRY(tags.alloc(4 * capacity));
     HY_TRY(keys.alloc(8 * capacity * words));
     HY_TRY(first.alloc(8 * capacity));
     HY_TRY(last.alloc(8 * capacity));
-    HY_TRY(values.alloc(8 * capacity * (n_aggregates ? n_aggregates : 1)));
-    HY_TRY(counts.alloc(8 * capacity * (n_aggregates ? n_aggregates : 1)));
+    HY_TRY(values.alloc(8 * capacity * per_group));
+    HY_TRY(counts.alloc(8 * capacity * per_group));
     HY_TRY(flags.alloc(64));
     HY_HIP(hipMemsetAsync(tags.ptr, 0, 4 * capacity, stream));
     HY_HIP(hipMemsetAsync(flags.ptr, 0, 64, stream));
-    lap("table allocated", round);
+    HY_TRY(c_keys.alloc(8 * size_t{out_capacity} * words));
+    HY_TRY(c_first.alloc(8 * size_t{out_capacity}));
+    HY_TRY(c_last.alloc(8 * size_t{out_capacity}));
+    HY_TRY(c_values.alloc(8 * size_t{out_capacity} * per_group));
+    HY_TRY(c_counts.alloc(8 * size_t{out_capacity} * per_group));
+    return pinned_staging(64 + 8 * size_t{STAGED_GROUPS} * (words + 2 + 2 * per_group), &pinned_host, &pinned_dev);
+  }
+  void bind(AggArgs& a) const {
     a.capacity = static_cast<uint32_t>(capacity);
     a.tags = tags.as<uint32_t>();
     a.keys = keys.as<uint64_t>();
@@ -2724,252 +2767,278 @@ static hy_status device_groups(AggArgs a, const hy_column* shape, DeviceGroups& 
     a.values = values.as<uint64_t>();
     a.counts = counts.as<uint64_t>();
     a.overflow = flags.as<uint32_t>();
-    // rows outside the LDS tables cost a handful of device-scope atomics each; the partitioned path costs about as much as one
-    // such row in sixteen -- plus the attempt it abandons: aggregate_rows goes on up to one row in eight (tables with thousands of
-    // groups are recognised by their first slices, FLAG_CROWDED); partitions too coarse for their tables are refined at one in sixteen.
-    // (No limit where there is nothing to switch to.)
-    const bool last_resort = !can_partition || unlimited || (partition_bits && partition_bits >= MAX_PARTITION_BITS);
-    // (SSB Q2.1 at SF30: 280 groups, 9 % of 1.4 M rows outside the 256-slot tables -- 3.9 ms with them, 4.5 ms through the give-up at rows / 16)
-    const int spill_shift = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(8, option(HY_OPT_AGG_SPILL_SHIFT))));
-    a.spill_limit = last_resort ? 0xFFFFFFFFu : static_cast<uint32_t>(std::max<uint64_t>(65536, shape->rows >> (partition_bits ? 4 : spill_shift)));
-    a.trace = nullptr;
-    if (HY_DEBUG_ENV("HY_AGG_TRACE") && shape->n_slices <= (1u << 14)) {
-      static uint64_t* trace_buffer = nullptr;
-      if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 12 * size_t{1u << 14});
-      (void)hipMemsetAsync(trace_buffer, 0, 8 * 12 * size_t{shape->n_slices}, stream);
-      a.trace = trace_buffer;
-      g_agg_trace = trace_buffer;
-      g_agg_trace_slices = shape->n_slices;
+  }
+  StagedGroups staged_arrays(void* base) const {
+    StagedGroups g;
+    g.keys = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(base) + 64);
+    g.first = g.keys + size_t{STAGED_GROUPS} * words;
+    g.last = g.first + STAGED_GROUPS;
+    g.values = g.last + STAGED_GROUPS;
+    g.counts = g.values + size_t{STAGED_GROUPS} * per_group;
+    g.capacity = STAGED_GROUPS;
+    return g;
+  }
+  uint32_t* group_counter() const { return flags.as<uint32_t>() + FLAG_GROUPS; }
+};
+
+// HY_AGG_TRACE: aggregate_rows stamps its phases per slice (hy_debug_aggregate_trace reads them)
+static uint64_t* trace_stamps(const hy_column* shape, hipStream_t stream) {
+  if (!HY_DEBUG_ENV("HY_AGG_TRACE") || shape->n_slices > (1u << 14)) return nullptr;
+  static uint64_t* trace_buffer = nullptr;
+  if (!trace_buffer) (void)hipMalloc(reinterpret_cast<void**>(&trace_buffer), 8 * 12 * size_t{1u << 14});
+  (void)hipMemsetAsync(trace_buffer, 0, 8 * 12 * size_t{shape->n_slices}, stream);
+  g_agg_trace = trace_buffer;
+  g_agg_trace_slices = shape->n_slices;
+  return trace_buffer;
+}
+
+// Rows outside the LDS tables cost a handful of device-scope atomics each; the partitioned path costs about as much as one such row in
+// sixteen -- plus the attempt it abandons: aggregate_rows goes on up to one row in eight (tables with thousands of groups are recognised by
+// their first slices, FLAG_CROWDED); partitions too coarse for their tables are refined at one in sixteen.  No limit where there is nothing
+// to switch to.  (SSB Q2.1 at SF30: 280 groups, 9 % of 1.4 M rows outside the 256-slot tables -- 3.9 ms with them, 4.5 ms through the
+// give-up at rows / 16.)
+static uint32_t spill_limit(const GroupsRun& run) {
+  const bool last_resort = !run.can_partition || run.unlimited || (run.partition_bits && run.partition_bits >= MAX_PARTITION_BITS);
+  if (last_resort) return 0xFFFFFFFFu;
+  const int spill_shift = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(8, option(HY_OPT_AGG_SPILL_SHIFT))));
+  return static_cast<uint32_t>(std::max<uint64_t>(65536, run.shape->rows >> (run.partition_bits ? 4 : spill_shift)));
+}
+
+static hy_status launch_fused_small(const GroupsRun& run) {   // the Q1 shape: one workgroup of 1024 threads per chunk (fused_small.hpp)
+  HY_HIP(raise_dynamic_lds<fused_small_domain>(fs_lds_bytes()));
+  hipLaunchKernelGGL(fused_small_domain, dim3(run.shape->n_chunks), dim3(FS_THREADS), fs_lds_bytes(), run.stream, run.a, run.fused, *run.fused_small, run.shape->n_chunks);
+  return HY_OK;
+}
+
+static hy_status launch_fused_rows(const GroupsRun& run) {   // one workgroup per chunk
+  const uint32_t n_aggregates = run.a.n_aggregates;
+  const size_t fused_lds = size_t{fused_lds_slots(run.a.n_groupby)} * (lds_slot_bytes(run.words, n_aggregates) + 4) + 64 + 2 * size_t{SLICE_ROWS} + sizeof(ColumnView) * FUSED_VIEWS +
+                           sizeof(ScanJob) * HY_MAX_FILTERS + sizeof(FusedInput) * n_aggregates + size_t{FUSED_DENSE} * FUSED_CELLS * (8 * (n_aggregates + 2) + 4 * n_aggregates);
+  if (fused_lds > 65536) HY_HIP(raise_dynamic_lds<fused_rows>(160 * 1024));
+  hipLaunchKernelGGL(fused_rows, dim3(run.shape->n_chunks), dim3(256), fused_lds, run.stream, run.a, run.fused, run.shape->n_chunks);
+  return HY_OK;
+}
+
+// A handful of groups over dictionary columns (aggregate_small.hpp), two launches: the GROUP BY ids and 1-byte columns per chunk, then the
+// 2-byte column per (chunk, part of the value-id range); between them a nibble per row (its dense group) and the chunks' global-table slots.
+static hy_status launch_small_domain(const GroupsRun& run, GroupTable& table) {
+  const uint32_t n_chunks = run.shape->n_chunks;
+  SmallDomainPlan plan = *run.small;
+  const bool has_wide = plan.n_columns > plan.n_narrow;
+  if (has_wide) {
+    HY_TRY(table.small_nibbles.alloc(size_t{n_chunks} * SD_NIBBLE_BYTES));
+    HY_TRY(table.small_slots.alloc(4 * size_t{n_chunks} * SD_DENSE));
+    plan.nibbles = table.small_nibbles.as<uint8_t>();
+    plan.chunk_slots = table.small_slots.as<uint32_t>();
+  }
+  hipLaunchKernelGGL(sd_groups, dim3(n_chunks), dim3(SD_THREADS), 0, run.stream, run.a, plan, n_chunks);
+  if (has_wide && !(plan.debug & 2)) {
+    HY_HIP(raise_dynamic_lds<sd_wide>(sd_wide_lds_bytes()));
+    hipLaunchKernelGGL(sd_wide, dim3((n_chunks + 7) / 8 * 8 * SD_WIDE_PARTS), dim3(SD_WIDE_THREADS), sd_wide_lds_bytes(), run.stream, run.a, plan, n_chunks);
+  }
+  return HY_OK;
+}
+
+static hy_status launch_rows(const GroupsRun& run) {
+  const size_t lds_bytes = size_t{LDS_SLOTS} * (lds_slot_bytes(run.words, run.a.n_aggregates) + 4) + 4 * DENSE_GROUPS + 64 + 64 + SLICE_ROWS +
+                           (run.a.pos_cache ? SLICE_ROWS : 0);   // (+ aggregate_rows' PosList offsets, one word per four rows)
+  if (lds_bytes > 65536) HY_HIP(raise_dynamic_lds<aggregate_rows>(160 * 1024));   // (seventeen-word tuples: 256 slots of them exceed what a workgroup gets without asking)
+  hipLaunchKernelGGL(aggregate_rows, dim3(run.shape->n_slices), dim3(256), lds_bytes, run.stream, run.a);
+  return HY_OK;
+}
+
+// The rows as records, partition by partition: count per tile, scan, scatter.  Done once per number of bits.
+static hy_status prepare_partitions(GroupsRun& run) {
+  const AggArgs& a = run.a;
+  PartitionArgs& pa = run.pa;
+  const uint32_t words = run.words, n_aggregates = a.n_aggregates, partitions = 1u << run.partition_bits;
+  pa.tile_slices = run.partition_bits <= 11 ? 1 : 8;   // (a tile's histogram is written and scanned: 2^bits cells per tile)
+  pa.n_slices = run.shape->n_slices;
+  pa.n_parts = (run.shape->n_slices + pa.tile_slices - 1) / pa.tile_slices;
+  const uint64_t cells = uint64_t{partitions} * pa.n_parts;
+  const uint32_t n_blocks = static_cast<uint32_t>((cells + SCAN_BLOCK - 1) / SCAN_BLOCK);
+  HY_TRY(run.part_offsets.alloc(4 * cells));
+  HY_TRY(run.part_sums.alloc(4 * (size_t{n_blocks} + 1)));
+  uint32_t carried = 0;
+  while (carried < n_aggregates && a.aggregates[carried].segments) ++carried;   // (columns_first puts COUNT(*) last)
+  for (uint32_t g = carried; g < n_aggregates; ++g) if (a.aggregates[g].segments) return fail(HY_ERR_DEVICE, "aggregates with a column must come first (internal error)");
+  pa.carried = carried;
+  pa.record_words = (1 + words + carried + 1) / 2 * 2;
+  pa.narrow = 1;   // every key and every carried input a 4-byte type: 32-bit words (partition_rows)
+  for (uint32_t g = 0; g + 1 < words; ++g) if (a.groupby[g].data_type != HY_TYPE_INT && a.groupby[g].data_type != HY_TYPE_FLOAT) pa.narrow = 0;
+  for (uint32_t g = 0; g < carried; ++g) if (a.aggregates[g].data_type != HY_TYPE_INT && a.aggregates[g].data_type != HY_TYPE_FLOAT) pa.narrow = 0;
+  if (pa.narrow) pa.record_words = (2 + (words - 1) + carried + 3) / 4 * 2;   // (16-byte units either way)
+  HY_TRY(run.part_rows.alloc(8 * size_t{pa.record_words} * run.shape->rows));
+  pa.bits = run.partition_bits;
+  pa.offsets = run.part_offsets.as<uint32_t>();
+  pa.records = run.part_rows.as<uint64_t>();
+  pa.total_rows = run.shape->rows;
+  pa.lds_slots = 2048;
+  const size_t lds_budget = static_cast<size_t>(std::max<int64_t>(1024, FIXED_AGG_LDS_BUDGET));
+  while (pa.lds_slots > 64 && pa.lds_slots * lds_slot_bytes(words, n_aggregates) > lds_budget) pa.lds_slots >>= 1;
+  uint32_t* sums = run.part_sums.as<uint32_t>();
+  launch_partition_rows(false, words, pa.n_parts, 4 * size_t{partitions}, run.stream, a, pa);
+  hipLaunchKernelGGL(scan_blocks, dim3(n_blocks), dim3(256), 0, run.stream, pa.offsets, cells, sums);
+  hipLaunchKernelGGL(scan_sums, dim3(1), dim3(256), 0, run.stream, sums, n_blocks);
+  hipLaunchKernelGGL(scan_add, dim3(n_blocks), dim3(256), 0, run.stream, pa.offsets, cells, sums);
+  launch_partition_rows(true, words, pa.n_parts, 4 * size_t{partitions}, run.stream, a, pa);
+  run.partitions_ready = true;
+  return HY_OK;
+}
+
+// One workgroup per (part of a) partition aggregates its records in an LDS table; with one workgroup per partition its groups are final and
+// go straight into the dense arrays (DirectGroups), otherwise they meet in the global table.
+static void launch_partition_merge(GroupsRun& run, const GroupTable& table) {
+  PartitionArgs& pa = run.pa;
+  // about 16 Ki rows per workgroup: coarse partitions (long contiguous runs for the scatter) are shared by several
+  pa.split = 1;
+  while (pa.split < 64 && (run.shape->rows >> run.partition_bits) / pa.split > 16384) pa.split <<= 1;
+  if (FIXED_AGG_SPLIT > 0) pa.split = static_cast<uint32_t>(FIXED_AGG_SPLIT);
+  DirectGroups direct;
+  std::memset(&direct, 0, sizeof(direct));
+  direct.enabled = pa.split == 1 ? 1u : 0u;
+  direct.out_capacity = table.out_capacity;
+  direct.counter = table.group_counter();
+  direct.keys = table.c_keys.as<uint64_t>();
+  direct.first = table.c_first.as<uint64_t>();
+  direct.last = table.c_last.as<uint64_t>();
+  direct.values = table.c_values.as<uint64_t>();
+  direct.counts = table.c_counts.as<uint64_t>();
+  direct.staged = table.staged_arrays(table.pinned_dev);
+  launch_aggregate_partitions(run.words, (1u << run.partition_bits) * pa.split, pa.lds_slots * lds_slot_bytes(run.words, run.a.n_aggregates) + 64, run.stream, run.a, pa, direct);
+}
+
+// The route of this round ("Routes"): nothing over an empty input.
+static hy_status launch_route(GroupsRun& run, GroupTable& table) {
+  const bool small = run.small && run.partition_bits == 0 && !run.fused;
+  g_agg_path = run.partition_bits;
+  g_agg_small = run.fused && run.fused_small ? 2u : small ? 1u : 0u;
+  if (!run.shape->n_slices || !run.shape->rows) return HY_OK;
+  profile_begin(run.stream, HY_KERNEL_AGGREGATE);
+  if (run.fused && run.fused_small) HY_TRY(launch_fused_small(run));
+  else if (run.fused) HY_TRY(launch_fused_rows(run));
+  else if (small) HY_TRY(launch_small_domain(run, table));
+  else if (run.partition_bits == 0) HY_TRY(launch_rows(run));
+  else {
+    if (!run.partitions_ready) HY_TRY(prepare_partitions(run));
+    launch_partition_merge(run, table);
+  }
+  profile_end(run.stream);
+  return HY_OK;
+}
+
+// What the flags of a finished round ask for.
+enum class Step { done, without_small, partition, larger_table };
+static hy_status next_step(const uint32_t* flags, uint32_t out_capacity, GroupsRun& run, Step* step) {
+  if (flags[FLAG_SMALL_REFUSED] && (run.small || run.fused_small)) {
+    // sd_groups: a value met sixteen times in one group of one chunk -> aggregate_rows; fused_small_domain: a fifth group in a chunk, a
+    // NULL input -> fused_rows
+    if (run.small) run.small = nullptr;
+    else run.fused_small = nullptr;
+    *step = Step::without_small;
+  } else if (flags[FLAG_GIVE_UP]) {   // too many rows outside the LDS tables: partition (more finely)
+    uint32_t first_bits = 6;
+    while (first_bits < MAX_PARTITION_BITS && (run.shape->rows >> first_bits) > 65536) ++first_bits;
+    if (run.partition_bits == 0) run.partition_bits = first_bits;
+    else if (run.partition_bits < MAX_PARTITION_BITS) run.partition_bits = MAX_PARTITION_BITS;
+    else run.unlimited = true;
+    run.partitions_ready = false;
+    *step = Step::partition;
+  } else if (flags[FLAG_OVERFLOW] || flags[FLAG_GROUPS] > out_capacity) {
+    // table overflow, or direct groups + the global table's are more than the dense arrays hold: retry with a larger one
+    if (run.rung == 3) {
+      return flags[FLAG_OVERFLOW] ? fail(HY_ERR_DEVICE, "the device group table overflowed at two slots per row (internal error)")
+                                  : fail(HY_ERR_DEVICE, "more groups than rows (internal error)");
     }
-    // where the groups go, densely (compact_groups; aggregate_partitions with DirectGroups)
-    DeviceBuffer c_keys, c_first, c_last, c_values, c_counts;
-    // (the partitioned path's groups mostly bypass the global table: room for 8 Mi of them whatever its size)
-    const uint32_t out_capacity = static_cast<uint32_t>(std::min<uint64_t>(partition_bits ? std::max<uint64_t>(capacity, 1u << 23) : capacity, shape->rows + 1));
-    HY_TRY(c_keys.alloc(8 * size_t{out_capacity} * words));
-    HY_TRY(c_first.alloc(8 * size_t{out_capacity}));
-    HY_TRY(c_last.alloc(8 * size_t{out_capacity}));
-    HY_TRY(c_values.alloc(8 * size_t{out_capacity} * (n_aggregates ? n_aggregates : 1)));
-    HY_TRY(c_counts.alloc(8 * size_t{out_capacity} * (n_aggregates ? n_aggregates : 1)));
-    // pinned block: header | keys | first | last | values | counts for up to STAGED_GROUPS groups
-    constexpr uint32_t STAGED_GROUPS = 4096;
-    const uint32_t per_group = n_aggregates ? n_aggregates : 1;
-    const size_t staged_bytes = 64 + 8 * size_t{STAGED_GROUPS} * (words + 2 + 2 * per_group);
-    void* pinned_host = nullptr;
-    void* pinned_dev = nullptr;
-    HY_TRY(pinned_staging(staged_bytes, &pinned_host, &pinned_dev));
-    auto staged_arrays = [&](void* base) {
-      StagedGroups g;
-      g.keys = reinterpret_cast<uint64_t*>(static_cast<unsigned char*>(base) + 64);
-      g.first = g.keys + size_t{STAGED_GROUPS} * words;
-      g.last = g.first + STAGED_GROUPS;
-      g.values = g.last + STAGED_GROUPS;
-      g.counts = g.values + size_t{STAGED_GROUPS} * per_group;
-      g.capacity = STAGED_GROUPS;
-      return g;
-    };
-    g_agg_path = partition_bits;
-    g_agg_small = small && partition_bits == 0 && !fused ? 1u : 0u;
-    g_agg_small = fused && fused_small ? 2u : g_agg_small;
-    if (shape->n_slices && shape->rows && fused && fused_small) {   // the Q1 shape: one workgroup of 1024 threads per chunk (fused_small.hpp)
-      profile_begin(stream, HY_KERNEL_AGGREGATE);
-      static OncePerDevice raised;
-      uint64_t device_bit = 0;
-      if (raised.pending(&device_bit)) {
-        HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_small_domain), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(fs_lds_bytes())));
-        raised.done(device_bit);
-      }
-      hipLaunchKernelGGL(fused_small_domain, dim3(shape->n_chunks), dim3(FS_THREADS), fs_lds_bytes(), stream, a, fused, *fused_small, shape->n_chunks);
-      profile_end(stream);
-    } else if (shape->n_slices && shape->rows && fused) {   // one workgroup per chunk
-      const size_t fused_lds = size_t{fused_lds_slots(a.n_groupby)} * (8 * words + 16 + 12 * n_aggregates + 4 + 4) + 64 + 2 * size_t{SLICE_ROWS} + sizeof(ColumnView) * FUSED_VIEWS +
-                               sizeof(ScanJob) * HY_MAX_FILTERS + sizeof(FusedInput) * n_aggregates + size_t{FUSED_DENSE} * FUSED_CELLS * (8 * (n_aggregates + 2) + 4 * n_aggregates);
-      profile_begin(stream, HY_KERNEL_AGGREGATE);
-      if (fused_lds > 65536) {
-        static OncePerDevice fused_lds_raised;
-        uint64_t device_bit = 0;
-        if (fused_lds_raised.pending(&device_bit)) {
-          HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          fused_lds_raised.done(device_bit);
-        }
-      }
-      hipLaunchKernelGGL(fused_rows, dim3(shape->n_chunks), dim3(256), fused_lds, stream, a, fused, shape->n_chunks);
-      profile_end(stream);
-    } else if (shape->n_slices && shape->rows && partition_bits == 0 && small) {   // a handful of groups over dictionary columns (aggregate_small.hpp)
-      // two launches: the GROUP BY ids and 1-byte columns per chunk, then the 2-byte column per (chunk, part of the value-id range); between
-      // them a nibble per row (its dense group) and the chunks' global-table slots
-      SmallDomainPlan plan = *small;
-      const bool has_wide = plan.n_columns > plan.n_narrow;
-      if (has_wide) {
-        HY_TRY(small_nibbles.alloc(size_t{shape->n_chunks} * SD_NIBBLE_BYTES));
-        HY_TRY(small_slots.alloc(4 * size_t{shape->n_chunks} * SD_DENSE));
-        plan.nibbles = small_nibbles.as<uint8_t>();
-        plan.chunk_slots = small_slots.as<uint32_t>();
-      }
-      profile_begin(stream, HY_KERNEL_AGGREGATE);
-      hipLaunchKernelGGL(sd_groups, dim3(shape->n_chunks), dim3(SD_THREADS), 0, stream, a, plan, shape->n_chunks);
-      if (has_wide && !(plan.debug & 2)) {
-        static OncePerDevice raised;
-        uint64_t device_bit = 0;
-        if (raised.pending(&device_bit)) {
-          HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sd_wide), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sd_wide_lds_bytes())));
-          raised.done(device_bit);
-        }
-        const uint32_t blocks = (shape->n_chunks + 7) / 8 * 8 * SD_WIDE_PARTS;
-        hipLaunchKernelGGL(sd_wide, dim3(blocks), dim3(SD_WIDE_THREADS), sd_wide_lds_bytes(), stream, a, plan, shape->n_chunks);
-      }
-      profile_end(stream);
-    } else if (shape->n_slices && shape->rows && partition_bits == 0) {
-      profile_begin(stream, HY_KERNEL_AGGREGATE);
-      if (lds_bytes > 65536) {   // (seventeen-word tuples: 256 slots of them exceed what a workgroup gets without asking)
-        static OncePerDevice rows_lds_raised;
-        uint64_t device_bit = 0;
-        if (rows_lds_raised.pending(&device_bit)) {
-          HY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(aggregate_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          rows_lds_raised.done(device_bit);
-        }
-      }
-      hipLaunchKernelGGL(aggregate_rows, dim3(shape->n_slices), dim3(256), lds_bytes, stream, a);
-      profile_end(stream);
-    } else if (shape->n_slices && shape->rows) {
-      const uint32_t partitions = 1u << partition_bits;
-      profile_begin(stream, HY_KERNEL_AGGREGATE);
-      if (!partitions_ready) {
-        pa.tile_slices = partition_bits <= 11 ? 1 : 8;   // (a tile's histogram is written and scanned: 2^bits cells per tile)
-        pa.n_slices = shape->n_slices;
-        pa.n_parts = (shape->n_slices + pa.tile_slices - 1) / pa.tile_slices;
-        const uint64_t cells = uint64_t{partitions} * pa.n_parts;
-        const uint32_t n_blocks = static_cast<uint32_t>((cells + SCAN_BLOCK - 1) / SCAN_BLOCK);
-        HY_TRY(part_offsets.alloc(4 * cells));
-        HY_TRY(part_sums.alloc(4 * (size_t{n_blocks} + 1)));
-        uint32_t carried = 0;
-        while (carried < n_aggregates && a.aggregates[carried].segments) ++carried;   // (run_aggregate puts COUNT(*) last)
-        for (uint32_t g = carried; g < n_aggregates; ++g) if (a.aggregates[g].segments) return fail(HY_ERR_DEVICE, "aggregates with a column must come first (internal error)");
-        pa.carried = carried;
-        pa.record_words = (1 + words + carried + 1) / 2 * 2;
-        pa.narrow = 1;   // every key and every carried input a 4-byte type: 32-bit words (partition_rows)
-        for (uint32_t g = 0; g + 1 < words; ++g) if (a.groupby[g].data_type != HY_TYPE_INT && a.groupby[g].data_type != HY_TYPE_FLOAT) pa.narrow = 0;
-        for (uint32_t g = 0; g < carried; ++g) if (a.aggregates[g].data_type != HY_TYPE_INT && a.aggregates[g].data_type != HY_TYPE_FLOAT) pa.narrow = 0;
-        if (pa.narrow) pa.record_words = (2 + (words - 1) + carried + 3) / 4 * 2;   // (16-byte units either way)
-        HY_TRY(part_rows.alloc(8 * size_t{pa.record_words} * shape->rows));
-        pa.bits = partition_bits;
-        pa.offsets = part_offsets.as<uint32_t>();
-        pa.records = part_rows.as<uint64_t>();
-        pa.total_rows = shape->rows;
-        const size_t per_slot = 8 * words + 16 + 12 * n_aggregates + 4;
-        pa.lds_slots = 2048;
-        const size_t lds_budget = static_cast<size_t>(std::max<int64_t>(1024, FIXED_AGG_LDS_BUDGET));
-        while (pa.lds_slots > 64 && pa.lds_slots * per_slot > lds_budget) pa.lds_slots >>= 1;
-        launch_partition_rows(false, words, pa.n_parts, 4 * size_t{partitions}, stream, a, pa);
-        hipLaunchKernelGGL(scan_blocks, dim3(n_blocks), dim3(256), 0, stream, pa.offsets, cells, part_sums.as<uint32_t>());
-        hipLaunchKernelGGL(scan_sums, dim3(1), dim3(256), 0, stream, part_sums.as<uint32_t>(), n_blocks);
-        hipLaunchKernelGGL(scan_add, dim3(n_blocks), dim3(256), 0, stream, pa.offsets, cells, part_sums.as<uint32_t>());
-        launch_partition_rows(true, words, pa.n_parts, 4 * size_t{partitions}, stream, a, pa);
-        partitions_ready = true;
-      }
-      const size_t per_slot = 8 * words + 16 + 12 * n_aggregates + 4;
-      // about 16 Ki rows per workgroup: coarse partitions (long contiguous runs for the scatter) are shared by several
-      pa.split = 1;
-      while (pa.split < 64 && (shape->rows >> partition_bits) / pa.split > 16384) pa.split <<= 1;
-      if (FIXED_AGG_SPLIT > 0) pa.split = static_cast<uint32_t>(FIXED_AGG_SPLIT);
-      DirectGroups direct;
-      std::memset(&direct, 0, sizeof(direct));
-      direct.enabled = pa.split == 1 ? 1u : 0u;
-      direct.out_capacity = out_capacity;
-      direct.counter = flags.as<uint32_t>() + FLAG_GROUPS;
-      direct.keys = c_keys.as<uint64_t>();
-      direct.first = c_first.as<uint64_t>();
-      direct.last = c_last.as<uint64_t>();
-      direct.values = c_values.as<uint64_t>();
-      direct.counts = c_counts.as<uint64_t>();
-      direct.staged = staged_arrays(pinned_dev);
-      if (pa.narrow) launch_aggregate_partitions<true>(words, partitions * pa.split, pa.lds_slots * per_slot + 64, stream, a, pa, direct);
-      else launch_aggregate_partitions<false>(words, partitions * pa.split, pa.lds_slots * per_slot + 64, stream, a, pa, direct);
-      profile_end(stream);
-    }
-    lap("kernels launched", round);
-    uint32_t host_flags[7] = {0, 0, 0, 0, 0, 0, 0};
-    hipLaunchKernelGGL(compact_groups, dim3(static_cast<uint32_t>((capacity + COMPACT_THREADS - 1) / COMPACT_THREADS)), dim3(COMPACT_THREADS), 0, stream, a, flags.as<uint32_t>() + FLAG_GROUPS, c_keys.as<uint64_t>(),
-                       c_first.as<uint64_t>(), c_last.as<uint64_t>(), c_values.as<uint64_t>(), c_counts.as<uint64_t>(), out_capacity, staged_arrays(pinned_dev));
-    hipLaunchKernelGGL(publish_group_flags, dim3(1), dim3(1), 0, stream, flags.as<uint32_t>(), static_cast<uint32_t*>(pinned_dev));
-    lap("compact launched", round);
-    HY_HIP(hipStreamSynchronize(stream));
-    lap("device finished", round);
-    std::memcpy(host_flags, pinned_host, 28);
-    if (host_flags[FLAG_SMALL_REFUSED] && small) {   // (a value met sixteen times in one group of one chunk)
-      small = nullptr;
-      continue;
-    }
-    if (host_flags[FLAG_SMALL_REFUSED] && fused_small) {   // (a fifth group in a chunk, a NULL input: fused_rows)
-      fused_small = nullptr;
-      continue;
-    }
-    if (host_flags[FLAG_GIVE_UP]) {   // too many rows outside the LDS tables: partition (more finely)
-      if (partition_bits == 0) partition_bits = first_bits;
-      else if (partition_bits < MAX_PARTITION_BITS) partition_bits = MAX_PARTITION_BITS;
-      else unlimited = true;
-      partitions_ready = false;
-      continue;
-    }
-    if (host_flags[FLAG_OVERFLOW]) {   // table overflow: retry with a larger one
-      if (rung < 3) ++rung;
-      else return fail(HY_ERR_DEVICE, "the device group table overflowed at two slots per row (internal error)");
-      continue;
-    }
-    const uint32_t n_groups = host_flags[FLAG_GROUPS];
-    if (n_groups > out_capacity) {   // (direct groups + the global table's: more than the arrays hold)
-      if (rung < 3) ++rung;
-      else return fail(HY_ERR_DEVICE, "more groups than rows (internal error)");
-      continue;
-    }
-    out.n_groups = n_groups;
-    out.passed_rows = static_cast<uint64_t>(host_flags[5]) << 32 | host_flags[4];
-    // What the next GROUP BY over these columns should start with: the path this one ended on -- or, where aggregate_rows ran to the end over
-    // a few million rows with more groups than a workgroup's table has slots (the rows of the groups that found no slot met in the global
-    // table, atomic by atomic: SSB Q2.1's 280 groups over 1.4 M rows took 0.42 ms there and take 0.2 ms in sixteen partitions), 4 bits.
-    uint32_t recommended_bits = partition_bits;
-    if (partition_bits == 0 && can_partition && !small && n_groups > LDS_SLOTS && shape->rows < (8u << 20)) recommended_bits = 4;
-    t_aggregate_recommended = recommended_bits ? recommended_bits + 1 : 0;
-    if (out.hint_owner && can_partition && !small && option(HY_OPT_AGG_PARTITION_BITS) <= 0) out.hint_owner->aggregate_hint.store((out.hint_signature >> 8) << 8 | (recommended_bits + 1), std::memory_order_relaxed);
-    if (out.keep_on_device && n_groups > STAGED_GROUPS) {
-      std::swap(out.d_keys.ptr, c_keys.ptr);     std::swap(out.d_keys.capacity, c_keys.capacity);
-      std::swap(out.d_first.ptr, c_first.ptr);   std::swap(out.d_first.capacity, c_first.capacity);
-      std::swap(out.d_last.ptr, c_last.ptr);     std::swap(out.d_last.capacity, c_last.capacity);
-      std::swap(out.d_values.ptr, c_values.ptr); std::swap(out.d_values.capacity, c_values.capacity);
-      std::swap(out.d_counts.ptr, c_counts.ptr); std::swap(out.d_counts.capacity, c_counts.capacity);
-      out.on_device = true;
-      lap("groups stay", round);
-      return HY_OK;
-    }
-    out.keys.resize(size_t{n_groups} * words);
-    out.first.resize(n_groups);
-    out.last.resize(n_groups);
-    out.values.resize(size_t{n_groups} * (n_aggregates ? n_aggregates : 1));
-    out.counts.resize(size_t{n_groups} * (n_aggregates ? n_aggregates : 1));
-    if (n_groups && n_groups <= STAGED_GROUPS) {   // everything is already here
-      const StagedGroups staged = staged_arrays(pinned_host);
-      std::memcpy(out.keys.data(), staged.keys, 8 * out.keys.size());
-      std::memcpy(out.first.data(), staged.first, 8 * size_t{n_groups});
-      std::memcpy(out.last.data(), staged.last, 8 * size_t{n_groups});
-      if (n_aggregates) {
-        std::memcpy(out.values.data(), staged.values, 8 * out.values.size());
-        std::memcpy(out.counts.data(), staged.counts, 8 * out.counts.size());
-      }
-    } else if (n_groups) {
-      HY_HIP(hipMemcpyAsync(out.keys.data(), c_keys.ptr, 8 * out.keys.size(), hipMemcpyDeviceToHost, stream));
-      HY_HIP(hipMemcpyAsync(out.first.data(), c_first.ptr, 8 * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
-      HY_HIP(hipMemcpyAsync(out.last.data(), c_last.ptr, 8 * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
-      if (n_aggregates) {
-        HY_HIP(hipMemcpyAsync(out.values.data(), c_values.ptr, 8 * out.values.size(), hipMemcpyDeviceToHost, stream));
-        HY_HIP(hipMemcpyAsync(out.counts.data(), c_counts.ptr, 8 * out.counts.size(), hipMemcpyDeviceToHost, stream));
-      }
-      HY_HIP(hipStreamSynchronize(stream));
-    }
-    lap("groups copied", round);
+    ++run.rung;
+    *step = Step::larger_table;
+  } else {
+    *step = Step::done;
+  }
+  return HY_OK;
+}
+
+// What the next GROUP BY over these columns should start with: the path this one ended on -- or, where aggregate_rows ran to the end over
+// a few million rows with more groups than a workgroup's table has slots (the rows of the groups that found no slot met in the global
+// table, atomic by atomic: SSB Q2.1's 280 groups over 1.4 M rows took 0.42 ms there and take 0.2 ms in sixteen partitions), 4 bits.
+static void remember_path(const GroupsRun& run, uint32_t n_groups) {
+  uint32_t recommended_bits = run.partition_bits;
+  if (run.partition_bits == 0 && run.can_partition && !run.small && n_groups > LDS_SLOTS && run.shape->rows < (8u << 20)) recommended_bits = 4;
+  t_aggregate_recommended = recommended_bits ? recommended_bits + 1 : 0;
+  if (run.hint_owner && run.can_partition && !run.small && option(HY_OPT_AGG_PARTITION_BITS) <= 0)
+    run.hint_owner->aggregate_hint.store((run.hint_signature >> 8) << 8 | (recommended_bits + 1), std::memory_order_relaxed);
+}
+
+// The groups to the caller: left on the device, taken from the pinned block (everything is already there), or copied.
+static hy_status hand_over(GroupsRun& run, GroupTable& table, DeviceGroups& out, int round) {
+  if (run.keep_on_device && out.n_groups > STAGED_GROUPS) {
+    swap(out.d_keys, table.c_keys);
+    swap(out.d_first, table.c_first);
+    swap(out.d_last, table.c_last);
+    swap(out.d_values, table.c_values);
+    swap(out.d_counts, table.c_counts);
+    out.on_device = true;
+    run.laps.since_last("groups stay", round);
     return HY_OK;
+  }
+  if (out.n_groups <= STAGED_GROUPS) {
+    const StagedGroups staged = table.staged_arrays(table.pinned_host);
+    HY_TRY(fetch_groups(out, GroupArrays{staged.keys, staged.first, staged.last, staged.values, staged.counts}, false, run.words, run.a.n_aggregates, run.stream));
+  } else {
+    HY_TRY(fetch_groups(out, GroupArrays{table.c_keys.ptr, table.c_first.ptr, table.c_last.ptr, table.c_values.ptr, table.c_counts.ptr}, true, run.words, run.a.n_aggregates, run.stream));
+  }
+  run.laps.since_last("groups copied", round);
+  return HY_OK;
+}
+
+// Runs the route for the columns wired into `run.a` (GROUP BY and device accumulators) + compact_groups, until the flags are content: a
+// larger global table when it overflows (the number of groups is not known: 64 Ki slots, then 2 Mi, then 32 Mi, then two slots per row,
+// which never overflows), the partitioned path when aggregate_rows gives up, the general kernel when a small-domain one refuses.
+static hy_status device_groups(GroupsRun& run, DeviceGroups& out) {
+  run.stream = current_stream();
+  run.words = run.a.n_groupby + 1;
+  while (run.two_per_row < 2 * run.shape->rows + 1024) run.two_per_row <<= 1;
+  const uint64_t ladder[4] = {std::max<uint64_t>(1u << 16, 2 * uint64_t{LDS_SLOTS}), 1u << 21, 1u << 25, run.two_per_row};
+  std::memset(&run.pa, 0, sizeof(run.pa));
+  // (the seventeen-word build -- nine to sixteen GROUP BY columns -- keeps to aggregate_rows and the global table: the partitioning kernels
+  //  are instantiated per tuple size, and eight more sizes of them for plans this rare would double the library's build time)
+  run.can_partition = !run.fused && run.a.n_groupby > 0 && run.shape->rows < (1ull << 32) && FIXED_AGG_PARTITIONS && MAX_GROUPBY <= 8;
+  run.partition_bits = starting_partition_bits(run);
+  t_aggregate_next_path = 0;   // (consumed by this call)
+  t_aggregate_recommended = 0;
+  for (int round = 0; round < 12; ++round) {
+    if (run.partition_bits && run.rung == 0) run.rung = 1;   // many groups are a given on this path
+    const uint64_t capacity = std::min(ladder[run.rung], run.two_per_row);
+    if (capacity > (1ull << 31)) return fail(HY_ERR_UNSUPPORTED, "too many rows for the device group table");
+    // (the partitioned path's groups mostly bypass the global table: room for 8 Mi of them whatever its size)
+    const uint32_t out_capacity = static_cast<uint32_t>(std::min<uint64_t>(run.partition_bits ? std::max<uint64_t>(capacity, 1u << 23) : capacity, run.shape->rows + 1));
+    GroupTable table;
+    HY_TRY(table.alloc(capacity, out_capacity, run.words, accumulators_per_group(run.a.n_aggregates), run.stream));
+    run.laps.since_last("table allocated", round);
+    table.bind(run.a);
+    run.a.spill_limit = spill_limit(run);
+    run.a.trace = trace_stamps(run.shape, run.stream);
+    HY_TRY(launch_route(run, table));
+    run.laps.since_last("kernels launched", round);
+    hipLaunchKernelGGL(compact_groups, dim3(static_cast<uint32_t>((capacity + COMPACT_THREADS - 1) / COMPACT_THREADS)), dim3(COMPACT_THREADS), 0, run.stream, run.a, table.group_counter(),
+                       table.c_keys.as<uint64_t>(), table.c_first.as<uint64_t>(), table.c_last.as<uint64_t>(), table.c_values.as<uint64_t>(), table.c_counts.as<uint64_t>(), out_capacity,
+                       table.staged_arrays(table.pinned_dev));
+    hipLaunchKernelGGL(publish_group_flags, dim3(1), dim3(1), 0, run.stream, table.flags.as<uint32_t>(), static_cast<uint32_t*>(table.pinned_dev));
+    run.laps.since_last("compact launched", round);
+    HY_HIP(hipStreamSynchronize(run.stream));
+    run.laps.since_last("device finished", round);
+    uint32_t host_flags[7];
+    std::memcpy(host_flags, table.pinned_host, 28);
+    Step step = Step::done;
+    HY_TRY(next_step(host_flags, out_capacity, run, &step));
+    if (step != Step::done) continue;
+    out.n_groups = host_flags[FLAG_GROUPS];
+    out.passed_rows = static_cast<uint64_t>(host_flags[5]) << 32 | host_flags[4];
+    remember_path(run, out.n_groups);
+    return hand_over(run, table, out, round);
   }
   return fail(HY_ERR_DEVICE, "the device group table did not settle (internal error)");
 }
-
 
 // Some value of a column (its first non-NULL one among the first rows of the chunks), as a double: STDDEV_SAMP accumulates
 // sum(x - pivot) and sum((x - pivot)^2).  The reference runs Welford's recurrence (abstract_aggregate_operator.hpp:83-113);
@@ -3036,7 +3105,7 @@ struct ChunkedColumn {
   uint64_t units() const { return uint64_t{n_chunks} * words_per_chunk; }   // (chunk, 64-row word) pairs: a wave each
   hy_status alloc(uint32_t data_type, uint64_t n_rows, uint32_t rows_per_chunk) {
     type = data_type;
-    width = (type == HY_TYPE_INT || type == HY_TYPE_FLOAT) ? 4 : 8;
+    width = static_cast<uint32_t>(value_width(type));
     rows = n_rows;
     chunk_rows = rows_per_chunk;
     n_chunks = static_cast<uint32_t>((n_rows + rows_per_chunk - 1) / rows_per_chunk);
@@ -3107,588 +3176,683 @@ struct FusedQuery {
   uint32_t same_as[MAX_AGGREGATES];
 };
 
-static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_groupby, const hy_aggregate_spec* specs, uint32_t n_aggregates,
-                               hy_aggregate_result* result, const FusedQuery* fused = nullptr, ColumnSink* sink = nullptr) {
-  if (n_groupby > MAX_GROUPBY) return fail(HY_ERR_UNSUPPORTED, "more than %u GROUP BY columns stay on the CPU path", MAX_GROUPBY);
-  if (n_aggregates > MAX_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "more than %u aggregates stay on the CPU path", MAX_AGGREGATES);
-  const hy_column* shape = fused ? fused->shape : n_groupby ? groupby[0] : nullptr;
-  for (uint32_t g = 0; g < n_aggregates && !shape; ++g) shape = specs[g].column;
-  if (!shape) return fail(HY_ERR_INVALID, "hy_aggregate_hash needs at least one column (pass any column of the table for a lone COUNT(*))");
+// ---- one aggregate call, resolved ------------------------------------------------------------------------------------------------------
+// Everything run_aggregate's stages need to know about the call, decided before any allocation or launch.
+struct AggregateRequest {
+  const hy_column* shape = nullptr;            // the table's chunk layout: the fused query's, the first GROUP BY column, else a spec's column
+  const hy_column* const* groupby = nullptr;
+  uint32_t n_groupby = 0;
+  const hy_aggregate_spec* specs = nullptr;
+  uint32_t n_aggregates = 0;
+  const FusedQuery* fused = nullptr;           // hy_scan_project_aggregate: the specs carry no columns, input g is fused->inputs[g]
+  ColumnSink* sink = nullptr;                  // hy_aggregate_hash_columns
+  // Device accumulators.  STDDEV_SAMP takes two (sum of x - pivot as double + count, sum of (x - pivot)^2); COUNT(DISTINCT) takes none: it
+  // is a second grouping by (GROUP BY columns, aggregate column) whose groups are counted per outer group.
+  int primary[MAX_AGGREGATES], secondary[MAX_AGGREGATES];   // per aggregate, -1: none
+  uint32_t spec_of_device[MAX_AGGREGATES] = {};             // per accumulator: whose column / expression feeds it
+  uint32_t n_device = 0;
+  uint32_t input_type[MAX_AGGREGATES] = {}, result_type[MAX_AGGREGATES] = {};
+  bool is_float[MAX_AGGREGATES] = {};          // the input is accumulated as double
+  bool reads_references = false;               // some wired column is a reference column (aggregate_rows' pos_cache)
+  bool keep_on_device = false;                 // a large result of plain aggregates is finished on the device; everything else comes to the host
+  const hy_column* hint_owner = nullptr;       // GroupsRun's
+  uint64_t hint_signature = 0;
+  AggArgs a;
+
+  uint32_t words() const { return n_groupby + 1; }
   // what an aggregate reads: a column, or (fused) an expression -- known to the accumulators only by its type and by a non-null marker
-  static const DevSegment expression_marker{};
-  auto has_input = [&](uint32_t g) { return fused ? fused->inputs[g].n_nodes != 0 : specs[g].column != nullptr; };
-  auto input_type = [&](uint32_t g) -> uint32_t { return fused ? (fused->inputs[g].n_nodes ? fused->inputs[g].type : static_cast<uint32_t>(HY_TYPE_LONG))
-                                                                : (specs[g].column ? specs[g].column->data_type : static_cast<uint32_t>(HY_TYPE_LONG)); };
-  auto same_input = [&](uint32_t x, uint32_t y) { return fused ? fused->same_as[x] == fused->same_as[y] : specs[x].column == specs[y].column; };
-  auto same_shape = [&](const hy_column* c) {
+  bool has_input(uint32_t g) const { return fused ? fused->inputs[g].n_nodes != 0 : specs[g].column != nullptr; }
+  bool same_input(uint32_t x, uint32_t y) const { return fused ? fused->same_as[x] == fused->same_as[y] : specs[x].column == specs[y].column; }
+  bool same_shape(const hy_column* c) const {
     if (c->n_chunks != shape->n_chunks || c->is_mvcc || (c->ref && c->ref->is_mvcc)) return false;
     for (uint32_t k = 0; k < c->n_chunks; ++k) if (c->host_segments[k].size != shape->host_segments[k].size) return false;
     return true;
-  };
-  bool reads_references = false;
-  auto wire = [&reads_references](AggColumn& slot, const hy_column* column, uint32_t function) {
-    if (column && column->is_reference) reads_references = true;
-    slot.segments = column ? column->d_segments : nullptr;
-    slot.data_type = column ? column->data_type : static_cast<uint32_t>(HY_TYPE_LONG);
-    slot.is_float = column && (column->data_type == HY_TYPE_FLOAT || column->data_type == HY_TYPE_DOUBLE);
-    slot.function = function;
-  };
-  auto wire_expression = [&](AggColumn& slot, uint32_t g, uint32_t function) {
-    slot.segments = has_input(g) ? &expression_marker : nullptr;   // (never dereferenced: fused_rows evaluates FusedPlan::inputs)
-    slot.data_type = input_type(g);
-    slot.is_float = has_input(g) && (slot.data_type == HY_TYPE_FLOAT || slot.data_type == HY_TYPE_DOUBLE);
-    slot.function = function;
-  };
-  AggArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.n_groupby = n_groupby;
+  }
+  FinishColumn finish_column(uint32_t g) const { return FinishColumn{specs[g].function, result_type[g], is_float[g] ? 1u : 0u, static_cast<uint32_t>(primary[g])}; }
+};
+
+static void wire(AggColumn& slot, const hy_column* column, uint32_t function) {
+  slot.segments = column ? column->d_segments : nullptr;
+  slot.data_type = column ? column->data_type : static_cast<uint32_t>(HY_TYPE_LONG);
+  slot.is_float = column && is_float_type(column->data_type);
+  slot.function = function;
+}
+static void wire_expression(AggColumn& slot, const AggregateRequest& r, uint32_t g, uint32_t function) {
+  static const DevSegment expression_marker{};
+  slot.segments = r.has_input(g) ? &expression_marker : nullptr;   // (never dereferenced: fused_rows evaluates FusedPlan::inputs)
+  slot.data_type = r.input_type[g];
+  slot.is_float = r.is_float[g];
+  slot.function = function;
+}
+
+// Accumulators with a column first, COUNT(*) last: the partitioned path carries the contributions of a prefix.
+static void columns_first(AggregateRequest& r) {
+  uint32_t place[MAX_AGGREGATES], next = 0;
+  for (uint32_t d = 0; d < r.n_device; ++d) if (r.a.aggregates[d].segments) place[d] = next++;
+  for (uint32_t d = 0; d < r.n_device; ++d) if (!r.a.aggregates[d].segments) place[d] = next++;
+  AggColumn wired[MAX_AGGREGATES];
+  uint32_t spec_of[MAX_AGGREGATES];
+  for (uint32_t d = 0; d < r.n_device; ++d) { wired[place[d]] = r.a.aggregates[d]; spec_of[place[d]] = r.spec_of_device[d]; }
+  for (uint32_t d = 0; d < r.n_device; ++d) { r.a.aggregates[d] = wired[d]; r.spec_of_device[d] = spec_of[d]; }
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) {
+    if (r.primary[g] >= 0) r.primary[g] = static_cast<int>(place[r.primary[g]]);
+    if (r.secondary[g] >= 0) r.secondary[g] = static_cast<int>(place[r.secondary[g]]);
+  }
+}
+
+// The accumulators of aggregate g, after its checks.  SUM and AVG of one floating-point column are the same accumulator (a double sum in
+// row order and a count of the non-NULL rows): TPC-H Q1 asks for both of l_quantity and of l_extendedprice.  (Integer columns: SUM adds
+// int64, AVG adds doubles -- two accumulators.)
+static hy_status resolve_aggregate(AggregateRequest& r, uint32_t g) {
+  const hy_aggregate_spec& spec = r.specs[g];
+  if (spec.function > HY_AGG_ANY) return fail(HY_ERR_INVALID, "unknown aggregate function %u", spec.function);
+  if (!r.has_input(g) && spec.function != HY_AGG_COUNT) return fail(HY_ERR_INVALID, "only COUNT may omit its column (aggregate_hash.cpp:1002)");
+  if (r.fused && spec.function > HY_AGG_COUNT) return fail(HY_ERR_UNSUPPORTED, "hy_scan_project_aggregate: MIN / MAX / SUM / AVG / COUNT only -- run the operator chain for function %u", spec.function);
+  if (spec.column) {
+    if (!r.same_shape(spec.column)) return fail(HY_ERR_INVALID, "aggregate column %u does not have the table's chunk layout", g);
+    if (spec.column->data_type == HY_TYPE_STRING && spec.function != HY_AGG_COUNT) return fail(HY_ERR_UNSUPPORTED, "string aggregates stay on the CPU path");
+  }
+  if (spec.function == HY_AGG_COUNT_DISTINCT) {
+    if (r.n_groupby + 1 > MAX_GROUPBY) return fail(HY_ERR_UNSUPPORTED, "COUNT(DISTINCT) with %u GROUP BY columns stays on the CPU path", r.n_groupby);
+    return HY_OK;
+  }
+  if (r.is_float[g] && (spec.function == HY_AGG_SUM || spec.function == HY_AGG_AVG)) {
+    for (uint32_t earlier = 0; earlier < g && r.primary[g] < 0; ++earlier) {
+      if (r.has_input(earlier) && r.same_input(earlier, g) && (r.specs[earlier].function == HY_AGG_SUM || r.specs[earlier].function == HY_AGG_AVG)) r.primary[g] = r.primary[earlier];
+    }
+    if (r.primary[g] >= 0) return HY_OK;
+  }
+  const bool stddev = spec.function == HY_AGG_STDDEV_SAMP;
+  if (r.n_device + (stddev ? 2 : 1) > MAX_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "more than %u device accumulators stay on the CPU path", MAX_AGGREGATES);
+  r.primary[g] = static_cast<int>(r.n_device);
+  r.spec_of_device[r.n_device] = g;
+  if (r.fused) {
+    wire_expression(r.a.aggregates[r.n_device++], r, g, spec.function);
+    return HY_OK;
+  }
+  if (spec.column && spec.column->is_reference) r.reads_references = true;
+  wire(r.a.aggregates[r.n_device++], spec.column, stddev ? AGG_SUM_SHIFTED : spec.function);
+  if (stddev) {
+    r.secondary[g] = static_cast<int>(r.n_device);
+    wire(r.a.aggregates[r.n_device++], spec.column, AGG_SUM_SQUARES);   // (both pivots: stddev_pivots)
+  }
+  return HY_OK;
+}
+
+// Checks the call and decides everything that needs no device work: every refusal but HY_ERR_CAPACITY comes from here.
+static hy_status resolve_aggregate_request(const hy_column* const* groupby, uint32_t n_groupby, const hy_aggregate_spec* specs, uint32_t n_aggregates,
+                                           const hy_aggregate_result* result, const FusedQuery* fused, ColumnSink* sink, AggregateRequest& r) {
+  if (n_groupby > MAX_GROUPBY) return fail(HY_ERR_UNSUPPORTED, "more than %u GROUP BY columns stay on the CPU path", MAX_GROUPBY);
+  if (n_aggregates > MAX_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "more than %u aggregates stay on the CPU path", MAX_AGGREGATES);
+  r.groupby = groupby, r.n_groupby = n_groupby, r.specs = specs, r.n_aggregates = n_aggregates, r.fused = fused, r.sink = sink;
+  r.shape = fused ? fused->shape : n_groupby ? groupby[0] : nullptr;
+  for (uint32_t g = 0; g < n_aggregates && !r.shape; ++g) r.shape = specs[g].column;
+  if (!r.shape) return fail(HY_ERR_INVALID, "hy_aggregate_hash needs at least one column (pass any column of the table for a lone COUNT(*))");
+  std::memset(&r.a, 0, sizeof(r.a));
+  r.a.n_groupby = n_groupby;
   for (uint32_t g = 0; g < n_groupby; ++g) {
-    if (!groupby[g] || !same_shape(groupby[g])) return fail(HY_ERR_INVALID, "GROUP BY column %u does not have the table's chunk layout", g);
+    if (!groupby[g] || !r.same_shape(groupby[g])) return fail(HY_ERR_INVALID, "GROUP BY column %u does not have the table's chunk layout", g);
     if (groupby[g]->data_type == HY_TYPE_STRING) return fail(HY_ERR_UNSUPPORTED, "string GROUP BY columns must be passed as dictionary segments of int64 key names (INTEGRATION.md)");
-    wire(a.groupby[g], groupby[g], 0);
+    if (groupby[g]->is_reference) r.reads_references = true;
+    wire(r.a.groupby[g], groupby[g], 0);
   }
-  // Device accumulators.  STDDEV_SAMP takes two (sum of x - pivot as double + count, sum of (x - pivot)^2); COUNT(DISTINCT) takes none: it
-  // is a second grouping by (GROUP BY columns, aggregate column) whose groups are counted per outer group.
-  std::vector<int> primary(n_aggregates, -1), secondary(n_aggregates, -1);
-  uint32_t n_device = 0;
-  uint32_t spec_of_device[MAX_AGGREGATES] = {0, 0, 0, 0, 0, 0, 0, 0};   // (fused: whose expression feeds the accumulator)
   for (uint32_t g = 0; g < n_aggregates; ++g) {
-    const hy_aggregate_spec& spec = specs[g];
-    if (spec.function > HY_AGG_ANY) return fail(HY_ERR_INVALID, "unknown aggregate function %u", spec.function);
-    if (!has_input(g) && spec.function != HY_AGG_COUNT) return fail(HY_ERR_INVALID, "only COUNT may omit its column (aggregate_hash.cpp:1002)");
-    if (fused && spec.function > HY_AGG_COUNT) return fail(HY_ERR_UNSUPPORTED, "hy_scan_project_aggregate: MIN / MAX / SUM / AVG / COUNT only -- run the operator chain for function %u", spec.function);
-    if (spec.column) {
-      if (!same_shape(spec.column)) return fail(HY_ERR_INVALID, "aggregate column %u does not have the table's chunk layout", g);
-      if (spec.column->data_type == HY_TYPE_STRING && spec.function != HY_AGG_COUNT) return fail(HY_ERR_UNSUPPORTED, "string aggregates stay on the CPU path");
-    }
-    if (spec.function == HY_AGG_COUNT_DISTINCT) {
-      if (n_groupby + 1 > MAX_GROUPBY) return fail(HY_ERR_UNSUPPORTED, "COUNT(DISTINCT) with %u GROUP BY columns stays on the CPU path", n_groupby);
-      continue;
-    }
-    // SUM and AVG of one floating-point column are the same accumulator (a double sum in row order and a count of the
-    // non-NULL rows): TPC-H Q1 asks for both of l_quantity and of l_extendedprice.  (Integer columns: SUM adds int64,
-    // AVG adds doubles -- two accumulators.)
-    const bool float_column = has_input(g) && (input_type(g) == HY_TYPE_FLOAT || input_type(g) == HY_TYPE_DOUBLE);
-    if (float_column && (spec.function == HY_AGG_SUM || spec.function == HY_AGG_AVG)) {
-      for (uint32_t earlier = 0; earlier < g && primary[g] < 0; ++earlier) {
-        if (has_input(earlier) && same_input(earlier, g) && (specs[earlier].function == HY_AGG_SUM || specs[earlier].function == HY_AGG_AVG)) primary[g] = primary[earlier];
-      }
-      if (primary[g] >= 0) continue;
-    }
-    const uint32_t wanted = spec.function == HY_AGG_STDDEV_SAMP ? 2 : 1;
-    if (n_device + wanted > MAX_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "more than %u device accumulators stay on the CPU path", MAX_AGGREGATES);
-    primary[g] = static_cast<int>(n_device);
-    spec_of_device[n_device] = g;
-    if (fused) {
-      wire_expression(a.aggregates[n_device++], g, spec.function);
-      continue;
-    }
-    wire(a.aggregates[n_device++], spec.column, spec.function == HY_AGG_STDDEV_SAMP ? AGG_SUM_SHIFTED : spec.function);
-    if (spec.function == HY_AGG_STDDEV_SAMP) {
-      secondary[g] = static_cast<int>(n_device);
-      wire(a.aggregates[n_device++], spec.column, AGG_SUM_SQUARES);
-      double* pivot_host = nullptr;   // a value of the column to shift by (column_pivot above)
-      double* pivot_dev = nullptr;
-      HY_TRY(pinned_staging(16, reinterpret_cast<void**>(&pivot_host), reinterpret_cast<void**>(&pivot_dev)));
-      pivot_host[0] = pivot_host[1] = 0.0;
-      if (spec.column->n_chunks) {
-        hipLaunchKernelGGL(column_pivot, dim3(1), dim3(256), 0, current_stream(), spec.column->d_segments, spec.column->n_chunks, pivot_dev);
-        HY_HIP(hipStreamSynchronize(current_stream()));
-      }
-      a.aggregates[n_device - 2].pivot = a.aggregates[n_device - 1].pivot = pivot_host[0];
-    }
+    r.primary[g] = r.secondary[g] = -1;
+    r.input_type[g] = fused ? (fused->inputs[g].n_nodes ? fused->inputs[g].type : static_cast<uint32_t>(HY_TYPE_LONG))
+                            : (specs[g].column ? specs[g].column->data_type : static_cast<uint32_t>(HY_TYPE_LONG));
+    r.is_float[g] = is_float_type(r.input_type[g]);
+    r.result_type[g] = result_type(specs[g].function, r.input_type[g]);
+    HY_TRY(resolve_aggregate(r, g));
   }
-  {   // accumulators with a column first, COUNT(*) last: the partitioned path carries the contributions of a prefix
-    AggColumn wired[MAX_AGGREGATES];
-    uint32_t place[MAX_AGGREGATES], next = 0;
-    for (uint32_t d = 0; d < n_device; ++d) wired[d] = a.aggregates[d];
-    for (uint32_t d = 0; d < n_device; ++d) if (wired[d].segments) place[d] = next++;
-    for (uint32_t d = 0; d < n_device; ++d) if (!wired[d].segments) place[d] = next++;
-    for (uint32_t d = 0; d < n_device; ++d) a.aggregates[place[d]] = wired[d];
-    {
-      uint32_t moved[MAX_AGGREGATES];
-      for (uint32_t d = 0; d < n_device; ++d) moved[place[d]] = spec_of_device[d];
-      for (uint32_t d = 0; d < n_device; ++d) spec_of_device[d] = moved[d];
-    }
-    for (uint32_t g = 0; g < n_aggregates; ++g) {
-      if (primary[g] >= 0) primary[g] = static_cast<int>(place[primary[g]]);
-      if (secondary[g] >= 0) secondary[g] = static_cast<int>(place[secondary[g]]);
-    }
+  columns_first(r);
+  r.a.n_aggregates = r.n_device;
+  r.a.slices = r.shape->d_slices;
+  r.a.row_base = r.shape->d_row_base;
+  r.a.pos_cache = !fused && r.reads_references ? 1u : 0u;
+  r.keep_on_device = n_groupby > 0 && r.shape->rows < (1ull << 32);
+  for (uint32_t g = 0; g < n_aggregates && r.keep_on_device; ++g) {
+    const uint32_t f = specs[g].function;
+    r.keep_on_device = r.primary[g] >= 0 && (f == HY_AGG_COUNT || f == HY_AGG_SUM || f == HY_AGG_AVG || f == HY_AGG_MIN || f == HY_AGG_MAX) && (sink || result->columns[g].values);
   }
-  a.n_aggregates = n_device;
-  a.slices = shape->d_slices;
-  a.row_base = shape->d_row_base;
-  hipStream_t stream = current_stream();
-  const uint32_t words = n_groupby + 1;
+  if (!fused && n_groupby) {
+    uint64_t signature = 0x9E3779B97F4A7C15ull * (n_groupby + 1);
+    for (uint32_t g = 0; g < n_groupby; ++g) signature = (signature ^ reinterpret_cast<uintptr_t>(groupby[g])) * 0xD6E8FEB86659FD93ull;
+    r.hint_owner = groupby[0];
+    r.hint_signature = signature | 0x100;   // (never zero above the path byte)
+  }
+  return HY_OK;
+}
 
-  const bool timing = HY_DEBUG_ENV("HY_AGG_TIMING") != nullptr;
-  const auto t_start = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (timing) std::fprintf(stderr, "[aggregate] %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
-  };
-  auto dictionary_column = [&](const hy_column* column, uint32_t* width) {   // every chunk a dictionary segment with its values on the device, one id width, aligned
-    if (!column || column->is_reference || column->has_dictionary_without_values || column->n_chunks == 0) return false;
-    *width = column->host_segments[0].width;
-    if (*width != 1 && *width != 2) return false;
-    for (uint32_t k = 0; k < column->n_chunks; ++k) {
-      const hy_segment& seg = column->host_segments[k];
-      if (seg.encoding != HY_ENC_DICTIONARY || seg.width != *width || (!seg.aux && seg.aux_size) || reinterpret_cast<uintptr_t>(seg.data) % 16 != 0 || (*width == 1 && seg.aux_size > 255)) return false;
+// STDDEV_SAMP: a value of the column to shift by (column_pivot above), for both of its accumulators
+static hy_status stddev_pivots(AggregateRequest& r) {
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) {
+    if (r.secondary[g] < 0) continue;
+    const hy_column* column = r.specs[g].column;
+    double* pivot_host = nullptr;
+    double* pivot_dev = nullptr;
+    HY_TRY(pinned_staging(16, reinterpret_cast<void**>(&pivot_host), reinterpret_cast<void**>(&pivot_dev)));
+    pivot_host[0] = pivot_host[1] = 0.0;
+    if (column->n_chunks) {
+      hipLaunchKernelGGL(column_pivot, dim3(1), dim3(256), 0, current_stream(), column->d_segments, column->n_chunks, pivot_dev);
+      HY_HIP(hipStreamSynchronize(current_stream()));
     }
-    return true;
-  };
-  // every chunk a dictionary segment, one width of 1 or 2 bytes per value id, aligned (the dictionary's values may be anywhere: filters test ids)
-  auto value_id_column = [&](const hy_column* column, uint32_t* width) {
-    if (!column || column->is_reference || column->n_chunks == 0) return false;
-    *width = column->host_segments[0].width;
-    if (*width != 1 && *width != 2) return false;
-    for (uint32_t k = 0; k < column->n_chunks; ++k) {
-      const hy_segment& seg = column->host_segments[k];
-      if (seg.encoding != HY_ENC_DICTIONARY || seg.width != *width || reinterpret_cast<uintptr_t>(seg.data) % 16 != 0) return false;
-    }
-    return true;
-  };
-  auto few_codes = [&]() {   // the GROUP BY columns of the small-domain kernels: 1-byte value ids, at most SD_CODES combinations per chunk
-    if (n_groupby > SD_KEYS) return false;
-    for (uint32_t g = 0; g < n_groupby; ++g) {
-      uint32_t key_width = 0;
-      if (!dictionary_column(groupby[g], &key_width) || key_width != 1) return false;
-    }
-    for (uint32_t k = 0; k < shape->n_chunks; ++k) {
-      uint64_t product = 1;
-      for (uint32_t g = 0; g < n_groupby; ++g) product *= uint64_t{groupby[g]->host_segments[k].aux_size} + 1;
-      if (product > SD_CODES) return false;
-    }
-    return true;
-  };
-  DeviceGroups main_groups;
-  {   // a large result of plain aggregates is finished on the device (finish kernels above); everything else comes to the host
-    bool plain_functions = n_groupby > 0 && result->mem == HY_MEM_HOST && shape->rows < (1ull << 32);
-    for (uint32_t g = 0; g < n_aggregates && plain_functions; ++g) {
-      const uint32_t f = specs[g].function;
-      plain_functions = primary[g] >= 0 && (f == HY_AGG_COUNT || f == HY_AGG_SUM || f == HY_AGG_AVG || f == HY_AGG_MIN || f == HY_AGG_MAX) && (sink || result->columns[g].values);
-    }
-    main_groups.keep_on_device = plain_functions;
-    if (!fused && n_groupby) {
-      uint64_t signature = 0x9E3779B97F4A7C15ull * (n_groupby + 1);
-      for (uint32_t g = 0; g < n_groupby; ++g) signature = (signature ^ reinterpret_cast<uintptr_t>(groupby[g])) * 0xD6E8FEB86659FD93ull;
-      main_groups.hint_owner = groupby[0];
-      main_groups.hint_signature = signature | 0x100;   // (never zero above the path byte)
-    }
+    r.a.aggregates[r.primary[g]].pivot = r.a.aggregates[r.secondary[g]].pivot = pivot_host[0];
   }
-  if (fused) {
-    // the plan in device memory: per filter the chunk jobs (prepare_jobs, like hy_table_scan), per accumulator its input expression
-    const uint32_t n_chunks = shape->n_chunks;
-    std::vector<size_t> staging_at(fused->n_filters + 1, 0);
-    for (uint32_t f = 0; f < fused->n_filters; ++f) {
-      const bool validate = fused->filters[f].predicate.condition == HY_FILTER_VALIDATE;
-      staging_at[f + 1] = staging_at[f] + (validate ? 256 : align_up(scan_jobs_staging_bytes(fused->filters[f].column, &fused->filters[f].predicate), 256));
+  return HY_OK;
+}
+
+// The fused plan in device memory: per filter the chunk jobs (prepare_jobs, like hy_table_scan), per accumulator its input expression.
+// `plan` is the host copy, which lives until device_groups has waited for the stream.
+static hy_status build_fused_plan(const AggregateRequest& r, DeviceBuffer& plan_buffer, FusedPlan& plan) {
+  const FusedQuery& q = *r.fused;
+  std::vector<size_t> staging_at(q.n_filters + 1, 0);
+  for (uint32_t f = 0; f < q.n_filters; ++f) {
+    const bool validate = q.filters[f].predicate.condition == HY_FILTER_VALIDATE;
+    staging_at[f + 1] = staging_at[f] + (validate ? 256 : align_up(scan_jobs_staging_bytes(q.filters[f].column, &q.filters[f].predicate), 256));
+  }
+  const size_t jobs_bytes = align_up(sizeof(ScanJob) * (size_t{r.shape->n_chunks} + 1), 256);
+  HY_TRY(plan_buffer.alloc(align_up(sizeof(FusedPlan), 256) + jobs_bytes * q.n_filters + staging_at[q.n_filters] + 256));
+  char* base = plan_buffer.as<char>();
+  char* jobs_base = base + align_up(sizeof(FusedPlan), 256);
+  char* staging_base = jobs_base + jobs_bytes * q.n_filters;
+  std::memset(&plan, 0, sizeof(plan));
+  plan.n_filters = q.n_filters;
+  for (uint32_t f = 0; f < q.n_filters; ++f) {
+    ScanJob* jobs = reinterpret_cast<ScanJob*>(jobs_base + jobs_bytes * f);
+    const hy_predicate& predicate = q.filters[f].predicate;
+    if (predicate.condition == HY_FILTER_VALIDATE) HY_TRY(prepare_visibility_scan_jobs(q.filters[f].column, predicate.value.value_id, predicate.value2.value_id, predicate.column_is_nullable, jobs, staging_base + staging_at[f]));
+    else HY_TRY(prepare_scan_jobs(q.filters[f].column, &predicate, jobs, staging_base + staging_at[f]));
+    plan.filters[f].segments = q.filters[f].column->d_segments;
+    plan.filters[f].jobs = jobs;
+  }
+  plan.n_columns = q.n_columns;
+  plan.lds_slots = fused_lds_slots(r.n_groupby);
+  plan.debug = HY_DEBUG_ENV("HY_FUSED_DEBUG") ? static_cast<uint32_t>(atoi(HY_DEBUG_ENV("HY_FUSED_DEBUG"))) : 0u;
+  for (uint32_t c = 0; c < q.n_columns; ++c) plan.columns[c] = q.columns[c]->d_segments;
+  for (uint32_t d = 0; d < r.n_device; ++d) plan.inputs[d] = q.inputs[r.spec_of_device[d]];
+  HY_HIP(hipMemcpyAsync(base, &plan, sizeof(plan), hipMemcpyHostToDevice, current_stream()));
+  return HY_OK;
+}
+
+// Every chunk a dictionary segment, one width of 1 or 2 bytes per value id, aligned.  `with_values`: and the dictionaries' values on the
+// device, at most 255 of them behind 1-byte ids (without: the values may be anywhere -- filters test ids).
+static bool value_id_column(const hy_column* column, uint32_t* width, bool with_values) {
+  if (!column || column->is_reference || column->n_chunks == 0 || (with_values && column->has_dictionary_without_values)) return false;
+  *width = column->host_segments[0].width;
+  if (*width != 1 && *width != 2) return false;
+  for (uint32_t k = 0; k < column->n_chunks; ++k) {
+    const hy_segment& seg = column->host_segments[k];
+    if (seg.encoding != HY_ENC_DICTIONARY || seg.width != *width || reinterpret_cast<uintptr_t>(seg.data) % 16 != 0) return false;
+    if (with_values && ((!seg.aux && seg.aux_size) || (*width == 1 && seg.aux_size > 255))) return false;
+  }
+  return true;
+}
+
+// the GROUP BY columns of the small-domain kernels: 1-byte value ids, at most SD_CODES combinations per chunk
+static bool few_codes(const AggregateRequest& r) {
+  if (r.n_groupby > SD_KEYS) return false;
+  for (uint32_t g = 0; g < r.n_groupby; ++g) {
+    uint32_t key_width = 0;
+    if (!value_id_column(r.groupby[g], &key_width, true) || key_width != 1) return false;
+  }
+  for (uint32_t k = 0; k < r.shape->n_chunks; ++k) {
+    uint64_t product = 1;
+    for (uint32_t g = 0; g < r.n_groupby; ++g) product *= uint64_t{r.groupby[g]->host_segments[k].aux_size} + 1;
+    if (product > SD_CODES) return false;
+  }
+  return true;
+}
+static bool chunks_within(const hy_column* shape, uint32_t rows) {
+  for (uint32_t k = 0; k < shape->n_chunks; ++k) if (shape->host_segments[k].size > rows) return false;
+  return true;
+}
+
+// fused_small_domain's program for accumulator d: five bits per node, literals by their index in a table of FS_LITERALS.  An input that
+// begins with the whole of the input before it (Q1: l_extendedprice, then l_extendedprice * (1 - l_discount), then that * (1 + l_tax))
+// continues on its stack.
+static bool fused_small_program(const FusedPlan& plan, uint32_t d, uint32_t n_columns, FusedSmallPlan& small, uint32_t* n_literals) {
+  const FusedInput& input = plan.inputs[d];
+  uint32_t skipped = 0;
+  if (d > 0 && plan.inputs[d - 1].n_nodes > 0 && plan.inputs[d - 1].n_nodes < input.n_nodes &&
+      std::memcmp(plan.inputs[d - 1].nodes, input.nodes, sizeof(FusedNode) * plan.inputs[d - 1].n_nodes) == 0 && FIXED_FUSED_SHARED_PREFIX) {
+    skipped = plan.inputs[d - 1].n_nodes;
+  }
+  for (uint32_t n = skipped; n < input.n_nodes; ++n) {
+    const FusedNode& node = input.nodes[n];
+    uint64_t code = 0;
+    if (node.kind == HY_EXPR_COLUMN) {
+      if (node.column >= n_columns) return false;
+      code = FS_PUSH_COLUMN + small.slot_of_column[node.column];
+    } else if (node.kind == HY_EXPR_LITERAL) {
+      uint32_t index = 0;
+      while (index < *n_literals && small.literal[index] != static_cast<uint32_t>(node.literal)) ++index;
+      if (index == *n_literals) {
+        if (*n_literals == FS_LITERALS) return false;
+        small.literal[(*n_literals)++] = static_cast<uint32_t>(node.literal);
+      }
+      code = FS_PUSH_LITERAL + index;
+    } else {
+      code = node.op == HY_ARITH_ADD ? FS_ADD : node.op == HY_ARITH_SUB ? FS_SUB : FS_MUL;
     }
-    const size_t jobs_bytes = align_up(sizeof(ScanJob) * (size_t{n_chunks} + 1), 256);
-    DeviceBuffer plan_buffer;
-    HY_TRY(plan_buffer.alloc(align_up(sizeof(FusedPlan), 256) + jobs_bytes * fused->n_filters + staging_at[fused->n_filters] + 256));
-    char* base = plan_buffer.as<char>();
-    char* jobs_base = base + align_up(sizeof(FusedPlan), 256);
-    char* staging_base = jobs_base + jobs_bytes * fused->n_filters;
-    FusedPlan plan;
-    std::memset(&plan, 0, sizeof(plan));
-    plan.n_filters = fused->n_filters;
-    for (uint32_t f = 0; f < fused->n_filters; ++f) {
-      ScanJob* jobs = reinterpret_cast<ScanJob*>(jobs_base + jobs_bytes * f);
-      const hy_predicate& predicate = fused->filters[f].predicate;
-      if (predicate.condition == HY_FILTER_VALIDATE) HY_TRY(prepare_visibility_scan_jobs(fused->filters[f].column, predicate.value.value_id, predicate.value2.value_id, predicate.column_is_nullable, jobs, staging_base + staging_at[f]));
-      else HY_TRY(prepare_scan_jobs(fused->filters[f].column, &predicate, jobs, staging_base + staging_at[f]));
-      plan.filters[f].segments = fused->filters[f].column->d_segments;
-      plan.filters[f].jobs = jobs;
+    small.program[d] |= code << (5 * (n - skipped));
+  }
+  small.n_nodes |= (input.n_nodes - skipped) << (4 * d);
+  return true;
+}
+
+// fused_small_domain's slots for the columns the expressions read: 1-byte value ids in slots 0 .. FS_NARROW - 1, 2-byte value ids in the last
+static bool fused_small_slots(const AggregateRequest& r, FusedSmallPlan& small) {
+  const FusedQuery& q = *r.fused;
+  uint32_t n_narrow = 0;
+  for (uint32_t c = 0; c < q.n_columns; ++c) {
+    uint32_t width = 0, slot = FS_NARROW;
+    if (q.columns[c]->data_type != HY_TYPE_FLOAT || !value_id_column(q.columns[c], &width, true)) return false;
+    if (width == 1) {
+      if (n_narrow == FS_NARROW) return false;
+      slot = n_narrow++;
+    } else {
+      if (small.column_of_slot[FS_NARROW] != 0xFFFFFFFFu) return false;
+      for (uint32_t k = 0; k < r.shape->n_chunks; ++k) if (reinterpret_cast<uintptr_t>(q.columns[c]->host_segments[k].aux) % 16 != 0) return false;   // (staged with 16-byte loads)
     }
-    plan.n_columns = fused->n_columns;
-    plan.lds_slots = fused_lds_slots(n_groupby);
-    plan.debug = HY_DEBUG_ENV("HY_FUSED_DEBUG") ? static_cast<uint32_t>(atoi(HY_DEBUG_ENV("HY_FUSED_DEBUG"))) : 0u;
-    for (uint32_t c = 0; c < fused->n_columns; ++c) plan.columns[c] = fused->columns[c]->d_segments;
-    for (uint32_t d = 0; d < n_device; ++d) plan.inputs[d] = fused->inputs[spec_of_device[d]];
-    HY_HIP(hipMemcpyAsync(base, &plan, sizeof(plan), hipMemcpyHostToDevice, stream));   // (`plan` lives until device_groups below has waited for the stream)
-    // The TPC-H Q1 shape -- a handful of groups, filters on value ids, float expressions over dictionary columns -- has a kernel of its
-    // own (fused_small.hpp); everything else, and whatever that kernel refuses at run time, takes fused_rows.
-    FusedSmallPlan small_plan;
-    std::memset(&small_plan, 0, sizeof(small_plan));
-    for (uint32_t c = 0; c < FS_COLUMNS; ++c) small_plan.column_of_slot[c] = 0xFFFFFFFFu;
-    bool lean = option(HY_OPT_FUSED_SMALL_DOMAIN) && shape->rows > 0 && fused->n_filters <= FS_FILTERS && fused->n_columns <= FS_COLUMNS && few_codes();
-    for (uint32_t k = 0; k < shape->n_chunks && lean; ++k) lean = shape->host_segments[k].size <= FS_SPAN;
-    for (uint32_t f = 0; f < fused->n_filters && lean; ++f) {
-      const uint32_t condition = fused->filters[f].predicate.condition;
-      lean = condition != HY_FILTER_VALIDATE && !(condition >= HY_PRED_IN && condition <= HY_PRED_NOT_LIKE_INSENSITIVE) && value_id_column(fused->filters[f].column, &small_plan.filter_width[f]);
+    small.column_of_slot[slot] = c;
+    small.slot_of_column[c] = slot;
+  }
+  return true;
+}
+
+// The TPC-H Q1 shape -- a handful of groups, filters on value ids, float expressions over dictionary columns -- has a kernel of its own
+// (fused_small.hpp); everything else, and whatever that kernel refuses at run time, takes fused_rows.
+static bool qualify_fused_small(const AggregateRequest& r, const FusedPlan& plan, FusedSmallPlan& small) {
+  const FusedQuery& q = *r.fused;
+  std::memset(&small, 0, sizeof(small));
+  for (uint32_t c = 0; c < FS_COLUMNS; ++c) small.column_of_slot[c] = 0xFFFFFFFFu;
+  if (!option(HY_OPT_FUSED_SMALL_DOMAIN) || r.shape->rows == 0 || q.n_filters > FS_FILTERS || q.n_columns > FS_COLUMNS || !few_codes(r) || !chunks_within(r.shape, FS_SPAN)) return false;
+  for (uint32_t f = 0; f < q.n_filters; ++f) {
+    const uint32_t condition = q.filters[f].predicate.condition;
+    if (condition == HY_FILTER_VALIDATE || (condition >= HY_PRED_IN && condition <= HY_PRED_NOT_LIKE_INSENSITIVE) || !value_id_column(q.filters[f].column, &small.filter_width[f], false)) return false;
+  }
+  if (!fused_small_slots(r, small)) return false;
+  uint32_t n_literals = 0;
+  for (uint32_t d = 0; d < r.n_device; ++d) {
+    const FusedInput& input = plan.inputs[d];
+    const uint32_t function = r.a.aggregates[d].function;
+    if (function != HY_AGG_SUM && function != HY_AGG_AVG && function != HY_AGG_COUNT) return false;
+    if (input.n_nodes == 0) continue;   // COUNT(*): behind the accumulators with an expression
+    if (d >= FS_INPUTS || input.type != HY_TYPE_FLOAT) return false;
+    for (uint32_t n = 0; n < input.n_nodes; ++n) {
+      const FusedNode& node = input.nodes[n];
+      if (node.type != HY_TYPE_FLOAT || !(node.kind == HY_EXPR_COLUMN || node.kind == HY_EXPR_LITERAL || (node.kind == HY_EXPR_ARITHMETIC && node.op <= HY_ARITH_MUL))) return false;
     }
-    uint32_t n_narrow = 0;
-    for (uint32_t c = 0; c < fused->n_columns && lean; ++c) {   // 1-byte value ids: slots 0 .. FS_NARROW - 1; 2-byte value ids: the last slot
+    small.n_inputs = d + 1;
+    if (!fused_small_program(plan, d, q.n_columns, small, &n_literals)) return false;
+  }
+  return true;
+}
+
+// The TPC-H Q1 shape -- a handful of groups over dictionary columns, SUM / AVG / COUNT / MIN / MAX over dictionary-encoded numeric
+// columns with 1- or 2-byte value ids -- has a kernel of its own (aggregate_small.hpp); everything else takes aggregate_rows.
+static bool qualify_small_domain(const AggregateRequest& r, SmallDomainPlan& small) {
+  std::memset(&small, 0, sizeof(small));
+  if (!option(HY_OPT_AGG_SMALL_DOMAIN) || r.shape->rows == 0 || !few_codes(r) || !chunks_within(r.shape, SD_MAX_CHUNK_ROWS)) return false;   // (a chunk is one pass of either kernel)
+  std::vector<const hy_column*> inputs;   // distinct input columns, 1-byte ids first
+  for (int pass = 0; pass < 2; ++pass) {
+    for (uint32_t d = 0; d < r.n_device; ++d) {
+      const hy_column* column = r.specs[r.spec_of_device[d]].column;
+      const uint32_t function = r.a.aggregates[d].function;
+      if (function != HY_AGG_SUM && function != HY_AGG_AVG && function != HY_AGG_COUNT && function != HY_AGG_MIN && function != HY_AGG_MAX) return false;
+      if (!column) continue;
       uint32_t width = 0;
-      lean = fused->columns[c]->data_type == HY_TYPE_FLOAT && dictionary_column(fused->columns[c], &width);
-      if (!lean) break;
-      uint32_t slot = FS_NARROW;
-      if (width == 1) {
-        lean = n_narrow < FS_NARROW;
-        slot = n_narrow++;
-      } else {
-        lean = small_plan.column_of_slot[FS_NARROW] == 0xFFFFFFFFu;
-        for (uint32_t k = 0; k < shape->n_chunks && lean; ++k) lean = reinterpret_cast<uintptr_t>(fused->columns[c]->host_segments[k].aux) % 16 == 0;   // (staged with 16-byte loads)
-      }
-      if (lean) { small_plan.column_of_slot[slot] = c; small_plan.slot_of_column[c] = slot; }
+      if (column->data_type < HY_TYPE_INT || column->data_type > HY_TYPE_DOUBLE || !value_id_column(column, &width, true)) return false;
+      if (width == (pass == 0 ? 1u : 2u) && std::find(inputs.begin(), inputs.end(), column) == inputs.end()) inputs.push_back(column);
     }
-    uint32_t n_literals = 0;
-    for (uint32_t d = 0; d < n_device && lean; ++d) {
-      const FusedInput& input = plan.inputs[d];
-      const uint32_t function = a.aggregates[d].function;
-      lean = function == HY_AGG_SUM || function == HY_AGG_AVG || function == HY_AGG_COUNT;
-      if (input.n_nodes == 0) continue;   // COUNT(*): behind the accumulators with an expression
-      lean = lean && d < FS_INPUTS && input.type == HY_TYPE_FLOAT;
-      for (uint32_t n = 0; n < input.n_nodes && lean; ++n) {
-        const FusedNode& node = input.nodes[n];
-        lean = node.type == HY_TYPE_FLOAT && (node.kind == HY_EXPR_COLUMN || node.kind == HY_EXPR_LITERAL || (node.kind == HY_EXPR_ARITHMETIC && node.op <= HY_ARITH_MUL));
-      }
-      small_plan.n_inputs = d + 1;
-      // the program: five bits per node, literals by their index in a table of FS_LITERALS.  An input that begins with the whole of the
-      // input before it (Q1: l_extendedprice, then l_extendedprice * (1 - l_discount), then that * (1 + l_tax)) continues on its stack.
-      uint32_t skipped = 0;
-      if (d > 0 && plan.inputs[d - 1].n_nodes > 0 && plan.inputs[d - 1].n_nodes < input.n_nodes &&
-          std::memcmp(plan.inputs[d - 1].nodes, input.nodes, sizeof(FusedNode) * plan.inputs[d - 1].n_nodes) == 0 && FIXED_FUSED_SHARED_PREFIX) {
-        skipped = plan.inputs[d - 1].n_nodes;
-      }
-      for (uint32_t n = skipped; n < input.n_nodes && lean; ++n) {
-        const FusedNode& node = input.nodes[n];
-        uint64_t code = 0;
-        if (node.kind == HY_EXPR_COLUMN) {
-          lean = node.column < fused->n_columns;
-          code = FS_PUSH_COLUMN + small_plan.slot_of_column[lean ? node.column : 0];
-        } else if (node.kind == HY_EXPR_LITERAL) {
-          uint32_t index = 0;
-          while (index < n_literals && small_plan.literal[index] != static_cast<uint32_t>(node.literal)) ++index;
-          if (index == n_literals) {
-            lean = n_literals < FS_LITERALS;
-            if (lean) small_plan.literal[n_literals++] = static_cast<uint32_t>(node.literal);
-          }
-          code = FS_PUSH_LITERAL + index;
-        } else {
-          code = node.op == HY_ARITH_ADD ? FS_ADD : node.op == HY_ARITH_SUB ? FS_SUB : FS_MUL;
-        }
-        small_plan.program[d] |= code << (5 * (n - skipped));
-      }
-      small_plan.n_nodes |= (input.n_nodes - skipped) << (4 * d);
-    }
-    HY_TRY(device_groups(a, shape, main_groups, reinterpret_cast<const FusedPlan*>(base), nullptr, lean ? &small_plan : nullptr));
-  } else {
-    // The TPC-H Q1 shape -- a handful of groups over dictionary columns, SUM / AVG / COUNT / MIN / MAX over dictionary-encoded numeric
-    // columns with 1- or 2-byte value ids -- has a kernel of its own (aggregate_small.hpp); everything else takes aggregate_rows.
+    if (pass == 0) small.n_narrow = static_cast<uint32_t>(inputs.size());
+  }
+  if (small.n_narrow > SD_NARROW || inputs.size() - small.n_narrow > SD_WIDE) return false;
+  if (const char* debug = HY_DEBUG_ENV("HY_AGG_SMALL_DEBUG")) small.debug = static_cast<uint32_t>(atoi(debug));   // timing experiments only
+  small.n_columns = static_cast<uint32_t>(inputs.size());
+  small.joint = small.n_narrow == 2 && FIXED_AGG_JOINT_HISTOGRAM ? 1u : 0u;
+  for (uint32_t k = 0; k < r.shape->n_chunks && small.joint; ++k) {
+    if ((uint64_t{inputs[0]->host_segments[k].aux_size} + 1) * (uint64_t{inputs[1]->host_segments[k].aux_size} + 1) > SD_JOINT_CELLS) small.joint = 0;
+  }
+  for (uint32_t c = 0; c < small.n_columns; ++c) small.column[c] = inputs[c]->d_segments;
+  for (uint32_t d = 0; d < r.n_device; ++d) {
+    const hy_column* column = r.specs[r.spec_of_device[d]].column;
+    small.column_of_aggregate[d] = column ? static_cast<uint32_t>(std::find(inputs.begin(), inputs.end(), column) - inputs.begin()) : 0xFFFFFFFFu;
+    if (column && (r.a.aggregates[d].function == HY_AGG_MIN || r.a.aggregates[d].function == HY_AGG_MAX)) small.extremes |= 1u << small.column_of_aggregate[d];
+  }
+  return true;
+}
+
+// The main pass: the request's columns through device_groups, on the route the plans qualify for.
+static hy_status main_groups(const AggregateRequest& r, DeviceGroups& groups) {
+  GroupsRun run;
+  run.a = r.a;
+  run.shape = r.shape;
+  run.keep_on_device = r.keep_on_device;
+  run.hint_owner = r.hint_owner;
+  run.hint_signature = r.hint_signature;
+  if (!r.fused) {
     SmallDomainPlan small;
-    std::memset(&small, 0, sizeof(small));
-    bool lean = option(HY_OPT_AGG_SMALL_DOMAIN) && shape->rows > 0 && few_codes();
-    for (uint32_t k = 0; k < shape->n_chunks && lean; ++k) lean = shape->host_segments[k].size <= SD_MAX_CHUNK_ROWS;   // (a chunk is one pass of either kernel)
-    std::vector<const hy_column*> inputs;   // distinct input columns, 1-byte ids first
-    for (int pass = 0; pass < 2 && lean; ++pass) {
-      for (uint32_t d = 0; d < n_device && lean; ++d) {
-        const hy_column* column = specs[spec_of_device[d]].column;
-        const uint32_t function = a.aggregates[d].function;
-        lean = function == HY_AGG_SUM || function == HY_AGG_AVG || function == HY_AGG_COUNT || function == HY_AGG_MIN || function == HY_AGG_MAX;
-        if (!column || !lean) continue;
-        uint32_t width = 0;
-        lean = (column->data_type == HY_TYPE_INT || column->data_type == HY_TYPE_LONG || column->data_type == HY_TYPE_FLOAT || column->data_type == HY_TYPE_DOUBLE) && dictionary_column(column, &width);
-        if (lean && width == (pass == 0 ? 1u : 2u) && std::find(inputs.begin(), inputs.end(), column) == inputs.end()) inputs.push_back(column);
-      }
-      if (pass == 0) small.n_narrow = static_cast<uint32_t>(inputs.size());
-    }
-    lean = lean && small.n_narrow <= SD_NARROW && inputs.size() - small.n_narrow <= SD_WIDE;
-    if (lean) {
-      if (const char* debug = HY_DEBUG_ENV("HY_AGG_SMALL_DEBUG")) small.debug = static_cast<uint32_t>(atoi(debug));   // timing experiments only
-      small.n_columns = static_cast<uint32_t>(inputs.size());
-      small.joint = small.n_narrow == 2 && FIXED_AGG_JOINT_HISTOGRAM ? 1u : 0u;
-      for (uint32_t k = 0; k < shape->n_chunks && small.joint; ++k) {
-        if ((uint64_t{inputs[0]->host_segments[k].aux_size} + 1) * (uint64_t{inputs[1]->host_segments[k].aux_size} + 1) > SD_JOINT_CELLS) small.joint = 0;
-      }
-      for (uint32_t c = 0; c < small.n_columns; ++c) small.column[c] = inputs[c]->d_segments;
-      for (uint32_t d = 0; d < n_device; ++d) {
-        const hy_column* column = specs[spec_of_device[d]].column;
-        small.column_of_aggregate[d] = column ? static_cast<uint32_t>(std::find(inputs.begin(), inputs.end(), column) - inputs.begin()) : 0xFFFFFFFFu;
-        if (column && (a.aggregates[d].function == HY_AGG_MIN || a.aggregates[d].function == HY_AGG_MAX)) small.extremes |= 1u << small.column_of_aggregate[d];
-      }
-    }
-    a.pos_cache = reads_references ? 1u : 0u;
-    HY_TRY(device_groups(a, shape, main_groups, nullptr, lean ? &small : nullptr));
+    if (qualify_small_domain(r, small)) run.small = &small;
+    return device_groups(run, groups);
   }
-  lap("device groups on host");
-  if (main_groups.on_device) {
-    const uint32_t n_groups = main_groups.n_groups;
-    result->n_groups = n_groups;
-    if (!sink && n_groups > result->group_capacity) return fail(HY_ERR_CAPACITY, "aggregate produces %u groups, capacity is %u", n_groups, result->group_capacity);
-    const bool int_key = n_groupby == 1 && groupby[0]->data_type == HY_TYPE_INT;
-    GroupExtent* extent_host = nullptr;
-    GroupExtent* extent_dev = nullptr;
-    HY_TRY(pinned_staging(sizeof(GroupExtent), reinterpret_cast<void**>(&extent_host), reinterpret_cast<void**>(&extent_dev)));
-    const uint32_t blocks = (n_groups + 255) / 256;
-    DeviceBuffer extent_partial;
-    HY_TRY(extent_partial.alloc(sizeof(GroupExtent) + 8));
-    HY_HIP(hipMemsetAsync(extent_partial.ptr, 0, sizeof(GroupExtent) + 8, stream));
-    HY_HIP(hipMemsetAsync(extent_partial.ptr, 0xFF, 8, stream));   // key_min
-    hipLaunchKernelGGL(finish_extent, dim3(std::min(blocks, 1024u)), dim3(256), 0, stream, main_groups.d_keys.as<uint64_t>(), main_groups.d_first.as<uint64_t>(), n_groups, words, int_key ? 1u : 0u,
-                       extent_partial.as<GroupExtent>(), extent_dev);
-    HY_HIP(hipStreamSynchronize(stream));
-    const uint64_t min_key = extent_host->key_min, max_key = extent_host->key_max;
-    // the immediate-key shortcut, as below (aggregate_hash.cpp:388-401)
-    const bool immediate = int_key && max_key > 0 && static_cast<double>(max_key - min_key) < static_cast<double>(fused ? main_groups.passed_rows : shape->rows) * 1.2;
-    const uint64_t largest_sort_key = immediate ? max_key - min_key + 1 : extent_host->row_max;
-    if (largest_sort_key >= (1ull << 32)) HY_TRY(download_groups(main_groups, words, n_device, stream));   // (keys spread over more than 2^32 values with more rows than that to justify it: never)
-    else {
-      uint32_t key_bits = 1;
-      while (key_bits < 32 && (largest_sort_key >> key_bits) != 0) ++key_bits;
-      DeviceBuffer sort_keys, sort_ids, sort_keys_tmp, sort_ids_tmp;
-      HY_TRY(sort_keys.alloc(4 * size_t{n_groups}));
-      HY_TRY(sort_ids.alloc(4 * size_t{n_groups}));
-      HY_TRY(sort_keys_tmp.alloc(4 * size_t{n_groups}));
-      HY_TRY(sort_ids_tmp.alloc(4 * size_t{n_groups}));
-      hipLaunchKernelGGL(finish_sort_keys, dim3(blocks), dim3(256), 0, stream, main_groups.d_keys.as<uint64_t>(), main_groups.d_first.as<uint64_t>(), n_groups, words, immediate ? 1u : 0u, min_key,
-                         sort_keys.as<uint32_t>(), sort_ids.as<uint32_t>());
-      uint32_t* sorted_keys = sort_keys.as<uint32_t>();
-      uint32_t* order = sort_ids.as<uint32_t>();
-      HY_TRY(sort_pairs_u32(&sorted_keys, &order, sort_keys_tmp.as<uint32_t>(), sort_ids_tmp.as<uint32_t>(), n_groups, key_bits, stream));
-      if (sink) {   // hy_aggregate_hash_columns: RowIDs into a result-pool buffer, cells into the output columns' chunks; nothing comes to the host
-        const RowIdOf row_id_of(shape);
-        HY_TRY(hy_result_pool_acquire(sizeof(hy_row_id) * uint64_t{n_groups}, reinterpret_cast<void**>(&sink->row_ids)));
-        hipLaunchKernelGGL(finish_row_ids, dim3(blocks), dim3(256), 0, stream, order, immediate ? main_groups.d_last.as<uint64_t>() : main_groups.d_first.as<uint64_t>(), n_groups, shape->d_row_base,
-                           shape->n_chunks, static_cast<uint32_t>(row_id_of.size), sink->row_ids);
-        ChunkedColumn chunked[MAX_AGGREGATES];
-        for (uint32_t g = 0; g < n_aggregates; ++g) {
-          const uint32_t in_type = input_type(g);
-          result->columns[g].data_type = result_type(specs[g].function, in_type);
-          HY_TRY(chunked[g].alloc(result->columns[g].data_type, n_groups, sink->chunk_rows));
-          const FinishColumn c{specs[g].function, result->columns[g].data_type, (in_type == HY_TYPE_FLOAT || in_type == HY_TYPE_DOUBLE) ? 1u : 0u, static_cast<uint32_t>(primary[g])};
-          const uint64_t units = chunked[g].units();
-          const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((units + 3) / 4, 8192)));
-          hipLaunchKernelGGL(finish_column_chunks, dim3(grid), dim3(256), 0, stream, order, main_groups.d_values.as<uint64_t>(), main_groups.d_counts.as<uint64_t>(), n_groups, n_device, c,
-                             chunked[g].chunk_rows, chunked[g].words_per_chunk, chunked[g].value_stride, chunked[g].null_stride, chunked[g].arena, chunked[g].nulls(), units);
-        }
-        HY_HIP(hipGetLastError());
-        HY_HIP(hipStreamSynchronize(stream));   // (the accumulators and the order go back to the pool as this returns)
-        for (uint32_t g = 0; g < n_aggregates; ++g) HY_TRY(chunked[g].adopt(&sink->columns[g]));
-        sink->n_groups = n_groups;
-        sink->finished = true;
-        g_agg_finished_on_device = 1;
-        lap("finished on the device, into columns");
-        return HY_OK;
-      }
-      // Results up to 16 MiB are written straight into pinned host memory by the kernels and copied out by the host (every hipMemcpyAsync
-      // into pageable memory is a staged copy with ~0.2 ms of host work around it: five of them cost more than the kernels); larger ones
-      // go through device arrays and one copy each.
-      const RowIdOf row_id_of(shape);
-      size_t value_bytes[MAX_AGGREGATES], values_at[MAX_AGGREGATES], nulls_at[MAX_AGGREGATES];
-      size_t staged_bytes = result->group_row_ids ? align_up(sizeof(hy_row_id) * size_t{n_groups}, 256) : 0;
-      for (uint32_t g = 0; g < n_aggregates; ++g) {
-        hy_aggregate_column& col = result->columns[g];
-        col.data_type = result_type(specs[g].function, input_type(g));
-        value_bytes[g] = (col.data_type == HY_TYPE_INT || col.data_type == HY_TYPE_FLOAT) ? 4 : 8;
-        values_at[g] = staged_bytes;
-        staged_bytes += align_up(value_bytes[g] * n_groups, 256);
-        nulls_at[g] = staged_bytes;
-        if (col.is_null) staged_bytes += align_up(size_t{n_groups}, 256);
-      }
-      const bool through_pinned = staged_bytes <= (size_t{16} << 20);
-      unsigned char* staged_host = nullptr;
-      unsigned char* staged_dev = nullptr;
-      DeviceBuffer staged_device_memory;
-      if (through_pinned) HY_TRY(pinned_staging(staged_bytes, reinterpret_cast<void**>(&staged_host), reinterpret_cast<void**>(&staged_dev)));
-      else {
-        HY_TRY(staged_device_memory.alloc(staged_bytes));
-        staged_dev = staged_device_memory.as<unsigned char>();
-      }
-      if (result->group_row_ids) {
-        hipLaunchKernelGGL(finish_row_ids, dim3(blocks), dim3(256), 0, stream, order, immediate ? main_groups.d_last.as<uint64_t>() : main_groups.d_first.as<uint64_t>(), n_groups, shape->d_row_base,
-                           shape->n_chunks, static_cast<uint32_t>(row_id_of.size), reinterpret_cast<hy_row_id*>(staged_dev));
-        if (!through_pinned) HY_HIP(hipMemcpyAsync(result->group_row_ids, staged_dev, sizeof(hy_row_id) * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
-      }
-      for (uint32_t g = 0; g < n_aggregates; ++g) {
-        hy_aggregate_column& col = result->columns[g];
-        const uint32_t in_type = input_type(g);
-        const FinishColumn c{specs[g].function, col.data_type, (in_type == HY_TYPE_FLOAT || in_type == HY_TYPE_DOUBLE) ? 1u : 0u, static_cast<uint32_t>(primary[g])};
-        hipLaunchKernelGGL(finish_column, dim3(blocks), dim3(256), 0, stream, order, main_groups.d_values.as<uint64_t>(), main_groups.d_counts.as<uint64_t>(), n_groups, n_device, c, staged_dev + values_at[g],
-                           col.is_null ? staged_dev + nulls_at[g] : nullptr);
-        if (through_pinned) continue;
-        HY_HIP(hipMemcpyAsync(col.values, staged_dev + values_at[g], value_bytes[g] * n_groups, hipMemcpyDeviceToHost, stream));
-        if (col.is_null) HY_HIP(hipMemcpyAsync(col.is_null, staged_dev + nulls_at[g], n_groups, hipMemcpyDeviceToHost, stream));
-      }
-      HY_HIP(hipStreamSynchronize(stream));
-      if (through_pinned) {
-        if (result->group_row_ids) std::memcpy(result->group_row_ids, staged_host, sizeof(hy_row_id) * size_t{n_groups});
-        for (uint32_t g = 0; g < n_aggregates; ++g) {
-          std::memcpy(result->columns[g].values, staged_host + values_at[g], value_bytes[g] * n_groups);
-          if (result->columns[g].is_null) std::memcpy(result->columns[g].is_null, staged_host + nulls_at[g], n_groups);
-        }
-      }
-      g_agg_finished_on_device = 1;
-      lap("finished on the device");
-      return HY_OK;
-    }
-  }
-  g_agg_finished_on_device = 0;
-  const uint32_t n_groups = main_groups.n_groups;
-  const std::vector<uint64_t>&h_keys = main_groups.keys, &h_first = main_groups.first, &h_last = main_groups.last, &h_values = main_groups.values,
-                             &h_counts = main_groups.counts;
+  DeviceBuffer plan_buffer;
+  FusedPlan plan;
+  FusedSmallPlan fused_small;
+  HY_TRY(build_fused_plan(r, plan_buffer, plan));
+  run.fused = plan_buffer.as<FusedPlan>();
+  if (qualify_fused_small(r, plan, fused_small)) run.fused_small = &fused_small;
+  return device_groups(run, groups);
+}
 
-  // COUNT(DISTINCT column): groups of (GROUP BY columns, column) with a non-NULL column value, counted per outer group
-  std::vector<std::vector<uint64_t>> distinct_counts(n_aggregates);
-  for (uint32_t g = 0; g < n_aggregates; ++g) {
-    if (specs[g].function != HY_AGG_COUNT_DISTINCT) continue;
-    AggArgs inner = a;
-    inner.n_groupby = n_groupby + 1;
-    inner.n_aggregates = 0;
-    wire(inner.groupby[n_groupby], specs[g].column, 0);
-    inner.pos_cache = reads_references ? 1u : 0u;
-    DeviceGroups combos;
-    HY_TRY(device_groups(inner, shape, combos));
-    std::map<std::vector<uint64_t>, uint32_t> group_of_key;
-    for (uint32_t i = 0; i < n_groups; ++i) group_of_key.emplace(std::vector<uint64_t>(h_keys.begin() + size_t{i} * words, h_keys.begin() + size_t{i + 1} * words), i);
-    distinct_counts[g].assign(n_groups, 0);
-    const uint32_t inner_words = words + 1;
-    for (uint32_t i = 0; i < combos.n_groups; ++i) {
-      const uint64_t* tuple = combos.keys.data() + size_t{i} * inner_words;
-      if ((tuple[0] >> n_groupby) & 1) continue;   // the aggregate column is NULL in this combination
-      std::vector<uint64_t> outer(tuple, tuple + words);
-      outer[0] &= (1ull << n_groupby) - 1;
-      const auto it = group_of_key.find(outer);
-      if (it != group_of_key.end()) distinct_counts[g][it->second] += 1;
-    }
-  }
-
-  // ---- order of the result rows (aggregate_hash.cpp:388-401, 770-804) ---------------------------------------------------
-  std::vector<uint32_t> order(n_groups);
-  for (uint32_t i = 0; i < n_groups; ++i) order[i] = i;
+// ---- the finish on the device: large results of plain aggregates -----------------------------------------------------------------------
+// The order of the result rows, made on the device: `order` (nullptr: the sort keys do not fit 32 bits -- the groups were downloaded, the
+// host finishes after all) and whether it is the immediate-key order.
+struct DeviceOrder {
+  DeviceBuffer sort_keys, sort_ids, sort_keys_tmp, sort_ids_tmp;
+  uint32_t* order = nullptr;
   bool immediate = false;
-  if (n_groupby == 1 && groupby[0]->data_type == HY_TYPE_INT) {
+};
+static hy_status order_groups_on_device(const AggregateRequest& r, DeviceGroups& groups, DeviceOrder& out) {
+  hipStream_t stream = current_stream();
+  const uint32_t n_groups = groups.n_groups, words = r.words(), blocks = (n_groups + 255) / 256;
+  const bool int_key = r.n_groupby == 1 && r.groupby[0]->data_type == HY_TYPE_INT;
+  GroupExtent* extent_host = nullptr;
+  GroupExtent* extent_dev = nullptr;
+  HY_TRY(pinned_staging(sizeof(GroupExtent), reinterpret_cast<void**>(&extent_host), reinterpret_cast<void**>(&extent_dev)));
+  DeviceBuffer extent_partial;
+  HY_TRY(extent_partial.alloc(sizeof(GroupExtent) + 8));
+  HY_HIP(hipMemsetAsync(extent_partial.ptr, 0, sizeof(GroupExtent) + 8, stream));
+  HY_HIP(hipMemsetAsync(extent_partial.ptr, 0xFF, 8, stream));   // key_min
+  hipLaunchKernelGGL(finish_extent, dim3(std::min(blocks, 1024u)), dim3(256), 0, stream, groups.d_keys.as<uint64_t>(), groups.d_first.as<uint64_t>(), n_groups, words, int_key ? 1u : 0u,
+                     extent_partial.as<GroupExtent>(), extent_dev);
+  HY_HIP(hipStreamSynchronize(stream));
+  const uint64_t min_key = extent_host->key_min, max_key = extent_host->key_max;
+  // the immediate-key shortcut, as in order_groups_on_host (aggregate_hash.cpp:388-401)
+  out.immediate = int_key && max_key > 0 && static_cast<double>(max_key - min_key) < static_cast<double>(r.fused ? groups.passed_rows : r.shape->rows) * 1.2;
+  const uint64_t largest_sort_key = out.immediate ? max_key - min_key + 1 : extent_host->row_max;
+  // (keys spread over more than 2^32 values with more rows than that to justify it: never)
+  if (largest_sort_key >= (1ull << 32)) return download_groups(groups, words, r.n_device, stream);
+  uint32_t key_bits = 1;
+  while (key_bits < 32 && (largest_sort_key >> key_bits) != 0) ++key_bits;
+  HY_TRY(out.sort_keys.alloc(4 * size_t{n_groups}));
+  HY_TRY(out.sort_ids.alloc(4 * size_t{n_groups}));
+  HY_TRY(out.sort_keys_tmp.alloc(4 * size_t{n_groups}));
+  HY_TRY(out.sort_ids_tmp.alloc(4 * size_t{n_groups}));
+  hipLaunchKernelGGL(finish_sort_keys, dim3(blocks), dim3(256), 0, stream, groups.d_keys.as<uint64_t>(), groups.d_first.as<uint64_t>(), n_groups, words, out.immediate ? 1u : 0u, min_key,
+                     out.sort_keys.as<uint32_t>(), out.sort_ids.as<uint32_t>());
+  uint32_t* sorted_keys = out.sort_keys.as<uint32_t>();
+  out.order = out.sort_ids.as<uint32_t>();
+  return sort_pairs_u32(&sorted_keys, &out.order, out.sort_keys_tmp.as<uint32_t>(), out.sort_ids_tmp.as<uint32_t>(), n_groups, key_bits, stream);
+}
+
+// the groups' representative rows as RowIDs, in result order
+static void launch_finish_row_ids(const AggregateRequest& r, const DeviceGroups& groups, const DeviceOrder& order, hy_row_id* out) {
+  const RowIdOf row_id_of(r.shape);
+  hipLaunchKernelGGL(finish_row_ids, dim3((groups.n_groups + 255) / 256), dim3(256), 0, current_stream(), order.order, order.immediate ? groups.d_last.as<uint64_t>() : groups.d_first.as<uint64_t>(),
+                     groups.n_groups, r.shape->d_row_base, r.shape->n_chunks, static_cast<uint32_t>(row_id_of.size), out);
+}
+
+// hy_aggregate_hash_columns: RowIDs into a result-pool buffer, cells into the output columns' chunks; nothing comes to the host
+static hy_status finish_into_columns(const AggregateRequest& r, hy_aggregate_result* result, const DeviceGroups& groups, const DeviceOrder& order) {
+  hipStream_t stream = current_stream();
+  ColumnSink* sink = r.sink;
+  const uint32_t n_groups = groups.n_groups;
+  HY_TRY(hy_result_pool_acquire(sizeof(hy_row_id) * uint64_t{n_groups}, reinterpret_cast<void**>(&sink->row_ids)));
+  launch_finish_row_ids(r, groups, order, sink->row_ids);
+  ChunkedColumn chunked[MAX_AGGREGATES];
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) {
+    result->columns[g].data_type = r.result_type[g];
+    HY_TRY(chunked[g].alloc(r.result_type[g], n_groups, sink->chunk_rows));
+    const uint64_t units = chunked[g].units();
+    const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((units + 3) / 4, 8192)));
+    hipLaunchKernelGGL(finish_column_chunks, dim3(grid), dim3(256), 0, stream, order.order, groups.d_values.as<uint64_t>(), groups.d_counts.as<uint64_t>(), n_groups, r.n_device, r.finish_column(g),
+                       chunked[g].chunk_rows, chunked[g].words_per_chunk, chunked[g].value_stride, chunked[g].null_stride, chunked[g].arena, chunked[g].nulls(), units);
+  }
+  HY_HIP(hipGetLastError());
+  HY_HIP(hipStreamSynchronize(stream));   // (the accumulators and the order go back to the pool as this returns)
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) HY_TRY(chunked[g].adopt(&sink->columns[g]));
+  sink->n_groups = n_groups;
+  sink->finished = true;
+  return HY_OK;
+}
+
+// Results up to 16 MiB are written straight into pinned host memory by the kernels and copied out by the host (every hipMemcpyAsync
+// into pageable memory is a staged copy with ~0.2 ms of host work around it: five of them cost more than the kernels); larger ones
+// go through device arrays and one copy each.
+static hy_status finish_into_host_result(const AggregateRequest& r, hy_aggregate_result* result, const DeviceGroups& groups, const DeviceOrder& order) {
+  hipStream_t stream = current_stream();
+  const uint32_t n_groups = groups.n_groups, blocks = (n_groups + 255) / 256;
+  size_t value_bytes[MAX_AGGREGATES], values_at[MAX_AGGREGATES], nulls_at[MAX_AGGREGATES];
+  size_t staged_bytes = result->group_row_ids ? align_up(sizeof(hy_row_id) * size_t{n_groups}, 256) : 0;
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) {
+    result->columns[g].data_type = r.result_type[g];
+    value_bytes[g] = value_width(r.result_type[g]);
+    values_at[g] = staged_bytes;
+    staged_bytes += align_up(value_bytes[g] * n_groups, 256);
+    nulls_at[g] = staged_bytes;
+    if (result->columns[g].is_null) staged_bytes += align_up(size_t{n_groups}, 256);
+  }
+  const bool through_pinned = staged_bytes <= (size_t{16} << 20);
+  unsigned char* staged_host = nullptr;
+  unsigned char* staged_dev = nullptr;
+  DeviceBuffer staged_device_memory;
+  if (through_pinned) HY_TRY(pinned_staging(staged_bytes, reinterpret_cast<void**>(&staged_host), reinterpret_cast<void**>(&staged_dev)));
+  else {
+    HY_TRY(staged_device_memory.alloc(staged_bytes));
+    staged_dev = staged_device_memory.as<unsigned char>();
+  }
+  if (result->group_row_ids) {
+    launch_finish_row_ids(r, groups, order, reinterpret_cast<hy_row_id*>(staged_dev));
+    if (!through_pinned) HY_HIP(hipMemcpyAsync(result->group_row_ids, staged_dev, sizeof(hy_row_id) * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
+  }
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) {
+    hy_aggregate_column& col = result->columns[g];
+    hipLaunchKernelGGL(finish_column, dim3(blocks), dim3(256), 0, stream, order.order, groups.d_values.as<uint64_t>(), groups.d_counts.as<uint64_t>(), n_groups, r.n_device, r.finish_column(g),
+                       staged_dev + values_at[g], col.is_null ? staged_dev + nulls_at[g] : nullptr);
+    if (through_pinned) continue;
+    HY_HIP(hipMemcpyAsync(col.values, staged_dev + values_at[g], value_bytes[g] * n_groups, hipMemcpyDeviceToHost, stream));
+    if (col.is_null) HY_HIP(hipMemcpyAsync(col.is_null, staged_dev + nulls_at[g], n_groups, hipMemcpyDeviceToHost, stream));
+  }
+  HY_HIP(hipStreamSynchronize(stream));
+  if (!through_pinned) return HY_OK;
+  if (result->group_row_ids) std::memcpy(result->group_row_ids, staged_host, sizeof(hy_row_id) * size_t{n_groups});
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) {
+    std::memcpy(result->columns[g].values, staged_host + values_at[g], value_bytes[g] * n_groups);
+    if (result->columns[g].is_null) std::memcpy(result->columns[g].is_null, staged_host + nulls_at[g], n_groups);
+  }
+  return HY_OK;
+}
+
+// Groups that stayed on the device: ordered there and written by the finish kernels.  *finished = false: the host finishes after all.
+static hy_status finish_on_device(const AggregateRequest& r, hy_aggregate_result* result, DeviceGroups& groups, const Laps& laps, bool* finished) {
+  result->n_groups = groups.n_groups;
+  if (!r.sink && groups.n_groups > result->group_capacity) return fail(HY_ERR_CAPACITY, "aggregate produces %u groups, capacity is %u", groups.n_groups, result->group_capacity);
+  DeviceOrder order;
+  HY_TRY(order_groups_on_device(r, groups, order));
+  *finished = order.order != nullptr;
+  if (!*finished) return HY_OK;
+  HY_TRY(r.sink ? finish_into_columns(r, result, groups, order) : finish_into_host_result(r, result, groups, order));
+  g_agg_finished_on_device = 1;
+  laps.since_start(r.sink ? "finished on the device, into columns" : "finished on the device");
+  return HY_OK;
+}
+
+// ---- the finish on the host ------------------------------------------------------------------------------------------------------------
+// What the host loops share: the groups in host memory, their order, and what only some aggregates need.
+struct HostFinish {
+  const DeviceGroups& groups;
+  uint32_t n_groups = 0, out_groups = 0;   // out_groups: n_groups, or the one row of no GROUP BY over an empty input
+  std::vector<uint32_t> order;
+  bool immediate = false;
+  std::vector<hy_row_id> representative;
+  std::vector<std::vector<uint64_t>> distinct_counts;   // [aggregate][group], COUNT(DISTINCT) only
+  explicit HostFinish(const DeviceGroups& g) : groups(g), n_groups(g.n_groups) {}
+};
+
+// COUNT(DISTINCT column): groups of (GROUP BY columns, column) with a non-NULL column value, counted per outer group
+static hy_status count_distinct(AggregateRequest& r, uint32_t g, const DeviceGroups& outer_groups, std::vector<uint64_t>& distinct) {
+  const uint32_t n_groups = outer_groups.n_groups, words = r.words(), n_groupby = r.n_groupby;
+  GroupsRun run;
+  run.a = r.a;
+  run.a.n_groupby = n_groupby + 1;
+  run.a.n_aggregates = 0;
+  wire(run.a.groupby[n_groupby], r.specs[g].column, 0);
+  if (r.specs[g].column->is_reference) r.reads_references = true;
+  run.a.pos_cache = r.reads_references ? 1u : 0u;
+  run.shape = r.shape;
+  DeviceGroups combos;
+  HY_TRY(device_groups(run, combos));
+  std::map<std::vector<uint64_t>, uint32_t> group_of_key;
+  const std::vector<uint64_t>& keys = outer_groups.keys;
+  for (uint32_t i = 0; i < n_groups; ++i) group_of_key.emplace(std::vector<uint64_t>(keys.begin() + size_t{i} * words, keys.begin() + size_t{i + 1} * words), i);
+  distinct.assign(n_groups, 0);
+  const uint32_t inner_words = words + 1;
+  for (uint32_t i = 0; i < combos.n_groups; ++i) {
+    const uint64_t* tuple = combos.keys.data() + size_t{i} * inner_words;
+    if ((tuple[0] >> n_groupby) & 1) continue;   // the aggregate column is NULL in this combination
+    std::vector<uint64_t> outer(tuple, tuple + words);
+    outer[0] &= (1ull << n_groupby) - 1;
+    const auto it = group_of_key.find(outer);
+    if (it != group_of_key.end()) distinct[it->second] += 1;
+  }
+  return HY_OK;
+}
+
+// The order of the result rows (aggregate_hash.cpp:388-401, 770-804): ascending key (NULL first) under the immediate-key shortcut, else
+// first row.  An LSD radix sort of (64-bit sort key, group) -- a comparison sort of 100 000 groups through an index costs more than the
+// device spends on the whole table.
+static void order_groups_on_host(const AggregateRequest& r, HostFinish& h) {
+  const uint32_t n_groups = h.n_groups, words = r.words();
+  const std::vector<uint64_t>& keys = h.groups.keys;
+  auto key_of = [&](uint32_t i) { return static_cast<uint64_t>(static_cast<int64_t>(keys[size_t{i} * words + 1]) - static_cast<int64_t>(INT32_MIN)) + 1; };
+  h.order.resize(n_groups);
+  for (uint32_t i = 0; i < n_groups; ++i) h.order[i] = i;
+  if (r.n_groupby == 1 && r.groupby[0]->data_type == HY_TYPE_INT) {
     uint64_t min_key = ~0ull, max_key = 0;
     for (uint32_t i = 0; i < n_groups; ++i) {
-      if (h_keys[size_t{i} * words] & 1) continue;   // NULL group
-      const uint64_t k = static_cast<uint64_t>(static_cast<int64_t>(h_keys[size_t{i} * words + 1]) - static_cast<int64_t>(INT32_MIN)) + 1;
-      min_key = std::min(min_key, k);
-      max_key = std::max(max_key, k);
+      if (keys[size_t{i} * words] & 1) continue;   // NULL group
+      min_key = std::min(min_key, key_of(i));
+      max_key = std::max(max_key, key_of(i));
     }
     // (the row count is that of the aggregate's INPUT: behind fused filters, the rows that passed them)
-    immediate = max_key > 0 && static_cast<double>(max_key - min_key) < static_cast<double>(fused ? main_groups.passed_rows : shape->rows) * 1.2;
+    h.immediate = max_key > 0 && static_cast<double>(max_key - min_key) < static_cast<double>(r.fused ? h.groups.passed_rows : r.shape->rows) * 1.2;
   }
-  {   // ascending key (NULL first) or first row: an LSD radix sort of (64-bit sort key, group) -- a comparison sort of 100 000 groups
-      // through an index costs more than the device spends on the whole table
-    std::vector<uint64_t> sort_key(n_groups);
-    uint64_t all_bits = 0;
-    for (uint32_t i = 0; i < n_groups; ++i) {
-      if (immediate) sort_key[i] = (h_keys[size_t{i} * words] & 1) ? 0 : static_cast<uint64_t>(static_cast<int64_t>(h_keys[size_t{i} * words + 1]) - static_cast<int64_t>(INT32_MIN)) + 1;
-      else sort_key[i] = h_first[i];
-      all_bits |= sort_key[i];
-    }
-    std::vector<uint32_t> scratch_order(n_groups);
-    if (n_groups <= 2048) {   // (a handful of groups -- TPC-H Q1 has four: two passes over 65 536 buckets cost 17 us of a 0.28 ms call)
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return sort_key[x] < sort_key[y]; });
-      all_bits = 0;
-    }
-    for (uint32_t shift = 0; shift < 64 && (all_bits >> shift) != 0; shift += 16) {
-      std::vector<uint32_t> bucket(65537, 0);
-      for (uint32_t i = 0; i < n_groups; ++i) ++bucket[((sort_key[order[i]] >> shift) & 0xFFFF) + 1];
-      for (uint32_t b = 0; b < 65536; ++b) bucket[b + 1] += bucket[b];
-      for (uint32_t i = 0; i < n_groups; ++i) scratch_order[bucket[(sort_key[order[i]] >> shift) & 0xFFFF]++] = order[i];
-      order.swap(scratch_order);
-    }
+  std::vector<uint64_t> sort_key(n_groups);
+  uint64_t all_bits = 0;
+  for (uint32_t i = 0; i < n_groups; ++i) {
+    if (h.immediate) sort_key[i] = (keys[size_t{i} * words] & 1) ? 0 : key_of(i);
+    else sort_key[i] = h.groups.first[i];
+    all_bits |= sort_key[i];
   }
+  std::vector<uint32_t>& order = h.order;
+  std::vector<uint32_t> scratch_order(n_groups);
+  if (n_groups <= 2048) {   // (a handful of groups -- TPC-H Q1 has four: two passes over 65 536 buckets cost 17 us of a 0.28 ms call)
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return sort_key[x] < sort_key[y]; });
+    all_bits = 0;
+  }
+  for (uint32_t shift = 0; shift < 64 && (all_bits >> shift) != 0; shift += 16) {
+    std::vector<uint32_t> bucket(65537, 0);
+    for (uint32_t i = 0; i < n_groups; ++i) ++bucket[((sort_key[order[i]] >> shift) & 0xFFFF) + 1];
+    for (uint32_t b = 0; b < 65536; ++b) bucket[b + 1] += bucket[b];
+    for (uint32_t i = 0; i < n_groups; ++i) scratch_order[bucket[(sort_key[order[i]] >> shift) & 0xFFFF]++] = order[i];
+    order.swap(scratch_order);
+  }
+}
 
-  lap("groups ordered");
-  const bool no_groupby_empty = n_groupby == 0 && n_groups == 0;   // one row of NULLs / zero counts (:1422-1432)
-  const uint32_t out_groups = no_groupby_empty ? 1 : n_groups;
-  result->n_groups = out_groups;
-  if (sink) HY_TRY(sink->host_buffers(out_groups, n_aggregates, result));
-  if (out_groups > result->group_capacity) return fail(HY_ERR_CAPACITY, "aggregate produces %u groups, capacity is %u", out_groups, result->group_capacity);
-  if (result->mem != HY_MEM_HOST) return fail(HY_ERR_UNSUPPORTED, "aggregate results are returned in host memory (they are ordered on the host)");
-  std::vector<hy_row_id> representative(out_groups, hy_row_id{0, 0});
-  const RowIdOf row_id_of(shape);
-  for_each_group_range(n_groups, [&](uint32_t begin, uint32_t end) {
-    const uint64_t* rows_of_groups = immediate ? h_last.data() : h_first.data();
+// every group's representative row as a RowID, in result order: its last row under the immediate-key order, else its first
+static void representatives(const AggregateRequest& r, HostFinish& h) {
+  h.representative.assign(h.out_groups, hy_row_id{0, 0});
+  const RowIdOf row_id_of(r.shape);
+  const uint64_t* rows_of_groups = h.immediate ? h.groups.last.data() : h.groups.first.data();
+  const uint32_t* order = h.order.data();
+  hy_row_id* representative = h.representative.data();
+  for_each_group_range(h.n_groups, [&](uint32_t begin, uint32_t end) {
     for (uint32_t o = begin; o < end; ++o) {
       if (o + 16 < end) __builtin_prefetch(rows_of_groups + order[o + 16]);   // (the groups come in table order, the result in its own)
       representative[o] = row_id_of(rows_of_groups[order[o]]);
     }
   });
-  if (result->group_row_ids) std::memcpy(result->group_row_ids, representative.data(), sizeof(hy_row_id) * out_groups);
-  lap("representatives");
+}
 
-  for (uint32_t g = 0; g < n_aggregates; ++g) {
-    hy_aggregate_column& col = result->columns[g];
-    const uint32_t function = specs[g].function;
-    const uint32_t in_type = input_type(g);
-    const bool is_float = in_type == HY_TYPE_FLOAT || in_type == HY_TYPE_DOUBLE;
-    col.data_type = result_type(function, in_type);
-    if (!col.values) return fail(HY_ERR_INVALID, "aggregate %u: values buffer missing", g);
-    std::vector<uint64_t> any_bits;
-    std::vector<uint8_t> any_null;
-    if (function == HY_AGG_ANY && n_groups) {
-      DeviceBuffer d_rows, d_bits, d_null;
-      HY_TRY(d_rows.alloc(8 * size_t{n_groups}));
-      HY_TRY(d_bits.alloc(8 * size_t{n_groups}));
-      HY_TRY(d_null.alloc(n_groups));
-      HY_HIP(hipMemcpyAsync(d_rows.ptr, representative.data(), 8 * size_t{n_groups}, hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(gather_values, dim3((n_groups + 255) / 256), dim3(256), 0, stream, specs[g].column->d_segments, d_rows.as<hy_row_id>(), n_groups, is_float ? 1u : 0u,
-                         d_bits.as<uint64_t>(), d_null.as<uint8_t>());
-      any_bits.resize(n_groups);
-      any_null.resize(n_groups);
-      HY_HIP(hipMemcpyAsync(any_bits.data(), d_bits.ptr, 8 * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
-      HY_HIP(hipMemcpyAsync(any_null.data(), d_null.ptr, n_groups, hipMemcpyDeviceToHost, stream));
-      HY_HIP(hipStreamSynchronize(stream));
+// ANY: the column's value at every group's representative row
+static hy_status gather_any_values(const AggregateRequest& r, uint32_t g, const HostFinish& h, std::vector<uint64_t>& any_bits, std::vector<uint8_t>& any_null) {
+  hipStream_t stream = current_stream();
+  const uint32_t n_groups = h.n_groups;
+  DeviceBuffer d_rows, d_bits, d_null;
+  HY_TRY(d_rows.alloc(8 * size_t{n_groups}));
+  HY_TRY(d_bits.alloc(8 * size_t{n_groups}));
+  HY_TRY(d_null.alloc(n_groups));
+  HY_HIP(hipMemcpyAsync(d_rows.ptr, h.representative.data(), 8 * size_t{n_groups}, hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(gather_values, dim3((n_groups + 255) / 256), dim3(256), 0, stream, r.specs[g].column->d_segments, d_rows.as<hy_row_id>(), n_groups, r.is_float[g] ? 1u : 0u,
+                     d_bits.as<uint64_t>(), d_null.as<uint8_t>());
+  any_bits.resize(n_groups);
+  any_null.resize(n_groups);
+  HY_HIP(hipMemcpyAsync(any_bits.data(), d_bits.ptr, 8 * size_t{n_groups}, hipMemcpyDeviceToHost, stream));
+  HY_HIP(hipMemcpyAsync(any_null.data(), d_null.ptr, n_groups, hipMemcpyDeviceToHost, stream));
+  HY_HIP(hipStreamSynchronize(stream));
+  return HY_OK;
+}
+
+// The common shapes as tight loops (a result of 100 000 groups spends more time here than the device spends on the table).  COUNT -> int64:
+static void write_counts(const hy_aggregate_column& col, const uint64_t* group_counts, const uint32_t* order, uint32_t n_device, uint32_t out_groups) {
+  for_each_group_range(out_groups, [&](uint32_t range_begin, uint32_t range_end) {
+    int64_t* out_values = static_cast<int64_t*>(col.values);
+    for (uint32_t o = range_begin; o < range_end; ++o) {
+      if (o + 16 < range_end) __builtin_prefetch(group_counts + size_t{order[o + 16]} * n_device);
+      out_values[o] = static_cast<int64_t>(group_counts[size_t{order[o]} * n_device]);
     }
-    // the common shapes as tight loops (a result of 100 000 groups spends more time here than the device spends on the table):
-    // COUNT -> int64, SUM / AVG of a floating-point column or AVG of an integer one -> double, SUM of an integer column -> int64
-    const bool plain = out_groups == n_groups && primary[g] >= 0;
-    const uint64_t* group_values = h_values.data() + (primary[g] >= 0 ? primary[g] : 0);
-    const uint64_t* group_counts = h_counts.data() + (primary[g] >= 0 ? primary[g] : 0);
-    if (plain && function == HY_AGG_COUNT && col.data_type == HY_TYPE_LONG) {
-      for_each_group_range(out_groups, [&](uint32_t range_begin, uint32_t range_end) {
-        int64_t* out_values = static_cast<int64_t*>(col.values);
-        for (uint32_t o = range_begin; o < range_end; ++o) {
-          if (o + 16 < range_end) __builtin_prefetch(group_counts + size_t{order[o + 16]} * n_device);
-          out_values[o] = static_cast<int64_t>(group_counts[size_t{order[o]} * n_device]);
-        }
-        if (col.is_null) std::memset(col.is_null + range_begin, 0, range_end - range_begin);
-      });
-      continue;
+    if (col.is_null) std::memset(col.is_null + range_begin, 0, range_end - range_begin);
+  });
+}
+// ... SUM / AVG of a floating-point column or AVG of an integer one -> double, SUM of an integer column -> int64:
+static void write_sums(const hy_aggregate_column& col, bool divide, const uint64_t* group_values, const uint64_t* group_counts, const uint32_t* order, uint32_t n_device, uint32_t out_groups) {
+  const bool as_double = col.data_type == HY_TYPE_DOUBLE;
+  for_each_group_range(out_groups, [&](uint32_t range_begin, uint32_t range_end) {
+    for (uint32_t o = range_begin; o < range_end; ++o) {
+      if (o + 16 < range_end) {
+        __builtin_prefetch(group_values + size_t{order[o + 16]} * n_device);
+        __builtin_prefetch(group_counts + size_t{order[o + 16]} * n_device);
+      }
+      const size_t at = size_t{order[o]} * n_device;
+      const uint64_t bits = group_values[at], count = group_counts[at];
+      const bool is_null = count == 0;
+      if (col.is_null) col.is_null[o] = is_null;
+      if (as_double) {
+        double sum;
+        std::memcpy(&sum, &bits, 8);
+        static_cast<double*>(col.values)[o] = is_null ? 0.0 : (divide ? sum / static_cast<double>(count) : sum);
+      } else {
+        static_cast<int64_t*>(col.values)[o] = is_null ? 0 : static_cast<int64_t>(bits);
+      }
     }
-    if (plain && (function == HY_AGG_SUM || function == HY_AGG_AVG) && (col.data_type == HY_TYPE_DOUBLE || (function == HY_AGG_SUM && col.data_type == HY_TYPE_LONG))) {
-      const bool as_double = col.data_type == HY_TYPE_DOUBLE, divide = function == HY_AGG_AVG;
-      for_each_group_range(out_groups, [&](uint32_t range_begin, uint32_t range_end) {
-        for (uint32_t o = range_begin; o < range_end; ++o) {
-          if (o + 16 < range_end) {
-            __builtin_prefetch(group_values + size_t{order[o + 16]} * n_device);
-            __builtin_prefetch(group_counts + size_t{order[o + 16]} * n_device);
-          }
-          const size_t at = size_t{order[o]} * n_device;
-          const uint64_t bits = group_values[at], count = group_counts[at];
-          const bool is_null = count == 0;
-          if (col.is_null) col.is_null[o] = is_null;
-          if (as_double) {
-            double sum;
-            std::memcpy(&sum, &bits, 8);
-            static_cast<double*>(col.values)[o] = is_null ? 0.0 : (divide ? sum / static_cast<double>(count) : sum);
-          } else {
-            static_cast<int64_t*>(col.values)[o] = is_null ? 0 : static_cast<int64_t>(bits);
-          }
-        }
-      });
-      continue;
-    }
-    for_each_group_range(out_groups, [&](uint32_t range_begin, uint32_t range_end) {
+  });
+}
+
+// ... and every function, cell by cell.
+static void write_cells(const AggregateRequest& r, uint32_t g, const HostFinish& h, const hy_aggregate_column& col, const std::vector<uint64_t>& any_bits, const std::vector<uint8_t>& any_null) {
+  const uint32_t function = r.specs[g].function, n_device = r.n_device, n_groups = h.n_groups;
+  const int primary = r.primary[g], secondary = r.secondary[g];
+  const bool is_float = r.is_float[g];
+  const std::vector<uint64_t>&h_values = h.groups.values, &h_counts = h.groups.counts;
+  const std::vector<uint32_t>& order = h.order;
+  for_each_group_range(h.out_groups, [&](uint32_t range_begin, uint32_t range_end) {
     for (uint32_t o = range_begin; o < range_end; ++o) {
       const bool have = o < n_groups;
-      const uint64_t bits = have && primary[g] >= 0 ? h_values[size_t{order[o]} * n_device + primary[g]] : 0;
-      const uint64_t count = have && primary[g] >= 0 ? h_counts[size_t{order[o]} * n_device + primary[g]] : 0;
+      const uint64_t bits = have && primary >= 0 ? h_values[size_t{order[o]} * n_device + primary] : 0;
+      const uint64_t count = have && primary >= 0 ? h_counts[size_t{order[o]} * n_device + primary] : 0;
       bool is_null = false;
       int64_t vi = 0;
       double vf = 0.0;
       switch (function) {
         case HY_AGG_COUNT: vi = static_cast<int64_t>(count); break;
-        case HY_AGG_COUNT_DISTINCT: vi = have ? static_cast<int64_t>(distinct_counts[g][order[o]]) : 0; break;
+        case HY_AGG_COUNT_DISTINCT: vi = have ? static_cast<int64_t>(h.distinct_counts[g][order[o]]) : 0; break;
         case HY_AGG_STDDEV_SAMP:   // abstract_aggregate_operator.hpp:83-113 (Welford there; sums of the values shifted by a value of the column here)
           is_null = count <= 1;
           if (count > 1) {
             double sum, squares;
             std::memcpy(&sum, &bits, 8);
-            std::memcpy(&squares, &h_values[size_t{order[o]} * n_device + secondary[g]], 8);
+            std::memcpy(&squares, &h_values[size_t{order[o]} * n_device + secondary], 8);
             const double n = static_cast<double>(count);
             const double variance = (squares - sum * sum / n) / (n - 1.0);
             vf = variance > 0.0 ? std::sqrt(variance) : 0.0;
@@ -3724,24 +3888,71 @@ static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_group
         default: static_cast<double*>(col.values)[o] = is_null ? 0.0 : vf; break;
       }
     }
-    });
-  }
-  lap("result written");
+  });
+}
+
+static hy_status write_result_column(const AggregateRequest& r, uint32_t g, const HostFinish& h, hy_aggregate_column& col) {
+  const uint32_t function = r.specs[g].function;
+  col.data_type = r.result_type[g];
+  if (!col.values) return fail(HY_ERR_INVALID, "aggregate %u: values buffer missing", g);
+  std::vector<uint64_t> any_bits;
+  std::vector<uint8_t> any_null;
+  if (function == HY_AGG_ANY && h.n_groups) HY_TRY(gather_any_values(r, g, h, any_bits, any_null));
+  const bool plain = h.out_groups == h.n_groups && r.primary[g] >= 0;
+  const uint64_t* group_values = h.groups.values.data() + (r.primary[g] >= 0 ? r.primary[g] : 0);
+  const uint64_t* group_counts = h.groups.counts.data() + (r.primary[g] >= 0 ? r.primary[g] : 0);
+  if (plain && function == HY_AGG_COUNT && col.data_type == HY_TYPE_LONG) write_counts(col, group_counts, h.order.data(), r.n_device, h.out_groups);
+  else if (plain && (function == HY_AGG_SUM || function == HY_AGG_AVG) && (col.data_type == HY_TYPE_DOUBLE || (function == HY_AGG_SUM && col.data_type == HY_TYPE_LONG)))
+    write_sums(col, function == HY_AGG_AVG, group_values, group_counts, h.order.data(), r.n_device, h.out_groups);
+  else write_cells(r, g, h, col, any_bits, any_null);
   return HY_OK;
 }
 
-// hy_scan_project_aggregate: checks the plan, types the expressions (expression_common_type per arithmetic node, like
-// hy_projection_arithmetic per call) and runs the aggregate with fused_rows in the place of aggregate_rows.
-static hy_status run_fused(const hy_filter* filters, uint32_t n_filters, const hy_column* const* groupby, uint32_t n_groupby, const hy_fused_aggregate* aggregates,
-                           uint32_t n_aggregates, hy_aggregate_result* result) {
-  if (n_filters > HY_MAX_FILTERS) return fail(HY_ERR_UNSUPPORTED, "more than %d fused filters: run the operator chain", static_cast<int>(HY_MAX_FILTERS));
-  if (n_aggregates > MAX_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "more than %u aggregates stay on the CPU path", MAX_AGGREGATES);
-  if (n_groupby > MAX_GROUPBY) return fail(HY_ERR_UNSUPPORTED, "more than %u GROUP BY columns stay on the CPU path", MAX_GROUPBY);
-  auto query = std::make_unique<FusedQuery>();
-  FusedQuery& q = *query;
-  std::memset(&q, 0, sizeof(q));
+// The groups in host memory -> the result: COUNT(DISTINCT)'s second groupings, the order, the representative rows, column by column.
+static hy_status finish_on_host(AggregateRequest& r, hy_aggregate_result* result, const DeviceGroups& groups, const Laps& laps) {
+  g_agg_finished_on_device = 0;
+  HostFinish h(groups);
+  h.distinct_counts.resize(r.n_aggregates);
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) if (r.specs[g].function == HY_AGG_COUNT_DISTINCT) HY_TRY(count_distinct(r, g, groups, h.distinct_counts[g]));
+  order_groups_on_host(r, h);
+  laps.since_start("groups ordered");
+  const bool no_groupby_empty = r.n_groupby == 0 && h.n_groups == 0;   // one row of NULLs / zero counts (:1422-1432)
+  h.out_groups = no_groupby_empty ? 1 : h.n_groups;
+  result->n_groups = h.out_groups;
+  if (r.sink) HY_TRY(r.sink->host_buffers(h.out_groups, r.n_aggregates, result));
+  if (h.out_groups > result->group_capacity) return fail(HY_ERR_CAPACITY, "aggregate produces %u groups, capacity is %u", h.out_groups, result->group_capacity);
+  representatives(r, h);
+  if (result->group_row_ids) std::memcpy(result->group_row_ids, h.representative.data(), sizeof(hy_row_id) * h.out_groups);
+  laps.since_start("representatives");
+  for (uint32_t g = 0; g < r.n_aggregates; ++g) HY_TRY(write_result_column(r, g, h, result->columns[g]));
+  laps.since_start("result written");
+  return HY_OK;
+}
+
+// One aggregate call: the request resolved, the groups made on the device, the result finished where the request allows.  (Both callers
+// pass a result in host memory: run_with_result_memory's shadow, hy_aggregate_hash_columns' own.)
+static hy_status run_aggregate(const hy_column* const* groupby, uint32_t n_groupby, const hy_aggregate_spec* specs, uint32_t n_aggregates,
+                               hy_aggregate_result* result, const FusedQuery* fused = nullptr, ColumnSink* sink = nullptr) {
+  AggregateRequest request;
+  HY_TRY(resolve_aggregate_request(groupby, n_groupby, specs, n_aggregates, result, fused, sink, request));
+  HY_TRY(stddev_pivots(request));
+  const Laps laps;
+  DeviceGroups groups;
+  HY_TRY(main_groups(request, groups));
+  laps.since_start("device groups on host");
+  if (groups.on_device) {
+    bool finished = false;
+    HY_TRY(finish_on_device(request, result, groups, laps, &finished));
+    if (finished) return HY_OK;
+  }
+  return finish_on_host(request, result, groups, laps);
+}
+
+// ---- hy_scan_project_aggregate: the plan checked, the expressions typed ----------------------------------------------------------------
+// The columns of a fused plan all belong to one data table: the first one seen gives the chunk layout.
+struct FusedTable {
   const hy_column* shape = nullptr;
-  auto table_column = [&](const hy_column* c, const char* what) -> hy_status {
+  hy_status column(const hy_column* c, const char* what) {
     if (!c) return fail(HY_ERR_INVALID, "hy_scan_project_aggregate: %s column missing", what);
     if (c->is_reference || c->is_mvcc) return fail(HY_ERR_UNSUPPORTED, "hy_scan_project_aggregate reads the columns of a data table (%s column is a reference / MVCC column): run the operator chain", what);
     if (!shape) { shape = c; return HY_OK; }
@@ -3750,109 +3961,218 @@ static hy_status run_fused(const hy_filter* filters, uint32_t n_filters, const h
       if (c->host_segments[k].size != shape->host_segments[k].size) return fail(HY_ERR_INVALID, "%s column does not belong to the table (chunk %u)", what, k);
     }
     return HY_OK;
-  };
-  auto numeric = [](uint32_t t) { return t >= HY_TYPE_INT && t <= HY_TYPE_DOUBLE; };
-  for (uint32_t f = 0; f < n_filters; ++f) {
-    if (filters[f].predicate.condition == HY_FILTER_VALIDATE) {   // the table's MvccData: same chunk layout, checked like a column
-      const hy_column* mvcc = filters[f].column;
-      if (!mvcc || !mvcc->is_mvcc || mvcc->is_reference) return fail(HY_ERR_INVALID, "a Validate filter needs the table's column of HY_ENC_MVCC segments");
-      if (shape && mvcc->n_chunks != shape->n_chunks) return fail(HY_ERR_INVALID, "the MvccData does not belong to the table (chunk counts differ)");
-      if (!shape) shape = mvcc;
-      continue;
-    }
-    HY_TRY(table_column(filters[f].column, "filter"));
   }
-  for (uint32_t g = 0; g < n_groupby; ++g) HY_TRY(table_column(groupby[g], "GROUP BY"));
-  for (uint32_t g = 0; g < n_aggregates; ++g) {
-    const hy_expression* e = aggregates[g].input;
-    FusedInput& input = q.inputs[g];
-    q.same_as[g] = g;
-    if (!e) continue;   // COUNT(*)
-    if (e->n_nodes == 0 || e->n_nodes > HY_MAX_EXPRESSION_NODES) return fail(HY_ERR_INVALID, "aggregate %u: an expression has 1 to %d nodes", g, static_cast<int>(HY_MAX_EXPRESSION_NODES));
-    uint32_t types[4] = {0, 0, 0, 0}, depth = 0;
-    int producers[4] = {-1, -1, -1, -1};   // the LITERAL node that put the stack entry there, else -1
-    for (uint32_t k = 0; k < e->n_nodes; ++k) {
-      const hy_expression_node& n = e->nodes[k];
-      FusedNode& out = input.nodes[k];
-      out.kind = n.kind;
-      if (n.kind == HY_EXPR_ARITHMETIC) {
-        if (n.op > HY_ARITH_MOD) return fail(HY_ERR_INVALID, "aggregate %u: unknown arithmetic operator %u", g, n.op);
-        if (depth < 2) return fail(HY_ERR_INVALID, "aggregate %u: node %u has no two operands below it (postfix order)", g, k);
-        const uint32_t left = types[depth - 2], right = types[depth - 1];
-        if (left == HY_TYPE_NULL && right == HY_TYPE_NULL) return fail(HY_ERR_INVALID, "Cannot deduce common type if both sides are NULL.");
-        out.op = n.op;
-        out.type = expression_common_type(left, right);
-        // A literal operand of + - * is converted to the operation's C++ type before anything is computed (arithmetic_cell): done here, once,
-        // so that the kernel finds two operands of the result's own type and takes its one-instruction path.
-        if (n.op <= HY_ARITH_MUL) {
-          for (int side = 0; side < 2; ++side) {
-            const uint32_t at = side == 0 ? left : right, other = side == 0 ? right : left;
-            const int producer = side == 0 ? producers[depth - 2] : producers[depth - 1];
-            if (producer < 0 || at == HY_TYPE_NULL || other == HY_TYPE_NULL) continue;
-            FusedNode& literal = input.nodes[producer];
-            const uint32_t common = (at == HY_TYPE_DOUBLE || other == HY_TYPE_DOUBLE) ? HY_TYPE_DOUBLE : (at == HY_TYPE_FLOAT || other == HY_TYPE_FLOAT) ? HY_TYPE_FLOAT
-                                    : (at == HY_TYPE_LONG || other == HY_TYPE_LONG) ? HY_TYPE_LONG : HY_TYPE_INT;   // std::common_type_t
-            if (common == at || common != out.type) continue;   // (int (op) long literal: the result type is the common type as well; long (op) float -> double is not)
-            double as_double = 0.0;
-            float as_float = 0.f;
-            int64_t as_integer = static_cast<int64_t>(literal.literal);
-            if (at == HY_TYPE_FLOAT) { uint32_t word = static_cast<uint32_t>(literal.literal); std::memcpy(&as_float, &word, 4); as_double = as_float; }
-            else as_double = static_cast<double>(as_integer);
-            if (common == HY_TYPE_DOUBLE) std::memcpy(&literal.literal, &as_double, 8);
-            else if (common == HY_TYPE_FLOAT) { as_float = static_cast<float>(as_double); uint32_t word; std::memcpy(&word, &as_float, 4); literal.literal = word; }   // (via double, like the device's convert())
-            else literal.literal = static_cast<uint64_t>(as_integer);   // int -> long
-            literal.type = common;
-          }
-        }
-        depth -= 1;
-        types[depth - 1] = out.type;
-        producers[depth - 1] = -1;
-        continue;
-      }
+  hy_status filter(const hy_filter& f) {
+    if (f.predicate.condition != HY_FILTER_VALIDATE) return column(f.column, "filter");
+    const hy_column* mvcc = f.column;   // the table's MvccData: same chunk layout, checked like a column
+    if (!mvcc || !mvcc->is_mvcc || mvcc->is_reference) return fail(HY_ERR_INVALID, "a Validate filter needs the table's column of HY_ENC_MVCC segments");
+    if (shape && mvcc->n_chunks != shape->n_chunks) return fail(HY_ERR_INVALID, "the MvccData does not belong to the table (chunk counts differ)");
+    if (!shape) shape = mvcc;
+    return HY_OK;
+  }
+};
+static bool is_numeric_type(uint32_t t) { return t >= HY_TYPE_INT && t <= HY_TYPE_DOUBLE; }
+
+// A literal operand of + - * is converted to the operation's C++ type before anything is computed (arithmetic_cell): done here, once,
+// so that the kernel finds two operands of the result's own type and takes its one-instruction path.
+static void convert_literal_operand(FusedNode& literal, uint32_t at, uint32_t other, uint32_t result) {
+  if (at == HY_TYPE_NULL || other == HY_TYPE_NULL) return;
+  const uint32_t common = (at == HY_TYPE_DOUBLE || other == HY_TYPE_DOUBLE) ? HY_TYPE_DOUBLE : (at == HY_TYPE_FLOAT || other == HY_TYPE_FLOAT) ? HY_TYPE_FLOAT
+                          : (at == HY_TYPE_LONG || other == HY_TYPE_LONG) ? HY_TYPE_LONG : HY_TYPE_INT;   // std::common_type_t
+  if (common == at || common != result) return;   // (int (op) long literal: the result type is the common type as well; long (op) float -> double is not)
+  double as_double = 0.0;
+  float as_float = 0.f;
+  int64_t as_integer = static_cast<int64_t>(literal.literal);
+  if (at == HY_TYPE_FLOAT) { uint32_t word = static_cast<uint32_t>(literal.literal); std::memcpy(&as_float, &word, 4); as_double = as_float; }
+  else as_double = static_cast<double>(as_integer);
+  if (common == HY_TYPE_DOUBLE) std::memcpy(&literal.literal, &as_double, 8);
+  else if (common == HY_TYPE_FLOAT) { as_float = static_cast<float>(as_double); uint32_t word; std::memcpy(&word, &as_float, 4); literal.literal = word; }   // (via double, like the device's convert())
+  else literal.literal = static_cast<uint64_t>(as_integer);   // int -> long
+  literal.type = common;
+}
+
+// a COLUMN or LITERAL node of aggregate g's expression -> `out`, typed
+static hy_status type_leaf(const hy_expression_node& n, uint32_t g, FusedNode& out, FusedQuery& q, FusedTable& table) {
+  if (n.kind == HY_EXPR_COLUMN) {
+    HY_TRY(table.column(n.column, "expression"));
+    if (!is_numeric_type(n.column->data_type)) return fail(HY_ERR_UNSUPPORTED, "string expressions stay on the CPU path");
+    uint32_t which = 0;
+    while (which < q.n_columns && q.columns[which] != n.column) ++which;
+    if (which == q.n_columns) {
+      if (q.n_columns == static_cast<uint32_t>(FUSED_COLUMNS)) return fail(HY_ERR_UNSUPPORTED, "the expressions read more than %d distinct columns: run the operator chain", FUSED_COLUMNS);
+      q.columns[q.n_columns++] = n.column;
+    }
+    out.column = which;
+    out.type = n.column->data_type;
+    return HY_OK;
+  }
+  if (n.kind != HY_EXPR_LITERAL) return fail(HY_ERR_INVALID, "aggregate %u: unknown expression node kind %u", g, n.kind);
+  if (n.literal_type != HY_TYPE_NULL && !is_numeric_type(n.literal_type)) return fail(HY_ERR_UNSUPPORTED, "string expressions stay on the CPU path");
+  out.type = n.literal_type;
+  double widened = 0.0;
+  switch (n.literal_type) {
+    case HY_TYPE_INT: out.literal = static_cast<uint64_t>(static_cast<int64_t>(n.literal.i32)); break;
+    case HY_TYPE_LONG: out.literal = static_cast<uint64_t>(n.literal.i64); break;
+    case HY_TYPE_FLOAT: { uint32_t word; std::memcpy(&word, &n.literal.f32, 4); out.literal = word; break; }   // (floats travel as their own bits)
+    case HY_TYPE_DOUBLE: widened = n.literal.f64; std::memcpy(&out.literal, &widened, 8); break;
+    default: break;
+  }
+  return HY_OK;
+}
+
+// Aggregate g's input expression in postfix order -> `input`: every node typed (expression_common_type per arithmetic node, like
+// hy_projection_arithmetic per call), literal operands converted.
+static hy_status type_expression(const hy_expression* e, uint32_t g, FusedInput& input, FusedQuery& q, FusedTable& table) {
+  if (e->n_nodes == 0 || e->n_nodes > HY_MAX_EXPRESSION_NODES) return fail(HY_ERR_INVALID, "aggregate %u: an expression has 1 to %d nodes", g, static_cast<int>(HY_MAX_EXPRESSION_NODES));
+  uint32_t types[4] = {0, 0, 0, 0}, depth = 0;
+  int producers[4] = {-1, -1, -1, -1};   // the LITERAL node that put the stack entry there, else -1
+  for (uint32_t k = 0; k < e->n_nodes; ++k) {
+    const hy_expression_node& n = e->nodes[k];
+    FusedNode& out = input.nodes[k];
+    out.kind = n.kind;
+    if (n.kind != HY_EXPR_ARITHMETIC) {
       if (depth == 3) return fail(HY_ERR_UNSUPPORTED, "aggregate %u: the expression needs more than three stack slots: run the operator chain", g);
-      if (n.kind == HY_EXPR_COLUMN) {
-        HY_TRY(table_column(n.column, "expression"));
-        if (!numeric(n.column->data_type)) return fail(HY_ERR_UNSUPPORTED, "string expressions stay on the CPU path");
-        uint32_t which = 0;
-        while (which < q.n_columns && q.columns[which] != n.column) ++which;
-        if (which == q.n_columns) {
-          if (q.n_columns == static_cast<uint32_t>(FUSED_COLUMNS)) return fail(HY_ERR_UNSUPPORTED, "the expressions read more than %d distinct columns: run the operator chain", FUSED_COLUMNS);
-          q.columns[q.n_columns++] = n.column;
-        }
-        out.column = which;
-        out.type = n.column->data_type;
-      } else if (n.kind == HY_EXPR_LITERAL) {
-        if (n.literal_type != HY_TYPE_NULL && !numeric(n.literal_type)) return fail(HY_ERR_UNSUPPORTED, "string expressions stay on the CPU path");
-        out.type = n.literal_type;
-        double widened = 0.0;
-        switch (n.literal_type) {
-          case HY_TYPE_INT: out.literal = static_cast<uint64_t>(static_cast<int64_t>(n.literal.i32)); break;
-          case HY_TYPE_LONG: out.literal = static_cast<uint64_t>(n.literal.i64); break;
-          case HY_TYPE_FLOAT: { uint32_t word; std::memcpy(&word, &n.literal.f32, 4); out.literal = word; break; }   // (floats travel as their own bits)
-          case HY_TYPE_DOUBLE: widened = n.literal.f64; std::memcpy(&out.literal, &widened, 8); break;
-          default: break;
-        }
-      } else {
-        return fail(HY_ERR_INVALID, "aggregate %u: unknown expression node kind %u", g, n.kind);
-      }
+      HY_TRY(type_leaf(n, g, out, q, table));
       producers[depth] = n.kind == HY_EXPR_LITERAL ? static_cast<int>(k) : -1;
       types[depth++] = out.type;
+      continue;
     }
-    if (depth != 1) return fail(HY_ERR_INVALID, "aggregate %u: the expression leaves %u results (postfix order)", g, depth);
-    if (types[0] == HY_TYPE_NULL) return fail(HY_ERR_UNSUPPORTED, "aggregate %u: an aggregate of the NULL literal stays on the CPU path", g);
-    input.n_nodes = e->n_nodes;
-    input.type = types[0];
+    if (n.op > HY_ARITH_MOD) return fail(HY_ERR_INVALID, "aggregate %u: unknown arithmetic operator %u", g, n.op);
+    if (depth < 2) return fail(HY_ERR_INVALID, "aggregate %u: node %u has no two operands below it (postfix order)", g, k);
+    const uint32_t left = types[depth - 2], right = types[depth - 1];
+    if (left == HY_TYPE_NULL && right == HY_TYPE_NULL) return fail(HY_ERR_INVALID, "Cannot deduce common type if both sides are NULL.");
+    out.op = n.op;
+    out.type = expression_common_type(left, right);
+    if (n.op <= HY_ARITH_MUL) {
+      if (producers[depth - 2] >= 0) convert_literal_operand(input.nodes[producers[depth - 2]], left, right, out.type);
+      if (producers[depth - 1] >= 0) convert_literal_operand(input.nodes[producers[depth - 1]], right, left, out.type);
+    }
+    depth -= 1;
+    types[depth - 1] = out.type;
+    producers[depth - 1] = -1;
+  }
+  if (depth != 1) return fail(HY_ERR_INVALID, "aggregate %u: the expression leaves %u results (postfix order)", g, depth);
+  if (types[0] == HY_TYPE_NULL) return fail(HY_ERR_UNSUPPORTED, "aggregate %u: an aggregate of the NULL literal stays on the CPU path", g);
+  input.n_nodes = e->n_nodes;
+  input.type = types[0];
+  return HY_OK;
+}
+
+// hy_scan_project_aggregate: checks the plan, types the expressions and runs the aggregate with fused_rows in the place of aggregate_rows.
+static hy_status run_fused(const hy_filter* filters, uint32_t n_filters, const hy_column* const* groupby, uint32_t n_groupby, const hy_fused_aggregate* aggregates,
+                           uint32_t n_aggregates, hy_aggregate_result* result) {
+  if (n_filters > HY_MAX_FILTERS) return fail(HY_ERR_UNSUPPORTED, "more than %d fused filters: run the operator chain", static_cast<int>(HY_MAX_FILTERS));
+  if (n_aggregates > MAX_AGGREGATES) return fail(HY_ERR_UNSUPPORTED, "more than %u aggregates stay on the CPU path", MAX_AGGREGATES);
+  if (n_groupby > MAX_GROUPBY) return fail(HY_ERR_UNSUPPORTED, "more than %u GROUP BY columns stay on the CPU path", MAX_GROUPBY);
+  auto query = std::make_unique<FusedQuery>();
+  FusedQuery& q = *query;
+  std::memset(&q, 0, sizeof(q));
+  FusedTable table;
+  for (uint32_t f = 0; f < n_filters; ++f) HY_TRY(table.filter(filters[f]));
+  for (uint32_t g = 0; g < n_groupby; ++g) HY_TRY(table.column(groupby[g], "GROUP BY"));
+  for (uint32_t g = 0; g < n_aggregates; ++g) {
+    q.same_as[g] = g;
+    if (!aggregates[g].input) continue;   // COUNT(*)
+    HY_TRY(type_expression(aggregates[g].input, g, q.inputs[g], q, table));
     for (uint32_t earlier = 0; earlier < g; ++earlier) {
-      if (std::memcmp(&q.inputs[earlier], &input, sizeof(FusedInput)) == 0) { q.same_as[g] = q.same_as[earlier]; break; }
+      if (std::memcmp(&q.inputs[earlier], &q.inputs[g], sizeof(FusedInput)) == 0) { q.same_as[g] = q.same_as[earlier]; break; }
     }
   }
-  if (!shape) return fail(HY_ERR_INVALID, "hy_scan_project_aggregate needs at least one column");
-  q.shape = shape;
+  if (!table.shape) return fail(HY_ERR_INVALID, "hy_scan_project_aggregate needs at least one column");
+  q.shape = table.shape;
   q.filters = filters;
   q.n_filters = n_filters;
   std::vector<hy_aggregate_spec> specs(n_aggregates ? n_aggregates : 1);
   for (uint32_t g = 0; g < n_aggregates; ++g) specs[g] = hy_aggregate_spec{aggregates[g].function, nullptr};
   return run_aggregate(groupby, n_groupby, specs.data(), n_aggregates, result, &q);
+}
+
+// ---- what the entry points share -------------------------------------------------------------------------------------------------------
+// COUNT(DISTINCT x) groups by the GROUP BY columns and x: one more key word -- more than this build's tuples hold?
+static bool needs_next_build(uint32_t n_groupby, const hy_aggregate_spec* specs, uint32_t n_aggregates) {
+  uint32_t key_columns = n_groupby;
+  for (uint32_t i = 0; specs && i < n_aggregates; ++i) if (specs[i].function == HY_AGG_COUNT_DISTINCT) key_columns = n_groupby + 1;
+  return key_columns > MAX_GROUPBY;
+}
+
+static uint32_t accumulators_of(const hy_aggregate_spec& spec) {
+  return spec.function == HY_AGG_STDDEV_SAMP ? 2u : spec.function == HY_AGG_COUNT_DISTINCT ? 0u : 1u;
+}
+static bool fits_one_pass(const hy_aggregate_spec* specs, uint32_t n_aggregates) {
+  uint32_t needed = 0;
+  for (uint32_t g = 0; g < n_aggregates; ++g) needed += accumulators_of(specs[g]);
+  return needed <= MAX_AGGREGATES && n_aggregates <= MAX_AGGREGATES;
+}
+
+// Every column lives on the calling thread's device (hy_bind_device: one worker thread per GPU) -- checked before a compressed column's twin
+// is decoded, which would happen on the wrong device with this thread's pool; then run-length / bit-packed segments give way to their
+// decoded twins (hy_device.hpp).
+static hy_status check_and_plain(const hy_column* const* groupby, uint32_t n_groupby, const hy_aggregate_spec* specs, uint32_t n_aggregates, const char* who,
+                                 std::vector<const hy_column*>& plain_groupby, std::vector<hy_aggregate_spec>& plain_specs) {
+  for (uint32_t i = 0; i < n_groupby; ++i) HY_TRY(on_this_device(groupby[i], who));
+  for (uint32_t i = 0; i < n_aggregates; ++i) HY_TRY(on_this_device(specs[i].column, who));
+  plain_groupby.assign(groupby, groupby + n_groupby);
+  for (const hy_column*& column : plain_groupby) HY_TRY(plain_column(column, &column));
+  plain_specs.assign(specs, specs + n_aggregates);
+  for (hy_aggregate_spec& spec : plain_specs) HY_TRY(plain_column(spec.column, &spec.column));
+  return HY_OK;
+}
+
+// More aggregates than one pass has accumulators for (eight; STDDEV_SAMP takes two) run in several passes over the same GROUP BY
+// columns: the groups and their order -- first occurrence, or key order -- do not depend on the aggregates, so pass k just fills its
+// own result columns (aggregate_hash.cpp:1016-1176 has one context per aggregate as well).  Each pass takes what fits.
+static hy_status run_in_passes(const hy_column* const* groupby, uint32_t n_groupby, const hy_aggregate_spec* specs, uint32_t n_aggregates, hy_aggregate_result* out) {
+  uint32_t n_groups = 0;
+  for (uint32_t begin = 0; begin < n_aggregates;) {
+    uint32_t end = begin, taken = 0;
+    while (end < n_aggregates && end - begin < MAX_AGGREGATES && taken + accumulators_of(specs[end]) <= MAX_AGGREGATES) taken += accumulators_of(specs[end++]);
+    hy_aggregate_result pass = *out;
+    pass.columns = out->columns + begin;
+    std::vector<hy_row_id> rows;
+    if (begin != 0) {   // (later passes: their representative rows only confirm that the groups came in the same order)
+      rows.resize(out->group_capacity ? out->group_capacity : 1);
+      pass.group_row_ids = out->group_row_ids ? rows.data() : nullptr;
+    }
+    const hy_status status = run_aggregate(groupby, n_groupby, specs + begin, end - begin, &pass);
+    out->n_groups = pass.n_groups;
+    if (status != HY_OK) return status;
+    if (begin == 0) n_groups = pass.n_groups;
+    else if (pass.n_groups != n_groups || (out->group_row_ids && n_groups && std::memcmp(rows.data(), out->group_row_ids, sizeof(hy_row_id) * n_groups) != 0))
+      return fail(HY_ERR_DEVICE, "hy_aggregate_hash: two passes over the same GROUP BY columns disagree about the groups");
+    begin = end;
+  }
+  return HY_OK;
+}
+
+// A result finished on the host -> hy_aggregate_hash_columns' output: one upload per column into the layout the device finish writes, and
+// the RowIDs into a result-pool buffer.
+static hy_status upload_host_columns(const hy_aggregate_result& host, uint32_t n_aggregates, uint32_t chunk_rows, ColumnSink& sink) {
+  hipStream_t stream = current_stream();
+  const uint32_t n_groups = host.n_groups;
+  sink.n_groups = n_groups;
+  std::vector<char> image;
+  for (uint32_t a = 0; a < n_aggregates; ++a) {
+    const hy_aggregate_column& column = host.columns[a];
+    ChunkedColumn chunked;
+    HY_TRY(chunked.alloc(column.data_type, n_groups, chunk_rows));
+    image.assign(chunked.bytes(), 0);
+    const char* values = static_cast<const char*>(column.values);
+    uint64_t* null_words = reinterpret_cast<uint64_t*>(image.data() + chunked.value_stride * chunked.n_chunks);
+    for (uint32_t k = 0; k < chunked.n_chunks; ++k) {
+      const uint64_t begin = uint64_t{k} * chunk_rows, size = std::min<uint64_t>(chunk_rows, n_groups - begin);
+      std::memcpy(image.data() + k * chunked.value_stride, values + begin * chunked.width, size * chunked.width);
+      for (uint64_t i = 0; i < size; ++i) if (column.is_null[begin + i]) null_words[k * chunked.null_stride + i / 64] |= uint64_t{1} << (i % 64);
+    }
+    if (!image.empty()) HY_HIP(hipMemcpyAsync(chunked.arena, image.data(), image.size(), hipMemcpyHostToDevice, stream));
+    HY_HIP(hipStreamSynchronize(stream));   // (`image` is used again)
+    HY_TRY(chunked.adopt(&sink.columns[a]));
+  }
+  if (n_groups) {
+    HY_TRY(hy_result_pool_acquire(sizeof(hy_row_id) * uint64_t{n_groups}, reinterpret_cast<void**>(&sink.row_ids)));
+    HY_HIP(hipMemcpyAsync(sink.row_ids, host.group_row_ids, sizeof(hy_row_id) * size_t{n_groups}, hipMemcpyHostToDevice, stream));
+    HY_HIP(hipStreamSynchronize(stream));
+  }
+  return HY_OK;
 }
 
 }  // namespace HY_AGG_NAMESPACE
@@ -3885,9 +4205,8 @@ static hy_status run_with_result_memory(hy_aggregate_result* result, uint32_t n_
   if (result->group_row_ids && n) HY_HIP(hipMemcpyAsync(result->group_row_ids, rows.data(), sizeof(hy_row_id) * n, hipMemcpyHostToDevice, stream));
   for (uint32_t a = 0; a < n_aggregates; ++a) {
     result->columns[a].data_type = columns[a].data_type;
-    const size_t width = columns[a].data_type == HY_TYPE_INT || columns[a].data_type == HY_TYPE_FLOAT ? 4 : 8;
     if (!result->columns[a].values) return fail(HY_ERR_INVALID, "aggregate %u: values buffer missing", a);
-    if (n) HY_HIP(hipMemcpyAsync(result->columns[a].values, values[a].data(), width * n, hipMemcpyHostToDevice, stream));
+    if (n) HY_HIP(hipMemcpyAsync(result->columns[a].values, values[a].data(), value_width(columns[a].data_type) * n, hipMemcpyHostToDevice, stream));
     if (result->columns[a].is_null && n) HY_HIP(hipMemcpyAsync(result->columns[a].is_null, nulls[a].data(), n, hipMemcpyHostToDevice, stream));
   }
   HY_HIP(hipStreamSynchronize(stream));   // (the shadows die with this call)
@@ -3918,8 +4237,7 @@ hy_status HY_AGG_ENTRY(hy_scan_project_aggregate)(const hy_filter* filters, uint
 #endif
   if (!result || (n_filters && !filters) || (n_groupby && !groupby_columns) || (n_aggregates && !aggregates)) return fail(HY_ERR_INVALID, "hy_scan_project_aggregate: null argument");
   if (n_aggregates && !result->columns) return fail(HY_ERR_INVALID, "hy_scan_project_aggregate: result columns missing");
-  // every column of the plan lives on the calling thread's device (hy_bind_device: one worker thread per GPU) -- checked before a compressed
-  // column's twin is decoded, which would happen on the wrong device with this thread's pool
+  // (on this device, then the decoded twins: as in check_and_plain)
   for (uint32_t f = 0; f < n_filters; ++f) HY_TRY(on_this_device(filters[f].column, "hy_scan_project_aggregate"));
   for (uint32_t i = 0; i < n_groupby; ++i) HY_TRY(on_this_device(groupby_columns[i], "hy_scan_project_aggregate"));
   for (uint32_t g = 0; g < n_aggregates; ++g) {
@@ -3927,7 +4245,6 @@ hy_status HY_AGG_ENTRY(hy_scan_project_aggregate)(const hy_filter* filters, uint
     for (uint32_t k = 0; k < aggregates[g].input->n_nodes && k < HY_MAX_EXPRESSION_NODES; ++k)
       if (aggregates[g].input->nodes[k].kind == HY_EXPR_COLUMN) HY_TRY(on_this_device(aggregates[g].input->nodes[k].column, "hy_scan_project_aggregate"));
   }
-  // run-length / bit-packed segments: the decoded twins (hy_device.hpp)
   std::vector<hy_filter> plain_filters(filters, filters + n_filters);
   for (hy_filter& filter : plain_filters) HY_TRY(plain_column(filter.column, &filter.column));
   std::vector<const hy_column*> plain_groupby(groupby_columns, groupby_columns + n_groupby);
@@ -3950,65 +4267,59 @@ hy_status HY_AGG_ENTRY(hy_scan_project_aggregate)(const hy_filter* filters, uint
 hy_status HY_AGG_ENTRY(hy_aggregate_hash)(const hy_column* const* groupby_columns, uint32_t n_groupby, const hy_aggregate_spec* aggregates,
                                           uint32_t n_aggregates, hy_aggregate_result* result) {
 #ifdef HY_AGG_NEXT
-  {   // (COUNT(DISTINCT x) groups by the GROUP BY columns and x: one more key word)
-    uint32_t key_columns = n_groupby;
-    for (uint32_t i = 0; aggregates && i < n_aggregates; ++i) if (aggregates[i].function == HY_AGG_COUNT_DISTINCT) key_columns = n_groupby + 1;
-    g_last_aggregate_was_wide = key_columns > MAX_GROUPBY;
-    if (g_last_aggregate_was_wide) return HY_AGG_NEXT(hy_aggregate_hash)(groupby_columns, n_groupby, aggregates, n_aggregates, result);
-  }
+  g_last_aggregate_was_wide = needs_next_build(n_groupby, aggregates, n_aggregates);
+  if (g_last_aggregate_was_wide) return HY_AGG_NEXT(hy_aggregate_hash)(groupby_columns, n_groupby, aggregates, n_aggregates, result);
 #endif
   if (!result || (n_groupby && !groupby_columns) || (n_aggregates && !aggregates)) return fail(HY_ERR_INVALID, "hy_aggregate_hash: null argument");
   if (n_aggregates && !result->columns) return fail(HY_ERR_INVALID, "hy_aggregate_hash: result columns missing");
-  for (uint32_t i = 0; i < n_groupby; ++i) HY_TRY(on_this_device(groupby_columns[i], "hy_aggregate_hash"));
-  for (uint32_t i = 0; i < n_aggregates; ++i) HY_TRY(on_this_device(aggregates[i].column, "hy_aggregate_hash"));
-  std::vector<const hy_column*> plain_groupby(groupby_columns, groupby_columns + n_groupby);   // run-length / bit-packed segments: the decoded twins
-  for (const hy_column*& column : plain_groupby) HY_TRY(plain_column(column, &column));
-  std::vector<hy_aggregate_spec> plain_aggregates(aggregates, aggregates + n_aggregates);
-  for (hy_aggregate_spec& spec : plain_aggregates) HY_TRY(plain_column(spec.column, &spec.column));
+  std::vector<const hy_column*> plain_groupby;
+  std::vector<hy_aggregate_spec> plain_aggregates;
+  HY_TRY(check_and_plain(groupby_columns, n_groupby, aggregates, n_aggregates, "hy_aggregate_hash", plain_groupby, plain_aggregates));
   return run_with_result_memory(result, n_aggregates, [&](hy_aggregate_result* out) -> hy_status {
-    // More aggregates than one pass has accumulators for (eight; STDDEV_SAMP takes two) run in several passes over the same GROUP BY
-    // columns: the groups and their order -- first occurrence, or key order -- do not depend on the aggregates, so pass k just fills its
-    // own result columns (aggregate_hash.cpp:1016-1176 has one context per aggregate as well).  Each pass takes what fits.
-    auto accumulators_of = [&](const hy_aggregate_spec& spec) -> uint32_t {
-      return spec.function == HY_AGG_STDDEV_SAMP ? 2u : spec.function == HY_AGG_COUNT_DISTINCT ? 0u : 1u;
-    };
-    uint32_t needed = 0;
-    for (uint32_t g = 0; g < n_aggregates; ++g) needed += accumulators_of(plain_aggregates[g]);
-    if (needed <= MAX_AGGREGATES && n_aggregates <= MAX_AGGREGATES) return run_aggregate(plain_groupby.data(), n_groupby, plain_aggregates.data(), n_aggregates, out);
-    uint32_t n_groups = 0;
-    std::vector<hy_row_id> first_pass_rows;
-    for (uint32_t begin = 0; begin < n_aggregates;) {
-      uint32_t end = begin, taken = 0;
-      while (end < n_aggregates && end - begin < MAX_AGGREGATES && taken + accumulators_of(plain_aggregates[end]) <= MAX_AGGREGATES) taken += accumulators_of(plain_aggregates[end++]);
-      hy_aggregate_result pass = *out;
-      pass.columns = out->columns + begin;
-      std::vector<hy_row_id> rows;
-      if (begin != 0) {   // (later passes: their representative rows only confirm that the groups came in the same order)
-        rows.resize(out->group_capacity ? out->group_capacity : 1);
-        pass.group_row_ids = out->group_row_ids ? rows.data() : nullptr;
-      }
-      const hy_status status = run_aggregate(plain_groupby.data(), n_groupby, plain_aggregates.data() + begin, end - begin, &pass);
-      out->n_groups = pass.n_groups;
-      if (status != HY_OK) return status;
-      if (begin == 0) n_groups = pass.n_groups;
-      else if (pass.n_groups != n_groups || (out->group_row_ids && n_groups && std::memcmp(rows.data(), out->group_row_ids, sizeof(hy_row_id) * n_groups) != 0))
-        return fail(HY_ERR_DEVICE, "hy_aggregate_hash: two passes over the same GROUP BY columns disagree about the groups");
-      begin = end;
-    }
-    return HY_OK;
+    if (fits_one_pass(plain_aggregates.data(), n_aggregates)) return run_aggregate(plain_groupby.data(), n_groupby, plain_aggregates.data(), n_aggregates, out);
+    return run_in_passes(plain_groupby.data(), n_groupby, plain_aggregates.data(), n_aggregates, out);
   });
+}
+
+// hy_aggregate_hash_columns' work between the argument checks and the hand-over: the aggregate into the sink (several passes go through
+// hy_aggregate_hash and come back as a host result), a host result uploaded, the GROUP BY columns gathered at the representative rows.
+static hy_status aggregate_into_columns(const hy_column* const* groupby_columns, uint32_t n_groupby, const hy_aggregate_spec* aggregates, uint32_t n_aggregates, uint32_t chunk_rows,
+                                        hy_aggregate_columns* out, ColumnSink& sink) {
+  std::vector<const hy_column*> plain_groupby;
+  std::vector<hy_aggregate_spec> plain_aggregates;
+  HY_TRY(check_and_plain(groupby_columns, n_groupby, aggregates, n_aggregates, "hy_aggregate_hash_columns", plain_groupby, plain_aggregates));
+  std::vector<hy_aggregate_column> host_columns(std::max<uint32_t>(1, n_aggregates));
+  std::memset(host_columns.data(), 0, sizeof(hy_aggregate_column) * host_columns.size());
+  hy_aggregate_result host{};
+  host.mem = HY_MEM_HOST;
+  host.columns = host_columns.data();
+  if (fits_one_pass(plain_aggregates.data(), n_aggregates)) {
+    HY_TRY(run_aggregate(plain_groupby.data(), n_groupby, plain_aggregates.data(), n_aggregates, &host, nullptr, &sink));
+  } else {   // a group per input row is the most there can be (+ 1: no GROUP BY over an empty input)
+    const hy_column* shape = n_groupby ? groupby_columns[0] : nullptr;
+    for (uint32_t g = 0; g < n_aggregates && !shape; ++g) shape = aggregates[g].column;
+    if (!shape) return fail(HY_ERR_INVALID, "hy_aggregate_hash_columns needs at least one column");
+    if (shape->rows >= 0xFFFFFFFFull) return fail(HY_ERR_UNSUPPORTED, "hy_aggregate_hash_columns: %llu rows in several passes", static_cast<unsigned long long>(shape->rows));
+    HY_TRY(sink.host_buffers(static_cast<uint32_t>(shape->rows + 1), n_aggregates, &host));   // (allocated, not touched)
+    HY_TRY(HY_AGG_ENTRY(hy_aggregate_hash)(groupby_columns, n_groupby, aggregates, n_aggregates, &host));
+  }
+  if (!sink.finished) HY_TRY(upload_host_columns(host, n_aggregates, chunk_rows, sink));
+  // the GROUP BY columns at the representative rows (write_groupby_output): the RowIDs are read where they lie
+  for (uint32_t g = 0; g < n_groupby; ++g) {
+    if (g < 64 && (out->skip_groupby_mask >> g & 1)) continue;
+    const uint32_t type = groupby_columns[g]->data_type;
+    if (type < HY_TYPE_INT || type > HY_TYPE_DOUBLE || groupby_columns[g]->has_dictionary_without_values) continue;   // (what hy_column_gather refuses)
+    HY_TRY(hy_column_gather(groupby_columns[g], sink.row_ids, sink.n_groups, chunk_rows, &out->groupby_columns[g]));
+  }
+  return HY_OK;
 }
 
 // hy_aggregate_hash's result as the columns of the output table, in device memory (include/hyrise_amd.h).
 hy_status HY_AGG_ENTRY(hy_aggregate_hash_columns)(const hy_column* const* groupby_columns, uint32_t n_groupby, const hy_aggregate_spec* aggregates,
                                                   uint32_t n_aggregates, uint32_t chunk_rows, hy_aggregate_columns* out) {
 #ifdef HY_AGG_NEXT
-  {   // (as in hy_aggregate_hash: COUNT(DISTINCT x) takes one more key word)
-    uint32_t key_columns = n_groupby;
-    for (uint32_t i = 0; aggregates && i < n_aggregates; ++i) if (aggregates[i].function == HY_AGG_COUNT_DISTINCT) key_columns = n_groupby + 1;
-    g_last_aggregate_was_wide = key_columns > MAX_GROUPBY;
-    if (g_last_aggregate_was_wide) return HY_AGG_NEXT(hy_aggregate_hash_columns)(groupby_columns, n_groupby, aggregates, n_aggregates, chunk_rows, out);
-  }
+  g_last_aggregate_was_wide = needs_next_build(n_groupby, aggregates, n_aggregates);
+  if (g_last_aggregate_was_wide) return HY_AGG_NEXT(hy_aggregate_hash_columns)(groupby_columns, n_groupby, aggregates, n_aggregates, chunk_rows, out);
 #endif
   if (!out || (n_groupby && (!groupby_columns || !out->groupby_columns)) || (n_aggregates && (!aggregates || !out->aggregate_columns)))
     return fail(HY_ERR_INVALID, "hy_aggregate_hash_columns: null argument");
@@ -4017,69 +4328,10 @@ hy_status HY_AGG_ENTRY(hy_aggregate_hash_columns)(const hy_column* const* groupb
   for (uint32_t g = 0; g < n_groupby; ++g) out->groupby_columns[g] = nullptr;
   for (uint32_t a = 0; a < n_aggregates; ++a) out->aggregate_columns[a] = nullptr;
   if (!chunk_rows) return fail(HY_ERR_INVALID, "hy_aggregate_hash_columns: chunk_rows == 0");
-  for (uint32_t i = 0; i < n_groupby; ++i) HY_TRY(on_this_device(groupby_columns[i], "hy_aggregate_hash_columns"));
-  for (uint32_t i = 0; i < n_aggregates; ++i) HY_TRY(on_this_device(aggregates[i].column, "hy_aggregate_hash_columns"));
-  std::vector<const hy_column*> plain_groupby(groupby_columns, groupby_columns + n_groupby);   // run-length / bit-packed segments: the decoded twins
-  for (const hy_column*& column : plain_groupby) HY_TRY(plain_column(column, &column));
-  std::vector<hy_aggregate_spec> plain_aggregates(aggregates, aggregates + n_aggregates);
-  for (hy_aggregate_spec& spec : plain_aggregates) HY_TRY(plain_column(spec.column, &spec.column));
-
   ColumnSink sink;
   sink.chunk_rows = chunk_rows;
   sink.columns = out->aggregate_columns;
-  std::vector<hy_aggregate_column> host_columns(std::max<uint32_t>(1, n_aggregates));
-  std::memset(host_columns.data(), 0, sizeof(hy_aggregate_column) * host_columns.size());
-  hy_aggregate_result host{};
-  host.mem = HY_MEM_HOST;
-  host.columns = host_columns.data();
-  hipStream_t stream = current_stream();
-  const hy_status status = [&]() -> hy_status {
-    uint32_t needed = 0;
-    for (uint32_t g = 0; g < n_aggregates; ++g) needed += plain_aggregates[g].function == HY_AGG_STDDEV_SAMP ? 2u : plain_aggregates[g].function == HY_AGG_COUNT_DISTINCT ? 0u : 1u;
-    if (needed <= MAX_AGGREGATES && n_aggregates <= MAX_AGGREGATES) {
-      HY_TRY(run_aggregate(plain_groupby.data(), n_groupby, plain_aggregates.data(), n_aggregates, &host, nullptr, &sink));
-    } else {   // several passes (hy_aggregate_hash): a group per input row is the most there can be (+ 1: no GROUP BY over an empty input)
-      const hy_column* shape = n_groupby ? groupby_columns[0] : nullptr;
-      for (uint32_t g = 0; g < n_aggregates && !shape; ++g) shape = aggregates[g].column;
-      if (!shape) return fail(HY_ERR_INVALID, "hy_aggregate_hash_columns needs at least one column");
-      if (shape->rows >= 0xFFFFFFFFull) return fail(HY_ERR_UNSUPPORTED, "hy_aggregate_hash_columns: %llu rows in several passes", static_cast<unsigned long long>(shape->rows));
-      HY_TRY(sink.host_buffers(static_cast<uint32_t>(shape->rows + 1), n_aggregates, &host));   // (allocated, not touched)
-      HY_TRY(HY_AGG_ENTRY(hy_aggregate_hash)(groupby_columns, n_groupby, aggregates, n_aggregates, &host));
-    }
-    if (!sink.finished) {   // finished on the host: one upload per column into the layout the device finish writes
-      const uint32_t n_groups = host.n_groups;
-      sink.n_groups = n_groups;
-      std::vector<char> image;
-      for (uint32_t a = 0; a < n_aggregates; ++a) {
-        ChunkedColumn chunked;
-        HY_TRY(chunked.alloc(host_columns[a].data_type, n_groups, chunk_rows));
-        image.assign(chunked.bytes(), 0);
-        const char* values = static_cast<const char*>(host_columns[a].values);
-        uint64_t* null_words = reinterpret_cast<uint64_t*>(image.data() + chunked.value_stride * chunked.n_chunks);
-        for (uint32_t k = 0; k < chunked.n_chunks; ++k) {
-          const uint64_t begin = uint64_t{k} * chunk_rows, size = std::min<uint64_t>(chunk_rows, n_groups - begin);
-          std::memcpy(image.data() + k * chunked.value_stride, values + begin * chunked.width, size * chunked.width);
-          for (uint64_t i = 0; i < size; ++i) if (host_columns[a].is_null[begin + i]) null_words[k * chunked.null_stride + i / 64] |= uint64_t{1} << (i % 64);
-        }
-        if (!image.empty()) HY_HIP(hipMemcpyAsync(chunked.arena, image.data(), image.size(), hipMemcpyHostToDevice, stream));
-        HY_HIP(hipStreamSynchronize(stream));   // (`image` is used again)
-        HY_TRY(chunked.adopt(&out->aggregate_columns[a]));
-      }
-      if (n_groups) {
-        HY_TRY(hy_result_pool_acquire(sizeof(hy_row_id) * uint64_t{n_groups}, reinterpret_cast<void**>(&sink.row_ids)));
-        HY_HIP(hipMemcpyAsync(sink.row_ids, host.group_row_ids, sizeof(hy_row_id) * size_t{n_groups}, hipMemcpyHostToDevice, stream));
-        HY_HIP(hipStreamSynchronize(stream));
-      }
-    }
-    // the GROUP BY columns at the representative rows (write_groupby_output): the RowIDs are read where they lie
-    for (uint32_t g = 0; g < n_groupby; ++g) {
-      if (g < 64 && (out->skip_groupby_mask >> g & 1)) continue;
-      const uint32_t type = groupby_columns[g]->data_type;
-      if (type < HY_TYPE_INT || type > HY_TYPE_DOUBLE || groupby_columns[g]->has_dictionary_without_values) continue;   // (what hy_column_gather refuses)
-      HY_TRY(hy_column_gather(groupby_columns[g], sink.row_ids, sink.n_groups, chunk_rows, &out->groupby_columns[g]));
-    }
-    return HY_OK;
-  }();
+  const hy_status status = aggregate_into_columns(groupby_columns, n_groupby, aggregates, n_aggregates, chunk_rows, out, sink);
   if (status != HY_OK) {   // nothing is left to the caller
     for (uint32_t g = 0; g < n_groupby; ++g) { if (out->groupby_columns[g]) (void)hy_column_destroy(out->groupby_columns[g]); out->groupby_columns[g] = nullptr; }
     for (uint32_t a = 0; a < n_aggregates; ++a) { if (out->aggregate_columns[a]) (void)hy_column_destroy(out->aggregate_columns[a]); out->aggregate_columns[a] = nullptr; }
@@ -4102,7 +4354,7 @@ HY_AGG_DEBUG(hy_debug_aggregate_path, g_agg_path)
 // debug / tests only: 1 = the last aggregate of this process was ordered and written by the finish kernels (large results of plain functions)
 HY_AGG_DEBUG(hy_debug_aggregate_finished_on_device, g_agg_finished_on_device)
 
-// debug / tests only: 1 = the last hy_aggregate_hash of this process ran aggregate_small_domain (aggregate_small.hpp)
+// debug / tests only: 1 = the last hy_aggregate_hash of this process ran aggregate_small_domain (aggregate_small.hpp), 2 = fused_small_domain
 HY_AGG_DEBUG(hy_debug_aggregate_small_domain, g_agg_small)
 
 // debug only (HY_AGG_TRACE): the per-slice phase stamps of the last aggregate_rows launch; not part of the public header
