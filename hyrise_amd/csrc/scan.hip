@@ -189,7 +189,17 @@ __device__ __forceinline__ void finish_job(const DevSegment& s, uint32_t c, cons
       upper = p.per_chunk_upper[c];
       found = p.per_chunk_found ? p.per_chunk_found[c] != 0 : false;
     }
-    if (is_between(cond)) {  // column_between_table_scan_impl.cpp:112-193
+    // A NaN literal: the bounds above searched nothing (every comparison with it is false; `<= NaN`, `>= NaN` and BETWEEN would come out as
+    // "all rows").  The chunk answers like the row-by-row comparison of every other layout: no row matches, except for <> (not found: all).
+    const bool between = is_between(cond);
+    const bool nan_literal = s.data_type == HY_TYPE_FLOAT    ? p.value.f32 != p.value.f32 || (between && p.value2.f32 != p.value2.f32)
+                             : s.data_type == HY_TYPE_DOUBLE ? p.value.f64 != p.value.f64 || (between && p.value2.f64 != p.value2.f64)
+                                                             : false;
+    if (nan_literal && cond != HY_PRED_NOT_EQUALS) {
+      job.mode = JOB_NONE;
+      return;
+    }
+    if (between) {  // column_between_table_scan_impl.cpp:112-193
       uint32_t lower_vid, upper_vid;
       if ((s.aux || s.aux_size == 0) && s.data_type != HY_TYPE_STRING) {
         lower_vid = lower_inclusive(cond) ? lower : upper;

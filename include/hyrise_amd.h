@@ -383,7 +383,8 @@ hy_status hy_column_chunk_count(const hy_column* column, uint32_t* chunks);
 
 /* ---- TableScan (replaces TableScan::_on_execute's per-chunk scan_chunk() fan-out, table_scan.cpp:97-240) --------- */
 /* ColumnVsValue / ColumnBetween / ColumnIsNull (column_vs_value_table_scan_impl.cpp, column_between_table_scan_impl.cpp,
- * column_is_null_table_scan_impl.cpp), over data or reference columns.  excluded_chunks may be NULL. */
+ * column_is_null_table_scan_impl.cpp), over data or reference columns.  excluded_chunks may be NULL.
+ * Floating point compares as IEEE on every layout: -0.0 equals 0.0; a NaN row and a NaN literal (it is not refused) match only <>. */
 hy_status hy_table_scan(const hy_column* column, const hy_predicate* predicate, const uint32_t* excluded_chunks,
                         uint32_t n_excluded, hy_scan_result* result);
 /* `column IN (v1, ..., vk)` / `column NOT IN (...)` over a literal list -- the InExpressions that InExpressionRewriteRule leaves alone

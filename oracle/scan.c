@@ -187,6 +187,12 @@ static int scan_vs_value_dictionary(const hy_segment* s, uint32_t data_chunk_id,
   if (s->aux && s->data_type != HY_TYPE_STRING) {
     /* _get_search_value_id (column_vs_value_table_scan_impl.cpp:211-226) */
     const decoded_t lit = literal_of(p->value_type, &p->value);
+    /* A NaN literal: lower_bound / upper_bound with it search nothing (every comparison is false; `<= NaN` and `>= NaN` would come out
+     * as "all rows").  The scan answers like the generic path's row-by-row comparison: nothing matches, except for <> (not found: all). */
+    if (type_is_float(s->data_type) && isnan(lit.f) && cond != HY_PRED_NOT_EQUALS) {
+      if (state) *state = HY_CHUNK_NONE_MATCH;
+      return 0;
+    }
     search = dict_bound(s, lit, use_upper);
     found = search != HY_INVALID_VALUE_ID && dict_value_equals(s, search, lit);
   } else {
@@ -280,6 +286,10 @@ static int scan_between_dictionary(const hy_segment* s, uint32_t data_chunk_id, 
   uint32_t lower, upper;
   if (s->aux && s->data_type != HY_TYPE_STRING) { /* :112-124 */
     const decoded_t l = literal_of(p->value_type, &p->value), r = literal_of(p->value_type, &p->value2);
+    if (type_is_float(s->data_type) && (isnan(l.f) || isnan(r.f))) { /* (a NaN bound: no row lies between, see scan_vs_value_dictionary) */
+      if (state) *state = HY_CHUNK_NONE_MATCH;
+      return 0;
+    }
     lower = dict_bound(s, l, !lower_inclusive(p->condition));
     upper = dict_bound(s, r, upper_inclusive(p->condition));
   } else {
@@ -319,11 +329,14 @@ static int scan_between_generic(const hy_segment* s, uint32_t out_chunk_id, cons
   const decoded_t l = literal_of(p->value_type, &p->value), r = literal_of(p->value_type, &p->value2);
   const int li = lower_inclusive(p->condition), ui = upper_inclusive(p->condition);
   if (!type_is_float(s->data_type)) {
-    /* :86-94 empty range; then type_comparison.hpp:120-132 in the column's unsigned type */
+    /* :86-94 empty range; then type_comparison.hpp:120-132 in the column's unsigned type.  The reference forms `right - left` and
+     * `upper_bound - lower_bound` in the column's SIGNED type: bounds further apart than the type's maximum overflow it (undefined
+     * behaviour).  What it means is lower <= x <= upper, so the differences are formed in a wider type here; wherever the reference's
+     * arithmetic is defined the two agree. */
     if (s->data_type == HY_TYPE_INT) {
-      const int32_t diff = (int32_t)((uint32_t)(int32_t)r.i - (uint32_t)(int32_t)l.i) - !li - !ui;
+      const int64_t diff = r.i - l.i - !li - !ui;
       if (diff < 0) return 0;
-      const int32_t lb = li ? (int32_t)l.i : (int32_t)l.i + 1, ub = ui ? (int32_t)r.i : (int32_t)r.i - 1;
+      const int32_t lb = (int32_t)(l.i + !li), ub = (int32_t)(r.i - !ui);
       const uint32_t vd = (uint32_t)ub - (uint32_t)lb;
       for (uint32_t i = 0; i < pos->count; ++i) {
         const uint32_t off = pos_offset(pos, i);
@@ -331,9 +344,9 @@ static int scan_between_generic(const hy_segment* s, uint32_t out_chunk_id, cons
         if ((uint32_t)((uint32_t)(int32_t)seg_value(s, off).i - (uint32_t)lb) <= vd) emit(matches, n, out_chunk_id, i);
       }
     } else {
-      const int64_t diff = (int64_t)((uint64_t)r.i - (uint64_t)l.i) - !li - !ui;
+      const __int128 diff = (__int128)r.i - (__int128)l.i - !li - !ui;
       if (diff < 0) return 0;
-      const int64_t lb = li ? l.i : l.i + 1, ub = ui ? r.i : r.i - 1;
+      const int64_t lb = (int64_t)((__int128)l.i + !li), ub = (int64_t)((__int128)r.i - !ui);
       const uint64_t vd = (uint64_t)ub - (uint64_t)lb;
       for (uint32_t i = 0; i < pos->count; ++i) {
         const uint32_t off = pos_offset(pos, i);
