@@ -246,10 +246,30 @@ hy_status string_twins_launch(const StringTwins& twins, hipStream_t stream);
 // for `total` entries; the refusals of a dictionary (device, E >= 2^31) and of a string column with its dictionary (hy_column_string_ranks'),
 // before any launch; the launch sequence itself -- d_ranks[entry_offsets[c] + v] and *d_n_distinct, carved from `sc`, total > 0.
 struct Scratch;
-size_t order_scratch_bytes(uint64_t total);
 hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point);
 hy_status string_column_check(const hy_column* column, const hy_string_dictionary* dict, const char* entry_point);
-hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream);
+// With d_windows (one EntryWindow per entry, at entry_offsets[c] + v) the entries are ordered as their windows read; `sorted_chunks` says that
+// every chunk's windowed entries still ascend (equal neighbours allowed), so that the merge may start from whole chunks as it does without windows.
+struct EntryWindow {   // bytes [begin, begin + length) of a dictionary entry
+  uint32_t begin;
+  uint32_t length;
+};
+size_t order_scratch_bytes(uint64_t total);
+hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream, const EntryWindow* d_windows = nullptr,
+                              bool sorted_chunks = true);
+// string_gather.hip's back end for the other producers of string columns (string_substr.hip).  The output chunks' sizes on the host:
+struct OutChunks {
+  std::vector<uint32_t> sizes;
+  uint32_t chunk_rows = 0;   // 0: the sizes are another column's (uploaded as row_base / vector_at)
+  uint64_t n = 0;
+};
+// what gather_entries, the ranking and the front end in front of it carve from the scratch arena (`inverse`: 4 more bytes per source entry)
+size_t gather_scratch_bytes(uint64_t n_source_entries, uint64_t n, uint64_t n_chunks, bool inverse);
+// d_entry: per output row the global entry index into `dict`, or -1; d_ranks: the order of the (windowed) entries, queued on `stream` already
+// (nullptr for a dictionary without entries); d_windows: what of every entry the output holds, or nullptr: all of it.
+hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out, const int32_t* d_entry, const int32_t* d_ranks, const EntryWindow* d_windows, Scratch& sc,
+                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict);
+hy_status empty_string_results(hy_column** result, hy_string_dictionary** result_dict);   // a column and a dictionary of zero chunks
 // The int32 stand-in of a string column over a table of E int32_t in device memory (entry v of data chunk c reads d_table[entry_offsets[c] + v]):
 // the caller's attribute vectors and PosLists, shared.  A reference column's stand-in owns its data stand-in; the table stays the caller's.
 hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, int32_t* d_table, hy_column** out);

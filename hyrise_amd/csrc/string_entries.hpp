@@ -33,6 +33,29 @@ __device__ __forceinline__ Entry entry_of(const LikeChunk& chunk, uint32_t v, ui
   return Entry{slot, length};
 }
 
+// strnlen(slot, L) of a fixed slot, four bytes at a time where the slot lies on a 4-byte boundary
+__device__ __forceinline__ uint32_t slot_length(const uint8_t* slot, uint32_t L) {
+  uint32_t length = 0;
+  if (reinterpret_cast<uintptr_t>(slot) % 4 == 0) {
+    for (; length + 4 <= L; length += 4) {
+      const uint32_t w = *reinterpret_cast<const uint32_t*>(slot + length);
+      if ((w - 0x01010101u) & ~w & 0x80808080u) break;   // a zero byte among the four
+    }
+  }
+  while (length < L && slot[length] != 0) ++length;
+  return length;
+}
+
+// The entry seen through a window (SUBSTR, string_substr.hip): bytes [begin, begin + length) of it.  `windows` are the chunk's, one per entry,
+// made from the entries' own lengths (entry_windows: begin + length never exceeds the entry); nullptr is the identity window, the whole entry.
+__device__ __forceinline__ Entry entry_of(const LikeChunk& chunk, uint32_t v, uint32_t end, const EntryWindow* windows) {
+  if (!windows) return entry_of(chunk, v, end);
+  const uint8_t* chars = reinterpret_cast<const uint8_t*>(chunk.chars);
+  const EntryWindow window = windows[v];
+  const uint8_t* entry = chunk.offsets ? chars + min(chunk.offsets[v], end) : chars + size_t{v} * chunk.string_length;
+  return Entry{entry + window.begin, window.length};
+}
+
 __device__ __forceinline__ uint32_t load_word(const uint8_t* p) {   // four bytes at any address, first byte most significant
   uint32_t w;
   __builtin_memcpy(&w, p, 4);

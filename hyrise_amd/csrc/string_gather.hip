@@ -209,8 +209,9 @@ __global__ __launch_bounds__(WG) void value_ids(OutLayout l, const int32_t* entr
 }
 
 // ---- step 4: where every output entry's bytes are, and how many ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void unique_lengths(const LikeChunk* chunks, const uint64_t* entry_offsets, uint32_t n_source_chunks, const int32_t* unique_entry,
-                                                     const uint32_t* n_unique, const uint8_t** source, uint64_t* local_bytes, uint64_t* tile_bytes) {
+// (windows: what of every source entry the output holds -- SUBSTR -- or nullptr: all of it)
+__global__ __launch_bounds__(WG) void unique_lengths(const LikeChunk* chunks, const uint64_t* entry_offsets, uint32_t n_source_chunks, const EntryWindow* windows,
+                                                     const int32_t* unique_entry, const uint32_t* n_unique, const uint8_t** source, uint64_t* local_bytes, uint64_t* tile_bytes) {
   __shared__ uint64_t s_sums[WG];
   const uint64_t u = uint64_t{blockIdx.x} * WG + threadIdx.x;
   const bool mine = u < *n_unique;
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(WG) void unique_lengths(const LikeChunk* chunks, co
     const uint32_t e = static_cast<uint32_t>(unique_entry[u]);
     const uint32_t c = last_at_or_below(entry_offsets, n_source_chunks, e);
     const LikeChunk chunk = chunks[c];
-    const Entry found = entry_of(chunk, min(static_cast<uint32_t>(e - entry_offsets[c]), chunk.n_entries - 1), chunk_bytes(chunk));
+    const Entry found = entry_of(chunk, min(static_cast<uint32_t>(e - entry_offsets[c]), chunk.n_entries - 1), chunk_bytes(chunk), windows ? windows + entry_offsets[c] : nullptr);
     source[u] = found.bytes;
     length = found.length;
   }
@@ -327,6 +328,8 @@ __global__ __launch_bounds__(WG) void copy_entry_bytes(const uint8_t* const* sou
 
 uint32_t tiles_of(uint64_t items) { return static_cast<uint32_t>((items + WG - 1) / WG); }
 
+}  // namespace
+
 // What gather_entries and the front ends in front of it carve from the scratch arena
 size_t gather_scratch_bytes(uint64_t n_source_entries, uint64_t n, uint64_t n_chunks, bool inverse) {
   const uint64_t tiles = tiles_of(n);
@@ -335,17 +338,10 @@ size_t gather_scratch_bytes(uint64_t n_source_entries, uint64_t n, uint64_t n_ch
          2 * align_up(8 * (n_chunks + 1), 256) + 16 * 256 + 4096;
 }
 
-// The output chunks' sizes on the host, and what of them the kernels need in device memory
-struct OutChunks {
-  std::vector<uint32_t> sizes;
-  uint32_t chunk_rows = 0;   // 0: the sizes are another column's (uploaded as row_base / vector_at)
-  uint64_t n = 0;
-};
-
 // The back end.  d_entry: per output row the global entry index into `dict`, or -1; d_ranks: the dictionary's order (column_order_launch), queued
-// on `stream` already (nullptr for a dictionary without entries).  The arena `sc` is reserved by the caller (gather_scratch_bytes).
-hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out, const int32_t* d_entry, const int32_t* d_ranks, Scratch& sc, hipStream_t stream, const char* name,
-                         hy_column** result, hy_string_dictionary** result_dict) {
+// on `stream` already (nullptr for a dictionary without entries); d_windows: what of every entry the output holds, ranked as such, or nullptr.  The arena `sc` is reserved by the caller (gather_scratch_bytes).
+hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out, const int32_t* d_entry, const int32_t* d_ranks, const EntryWindow* d_windows, Scratch& sc,
+                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict) {
   const uint32_t n = static_cast<uint32_t>(out.n);
   const uint32_t n_chunks = static_cast<uint32_t>(out.sizes.size());
   const uint32_t n_source_entries = static_cast<uint32_t>(dict->entry_offsets[dict->n_chunks]);
@@ -414,7 +410,7 @@ hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out,
   hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_heads, n_tiles, d_n_unique);
   hipLaunchKernelGGL(chunk_firsts, dim3(tiles_of(uint64_t{n_chunks} + 1)), dim3(WG), 0, stream, layout, local, tile_heads, chunk_first);
   hipLaunchKernelGGL(value_ids, dim3(n_tiles), dim3(WG), 0, stream, layout, d_entry, order.perm, local, tile_heads, chunk_first, arena, unique_entry);
-  hipLaunchKernelGGL(unique_lengths, dim3(n_tiles), dim3(WG), 0, stream, dict->d_chunks, dict->d_entry_offsets, dict->n_chunks, unique_entry, d_n_unique, source, local_bytes, tile_bytes);
+  hipLaunchKernelGGL(unique_lengths, dim3(n_tiles), dim3(WG), 0, stream, dict->d_chunks, dict->d_entry_offsets, dict->n_chunks, d_windows, unique_entry, d_n_unique, source, local_bytes, tile_bytes);
   hipLaunchKernelGGL(scan_tiles<uint64_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_bytes, n_tiles, d_total_bytes);
   hipLaunchKernelGGL(chunk_totals, dim3(tiles_of(n_chunks)), dim3(WG), 0, stream, chunk_first, n_chunks, local_bytes, tile_bytes, d_totals);
   st = check(hipGetLastError());
@@ -483,7 +479,7 @@ hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out,
 }
 
 // Results without rows: a column and a dictionary of zero chunks
-hy_status empty_results(hy_column** result, hy_string_dictionary** result_dict) {
+hy_status empty_string_results(hy_column** result, hy_string_dictionary** result_dict) {
   hy_string_dictionary_chunk no_chunk{};
   hy_segment no_segment{};
   HY_TRY(hy_string_dictionary_create(&no_chunk, 0, HY_MEM_DEVICE, result_dict));
@@ -494,6 +490,8 @@ hy_status empty_results(hy_column** result, hy_string_dictionary** result_dict) 
   }
   return st;
 }
+
+namespace {
 
 // Destroys a column when the scope ends (the stand-in of the RowID front end: it lives as long as the launches that read it)
 struct ColumnGuard {
@@ -519,7 +517,7 @@ hy_status hy_string_column_gather(const hy_column* column, const hy_string_dicti
   if (reinterpret_cast<uintptr_t>(positions) % 8 != 0) return fail(HY_ERR_INVALID, "%s: positions not on an 8-byte boundary", name);
   HY_TRY(string_column_check(column, dict, name));
   if (n >= (uint64_t{1} << 32)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu rows (32-bit row ids)", name, static_cast<unsigned long long>(n));
-  if (!n) return empty_results(result, result_dict);
+  if (!n) return empty_string_results(result, result_dict);
   OutChunks out;
   out.n = n;
   out.chunk_rows = chunk_rows;
@@ -555,7 +553,7 @@ hy_status hy_string_column_gather(const hy_column* column, const hy_string_dicti
   if (st == HY_OK) hipLaunchKernelGGL(entries_at_positions, dim3(grid_for(n)), dim3(WG), 0, stream, values.as<int32_t>(), nulls.as<uint8_t>(), column->d_row_base, column->n_chunks, positions,
                                            static_cast<uint32_t>(n), static_cast<uint32_t>(n_source_entries), entry.as<int32_t>());
   profile_end(stream);
-  if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), d_ranks, sc, stream, name, result, result_dict);
+  if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), d_ranks, nullptr, sc, stream, name, result, result_dict);
   (void)hipStreamSynchronize(stream);   // (the temporaries go back to the pool, the stand-in dies)
   return st;
 }
@@ -571,7 +569,7 @@ hy_status hy_string_ranks_gather(const hy_string_dictionary* dict, const hy_colu
     if (segment.encoding != HY_ENC_UNENCODED) return fail(HY_ERR_INVALID, "%s: ranks are unencoded segments", name);
   HY_TRY(column_order_check(dict, name));
   if (ranks->rows >= (uint64_t{1} << 32)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu rows (32-bit row ids)", name, static_cast<unsigned long long>(ranks->rows));
-  if (!ranks->n_chunks) return empty_results(result, result_dict);
+  if (!ranks->n_chunks) return empty_string_results(result, result_dict);
   OutChunks out;
   out.n = ranks->rows;
   for (const hy_segment& segment : ranks->host_segments) out.sizes.push_back(segment.size);
@@ -607,7 +605,7 @@ hy_status hy_string_ranks_gather(const hy_string_dictionary* dict, const hy_colu
                          static_cast<uint32_t>(n_source_entries), entry.as<int32_t>());
   }
   profile_end(stream);
-  if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), d_ranks, sc, stream, name, result, result_dict);
+  if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), d_ranks, nullptr, sc, stream, name, result, result_dict);
   (void)hipStreamSynchronize(stream);
   return st;
 }

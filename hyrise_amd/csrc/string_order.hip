@@ -104,13 +104,15 @@ struct OrderArgs {
   const LikeBlock* blocks;
   const uint64_t* entry_offsets;    // [n_chunks + 1]
   uint32_t n_chunks;
+  const EntryWindow* windows;       // [entry_offsets[n_chunks]]: what of every entry is compared, or nullptr: all of it
+  uint64_t run_positions;           // 0: round 0 merges whole chunks (each one a sorted run); else single positions (windows that do not ascend)
 };
 
 __device__ __forceinline__ Entry element_entry(const OrderArgs& a, uint64_t element) {
   const uint32_t c = min(static_cast<uint32_t>(element >> 32), a.n_chunks - 1);
   const LikeChunk chunk = a.chunks[c];
   if (chunk.n_entries == 0) return Entry{nullptr, 0};
-  return entry_of(chunk, min(static_cast<uint32_t>(element), chunk.n_entries - 1), chunk_bytes(chunk));
+  return entry_of(chunk, min(static_cast<uint32_t>(element), chunk.n_entries - 1), chunk_bytes(chunk), a.windows ? a.windows + a.entry_offsets[c] : nullptr);
 }
 
 __global__ __launch_bounds__(ORDER_WG) void order_identity(OrderArgs a, uint64_t* elements) {
@@ -126,10 +128,18 @@ __global__ __launch_bounds__(ORDER_WG) void order_merge(OrderArgs a, const uint6
   if (v >= a.chunks[block.chunk].n_entries) return;
   // the pair of runs the position lies in: chunks [first, middle) and [middle, last)
   const uint64_t run = uint64_t{1} << round;
-  const uint64_t first = (block.chunk >> round & ~1u) * run;
-  const uint64_t middle = min(first + run, uint64_t{a.n_chunks}), last = min(first + 2 * run, uint64_t{a.n_chunks});
-  const uint64_t left_begin = a.entry_offsets[first], right_begin = a.entry_offsets[middle], right_end = a.entry_offsets[last];
   const uint64_t position = a.entry_offsets[block.chunk] + v;
+  uint64_t left_begin, right_begin, right_end;
+  if (a.run_positions) {   // runs of 2^round positions
+    const uint64_t total = a.entry_offsets[a.n_chunks];
+    left_begin = position >> (round + 1) << (round + 1);
+    right_begin = min(left_begin + run, total);
+    right_end = min(left_begin + 2 * run, total);
+  } else {
+    const uint64_t first = (block.chunk >> round & ~1u) * run;
+    const uint64_t middle = min(first + run, uint64_t{a.n_chunks}), last = min(first + 2 * run, uint64_t{a.n_chunks});
+    left_begin = a.entry_offsets[first], right_begin = a.entry_offsets[middle], right_end = a.entry_offsets[last];
+  }
   const uint64_t element = in[position];
   const Entry mine = element_entry(a, element);
   const bool in_left = position < right_begin;
@@ -208,7 +218,8 @@ size_t order_scratch_bytes(uint64_t total) {
 
 // Queues the whole sequence on `stream`: d_ranks[entry_offsets[c] + v] and *d_n_distinct (device memory, carved here: d_ranks may be a
 // block of the arena that the caller carved BEFORE this call).  total = entry_offsets[n_chunks] > 0.
-hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream) {
+hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream, const EntryWindow* d_windows,
+                              bool sorted_chunks) {
   HY_TRY(like_dictionary_tables(dict));
   const uint64_t total = dict->entry_offsets[dict->n_chunks];
   const uint32_t n_blocks = static_cast<uint32_t>(dict->blocks.size());
@@ -218,10 +229,12 @@ hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int
   uint32_t* tile_heads = carve<uint32_t>(sc, n_tiles);
   *d_n_distinct = carve<uint32_t>(sc, 1);
   if (!ping || !pong || !tile_heads || !*d_n_distinct) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-  OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks};
+  const bool by_position = d_windows && !sorted_chunks;
+  OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks, d_windows, by_position ? 1u : 0u};
+  const uint64_t n_runs = by_position ? total : dict->n_chunks;
   profile_begin(stream, HY_KERNEL_STRING_RANK);
   hipLaunchKernelGGL(order_identity, dim3(n_blocks), dim3(ORDER_WG), 0, stream, args, ping);
-  for (uint32_t round = 0; (uint64_t{1} << round) < dict->n_chunks; ++round) {
+  for (uint32_t round = 0; (uint64_t{1} << round) < n_runs; ++round) {
     hipLaunchKernelGGL(order_merge, dim3(n_blocks), dim3(ORDER_WG), 0, stream, args, ping, pong, round);
     std::swap(ping, pong);
   }

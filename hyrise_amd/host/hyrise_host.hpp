@@ -2847,9 +2847,16 @@ class AggregateHash : public AbstractReadOnlyOperator {   // operators/aggregate
     const auto input = left_input_table();
     std::vector<std::shared_ptr<DeviceColumn>> keep;
     std::vector<const hy_column*> groupby;
-    for (const auto id : _groupby) { keep.push_back(device_column(input, id, input->column_data_type(id) == DataType::String ? StringKeys::AggregateKeyNames : StringKeys::None)); groupby.push_back(keep.back()->handle); }
+    // A string GROUP BY column that an operator left in HBM (DeviceStringDictionarySegments: AggregateHash's and Projection's SUBSTR outputs)
+    // is grouped by its rank stand-in, made in HBM: key names would have to be made from its dictionaries on the host, which is a fetch.
+    const auto string_keys_of = [&](ColumnID id) {
+      if (input->column_data_type(id) != DataType::String) return StringKeys::None;
+      const bool resident = input->chunk_count() > 0 && dynamic_cast<const DeviceStringDictionarySegment*>(input->get_chunk(ChunkID{0})->get_segment(id).get()) != nullptr;
+      return resident && device_string_ranking() ? StringKeys::Ranks : StringKeys::AggregateKeyNames;
+    };
+    for (const auto id : _groupby) { keep.push_back(device_column(input, id, string_keys_of(id))); groupby.push_back(keep.back()->handle); }
     std::vector<hy_aggregate_spec> specs;
-    bool string_aggregates = false;   // MIN / MAX / ANY over a string column: their output segments are made by resident_output
+    bool string_aggregates = false;  // MIN / MAX / ANY over a string column: their output segments are made by resident_output
     for (const auto& aggregate : _aggregates) {
       hy_aggregate_spec spec{};
       spec.function = static_cast<uint32_t>(aggregate.function);
@@ -3370,7 +3377,9 @@ class StarJoinAggregate : public AbstractReadOnlyOperator {
 // ---- Projection (operators/projection.hpp, projection.cpp) ------------------------------------------------------------------------------
 // A minimal expression tree (expression/*.hpp): what hy_projection_expression evaluates.  A predicate between a STRING column and string
 // literals (binary, LIKE family, In / NotIn) becomes a column test, lowered through TableScan's own functions.
-enum class ExpressionType : uint8_t { Column, Value, Arithmetic, Predicate, IsNull, IsNotNull, And, Or, UnaryMinus, Case };
+// Substr (FunctionExpression(Substring), expression_evaluator.cpp:1566-1642) is a Projection's column of its own, not a node of a program:
+// SUBSTR(string column, literal, literal) becomes one hy_string_column_substr call; over anything else, or below another expression, a Fail.
+enum class ExpressionType : uint8_t { Column, Value, Arithmetic, Predicate, IsNull, IsNotNull, And, Or, UnaryMinus, Case, Substr };
 struct Expression {
   ExpressionType type;
   ColumnID column_id = 0;                      // Column
@@ -3378,6 +3387,7 @@ struct Expression {
   ArithmeticOperator arithmetic_operator = ArithmeticOperator::Addition;
   PredicateCondition condition = PredicateCondition::Equals;
   std::vector<std::shared_ptr<const Expression>> arguments;   // Predicate: left, right (In / NotIn: left, then the list's elements)
+  int32_t substr_start = 0, substr_length = 0;   // Substr: the two literals, Long ones cast to Int (expression_evaluator.cpp:1572-1578)
 };
 using ExpressionPtr = std::shared_ptr<const Expression>;
 inline ExpressionPtr column_(ColumnID column_id) { auto e = std::make_shared<Expression>(); e->type = ExpressionType::Column; e->column_id = column_id; return e; }
@@ -3397,6 +3407,21 @@ inline ExpressionPtr or_(ExpressionPtr l, ExpressionPtr r) { return expression_o
 inline ExpressionPtr is_null_(ExpressionPtr x) { return expression_of(ExpressionType::IsNull, {std::move(x)}); }
 inline ExpressionPtr is_not_null_(ExpressionPtr x) { return expression_of(ExpressionType::IsNotNull, {std::move(x)}); }
 inline ExpressionPtr unary_minus_(ExpressionPtr x) { return expression_of(ExpressionType::UnaryMinus, {std::move(x)}); }
+inline ExpressionPtr substr_(ExpressionPtr string_column, int32_t start, int32_t length) {
+  auto e = std::make_shared<Expression>(); e->type = ExpressionType::Substr; e->arguments = {std::move(string_column)}; e->substr_start = start; e->substr_length = length; return e;
+}
+// _evaluate_substring's loop body (expression_evaluator.cpp:1597-1638) in 64-bit arithmetic: what hy_string_column_substr computes per entry
+inline std::string substr_of(const std::string& string, int32_t start, int32_t length) {
+  if (length <= 0) return {};
+  const auto n = static_cast<int64_t>(string.size());
+  int64_t s = 0, l = length;
+  if (start < 0) s = int64_t{start} + n;
+  else if (start == 0) l -= 1;
+  else s = int64_t{start} - 1;
+  const auto e = std::min(s + l, n);
+  s = std::max<int64_t>(s, 0);
+  return s < n && e > s ? string.substr(static_cast<size_t>(s), static_cast<size_t>(e - s)) : std::string{};
+}
 inline ExpressionPtr case_(ExpressionPtr when, ExpressionPtr then, ExpressionPtr otherwise) { return expression_of(ExpressionType::Case, {std::move(when), std::move(then), std::move(otherwise)}); }
 
 class Projection : public AbstractReadOnlyOperator {
@@ -3415,6 +3440,7 @@ class Projection : public AbstractReadOnlyOperator {
     for (const auto& e : _expressions) any_computed = any_computed || e->type != ExpressionType::Column;
     // ---- evaluate (projection.cpp:129-190: one ExpressionEvaluator per chunk; here: one hy_projection_expression per computed column)
     std::vector<std::shared_ptr<const DeviceColumnOwner>> owners(_expressions.size());
+    std::vector<std::shared_ptr<const DeviceStringResult>> substrings(_expressions.size());   // SUBSTR made in HBM; without one, the host loop below
     TableColumnDefinitions definitions;
     for (size_t i = 0; i < _expressions.size(); ++i) {
       const auto& e = _expressions[i];
@@ -3426,6 +3452,12 @@ class Projection : public AbstractReadOnlyOperator {
         // live in it (:201-215 materialises it through the evaluator).  Numeric: the column itself as a one-node program -- hy_column_gather's
         // result with the input's chunk layout kept --, strings from the RowIDs on the host (below).
         if (any_computed && in_table->type() == TableType::References && type != DataType::String && chunk_count) owners[i] = evaluate(in_table, e);
+        continue;
+      }
+      if (e->type == ExpressionType::Substr) {
+        Assert(e->arguments.size() == 1 && is_string_column(*in_table, *e->arguments[0]), "Projection: SUBSTR takes a string column (SUBSTR of an expression: the stock evaluator)");
+        substrings[i] = substring_column(in_table, e->arguments[0]->column_id, e->substr_start, e->substr_length);
+        definitions.push_back({name, DataType::String, true});
         continue;
       }
       Assert(chunk_count > 0, "Projection: an expression over a table without chunks has no device column to read");
@@ -3446,6 +3478,19 @@ class Projection : public AbstractReadOnlyOperator {
       Segments segments;
       for (size_t i = 0; i < _expressions.size(); ++i) {
         if (owners[i]) { segments.push_back(resident_segment(definitions[i].data_type, owners[i], chunk_id, chunk_in->size())); continue; }
+        if (substrings[i]) { segments.push_back(std::make_shared<DeviceStringDictionarySegment>(substrings[i], chunk_id, chunk_in->size())); continue; }
+        if (_expressions[i]->type == ExpressionType::Substr) {   // the host path: the same formula over the values, row by row
+          const auto& e = *_expressions[i];
+          const auto argument = chunk_in->get_segment(e.arguments[0]->column_id);
+          std::vector<std::vector<AllTypeVariant>> cells;
+          for (ChunkOffset r = 0; r < chunk_in->size(); ++r) {
+            const auto value = (*argument)[r];
+            if (variant_is_null(value)) cells.push_back({value});
+            else cells.push_back({substr_of(std::get<std::string>(value), e.substr_start, e.substr_length)});
+          }
+          segments.push_back(make_value_segment<std::string>(cells, ColumnID{0}, true));
+          continue;
+        }
         const auto segment = chunk_in->get_segment(_expressions[i]->column_id);
         if (!any_computed || in_table->type() == TableType::Data) { segments.push_back(segment); continue; }   // shared
         std::vector<std::vector<AllTypeVariant>> cells;   // a string column behind a PosList, materialised from the RowIDs on the host
@@ -3499,6 +3544,7 @@ class Projection : public AbstractReadOnlyOperator {
         node.literal_type = static_cast<uint32_t>(data_type_from_all_type_variant(e.value));
         if (e.value.index() >= 1 && e.value.index() <= 4) node.literal = to_hy_value(e.value);
         break;
+      case ExpressionType::Substr: Fail("Projection: SUBSTR below another expression is not evaluated (string-valued nodes: the stock evaluator)");
       case ExpressionType::Predicate:
         if (is_string_column(*in_table, *e.arguments[0])) { lower_column_test(in_table, e, l); return; }
         if (e.condition == PredicateCondition::IsNull || e.condition == PredicateCondition::IsNotNull) {
@@ -3586,6 +3632,22 @@ class Projection : public AbstractReadOnlyOperator {
     node.kind = HY_PROJ_COLUMN_TEST;
     node.index = l.program.n_tests++;
     push(l, node);
+  }
+
+  // SUBSTR(column, start, length) made in HBM: one hy_string_column_substr over the input's column -- a data column, or a reference column with
+  // its PosLists where they are.  nullptr: the switch is off, the column is not wholly dictionary-encoded, or the library refused it.
+  static std::shared_ptr<const DeviceStringResult> substring_column(const std::shared_ptr<const Table>& in_table, ColumnID column_id, int32_t start, int32_t length) {
+    std::shared_ptr<const Table> data_table;
+    ColumnID data_column_id = column_id;
+    if (!device_string_results() || !string_dictionary_column(in_table, column_id, data_table, data_column_id)) return nullptr;
+    const auto column = device_column(in_table, column_id);
+    const auto dictionary = device_string_dictionary(data_table, data_column_id);
+    hy_column* made = nullptr;
+    hy_string_dictionary* made_dictionary = nullptr;
+    const auto status = hy_string_column_substr(column->handle, dictionary->handle, start, length, &made, &made_dictionary);
+    if (status == HY_ERR_UNSUPPORTED) return nullptr;
+    check_status(status);
+    return std::make_shared<const DeviceStringResult>(made, made_dictionary);
   }
 
   std::shared_ptr<const DeviceColumnOwner> evaluate(const std::shared_ptr<const Table>& in_table, const ExpressionPtr& e) const {

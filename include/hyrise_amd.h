@@ -591,6 +591,26 @@ hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictio
 hy_status hy_string_column_gather(const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, uint32_t chunk_rows,
                                   hy_column** result, hy_string_dictionary** result_dict);
 hy_status hy_string_ranks_gather(const hy_string_dictionary* dict, const hy_column* ranks, hy_column** result, hy_string_dictionary** result_dict);
+/* hy_string_column_substr   SUBSTR(column, start, length) as a new string column: the same pair as above, in `column`'s OWN chunk layout --
+ *   row r of chunk c is SUBSTR of row r of chunk c, a NULL row stays NULL -- and *result_dict holds per output chunk the distinct RESULT
+ *   strings (equal substrings of different source entries or source chunks are one entry, "" is an entry like any other).  `column` and
+ *   `dict` are what hy_string_column_gather takes (a data column of string dictionary segments in either layout, or a reference column over
+ *   one with PosLists in either memory space); start / length are the two literal arguments as int32 (the evaluator casts Long literals to
+ *   Int first, expression_evaluator.cpp:1572-1578: the caller's job).  Semantics are the reference's _evaluate_substring
+ *   (expression_evaluator.cpp:1597-1638) on bytes, with n the entry's size:
+ *     length <= 0: "" (not NULL).  start < 0: s = start + n.  start == 0: s = 0 and length loses 1.  start > 0: s = start - 1.
+ *     e = min(s + length, n), s = max(s, 0); the result is bytes [s, e) when s < n and e > s, else "".
+ *   evaluated in 64-bit arithmetic (the reference's own int32 sum overflows for arguments near INT32_MAX; every pair of int32 arguments is
+ *   answered here).  SUBSTR('HELLO', 0, 2) = 'H', (-1, 2) = 'O', (-8, 1) = '', (-8, 5) = 'HE'.  A multi-byte UTF-8 sequence may be cut.
+ *   On the device a substring is a window (byte begin, byte length) into the chars that are in HBM already: one launch makes a window per
+ *   source entry, the windowed entries are ranked by hy_string_dictionary_order's launches, and the rest is the gather's back end reading
+ *   through the windows; no intermediate string is written.  A column of zero chunks: HY_OK, a column and a dictionary of zero chunks, no
+ *   launch.  The refusals mirror hy_string_column_gather's: HY_ERR_INVALID for a null argument, a column that is no string column, a
+ *   dictionary that disagrees with the data column or lives on another device; HY_ERR_UNSUPPORTED for unencoded or LZ4 string segments,
+ *   E >= 2^31 source entries, 2^32 rows or more, an output chunk whose chars would take 2^32 bytes or more (the only refusal behind a
+ *   launch).  On every error both out pointers are NULL and nothing stays allocated. */
+hy_status hy_string_column_substr(const hy_column* column, const hy_string_dictionary* dict, int32_t start, int32_t length, hy_column** result,
+                                  hy_string_dictionary** result_dict);
 /* An offsets-layout chunk of a dictionary read back, whether the library owns its buffers (an upload, a gather's result) or the caller:
  * chunk_size gives n_entries and the bytes of its chars (offsets[n_entries]); read_chunk copies the n_entries + 1 offsets as they are and the
  * chars' bytes [0, offsets[n_entries]) to host memory (chars may be NULL when there are none).  A fixed-slot chunk with entries:
