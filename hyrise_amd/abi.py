@@ -126,7 +126,7 @@ NLJ_MAX_TEMPORARY_BYTES = 1 << 31      # HY_NLJ_MAX_TEMPORARY_BYTES
 # hy_set_option (include/hyrise_amd.h HY_OPT_*): equivalent paths / launch shapes; every setting gives the same results
 (OPT_ALLOW_ANY_ARCH, OPT_JOIN_RANK_TABLE, OPT_JOIN_HINT, OPT_JOIN_BREAK_HINT, OPT_JOIN_PKFK, OPT_JOIN_LDS_BUILD, OPT_JOIN_LDS_BUILD_TILES, OPT_JOIN_FILL_WGS_PER_CU,
  OPT_JOIN_HAND_OVER_RANKS, OPT_AGG_PARTITION_BITS, OPT_AGG_SPILL_SHIFT, OPT_AGG_SMALL_DOMAIN, OPT_FUSED_SMALL_DOMAIN, OPT_SCAN_TWO_COLUMNS, OPT_STAR_FUSED_PROBE, OPT_STAR_FUSED_FINISH,
- OPT_LDS_ORDERED_ATOMICS, OPT_PRODUCT_NONTEMPORAL, OPT_JOIN_COMPACT_STAGE) = range(19)
+ OPT_LDS_ORDERED_ATOMICS, OPT_PRODUCT_NONTEMPORAL, OPT_JOIN_COMPACT_STAGE, OPT_STRING_SPARSE_GATHER) = range(20)
 KERNEL_OTHER, KERNEL_SCAN, KERNEL_JOIN_PROBE, KERNEL_JOIN_COUNT, KERNEL_JOIN_BUILD, KERNEL_AGGREGATE, KERNEL_PROJECTION, KERNEL_LIKE, KERNEL_STRING_RANK = range(9)   # hy_profile_read_kernel
 ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV, ARITH_MOD = range(5)
 
@@ -287,6 +287,8 @@ SYMBOLS = [
     ("hy_string_column_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("hy_string_ranks_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("hy_string_column_substr", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("hy_temporary_pool_stats", C.c_int32, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hy_string_column_materialize", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("hy_string_dictionary_chunk_size", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     ("hy_string_dictionary_read_chunk", C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("hy_projection_arithmetic", C.c_int32, [C.c_uint32, C.POINTER(Operand), C.POINTER(Operand), C.POINTER(C.c_void_p)]),
@@ -396,7 +398,7 @@ _SWITCHES = {
     "HY_JOIN_FILL_WGS_PER_CU": (OPT_JOIN_FILL_WGS_PER_CU, None), "HY_JOIN_HAND_OVER_RANKS": (OPT_JOIN_HAND_OVER_RANKS, None),
     "HY_AGG_PARTITION_BITS": (OPT_AGG_PARTITION_BITS, None), "HY_AGG_SPILL_SHIFT": (OPT_AGG_SPILL_SHIFT, None), "HY_AGG_NO_SMALL_DOMAIN": (OPT_AGG_SMALL_DOMAIN, 0),
     "HY_FUSED_NO_SMALL_DOMAIN": (OPT_FUSED_SMALL_DOMAIN, 0), "HY_LDS_NO_ORDERED_ATOMICS": (OPT_LDS_ORDERED_ATOMICS, 0),
-    "HY_OPT_JOIN_COMPACT_STAGE": (OPT_JOIN_COMPACT_STAGE, None)
+    "HY_OPT_JOIN_COMPACT_STAGE": (OPT_JOIN_COMPACT_STAGE, None), "HY_OPT_STRING_SPARSE_GATHER": (OPT_STRING_SPARSE_GATHER, None)
 }
 
 

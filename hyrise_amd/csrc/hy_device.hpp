@@ -265,10 +265,38 @@ struct OutChunks {
 };
 // what gather_entries, the ranking and the front end in front of it carve from the scratch arena (`inverse`: 4 more bytes per source entry)
 size_t gather_scratch_bytes(uint64_t n_source_entries, uint64_t n, uint64_t n_chunks, bool inverse);
+// The sparse route (HY_OPT_STRING_SPARSE_GATHER, string_gather.hip): the column read at the rows asked for, the entries they reference -- the
+// SUBSET, U <= min(n, E) of them in ascending entry order -- as a table of (address, length) that the ranking and the back end read instead
+// of the dictionary, and ranks per subset index.  A row's entry is then its index into the table.
+struct SubsetEntry {   // the bytes of a referenced entry, seen through its window if there is one
+  const uint8_t* bytes;
+  uint32_t length;
+  uint32_t reserved;
+};
+struct SubstrArguments {
+  int32_t start, length;
+};
+struct SparseSubset {
+  const SubsetEntry* table = nullptr;   // [n]
+  const int32_t* ranks = nullptr;       // [n]: equal strings (of different source chunks, or equal windows) have one rank
+  uint32_t n = 0;                       // U
+};
+bool string_sparse_route(uint64_t n, uint64_t column_rows, uint64_t n_source_entries);   // which route n rows out of such a column take
+size_t sparse_gather_scratch_bytes(uint64_t n_source_entries, uint64_t n_source_chunks, uint64_t n, uint64_t n_chunks);
+// d_entry[i] (n of them): the subset index of the entry that row positions[i] of `column` holds -- positions == nullptr: row i of the column
+// itself -- or -1 (a NULL RowID, one outside the table, a NULL row); *subset: the table and its ranks, carved from `sc`
+// (sparse_gather_scratch_bytes reserved by the caller).  `substr`: the window every entry is seen through, or nullptr.  One 4-byte copy to the host (U).
+hy_status sparse_entries(const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, const SubstrArguments* substr, Scratch& sc,
+                         int32_t* d_entry, hipStream_t stream, const char* name, SparseSubset* subset);
+// string_order.hip: the order of a table of `total` > 0 entries whose chunk runs [d_run_offsets[c], d_run_offsets[c + 1]) each ascend
+// (by_position: they need not -- the merge starts from single positions); d_ranks[i] for table entry i.  Takes order_scratch_bytes(total).
+hy_status table_order_launch(const SubsetEntry* d_table, const uint64_t* d_run_offsets, uint32_t n_chunks, uint64_t total, bool by_position, Scratch& sc, int32_t* d_ranks,
+                             hipStream_t stream);
 // d_entry: per output row the global entry index into `dict`, or -1; d_ranks: the order of the (windowed) entries, queued on `stream` already
 // (nullptr for a dictionary without entries); d_windows: what of every entry the output holds, or nullptr: all of it.
+// With `subset` (the sparse route) d_entry holds subset indices, d_ranks is indexed by them and the bytes come from the subset's table: d_windows is nullptr.
 hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out, const int32_t* d_entry, const int32_t* d_ranks, const EntryWindow* d_windows, Scratch& sc,
-                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict);
+                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict, const SparseSubset* subset = nullptr);
 hy_status empty_string_results(hy_column** result, hy_string_dictionary** result_dict);   // a column and a dictionary of zero chunks
 // The int32 stand-in of a string column over a table of E int32_t in device memory (entry v of data chunk c reads d_table[entry_offsets[c] + v]):
 // the caller's attribute vectors and PosLists, shared.  A reference column's stand-in owns its data stand-in; the table stays the caller's.

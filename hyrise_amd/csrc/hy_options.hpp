@@ -35,6 +35,13 @@ constexpr int64_t FIXED_AGG_SPLIT = 0;              // workgroups per partition:
 constexpr int64_t FIXED_AGG_JOINT_HISTOGRAM = 1;    // two 1-byte measure columns are counted in one pair histogram
 constexpr int64_t FIXED_FUSED_SHARED_PREFIX = 1;    // fused inputs that begin with an earlier input continue on its stack
 
+// HY_OPT_STRING_SPARSE_GATHER = 1: n rows out of a string column of `rows` rows and E dictionary entries take the sparse route (string_gather.hip)
+// when n <= (rows + E) / STRING_SPARSE_DIVISOR -- rows + E is the work the dense route does whatever n is.  Measured in
+// profiles/string_gather_sparse.txt (tools/string_gather_sparse_timing.py): the sparse route took 0.04 - 0.79 of the
+// dense route's time at every n measured in both shapes; the largest n / (rows + E) that BOTH shapes were measured at is 1.7e-2 (l_shipdate,
+// n = 2^20: 0.46; c_name at 2.2e-2: 0.37), and 1 / 64 lies below it.  Nothing was measured beyond: the rule stops where the measurements do.
+constexpr int64_t STRING_SPARSE_DIVISOR = 64;
+
 }  // namespace hy
 
 #ifdef HY_DEBUG_SWITCHES

@@ -35,6 +35,7 @@ struct OptionDefaults {
     set(HY_OPT_STAR_FUSED_FINISH, 1);
     set(HY_OPT_LDS_ORDERED_ATOMICS, 1);
     set(HY_OPT_JOIN_COMPACT_STAGE, 1);
+    set(HY_OPT_STRING_SPARSE_GATHER, 1);
   }
 };
 OptionDefaults g_option_defaults;   // (static initialisation: before any entry point can run)
@@ -425,6 +426,17 @@ hy_status hy_profile_read_kernel(uint32_t kernel, float* total_milliseconds, uin
   if (!total_milliseconds || !launches) return fail(HY_ERR_INVALID, "hy_profile_read_kernel: null argument");
   if (kernel >= HY_KERNEL_KINDS) return fail(HY_ERR_INVALID, "hy_profile_read_kernel: unknown kernel kind %u", kernel);
   return profile_sum(kernel, total_milliseconds, launches);
+}
+
+hy_status hy_temporary_pool_stats(uint64_t* held_bytes, uint64_t* largest_block_bytes) {
+  uint64_t held = 0, largest = 0;
+  for (const auto& block : t_pool.free_blocks) {
+    held += block.first;
+    largest = std::max<uint64_t>(largest, block.first);
+  }
+  if (held_bytes) *held_bytes = held;
+  if (largest_block_bytes) *largest_block_bytes = largest;
+  return HY_OK;
 }
 
 // Releases what the CALLING thread holds between calls: its scratch arena, its pool of temporary blocks, its pinned

@@ -14,6 +14,17 @@ struct Entry {
   uint32_t length;
 };
 
+// the last i in [0, n) with table[i] <= x, for an ascending table whose first element is <= x (equal elements: the last of them)
+template <typename T>
+__device__ __forceinline__ uint32_t last_at_or_below(const T* table, uint32_t n, uint64_t x) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (table[mid] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // bytes in the chunk's chars: what the entries may be read from
 __device__ __forceinline__ uint32_t chunk_bytes(const LikeChunk& chunk) {
   if (chunk.n_entries == 0) return 0;
@@ -55,6 +66,22 @@ __device__ __forceinline__ Entry entry_of(const LikeChunk& chunk, uint32_t v, ui
   const uint8_t* entry = chunk.offsets ? chars + min(chunk.offsets[v], end) : chars + size_t{v} * chunk.string_length;
   return Entry{entry + window.begin, window.length};
 }
+
+// SUBSTR(entry of n bytes, start, length) as a window: the reference's _evaluate_substring (expression_evaluator.cpp:1597-1638) in 64-bit arithmetic
+__device__ __forceinline__ EntryWindow substr_window(uint32_t n, int32_t start, int32_t length) {
+  if (length <= 0) return EntryWindow{0, 0};
+  int64_t s, l = length;
+  if (start < 0) s = int64_t{start} + n;
+  else if (start == 0) { s = 0; l -= 1; }
+  else s = int64_t{start} - 1;
+  const int64_t e = min(s + l, int64_t{n});
+  s = max(s, int64_t{0});
+  if (s < int64_t{n} && e > s) return EntryWindow{static_cast<uint32_t>(s), static_cast<uint32_t>(e - s)};
+  return EntryWindow{0, 0};
+}
+
+// An entry of the sparse route's table (hy_device.hpp: SubsetEntry), as the comparisons and the copy read it
+__device__ __forceinline__ Entry entry_of(const SubsetEntry& e) { return Entry{e.bytes, e.length}; }
 
 __device__ __forceinline__ uint32_t load_word(const uint8_t* p) {   // four bytes at any address, first byte most significant
   uint32_t w;

@@ -27,6 +27,10 @@
 // 256 rows 12, per output chunk 20.  Pool blocks: the word sort's 16 bytes per row; for the RowID front end the stand-in's table (4 per
 // source entry) and its export (5 per SOURCE row).  Results: the attribute vectors and null-free segments in one pooled arena owned by the
 // column (hy_column_gather's layout); offsets and chars in one allocation owned by the dictionary.
+// The sparse route (HY_OPT_STRING_SPARSE_GATHER) is for few rows out of a large column: the column is read AT the rows
+// (sparse_mark: PosLists and attribute vectors of any width or packing in place, no stand-in, no export), the entries they reference are
+// marked in a bitmap over E and compacted into a table of (address, length), only those are ranked (table_order_launch), and the back end
+// reads entries by table index.  Its temporaries follow n and the subset, plus one bit per source entry (sparse_gather_scratch_bytes).
 #include "hy_device.hpp"
 #include "sort_words.hpp"
 #include "string_entries.hpp"
@@ -59,17 +63,6 @@ struct ChunkTotals {   // what crosses to the host, per output chunk
   uint32_t n_entries;
   uint32_t reserved;
 };
-
-// the last i in [0, n) with table[i] <= x, for an ascending table whose first element is <= x (equal elements: the last of them)
-template <typename T>
-__device__ __forceinline__ uint32_t last_at_or_below(const T* table, uint32_t n, uint64_t x) {
-  uint32_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (table[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ uint32_t chunk_of(const OutLayout& l, uint32_t row) {
   return l.row_base ? last_at_or_below(l.row_base, l.n_chunks, row) : row / l.chunk_rows;
@@ -211,12 +204,17 @@ __global__ __launch_bounds__(WG) void value_ids(OutLayout l, const int32_t* entr
 // ---- step 4: where every output entry's bytes are, and how many ---------------------------------------------------------------------------------
 // (windows: what of every source entry the output holds -- SUBSTR -- or nullptr: all of it)
 __global__ __launch_bounds__(WG) void unique_lengths(const LikeChunk* chunks, const uint64_t* entry_offsets, uint32_t n_source_chunks, const EntryWindow* windows,
-                                                     const int32_t* unique_entry, const uint32_t* n_unique, const uint8_t** source, uint64_t* local_bytes, uint64_t* tile_bytes) {
+                                                     const SubsetEntry* table, uint32_t n_table, const int32_t* unique_entry, const uint32_t* n_unique, const uint8_t** source,
+                                                     uint64_t* local_bytes, uint64_t* tile_bytes) {
   __shared__ uint64_t s_sums[WG];
   const uint64_t u = uint64_t{blockIdx.x} * WG + threadIdx.x;
   const bool mine = u < *n_unique;
   uint64_t length = 0;
-  if (mine) {
+  if (mine && table) {   // the sparse route: the entry is an index into the subset's table, the window applied already
+    const SubsetEntry found = table[min(static_cast<uint32_t>(unique_entry[u]), n_table - 1)];
+    source[u] = found.bytes;
+    length = found.length;
+  } else if (mine) {
     const uint32_t e = static_cast<uint32_t>(unique_entry[u]);
     const uint32_t c = last_at_or_below(entry_offsets, n_source_chunks, e);
     const LikeChunk chunk = chunks[c];
@@ -326,25 +324,235 @@ __global__ __launch_bounds__(WG) void copy_entry_bytes(const uint8_t* const* sou
   *reinterpret_cast<u32x4_t*>(chars + at) = u32x4_t{static_cast<uint32_t>(low), static_cast<uint32_t>(low >> 32), static_cast<uint32_t>(high), static_cast<uint32_t>(high >> 32)};
 }
 
+// ---- the sparse route: the column read AT the rows, the entries they reference as a table ---------------------------------------------------
+// Which entries the rows reference is a bitmap over the E entries (bit e of word e / 64), set with one vector atomicOr per non-NULL row: the
+// result does not depend on any order, an entry's subset index is a popcount (bits below it), and the entries come out ascending -- chunk
+// by chunk, inside a chunk in dictionary order -- without a sort.
+struct RowSource {
+  const DevSegment* segments;       // the column's: dictionary segments, or reference segments over them
+  const uint64_t* row_base;         // [n_chunks + 1]
+  const uint64_t* entry_offsets;    // [n_data_chunks + 1], the data column's dictionaries
+  uint32_t n_chunks;
+  uint32_t n_data_chunks;
+};
+
+// element `row` of an attribute vector of 1, 2 or 4 bytes at any byte address, or of a bit-packed one (little-endian stream of 64-bit words)
+__device__ __forceinline__ uint32_t value_id_at(const DevSegment& s, uint32_t row) {
+  if (seg_is_packed(s)) {
+    const uint64_t* words = static_cast<const uint64_t*>(s.data);
+    const uint32_t bits = seg_bits(s);
+    const uint64_t at = uint64_t{row} * bits;
+    const uint32_t shift = static_cast<uint32_t>(at & 63);
+    uint64_t value = words[at >> 6] >> shift;
+    if (shift + bits > 64) value |= words[(at >> 6) + 1] << (64 - shift);
+    return static_cast<uint32_t>(value & ((1ull << bits) - 1));
+  }
+  const uint8_t* data = static_cast<const uint8_t*>(s.data);
+  if (s.width == 1) return data[row];
+  if (s.width == 2) {
+    uint16_t v;
+    __builtin_memcpy(&v, data + 2 * size_t{row}, 2);
+    return v;
+  }
+  uint32_t v;
+  __builtin_memcpy(&v, data + 4 * size_t{row}, 4);
+  return v;
+}
+
+// The global entry index of row (chunk_id, chunk_offset) of the column, or -1: a NULL RowID, a RowID outside the table, a NULL row
+__device__ __forceinline__ int32_t entry_at_row(const RowSource& src, uint32_t chunk_id, uint32_t chunk_offset) {
+  if (chunk_offset == 0xFFFFFFFFu || chunk_id >= src.n_chunks) return -1;
+  const DevSegment* s = src.segments + chunk_id;
+  if (chunk_offset >= s->size) return -1;
+  if (s->encoding == HY_ENC_REFERENCE) {
+    hy_row_id r{s->ref_chunk_id, chunk_offset};   // (no list: an EntireChunkPosList)
+    if (s->data) r = static_cast<const hy_row_id*>(s->data)[chunk_offset];
+    if (r.chunk_offset == 0xFFFFFFFFu || r.chunk_id >= src.n_data_chunks) return -1;
+    chunk_id = r.chunk_id;
+    chunk_offset = r.chunk_offset;
+    s = s->ref + chunk_id;
+    if (chunk_offset >= s->size) return -1;
+  }
+  if (s->encoding != HY_ENC_DICTIONARY || chunk_id >= src.n_data_chunks) return -1;
+  const uint32_t value_id = value_id_at(*s, chunk_offset);
+  const uint64_t first = src.entry_offsets[chunk_id];
+  if (value_id >= s->aux_size || value_id >= src.entry_offsets[chunk_id + 1] - first) return -1;   // (the NULL value id, or one no entry has)
+  return static_cast<int32_t>(first + value_id);
+}
+
+// entry[i] = the global entry index of row positions[i] -- positions == nullptr: of row i of the column -- and its bit in the bitmap
+__global__ __launch_bounds__(WG) void sparse_mark(RowSource src, const hy_row_id* positions, uint32_t n, int32_t* entry, unsigned long long* bitmap) {
+  for (uint32_t i = blockIdx.x * WG + threadIdx.x; i < n; i += gridDim.x * WG) {
+    hy_row_id p;
+    if (positions) {
+      p = positions[i];
+    } else {
+      p.chunk_id = last_at_or_below(src.row_base, src.n_chunks, i);
+      p.chunk_offset = static_cast<uint32_t>(i - src.row_base[p.chunk_id]);
+    }
+    const int32_t e = entry_at_row(src, p.chunk_id, p.chunk_offset);
+    entry[i] = e;
+    if (e >= 0) atomicOr(bitmap + (static_cast<uint32_t>(e) >> 6), 1ull << (e & 63));
+  }
+}
+
+// local[w] = set bits in the words of w's workgroup up to and including w; tile_bits[workgroup] = its bits
+__global__ __launch_bounds__(WG) void sparse_count(const unsigned long long* bitmap, uint32_t n_words, uint32_t* local, uint32_t* tile_bits) {
+  __shared__ uint32_t s_sums[WG];
+  const uint32_t w = blockIdx.x * WG + threadIdx.x;
+  s_sums[threadIdx.x] = w < n_words ? static_cast<uint32_t>(__popcll(bitmap[w])) : 0;
+  __syncthreads();
+  for (uint32_t step = 1; step < WG; step <<= 1) {   // Hillis-Steele, inclusive
+    const uint32_t add = threadIdx.x >= step ? s_sums[threadIdx.x - step] : 0;
+    __syncthreads();
+    s_sums[threadIdx.x] += add;
+    __syncthreads();
+  }
+  if (w < n_words) local[w] = s_sums[threadIdx.x];
+  if (threadIdx.x == WG - 1) tile_bits[blockIdx.x] = s_sums[WG - 1];
+}
+
+// set bits below bit e of the bitmap: the subset index of entry e, if it is in the subset (e <= E: word e / 64 exists, the bitmap has E / 64 + 1)
+__device__ __forceinline__ uint32_t bits_below(const unsigned long long* bitmap, const uint32_t* local, const uint32_t* tile_bits, uint64_t e) {
+  return sum_before(local, tile_bits, e >> 6) + static_cast<uint32_t>(__popcll(bitmap[e >> 6] & ((1ull << (e & 63)) - 1)));
+}
+
+// The subset's table.  A lane loads one bitmap word, the wave then takes its non-zero words one after the other, lane l the word's bit l:
+// the entry's chunk (binary search over entry_offsets), its bytes and length, through the window if there is one.
+__global__ __launch_bounds__(WG) void sparse_table(const unsigned long long* bitmap, uint32_t n_words, const uint32_t* local, const uint32_t* tile_bits, const LikeChunk* chunks,
+                                                   const uint64_t* entry_offsets, uint32_t n_source_chunks, bool windowed, SubstrArguments substr, uint32_t n_subset, SubsetEntry* table) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n_waves = gridDim.x * (WG / 64);
+  for (uint64_t base = (uint64_t{blockIdx.x} * (WG / 64) + (threadIdx.x >> 6)) * 64; base < n_words; base += uint64_t{n_waves} * 64) {   // (whole waves)
+    const uint64_t w = base + lane;
+    const unsigned long long mine = w < n_words ? bitmap[w] : 0ull;
+    const uint32_t before_mine = mine ? sum_before(local, tile_bits, w) : 0;
+    for (uint64_t pending = __ballot(mine != 0); pending; pending &= pending - 1) {
+      const int from = __ffsll(static_cast<unsigned long long>(pending)) - 1;
+      const unsigned long long word = __shfl(mine, from);
+      const uint32_t before = __shfl(before_mine, from);
+      if (!((word >> lane) & 1)) continue;
+      const uint32_t index = before + static_cast<uint32_t>(__popcll(word & ((1ull << lane) - 1)));
+      if (index >= n_subset) continue;   // (cannot happen: the counts are the bitmap's)
+      const uint64_t e = (base + from) * 64 + lane;
+      const uint32_t c = last_at_or_below(entry_offsets, n_source_chunks, e);
+      const LikeChunk chunk = chunks[c];
+      Entry found = entry_of(chunk, min(static_cast<uint32_t>(e - entry_offsets[c]), chunk.n_entries - 1), chunk_bytes(chunk));
+      if (windowed) {
+        const EntryWindow window = substr_window(found.length, substr.start, substr.length);
+        found = Entry{found.bytes + window.begin, window.length};
+      }
+      table[index] = SubsetEntry{found.bytes, found.length, 0};
+    }
+  }
+}
+
+// entry[i]: global entry index -> subset index; run_offsets[c] = subset entries of the source chunks before c, c <= n_source_chunks
+__global__ __launch_bounds__(WG) void sparse_indices(const unsigned long long* bitmap, const uint32_t* local, const uint32_t* tile_bits, const uint64_t* entry_offsets,
+                                                     uint32_t n_source_chunks, uint32_t n, int32_t* entry, uint64_t* run_offsets) {
+  for (uint32_t i = blockIdx.x * WG + threadIdx.x; i < n || i <= n_source_chunks; i += gridDim.x * WG) {
+    if (i < n && entry[i] >= 0) entry[i] = static_cast<int32_t>(bits_below(bitmap, local, tile_bits, static_cast<uint32_t>(entry[i])));
+    if (i <= n_source_chunks) run_offsets[i] = bits_below(bitmap, local, tile_bits, entry_offsets[i]);
+  }
+}
+
 uint32_t tiles_of(uint64_t items) { return static_cast<uint32_t>((items + WG - 1) / WG); }
+
+// what gather_entries itself carves
+size_t back_end_scratch_bytes(uint64_t n, uint64_t n_chunks) {
+  const uint64_t tiles = tiles_of(n);
+  return 3 * align_up(4 * n + 16, 256) + 2 * align_up(8 * n + 16, 256) + align_up(4 * tiles, 256) + align_up(8 * tiles, 256) + align_up(4 * (n_chunks + 1), 256) +
+         align_up(sizeof(ChunkTotals) * n_chunks, 256) + 2 * align_up(8 * (n_chunks + 1), 256) + 16 * 256 + 4096;
+}
 
 }  // namespace
 
 // What gather_entries and the front ends in front of it carve from the scratch arena
 size_t gather_scratch_bytes(uint64_t n_source_entries, uint64_t n, uint64_t n_chunks, bool inverse) {
-  const uint64_t tiles = tiles_of(n);
-  return (n_source_entries ? order_scratch_bytes(n_source_entries) : 0) + (inverse ? 2 : 1) * align_up(4 * n_source_entries + 16, 256) + 3 * align_up(4 * n + 16, 256) +
-         2 * align_up(8 * n + 16, 256) + align_up(4 * tiles, 256) + align_up(8 * tiles, 256) + align_up(4 * (n_chunks + 1), 256) + align_up(sizeof(ChunkTotals) * n_chunks, 256) +
-         2 * align_up(8 * (n_chunks + 1), 256) + 16 * 256 + 4096;
+  return (n_source_entries ? order_scratch_bytes(n_source_entries) : 0) + (inverse ? 2 : 1) * align_up(4 * n_source_entries + 16, 256) + back_end_scratch_bytes(n, n_chunks);
+}
+
+// Which route n rows out of a column of `column_rows` rows and E entries take: column_rows + E is what the dense route reads whatever n is
+bool string_sparse_route(uint64_t n, uint64_t column_rows, uint64_t n_source_entries) {
+  const int64_t mode = option(HY_OPT_STRING_SPARSE_GATHER);
+  if (mode == 2) return true;
+  if (mode != 1 || STRING_SPARSE_DIVISOR <= 0) return false;
+  return n <= (column_rows + n_source_entries) / static_cast<uint64_t>(STRING_SPARSE_DIVISOR);
+}
+
+// What sparse_entries and gather_entries behind it carve: the bitmap (one bit per source entry) with 4 bytes of counts per 64 entries, per
+// subset entry (U <= min(n, E)) 16 of table + 4 of ranks + 16 of ranking, per source chunk 8 -- nothing else that grows with E or the column's rows
+size_t sparse_gather_scratch_bytes(uint64_t n_source_entries, uint64_t n_source_chunks, uint64_t n, uint64_t n_chunks) {
+  const uint64_t n_words = n_source_entries / 64 + 1, n_subset = std::min(n, n_source_entries);
+  return align_up(8 * n_words, 256) + align_up(4 * n_words, 256) + align_up(4 * tiles_of(n_words), 256) + 256 + align_up(8 * (n_source_chunks + 1), 256) +
+         align_up(sizeof(SubsetEntry) * n_subset + 16, 256) + align_up(4 * n_subset + 16, 256) + (n_subset ? order_scratch_bytes(n_subset) : 0) + back_end_scratch_bytes(n, n_chunks) + 4096;
+}
+
+hy_status sparse_entries(const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, const SubstrArguments* substr, Scratch& sc,
+                         int32_t* d_entry, hipStream_t stream, const char* name, SparseSubset* subset) {
+  *subset = SparseSubset{};
+  const uint64_t n_source_entries = dict->entry_offsets[dict->n_chunks];
+  const uint32_t n_words = static_cast<uint32_t>(n_source_entries / 64 + 1), n_word_tiles = tiles_of(n_words);
+  unsigned long long* bitmap = carve<unsigned long long>(sc, n_words);
+  uint32_t* local = carve<uint32_t>(sc, n_words);
+  uint32_t* tile_bits = carve<uint32_t>(sc, n_word_tiles);
+  uint32_t* d_n_subset = carve<uint32_t>(sc, 1);
+  uint64_t* run_offsets = carve<uint64_t>(sc, size_t{dict->n_chunks} + 1);
+  if (!bitmap || !local || !tile_bits || !d_n_subset || !run_offsets) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  auto check = [&](hipError_t err) { return err == hipSuccess ? HY_OK : fail(HY_ERR_DEVICE, "%s: %s", name, hipGetErrorString(err)); };
+  const hy_column* data_column = column->is_reference ? column->ref : column;
+  const RowSource src{column->d_segments, column->d_row_base, dict->d_entry_offsets, column->n_chunks, data_column ? data_column->n_chunks : 0};
+  profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the front end: a bracket of its own)
+  hy_status st = check(hipMemsetAsync(bitmap, 0, 8 * size_t{n_words}, stream));
+  uint32_t n_subset = 0;
+  if (st == HY_OK) {
+    hipLaunchKernelGGL(sparse_mark, dim3(grid_for(n)), dim3(WG), 0, stream, src, positions, static_cast<uint32_t>(n), d_entry, bitmap);
+    hipLaunchKernelGGL(sparse_count, dim3(n_word_tiles), dim3(WG), 0, stream, bitmap, n_words, local, tile_bits);
+    hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_bits, n_word_tiles, d_n_subset);
+    st = check(hipGetLastError());
+    if (st == HY_OK) st = check(hipMemcpyAsync(&n_subset, d_n_subset, 4, hipMemcpyDeviceToHost, stream));
+    if (st == HY_OK) st = check(hipStreamSynchronize(stream));
+  }
+  if (st == HY_OK && n_subset > std::min(n, n_source_entries)) st = fail(HY_ERR_DEVICE, "%s: %u entries marked by %llu rows", name, n_subset, static_cast<unsigned long long>(n));
+  SubsetEntry* table = nullptr;
+  int32_t* ranks = nullptr;
+  if (st == HY_OK && n_subset) {   // (none: every row is NULL, every entry -1 already)
+    table = carve<SubsetEntry>(sc, n_subset);
+    ranks = carve<int32_t>(sc, n_subset);
+    if (!table || !ranks) st = fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  }
+  if (st == HY_OK && n_subset) {
+    const SubstrArguments window = substr ? *substr : SubstrArguments{0, 0};
+    hipLaunchKernelGGL(sparse_table, dim3(std::min<uint32_t>(tiles_of(n_words), 4096)), dim3(WG), 0, stream, bitmap, n_words, local, tile_bits, dict->d_chunks, dict->d_entry_offsets,
+                       dict->n_chunks, substr != nullptr, window, n_subset, table);
+    hipLaunchKernelGGL(sparse_indices, dim3(grid_for(std::max<uint64_t>(n, uint64_t{dict->n_chunks} + 1))), dim3(WG), 0, stream, bitmap, local, tile_bits, dict->d_entry_offsets,
+                       dict->n_chunks, static_cast<uint32_t>(n), d_entry, run_offsets);
+    st = check(hipGetLastError());
+  }
+  profile_end(stream);
+  if (st == HY_OK && n_subset) {
+    // a window at the entry's first byte keeps a sorted run sorted; single positions also where they are fewer than the chunks (fewer rounds)
+    const bool sorted_runs = !substr || substr->length <= 0 || substr->start == 0 || substr->start == 1;
+    st = table_order_launch(table, run_offsets, dict->n_chunks, n_subset, !sorted_runs || n_subset < dict->n_chunks, sc, ranks, stream);
+  }
+  if (st != HY_OK) {   // (launches may be queued: the temporaries go back to the pool behind them)
+    (void)hipStreamSynchronize(stream);
+    return st;
+  }
+  subset->table = table;
+  subset->ranks = ranks;
+  subset->n = n_subset;
+  return HY_OK;
 }
 
 // The back end.  d_entry: per output row the global entry index into `dict`, or -1; d_ranks: the dictionary's order (column_order_launch), queued
 // on `stream` already (nullptr for a dictionary without entries); d_windows: what of every entry the output holds, ranked as such, or nullptr.  The arena `sc` is reserved by the caller (gather_scratch_bytes).
 hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out, const int32_t* d_entry, const int32_t* d_ranks, const EntryWindow* d_windows, Scratch& sc,
-                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict) {
+                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict, const SparseSubset* subset) {
   const uint32_t n = static_cast<uint32_t>(out.n);
   const uint32_t n_chunks = static_cast<uint32_t>(out.sizes.size());
-  const uint32_t n_source_entries = static_cast<uint32_t>(dict->entry_offsets[dict->n_chunks]);
+  // (what the ranks run below and d_entry indexes: the dictionary's entries, or the subset's)
+  const uint32_t n_source_entries = subset ? subset->n : static_cast<uint32_t>(dict->entry_offsets[dict->n_chunks]);
   const uint32_t n_tiles = tiles_of(n);
 
   // the attribute vectors: one pooled arena, chunk c's vector 256-byte aligned with 16 bytes of slack (hy_column_gather's layout)
@@ -410,7 +618,8 @@ hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out,
   hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_heads, n_tiles, d_n_unique);
   hipLaunchKernelGGL(chunk_firsts, dim3(tiles_of(uint64_t{n_chunks} + 1)), dim3(WG), 0, stream, layout, local, tile_heads, chunk_first);
   hipLaunchKernelGGL(value_ids, dim3(n_tiles), dim3(WG), 0, stream, layout, d_entry, order.perm, local, tile_heads, chunk_first, arena, unique_entry);
-  hipLaunchKernelGGL(unique_lengths, dim3(n_tiles), dim3(WG), 0, stream, dict->d_chunks, dict->d_entry_offsets, dict->n_chunks, d_windows, unique_entry, d_n_unique, source, local_bytes, tile_bytes);
+  hipLaunchKernelGGL(unique_lengths, dim3(n_tiles), dim3(WG), 0, stream, dict->d_chunks, dict->d_entry_offsets, dict->n_chunks, d_windows,
+                     subset ? subset->table : nullptr, subset ? subset->n : 0, unique_entry, d_n_unique, source, local_bytes, tile_bytes);
   hipLaunchKernelGGL(scan_tiles<uint64_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_bytes, n_tiles, d_total_bytes);
   hipLaunchKernelGGL(chunk_totals, dim3(tiles_of(n_chunks)), dim3(WG), 0, stream, chunk_first, n_chunks, local_bytes, tile_bytes, d_totals);
   st = check(hipGetLastError());
@@ -525,6 +734,18 @@ hy_status hy_string_column_gather(const hy_column* column, const hy_string_dicti
 
   hipStream_t stream = current_stream();
   const uint64_t n_source_entries = dict->entry_offsets[dict->n_chunks];
+  if (string_sparse_route(n, column->rows, n_source_entries)) {   // the column read at the RowIDs, the entries they reference ranked
+    DeviceBuffer entry;
+    HY_TRY(entry.alloc(4 * n + 16));
+    Scratch& sc = scratch();
+    HY_TRY(sc.reserve(sparse_gather_scratch_bytes(n_source_entries, dict->n_chunks, n, out.sizes.size())));
+    HY_TRY(like_dictionary_tables(dict));
+    SparseSubset subset;
+    hy_status st = sparse_entries(column, dict, positions, n, nullptr, sc, entry.as<int32_t>(), stream, name, &subset);
+    if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), subset.ranks, nullptr, sc, stream, name, result, result_dict, &subset);
+    (void)hipStreamSynchronize(stream);   // (the temporaries go back to the pool)
+    return st;
+  }
   // the column's stand-in over 0, 1, 2, ... exported: every source row's global entry index
   DeviceBuffer table, values, nulls, entry;
   ColumnGuard stand_in;

@@ -106,39 +106,62 @@ struct OrderArgs {
   uint32_t n_chunks;
   const EntryWindow* windows;       // [entry_offsets[n_chunks]]: what of every entry is compared, or nullptr: all of it
   uint64_t run_positions;           // 0: round 0 merges whole chunks (each one a sorted run); else single positions (windows that do not ascend)
+  // The positions: entry_offsets[c] + v of the dictionary's entries (table == nullptr: run_offsets == entry_offsets, a workgroup owns a LikeBlock),
+  // or -- the sparse route of string_gather.hip -- the n_positions entries of a table, chunk c's run at [run_offsets[c], run_offsets[c + 1]),
+  // a workgroup owning 256 consecutive positions; an element is then the entry's index into the table.
+  const SubsetEntry* table;
+  const uint64_t* run_offsets;      // [n_chunks + 1]
+  uint64_t n_positions;
 };
 
 __device__ __forceinline__ Entry element_entry(const OrderArgs& a, uint64_t element) {
+  if (a.table) return entry_of(a.table[min(element, a.n_positions - 1)]);
   const uint32_t c = min(static_cast<uint32_t>(element >> 32), a.n_chunks - 1);
   const LikeChunk chunk = a.chunks[c];
   if (chunk.n_entries == 0) return Entry{nullptr, 0};
   return entry_of(chunk, min(static_cast<uint32_t>(element), chunk.n_entries - 1), chunk_bytes(chunk), a.windows ? a.windows + a.entry_offsets[c] : nullptr);
 }
 
-__global__ __launch_bounds__(ORDER_WG) void order_identity(OrderArgs a, uint64_t* elements) {
+// The position a lane owns, the chunk whose run it lies in and the element that lies there before round 0; false: the lane has none
+__device__ __forceinline__ bool own_position(const OrderArgs& a, uint64_t* position, uint32_t* chunk, uint64_t* element) {
+  if (a.table) {
+    const uint64_t p = uint64_t{blockIdx.x} * ORDER_WG + threadIdx.x;
+    if (p >= a.n_positions) return false;
+    *position = *element = p;
+    *chunk = last_at_or_below(a.run_offsets, a.n_chunks, p);   // (of equal offsets the last: the chunk that has the position)
+    return true;
+  }
   const LikeBlock block = a.blocks[blockIdx.x];
   const uint32_t v = block.first_entry + threadIdx.x;
-  if (v >= a.chunks[block.chunk].n_entries) return;
-  elements[a.entry_offsets[block.chunk] + v] = uint64_t{block.chunk} << 32 | v;
+  if (v >= a.chunks[block.chunk].n_entries) return false;
+  *position = a.entry_offsets[block.chunk] + v;
+  *chunk = block.chunk;
+  *element = uint64_t{block.chunk} << 32 | v;
+  return true;
+}
+
+__global__ __launch_bounds__(ORDER_WG) void order_identity(OrderArgs a, uint64_t* elements) {
+  uint64_t position, element;
+  uint32_t chunk;
+  if (own_position(a, &position, &chunk, &element)) elements[position] = element;
 }
 
 __global__ __launch_bounds__(ORDER_WG) void order_merge(OrderArgs a, const uint64_t* in, uint64_t* out, uint32_t round) {
-  const LikeBlock block = a.blocks[blockIdx.x];
-  const uint32_t v = block.first_entry + threadIdx.x;
-  if (v >= a.chunks[block.chunk].n_entries) return;
+  uint64_t position, identity;
+  uint32_t chunk;
+  if (!own_position(a, &position, &chunk, &identity)) return;
   // the pair of runs the position lies in: chunks [first, middle) and [middle, last)
   const uint64_t run = uint64_t{1} << round;
-  const uint64_t position = a.entry_offsets[block.chunk] + v;
   uint64_t left_begin, right_begin, right_end;
   if (a.run_positions) {   // runs of 2^round positions
-    const uint64_t total = a.entry_offsets[a.n_chunks];
+    const uint64_t total = a.run_offsets[a.n_chunks];
     left_begin = position >> (round + 1) << (round + 1);
     right_begin = min(left_begin + run, total);
     right_end = min(left_begin + 2 * run, total);
   } else {
-    const uint64_t first = (block.chunk >> round & ~1u) * run;
+    const uint64_t first = (chunk >> round & ~1u) * run;
     const uint64_t middle = min(first + run, uint64_t{a.n_chunks}), last = min(first + 2 * run, uint64_t{a.n_chunks});
-    left_begin = a.entry_offsets[first], right_begin = a.entry_offsets[middle], right_end = a.entry_offsets[last];
+    left_begin = a.run_offsets[first], right_begin = a.run_offsets[middle], right_end = a.run_offsets[last];
   }
   const uint64_t element = in[position];
   const Entry mine = element_entry(a, element);
@@ -201,6 +224,10 @@ __global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uin
   const uint64_t p = uint64_t{blockIdx.x} * ORDER_WG + threadIdx.x;
   if (p >= n) return;
   const uint64_t element = sorted[p];
+  if (a.table) {   // ranks by table index
+    ranks[min(element, a.n_positions - 1)] = static_cast<int32_t>(tile_heads[blockIdx.x] + local[p] - 1);
+    return;
+  }
   const uint32_t c = min(static_cast<uint32_t>(element >> 32), a.n_chunks - 1);
   const uint32_t n_entries = a.chunks[c].n_entries;
   if (n_entries == 0) return;
@@ -230,7 +257,7 @@ hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int
   *d_n_distinct = carve<uint32_t>(sc, 1);
   if (!ping || !pong || !tile_heads || !*d_n_distinct) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
   const bool by_position = d_windows && !sorted_chunks;
-  OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks, d_windows, by_position ? 1u : 0u};
+  OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks, d_windows, by_position ? 1u : 0u, nullptr, dict->d_entry_offsets, total};
   const uint64_t n_runs = by_position ? total : dict->n_chunks;
   profile_begin(stream, HY_KERNEL_STRING_RANK);
   hipLaunchKernelGGL(order_identity, dim3(n_blocks), dim3(ORDER_WG), 0, stream, args, ping);
@@ -241,6 +268,32 @@ hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int
   uint32_t* local = reinterpret_cast<uint32_t*>(pong);   // (the buffer the last round read: free again)
   hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads);
   hipLaunchKernelGGL(order_scan_tiles, dim3(1), dim3(ORDER_SCAN_WG), 0, stream, tile_heads, n_tiles, *d_n_distinct);
+  hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads, d_ranks);
+  profile_end(stream);
+  HY_HIP(hipGetLastError());
+  return HY_OK;
+}
+
+// The same sequence over a table of entries (the sparse route of string_gather.hip): `total` > 0 positions, 256 per workgroup
+hy_status table_order_launch(const SubsetEntry* d_table, const uint64_t* d_run_offsets, uint32_t n_chunks, uint64_t total, bool by_position, Scratch& sc, int32_t* d_ranks,
+                             hipStream_t stream) {
+  const uint32_t n_tiles = static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG);
+  uint64_t* ping = carve<uint64_t>(sc, total);
+  uint64_t* pong = carve<uint64_t>(sc, total);
+  uint32_t* tile_heads = carve<uint32_t>(sc, n_tiles);
+  uint32_t* d_n_distinct = carve<uint32_t>(sc, 1);
+  if (!ping || !pong || !tile_heads || !d_n_distinct) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  OrderArgs args{nullptr, nullptr, nullptr, n_chunks, nullptr, by_position ? 1u : 0u, d_table, d_run_offsets, total};
+  const uint64_t n_runs = by_position ? total : n_chunks;
+  profile_begin(stream, HY_KERNEL_STRING_RANK);
+  hipLaunchKernelGGL(order_identity, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping);
+  for (uint32_t round = 0; (uint64_t{1} << round) < n_runs; ++round) {
+    hipLaunchKernelGGL(order_merge, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, pong, round);
+    std::swap(ping, pong);
+  }
+  uint32_t* local = reinterpret_cast<uint32_t*>(pong);   // (the buffer the last round read: free again)
+  hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads);
+  hipLaunchKernelGGL(order_scan_tiles, dim3(1), dim3(ORDER_SCAN_WG), 0, stream, tile_heads, n_tiles, d_n_distinct);
   hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads, d_ranks);
   profile_end(stream);
   HY_HIP(hipGetLastError());

@@ -28,18 +28,6 @@ namespace {
 
 constexpr uint32_t WG = 256;   // = like.hip's LIKE_WG: the block table is the matcher's
 
-__device__ __forceinline__ EntryWindow substr_window(uint32_t n, int32_t start, int32_t length) {
-  if (length <= 0) return EntryWindow{0, 0};
-  int64_t s, l = length;
-  if (start < 0) s = int64_t{start} + n;
-  else if (start == 0) { s = 0; l -= 1; }
-  else s = int64_t{start} - 1;
-  const int64_t e = min(s + l, int64_t{n});
-  s = max(s, int64_t{0});
-  if (s < int64_t{n} && e > s) return EntryWindow{static_cast<uint32_t>(s), static_cast<uint32_t>(e - s)};
-  return EntryWindow{0, 0};
-}
-
 __global__ __launch_bounds__(WG) void entry_windows(const LikeChunk* chunks, const LikeBlock* blocks, const uint64_t* entry_offsets, int32_t start, int32_t length, EntryWindow* windows) {
   const LikeBlock block = blocks[blockIdx.x];
   const LikeChunk chunk = chunks[block.chunk];
@@ -72,16 +60,11 @@ struct ColumnGuard {
   ~ColumnGuard() { if (column) (void)hy_column_destroy(column); }
 };
 
-}  // namespace
-
-}  // namespace hy
-
-using namespace hy;
-
-extern "C" {
-
-hy_status hy_string_column_substr(const hy_column* column, const hy_string_dictionary* dict, int32_t start, int32_t length, hy_column** result, hy_string_dictionary** result_dict) {
-  const char* name = "hy_string_column_substr";
+// The rows of `column` themselves as a new string column in its own chunk layout, every entry seen through SUBSTR's window (`substr`) or
+// whole (nullptr): hy_string_column_substr and hy_string_column_materialize.
+hy_status column_rows_strings(const hy_column* column, const hy_string_dictionary* dict, const SubstrArguments* substr, const char* name, hy_column** result,
+                              hy_string_dictionary** result_dict) {
+  const int32_t start = substr ? substr->start : 1, length = substr ? substr->length : 0;
   if (result) *result = nullptr;
   if (result_dict) *result_dict = nullptr;
   if (!result || !result_dict || !column || !dict) return fail(HY_ERR_INVALID, "%s: null argument", name);
@@ -94,6 +77,19 @@ hy_status hy_string_column_substr(const hy_column* column, const hy_string_dicti
 
   hipStream_t stream = current_stream();
   const uint64_t n = column->rows, n_source_entries = dict->entry_offsets[dict->n_chunks];
+  if (string_sparse_route(n, n, n_source_entries)) {   // few rows against the dictionary: the column read row by row, the entries they reference windowed and ranked
+    DeviceBuffer entry;
+    HY_TRY(entry.alloc(4 * n + 16));
+    Scratch& sc = scratch();
+    HY_TRY(sc.reserve(sparse_gather_scratch_bytes(n_source_entries, dict->n_chunks, n, out.sizes.size())));
+    HY_TRY(like_dictionary_tables(dict));
+    SparseSubset subset;
+    hy_status st = HY_OK;
+    if (n) st = sparse_entries(column, dict, nullptr, n, substr, sc, entry.as<int32_t>(), stream, name, &subset);
+    if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), subset.ranks, nullptr, sc, stream, name, result, result_dict, &subset);
+    (void)hipStreamSynchronize(stream);   // (the temporaries go back to the pool)
+    return st;
+  }
   DeviceBuffer table, values, nulls, entry;
   ColumnGuard stand_in;
   HY_TRY(table.alloc(4 * n_source_entries + 16));
@@ -101,20 +97,23 @@ hy_status hy_string_column_substr(const hy_column* column, const hy_string_dicti
   HY_TRY(nulls.alloc(n + 16));
   HY_TRY(entry.alloc(4 * n + 16));
   Scratch& sc = scratch();
-  HY_TRY(sc.reserve(gather_scratch_bytes(n_source_entries, n, out.sizes.size(), false) + align_up(sizeof(EntryWindow) * n_source_entries + 16, 256)));
+  HY_TRY(sc.reserve(gather_scratch_bytes(n_source_entries, n, out.sizes.size(), false) + (substr ? align_up(sizeof(EntryWindow) * n_source_entries + 16, 256) : 0)));
   HY_TRY(like_dictionary_tables(dict));
   int32_t* d_ranks = nullptr;
   EntryWindow* d_windows = nullptr;
   if (n_source_entries) {
     d_ranks = carve<int32_t>(sc, n_source_entries);
-    d_windows = carve<EntryWindow>(sc, n_source_entries);
-    if (!d_ranks || !d_windows) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-    profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the windows: a bracket of their own)
-    hipLaunchKernelGGL(entry_windows, dim3(static_cast<uint32_t>(dict->blocks.size())), dim3(WG), 0, stream, dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, start, length, d_windows);
-    profile_end(stream);
+    if (!d_ranks) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+    if (substr) {
+      d_windows = carve<EntryWindow>(sc, n_source_entries);
+      if (!d_windows) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+      profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the windows: a bracket of their own)
+      hipLaunchKernelGGL(entry_windows, dim3(static_cast<uint32_t>(dict->blocks.size())), dim3(WG), 0, stream, dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, start, length, d_windows);
+      profile_end(stream);
+    }
     uint32_t* d_n_distinct = nullptr;
     // a window at the entry's first byte keeps a sorted dictionary sorted
-    const hy_status ranked = column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream, d_windows, length <= 0 || start == 0 || start == 1);
+    const hy_status ranked = column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream, d_windows, !substr || length <= 0 || start == 0 || start == 1);
     if (ranked != HY_OK) {   // (launches may be queued: the temporaries go back to the pool behind them)
       (void)hipStreamSynchronize(stream);
       return ranked;
@@ -133,6 +132,23 @@ hy_status hy_string_column_substr(const hy_column* column, const hy_string_dicti
   if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), d_ranks, d_windows, sc, stream, name, result, result_dict);
   (void)hipStreamSynchronize(stream);   // (the temporaries go back to the pool, the stand-in dies)
   return st;
+}
+
+}  // namespace
+
+}  // namespace hy
+
+using namespace hy;
+
+extern "C" {
+
+hy_status hy_string_column_substr(const hy_column* column, const hy_string_dictionary* dict, int32_t start, int32_t length, hy_column** result, hy_string_dictionary** result_dict) {
+  const SubstrArguments substr{start, length};
+  return column_rows_strings(column, dict, &substr, "hy_string_column_substr", result, result_dict);
+}
+
+hy_status hy_string_column_materialize(const hy_column* column, const hy_string_dictionary* dict, hy_column** result, hy_string_dictionary** result_dict) {
+  return column_rows_strings(column, dict, nullptr, "hy_string_column_materialize", result, result_dict);
 }
 
 }  // extern "C"

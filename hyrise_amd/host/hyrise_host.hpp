@@ -2585,7 +2585,8 @@ class Sort : public AbstractReadOnlyOperator {
   }
 
   // write_materialized_output_table (:58-150): ValueSegments of output_chunk_size rows, nullable iff the column is; numeric columns gathered on
-  // the device (hy_column_gather), strings -- and columns the device cannot read where they lie -- through the segments on the host
+  // the device (hy_column_gather), wholly dictionary-encoded string columns as DictionarySegments made in HBM (hy_string_column_gather at the
+  // sorted positions, device_string_results()), other strings -- and columns the device cannot read where they lie -- through the segments on the host
   std::shared_ptr<Table> materialized_output(const std::shared_ptr<const Table>& input, const std::shared_ptr<DeviceBlock>& positions, uint64_t rows) const {
     const uint64_t n_chunks = (rows + _output_chunk_size - 1) / _output_chunk_size;
     std::vector<Segments> segments(n_chunks, Segments(input->column_count()));
@@ -2594,6 +2595,22 @@ class Sort : public AbstractReadOnlyOperator {
       resolve_type(input->column_data_type(c), [&](auto tag) {
         using T = decltype(tag);
         hy_column* gathered = nullptr;
+        std::shared_ptr<const DeviceStringResult> strings;
+        if constexpr (std::is_same_v<T, std::string>) {
+          std::shared_ptr<const Table> data_table;
+          ColumnID data_column_id = c;
+          if (device_string_results() && rows && !references_several_columns(*input, c) && string_dictionary_column(input, c, data_table, data_column_id)) {
+            const auto column = device_column(input, c);
+            const auto dictionary = device_string_dictionary(data_table, data_column_id);
+            hy_column* made = nullptr;
+            hy_string_dictionary* made_dictionary = nullptr;
+            const auto status = hy_string_column_gather(column->handle, dictionary->handle, static_cast<const hy_row_id*>(positions->ptr), rows, _output_chunk_size, &made, &made_dictionary);
+            if (status != HY_ERR_UNSUPPORTED) {
+              check_status(status);
+              strings = std::make_shared<const DeviceStringResult>(made, made_dictionary);
+            }
+          }
+        }
         if constexpr (!std::is_same_v<T, std::string>) {
           if (!references_several_columns(*input, c)) {
             try {
@@ -2606,6 +2623,10 @@ class Sort : public AbstractReadOnlyOperator {
         }
         for (uint64_t k = 0; k < n_chunks; ++k) {
           const uint64_t begin = k * _output_chunk_size, size = std::min<uint64_t>(_output_chunk_size, rows - begin);
+          if (strings) {
+            segments[k][c] = std::make_shared<DeviceStringDictionarySegment>(strings, static_cast<uint32_t>(k), static_cast<ChunkOffset>(size));
+            continue;
+          }
           std::vector<T> values(size);
           std::vector<bool> nulls(size);
           if (gathered) {
@@ -3440,7 +3461,7 @@ class Projection : public AbstractReadOnlyOperator {
     for (const auto& e : _expressions) any_computed = any_computed || e->type != ExpressionType::Column;
     // ---- evaluate (projection.cpp:129-190: one ExpressionEvaluator per chunk; here: one hy_projection_expression per computed column)
     std::vector<std::shared_ptr<const DeviceColumnOwner>> owners(_expressions.size());
-    std::vector<std::shared_ptr<const DeviceStringResult>> substrings(_expressions.size());   // SUBSTR made in HBM; without one, the host loop below
+    std::vector<std::shared_ptr<const DeviceStringResult>> substrings(_expressions.size());   // SUBSTR, or a forwarded string column behind PosLists, made in HBM; without one, the host loops below
     TableColumnDefinitions definitions;
     for (size_t i = 0; i < _expressions.size(); ++i) {
       const auto& e = _expressions[i];
@@ -3452,6 +3473,11 @@ class Projection : public AbstractReadOnlyOperator {
         // live in it (:201-215 materialises it through the evaluator).  Numeric: the column itself as a one-node program -- hy_column_gather's
         // result with the input's chunk layout kept --, strings from the RowIDs on the host (below).
         if (any_computed && in_table->type() == TableType::References && type != DataType::String && chunk_count) owners[i] = evaluate(in_table, e);
+        // A string column behind PosLists, wholly dictionary-encoded: one hy_string_column_materialize, the chunks DictionarySegments in HBM
+        if (any_computed && in_table->type() == TableType::References && type == DataType::String && chunk_count) {
+          substrings[i] = materialized_string_column(in_table, e->column_id);
+          if (substrings[i]) definitions.back().nullable = true;   // (as the host loop below leaves it)
+        }
         continue;
       }
       if (e->type == ExpressionType::Substr) {
@@ -3645,6 +3671,22 @@ class Projection : public AbstractReadOnlyOperator {
     hy_column* made = nullptr;
     hy_string_dictionary* made_dictionary = nullptr;
     const auto status = hy_string_column_substr(column->handle, dictionary->handle, start, length, &made, &made_dictionary);
+    if (status == HY_ERR_UNSUPPORTED) return nullptr;
+    check_status(status);
+    return std::make_shared<const DeviceStringResult>(made, made_dictionary);
+  }
+
+  // A forwarded string column of a reference table made in HBM (projection.cpp:201-215 materialises it through the evaluator): one
+  // hy_string_column_materialize over the reference column, its PosLists where they are.  nullptr: as substring_column.
+  static std::shared_ptr<const DeviceStringResult> materialized_string_column(const std::shared_ptr<const Table>& in_table, ColumnID column_id) {
+    std::shared_ptr<const Table> data_table;
+    ColumnID data_column_id = column_id;
+    if (!device_string_results() || !string_dictionary_column(in_table, column_id, data_table, data_column_id)) return nullptr;
+    const auto column = device_column(in_table, column_id);
+    const auto dictionary = device_string_dictionary(data_table, data_column_id);
+    hy_column* made = nullptr;
+    hy_string_dictionary* made_dictionary = nullptr;
+    const auto status = hy_string_column_materialize(column->handle, dictionary->handle, &made, &made_dictionary);
     if (status == HY_ERR_UNSUPPORTED) return nullptr;
     check_status(status);
     return std::make_shared<const DeviceStringResult>(made, made_dictionary);

@@ -434,6 +434,16 @@ def string_column_substr(column, dictionary, start, length):
     return StringResultColumn(handle, dict_handle)
 
 
+def string_column_materialize(column, dictionary):
+    """hy_string_column_materialize: the rows of a string DeviceColumn themselves (data or reference column; `dictionary`: the
+    DeviceStringDictionary of its data column) as a StringResultColumn with `column`'s chunk layout -- what Projection makes of a forwarded
+    string column of a reference table."""
+    lib = abi.load_library()
+    handle, dict_handle = C.c_void_p(), C.c_void_p()
+    abi.check(lib.hy_string_column_materialize(column.handle, dictionary.handle, C.byref(handle), C.byref(dict_handle)))
+    return StringResultColumn(handle, dict_handle)
+
+
 def table_scan_columns_strings(left, left_dict, right, right_dict, condition, flags=0, device=False):
     """hy_table_scan_columns_strings: `left <condition> right` over two string columns of one table and their dictionaries (for reference
     columns: the referenced data columns') -> HostScanResult like table_scan_columns, or with device=True the chunk-region result in

@@ -271,6 +271,9 @@ hy_status hy_result_pool_calibrate(const hy_column* left, const hy_column* right
                                    float* ms_per_candidate, uint32_t* chosen);
 hy_status hy_result_pool_trim(void);
 hy_status hy_result_pool_stats(uint64_t* held_bytes, uint64_t* in_use_bytes, uint32_t* calibrated_pairs);
+/* The calling thread's pool of TEMPORARY blocks (what operators take for exports, sort buffers and the like, and hand back in stream order;
+ * hy_shutdown frees it): the bytes it holds between calls and its largest block.  Either pointer may be NULL. */
+hy_status hy_temporary_pool_stats(uint64_t* held_bytes, uint64_t* largest_block_bytes);
 
 /* ---- options: which of several equivalent paths / launch shapes an operator takes ---------------------------------------------
  * Process-wide integers with the defaults below.  EVERY setting produces the same results: the tests force each path with them and
@@ -309,7 +312,13 @@ enum {
   HY_OPT_JOIN_COMPACT_STAGE = 18,   /* 1    pk_emit stages 4-byte records (row, null partner, rank as a 16-bit delta on its wave's rank base) where every
                                       *      segment of the probe column is stored 1 or 2 bytes wide: three workgroups per CU instead of two;
                                       *      0 = the 8-byte records everywhere                                                                  */
-  HY_OPT_COUNT = 19
+  HY_OPT_STRING_SPARSE_GATHER = 19, /* 1    the string producers (hy_string_column_gather, hy_string_column_substr, hy_string_column_materialize) take the
+                                      *      sparse route -- the column read at the rows asked for, only the entries those rows reference ranked
+                                      *      (csrc/string_gather.hip) -- where the rows are few against the column's rows + dictionary entries
+                                      *      (STRING_SPARSE_DIVISOR, csrc/hy_options.hpp); 0 = the dense route always (export of every source row,
+                                      *      ranking of every entry); 2 = the sparse route always (tests, tools/string_gather_sparse_timing.py).
+                                      *      Every setting gives the same bytes                                                                    */
+  HY_OPT_COUNT = 20
   /* (rounds 4-5 had 33: launch shapes and store flavours whose A/B timings were flat twice are constants now -- csrc/hy_options.hpp --,
    *  the radix-partitioned join path, which lost to the rank table read in place by 1.7 x, is gone) */
 };
@@ -611,6 +620,18 @@ hy_status hy_string_ranks_gather(const hy_string_dictionary* dict, const hy_colu
  *   launch).  On every error both out pointers are NULL and nothing stays allocated. */
 hy_status hy_string_column_substr(const hy_column* column, const hy_string_dictionary* dict, int32_t start, int32_t length, hy_column** result,
                                   hy_string_dictionary** result_dict);
+/* hy_string_column_materialize   the rows of `column` themselves as a new string column: the same pair as above in `column`'s OWN chunk
+ *   layout (one output chunk per input chunk, same sizes) -- row r of chunk c is row r of chunk c, a NULL row or NULL RowID stays NULL --,
+ *   *result_dict per output chunk the distinct strings of its non-NULL rows.  It is what Projection does with a forwarded string column of a
+ *   reference table once another column of the projection is computed (projection.cpp:201-215 materialises it through the evaluator, one
+ *   string per row): `column` is a data column of string dictionary segments or a reference column over one with PosLists in either memory
+ *   space, `dict` the DATA column's dictionaries.  On the device it is hy_string_column_substr's path without windows; where the column's
+ *   rows are few against the dictionary (HY_OPT_STRING_SPARSE_GATHER) only the entries they reference are ranked.  A column of zero chunks:
+ *   HY_OK, a column and a dictionary of zero chunks, no launch.  The refusals are hy_string_column_substr's: HY_ERR_INVALID for a null
+ *   argument, a column that is no string column, a dictionary that disagrees with the data column or lives on another device;
+ *   HY_ERR_UNSUPPORTED for unencoded or LZ4 string segments, E >= 2^31 source entries, 2^32 rows or more, an output chunk whose chars would
+ *   take 2^32 bytes or more (the only refusal behind a launch).  On every error both out pointers are NULL and nothing stays allocated. */
+hy_status hy_string_column_materialize(const hy_column* column, const hy_string_dictionary* dict, hy_column** result, hy_string_dictionary** result_dict);
 /* An offsets-layout chunk of a dictionary read back, whether the library owns its buffers (an upload, a gather's result) or the caller:
  * chunk_size gives n_entries and the bytes of its chars (offsets[n_entries]); read_chunk copies the n_entries + 1 offsets as they are and the
  * chars' bytes [0, offsets[n_entries]) to host memory (chars may be NULL when there are none).  A fixed-slot chunk with entries:
