@@ -128,6 +128,7 @@ NLJ_MAX_TEMPORARY_BYTES = 1 << 31      # HY_NLJ_MAX_TEMPORARY_BYTES
  OPT_JOIN_HAND_OVER_RANKS, OPT_AGG_PARTITION_BITS, OPT_AGG_SPILL_SHIFT, OPT_AGG_SMALL_DOMAIN, OPT_FUSED_SMALL_DOMAIN, OPT_SCAN_TWO_COLUMNS, OPT_STAR_FUSED_PROBE, OPT_STAR_FUSED_FINISH,
  OPT_LDS_ORDERED_ATOMICS, OPT_PRODUCT_NONTEMPORAL, OPT_JOIN_COMPACT_STAGE, OPT_STRING_SPARSE_GATHER) = range(20)
 KERNEL_OTHER, KERNEL_SCAN, KERNEL_JOIN_PROBE, KERNEL_JOIN_COUNT, KERNEL_JOIN_BUILD, KERNEL_AGGREGATE, KERNEL_PROJECTION, KERNEL_LIKE, KERNEL_STRING_RANK = range(9)   # hy_profile_read_kernel
+STRING_KEYS_RANKS, STRING_KEYS_HASH_IDS = 0, 1   # hy_column_string_join_keys: int32 ranks / int64 join ids
 ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV, ARITH_MOD = range(5)
 
 
@@ -284,6 +285,9 @@ SYMBOLS = [
     ("hy_table_scan_columns_strings", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScanResult)]),
     ("hy_string_dictionary_order", C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("hy_column_string_ranks", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("hy_string_dictionary_order_pair", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("hy_string_dictionary_join_ids", C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("hy_column_string_join_keys", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("hy_string_column_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("hy_string_ranks_gather", C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("hy_string_column_substr", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

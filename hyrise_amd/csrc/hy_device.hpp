@@ -300,7 +300,19 @@ hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out,
 hy_status empty_string_results(hy_column** result, hy_string_dictionary** result_dict);   // a column and a dictionary of zero chunks
 // The int32 stand-in of a string column over a table of E int32_t in device memory (entry v of data chunk c reads d_table[entry_offsets[c] + v]):
 // the caller's attribute vectors and PosLists, shared.  A reference column's stand-in owns its data stand-in; the table stays the caller's.
-hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, int32_t* d_table, hy_column** out);
+// data_type HY_TYPE_LONG: a table of E int64_t, an int64 stand-in (the join ids of string_join_keys.hip).
+hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, void* d_table, hy_column** out, uint32_t data_type = HY_TYPE_INT);
+// string_order.hip: the merge sequence over the chunks of two dictionaries laid end to end -- the tables are the caller's, in device memory
+// (chunks [n_chunks], blocks [n_blocks] with joint chunk indices, entry_offsets [n_chunks + 1]); positions below `split` are the left
+// dictionary's.  Takes order_scratch_bytes(total) from `sc`; total > 0.
+struct PairTables {
+  const LikeChunk* chunks;
+  const LikeBlock* blocks;
+  const uint64_t* entry_offsets;
+  uint32_t n_chunks, n_blocks;
+  uint64_t total, split;
+};
+hy_status pair_order_launch(const PairTables& tables, Scratch& sc, int32_t* d_left_ranks, int32_t* d_right_ranks, uint32_t** d_n_distinct, hipStream_t stream);
 // scan.hip: `dict` is the string dictionary of `column`'s data column, chunk by chunk, on `column`'s device; `which`: "", "left " or "right "
 hy_status check_dictionary(const hy_string_dictionary* dict, const hy_column* column, const char* which, const char* entry_point);
 

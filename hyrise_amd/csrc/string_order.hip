@@ -220,7 +220,9 @@ __global__ __launch_bounds__(ORDER_SCAN_WG) void order_scan_tiles(uint32_t* tile
   if (threadIdx.x == ORDER_SCAN_WG - 1) *n_distinct = s_sums[ORDER_SCAN_WG - 1];
 }
 
-__global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uint64_t* sorted, uint64_t n, const uint32_t* local, const uint32_t* tile_heads, int32_t* ranks) {
+// (split: the joint order of two dictionaries, below -- a position at or behind it is an entry of the right one and goes to right_ranks)
+__global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uint64_t* sorted, uint64_t n, const uint32_t* local, const uint32_t* tile_heads, int32_t* ranks,
+                                                          int32_t* right_ranks, uint64_t split) {
   const uint64_t p = uint64_t{blockIdx.x} * ORDER_WG + threadIdx.x;
   if (p >= n) return;
   const uint64_t element = sorted[p];
@@ -232,7 +234,10 @@ __global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uin
   const uint32_t n_entries = a.chunks[c].n_entries;
   if (n_entries == 0) return;
   const uint32_t v = min(static_cast<uint32_t>(element), n_entries - 1);
-  ranks[a.entry_offsets[c] + v] = static_cast<int32_t>(tile_heads[blockIdx.x] + local[p] - 1);   // (position 0 is a head: never below 0)
+  const uint64_t position = a.entry_offsets[c] + v;
+  const int32_t rank = static_cast<int32_t>(tile_heads[blockIdx.x] + local[p] - 1);   // (position 0 is a head: never below 0)
+  if (position >= split) right_ranks[position - split] = rank;
+  else ranks[position] = rank;
 }
 
 }  // namespace
@@ -243,61 +248,58 @@ size_t order_scratch_bytes(uint64_t total) {
   return 2 * align_up(8 * total, 256) + align_up(4 * tiles, 256) + 256 + 4096;
 }
 
-// Queues the whole sequence on `stream`: d_ranks[entry_offsets[c] + v] and *d_n_distinct (device memory, carved here: d_ranks may be a
-// block of the arena that the caller carved BEFORE this call).  total = entry_offsets[n_chunks] > 0.
-hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream, const EntryWindow* d_windows,
-                              bool sorted_chunks) {
-  HY_TRY(like_dictionary_tables(dict));
-  const uint64_t total = dict->entry_offsets[dict->n_chunks];
-  const uint32_t n_blocks = static_cast<uint32_t>(dict->blocks.size());
+// The launch sequence, once, for its three callers: identity, the merge rounds over `n_runs` runs, heads, the scan of the tiles' heads, the
+// scatter (positions at or behind `split` to d_right_ranks).  `merge_workgroups`: what order_identity and order_merge are launched with (a
+// block table's size, or the tiles of a table of entries); a.n_positions > 0.  *d_n_distinct is carved here.
+static hy_status order_sequence(const OrderArgs& a, uint32_t merge_workgroups, uint64_t n_runs, Scratch& sc, int32_t* d_ranks, int32_t* d_right_ranks, uint64_t split,
+                                uint32_t** d_n_distinct, hipStream_t stream) {
+  const uint64_t total = a.n_positions;
   const uint32_t n_tiles = static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG);
   uint64_t* ping = carve<uint64_t>(sc, total);
   uint64_t* pong = carve<uint64_t>(sc, total);
   uint32_t* tile_heads = carve<uint32_t>(sc, n_tiles);
   *d_n_distinct = carve<uint32_t>(sc, 1);
   if (!ping || !pong || !tile_heads || !*d_n_distinct) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-  const bool by_position = d_windows && !sorted_chunks;
-  OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks, d_windows, by_position ? 1u : 0u, nullptr, dict->d_entry_offsets, total};
-  const uint64_t n_runs = by_position ? total : dict->n_chunks;
   profile_begin(stream, HY_KERNEL_STRING_RANK);
-  hipLaunchKernelGGL(order_identity, dim3(n_blocks), dim3(ORDER_WG), 0, stream, args, ping);
+  hipLaunchKernelGGL(order_identity, dim3(merge_workgroups), dim3(ORDER_WG), 0, stream, a, ping);
   for (uint32_t round = 0; (uint64_t{1} << round) < n_runs; ++round) {
-    hipLaunchKernelGGL(order_merge, dim3(n_blocks), dim3(ORDER_WG), 0, stream, args, ping, pong, round);
+    hipLaunchKernelGGL(order_merge, dim3(merge_workgroups), dim3(ORDER_WG), 0, stream, a, ping, pong, round);
     std::swap(ping, pong);
   }
   uint32_t* local = reinterpret_cast<uint32_t*>(pong);   // (the buffer the last round read: free again)
-  hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads);
+  hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, a, ping, total, local, tile_heads);
   hipLaunchKernelGGL(order_scan_tiles, dim3(1), dim3(ORDER_SCAN_WG), 0, stream, tile_heads, n_tiles, *d_n_distinct);
-  hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads, d_ranks);
+  hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, a, ping, total, local, tile_heads, d_ranks, d_right_ranks, split);
   profile_end(stream);
   HY_HIP(hipGetLastError());
   return HY_OK;
 }
 
+// Queues the whole sequence on `stream`: d_ranks[entry_offsets[c] + v] and *d_n_distinct (device memory, carved here: d_ranks may be a
+// block of the arena that the caller carved BEFORE this call).  total = entry_offsets[n_chunks] > 0.
+hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream, const EntryWindow* d_windows,
+                              bool sorted_chunks) {
+  HY_TRY(like_dictionary_tables(dict));
+  const uint64_t total = dict->entry_offsets[dict->n_chunks];
+  const bool by_position = d_windows && !sorted_chunks;
+  const OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks, d_windows, by_position ? 1u : 0u, nullptr, dict->d_entry_offsets, total};
+  return order_sequence(args, static_cast<uint32_t>(dict->blocks.size()), by_position ? total : dict->n_chunks, sc, d_ranks, nullptr, ~0ull, d_n_distinct, stream);
+}
+
 // The same sequence over a table of entries (the sparse route of string_gather.hip): `total` > 0 positions, 256 per workgroup
 hy_status table_order_launch(const SubsetEntry* d_table, const uint64_t* d_run_offsets, uint32_t n_chunks, uint64_t total, bool by_position, Scratch& sc, int32_t* d_ranks,
                              hipStream_t stream) {
-  const uint32_t n_tiles = static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG);
-  uint64_t* ping = carve<uint64_t>(sc, total);
-  uint64_t* pong = carve<uint64_t>(sc, total);
-  uint32_t* tile_heads = carve<uint32_t>(sc, n_tiles);
-  uint32_t* d_n_distinct = carve<uint32_t>(sc, 1);
-  if (!ping || !pong || !tile_heads || !d_n_distinct) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-  OrderArgs args{nullptr, nullptr, nullptr, n_chunks, nullptr, by_position ? 1u : 0u, d_table, d_run_offsets, total};
-  const uint64_t n_runs = by_position ? total : n_chunks;
-  profile_begin(stream, HY_KERNEL_STRING_RANK);
-  hipLaunchKernelGGL(order_identity, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping);
-  for (uint32_t round = 0; (uint64_t{1} << round) < n_runs; ++round) {
-    hipLaunchKernelGGL(order_merge, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, pong, round);
-    std::swap(ping, pong);
-  }
-  uint32_t* local = reinterpret_cast<uint32_t*>(pong);   // (the buffer the last round read: free again)
-  hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads);
-  hipLaunchKernelGGL(order_scan_tiles, dim3(1), dim3(ORDER_SCAN_WG), 0, stream, tile_heads, n_tiles, d_n_distinct);
-  hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, args, ping, total, local, tile_heads, d_ranks);
-  profile_end(stream);
-  HY_HIP(hipGetLastError());
-  return HY_OK;
+  const OrderArgs args{nullptr, nullptr, nullptr, n_chunks, nullptr, by_position ? 1u : 0u, d_table, d_run_offsets, total};
+  uint32_t* d_n_distinct = nullptr;
+  return order_sequence(args, static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG), by_position ? total : n_chunks, sc, d_ranks, nullptr, ~0ull, &d_n_distinct, stream);
+}
+
+// The same sequence over the chunks of TWO dictionaries laid end to end (string_join_keys.hip builds the tables): left's chunks are runs
+// 0 .. n_l - 1, right's follow, so equal strings of either side get one rank.  Positions below t.split are left's entries and go to
+// d_left_ranks, the others to d_right_ranks[position - split].  t.total > 0.
+hy_status pair_order_launch(const PairTables& t, Scratch& sc, int32_t* d_left_ranks, int32_t* d_right_ranks, uint32_t** d_n_distinct, hipStream_t stream) {
+  const OrderArgs args{t.chunks, t.blocks, t.entry_offsets, t.n_chunks, nullptr, 0u, nullptr, t.entry_offsets, t.total};
+  return order_sequence(args, t.n_blocks, t.n_chunks, sc, d_left_ranks, d_right_ranks, t.split, d_n_distinct, stream);
 }
 
 // The refusals of a dictionary that is to be ordered, before any launch and any allocation
@@ -339,17 +341,17 @@ hy_status string_order_launch(const hy_string_dictionary* left, const hy_string_
 }
 
 // The int32 stand-in of a string column (a data column, or a reference column over one) over a table of E int32_t in device memory: entry v
-// of data chunk c reads table[entry_offsets[c] + v].  The data stand-in has DictionarySegment<int32> chunks over the caller's attribute
+// of data chunk c reads table[entry_offsets[c] + v].  (data_type HY_TYPE_LONG: a table of E int64_t and an int64 stand-in, string_join_keys.hip.)  The data stand-in has DictionarySegment<int32> chunks over the caller's attribute
 // vectors, whatever their width or packing, with the NULL value id still aux_size; a reference column gets the same PosLists over it, and
 // owns it (hy_column::stand_in).  The table stays the caller's.
-hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, int32_t* d_table, hy_column** out) {
+hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, void* d_table, hy_column** out, uint32_t data_type) {
   *out = nullptr;
   const hy_column* data_column = column->is_reference ? column->ref : column;
   const uint32_t n_data_chunks = data_column->n_chunks;
   std::vector<hy_segment> segments(data_column->host_segments);
   for (uint32_t c = 0; c < n_data_chunks; ++c) {
-    segments[c].data_type = HY_TYPE_INT;
-    segments[c].aux = d_table + dict->entry_offsets[c];
+    segments[c].data_type = data_type;
+    segments[c].aux = static_cast<char*>(d_table) + (data_type == HY_TYPE_LONG ? 8 : 4) * dict->entry_offsets[c];
   }
   hy_column* stand_in = nullptr;
   HY_TRY(hy_column_create(segments.data(), n_data_chunks, HY_MEM_DEVICE, &stand_in));
@@ -357,7 +359,7 @@ hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* d
   if (column->is_reference) {   // the same PosLists over the stand-in
     segments = column->host_segments;
     for (hy_segment& segment : segments) {
-      segment.data_type = HY_TYPE_INT;
+      segment.data_type = data_type;
       segment.ref = stand_in;
       // (an uploaded PosList without rows has no device buffer: as a descriptor over device memory it reads as an entire-chunk list, whose
       // chunk id must exist -- of no rows, so which chunk does not matter)

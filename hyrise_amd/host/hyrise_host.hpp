@@ -1008,6 +1008,12 @@ inline std::shared_ptr<DeviceColumn> device_column_of_chunks(const std::shared_p
         d.aux = nullptr;   // scans compare value ids; literals are resolved per chunk by the caller
       }
       ok = true;
+    } else if (const auto* s = string_keys == StringKeys::JoinIds ? dynamic_cast<const ValueSegment<std::string>*>(segment.get()) : nullptr) {
+      // an unencoded string chunk as a join key: the rows' ids, one registry lookup per row (JoinHash's host route)
+      for (ChunkOffset row = 0; row < s->size(); ++row) column->key_names[chunk_id].push_back(s->is_null(row) ? 0 : string_join_id(s->values()[row]));   // (a NULL row's placeholder gets no id)
+      d.encoding = HY_ENC_UNENCODED; d.width = 8; d.data = column->key_names[chunk_id].data(); d.data_type = HY_TYPE_LONG;
+      d.nulls = s->is_nullable() ? s->null_words().data() : nullptr;
+      ok = true;
     } else if (const auto* s = dynamic_cast<const FrameOfReferenceSegment*>(segment.get())) {
       d.encoding = HY_ENC_FRAME_OF_REFERENCE; d.width = s->offset_values().width; d.data = s->offset_values().bytes.data();
       d.aux = s->block_minima().data(); d.aux_size = static_cast<uint32_t>(s->block_minima().size());
@@ -1160,6 +1166,32 @@ inline std::shared_ptr<DeviceColumn> device_string_rank_column(const std::shared
   const auto dictionary = device_string_dictionary(data_table, data_column_id);
   if (hy_column_string_ranks(column->strings->handle, dictionary->handle, &column->handle) != HY_OK) return nullptr;
   return column;
+}
+
+// The keys two string columns join on, made on the device (hy_column_string_join_keys); false: JoinHash's ids come from string_join_id on the
+// host, and JoinSortMerge does not take string keys (tests/cpp/string_join_keys_tests.cpp runs both).
+inline bool& device_string_join_keys() { static bool enabled = true; return enabled; }
+inline std::atomic<uint64_t>& device_string_join_key_pairs() { static std::atomic<uint64_t> pairs{0}; return pairs; }   // joins whose keys hy_column_string_join_keys made
+
+// The stand-ins of a pair of string key columns -- HY_STRING_KEYS_HASH_IDS for JoinHash, HY_STRING_KEYS_RANKS for JoinSortMerge -- without any
+// string work on the host: both columns wholly dictionary-encoded (string_dictionary_column), each sent as it is for a scan, its data
+// column's dictionaries as they are for LIKE.  The stand-ins belong to the join, not to the column cache: they depend on the partner column.
+// false: the switch is off, one of the columns is not such a column, or the library refused the pair -- the caller takes its host route.
+inline bool device_string_join_key_columns(const std::shared_ptr<const Table>& left, ColumnID left_id, const std::shared_ptr<const Table>& right, ColumnID right_id, uint32_t kind,
+                                           std::shared_ptr<DeviceColumn>& left_keys, std::shared_ptr<DeviceColumn>& right_keys) {
+  if (!device_string_join_keys()) return false;
+  std::shared_ptr<const Table> left_data, right_data;
+  ColumnID left_data_id = left_id, right_data_id = right_id;
+  if (!string_dictionary_column(left, left_id, left_data, left_data_id) || !string_dictionary_column(right, right_id, right_data, right_data_id)) return false;
+  auto l = std::make_shared<DeviceColumn>(), r = std::make_shared<DeviceColumn>();
+  l->strings = device_column(left, left_id, StringKeys::None);
+  r->strings = device_column(right, right_id, StringKeys::None);
+  const auto left_dictionary = device_string_dictionary(left_data, left_data_id), right_dictionary = device_string_dictionary(right_data, right_data_id);
+  if (hy_column_string_join_keys(l->strings->handle, left_dictionary->handle, r->strings->handle, right_dictionary->handle, kind, &l->handle, &r->handle) != HY_OK) return false;
+  device_string_join_key_pairs().fetch_add(1, std::memory_order_relaxed);
+  left_keys = l;
+  right_keys = r;
+  return true;
 }
 
 // LIKE scans match their dictionaries on the device (hy_table_scan_like); false: on the host, bitmaps through hy_predicate.match_words.
@@ -1898,7 +1930,13 @@ class JoinHash : public AbstractReadOnlyOperator {   // operators/join_hash.hpp:
     const bool string_keys = left->column_data_type(_column_ids.first) == DataType::String;
     Assert(string_keys == (right->column_data_type(_column_ids.second) == DataType::String), "JoinHash: a string key against a numeric key is not run on the device");
     const auto keys = string_keys ? StringKeys::JoinIds : StringKeys::None;
-    const auto left_column = device_column(left, _column_ids.first, keys), right_column = device_column(right, _column_ids.second, keys);
+    // ... made in HBM for the pair where both columns are wholly dictionary-encoded (hy_column_string_join_keys: another unique number above
+    // the hash bits, the same join); otherwise, and when the library refuses, each column's ids from the host's registry
+    std::shared_ptr<DeviceColumn> left_column, right_column;
+    if (!string_keys || !device_string_join_key_columns(left, _column_ids.first, right, _column_ids.second, HY_STRING_KEYS_HASH_IDS, left_column, right_column)) {
+      left_column = device_column(left, _column_ids.first, keys);
+      right_column = device_column(right, _column_ids.second, keys);
+    }
     // JoinHash::supports (join_hash.cpp:39-44)
     Assert(_mode != JoinMode::AntiNullAsTrue || _secondary_predicates.empty(), "JoinHash does not support secondary predicates with AntiNullAsTrue");
     std::vector<hy_join_predicate> secondary;
@@ -2097,8 +2135,8 @@ struct JoinConfiguration {
 // output's PosLists are views into them (a data input) or into the blocks hy_poslist_gather dereferences them into (a reference input:
 // JoinHash's DeviceSide).  The matched pairs, the unmatched left rows and the unmatched right rows each start a new output chunk, and inside
 // a part a chunk holds Chunk::DEFAULT_SIZE pairs.  The order of the rows is the library's contract (include/hyrise_amd.h), not the
-// reference's, whose order depends on its cluster count: the tables agree as multisets of rows.  What the library refuses -- strings, key
-// columns of different types, Semi / Anti / Cross, <> with an outer mode -- and joins with secondary predicates stay on the stock operator.
+// reference's, whose order depends on its cluster count: the tables agree as multisets of rows.  What the library refuses -- string keys that
+// are not wholly dictionary-encoded, key columns of different types, Semi / Anti / Cross, <> with an outer mode -- and joins with secondary predicates stay on the stock operator.
 class JoinSortMerge : public AbstractReadOnlyOperator {
  public:
   JoinSortMerge(std::shared_ptr<const AbstractOperator> left, std::shared_ptr<const AbstractOperator> right, JoinMode mode, OperatorJoinPredicate primary_predicate,
@@ -2117,8 +2155,17 @@ class JoinSortMerge : public AbstractReadOnlyOperator {
     const auto left = left_input_table(), right = right_input_table();
     Assert(_secondary_predicates.empty(), "JoinSortMerge: joins with secondary predicates are not run on the device");
     const auto ids = _primary_predicate.column_ids;
-    Assert(left->column_data_type(ids.first) != DataType::String && right->column_data_type(ids.second) != DataType::String, "JoinSortMerge: string keys are not run on the device");
-    const auto left_column = device_column(left, ids.first), right_column = device_column(right, ids.second);
+    // string keys join as their ranks among the distinct strings of BOTH columns, made in HBM (hy_column_string_join_keys): both columns
+    // wholly dictionary-encoded and device_string_join_keys() on; every other case of a string key stays on the stock operator
+    const bool left_strings = left->column_data_type(ids.first) == DataType::String, right_strings = right->column_data_type(ids.second) == DataType::String;
+    std::shared_ptr<DeviceColumn> left_column, right_column;
+    if (left_strings || right_strings) {
+      Assert(left_strings && right_strings && device_string_join_key_columns(left, ids.first, right, ids.second, HY_STRING_KEYS_RANKS, left_column, right_column),
+             "JoinSortMerge: string keys are not run on the device");
+    } else {
+      left_column = device_column(left, ids.first);
+      right_column = device_column(right, ids.second);
+    }
     // One call: room for one partner per row of the larger input; a join that needs more reports it with HY_ERR_CAPACITY (nothing written)
     // and runs once more with exactly that.
     uint64_t capacity = std::max<uint64_t>(1, std::max(left->row_count(), right->row_count()));

@@ -349,6 +349,47 @@ def column_string_ranks(dev_column, dev_dict):
     return StringRankColumn(handle, (dev_column, dev_dict))
 
 
+def _split_by_chunk(values, dev_dict):
+    bounds = np.concatenate([[0], np.cumsum(dev_dict.n_entries, dtype=np.int64)]).astype(np.int64)
+    return [values[int(bounds[c]):int(bounds[c + 1])] for c in range(dev_dict.n_chunks)]
+
+
+def string_dictionary_order_pair(left_dict, right_dict):
+    """hy_string_dictionary_order_pair with a host result over two storage.DeviceStringDictionary -> (per chunk of the left dictionary the
+    int32 dense ranks of its entries among the distinct strings of BOTH dictionaries, the same for the right one, the number of distinct
+    strings): equal strings on either side have one rank."""
+    lib = abi.load_library()
+    left = np.zeros(max(1, sum(left_dict.n_entries)), dtype=np.int32)
+    right = np.zeros(max(1, sum(right_dict.n_entries)), dtype=np.int32)
+    n_distinct = C.c_uint32(0xFFFFFFFF)
+    abi.check(lib.hy_string_dictionary_order_pair(left_dict.handle, right_dict.handle, abi.MEM_HOST, left.ctypes.data, right.ctypes.data, C.byref(n_distinct)))
+    return _split_by_chunk(left, left_dict), _split_by_chunk(right, right_dict), int(n_distinct.value)
+
+
+def string_dictionary_join_ids(left_dict, right_dict):
+    """hy_string_dictionary_join_ids with a host result -> per chunk of either dictionary the int64 join ids of its entries:
+    (joint rank + 1) << 20 | std::hash & 0xFFFFF, what join_keys.StringJoinKeys hands out on the host with another unique number on top."""
+    lib = abi.load_library()
+    left = np.zeros(max(1, sum(left_dict.n_entries)), dtype=np.int64)
+    right = np.zeros(max(1, sum(right_dict.n_entries)), dtype=np.int64)
+    abi.check(lib.hy_string_dictionary_join_ids(left_dict.handle, right_dict.handle, abi.MEM_HOST, left.ctypes.data, right.ctypes.data))
+    return _split_by_chunk(left, left_dict), _split_by_chunk(right, right_dict)
+
+
+def column_string_join_keys(left_column, left_dict, right_column, right_dict, kind):
+    """hy_column_string_join_keys: two string DeviceColumns (data or reference columns, independently) and the DeviceStringDictionary of
+    each one's data column -> their two stand-ins (StringRankColumn) over keys consistent across both: abi.STRING_KEYS_RANKS (int32, for
+    join_sort_merge / join_nested_loop) or abi.STRING_KEYS_HASH_IDS (int64, for join_hash), made and kept in HBM."""
+    lib = abi.load_library()
+    left, right = C.c_void_p(), C.c_void_p()
+    abi.check(lib.hy_column_string_join_keys(left_column.handle, left_dict.handle, right_column.handle, right_dict.handle, kind, C.byref(left), C.byref(right)))
+    data_type = abi.TYPE_LONG if kind == abi.STRING_KEYS_HASH_IDS else abi.TYPE_INT
+    stand_ins = StringRankColumn(left, (left_column, left_dict)), StringRankColumn(right, (right_column, right_dict))
+    for stand_in in stand_ins:
+        stand_in.data_type = data_type
+    return stand_ins
+
+
 class StringResultColumn:
     """A dictionary-encoded string column the library made in HBM (hy_string_column_gather / hy_string_ranks_gather) with the
     DeviceStringDictionary that belongs to it: usable wherever a string DeviceColumn and its dictionary are."""

@@ -527,7 +527,7 @@ hy_status hy_string_dictionary_ranks(const hy_string_dictionary* left, const hy_
 hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_dictionary* left_dict, const hy_column* right,
                                         const hy_string_dictionary* right_dict, uint32_t condition, hy_scan_result* result);
 
-/* ---- One string column's global order (what Sort, and later MIN / MAX and JoinSortMerge, need of a pmr_string column) -------------------
+/* ---- One string column's global order (what Sort and MIN / MAX need of a pmr_string column; the joins read the joint order below) ------
  * hy_string_dictionary_ranks orders chunk c of one column against chunk c of another.  The entry points below order ALL chunks of ONE
  * column against each other: for entry v of chunk c
  *     rank(c, v) = the number of DISTINCT strings, over all chunks of `dict`, that are smaller than the entry        (dense rank)
@@ -565,6 +565,50 @@ hy_status hy_table_scan_columns_strings(const hy_column* left, const hy_string_d
  *   allocated.  Ranks are not cached inside `dict`: every call ranks again. */
 hy_status hy_string_dictionary_order(const hy_string_dictionary* dict, uint32_t mem, int32_t* ranks, uint32_t* n_distinct);
 hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictionary* dict, hy_column** out);
+
+/* ---- The keys two string columns join on (what JoinHash and JoinSortMerge need of two pmr_string columns of two tables) -----------------
+ * The order above is one column's.  A join needs a stand-in that is consistent across TWO columns: for an entry of either dictionary
+ *     rank(entry) = the number of DISTINCT strings, over all chunks of `left` AND `right` together, that are smaller than the entry
+ *     id(entry)   = ((int64_t)rank(entry) + 1) << 20 | (hash(entry) & 0xFFFFF)
+ * Equal strings on either side get equal ranks and equal ids; ranks run 0 .. n_distinct - 1.  Order is std::string's, as above (a '\0'
+ * inside an entry of the offsets layout is data, an entry of the fixed-length layout ends at strnlen(slot, string_length)).  hash is
+ * libstdc++'s std::hash<std::string> over exactly the entry's bytes (_Hash_bytes, libsupc++/hash_bytes.cc: seed 0xc70f6907,
+ * mul 0xc6a4a7935bd1e995, 8-byte little-endian words, a tail of 1-7 bytes assembled from unsigned bytes, two final shift-mixes).  The id
+ * formula is a contract: the reference's JoinHash takes its radix partition (hash & mask, radix_bits <= 8) and its Bloom index
+ * (hash % 2^20) from the low bits, so hy_join_hash over the ids is the reference's join over the strings -- same partitions, same probe-row
+ * and build-side order -- whatever unique number stands above bit 20.  The ranks feed hy_join_sort_merge and hy_join_nested_loop, the ids
+ * hy_join_hash.
+ * On the device the chunks of both dictionaries, laid end to end (left's first), go through hy_string_dictionary_order's merge sequence,
+ * ceil(log2(n_l + n_r)) rounds; the ids take one more launch, a lane per entry.  The joint tables are built per call: the dictionaries stay
+ * as they are.  Timed under HY_KERNEL_STRING_RANK; temporaries (16 bytes per entry of both sides, 4 more under the ids) come from the
+ * thread's scratch arena.
+ *
+ * hy_string_dictionary_order_pair / hy_string_dictionary_join_ids   left_* / right_*: one int32_t rank / int64_t id per entry of that side,
+ *   in the layout of hy_string_dictionary_order (chunk c's start at the sum of that side's n_entries before c).  mem == HY_MEM_DEVICE: they
+ *   stay in the caller's device buffers (ranks on 4 bytes, ids on 8, otherwise HY_ERR_INVALID), complete in the order of the calling
+ *   thread's stream.  mem == HY_MEM_HOST: copied back; the call returns when they are there.  n_distinct: HOST memory, may be NULL; when it
+ *   is given the call waits for the stream.  The dictionaries may have different chunk counts; a side without entries is legal; no entries
+ *   on either side: HY_OK, nothing is launched, *n_distinct = 0.  Passing the same dictionary on both sides (a self join) is legal.
+ *   HY_ERR_INVALID: a null argument, a bad mem, dictionaries on different devices or not on the calling thread's.  HY_ERR_UNSUPPORTED: 2^31
+ *   entries or more on both sides together.  All refusals come before any launch and any allocation; nothing is written.
+ *
+ * hy_column_string_join_keys   hy_column_string_ranks for two columns: *left_out / *right_out are the stand-ins of `left` / `right` --
+ *   dictionary columns over the SAME attribute vectors (shared, not copied, at every width and packing) whose aux holds the chunk's ranks
+ *   (HY_STRING_KEYS_RANKS: HY_TYPE_INT) or ids (HY_STRING_KEYS_HASH_IDS: HY_TYPE_LONG), the NULL value id still aux_size; for a reference
+ *   column a reference column over the same PosLists whose referenced column is such a stand-in.  Either side may be a data or a reference
+ *   column, independently; the two columns belong to different tables (or to one).  Lifetime and ownership: hy_column_string_ranks', per
+ *   side -- each stand-in owns its keys, the columns outlive their stand-ins, the dictionaries may be destroyed once the call has returned.
+ *   Refusals: hy_column_string_ranks', per side (HY_ERR_INVALID: a column that is no string column, a dictionary that disagrees with the
+ *   segments' aux_size; HY_ERR_UNSUPPORTED: unencoded or LZ4 string segments), those of the two calls above, and HY_ERR_INVALID for an
+ *   unknown `kind`.  On any error both outputs are NULL and nothing stays allocated.  Keys are not cached between calls: they depend on
+ *   the pair, and every call makes them again. */
+enum { HY_STRING_KEYS_RANKS = 0 /* int32 */, HY_STRING_KEYS_HASH_IDS = 1 /* int64 */ };
+hy_status hy_string_dictionary_order_pair(const hy_string_dictionary* left, const hy_string_dictionary* right, uint32_t mem,
+                                          int32_t* left_ranks, int32_t* right_ranks, uint32_t* n_distinct);
+hy_status hy_string_dictionary_join_ids(const hy_string_dictionary* left, const hy_string_dictionary* right, uint32_t mem,
+                                        int64_t* left_ids, int64_t* right_ids);
+hy_status hy_column_string_join_keys(const hy_column* left, const hy_string_dictionary* left_dict, const hy_column* right,
+                                     const hy_string_dictionary* right_dict, uint32_t kind, hy_column** left_out, hy_column** right_out);
 
 /* ---- String columns made on the device (what AggregateHash's string GROUP BY columns, MIN / MAX / ANY over strings, and the materialised
  * string columns of Sort / Projection need: the way from RowIDs, or from ranks, back to strings) ----------------------------------------
