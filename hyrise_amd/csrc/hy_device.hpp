@@ -223,9 +223,17 @@ hy_status like_dictionary_tables(const hy_string_dictionary* dict);   // ensures
 // queues the matcher on `stream`: d_words[word_offsets[c] + v / 64] bit v % 64 for every entry v of every chunk c (tail bits zero)
 hy_status like_launch(const hy_string_dictionary* dict, const LikeProgram& program, uint64_t* d_words, hipStream_t stream);
 
-// ---- string_order.hip: one column's dictionaries ordered against another's, chunk by chunk (hy_string_dictionary_ranks) --------------
-// Refusals of a (left, right) pair, before any launch: chunk counts, devices, a right chunk of 2^30 entries or more.
+// ---- string_order.hip, string_gather.hip, string_substr.hip, string_join_keys.hip: the operators over string dictionaries ------------------
+// (Scratch and Carver are declared below; every temporary of these files is a block of a *_layout: sizing is a dry run of the layout.)
+struct Scratch;
+struct Carver;
+// The two refusals of a dictionary, before any launch and any allocation: it lives on the calling thread's device; `total` entries fit int32 ranks.
+hy_status dictionary_device_check(const hy_string_dictionary* dict, const char* entry_point);
+hy_status entries_fit_ranks(uint64_t total, const char* entry_point);
+// Refusals of a (left, right) pair ordered chunk by chunk (hy_string_dictionary_ranks): chunk counts, devices, a right chunk of 2^30 entries or more.
 hy_status string_order_check(const hy_string_dictionary* left, const hy_string_dictionary* right, const char* entry_point);
+hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point);   // both refusals above, of a dictionary that is to be ordered
+hy_status string_column_check(const hy_column* column, const hy_string_dictionary* dict, const char* entry_point);   // ... of a string column and its dictionary
 // queues the ranking on `stream`: d_ranks[left->entry_offsets[c] + v] for every entry v of every chunk c of `left`
 hy_status string_order_launch(const hy_string_dictionary* left, const hy_string_dictionary* right, int32_t* d_ranks, hipStream_t stream);
 // The int32 stand-ins of a pair of string columns (hy_table_scan_columns_strings): every segment descriptor of the data columns copied with
@@ -242,29 +250,29 @@ struct StringTwins {
   uint32_t n_data_chunks, n_chunks, n_evens;
 };
 hy_status string_twins_launch(const StringTwins& twins, hipStream_t stream);
-// One column's global string order (hy_string_dictionary_order) for the other translation units: what the launches take from the scratch arena
-// for `total` entries; the refusals of a dictionary (device, E >= 2^31) and of a string column with its dictionary (hy_column_string_ranks'),
-// before any launch; the launch sequence itself -- d_ranks[entry_offsets[c] + v] and *d_n_distinct, carved from `sc`, total > 0.
-struct Scratch;
-hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point);
-hy_status string_column_check(const hy_column* column, const hy_string_dictionary* dict, const char* entry_point);
-// With d_windows (one EntryWindow per entry, at entry_offsets[c] + v) the entries are ordered as their windows read; `sorted_chunks` says that
-// every chunk's windowed entries still ascend (equal neighbours allowed), so that the merge may start from whole chunks as it does without windows.
+// The merge sequence (one column's global string order, hy_string_dictionary_order) for the other translation units: its temporaries for
+// `total` > 0 positions, and the three sequences over them.  *blocks.n_distinct is the number of distinct strings, in device memory.
+struct MergeBlocks {
+  uint64_t* ping;
+  uint64_t* pong;
+  uint32_t* tile_heads;
+  uint32_t* n_distinct;
+};
+void merge_layout(Carver& carver, uint64_t total, MergeBlocks& blocks);
 struct EntryWindow {   // bytes [begin, begin + length) of a dictionary entry
   uint32_t begin;
   uint32_t length;
 };
-size_t order_scratch_bytes(uint64_t total);
-hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream, const EntryWindow* d_windows = nullptr,
-                              bool sorted_chunks = true);
-// string_gather.hip's back end for the other producers of string columns (string_substr.hip).  The output chunks' sizes on the host:
-struct OutChunks {
-  std::vector<uint32_t> sizes;
-  uint32_t chunk_rows = 0;   // 0: the sizes are another column's (uploaded as row_base / vector_at)
-  uint64_t n = 0;
+struct SubstrArguments {
+  int32_t start, length;
 };
-// what gather_entries, the ranking and the front end in front of it carve from the scratch arena (`inverse`: 4 more bytes per source entry)
-size_t gather_scratch_bytes(uint64_t n_source_entries, uint64_t n, uint64_t n_chunks, bool inverse);
+// A window at the entry's first byte (start 0 or 1, or an empty result; no window at all) keeps a sorted run of entries sorted: the merge
+// may start from whole chunks.  Any other window does not, and the merge starts from single positions.
+inline bool windows_keep_order(const SubstrArguments* substr) { return !substr || substr->length <= 0 || substr->start == 0 || substr->start == 1; }
+// d_ranks[entry_offsets[c] + v], total = entry_offsets[n_chunks] > 0.  With d_windows (one EntryWindow per entry, at entry_offsets[c] + v) the
+// entries are ordered as their windows read; `sorted_chunks` says that every chunk's windowed entries still ascend (equal neighbours allowed).
+hy_status column_order_launch(const hy_string_dictionary* dict, const MergeBlocks& blocks, int32_t* d_ranks, hipStream_t stream, const EntryWindow* d_windows = nullptr,
+                              bool sorted_chunks = true);
 // The sparse route (HY_OPT_STRING_SPARSE_GATHER, string_gather.hip): the column read at the rows asked for, the entries they reference -- the
 // SUBSET, U <= min(n, E) of them in ascending entry order -- as a table of (address, length) that the ranking and the back end read instead
 // of the dictionary, and ranks per subset index.  A row's entry is then its index into the table.
@@ -273,38 +281,12 @@ struct SubsetEntry {   // the bytes of a referenced entry, seen through its wind
   uint32_t length;
   uint32_t reserved;
 };
-struct SubstrArguments {
-  int32_t start, length;
-};
-struct SparseSubset {
-  const SubsetEntry* table = nullptr;   // [n]
-  const int32_t* ranks = nullptr;       // [n]: equal strings (of different source chunks, or equal windows) have one rank
-  uint32_t n = 0;                       // U
-};
-bool string_sparse_route(uint64_t n, uint64_t column_rows, uint64_t n_source_entries);   // which route n rows out of such a column take
-size_t sparse_gather_scratch_bytes(uint64_t n_source_entries, uint64_t n_source_chunks, uint64_t n, uint64_t n_chunks);
-// d_entry[i] (n of them): the subset index of the entry that row positions[i] of `column` holds -- positions == nullptr: row i of the column
-// itself -- or -1 (a NULL RowID, one outside the table, a NULL row); *subset: the table and its ranks, carved from `sc`
-// (sparse_gather_scratch_bytes reserved by the caller).  `substr`: the window every entry is seen through, or nullptr.  One 4-byte copy to the host (U).
-hy_status sparse_entries(const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, const SubstrArguments* substr, Scratch& sc,
-                         int32_t* d_entry, hipStream_t stream, const char* name, SparseSubset* subset);
-// string_order.hip: the order of a table of `total` > 0 entries whose chunk runs [d_run_offsets[c], d_run_offsets[c + 1]) each ascend
-// (by_position: they need not -- the merge starts from single positions); d_ranks[i] for table entry i.  Takes order_scratch_bytes(total).
-hy_status table_order_launch(const SubsetEntry* d_table, const uint64_t* d_run_offsets, uint32_t n_chunks, uint64_t total, bool by_position, Scratch& sc, int32_t* d_ranks,
+// the order of a table of `total` > 0 entries whose chunk runs [d_run_offsets[c], d_run_offsets[c + 1]) each ascend (by_position: they need
+// not -- the merge starts from single positions); d_ranks[i] for table entry i
+hy_status table_order_launch(const SubsetEntry* d_table, const uint64_t* d_run_offsets, uint32_t n_chunks, uint64_t total, bool by_position, const MergeBlocks& blocks, int32_t* d_ranks,
                              hipStream_t stream);
-// d_entry: per output row the global entry index into `dict`, or -1; d_ranks: the order of the (windowed) entries, queued on `stream` already
-// (nullptr for a dictionary without entries); d_windows: what of every entry the output holds, or nullptr: all of it.
-// With `subset` (the sparse route) d_entry holds subset indices, d_ranks is indexed by them and the bytes come from the subset's table: d_windows is nullptr.
-hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out, const int32_t* d_entry, const int32_t* d_ranks, const EntryWindow* d_windows, Scratch& sc,
-                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict, const SparseSubset* subset = nullptr);
-hy_status empty_string_results(hy_column** result, hy_string_dictionary** result_dict);   // a column and a dictionary of zero chunks
-// The int32 stand-in of a string column over a table of E int32_t in device memory (entry v of data chunk c reads d_table[entry_offsets[c] + v]):
-// the caller's attribute vectors and PosLists, shared.  A reference column's stand-in owns its data stand-in; the table stays the caller's.
-// data_type HY_TYPE_LONG: a table of E int64_t, an int64 stand-in (the join ids of string_join_keys.hip).
-hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, void* d_table, hy_column** out, uint32_t data_type = HY_TYPE_INT);
-// string_order.hip: the merge sequence over the chunks of two dictionaries laid end to end -- the tables are the caller's, in device memory
-// (chunks [n_chunks], blocks [n_blocks] with joint chunk indices, entry_offsets [n_chunks + 1]); positions below `split` are the left
-// dictionary's.  Takes order_scratch_bytes(total) from `sc`; total > 0.
+// the merge sequence over the chunks of two dictionaries laid end to end -- the tables are the caller's, in device memory (chunks [n_chunks],
+// blocks [n_blocks] with joint chunk indices, entry_offsets [n_chunks + 1]); positions below `split` are the left dictionary's.  total > 0.
 struct PairTables {
   const LikeChunk* chunks;
   const LikeBlock* blocks;
@@ -312,7 +294,57 @@ struct PairTables {
   uint32_t n_chunks, n_blocks;
   uint64_t total, split;
 };
-hy_status pair_order_launch(const PairTables& tables, Scratch& sc, int32_t* d_left_ranks, int32_t* d_right_ranks, uint32_t** d_n_distinct, hipStream_t stream);
+hy_status pair_order_launch(const PairTables& tables, const MergeBlocks& blocks, int32_t* d_left_ranks, int32_t* d_right_ranks, hipStream_t stream);
+// An output in the caller's device memory, or in host memory behind a twin carved from the arena: `parts` of the twin are copied to the
+// host, then *n_distinct (if asked for), and the stream is waited for.  A device output without n_distinct returns without a synchronise:
+// it is complete in the order of the calling thread's stream.
+struct TwinPart {
+  void* host;
+  const void* device;
+  size_t bytes;
+};
+hy_status outputs_to_caller(uint32_t mem, const TwinPart* parts, uint32_t n_parts, const uint32_t* d_n_distinct, uint32_t* n_distinct, hipStream_t stream);
+// The int32 stand-in of a string column over a table of E int32_t in device memory (entry v of data chunk c reads d_table[entry_offsets[c] + v]):
+// the caller's attribute vectors and PosLists, shared.  A reference column's stand-in owns its data stand-in; the table stays the caller's.
+// data_type HY_TYPE_LONG: a table of E int64_t, an int64 stand-in (the join ids of string_join_keys.hip).
+hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* dict, void* d_table, hy_column** out, uint32_t data_type = HY_TYPE_INT);
+// A table of keys of its own allocation and the stand-in over it, which owns the table once it is made (hy_column_string_ranks,
+// hy_column_string_join_keys).  drop(): what a call that gives up does, after it has synchronised -- the stand-in with its table, or the table alone.
+struct KeyColumn {
+  void* d_keys = nullptr;
+  hy_column* stand_in = nullptr;
+  hy_status alloc(size_t bytes);
+  hy_status make_stand_in(const hy_column* column, const hy_string_dictionary* dict, uint32_t data_type);
+  void drop();
+};
+// string_gather.hip: the four producers of string columns (hy_string_column_gather, hy_string_ranks_gather, hy_string_column_substr,
+// hy_string_column_materialize) as one request: resolved once, then run as stages (DESIGN.md sections 4.17 - 4.20).
+struct OutChunks {   // the output chunks' sizes on the host
+  std::vector<uint32_t> sizes;
+  uint32_t chunk_rows = 0;   // 0: the sizes are another column's (uploaded as row_base / vector_at)
+  uint64_t n = 0;
+};
+enum class StringRoute : uint32_t { ColumnRows, RowIds, Ranks, Sparse };   // Sparse: the column read at `positions`, or (nullptr) at its own rows
+struct StringRequest {
+  const char* name = nullptr;                   // the entry point's
+  const hy_column* column = nullptr;            // the string column; Ranks: the int32 column of ranks
+  const hy_string_dictionary* dict = nullptr;
+  const hy_row_id* positions = nullptr;
+  uint64_t n = 0;                               // output rows
+  const SubstrArguments* substr = nullptr;
+  OutChunks out;
+  StringRoute route = StringRoute::ColumnRows;
+  hy_column** result = nullptr;
+  hy_string_dictionary** result_dict = nullptr;
+};
+// Every refusal, and the results without rows (*answered), before anything is allocated or launched.  `route`: ColumnRows, RowIds or Ranks --
+// the resolver turns the first two into Sparse where string_sparse_route says so.  chunk_rows: RowIds only.
+hy_status string_request(StringRoute route, const char* name, const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, uint32_t chunk_rows,
+                         const SubstrArguments* substr, hy_column** result, hy_string_dictionary** result_dict, StringRequest* request, bool* answered);
+hy_status string_request_run(const StringRequest& request);
+// string_substr.hip, for the stages of a request: the windows of every entry; every row's entry from the exported stand-in over 0, 1, 2, ...
+void entry_windows_launch(const hy_string_dictionary* dict, const SubstrArguments& substr, EntryWindow* d_windows, hipStream_t stream);
+void entries_of_rows_launch(const int32_t* values, const uint8_t* nulls, uint64_t n, uint64_t n_source_entries, int32_t* d_entry, hipStream_t stream);
 // scan.hip: `dict` is the string dictionary of `column`'s data column, chunk by chunk, on `column`'s device; `which`: "", "left " or "right "
 hy_status check_dictionary(const hy_string_dictionary* dict, const hy_column* column, const char* which, const char* entry_point);
 
@@ -395,6 +427,16 @@ struct Carver {
   template <typename T>
   T* take(size_t count) { return static_cast<T*>(take_bytes(sizeof(T) * (count ? count : 1))); }
 };
+// The thread's arena sized by a dry run of `layout`, then the layout run against it: one reserve, before any carve, and one check.
+template <typename Layout>
+inline hy_status reserve_and_carve(Layout&& layout) {
+  Carver sizing;
+  layout(sizing);
+  HY_TRY(scratch().reserve(sizing.used));
+  Carver carver{&scratch()};
+  layout(carver);
+  return carver.failed ? fail(HY_ERR_DEVICE, "scratch arena exhausted") : HY_OK;
+}
 
 
 // Temporary device buffers come from a per-thread pool of power-of-two blocks that is reused across calls in stream

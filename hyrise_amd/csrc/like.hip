@@ -286,7 +286,7 @@ hy_status hy_like_matches(const hy_string_dictionary* dict, const char* pattern,
   LikeProgram program;
   HY_TRY(like_program(pattern, pattern_bytes, condition, &program, "hy_like_matches"));
   if (mem == HY_MEM_DEVICE && reinterpret_cast<uintptr_t>(match_words) % 8 != 0) return fail(HY_ERR_INVALID, "hy_like_matches: match_words not on an 8-byte boundary");
-  if (dict->device != this_thread_device()) return fail(HY_ERR_INVALID, "hy_like_matches: the dictionary lives on device %d, the calling thread works on device %d", dict->device, this_thread_device());
+  HY_TRY(dictionary_device_check(dict, "hy_like_matches"));
   const uint64_t total_words = dict->word_offsets[dict->n_chunks];
   if (!total_words) return HY_OK;
   hipStream_t stream = current_stream();

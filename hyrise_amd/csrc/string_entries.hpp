@@ -1,6 +1,6 @@
 // string_entries.hpp -- one dictionary entry as the kernels over string dictionaries read it (string_order.hip: the rankings; string_gather.hip:
-// the gather): where its bytes lie and how many they are, in either chunk layout, and std::string's order of two entries.  Every translation
-// unit that includes this gets its own copy (anonymous namespace).
+// the gather): where its bytes lie and how many they are, in either chunk layout, and std::string's order of two entries; and the scan over
+// tile sums that both run behind their head flags.  Every translation unit that includes this gets its own copy (anonymous namespace).
 #pragma once
 
 #include "hy_device.hpp"
@@ -102,6 +102,34 @@ __device__ __forceinline__ int compare_entries(const Entry& x, const Entry& y) {
     if (p != q) return p < q ? -1 : 1;
   }
   return x.length == y.length ? 0 : x.length < y.length ? -1 : 1;
+}
+
+constexpr uint32_t SCAN_WG = 1024;
+
+// tiles[t] becomes the sum of the tiles before t; *total = the sum of all.  One workgroup: a thread sums a contiguous share, the shares' sums
+// are scanned in LDS, the thread walks its share again.
+template <typename T>
+__global__ __launch_bounds__(SCAN_WG) void scan_tiles(T* tiles, uint32_t n_tiles, T* total) {
+  __shared__ T s_sums[SCAN_WG];
+  const uint32_t share = (n_tiles + SCAN_WG - 1) / SCAN_WG;
+  const uint32_t begin = min(threadIdx.x * share, n_tiles), end = min(begin + share, n_tiles);
+  T sum = 0;
+  for (uint32_t i = begin; i < end; ++i) sum += tiles[i];
+  s_sums[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t step = 1; step < SCAN_WG; step <<= 1) {   // Hillis-Steele, inclusive
+    const T add = threadIdx.x >= step ? s_sums[threadIdx.x - step] : 0;
+    __syncthreads();
+    s_sums[threadIdx.x] += add;
+    __syncthreads();
+  }
+  T running = s_sums[threadIdx.x] - sum;
+  for (uint32_t i = begin; i < end; ++i) {
+    const T here = tiles[i];
+    tiles[i] = running;
+    running += here;
+  }
+  if (threadIdx.x == SCAN_WG - 1) *total = s_sums[SCAN_WG - 1];
 }
 
 }  // namespace

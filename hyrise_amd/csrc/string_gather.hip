@@ -22,7 +22,7 @@
 //      workgroup's stretch of entry starts (staged in LDS while it has at most COPY_TILE entries, else read where they are), gathers from
 //      as many entries as its 16 bytes span -- 8, 4 or 1 source bytes at a time at any byte address, never a byte outside an entry -- and
 //      stores one 16-byte vector.  A 100 kB entry is copied by 6 250 lanes.
-// Temporaries.  Scratch arena: per source entry 16 bytes of ranking (order_scratch_bytes) + 4 of ranks (+ 4 of inverse table for the rank front
+// Temporaries.  Scratch arena: per source entry 16 bytes of ranking (merge_layout) + 4 of ranks (+ 4 of inverse table for the rank front
 // end); per output row 4 (entry) + 4 (tile-local heads) + 4 (output entry's source entry) + 8 (its address) + 8 (tile-local byte sums), per
 // 256 rows 12, per output chunk 20.  Pool blocks: the word sort's 16 bytes per row; for the RowID front end the stand-in's table (4 per
 // source entry) and its export (5 per SOURCE row).  Results: the attribute vectors and null-free segments in one pooled arena owned by the
@@ -30,7 +30,9 @@
 // The sparse route (HY_OPT_STRING_SPARSE_GATHER) is for few rows out of a large column: the column is read AT the rows
 // (sparse_mark: PosLists and attribute vectors of any width or packing in place, no stand-in, no export), the entries they reference are
 // marked in a bitmap over E and compacted into a table of (address, length), only those are ranked (table_order_launch), and the back end
-// reads entries by table index.  Its temporaries follow n and the subset, plus one bit per source entry (sparse_gather_scratch_bytes).
+// reads entries by table index.  Its temporaries follow n and the subset, plus one bit per source entry (sparse_layout, subset_layout).
+// The host side: the four producers of string columns (these two, hy_string_column_substr, hy_string_column_materialize) are one StringRequest,
+// resolved once (string_request) and run as stages (string_request_run): reserve by layout, rank the source, row entries, gather_entries.
 #include "hy_device.hpp"
 #include "sort_words.hpp"
 #include "string_entries.hpp"
@@ -44,7 +46,6 @@ namespace hy {
 namespace {
 
 constexpr uint32_t WG = 256;
-constexpr uint32_t SCAN_WG = 1024;
 constexpr uint32_t COPY_SPAN = 16;      // output bytes per lane: one vector store
 constexpr uint32_t COPY_TILE = 1024;    // entry starts a workgroup stages in LDS (4 KiB of output hold that many entries of 4 bytes)
 
@@ -148,32 +149,6 @@ __global__ __launch_bounds__(WG) void key_heads(OutLayout l, const int32_t* entr
   for (uint32_t w = 0; w < wave; ++w) before += s_wave_heads[w];
   if (p < l.n) local[p] = before + __popcll(ballot & (~0ull >> (63 - lane)));
   if (threadIdx.x == WG - 1) tile_heads[blockIdx.x] = before + s_wave_heads[wave];
-}
-
-// tiles[t] becomes the sum of the tiles before t; *total = the sum of all.  One workgroup: a thread sums a contiguous share, the shares' sums
-// are scanned in LDS, the thread walks its share again.
-template <typename T>
-__global__ __launch_bounds__(SCAN_WG) void scan_tiles(T* tiles, uint32_t n_tiles, T* total) {
-  __shared__ T s_sums[SCAN_WG];
-  const uint32_t share = (n_tiles + SCAN_WG - 1) / SCAN_WG;
-  const uint32_t begin = min(threadIdx.x * share, n_tiles), end = min(begin + share, n_tiles);
-  T sum = 0;
-  for (uint32_t i = begin; i < end; ++i) sum += tiles[i];
-  s_sums[threadIdx.x] = sum;
-  __syncthreads();
-  for (uint32_t step = 1; step < SCAN_WG; step <<= 1) {   // Hillis-Steele, inclusive
-    const T add = threadIdx.x >= step ? s_sums[threadIdx.x - step] : 0;
-    __syncthreads();
-    s_sums[threadIdx.x] += add;
-    __syncthreads();
-  }
-  T running = s_sums[threadIdx.x] - sum;
-  for (uint32_t i = begin; i < end; ++i) {
-    const T here = tiles[i];
-    tiles[i] = running;
-    running += here;
-  }
-  if (threadIdx.x == SCAN_WG - 1) *total = s_sums[SCAN_WG - 1];
 }
 
 // the sum of the first `count` elements of a sequence kept as tile-local inclusive sums and scanned tile sums
@@ -458,233 +433,403 @@ __global__ __launch_bounds__(WG) void sparse_indices(const unsigned long long* b
 
 uint32_t tiles_of(uint64_t items) { return static_cast<uint32_t>((items + WG - 1) / WG); }
 
-// what gather_entries itself carves
-size_t back_end_scratch_bytes(uint64_t n, uint64_t n_chunks) {
-  const uint64_t tiles = tiles_of(n);
-  return 3 * align_up(4 * n + 16, 256) + 2 * align_up(8 * n + 16, 256) + align_up(4 * tiles, 256) + align_up(8 * tiles, 256) + align_up(4 * (n_chunks + 1), 256) +
-         align_up(sizeof(ChunkTotals) * n_chunks, 256) + 2 * align_up(8 * (n_chunks + 1), 256) + 16 * 256 + 4096;
+uint64_t entries_of(const hy_string_dictionary* dict) { return dict->entry_offsets[dict->n_chunks]; }
+
+// Destroys a column when the scope ends (the stand-in of the RowID front end: it lives as long as the launches that read it)
+struct ColumnGuard {
+  hy_column* column = nullptr;
+  ~ColumnGuard() { if (column) (void)hy_column_destroy(column); }
+};
+
+// ---- the temporaries in the scratch arena, as layouts: sizing is a dry run of them ----------------------------------------------------------
+struct SourceBlocks {   // the dense routes: the dictionary ranked
+  int32_t* ranks;         // [E]
+  EntryWindow* windows;   // [E], with SUBSTR
+  uint32_t* inverse;      // [E], the rank front end
+  MergeBlocks merge;
+};
+struct SparseBlocks {   // the sparse front end, before the subset's size is known
+  unsigned long long* bitmap;
+  uint32_t* local;
+  uint32_t* tile_bits;
+  uint32_t* n_subset;
+  uint64_t* run_offsets;
+};
+struct SubsetBlocks {   // ... and behind it
+  SubsetEntry* table;
+  int32_t* ranks;
+  MergeBlocks merge;
+};
+struct BackEndBlocks {
+  uint32_t* local;
+  uint32_t* tile_heads;
+  uint32_t* chunk_first;
+  int32_t* unique_entry;
+  const uint8_t** source;
+  uint64_t* local_bytes;
+  uint64_t* tile_bytes;
+  ChunkTotals* totals;
+  uint32_t* n_unique;
+  uint64_t* total_bytes;
+  uint64_t* row_base;    // the chunks of another column: their first rows and where their vectors begin
+  uint64_t* vector_at;
+};
+struct RequestBlocks {
+  SourceBlocks source;
+  SparseBlocks sparse;
+  SubsetBlocks subset;
+  BackEndBlocks back;
+};
+
+void source_layout(Carver& carver, const StringRequest& rq, SourceBlocks& b) {
+  const uint64_t n_source_entries = entries_of(rq.dict);
+  b = SourceBlocks{};
+  if (rq.route == StringRoute::Ranks) b.inverse = carver.take<uint32_t>(n_source_entries);
+  if (!n_source_entries) return;
+  b.ranks = carver.take<int32_t>(n_source_entries);
+  if (rq.substr) b.windows = carver.take<EntryWindow>(n_source_entries);
+  merge_layout(carver, n_source_entries, b.merge);
 }
 
-}  // namespace
-
-// What gather_entries and the front ends in front of it carve from the scratch arena
-size_t gather_scratch_bytes(uint64_t n_source_entries, uint64_t n, uint64_t n_chunks, bool inverse) {
-  return (n_source_entries ? order_scratch_bytes(n_source_entries) : 0) + (inverse ? 2 : 1) * align_up(4 * n_source_entries + 16, 256) + back_end_scratch_bytes(n, n_chunks);
+// one bit per source entry with 4 bytes of counts per 64 entries, per source chunk 8 -- nothing else that grows with E or the column's rows
+void sparse_layout(Carver& carver, const hy_string_dictionary* dict, SparseBlocks& b) {
+  const uint64_t n_words = entries_of(dict) / 64 + 1;
+  b.bitmap = carver.take<unsigned long long>(n_words);
+  b.local = carver.take<uint32_t>(n_words);
+  b.tile_bits = carver.take<uint32_t>(tiles_of(n_words));
+  b.n_subset = carver.take<uint32_t>(1);
+  b.run_offsets = carver.take<uint64_t>(size_t{dict->n_chunks} + 1);
 }
 
-// Which route n rows out of a column of `column_rows` rows and E entries take: column_rows + E is what the dense route reads whatever n is
-bool string_sparse_route(uint64_t n, uint64_t column_rows, uint64_t n_source_entries) {
-  const int64_t mode = option(HY_OPT_STRING_SPARSE_GATHER);
-  if (mode == 2) return true;
-  if (mode != 1 || STRING_SPARSE_DIVISOR <= 0) return false;
-  return n <= (column_rows + n_source_entries) / static_cast<uint64_t>(STRING_SPARSE_DIVISOR);
+// per subset entry 16 bytes of table, 4 of ranks and the merge's 16; sized at the bound min(n, E), carved at the U the device counted
+void subset_layout(Carver& carver, uint64_t n_subset, SubsetBlocks& b) {
+  b = SubsetBlocks{};
+  if (!n_subset) return;
+  b.table = carver.take<SubsetEntry>(n_subset);
+  b.ranks = carver.take<int32_t>(n_subset);
+  merge_layout(carver, n_subset, b.merge);
 }
 
-// What sparse_entries and gather_entries behind it carve: the bitmap (one bit per source entry) with 4 bytes of counts per 64 entries, per
-// subset entry (U <= min(n, E)) 16 of table + 4 of ranks + 16 of ranking, per source chunk 8 -- nothing else that grows with E or the column's rows
-size_t sparse_gather_scratch_bytes(uint64_t n_source_entries, uint64_t n_source_chunks, uint64_t n, uint64_t n_chunks) {
-  const uint64_t n_words = n_source_entries / 64 + 1, n_subset = std::min(n, n_source_entries);
-  return align_up(8 * n_words, 256) + align_up(4 * n_words, 256) + align_up(4 * tiles_of(n_words), 256) + 256 + align_up(8 * (n_source_chunks + 1), 256) +
-         align_up(sizeof(SubsetEntry) * n_subset + 16, 256) + align_up(4 * n_subset + 16, 256) + (n_subset ? order_scratch_bytes(n_subset) : 0) + back_end_scratch_bytes(n, n_chunks) + 4096;
+void back_end_layout(Carver& carver, const OutChunks& out, BackEndBlocks& b) {
+  const uint64_t n = out.n, n_chunks = out.sizes.size(), n_tiles = tiles_of(n);
+  b.local = carver.take<uint32_t>(n);
+  b.tile_heads = carver.take<uint32_t>(n_tiles);
+  b.chunk_first = carver.take<uint32_t>(n_chunks + 1);
+  b.unique_entry = carver.take<int32_t>(n);
+  b.source = carver.take<const uint8_t*>(n);
+  b.local_bytes = carver.take<uint64_t>(n);
+  b.tile_bytes = carver.take<uint64_t>(n_tiles);
+  b.totals = carver.take<ChunkTotals>(n_chunks);
+  b.n_unique = carver.take<uint32_t>(1);
+  b.total_bytes = carver.take<uint64_t>(1);
+  b.row_base = out.chunk_rows ? nullptr : carver.take<uint64_t>(n_chunks + 1);
+  b.vector_at = out.chunk_rows ? nullptr : carver.take<uint64_t>(n_chunks + 1);
 }
 
-hy_status sparse_entries(const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, const SubstrArguments* substr, Scratch& sc,
-                         int32_t* d_entry, hipStream_t stream, const char* name, SparseSubset* subset) {
-  *subset = SparseSubset{};
-  const uint64_t n_source_entries = dict->entry_offsets[dict->n_chunks];
-  const uint32_t n_words = static_cast<uint32_t>(n_source_entries / 64 + 1), n_word_tiles = tiles_of(n_words);
-  unsigned long long* bitmap = carve<unsigned long long>(sc, n_words);
-  uint32_t* local = carve<uint32_t>(sc, n_words);
-  uint32_t* tile_bits = carve<uint32_t>(sc, n_word_tiles);
-  uint32_t* d_n_subset = carve<uint32_t>(sc, 1);
-  uint64_t* run_offsets = carve<uint64_t>(sc, size_t{dict->n_chunks} + 1);
-  if (!bitmap || !local || !tile_bits || !d_n_subset || !run_offsets) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-  auto check = [&](hipError_t err) { return err == hipSuccess ? HY_OK : fail(HY_ERR_DEVICE, "%s: %s", name, hipGetErrorString(err)); };
-  const hy_column* data_column = column->is_reference ? column->ref : column;
-  const RowSource src{column->d_segments, column->d_row_base, dict->d_entry_offsets, column->n_chunks, data_column ? data_column->n_chunks : 0};
-  profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the front end: a bracket of its own)
-  hy_status st = check(hipMemsetAsync(bitmap, 0, 8 * size_t{n_words}, stream));
-  uint32_t n_subset = 0;
-  if (st == HY_OK) {
-    hipLaunchKernelGGL(sparse_mark, dim3(grid_for(n)), dim3(WG), 0, stream, src, positions, static_cast<uint32_t>(n), d_entry, bitmap);
-    hipLaunchKernelGGL(sparse_count, dim3(n_word_tiles), dim3(WG), 0, stream, bitmap, n_words, local, tile_bits);
-    hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_bits, n_word_tiles, d_n_subset);
-    st = check(hipGetLastError());
-    if (st == HY_OK) st = check(hipMemcpyAsync(&n_subset, d_n_subset, 4, hipMemcpyDeviceToHost, stream));
-    if (st == HY_OK) st = check(hipStreamSynchronize(stream));
+void request_layout(Carver& carver, const StringRequest& rq, uint64_t n_subset, RequestBlocks& b) {
+  if (rq.route == StringRoute::Sparse) {
+    sparse_layout(carver, rq.dict, b.sparse);
+    subset_layout(carver, n_subset, b.subset);
+  } else {
+    source_layout(carver, rq, b.source);
   }
-  if (st == HY_OK && n_subset > std::min(n, n_source_entries)) st = fail(HY_ERR_DEVICE, "%s: %u entries marked by %llu rows", name, n_subset, static_cast<unsigned long long>(n));
-  SubsetEntry* table = nullptr;
-  int32_t* ranks = nullptr;
-  if (st == HY_OK && n_subset) {   // (none: every row is NULL, every entry -1 already)
-    table = carve<SubsetEntry>(sc, n_subset);
-    ranks = carve<int32_t>(sc, n_subset);
-    if (!table || !ranks) st = fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  back_end_layout(carver, rq.out, b.back);
+}
+
+// Stage 1: the arena sized for the whole request (the subset at its bound), then everything carved that does not wait for the subset's size
+hy_status reserve_request(const StringRequest& rq, RequestBlocks& blocks) {
+  Carver sizing;
+  request_layout(sizing, rq, std::min(rq.n, entries_of(rq.dict)), blocks);
+  HY_TRY(scratch().reserve(sizing.used));
+  Carver carver{&scratch()};
+  request_layout(carver, rq, 0, blocks);
+  return carver.failed ? fail(HY_ERR_DEVICE, "scratch arena exhausted") : HY_OK;
+}
+
+// The pool blocks of the front ends: the stand-in's table and its export (RowIDs, rows), the export of the ranks, every row's entry
+struct FrontBuffers {
+  DeviceBuffer table, values, nulls, entry;
+  ColumnGuard stand_in;
+  hy_status alloc(const StringRequest& rq) {
+    if (rq.route != StringRoute::Sparse) {
+      if (rq.route != StringRoute::Ranks) HY_TRY(table.alloc(4 * entries_of(rq.dict) + 16));
+      HY_TRY(values.alloc(4 * rq.column->rows + 16));
+      HY_TRY(nulls.alloc(rq.column->rows + 16));
+    }
+    return entry.alloc(4 * rq.n + 16);
   }
-  if (st == HY_OK && n_subset) {
-    const SubstrArguments window = substr ? *substr : SubstrArguments{0, 0};
-    hipLaunchKernelGGL(sparse_table, dim3(std::min<uint32_t>(tiles_of(n_words), 4096)), dim3(WG), 0, stream, bitmap, n_words, local, tile_bits, dict->d_chunks, dict->d_entry_offsets,
-                       dict->n_chunks, substr != nullptr, window, n_subset, table);
-    hipLaunchKernelGGL(sparse_indices, dim3(grid_for(std::max<uint64_t>(n, uint64_t{dict->n_chunks} + 1))), dim3(WG), 0, stream, bitmap, local, tile_bits, dict->d_entry_offsets,
-                       dict->n_chunks, static_cast<uint32_t>(n), d_entry, run_offsets);
-    st = check(hipGetLastError());
-  }
-  profile_end(stream);
-  if (st == HY_OK && n_subset) {
-    // a window at the entry's first byte keeps a sorted run sorted; single positions also where they are fewer than the chunks (fewer rounds)
-    const bool sorted_runs = !substr || substr->length <= 0 || substr->start == 0 || substr->start == 1;
-    st = table_order_launch(table, run_offsets, dict->n_chunks, n_subset, !sorted_runs || n_subset < dict->n_chunks, sc, ranks, stream);
-  }
-  if (st != HY_OK) {   // (launches may be queued: the temporaries go back to the pool behind them)
-    (void)hipStreamSynchronize(stream);
-    return st;
-  }
-  subset->table = table;
-  subset->ranks = ranks;
-  subset->n = n_subset;
+};
+
+// What the back end reads of the source: the dictionary with its order (d_ranks: nullptr for a dictionary without entries) and, with SUBSTR, what
+// of every entry the output holds; or -- `subset`, the sparse route -- a table of the referenced entries with its order, windows applied already.
+struct SparseSubset {
+  const SubsetEntry* table = nullptr;   // [n]
+  const int32_t* ranks = nullptr;       // [n]: equal strings (of different source chunks, or equal windows) have one rank
+  uint32_t n = 0;                       // U
+};
+struct RankedSource {
+  const hy_string_dictionary* dict;
+  const int32_t* d_ranks;
+  const EntryWindow* d_windows;
+  const SparseSubset* subset;
+};
+
+hy_status device_status(hipError_t err, const char* name) { return err == hipSuccess ? HY_OK : fail(HY_ERR_DEVICE, "%s: %s", name, hipGetErrorString(err)); }
+
+// Stage 2, dense routes: the windows, then the dictionary's order as they read.  A dictionary without entries has neither.
+hy_status rank_dictionary(const StringRequest& rq, const SourceBlocks& b, hipStream_t stream, RankedSource* source) {
+  if (!entries_of(rq.dict)) return HY_OK;
+  if (rq.substr) entry_windows_launch(rq.dict, *rq.substr, b.windows, stream);
+  HY_TRY(column_order_launch(rq.dict, b.merge, b.ranks, stream, b.windows, windows_keep_order(rq.substr)));
+  source->d_ranks = b.ranks;
+  source->d_windows = b.windows;
   return HY_OK;
 }
 
-// The back end.  d_entry: per output row the global entry index into `dict`, or -1; d_ranks: the dictionary's order (column_order_launch), queued
-// on `stream` already (nullptr for a dictionary without entries); d_windows: what of every entry the output holds, ranked as such, or nullptr.  The arena `sc` is reserved by the caller (gather_scratch_bytes).
-hy_status gather_entries(const hy_string_dictionary* dict, const OutChunks& out, const int32_t* d_entry, const int32_t* d_ranks, const EntryWindow* d_windows, Scratch& sc,
-                         hipStream_t stream, const char* name, hy_column** result, hy_string_dictionary** result_dict, const SparseSubset* subset) {
-  const uint32_t n = static_cast<uint32_t>(out.n);
-  const uint32_t n_chunks = static_cast<uint32_t>(out.sizes.size());
-  // (what the ranks run below and d_entry indexes: the dictionary's entries, or the subset's)
-  const uint32_t n_source_entries = subset ? subset->n : static_cast<uint32_t>(dict->entry_offsets[dict->n_chunks]);
-  const uint32_t n_tiles = tiles_of(n);
+// Stage 3, rows of the column or at RowIDs: the column's stand-in over 0, 1, 2, ... exported -- every source row's global entry index --
+// then one lookup per output row
+hy_status stand_in_entries(const StringRequest& rq, FrontBuffers& f, hipStream_t stream) {
+  const uint64_t n_source_entries = entries_of(rq.dict);
+  hy_status st = string_stand_in(rq.column, rq.dict, f.table.as<int32_t>(), &f.stand_in.column);
+  profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the front end: a bracket of its own)
+  if (st == HY_OK && n_source_entries) hipLaunchKernelGGL(iota_table, dim3(grid_for(n_source_entries)), dim3(WG), 0, stream, f.table.as<int32_t>(), static_cast<uint32_t>(n_source_entries));
+  if (st == HY_OK && rq.n) st = export_column_at(f.stand_in.column, f.values.ptr, f.nulls.as<uint8_t>(), nullptr);
+  if (st == HY_OK && rq.n && rq.route == StringRoute::RowIds)
+    hipLaunchKernelGGL(entries_at_positions, dim3(grid_for(rq.n)), dim3(WG), 0, stream, f.values.as<int32_t>(), f.nulls.as<uint8_t>(), rq.column->d_row_base, rq.column->n_chunks, rq.positions,
+                       static_cast<uint32_t>(rq.n), static_cast<uint32_t>(n_source_entries), f.entry.as<int32_t>());
+  else if (st == HY_OK && rq.n) entries_of_rows_launch(f.values.as<int32_t>(), f.nulls.as<uint8_t>(), rq.n, n_source_entries, f.entry.as<int32_t>(), stream);
+  profile_end(stream);
+  return st;
+}
 
-  // the attribute vectors: one pooled arena, chunk c's vector 256-byte aligned with 16 bytes of slack (hy_column_gather's layout)
-  std::vector<uint64_t> row_base(size_t{n_chunks} + 1, 0), vector_at(size_t{n_chunks} + 1, 0);
-  for (uint32_t c = 0; c < n_chunks; ++c) {
-    row_base[c + 1] = row_base[c] + out.sizes[c];
-    vector_at[c + 1] = vector_at[c] + align_up(4 * uint64_t{out.sizes[c]} + 16, 256);
+// Stage 3, ranks: the inverse table rank -> smallest entry with that rank, then one lookup per row of the exported ranks
+hy_status rank_entries(const StringRequest& rq, const SourceBlocks& b, FrontBuffers& f, hipStream_t stream) {
+  const uint64_t n_source_entries = entries_of(rq.dict);
+  hy_status st = HY_OK;
+  profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the front end: a bracket of its own)
+  if (n_source_entries) {
+    st = device_status(hipMemsetAsync(b.inverse, 0xFF, 4 * n_source_entries, stream), rq.name);
+    if (st == HY_OK) hipLaunchKernelGGL(inverse_ranks, dim3(grid_for(n_source_entries)), dim3(WG), 0, stream, b.ranks, static_cast<uint32_t>(n_source_entries), b.inverse);
   }
+  if (st == HY_OK && rq.n) st = export_column_at(rq.column, f.values.ptr, f.nulls.as<uint8_t>(), nullptr);
+  if (st == HY_OK && rq.n)
+    hipLaunchKernelGGL(entries_of_ranks, dim3(grid_for(rq.n)), dim3(WG), 0, stream, f.values.as<int32_t>(), f.nulls.as<uint8_t>(), b.inverse, static_cast<uint32_t>(rq.n),
+                       static_cast<uint32_t>(n_source_entries), f.entry.as<int32_t>());
+  profile_end(stream);
+  return st;
+}
+
+// Stage 3, sparse: the column read at the rows, the entries they reference marked and counted; *n_subset = U crosses to the host (4 bytes)
+hy_status sparse_mark_and_count(const StringRequest& rq, const SparseBlocks& b, int32_t* d_entry, hipStream_t stream, uint32_t* n_subset) {
+  const uint64_t n_source_entries = entries_of(rq.dict);
+  const uint32_t n_words = static_cast<uint32_t>(n_source_entries / 64 + 1), n_word_tiles = tiles_of(n_words);
+  const hy_column* data_column = rq.column->is_reference ? rq.column->ref : rq.column;
+  const RowSource src{rq.column->d_segments, rq.column->d_row_base, rq.dict->d_entry_offsets, rq.column->n_chunks, data_column ? data_column->n_chunks : 0};
+  HY_TRY(device_status(hipMemsetAsync(b.bitmap, 0, 8 * size_t{n_words}, stream), rq.name));
+  hipLaunchKernelGGL(sparse_mark, dim3(grid_for(rq.n)), dim3(WG), 0, stream, src, rq.positions, static_cast<uint32_t>(rq.n), d_entry, b.bitmap);
+  hipLaunchKernelGGL(sparse_count, dim3(n_word_tiles), dim3(WG), 0, stream, b.bitmap, n_words, b.local, b.tile_bits);
+  hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, b.tile_bits, n_word_tiles, b.n_subset);
+  HY_TRY(device_status(hipGetLastError(), rq.name));
+  HY_TRY(device_status(hipMemcpyAsync(n_subset, b.n_subset, 4, hipMemcpyDeviceToHost, stream), rq.name));
+  HY_TRY(device_status(hipStreamSynchronize(stream), rq.name));
+  if (*n_subset > std::min(rq.n, n_source_entries)) return fail(HY_ERR_DEVICE, "%s: %u entries marked by %llu rows", rq.name, *n_subset, static_cast<unsigned long long>(rq.n));
+  return HY_OK;
+}
+
+// ... the subset's table, every row's index into it, and (stage 2 of this route) the subset ranked.  U == 0: every row is NULL, every entry -1 already.
+hy_status sparse_entries(const StringRequest& rq, RequestBlocks& blocks, int32_t* d_entry, hipStream_t stream, SparseSubset* subset) {
+  const SparseBlocks& b = blocks.sparse;
+  const hy_string_dictionary* dict = rq.dict;
+  const uint32_t n_words = static_cast<uint32_t>(entries_of(dict) / 64 + 1);
+  uint32_t n_subset = 0;
+  profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the front end: a bracket of its own)
+  hy_status st = sparse_mark_and_count(rq, b, d_entry, stream, &n_subset);
+  if (st == HY_OK && n_subset) {
+    Carver carver{&scratch()};
+    subset_layout(carver, n_subset, blocks.subset);
+    if (carver.failed) st = fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  }
+  if (st == HY_OK && n_subset) {
+    const SubstrArguments window = rq.substr ? *rq.substr : SubstrArguments{0, 0};
+    hipLaunchKernelGGL(sparse_table, dim3(std::min<uint32_t>(tiles_of(n_words), 4096)), dim3(WG), 0, stream, b.bitmap, n_words, b.local, b.tile_bits, dict->d_chunks, dict->d_entry_offsets,
+                       dict->n_chunks, rq.substr != nullptr, window, n_subset, blocks.subset.table);
+    hipLaunchKernelGGL(sparse_indices, dim3(grid_for(std::max<uint64_t>(rq.n, uint64_t{dict->n_chunks} + 1))), dim3(WG), 0, stream, b.bitmap, b.local, b.tile_bits, dict->d_entry_offsets,
+                       dict->n_chunks, static_cast<uint32_t>(rq.n), d_entry, b.run_offsets);
+    st = device_status(hipGetLastError(), rq.name);
+  }
+  profile_end(stream);
+  if (st != HY_OK || !n_subset) return st;
+  // sorted runs stay runs; single positions where a window unsorts them, and where the entries are fewer than the chunks (fewer rounds)
+  HY_TRY(table_order_launch(blocks.subset.table, b.run_offsets, dict->n_chunks, n_subset, !windows_keep_order(rq.substr) || n_subset < dict->n_chunks, blocks.subset.merge,
+                            blocks.subset.ranks, stream));
+  *subset = SparseSubset{blocks.subset.table, blocks.subset.ranks, n_subset};
+  return HY_OK;
+}
+
+// ---- stage 4, the back end -----------------------------------------------------------------------------------------------------------------
+// The results' own memory -- the pooled arena of the attribute vectors (chunk c's vector 256-byte aligned with 16 bytes of slack,
+// hy_column_gather's layout) and the dictionary's block of offsets and chars -- given back unless the results took it
+struct ResultMemory {
   char* arena = nullptr;
   size_t arena_capacity = 0;
-  HY_TRY(pool_acquire(vector_at[n_chunks] + 256, reinterpret_cast<void**>(&arena), &arena_capacity));
   void* dictionary_block = nullptr;
-  auto release = [&](hy_status status) {
-    profile_end(stream);
-    (void)hipStreamSynchronize(stream);
-    pool_release(arena, arena_capacity);
+  ~ResultMemory() {
+    if (arena) pool_release(arena, arena_capacity);
     if (dictionary_block) (void)hipFree(dictionary_block);
-    return status;
-  };
-  auto check = [&](hipError_t err) { return err == hipSuccess ? HY_OK : fail(HY_ERR_DEVICE, "%s: %s", name, hipGetErrorString(err)); };
+  }
+};
 
-  OutLayout layout{nullptr, nullptr, n_chunks ? vector_at[1] : 0, out.chunk_rows, n_chunks, n};
-  uint32_t* local = carve<uint32_t>(sc, n);
-  uint32_t* tile_heads = carve<uint32_t>(sc, n_tiles);
-  uint32_t* chunk_first = carve<uint32_t>(sc, size_t{n_chunks} + 1);
-  int32_t* unique_entry = carve<int32_t>(sc, n);
-  const uint8_t** source = carve<const uint8_t*>(sc, n);
-  uint64_t* local_bytes = carve<uint64_t>(sc, n);
-  uint64_t* tile_bytes = carve<uint64_t>(sc, n_tiles);
-  ChunkTotals* d_totals = carve<ChunkTotals>(sc, n_chunks);
-  uint32_t* d_n_unique = carve<uint32_t>(sc, 1);
-  uint64_t* d_total_bytes = carve<uint64_t>(sc, 1);
-  uint64_t* d_row_base = out.chunk_rows ? nullptr : carve<uint64_t>(sc, size_t{n_chunks} + 1);
-  uint64_t* d_vector_at = out.chunk_rows ? nullptr : carve<uint64_t>(sc, size_t{n_chunks} + 1);
-  if (!local || !tile_heads || !chunk_first || !unique_entry || !source || !local_bytes || !tile_bytes || !d_totals || !d_n_unique || !d_total_bytes ||
-      (!out.chunk_rows && (!d_row_base || !d_vector_at)))
-    return release(fail(HY_ERR_DEVICE, "scratch arena exhausted"));
-  if (!out.chunk_rows) {
-    hy_status st = check(hipMemcpyAsync(d_row_base, row_base.data(), 8 * row_base.size(), hipMemcpyHostToDevice, stream));
-    if (st == HY_OK) st = check(hipMemcpyAsync(d_vector_at, vector_at.data(), 8 * vector_at.size(), hipMemcpyHostToDevice, stream));
-    if (st == HY_OK) st = check(hipStreamSynchronize(stream));   // (the host vectors are pageable)
-    if (st != HY_OK) return release(st);
-    layout.row_base = d_row_base;
-    layout.vector_at = d_vector_at;
+struct Gather {
+  const StringRequest& rq;
+  const RankedSource& source;
+  const int32_t* d_entry;
+  const BackEndBlocks& b;
+  hipStream_t stream;
+  const uint32_t n, n_chunks, n_tiles;
+  const uint32_t n_source_entries;   // what the ranks run below and d_entry indexes: the dictionary's entries, or the subset's
+  std::vector<uint64_t> row_base, vector_at;
+  std::vector<ChunkTotals> totals;   // (chunks without rows -- a column of empty chunks -- have no entries: nothing is launched for them)
+  OutLayout layout{};
+  WordSort order;
+  ResultMemory memory;
+  uint64_t n_unique = 0, total_bytes = 0;
+  uint32_t* d_offsets = nullptr;
+  uint8_t* d_chars = nullptr;
+
+  Gather(const StringRequest& request, const RankedSource& ranked, const int32_t* entry, const BackEndBlocks& blocks, hipStream_t on)
+      : rq(request), source(ranked), d_entry(entry), b(blocks), stream(on), n(static_cast<uint32_t>(request.out.n)), n_chunks(static_cast<uint32_t>(request.out.sizes.size())),
+        n_tiles(tiles_of(request.out.n)), n_source_entries(ranked.subset ? ranked.subset->n : static_cast<uint32_t>(entries_of(ranked.dict))), row_base(size_t{n_chunks} + 1, 0),
+        vector_at(size_t{n_chunks} + 1, 0), totals(n_chunks) {}
+
+  hy_status check(hipError_t err) const { return device_status(err, rq.name); }
+
+  // where every output chunk's rows and attribute vector begin; the arena; for the chunks of another column the two tables uploaded
+  hy_status output_layout() {
+    const OutChunks& out = rq.out;
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+      row_base[c + 1] = row_base[c] + out.sizes[c];
+      vector_at[c + 1] = vector_at[c] + align_up(4 * uint64_t{out.sizes[c]} + 16, 256);
+    }
+    HY_TRY(pool_acquire(vector_at[n_chunks] + 256, reinterpret_cast<void**>(&memory.arena), &memory.arena_capacity));
+    layout = OutLayout{nullptr, nullptr, n_chunks ? vector_at[1] : 0, out.chunk_rows, n_chunks, n};
+    if (out.chunk_rows) return HY_OK;
+    HY_TRY(check(hipMemcpyAsync(b.row_base, row_base.data(), 8 * row_base.size(), hipMemcpyHostToDevice, stream)));
+    HY_TRY(check(hipMemcpyAsync(b.vector_at, vector_at.data(), 8 * vector_at.size(), hipMemcpyHostToDevice, stream)));
+    HY_TRY(check(hipStreamSynchronize(stream)));   // (the host vectors are pageable)
+    layout.row_base = b.row_base;
+    layout.vector_at = b.vector_at;
+    return HY_OK;
   }
 
   // 2: the rows by (output chunk, rank)
-  WordSort order;
-  hy_status st = order.alloc(n);
-  if (st != HY_OK) return release(st);
-  std::vector<ChunkTotals> totals(n_chunks);   // (chunks without rows -- a column of empty chunks -- have no entries: nothing is launched for them)
-  if (n) {
-  profile_begin(stream, HY_KERNEL_STRING_RANK);
-  hipLaunchKernelGGL(rank_words, dim3(grid_for(n)), dim3(WG), 0, stream, d_entry, d_ranks, n_source_entries, n, order.key_words(), order.ids());
-  st = order.sort(n, n_source_entries ? 32 - static_cast<uint32_t>(__builtin_clz(n_source_entries)) : 0, stream);
-  if (st == HY_OK && n_chunks > 1) {
+  hy_status order_rows() {
+    hipLaunchKernelGGL(rank_words, dim3(grid_for(n)), dim3(WG), 0, stream, d_entry, source.d_ranks, n_source_entries, n, order.key_words(), order.ids());
+    HY_TRY(order.sort(n, n_source_entries ? 32 - static_cast<uint32_t>(__builtin_clz(n_source_entries)) : 0, stream));
+    if (n_chunks == 1) return HY_OK;
     hipLaunchKernelGGL(chunk_words, dim3(grid_for(n)), dim3(WG), 0, stream, layout, order.perm, order.key_words());
-    st = order.sort(n, 32 - static_cast<uint32_t>(__builtin_clz(n_chunks - 1)), stream);
+    return order.sort(n, 32 - static_cast<uint32_t>(__builtin_clz(n_chunks - 1)), stream);
   }
-  if (st != HY_OK) return release(st);
-  // 3 and 4
-  hipLaunchKernelGGL(key_heads, dim3(n_tiles), dim3(WG), 0, stream, layout, d_entry, d_ranks, n_source_entries, order.perm, local, tile_heads);
-  hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_heads, n_tiles, d_n_unique);
-  hipLaunchKernelGGL(chunk_firsts, dim3(tiles_of(uint64_t{n_chunks} + 1)), dim3(WG), 0, stream, layout, local, tile_heads, chunk_first);
-  hipLaunchKernelGGL(value_ids, dim3(n_tiles), dim3(WG), 0, stream, layout, d_entry, order.perm, local, tile_heads, chunk_first, arena, unique_entry);
-  hipLaunchKernelGGL(unique_lengths, dim3(n_tiles), dim3(WG), 0, stream, dict->d_chunks, dict->d_entry_offsets, dict->n_chunks, d_windows,
-                     subset ? subset->table : nullptr, subset ? subset->n : 0, unique_entry, d_n_unique, source, local_bytes, tile_bytes);
-  hipLaunchKernelGGL(scan_tiles<uint64_t>, dim3(1), dim3(SCAN_WG), 0, stream, tile_bytes, n_tiles, d_total_bytes);
-  hipLaunchKernelGGL(chunk_totals, dim3(tiles_of(n_chunks)), dim3(WG), 0, stream, chunk_first, n_chunks, local_bytes, tile_bytes, d_totals);
-  st = check(hipGetLastError());
-  if (st == HY_OK) st = check(hipMemcpyAsync(totals.data(), d_totals, sizeof(ChunkTotals) * n_chunks, hipMemcpyDeviceToHost, stream));
-  if (st == HY_OK) st = check(hipStreamSynchronize(stream));
-  if (st != HY_OK) return release(st);
+
+  // 3: heads and value ids
+  void heads_and_value_ids() {
+    hipLaunchKernelGGL(key_heads, dim3(n_tiles), dim3(WG), 0, stream, layout, d_entry, source.d_ranks, n_source_entries, order.perm, b.local, b.tile_heads);
+    hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, b.tile_heads, n_tiles, b.n_unique);
+    hipLaunchKernelGGL(chunk_firsts, dim3(tiles_of(uint64_t{n_chunks} + 1)), dim3(WG), 0, stream, layout, b.local, b.tile_heads, b.chunk_first);
+    hipLaunchKernelGGL(value_ids, dim3(n_tiles), dim3(WG), 0, stream, layout, d_entry, order.perm, b.local, b.tile_heads, b.chunk_first, memory.arena, b.unique_entry);
   }
-  uint64_t n_unique = 0, total_bytes = 0;
-  for (uint32_t c = 0; c < n_chunks; ++c) {
-    if (totals[c].chars_bytes >= (uint64_t{1} << 32))
-      return release(fail(HY_ERR_UNSUPPORTED, "%s: output chunk %u: %llu bytes of chars do not fit 32-bit offsets", name, c, static_cast<unsigned long long>(totals[c].chars_bytes)));
-    n_unique += totals[c].n_entries;
-    total_bytes += totals[c].chars_bytes;
+
+  // 4: every output entry's bytes, and per output chunk the entry count and the chars' bytes to the host in ONE copy
+  hy_status entry_bytes() {
+    const SparseSubset* subset = source.subset;
+    hipLaunchKernelGGL(unique_lengths, dim3(n_tiles), dim3(WG), 0, stream, source.dict->d_chunks, source.dict->d_entry_offsets, source.dict->n_chunks, source.d_windows,
+                       subset ? subset->table : nullptr, subset ? subset->n : 0, b.unique_entry, b.n_unique, b.source, b.local_bytes, b.tile_bytes);
+    hipLaunchKernelGGL(scan_tiles<uint64_t>, dim3(1), dim3(SCAN_WG), 0, stream, b.tile_bytes, n_tiles, b.total_bytes);
+    hipLaunchKernelGGL(chunk_totals, dim3(tiles_of(n_chunks)), dim3(WG), 0, stream, b.chunk_first, n_chunks, b.local_bytes, b.tile_bytes, b.totals);
+    HY_TRY(check(hipGetLastError()));
+    HY_TRY(check(hipMemcpyAsync(totals.data(), b.totals, sizeof(ChunkTotals) * n_chunks, hipMemcpyDeviceToHost, stream)));
+    return check(hipStreamSynchronize(stream));
   }
-  // 5: offsets and chars, one allocation the dictionary owns
-  const size_t offsets_bytes = align_up(4 * (n_unique + n_chunks) + 16, 256);
-  st = check(hipMalloc(&dictionary_block, offsets_bytes + align_up(total_bytes + 2 * COPY_SPAN, 256)));
-  if (st != HY_OK) { dictionary_block = nullptr; return release(st); }
-  uint32_t* d_offsets = static_cast<uint32_t*>(dictionary_block);
-  uint8_t* d_chars = static_cast<uint8_t*>(dictionary_block) + offsets_bytes;
-  if (n) hipLaunchKernelGGL(dictionary_offsets, dim3(tiles_of(std::max<uint64_t>(n_unique, n_chunks))), dim3(WG), 0, stream, chunk_first, n_chunks, local_bytes, tile_bytes,
-                            static_cast<uint32_t>(n_unique), d_offsets);
-  else st = check(hipMemsetAsync(d_offsets, 0, offsets_bytes, stream));   // (every chunk's one offset)
-  if (st != HY_OK) return release(st);
-  if (total_bytes)
-    hipLaunchKernelGGL(copy_entry_bytes, dim3(static_cast<uint32_t>((total_bytes + WG * COPY_SPAN - 1) / (WG * COPY_SPAN))), dim3(WG), 0, stream, source, local_bytes, tile_bytes,
-                       static_cast<uint32_t>(n_unique), total_bytes, d_chars);
-  profile_end(stream);
-  st = check(hipGetLastError());
-  if (st == HY_OK) st = check(hipStreamSynchronize(stream));
-  if (st != HY_OK) return release(st);
+
+  // 5: offsets and chars, one allocation that the dictionary will own
+  hy_status dictionary_block() {
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+      if (totals[c].chars_bytes >= (uint64_t{1} << 32))
+        return fail(HY_ERR_UNSUPPORTED, "%s: output chunk %u: %llu bytes of chars do not fit 32-bit offsets", rq.name, c, static_cast<unsigned long long>(totals[c].chars_bytes));
+      n_unique += totals[c].n_entries;
+      total_bytes += totals[c].chars_bytes;
+    }
+    const size_t offsets_bytes = align_up(4 * (n_unique + n_chunks) + 16, 256);
+    const hy_status allocated = check(hipMalloc(&memory.dictionary_block, offsets_bytes + align_up(total_bytes + 2 * COPY_SPAN, 256)));
+    if (allocated != HY_OK) { memory.dictionary_block = nullptr; return allocated; }
+    d_offsets = static_cast<uint32_t*>(memory.dictionary_block);
+    d_chars = static_cast<uint8_t*>(memory.dictionary_block) + offsets_bytes;
+    if (n) hipLaunchKernelGGL(dictionary_offsets, dim3(tiles_of(std::max<uint64_t>(n_unique, n_chunks))), dim3(WG), 0, stream, b.chunk_first, n_chunks, b.local_bytes, b.tile_bytes,
+                              static_cast<uint32_t>(n_unique), d_offsets);
+    else HY_TRY(check(hipMemsetAsync(d_offsets, 0, offsets_bytes, stream)));   // (every chunk's one offset)
+    if (total_bytes)
+      hipLaunchKernelGGL(copy_entry_bytes, dim3(static_cast<uint32_t>((total_bytes + WG * COPY_SPAN - 1) / (WG * COPY_SPAN))), dim3(WG), 0, stream, b.source, b.local_bytes, b.tile_bytes,
+                         static_cast<uint32_t>(n_unique), total_bytes, d_chars);
+    profile_end(stream);
+    HY_TRY(check(hipGetLastError()));
+    return check(hipStreamSynchronize(stream));
+  }
 
   // the handles: a dictionary over the block (caller-owned layout: pure host work), which it then owns; a column over the arena
-  std::vector<hy_string_dictionary_chunk> chunks(n_chunks ? n_chunks : 1);
-  std::vector<hy_segment> segments(n_chunks ? n_chunks : 1);
-  uint64_t first_entry = 0, first_byte = 0;
-  for (uint32_t c = 0; c < n_chunks; ++c) {
-    chunks[c] = hy_string_dictionary_chunk{totals[c].n_entries, 0, reinterpret_cast<const char*>(d_chars + first_byte), d_offsets + first_entry + c};
-    hy_segment& s = segments[c];
-    std::memset(&s, 0, sizeof(s));
-    s.encoding = HY_ENC_DICTIONARY;
-    s.data_type = HY_TYPE_STRING;
-    s.size = out.sizes[c];
-    s.width = 4;
-    s.data = arena + vector_at[c];
-    s.aux_size = totals[c].n_entries;
-    s.ref_chunk_id = 0xFFFFFFFFu;
-    first_entry += totals[c].n_entries;
-    first_byte += totals[c].chars_bytes;
+  hy_status handles() {
+    std::vector<hy_string_dictionary_chunk> chunks(n_chunks ? n_chunks : 1);
+    std::vector<hy_segment> segments(n_chunks ? n_chunks : 1);
+    uint64_t first_entry = 0, first_byte = 0;
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+      chunks[c] = hy_string_dictionary_chunk{totals[c].n_entries, 0, reinterpret_cast<const char*>(d_chars + first_byte), d_offsets + first_entry + c};
+      hy_segment& s = segments[c];
+      std::memset(&s, 0, sizeof(s));
+      s.encoding = HY_ENC_DICTIONARY;
+      s.data_type = HY_TYPE_STRING;
+      s.size = rq.out.sizes[c];
+      s.width = 4;
+      s.data = memory.arena + vector_at[c];
+      s.aux_size = totals[c].n_entries;
+      s.ref_chunk_id = 0xFFFFFFFFu;
+      first_entry += totals[c].n_entries;
+      first_byte += totals[c].chars_bytes;
+    }
+    hy_string_dictionary* made = nullptr;
+    HY_TRY(hy_string_dictionary_create(chunks.data(), n_chunks, HY_MEM_DEVICE, &made));
+    hy_column* gathered = nullptr;
+    const hy_status st = hy_column_create(segments.data(), n_chunks, HY_MEM_DEVICE, &gathered);
+    if (st != HY_OK) {
+      (void)hy_string_dictionary_destroy(made);
+      return st;
+    }
+    made->owned.push_back(memory.dictionary_block);
+    for (uint32_t c = 0; c < n_chunks; ++c) made->chars_bytes[c] = totals[c].chars_bytes;
+    gathered->pooled.emplace_back(memory.arena_capacity, memory.arena);
+    memory = ResultMemory{};
+    *rq.result = gathered;
+    *rq.result_dict = made;
+    return HY_OK;
   }
-  hy_string_dictionary* made = nullptr;
-  st = hy_string_dictionary_create(chunks.data(), n_chunks, HY_MEM_DEVICE, &made);
-  if (st != HY_OK) return release(st);
-  hy_column* gathered = nullptr;
-  st = hy_column_create(segments.data(), n_chunks, HY_MEM_DEVICE, &gathered);
-  if (st != HY_OK) {
-    (void)hy_string_dictionary_destroy(made);
-    return release(st);
+};
+
+// d_entry: per output row the global entry index into the dictionary (the sparse route: into the subset's table), or -1; the source's order
+// is queued on `stream` already.  Steps 2 to 5 of the file's header, then the handles.
+hy_status gather_entries(const StringRequest& rq, const RankedSource& source, const int32_t* d_entry, const BackEndBlocks& blocks, hipStream_t stream) {
+  Gather g(rq, source, d_entry, blocks, stream);
+  hy_status st = g.output_layout();
+  if (st == HY_OK) st = g.order.alloc(g.n);
+  if (st == HY_OK && g.n) {
+    profile_begin(stream, HY_KERNEL_STRING_RANK);
+    st = g.order_rows();
+    if (st == HY_OK) g.heads_and_value_ids();
+    if (st == HY_OK) st = g.entry_bytes();
   }
-  made->owned.push_back(dictionary_block);
-  for (uint32_t c = 0; c < n_chunks; ++c) made->chars_bytes[c] = totals[c].chars_bytes;
-  gathered->pooled.emplace_back(arena_capacity, arena);
-  *result = gathered;
-  *result_dict = made;
-  return HY_OK;
+  if (st == HY_OK) st = g.dictionary_block();
+  if (st == HY_OK) st = g.handles();
+  if (st != HY_OK) {   // (launches may be queued: the arena and the block go back behind them)
+    profile_end(stream);
+    (void)hipStreamSynchronize(stream);
+  }
+  return st;
 }
 
 // Results without rows: a column and a dictionary of zero chunks
@@ -700,15 +845,80 @@ hy_status empty_string_results(hy_column** result, hy_string_dictionary** result
   return st;
 }
 
-namespace {
+// Which route n rows out of a column of `column_rows` rows and E entries take: column_rows + E is what the dense route reads whatever n is
+bool string_sparse_route(uint64_t n, uint64_t column_rows, uint64_t n_source_entries) {
+  const int64_t mode = option(HY_OPT_STRING_SPARSE_GATHER);
+  if (mode == 2) return true;
+  if (mode != 1 || STRING_SPARSE_DIVISOR <= 0) return false;
+  return n <= (column_rows + n_source_entries) / static_cast<uint64_t>(STRING_SPARSE_DIVISOR);
+}
 
-// Destroys a column when the scope ends (the stand-in of the RowID front end: it lives as long as the launches that read it)
-struct ColumnGuard {
-  hy_column* column = nullptr;
-  ~ColumnGuard() { if (column) (void)hy_column_destroy(column); }
-};
+// the refusals of hy_string_ranks_gather's column of ranks
+hy_status ranks_column_check(const hy_column* ranks, const char* name) {
+  HY_TRY(on_this_device(ranks, name));
+  if (ranks->is_mvcc || ranks->is_reference || (ranks->data_type != HY_TYPE_INT && ranks->n_chunks)) return fail(HY_ERR_INVALID, "%s: ranks are an int32 data column", name);
+  for (const hy_segment& segment : ranks->host_segments)
+    if (segment.encoding != HY_ENC_UNENCODED) return fail(HY_ERR_INVALID, "%s: ranks are unencoded segments", name);
+  return HY_OK;
+}
 
 }  // namespace
+
+hy_status string_request(StringRoute route, const char* name, const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, uint32_t chunk_rows,
+                         const SubstrArguments* substr, hy_column** result, hy_string_dictionary** result_dict, StringRequest* rq, bool* answered) {
+  *answered = true;   // (a refusal, or results without rows: there is nothing to run)
+  if (result) *result = nullptr;
+  if (result_dict) *result_dict = nullptr;
+  if (!result || !result_dict || !column || !dict) return fail(HY_ERR_INVALID, "%s: null argument", name);
+  if (route == StringRoute::RowIds) {
+    if (!chunk_rows || (n && !positions)) return fail(HY_ERR_INVALID, "%s: positions missing or chunk_rows == 0", name);
+    if (reinterpret_cast<uintptr_t>(positions) % 8 != 0) return fail(HY_ERR_INVALID, "%s: positions not on an 8-byte boundary", name);
+  }
+  if (route == StringRoute::Ranks) {
+    HY_TRY(ranks_column_check(column, name));
+    HY_TRY(column_order_check(dict, name));
+  } else {
+    HY_TRY(string_column_check(column, dict, name));
+  }
+  const uint64_t rows = route == StringRoute::RowIds ? n : column->rows;
+  if (rows >= (uint64_t{1} << 32)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu rows (32-bit row ids)", name, static_cast<unsigned long long>(rows));
+  if (route == StringRoute::RowIds ? !rows : !column->n_chunks) return empty_string_results(result, result_dict);
+  *rq = StringRequest{name, column, dict, positions, rows, substr, OutChunks{}, route, result, result_dict};
+  rq->out.n = rows;
+  rq->out.chunk_rows = route == StringRoute::RowIds ? chunk_rows : 0;
+  if (route == StringRoute::RowIds)
+    for (uint64_t begin = 0; begin < rows; begin += chunk_rows) rq->out.sizes.push_back(static_cast<uint32_t>(std::min<uint64_t>(chunk_rows, rows - begin)));
+  else
+    for (const hy_segment& segment : column->host_segments) rq->out.sizes.push_back(segment.size);
+  if (route != StringRoute::Ranks && string_sparse_route(rows, column->rows, entries_of(dict))) rq->route = StringRoute::Sparse;   // few rows out of a large column
+  *answered = false;
+  return HY_OK;
+}
+
+// The stages of a request.  Every exit behind the first queued launch passes the synchronise at the end, before a temporary goes back to the pool.
+hy_status string_request_run(const StringRequest& rq) {
+  hipStream_t stream = current_stream();
+  FrontBuffers front;
+  HY_TRY(front.alloc(rq));
+  RequestBlocks blocks;
+  HY_TRY(reserve_request(rq, blocks));
+  HY_TRY(like_dictionary_tables(rq.dict));
+  int32_t* d_entry = front.entry.as<int32_t>();
+  SparseSubset subset;
+  RankedSource source{rq.dict, nullptr, nullptr, nullptr};
+  hy_status st = HY_OK;
+  if (rq.route == StringRoute::Sparse) {   // the rows' entries first: they say which entries there are to rank
+    if (rq.n) st = sparse_entries(rq, blocks, d_entry, stream, &subset);
+    source.subset = &subset;
+    source.d_ranks = subset.ranks;
+  } else {
+    st = rank_dictionary(rq, blocks.source, stream, &source);
+    if (st == HY_OK) st = rq.route == StringRoute::Ranks ? rank_entries(rq, blocks.source, front, stream) : stand_in_entries(rq, front, stream);
+  }
+  if (st == HY_OK) st = gather_entries(rq, source, d_entry, blocks.back, stream);
+  (void)hipStreamSynchronize(stream);   // (the temporaries go back to the pool, the stand-in dies)
+  return st;
+}
 
 }  // namespace hy
 
@@ -718,117 +928,17 @@ extern "C" {
 
 hy_status hy_string_column_gather(const hy_column* column, const hy_string_dictionary* dict, const hy_row_id* positions, uint64_t n, uint32_t chunk_rows, hy_column** result,
                                   hy_string_dictionary** result_dict) {
-  const char* name = "hy_string_column_gather";
-  if (result) *result = nullptr;
-  if (result_dict) *result_dict = nullptr;
-  if (!result || !result_dict || !column || !dict) return fail(HY_ERR_INVALID, "%s: null argument", name);
-  if (!chunk_rows || (n && !positions)) return fail(HY_ERR_INVALID, "%s: positions missing or chunk_rows == 0", name);
-  if (reinterpret_cast<uintptr_t>(positions) % 8 != 0) return fail(HY_ERR_INVALID, "%s: positions not on an 8-byte boundary", name);
-  HY_TRY(string_column_check(column, dict, name));
-  if (n >= (uint64_t{1} << 32)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu rows (32-bit row ids)", name, static_cast<unsigned long long>(n));
-  if (!n) return empty_string_results(result, result_dict);
-  OutChunks out;
-  out.n = n;
-  out.chunk_rows = chunk_rows;
-  for (uint64_t begin = 0; begin < n; begin += chunk_rows) out.sizes.push_back(static_cast<uint32_t>(std::min<uint64_t>(chunk_rows, n - begin)));
-
-  hipStream_t stream = current_stream();
-  const uint64_t n_source_entries = dict->entry_offsets[dict->n_chunks];
-  if (string_sparse_route(n, column->rows, n_source_entries)) {   // the column read at the RowIDs, the entries they reference ranked
-    DeviceBuffer entry;
-    HY_TRY(entry.alloc(4 * n + 16));
-    Scratch& sc = scratch();
-    HY_TRY(sc.reserve(sparse_gather_scratch_bytes(n_source_entries, dict->n_chunks, n, out.sizes.size())));
-    HY_TRY(like_dictionary_tables(dict));
-    SparseSubset subset;
-    hy_status st = sparse_entries(column, dict, positions, n, nullptr, sc, entry.as<int32_t>(), stream, name, &subset);
-    if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), subset.ranks, nullptr, sc, stream, name, result, result_dict, &subset);
-    (void)hipStreamSynchronize(stream);   // (the temporaries go back to the pool)
-    return st;
-  }
-  // the column's stand-in over 0, 1, 2, ... exported: every source row's global entry index
-  DeviceBuffer table, values, nulls, entry;
-  ColumnGuard stand_in;
-  HY_TRY(table.alloc(4 * n_source_entries + 16));
-  HY_TRY(values.alloc(4 * column->rows + 16));
-  HY_TRY(nulls.alloc(column->rows + 16));
-  HY_TRY(entry.alloc(4 * n + 16));
-  Scratch& sc = scratch();
-  HY_TRY(sc.reserve(gather_scratch_bytes(n_source_entries, n, out.sizes.size(), false)));
-  HY_TRY(like_dictionary_tables(dict));
-  int32_t* d_ranks = nullptr;
-  if (n_source_entries) {
-    d_ranks = carve<int32_t>(sc, n_source_entries);
-    if (!d_ranks) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-    uint32_t* d_n_distinct = nullptr;
-    const hy_status ranked = column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream);
-    if (ranked != HY_OK) {   // (launches may be queued: the temporaries go back to the pool behind them)
-      (void)hipStreamSynchronize(stream);
-      return ranked;
-    }
-  }
-  hy_status st = string_stand_in(column, dict, table.as<int32_t>(), &stand_in.column);
-  profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the front end: a bracket of its own)
-  if (st == HY_OK && n_source_entries) hipLaunchKernelGGL(iota_table, dim3(grid_for(n_source_entries)), dim3(WG), 0, stream, table.as<int32_t>(), static_cast<uint32_t>(n_source_entries));
-  if (st == HY_OK) st = export_column_at(stand_in.column, values.ptr, nulls.as<uint8_t>(), nullptr);
-  if (st == HY_OK) hipLaunchKernelGGL(entries_at_positions, dim3(grid_for(n)), dim3(WG), 0, stream, values.as<int32_t>(), nulls.as<uint8_t>(), column->d_row_base, column->n_chunks, positions,
-                                           static_cast<uint32_t>(n), static_cast<uint32_t>(n_source_entries), entry.as<int32_t>());
-  profile_end(stream);
-  if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), d_ranks, nullptr, sc, stream, name, result, result_dict);
-  (void)hipStreamSynchronize(stream);   // (the temporaries go back to the pool, the stand-in dies)
-  return st;
+  StringRequest request;
+  bool answered = false;
+  HY_TRY(string_request(StringRoute::RowIds, "hy_string_column_gather", column, dict, positions, n, chunk_rows, nullptr, result, result_dict, &request, &answered));
+  return answered ? HY_OK : string_request_run(request);
 }
 
 hy_status hy_string_ranks_gather(const hy_string_dictionary* dict, const hy_column* ranks, hy_column** result, hy_string_dictionary** result_dict) {
-  const char* name = "hy_string_ranks_gather";
-  if (result) *result = nullptr;
-  if (result_dict) *result_dict = nullptr;
-  if (!result || !result_dict || !dict || !ranks) return fail(HY_ERR_INVALID, "%s: null argument", name);
-  HY_TRY(on_this_device(ranks, name));
-  if (ranks->is_mvcc || ranks->is_reference || (ranks->data_type != HY_TYPE_INT && ranks->n_chunks)) return fail(HY_ERR_INVALID, "%s: ranks are an int32 data column", name);
-  for (const hy_segment& segment : ranks->host_segments)
-    if (segment.encoding != HY_ENC_UNENCODED) return fail(HY_ERR_INVALID, "%s: ranks are unencoded segments", name);
-  HY_TRY(column_order_check(dict, name));
-  if (ranks->rows >= (uint64_t{1} << 32)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu rows (32-bit row ids)", name, static_cast<unsigned long long>(ranks->rows));
-  if (!ranks->n_chunks) return empty_string_results(result, result_dict);
-  OutChunks out;
-  out.n = ranks->rows;
-  for (const hy_segment& segment : ranks->host_segments) out.sizes.push_back(segment.size);
-
-  hipStream_t stream = current_stream();
-  const uint64_t n = ranks->rows, n_source_entries = dict->entry_offsets[dict->n_chunks];
-  DeviceBuffer values, nulls, entry;
-  HY_TRY(values.alloc(4 * n + 16));
-  HY_TRY(nulls.alloc(n + 16));
-  HY_TRY(entry.alloc(4 * n + 16));
-  Scratch& sc = scratch();
-  HY_TRY(sc.reserve(gather_scratch_bytes(n_source_entries, n, out.sizes.size(), true)));
-  HY_TRY(like_dictionary_tables(dict));
-  int32_t* d_ranks = nullptr;
-  uint32_t* inverse = carve<uint32_t>(sc, n_source_entries);
-  if (!inverse) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-  hy_status st = HY_OK;
-  if (n_source_entries) {
-    d_ranks = carve<int32_t>(sc, n_source_entries);
-    if (!d_ranks) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-    uint32_t* d_n_distinct = nullptr;
-    st = column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream);
-  }
-  profile_begin(stream, HY_KERNEL_STRING_RANK);   // (the front end: a bracket of its own)
-  if (st == HY_OK && n_source_entries) {
-    if (hipMemsetAsync(inverse, 0xFF, 4 * n_source_entries, stream) != hipSuccess) st = fail(HY_ERR_DEVICE, "%s: hipMemsetAsync failed", name);
-    else hipLaunchKernelGGL(inverse_ranks, dim3(grid_for(n_source_entries)), dim3(WG), 0, stream, d_ranks, static_cast<uint32_t>(n_source_entries), inverse);
-  }
-  if (st == HY_OK && n) {
-    st = export_column_at(ranks, values.ptr, nulls.as<uint8_t>(), nullptr);
-    if (st == HY_OK)
-      hipLaunchKernelGGL(entries_of_ranks, dim3(grid_for(n)), dim3(WG), 0, stream, values.as<int32_t>(), nulls.as<uint8_t>(), inverse, static_cast<uint32_t>(n),
-                         static_cast<uint32_t>(n_source_entries), entry.as<int32_t>());
-  }
-  profile_end(stream);
-  if (st == HY_OK) st = gather_entries(dict, out, entry.as<int32_t>(), d_ranks, nullptr, sc, stream, name, result, result_dict);
-  (void)hipStreamSynchronize(stream);
-  return st;
+  StringRequest request;
+  bool answered = false;
+  HY_TRY(string_request(StringRoute::Ranks, "hy_string_ranks_gather", ranks, dict, nullptr, 0, 0, nullptr, result, result_dict, &request, &answered));
+  return answered ? HY_OK : string_request_run(request);
 }
 
 hy_status hy_string_dictionary_chunk_size(const hy_string_dictionary* dict, uint32_t chunk, uint32_t* n_entries, uint64_t* chars_bytes) {
@@ -840,7 +950,7 @@ hy_status hy_string_dictionary_chunk_size(const hy_string_dictionary* dict, uint
   *n_entries = c.n_entries;
   *chars_bytes = 0;
   if (!c.n_entries) return HY_OK;
-  if (dict->device != this_thread_device()) return fail(HY_ERR_INVALID, "%s: the dictionary lives on device %d, the calling thread works on device %d", name, dict->device, this_thread_device());
+  HY_TRY(dictionary_device_check(dict, name));
   if (dict->chars_bytes[chunk] == ~0ull) {   // caller-owned offsets, not read yet: once
     uint32_t end = 0;
     hipStream_t stream = current_stream();
@@ -860,7 +970,7 @@ hy_status hy_string_dictionary_read_chunk(const hy_string_dictionary* dict, uint
   if (c.n_entries && !c.offsets) return fail(HY_ERR_UNSUPPORTED, "%s: chunk %u has the fixed-slot layout (the caller holds its bytes)", name, chunk);
   offsets[0] = 0;
   if (!c.n_entries) return HY_OK;
-  if (dict->device != this_thread_device()) return fail(HY_ERR_INVALID, "%s: the dictionary lives on device %d, the calling thread works on device %d", name, dict->device, this_thread_device());
+  HY_TRY(dictionary_device_check(dict, name));
   hipStream_t stream = current_stream();
   HY_HIP(hipMemcpyAsync(offsets, c.offsets, 4 * (size_t{c.n_entries} + 1), hipMemcpyDeviceToHost, stream));
   HY_HIP(hipStreamSynchronize(stream));

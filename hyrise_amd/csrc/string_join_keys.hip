@@ -95,30 +95,36 @@ struct JointTables {
     entry_offsets.insert(entry_offsets.end(), left->entry_offsets.begin(), left->entry_offsets.end());   // (n_l + 1 of them: the last is `split`)
     for (uint32_t c = 1; c <= right->n_chunks; ++c) entry_offsets.push_back(split + right->entry_offsets[c]);
   }
-  size_t bytes() const { return align_up(sizeof(LikeChunk) * chunks.size(), 256) + align_up(sizeof(LikeBlock) * blocks.size(), 256) + align_up(8 * entry_offsets.size(), 256); }
 };
 
-// what join_keys_launch takes from the scratch arena: the joint tables, the merge's temporaries for the joint total, the ranks behind the ids
-size_t join_keys_scratch_bytes(const JointTables& tables, bool ids) {
-  return tables.bytes() + order_scratch_bytes(tables.total) + (ids ? align_up(4 * tables.total, 256) : 0) + 1024;
+// what join_keys_launch reads and writes in the scratch arena: the joint tables, the merge's temporaries for the joint total, the ranks behind the ids
+struct JoinKeyBlocks {
+  LikeChunk* chunks;
+  LikeBlock* blocks;
+  uint64_t* entry_offsets;
+  int32_t* joint_ranks;   // with ids
+  MergeBlocks merge;
+};
+
+void join_keys_layout(Carver& carver, const JointTables& tables, bool ids, JoinKeyBlocks& b) {
+  b.chunks = carver.take<LikeChunk>(tables.chunks.size());
+  b.blocks = carver.take<LikeBlock>(tables.blocks.size());
+  b.entry_offsets = carver.take<uint64_t>(tables.entry_offsets.size());
+  b.joint_ranks = ids ? carver.take<int32_t>(tables.total) : nullptr;
+  merge_layout(carver, tables.total, b.merge);
 }
 
 // Queues everything on `stream`: the tables' upload, the joint order and, with `ids`, string_join_ids.  d_left / d_right: int32 ranks, or
-// int64 ids, in the layout of hy_string_dictionary_order per side.  tables.total > 0; join_keys_scratch_bytes reserved by the caller.
-hy_status join_keys_launch(const JointTables& tables, bool ids, Scratch& sc, void* d_left, void* d_right, uint32_t** d_n_distinct, hipStream_t stream) {
-  LikeChunk* d_chunks = carve<LikeChunk>(sc, tables.chunks.size());
-  LikeBlock* d_blocks = carve<LikeBlock>(sc, tables.blocks.size());
-  uint64_t* d_entry_offsets = carve<uint64_t>(sc, tables.entry_offsets.size());
-  int32_t* d_joint_ranks = ids ? carve<int32_t>(sc, tables.total) : nullptr;
-  if (!d_chunks || !d_blocks || !d_entry_offsets || (ids && !d_joint_ranks)) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+// int64 ids, in the layout of hy_string_dictionary_order per side.  tables.total > 0.
+hy_status join_keys_launch(const JointTables& tables, bool ids, const JoinKeyBlocks& b, void* d_left, void* d_right, hipStream_t stream) {
   // (pageable memory: copied before the calls return)
-  HY_HIP(hipMemcpyAsync(d_chunks, tables.chunks.data(), sizeof(LikeChunk) * tables.chunks.size(), hipMemcpyHostToDevice, stream));
-  HY_HIP(hipMemcpyAsync(d_blocks, tables.blocks.data(), sizeof(LikeBlock) * tables.blocks.size(), hipMemcpyHostToDevice, stream));
-  HY_HIP(hipMemcpyAsync(d_entry_offsets, tables.entry_offsets.data(), 8 * tables.entry_offsets.size(), hipMemcpyHostToDevice, stream));
-  const PairTables pair{d_chunks, d_blocks, d_entry_offsets, static_cast<uint32_t>(tables.chunks.size()), static_cast<uint32_t>(tables.blocks.size()), tables.total, tables.split};
-  if (!ids) return pair_order_launch(pair, sc, static_cast<int32_t*>(d_left), static_cast<int32_t*>(d_right), d_n_distinct, stream);
-  HY_TRY(pair_order_launch(pair, sc, d_joint_ranks, d_joint_ranks + tables.split, d_n_distinct, stream));
-  const JoinIdArgs args{d_chunks, d_blocks, d_entry_offsets, d_joint_ranks, static_cast<int64_t*>(d_left), static_cast<int64_t*>(d_right), tables.split};
+  HY_HIP(hipMemcpyAsync(b.chunks, tables.chunks.data(), sizeof(LikeChunk) * tables.chunks.size(), hipMemcpyHostToDevice, stream));
+  HY_HIP(hipMemcpyAsync(b.blocks, tables.blocks.data(), sizeof(LikeBlock) * tables.blocks.size(), hipMemcpyHostToDevice, stream));
+  HY_HIP(hipMemcpyAsync(b.entry_offsets, tables.entry_offsets.data(), 8 * tables.entry_offsets.size(), hipMemcpyHostToDevice, stream));
+  const PairTables pair{b.chunks, b.blocks, b.entry_offsets, static_cast<uint32_t>(tables.chunks.size()), static_cast<uint32_t>(tables.blocks.size()), tables.total, tables.split};
+  if (!ids) return pair_order_launch(pair, b.merge, static_cast<int32_t*>(d_left), static_cast<int32_t*>(d_right), stream);
+  HY_TRY(pair_order_launch(pair, b.merge, b.joint_ranks, b.joint_ranks + tables.split, stream));
+  const JoinIdArgs args{b.chunks, b.blocks, b.entry_offsets, b.joint_ranks, static_cast<int64_t*>(d_left), static_cast<int64_t*>(d_right), tables.split};
   profile_begin(stream, HY_KERNEL_STRING_RANK);
   hipLaunchKernelGGL(string_join_ids, dim3(pair.n_blocks), dim3(IDS_WG), 0, stream, args);
   profile_end(stream);
@@ -129,9 +135,8 @@ hy_status join_keys_launch(const JointTables& tables, bool ids, Scratch& sc, voi
 // The refusals of a pair of dictionaries, before any launch and any allocation
 hy_status pair_check(const hy_string_dictionary* left, const hy_string_dictionary* right, const char* name) {
   if (left->device != right->device) return fail(HY_ERR_INVALID, "%s: the left dictionary lives on device %d, the right one on device %d", name, left->device, right->device);
-  if (left->device != this_thread_device()) return fail(HY_ERR_INVALID, "%s: the dictionaries live on device %d, the calling thread works on device %d", name, left->device, this_thread_device());
-  const uint64_t total = left->entry_offsets[left->n_chunks] + right->entry_offsets[right->n_chunks];
-  if (total >= (uint64_t{1} << 31)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu dictionary entries of both sides together do not fit int32 ranks", name, static_cast<unsigned long long>(total));
+  HY_TRY(dictionary_device_check(left, name));
+  HY_TRY(entries_fit_ranks(left->entry_offsets[left->n_chunks] + right->entry_offsets[right->n_chunks], name));
   if (left->blocks.size() + right->blocks.size() > 0x7FFFFFFFull) return fail(HY_ERR_UNSUPPORTED, "%s: more than 2^31 workgroups of entries", name);
   return HY_OK;
 }
@@ -151,18 +156,18 @@ hy_status dictionary_keys(const hy_string_dictionary* left, const hy_string_dict
     return HY_OK;
   }
   hipStream_t stream = current_stream();
-  Scratch& sc = scratch();
   const bool host = mem == HY_MEM_HOST;
-  HY_TRY(sc.reserve(join_keys_scratch_bytes(tables, ids) + (host ? align_up(width * tables.total, 256) : 0)));
-  char* d_out = host ? static_cast<char*>(sc.carve(width * tables.total)) : nullptr;
-  if (host && !d_out) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-  uint32_t* d_n_distinct = nullptr;
-  HY_TRY(join_keys_launch(tables, ids, sc, host ? d_out : left_out, host ? d_out + width * tables.split : right_out, &d_n_distinct, stream));
-  if (host && tables.split) HY_HIP(hipMemcpyAsync(left_out, d_out, width * tables.split, hipMemcpyDeviceToHost, stream));
-  if (host && tables.total > tables.split) HY_HIP(hipMemcpyAsync(right_out, d_out + width * tables.split, width * (tables.total - tables.split), hipMemcpyDeviceToHost, stream));
-  if (n_distinct) HY_HIP(hipMemcpyAsync(n_distinct, d_n_distinct, 4, hipMemcpyDeviceToHost, stream));
-  if (host || n_distinct) HY_HIP(hipStreamSynchronize(stream));   // (else: complete in the order of the calling thread's stream)
-  return HY_OK;
+  JoinKeyBlocks blocks;
+  char* d_twin = nullptr;
+  HY_TRY(reserve_and_carve([&](Carver& carver) {
+    if (host) d_twin = static_cast<char*>(carver.take_bytes(width * tables.total));
+    join_keys_layout(carver, tables, ids, blocks);
+  }));
+  char* d_left = host ? d_twin : static_cast<char*>(left_out);
+  char* d_right = host ? d_twin + width * tables.split : static_cast<char*>(right_out);
+  HY_TRY(join_keys_launch(tables, ids, blocks, d_left, d_right, stream));
+  const TwinPart parts[2] = {{left_out, d_left, width * tables.split}, {right_out, d_right, width * (tables.total - tables.split)}};
+  return outputs_to_caller(mem, parts, 2, blocks.merge.n_distinct, n_distinct, stream);
 }
 
 }  // namespace
@@ -199,40 +204,31 @@ hy_status hy_column_string_join_keys(const hy_column* left, const hy_string_dict
 
   // the keys: one buffer per side, which that side's stand-in owns (16 bytes of slack behind the last key, like every dictionary of a column)
   hipStream_t stream = current_stream();
-  void* d_left = nullptr;
-  void* d_right = nullptr;
-  hy_column* left_result = nullptr;
-  hy_column* right_result = nullptr;
+  KeyColumn left_keys, right_keys;
   auto give_up = [&](hy_status status) {
     (void)hipStreamSynchronize(stream);
-    if (left_result) (void)hy_column_destroy(left_result); else (void)hipFree(d_left);
-    if (right_result) (void)hy_column_destroy(right_result); else (void)hipFree(d_right);
+    left_keys.drop();
+    right_keys.drop();
     return status;
   };
-  HY_HIP(hipMalloc(&d_left, align_up(width * tables.split + 16, 256)));
-  if (hipMalloc(&d_right, align_up(width * (tables.total - tables.split) + 16, 256)) != hipSuccess) {
-    d_right = nullptr;
-    return give_up(fail(HY_ERR_DEVICE, "%s: hipMalloc failed: %s", name, hipGetErrorString(hipGetLastError())));
-  }
+  HY_TRY(left_keys.alloc(align_up(width * tables.split + 16, 256)));
+  hy_status status = right_keys.alloc(align_up(width * (tables.total - tables.split) + 16, 256));
+  if (status != HY_OK) return give_up(status);
   if (tables.total) {
-    Scratch& sc = scratch();
-    hy_status status = sc.reserve(join_keys_scratch_bytes(tables, ids));
-    uint32_t* d_n_distinct = nullptr;
-    if (status == HY_OK) status = join_keys_launch(tables, ids, sc, d_left, d_right, &d_n_distinct, stream);
+    JoinKeyBlocks blocks;
+    status = reserve_and_carve([&](Carver& carver) { join_keys_layout(carver, tables, ids, blocks); });
+    if (status == HY_OK) status = join_keys_launch(tables, ids, blocks, left_keys.d_keys, right_keys.d_keys, stream);
     if (status != HY_OK) return give_up(status);
   }
   const uint32_t data_type = ids ? HY_TYPE_LONG : HY_TYPE_INT;
-  hy_status status = string_stand_in(left, left_dict, d_left, &left_result, data_type);
+  status = left_keys.make_stand_in(left, left_dict, data_type);
+  if (status == HY_OK) status = right_keys.make_stand_in(right, right_dict, data_type);
   if (status != HY_OK) return give_up(status);
-  (left_result->stand_in ? left_result->stand_in : left_result)->owned.push_back(d_left);
-  status = string_stand_in(right, right_dict, d_right, &right_result, data_type);
-  if (status != HY_OK) return give_up(status);
-  (right_result->stand_in ? right_result->stand_in : right_result)->owned.push_back(d_right);
   // (the dictionaries may die as soon as the call has returned: nothing queued reads them any more)
   const hipError_t err = hipStreamSynchronize(stream);
   if (err != hipSuccess) return give_up(fail(HY_ERR_DEVICE, "%s: making the keys failed: %s", name, hipGetErrorString(err)));
-  *left_out = left_result;
-  *right_out = right_result;
+  *left_out = left_keys.stand_in;
+  *right_out = right_keys.stand_in;
   return HY_OK;
 }
 

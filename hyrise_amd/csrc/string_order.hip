@@ -91,13 +91,12 @@ __global__ __launch_bounds__(256) void string_twins(StringTwins t) {
 // left one first) and stores the element at its merged position in the other buffer -- one plain 8-byte store, no atomics, no LDS, nothing
 // that depends on lane order.  A run without a sibling finds an empty one and stays where it is.
 // Then: a head flag per position (the element differs from its predecessor), counted inclusively inside a workgroup's 256 positions
-// (order_heads), the workgroups' totals scanned by one workgroup (order_scan_tiles), and rank = heads at or before the position - 1
+// (order_heads), the workgroups' totals scanned by one workgroup (scan_tiles, string_entries.hpp), and rank = heads at or before the position - 1
 // scattered to ranks[entry_offsets[c] + v] (order_scatter).
 // Robustness: an element read from a buffer is clamped to a chunk and an entry that exist, offsets to the chunk's bytes; merged positions
 // are run begin + own index + a count of at most the sibling's length, so they stay inside the pair.  Dictionaries that are not sorted
 // leave positions unwritten and others written twice: unspecified ranks, nothing outside the buffers, no loop whose length is data.
 constexpr uint32_t ORDER_WG = 256;       // = LIKE_WG: the block table is the matcher's
-constexpr uint32_t ORDER_SCAN_WG = 1024;
 
 struct OrderArgs {
   const LikeChunk* chunks;
@@ -195,31 +194,6 @@ __global__ __launch_bounds__(ORDER_WG) void order_heads(OrderArgs a, const uint6
   if (threadIdx.x == ORDER_WG - 1) tile_heads[blockIdx.x] = before + s_wave_heads[wave];
 }
 
-// tile_heads becomes its own exclusive prefix sum; *n_distinct = the total.  One workgroup: a thread sums a contiguous share, the shares' sums
-// are scanned in LDS, the thread walks its share again.
-__global__ __launch_bounds__(ORDER_SCAN_WG) void order_scan_tiles(uint32_t* tile_heads, uint32_t n_tiles, uint32_t* n_distinct) {
-  __shared__ uint32_t s_sums[ORDER_SCAN_WG];
-  const uint32_t share = (n_tiles + ORDER_SCAN_WG - 1) / ORDER_SCAN_WG;
-  const uint32_t begin = min(threadIdx.x * share, n_tiles), end = min(begin + share, n_tiles);
-  uint32_t sum = 0;
-  for (uint32_t i = begin; i < end; ++i) sum += tile_heads[i];
-  s_sums[threadIdx.x] = sum;
-  __syncthreads();
-  for (uint32_t step = 1; step < ORDER_SCAN_WG; step <<= 1) {   // Hillis-Steele, inclusive
-    const uint32_t add = threadIdx.x >= step ? s_sums[threadIdx.x - step] : 0;
-    __syncthreads();
-    s_sums[threadIdx.x] += add;
-    __syncthreads();
-  }
-  uint32_t running = s_sums[threadIdx.x] - sum;
-  for (uint32_t i = begin; i < end; ++i) {
-    const uint32_t heads = tile_heads[i];
-    tile_heads[i] = running;
-    running += heads;
-  }
-  if (threadIdx.x == ORDER_SCAN_WG - 1) *n_distinct = s_sums[ORDER_SCAN_WG - 1];
-}
-
 // (split: the joint order of two dictionaries, below -- a position at or behind it is an entry of the right one and goes to right_ranks)
 __global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uint64_t* sorted, uint64_t n, const uint32_t* local, const uint32_t* tile_heads, int32_t* ranks,
                                                           int32_t* right_ranks, uint64_t split) {
@@ -242,24 +216,24 @@ __global__ __launch_bounds__(ORDER_WG) void order_scatter(OrderArgs a, const uin
 
 }  // namespace
 
-// What hy_string_dictionary_order takes from the scratch arena for a dictionary of `total` entries
-size_t order_scratch_bytes(uint64_t total) {
-  const uint64_t tiles = (total + ORDER_WG - 1) / ORDER_WG;
-  return 2 * align_up(8 * total, 256) + align_up(4 * tiles, 256) + 256 + 4096;
+// The merge sequence's temporaries for `total` positions: two buffers of elements (the one the last round read then holds the tile-local head
+// counts), the tiles' heads and the number of distinct strings.
+void merge_layout(Carver& carver, uint64_t total, MergeBlocks& blocks) {
+  blocks.ping = carver.take<uint64_t>(total);
+  blocks.pong = carver.take<uint64_t>(total);
+  blocks.tile_heads = carver.take<uint32_t>((total + ORDER_WG - 1) / ORDER_WG);
+  blocks.n_distinct = carver.take<uint32_t>(1);
 }
 
 // The launch sequence, once, for its three callers: identity, the merge rounds over `n_runs` runs, heads, the scan of the tiles' heads, the
 // scatter (positions at or behind `split` to d_right_ranks).  `merge_workgroups`: what order_identity and order_merge are launched with (a
-// block table's size, or the tiles of a table of entries); a.n_positions > 0.  *d_n_distinct is carved here.
-static hy_status order_sequence(const OrderArgs& a, uint32_t merge_workgroups, uint64_t n_runs, Scratch& sc, int32_t* d_ranks, int32_t* d_right_ranks, uint64_t split,
-                                uint32_t** d_n_distinct, hipStream_t stream) {
+// block table's size, or the tiles of a table of entries); a.n_positions > 0.
+static hy_status order_sequence(const OrderArgs& a, uint32_t merge_workgroups, uint64_t n_runs, const MergeBlocks& blocks, int32_t* d_ranks, int32_t* d_right_ranks, uint64_t split,
+                                hipStream_t stream) {
   const uint64_t total = a.n_positions;
   const uint32_t n_tiles = static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG);
-  uint64_t* ping = carve<uint64_t>(sc, total);
-  uint64_t* pong = carve<uint64_t>(sc, total);
-  uint32_t* tile_heads = carve<uint32_t>(sc, n_tiles);
-  *d_n_distinct = carve<uint32_t>(sc, 1);
-  if (!ping || !pong || !tile_heads || !*d_n_distinct) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  uint64_t* ping = blocks.ping;
+  uint64_t* pong = blocks.pong;
   profile_begin(stream, HY_KERNEL_STRING_RANK);
   hipLaunchKernelGGL(order_identity, dim3(merge_workgroups), dim3(ORDER_WG), 0, stream, a, ping);
   for (uint32_t round = 0; (uint64_t{1} << round) < n_runs; ++round) {
@@ -267,50 +241,54 @@ static hy_status order_sequence(const OrderArgs& a, uint32_t merge_workgroups, u
     std::swap(ping, pong);
   }
   uint32_t* local = reinterpret_cast<uint32_t*>(pong);   // (the buffer the last round read: free again)
-  hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, a, ping, total, local, tile_heads);
-  hipLaunchKernelGGL(order_scan_tiles, dim3(1), dim3(ORDER_SCAN_WG), 0, stream, tile_heads, n_tiles, *d_n_distinct);
-  hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, a, ping, total, local, tile_heads, d_ranks, d_right_ranks, split);
+  hipLaunchKernelGGL(order_heads, dim3(n_tiles), dim3(ORDER_WG), 0, stream, a, ping, total, local, blocks.tile_heads);
+  hipLaunchKernelGGL(scan_tiles<uint32_t>, dim3(1), dim3(SCAN_WG), 0, stream, blocks.tile_heads, n_tiles, blocks.n_distinct);
+  hipLaunchKernelGGL(order_scatter, dim3(n_tiles), dim3(ORDER_WG), 0, stream, a, ping, total, local, blocks.tile_heads, d_ranks, d_right_ranks, split);
   profile_end(stream);
   HY_HIP(hipGetLastError());
   return HY_OK;
 }
 
-// Queues the whole sequence on `stream`: d_ranks[entry_offsets[c] + v] and *d_n_distinct (device memory, carved here: d_ranks may be a
-// block of the arena that the caller carved BEFORE this call).  total = entry_offsets[n_chunks] > 0.
-hy_status column_order_launch(const hy_string_dictionary* dict, Scratch& sc, int32_t* d_ranks, uint32_t** d_n_distinct, hipStream_t stream, const EntryWindow* d_windows,
-                              bool sorted_chunks) {
+// Queues the whole sequence on `stream`: d_ranks[entry_offsets[c] + v] and *blocks.n_distinct.  total = entry_offsets[n_chunks] > 0.
+hy_status column_order_launch(const hy_string_dictionary* dict, const MergeBlocks& blocks, int32_t* d_ranks, hipStream_t stream, const EntryWindow* d_windows, bool sorted_chunks) {
   HY_TRY(like_dictionary_tables(dict));
   const uint64_t total = dict->entry_offsets[dict->n_chunks];
   const bool by_position = d_windows && !sorted_chunks;
   const OrderArgs args{dict->d_chunks, dict->d_blocks, dict->d_entry_offsets, dict->n_chunks, d_windows, by_position ? 1u : 0u, nullptr, dict->d_entry_offsets, total};
-  return order_sequence(args, static_cast<uint32_t>(dict->blocks.size()), by_position ? total : dict->n_chunks, sc, d_ranks, nullptr, ~0ull, d_n_distinct, stream);
+  return order_sequence(args, static_cast<uint32_t>(dict->blocks.size()), by_position ? total : dict->n_chunks, blocks, d_ranks, nullptr, ~0ull, stream);
 }
 
 // The same sequence over a table of entries (the sparse route of string_gather.hip): `total` > 0 positions, 256 per workgroup
-hy_status table_order_launch(const SubsetEntry* d_table, const uint64_t* d_run_offsets, uint32_t n_chunks, uint64_t total, bool by_position, Scratch& sc, int32_t* d_ranks,
+hy_status table_order_launch(const SubsetEntry* d_table, const uint64_t* d_run_offsets, uint32_t n_chunks, uint64_t total, bool by_position, const MergeBlocks& blocks, int32_t* d_ranks,
                              hipStream_t stream) {
   const OrderArgs args{nullptr, nullptr, nullptr, n_chunks, nullptr, by_position ? 1u : 0u, d_table, d_run_offsets, total};
-  uint32_t* d_n_distinct = nullptr;
-  return order_sequence(args, static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG), by_position ? total : n_chunks, sc, d_ranks, nullptr, ~0ull, &d_n_distinct, stream);
+  return order_sequence(args, static_cast<uint32_t>((total + ORDER_WG - 1) / ORDER_WG), by_position ? total : n_chunks, blocks, d_ranks, nullptr, ~0ull, stream);
 }
 
 // The same sequence over the chunks of TWO dictionaries laid end to end (string_join_keys.hip builds the tables): left's chunks are runs
 // 0 .. n_l - 1, right's follow, so equal strings of either side get one rank.  Positions below t.split are left's entries and go to
 // d_left_ranks, the others to d_right_ranks[position - split].  t.total > 0.
-hy_status pair_order_launch(const PairTables& t, Scratch& sc, int32_t* d_left_ranks, int32_t* d_right_ranks, uint32_t** d_n_distinct, hipStream_t stream) {
+hy_status pair_order_launch(const PairTables& t, const MergeBlocks& blocks, int32_t* d_left_ranks, int32_t* d_right_ranks, hipStream_t stream) {
   const OrderArgs args{t.chunks, t.blocks, t.entry_offsets, t.n_chunks, nullptr, 0u, nullptr, t.entry_offsets, t.total};
-  return order_sequence(args, t.n_blocks, t.n_chunks, sc, d_left_ranks, d_right_ranks, t.split, d_n_distinct, stream);
+  return order_sequence(args, t.n_blocks, t.n_chunks, blocks, d_left_ranks, d_right_ranks, t.split, stream);
 }
 
-// The refusals of a dictionary that is to be ordered, before any launch and any allocation
+// ---- the refusals, before any launch and any allocation -----------------------------------------------------------------------------------
+hy_status dictionary_device_check(const hy_string_dictionary* dict, const char* entry_point) {
+  if (dict->device == this_thread_device()) return HY_OK;
+  return fail(HY_ERR_INVALID, "%s: the dictionary lives on device %d, the calling thread works on device %d", entry_point, dict->device, this_thread_device());
+}
+
+hy_status entries_fit_ranks(uint64_t total, const char* entry_point) {
+  if (total < (uint64_t{1} << 31)) return HY_OK;
+  return fail(HY_ERR_UNSUPPORTED, "%s: %llu dictionary entries do not fit int32 ranks", entry_point, static_cast<unsigned long long>(total));
+}
+
 hy_status column_order_check(const hy_string_dictionary* dict, const char* entry_point) {
-  if (dict->device != this_thread_device()) return fail(HY_ERR_INVALID, "%s: the dictionary lives on device %d, the calling thread works on device %d", entry_point, dict->device, this_thread_device());
-  const uint64_t total = dict->entry_offsets[dict->n_chunks];
-  if (total >= (uint64_t{1} << 31)) return fail(HY_ERR_UNSUPPORTED, "%s: %llu dictionary entries do not fit int32 ranks", entry_point, static_cast<unsigned long long>(total));
-  return HY_OK;
+  HY_TRY(dictionary_device_check(dict, entry_point));
+  return entries_fit_ranks(dict->entry_offsets[dict->n_chunks], entry_point);
 }
 
-// The refusals of a string column and the dictionaries of its data column, before any launch and any allocation
 hy_status string_column_check(const hy_column* column, const hy_string_dictionary* dict, const char* entry_point) {
   HY_TRY(on_this_device(column, entry_point));
   if (column->is_mvcc || (column->data_type != HY_TYPE_STRING && column->n_chunks)) return fail(HY_ERR_INVALID, "%s: not a string column (type %u)", entry_point, column->data_type);
@@ -321,10 +299,18 @@ hy_status string_column_check(const hy_column* column, const hy_string_dictionar
 hy_status string_order_check(const hy_string_dictionary* left, const hy_string_dictionary* right, const char* entry_point) {
   if (left->n_chunks != right->n_chunks) return fail(HY_ERR_INVALID, "%s: the left dictionary has %u chunks, the right one %u", entry_point, left->n_chunks, right->n_chunks);
   if (left->device != right->device) return fail(HY_ERR_INVALID, "%s: the left dictionary lives on device %d, the right one on device %d", entry_point, left->device, right->device);
-  if (left->device != this_thread_device()) return fail(HY_ERR_INVALID, "%s: the dictionaries live on device %d, the calling thread works on device %d", entry_point, left->device, this_thread_device());
+  HY_TRY(dictionary_device_check(left, entry_point));
   for (uint32_t c = 0; c < right->n_chunks; ++c) {
     if (right->chunks[c].n_entries >= (1u << 30)) return fail(HY_ERR_UNSUPPORTED, "%s: chunk %u: a right dictionary of %u entries does not fit int32 ranks (2 * lo)", entry_point, c, right->chunks[c].n_entries);
   }
+  return HY_OK;
+}
+
+hy_status outputs_to_caller(uint32_t mem, const TwinPart* parts, uint32_t n_parts, const uint32_t* d_n_distinct, uint32_t* n_distinct, hipStream_t stream) {
+  for (uint32_t p = 0; mem == HY_MEM_HOST && p < n_parts; ++p)
+    if (parts[p].bytes) HY_HIP(hipMemcpyAsync(parts[p].host, parts[p].device, parts[p].bytes, hipMemcpyDeviceToHost, stream));
+  if (n_distinct) HY_HIP(hipMemcpyAsync(n_distinct, d_n_distinct, 4, hipMemcpyDeviceToHost, stream));
+  if (mem == HY_MEM_HOST || n_distinct) HY_HIP(hipStreamSynchronize(stream));
   return HY_OK;
 }
 
@@ -376,6 +362,24 @@ hy_status string_stand_in(const hy_column* column, const hy_string_dictionary* d
   return HY_OK;
 }
 
+hy_status KeyColumn::alloc(size_t bytes) {
+  HY_HIP(hipMalloc(&d_keys, bytes));
+  return HY_OK;
+}
+
+hy_status KeyColumn::make_stand_in(const hy_column* column, const hy_string_dictionary* dict, uint32_t data_type) {
+  HY_TRY(string_stand_in(column, dict, d_keys, &stand_in, data_type));
+  (stand_in->stand_in ? stand_in->stand_in : stand_in)->owned.push_back(d_keys);
+  return HY_OK;
+}
+
+void KeyColumn::drop() {
+  if (stand_in) (void)hy_column_destroy(stand_in);
+  else if (d_keys) (void)hipFree(d_keys);
+  stand_in = nullptr;
+  d_keys = nullptr;
+}
+
 hy_status string_twins_launch(const StringTwins& twins, hipStream_t stream) {
   const uint32_t lanes = std::max(twins.n_evens, std::max(twins.n_data_chunks, twins.n_chunks));
   if (!lanes) return HY_OK;
@@ -398,15 +402,11 @@ hy_status hy_string_dictionary_ranks(const hy_string_dictionary* left, const hy_
   const uint64_t total = left->entry_offsets[left->n_chunks];
   if (!total) return HY_OK;
   hipStream_t stream = current_stream();
-  if (mem == HY_MEM_DEVICE) return string_order_launch(left, right, ranks, stream);   // (complete in the order of the calling thread's stream)
-  Scratch& sc = scratch();
-  HY_TRY(sc.reserve(4 * total + 4096));
-  int32_t* d_ranks = carve<int32_t>(sc, total);
-  if (!d_ranks) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
+  int32_t* d_ranks = ranks;
+  if (mem == HY_MEM_HOST) HY_TRY(reserve_and_carve([&](Carver& carver) { d_ranks = carver.take<int32_t>(total); }));   // the twin
   HY_TRY(string_order_launch(left, right, d_ranks, stream));
-  HY_HIP(hipMemcpyAsync(ranks, d_ranks, 4 * total, hipMemcpyDeviceToHost, stream));
-  HY_HIP(hipStreamSynchronize(stream));
-  return HY_OK;
+  const TwinPart part{ranks, d_ranks, 4 * total};
+  return outputs_to_caller(mem, &part, 1, nullptr, nullptr, stream);
 }
 
 hy_status hy_string_dictionary_order(const hy_string_dictionary* dict, uint32_t mem, int32_t* ranks, uint32_t* n_distinct) {
@@ -421,16 +421,15 @@ hy_status hy_string_dictionary_order(const hy_string_dictionary* dict, uint32_t 
     return HY_OK;
   }
   hipStream_t stream = current_stream();
-  Scratch& sc = scratch();
-  HY_TRY(sc.reserve(order_scratch_bytes(total) + (mem == HY_MEM_HOST ? align_up(4 * total, 256) : 0)));
-  int32_t* d_ranks = mem == HY_MEM_DEVICE ? ranks : carve<int32_t>(sc, total);
-  if (!d_ranks) return fail(HY_ERR_DEVICE, "scratch arena exhausted");
-  uint32_t* d_n_distinct = nullptr;
-  HY_TRY(column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream));
-  if (mem == HY_MEM_HOST) HY_HIP(hipMemcpyAsync(ranks, d_ranks, 4 * total, hipMemcpyDeviceToHost, stream));
-  if (n_distinct) HY_HIP(hipMemcpyAsync(n_distinct, d_n_distinct, 4, hipMemcpyDeviceToHost, stream));
-  if (mem == HY_MEM_HOST || n_distinct) HY_HIP(hipStreamSynchronize(stream));   // (else: complete in the order of the calling thread's stream)
-  return HY_OK;
+  MergeBlocks merge;
+  int32_t* d_ranks = ranks;
+  HY_TRY(reserve_and_carve([&](Carver& carver) {
+    if (mem == HY_MEM_HOST) d_ranks = carver.take<int32_t>(total);   // the twin
+    merge_layout(carver, total, merge);
+  }));
+  HY_TRY(column_order_launch(dict, merge, d_ranks, stream));
+  const TwinPart part{ranks, d_ranks, 4 * total};
+  return outputs_to_caller(mem, &part, 1, merge.n_distinct, n_distinct, stream);
 }
 
 hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictionary* dict, hy_column** out) {
@@ -443,31 +442,25 @@ hy_status hy_column_string_ranks(const hy_column* column, const hy_string_dictio
 
   // the ranks: a buffer the stand-in owns (16 bytes of slack behind the last rank, like every dictionary of a column)
   hipStream_t stream = current_stream();
-  int32_t* d_ranks = nullptr;
-  HY_HIP(hipMalloc(reinterpret_cast<void**>(&d_ranks), align_up(4 * total + 16, 256)));
+  KeyColumn keys;
+  HY_TRY(keys.alloc(align_up(4 * total + 16, 256)));
   auto give_up = [&](hy_status status) {
     (void)hipStreamSynchronize(stream);
-    (void)hipFree(d_ranks);
+    keys.drop();
     return status;
   };
   if (total) {
-    Scratch& sc = scratch();
-    hy_status status = sc.reserve(order_scratch_bytes(total));
-    uint32_t* d_n_distinct = nullptr;
-    if (status == HY_OK) status = column_order_launch(dict, sc, d_ranks, &d_n_distinct, stream);
+    MergeBlocks merge;
+    hy_status status = reserve_and_carve([&](Carver& carver) { merge_layout(carver, total, merge); });
+    if (status == HY_OK) status = column_order_launch(dict, merge, static_cast<int32_t*>(keys.d_keys), stream);
     if (status != HY_OK) return give_up(status);
   }
-  hy_column* result = nullptr;
-  hy_status status = string_stand_in(column, dict, d_ranks, &result);
+  const hy_status status = keys.make_stand_in(column, dict, HY_TYPE_INT);
   if (status != HY_OK) return give_up(status);
-  (result->stand_in ? result->stand_in : result)->owned.push_back(d_ranks);
   // (the dictionary may die as soon as the call has returned: nothing queued reads it any more)
   const hipError_t err = hipStreamSynchronize(stream);
-  if (err != hipSuccess) {
-    (void)hy_column_destroy(result);
-    return fail(HY_ERR_DEVICE, "%s: ranking failed: %s", name, hipGetErrorString(err));
-  }
-  *out = result;
+  if (err != hipSuccess) return give_up(fail(HY_ERR_DEVICE, "%s: ranking failed: %s", name, hipGetErrorString(err)));
+  *out = keys.stand_in;
   return HY_OK;
 }
 
